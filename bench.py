@@ -15,7 +15,18 @@ N GPUs (torchrun, one process per GPU): every rank runs its own utterances
 (data parallel, no collective in the data path); barrier + synchronize around
 the timed region, time = max over ranks, value = total audio seconds / time.
 
-Also reported:
+A plain run sets up, warms up, times the steps and prints the result line
+(value, ms_per_step, the last step's phases, the per-rank records and, for
+--eos / --queue, what the timed steps themselves recorded).
+
+  --dump-outputs DIR  after the timed steps, the audio the last timed step
+                   returned to its caller: DIR/audio_r<rank>_<i>.npy (float32,
+                   one file per utterance; past 64 MB in all, a fixed seeded
+                   sample of every waveform).  The prompts, the model and the
+                   sampling seed are functions of the arguments alone, so two
+                   builds run with the same arguments compare file for file.
+
+With --full also reported (each takes runs of its own after the timed steps):
   first_packet_ms  generate() entry -> first 1920 samples available: prefill +
                    frame 0 + codec decode of that frame (the codec is causal,
                    so the first frame decodes on its own; measured after the
@@ -29,9 +40,13 @@ Also reported:
                    3 timed runs of 8 frames at the host cores this process may
                    use, plus a 1-thread row (one 2-frame run), the 128-frame
                    workload extrapolated from the median run
+  ref_audio_encode --voice-clone: the reference-audio encoders alone, timed,
+                   with their host port baseline
+  --eos            the same-length fixed-mode time beside the EOS-mode line
+                   (eos_mode.fixed_same_length_*)
+
   --eos            the reference's default mode instead of fixed length
-                   (max_new_tokens 4096, EOS stop), with the same-length
-                   fixed-mode time beside it (eos_mode)
+                   (max_new_tokens 4096, EOS stop)
 """
 import argparse
 import glob
@@ -386,6 +401,27 @@ def shared_queue_next(n, step):
     return nxt
 
 
+DUMP_CAP_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, rank, arrays, cap=DUMP_CAP_BYTES):
+    """--dump-outputs: the last timed step's waveforms as float32 .npy files,
+    audio_r<rank>_<i>.npy (i = the utterance's index in the step's request; an
+    utterance another rank took from a shared queue has no file here).  Past
+    `cap` bytes in all, every waveform is cut to the same fraction of its
+    samples at indices drawn from a fixed seed, sorted."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrs = [(i, np.ascontiguousarray(a, dtype=np.float32)) for i, a in enumerate(arrays) if a is not None]
+    total = sum(a.nbytes for _, a in arrs)
+    frac = min(1.0, cap / total) if total else 1.0
+    for i, a in arrs:
+        if frac < 1.0:
+            keep = int(a.size * frac)
+            a = a[np.sort(np.random.default_rng(i).choice(a.size, size=keep, replace=False))]
+        np.save(os.path.join(out_dir, f"audio_r{rank}_{i:03d}.npy"), a)
+    return len(arrs)
+
+
 def eos_frames(eos):
     """frames per utterance of an EOS / queue line (None: fixed-length)"""
     if "frames_per_utterance" in eos:
@@ -421,6 +457,12 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure what takes runs of its own: first packet, roofline and "
+                         "frame profile, HBM stream bandwidth, the CPU baselines, the voice-clone encoders alone, "
+                         "--eos's same-length fixed-mode time (--no-profile / --no-cpu-baseline narrow it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the audio the last timed step returned as DIR/audio_r<rank>_<i>.npy (float32)")
     ap.add_argument("--preset", default="1.7b")
     ap.add_argument("--frames", type=int, default=128)
     ap.add_argument("--greedy", action="store_true",
@@ -531,36 +573,35 @@ def main():
             raise SystemExit("bench.py --voice-clone: the model dir has no audio encoders (use --vc-codes)")
 
     def one_step():
+        """One step; the waveforms its caller receives stay in last_audio[0]."""
         if wavs is not None:
             rc, aud = m.generate_voice_clone_audio_batch(prompts, wavs, [v[0] for v in vc],
                                                          ["english"] * args.batch)
             if rc != 0:
                 raise RuntimeError("voice-clone (reference audio) generation failed")
-            return sum(len(a) for a in aud)
-        if vc is not None:
+        elif vc is not None:
             rc, aud = m.generate_voice_clone_batch(prompts, [v[0] for v in vc], [v[1] for v in vc],
                                                    [v[2] for v in vc], ["english"] * args.batch)
             if rc != 0:
                 raise RuntimeError("voice-clone generation failed")
-            return sum(len(a) for a in aud)
-        if qprompts is not None:
+        elif qprompts is not None:
             n = len(qprompts)
             rc, aud = m.generate_queue(qprompts, ["aiden"] * n, ["english"] * n, slots=args.batch, next_fn=qnext)
             qstep[0] += 1
             if rc != 0:
                 raise RuntimeError("queue generation failed")
             qstats.append(m.queue_stats())
-            return sum(len(a) for a in aud if a is not None)
-        if args.batch == 1:
+        elif args.batch == 1:
             a = m.generate(prompts[0], "aiden", "english")
             if a is None:
                 raise RuntimeError("generation produced no audio")
-            return len(a)
-        rc, aud = m.generate_batch(prompts, ["aiden"] * args.batch, ["english"] * args.batch)
-        if rc != 0:
-            raise RuntimeError("batch generation failed")
+            aud = [a]
+        else:
+            rc, aud = m.generate_batch(prompts, ["aiden"] * args.batch, ["english"] * args.batch)
+            if rc != 0:
+                raise RuntimeError("batch generation failed")
         last_audio[0] = aud
-        return sum(len(a) for a in aud)
+        return sum(len(a) for a in aud if a is not None)
 
     for _ in range(args.warmup):
         one_step()
@@ -574,6 +615,9 @@ def main():
     torch.cuda.synchronize()
     barrier(ws)
     el = time.perf_counter() - t0
+    if args.dump_outputs:
+        nf = dump_outputs(args.dump_outputs, rank, last_audio[0] or [], DUMP_CAP_BYTES // ws)
+        log(f"[bench] rank {rank}: {nf} waveforms of the last timed step written to {args.dump_outputs}")
     # the last timed step's phases (run_batch's perf_* fields: prefill, decode
     # loop, codec -- for a batch, every slot's codec pass)
     phases = dict(prefill_ms=m.c.perf_prefill_ms, talker_ms=m.c.perf_talker_ms, codec_ms=m.c.perf_codec_ms)
@@ -585,7 +629,9 @@ def main():
         # (batch 1 only: the slots of a batch stop at different frames, so one
         # fixed length would be a different workload; there the line reports
         # the mean frames per utterance alone)
-        if args.batch == 1 and not args.queue:
+        if args.batch == 1 and not args.queue and not args.full:
+            eos = dict(eos_gain=EOS_GAIN, frames_per_utterance=samples // (1920 * args.steps), max_new_tokens=4096)
+        elif args.batch == 1 and not args.queue:
             n_eos = samples // (1920 * args.steps)
             m.set_params(max_tokens=n_eos, fixed=n_eos, seed=42 + rank, **samp)
             one_step()
@@ -603,7 +649,7 @@ def main():
                        max_new_tokens=4096)
             # a lock-step batch runs every slot to the longest one (+ the one
             # frame of the lagged stop poll): useful slot-frames / launched
-            fr = [len(a) // 1920 for a in last_audio[0]] if last_audio[0] else []
+            fr = [len(a) // 1920 for a in last_audio[0]] if last_audio[0] and vc is None else []
             if fr:
                 eos["slot_occupancy"] = round(sum(fr) / (args.batch * (max(fr) + 1)), 4)
                 eos["frames_per_slot_last_step"] = fr
@@ -650,8 +696,9 @@ def main():
     # ---- first packet (BASELINE.json metric, configs[2]): streaming generation,
     # wall time from the call to the first audio chunk (frame 0 decoded by the
     # exact streaming codec and on the host) ----
+    full = args.full
     fp = None
-    if args.batch == 1 and vc is None:
+    if full and args.batch == 1 and vc is None:
         m.generate(prompts[0], "aiden", "english")       # non-streaming breakdown
         prefill_ms, talker_ms, codec_ms = m.c.perf_prefill_ms, m.c.perf_talker_ms, m.c.perf_codec_ms
         # the first streaming request of the process also allocates the
@@ -668,7 +715,7 @@ def main():
                   prefill_ms=prefill_ms, talker_ms=talker_ms, codec_ms=codec_ms)
 
     enc = None
-    if wavs is not None:
+    if full and wavs is not None:
         # the reference-audio encode of one step alone (both encoders, whole batch)
         m.speaker_embed(wavs)
         m.encode_audio(wavs)
@@ -688,7 +735,7 @@ def main():
                    speaker_tflops=round(gf[0] / spk_ms, 2), codes_tflops=round(gf[1] / cod_ms, 2),
                    note="wall time of the encoder call (host waveform in, host codes / x-vectors out), "
                         "dense-contraction GFLOP counted per SURVEY.md 8f N3 shapes")
-    if args.batch == 1 and vc is not None:
+    if full and args.batch == 1 and vc is not None:
         # voice-clone first packet: reference frames through the streaming codec, then frame 0
         for _ in range(2):   # second request, as for the custom-voice line
             m.generate_voice_clone_stream(prompts[0], vc[0][0], vc[0][1], vc[0][2], "english", chunk_frames=8)
@@ -704,15 +751,15 @@ def main():
     # (a voice-clone line reads its own passes: <tag>_vc8_kernel_stats.csv / _vc8_pmc.json)
     pvar = ("" if args.preset == "1.7b" else args.preset.replace(".", "") + "_") + \
         (f"vc{args.batch}_" if vc is not None else f"b{args.batch}_" if args.batch > 1 else "")
-    roof = None if args.no_profile else profile_roofline(m, qtts.lib(), pvar)
-    hbm = None if args.no_profile else hbm_stream_bw(qtts.lib())
+    roof = profile_roofline(m, qtts.lib(), pvar) if full and not args.no_profile else None
+    hbm = hbm_stream_bw(qtts.lib()) if full and not args.no_profile else None
     m.close()
 
     cpu = None
     # the reference c/ CPU leg belongs to the custom-voice line (the c/ reference
     # has no voice clone); a voice-clone line carries the encoders' host port
     # baseline in ref_audio_encode instead
-    if rank == 0 and ws == 1 and not args.no_cpu_baseline and vc is None and not args.eos:
+    if full and rank == 0 and ws == 1 and not args.no_cpu_baseline and vc is None and not args.eos:
         thr = args.cpu_threads or cpu_threads_default()
         cpu = cpu_baseline(md, prompts[0], thr, frames=args.cpu_frames, runs=args.cpu_runs, target_frames=args.frames,
                            greedy=args.greedy)

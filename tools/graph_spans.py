@@ -4,7 +4,7 @@
 tracer-widened gap, profiles/r05f_mb_launch_rocprof.txt, so the line also
 carries the span the stamps measure).
 
-Runs `bench.py --steps 1 --warmup 0` on the stamp build (lib_s: `make -C
+Runs `bench.py --full --steps 1 --warmup 0` on the stamp build (lib_s: `make -C
 qwen3-tts-c_amd VARIANT=_s EXTRA=-DQTTS_STAMPS`) twice -- QTTS_HIP_GM_DBG=99
 (sub-talker pass 5, layer 2: q|k|v GEMV, attention + O, gate|up, down) and
 QTTS_HIP_GM_DBG=5 (talker layer 5: q|k|v, O with the merge, gate|up, down) --
@@ -34,7 +34,7 @@ PAT = re.compile(r"\[gm_dbg\] (.{8}) launch at\s+([\d.]+) us after the first, la
 
 def run(layer):
     env = dict(os.environ, QTTS_LIB=LIB_S, QTTS_HIP_GM_DBG=layer)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "0",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "1", "--warmup", "0",
                         "--no-profile", "--no-cpu-baseline", "--frames", "16"], env=env, capture_output=True,
                        text=True, timeout=600)
     if r.returncode != 0:

@@ -34,11 +34,13 @@ waveform stays well inside [-1, 1].
 Usage:  python tools/synth_model.py --preset tiny --out /tmp/qtts_tiny
 """
 import argparse
+import collections
 import hashlib
 import json
 import os
 import struct
 import sys
+from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
@@ -500,16 +502,36 @@ def write_model(out, preset="tiny", seed=0, overrides=None, quiet=False):
     with open(os.path.join(out, "speech_tokenizer", "config.json"), "w") as f:
         json.dump(ccfg, f, indent=1)
 
-    for path, specs in files:
-        codec = "speech_tokenizer" in path
-        sp = [(n, "F32" if (codec or k in ("usage", "one")) else "BF16", s) for n, s, k, g in specs]
-        w = StWriter(path + ".tmp", sp)
-        for n, s, k, g in specs:
-            if not quiet and np.prod(s) > (1 << 24):
-                print(f"  gen {n} {s}", file=sys.stderr)
-            w.write(n, make_tensor(seed, n, s, k, g, p))
-        w.close()
-        os.replace(path + ".tmp", path)
+    # every tensor has its own stream, so the tensors are generated on a few
+    # threads (numpy's generator and the large array ops release the GIL) and
+    # written in spec order: the files are byte-identical to a serial write
+    def gen(n, s, k, g, dt):
+        t = make_tensor(seed, n, s, k, g, p)
+        return _f32_to_bf16(t) if dt == "BF16" else t
+
+    nthr = max(1, min(16, len(os.sched_getaffinity(0))))
+    with ThreadPoolExecutor(nthr) as pool:
+        for path, specs in files:
+            codec = "speech_tokenizer" in path
+            sp = [(n, "F32" if (codec or k in ("usage", "one")) else "BF16", s) for n, s, k, g in specs]
+            w = StWriter(path + ".tmp", sp)
+            pending = collections.deque()
+            todo = iter(zip(specs, sp))
+            while True:
+                while len(pending) < 2 * nthr:   # bounded look-ahead: memory stays a few tensors deep
+                    nx = next(todo, None)
+                    if nx is None:
+                        break
+                    (n, s, k, g), (_, dt, _) = nx
+                    if not quiet and np.prod(s) > (1 << 24):
+                        print(f"  gen {n} {s}", file=sys.stderr)
+                    pending.append((n, pool.submit(gen, n, s, k, g, dt)))
+                if not pending:
+                    break
+                n, fut = pending.popleft()
+                w.write(n, fut.result())
+            w.close()
+            os.replace(path + ".tmp", path)
     return out
 
 
