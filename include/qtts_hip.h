@@ -90,6 +90,27 @@ int qtts_dev_finalize(qtts_dev_t *dev);
 /* Device bytes currently allocated for weights / state. */
 size_t qtts_dev_bytes(const qtts_dev_t *dev, int which /*0 weights, 1 state*/);
 
+/* Element type of the talker KV cache: 0 fp32 (default, or $QTTS_HIP_KV at
+ * creation), 1 bf16 -- K (after k-norm and RoPE) and V rows rounded to nearest
+ * even as they are stored, a token's own k / v entering its attention as the
+ * rounded values, scores / softmax / P.V in fp32 as before.  The sub-talker,
+ * codec and encoder caches stay fp32.  set takes effect at the next
+ * qtts_dev_begin (new state, new frame graphs) and returns -1 on a bad value;
+ * the getter returns the value the next begin will use. */
+int qtts_dev_set_kv_dtype(qtts_dev_t *dev, int dtype);
+int qtts_dev_kv_dtype(const qtts_dev_t *dev);
+/* Diagnostics: talker cache rows [pos0, pos0 + n) of layer `layer`, slot b,
+ * to the host as fp32 [n][KV*HD] each (bf16 widened exactly; k_host or v_host
+ * may be NULL).  Waits for the context stream.  -1 out of range. */
+int qtts_dev_get_kv(qtts_dev_t *dev, int layer, int b, int pos0, int n, float *k_host, float *v_host);
+/* Diagnostics: what the last talker layer's decode attention of the most
+ * recent talker pass read and wrote, for every allocated slot: its q|k|v rows
+ * [slots][(NH + 2 KV) HD] and its output [slots][NH HD] (either may be NULL).
+ * Waits for the context stream.  The output exists only where the attention
+ * merges its own splits (a batch of >= 2 rows, or QTTS_HIP_ATTN_DEFER=0);
+ * -1 when asked for it after a pass that deferred the merge. */
+int qtts_dev_get_attn(qtts_dev_t *dev, float *qkv_host, float *att_host);
+
 /* ---- generation (batch of nb utterances in lock-step frames) ---- */
 /* Allocates state for nb slots, max_frames frames (KV capacity = max_prefill
  * + max_frames), resets counters / RNG, (re)captures the frame graphs. */
@@ -259,6 +280,21 @@ int qtts_hip_transposed_conv1d(float *out_dev, const float *in_dev, const float 
 /* kernel_snake_beta (c/qwen_tts_kernels.c:251), alpha/inv_beta pre-processed */
 int qtts_hip_snake_beta(float *out_dev, const float *x_dev, const float *alpha_dev, const float *inv_beta_dev,
                         int channels, int length, void *stream);
+/* The talker's decode attention (c/qwen_tts_talker.c:150-196 + kernel_causal_attention)
+ * as a talker layer launches it: per row r, q / k RMSNorm + RoPE at pos[r], k / v
+ * stored at row pos[r] of the caches [rows][S][KV*HD] (kv_dtype 0: fp32
+ * elements, 1: bf16 bit patterns, uint16), attention over keys [0, pos[r]],
+ * the kernel's own split merge.  qkv_dev [rows][(NH + 2 KV) HD], out_dev
+ * [rows][NH HD], rope tables [>= max pos + 1][HD], pos_dev[r] in [0, S).  The
+ * split scratch is allocated inside; returns after the launch has finished.
+ * A parity entry, not a timing one: every call allocates and frees its
+ * scratch and synchronises the stream twice, and it always uses the default
+ * keys per split (QTTS_HIP_ATTN_LPK is a model-level switch). */
+int qtts_hip_attn_decode(float *out_dev, const float *qkv_dev, void *kc_dev, void *vc_dev,
+                         const float *qn_w_dev, const float *kn_w_dev,
+                         const float *rope_cos_dev, const float *rope_sin_dev,
+                         const int *pos_dev, int NH, int KV, int HD, int S, int rows,
+                         float eps, int kv_dtype, void *stream);
 /* glibc-exact expf replica used by the sampler (for the libm cross-check test) */
 int qtts_hip_expf_glibc(float *out_dev, const float *in_dev, int n, void *stream);
 int qtts_hip_sync(void);

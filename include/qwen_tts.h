@@ -220,6 +220,18 @@ int qwen_tts_talker_hidden(qwen_tts_ctx_t *ctx, float *out);
  * is what qwen_tts_load uses).  No process-global state: one ctx per device
  * and host thread, each owning its device model, streams and graphs. */
 qwen_tts_ctx_t *qwen_tts_load_on(const char *model_dir, int device);
+/* Element type of the talker KV cache.  QWEN_TTS_KV_F32 (the default) keeps
+ * the codes bit-exact against the reference.  QWEN_TTS_KV_BF16 stores every K
+ * and V row of the talker rounded to bf16 (nearest even): half the cache bytes
+ * (114,688 instead of 229,376 B per position and slot on the 1.7B model), the
+ * attention arithmetic itself stays fp32, and the codes are no longer
+ * bit-exact against the reference (the Python reference runs its cache in
+ * bf16 too).  Takes effect with the next generation call; -1 on a bad value.
+ * $QTTS_HIP_KV=bf16|fp32 sets the default of every ctx loaded after it. */
+#define QWEN_TTS_KV_F32  0
+#define QWEN_TTS_KV_BF16 1
+int qwen_tts_set_kv_cache_dtype(qwen_tts_ctx_t *ctx, int dtype);
+int qwen_tts_kv_cache_dtype(qwen_tts_ctx_t *ctx);
 /* nb utterances in lock-step frames on this ctx's GPU (weights read once per
  * frame for all of them).  out_audio[i] malloc'd (caller frees), out_samples[i]
  * set; returns 0 when every utterance produced audio. */

@@ -12,6 +12,12 @@
 // Cached (mode 1, prefill): q was normalised/rotated in place and all k/v are
 // already in the cache (qtts_qk_prep), positions come per row.
 //
+// The talker's cache may hold bf16 elements instead (AttnArgs::kv_dtype 1, an
+// opt-in): k_attn, k_qk_prep, k_qk_prep_w and k_attn_dec are templates over
+// the cache element type; the fp32 instantiations are the kernels as they
+// were.  Rows are rounded to nearest even as they are stored, and a token's
+// own k / v enter its attention as the rounded values.
+//
 // Scores: HD/8 lanes per key (two float4 loads each) -> 256/(HD/8) keys per
 // pass; P.V: HD/4 lanes per row -> 256/(HD/4) rows per pass, partial sums
 // combined through LDS in a fixed order.
@@ -19,6 +25,7 @@
 #include "qtts_common.h"
 #include "qtts_kernels.h"
 #include "qtts_l2pf.h"
+#include <type_traits>
 
 namespace {
 
@@ -28,7 +35,39 @@ __device__ __forceinline__ void rope_lds(const float *x, float *y, const float *
     else y[i] = x[i] * cs[i] + x[i - half] * sn[i];
 }
 
+// bf16 cache elements (AttnArgs::kv_dtype 1): round to nearest even on the
+// way in (the fp32 value the fp32 cache would hold), a 16-bit shift on the
+// way out (exact)
+__device__ __forceinline__ bf16_t f2bf(float f) {
+    const uint32_t u = __float_as_uint(f);
+    return (bf16_t)((u + (((u >> 16) & 1u) + 0x7FFFu)) >> 16);
+}
+__device__ __forceinline__ float bf_round(float f) { return bf2f((uint32_t)f2bf(f)); }
+// 4 packed bf16 (two dwords) -> float4
+typedef uint32_t v2u __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ float4 bf4_widen(uint32_t a, uint32_t b) {
+    return make_float4(__uint_as_float(a << 16), __uint_as_float(a & 0xFFFF0000u), __uint_as_float(b << 16),
+                       __uint_as_float(b & 0xFFFF0000u));
+}
+// 4 consecutive cache elements (a 16-byte fp32 or 8-byte bf16 load) as fp32
+template <typename CT>
+__device__ __forceinline__ float4 cache_ld4(const CT *p) {
+    if constexpr (sizeof(CT) == 4) return *reinterpret_cast<const float4 *>(p);
+    else {
+        const v2u u = *reinterpret_cast<const v2u *>(p);
+        return bf4_widen(u.x, u.y);
+    }
+}
+// (base and index apart: the fp32 form is the plain indexed store, same index arithmetic as before)
+template <typename CT, typename I>
+__device__ __forceinline__ void cache_st(CT *p, I i, float v) {
+    if constexpr (sizeof(CT) == 4) p[i] = v;
+    else p[i] = f2bf(v);
+}
+
+template <typename CT>
 __global__ __launch_bounds__(256) void k_attn(AttnArgs a) {
+    constexpr bool B16 = sizeof(CT) == 2;
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int tid = threadIdx.x;
     const int h = blockIdx.x, r = blockIdx.y;
@@ -45,8 +84,9 @@ __global__ __launch_bounds__(256) void k_attn(AttnArgs a) {
     float *part = red + 8;       // [8][HD]
     float *sc = part + 8 * 128;  // [n]
     const float *row = a.qkv + (size_t)r * a.ld_qkv;
-    const float *Kc = a.kc + (size_t)b * a.S * KVD + kvh * HD;
-    const float *Vc = a.vc + (size_t)b * a.S * KVD + kvh * HD;
+    CT *kc = reinterpret_cast<CT *>(a.kc), *vc = reinterpret_cast<CT *>(a.vc);
+    const CT *Kc = kc + (size_t)b * a.S * KVD + kvh * HD;
+    const CT *Vc = vc + (size_t)b * a.S * KVD + kvh * HD;
 
     if (a.mode == 0) {
         float qv = 0.f, kv = 0.f;
@@ -54,6 +94,7 @@ __global__ __launch_bounds__(256) void k_attn(AttnArgs a) {
             qv = row[h * HD + tid];
             kv = row[a.NH * HD + kvh * HD + tid];
             vv[tid] = row[(a.NH + a.KV) * HD + kvh * HD + tid];
+            if constexpr (B16) vv[tid] = bf_round(vv[tid]);   // (the token's own v as the cache will hold it)
         }
         const float ssq = block_sum256(qv * qv, red);
         const float ssk = block_sum256(kv * kv, red + 4);
@@ -66,11 +107,17 @@ __global__ __launch_bounds__(256) void k_attn(AttnArgs a) {
             const float *cs = a.rope_cos + (size_t)p * HD, *sn = a.rope_sin + (size_t)p * HD;
             rope_lds(tmp, qr, cs, sn, HD, tid);
             rope_lds(tmp + 128, kr, cs, sn, HD, tid);
+            if constexpr (B16) kr[tid] = bf_round(kr[tid]);   // (each thread its own element)
         }
         __syncthreads();
         if (h % gph == 0 && tid < HD && !(a.skip && a.skip[b])) {
-            a.kc[((size_t)b * a.S + p) * KVD + kvh * HD + tid] = kr[tid];
-            a.vc[((size_t)b * a.S + p) * KVD + kvh * HD + tid] = vv[tid];
+            if constexpr (!B16) {
+                a.kc[((size_t)b * a.S + p) * KVD + kvh * HD + tid] = kr[tid];
+                a.vc[((size_t)b * a.S + p) * KVD + kvh * HD + tid] = vv[tid];
+            } else {   // (exact: both were rounded above)
+                kc[((size_t)b * a.S + p) * KVD + kvh * HD + tid] = f2bf(kr[tid]);
+                vc[((size_t)b * a.S + p) * KVD + kvh * HD + tid] = f2bf(vv[tid]);
+            }
         }
     } else {
         if (tid < HD) qr[tid] = row[h * HD + tid];
@@ -88,9 +135,19 @@ __global__ __launch_bounds__(256) void k_attn(AttnArgs a) {
         const int t = t0 + gi;
         float s = 0.f;
         if (t < n) {
-            const float *kp = (a.mode == 0 && t == p) ? kr + 8 * li : Kc + (size_t)t * KVD + 8 * li;
-            const float4 k0 = *reinterpret_cast<const float4 *>(kp);
-            const float4 k1 = *reinterpret_cast<const float4 *>(kp + 4);
+            float4 k0, k1;
+            if constexpr (!B16) {
+                const float *kp = (a.mode == 0 && t == p) ? kr + 8 * li : Kc + (size_t)t * KVD + 8 * li;
+                k0 = *reinterpret_cast<const float4 *>(kp);
+                k1 = *reinterpret_cast<const float4 *>(kp + 4);
+            } else if (a.mode == 0 && t == p) {
+                k0 = *reinterpret_cast<const float4 *>(kr + 8 * li);
+                k1 = *reinterpret_cast<const float4 *>(kr + 8 * li + 4);
+            } else {   // 8 bf16 elements, one 16-byte load
+                const v4u u = *reinterpret_cast<const v4u *>(Kc + (size_t)t * KVD + 8 * li);
+                k0 = bf4_widen(u.x, u.y);
+                k1 = bf4_widen(u.z, u.w);
+            }
             s = q0.x * k0.x + q0.y * k0.y + q0.z * k0.z + q0.w * k0.w + q1.x * k1.x + q1.y * k1.y + q1.z * k1.z +
                 q1.w * k1.w;
         }
@@ -118,8 +175,14 @@ __global__ __launch_bounds__(256) void k_attn(AttnArgs a) {
     const int g2 = tid / lpr, l2 = tid - g2 * lpr;
     float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
     for (int t = ts + g2; t < n; t += rpp) {
-        const float *vp = (a.mode == 0 && t == p) ? vv + 4 * l2 : Vc + (size_t)t * KVD + 4 * l2;
-        const float4 v4 = *reinterpret_cast<const float4 *>(vp);
+        float4 v4;
+        if constexpr (!B16) {
+            const float *vp = (a.mode == 0 && t == p) ? vv + 4 * l2 : Vc + (size_t)t * KVD + 4 * l2;
+            v4 = *reinterpret_cast<const float4 *>(vp);
+        } else {
+            v4 = (a.mode == 0 && t == p) ? *reinterpret_cast<const float4 *>(vv + 4 * l2)
+                                         : cache_ld4(Vc + (size_t)t * KVD + 4 * l2);
+        }
         const float w = sc[t];
         acc.x += w * v4.x; acc.y += w * v4.y; acc.z += w * v4.z; acc.w += w * v4.w;
     }
@@ -141,7 +204,9 @@ __global__ __launch_bounds__(256) void k_attn(AttnArgs a) {
 }
 
 // prefill: per row, normalise + rotate q heads in place, k heads -> cache, v -> cache
+template <typename CT>
 __global__ __launch_bounds__(256) void k_qk_prep(AttnArgs a) {
+    CT *kc = reinterpret_cast<CT *>(a.kc), *vc = reinterpret_cast<CT *>(a.vc);
     __shared__ float buf[4096 + 64];
     const int r = blockIdx.x, tid = threadIdx.x;
     const int HD = a.HD, NH = a.NH, KV = a.KV, KVD = KV * HD;
@@ -171,9 +236,9 @@ __global__ __launch_bounds__(256) void k_qk_prep(AttnArgs a) {
         if (e < half) y = xh[e] * cs[e] - xh[e + half] * sn[e];
         else y = xh[e] * cs[e] + xh[e - half] * sn[e];
         if (hh < NH) row[i] = y;
-        else a.kc[((size_t)b * a.S + p) * KVD + (hh - NH) * HD + e] = y;
+        else cache_st(kc, ((size_t)b * a.S + p) * KVD + (hh - NH) * HD + e, y);
     }
-    for (int i = tid; i < KVD; i += 256) a.vc[((size_t)b * a.S + p) * KVD + i] = row[nh * HD + i];
+    for (int i = tid; i < KVD; i += 256) cache_st(vc, ((size_t)b * a.S + p) * KVD + i, row[nh * HD + i]);
     (void)red;
 }
 
@@ -181,6 +246,7 @@ __global__ __launch_bounds__(256) void k_qk_prep(AttnArgs a) {
 // place, k -> cache), v heads -> cache; no LDS, no barrier.  grid (rows,
 // ceil((NH + 2 KV) / 4)), 256 threads.  HD = 128: a lane holds e and e + 64
 // (its own rotate-half partner); HD <= 64: one element, partner one xor away.
+template <typename CT>
 __global__ __launch_bounds__(256) void k_qk_prep_w(AttnArgs a) {
     const int r = blockIdx.x, w = threadIdx.x >> 6, l = threadIdx.x & 63;
     const int HD = a.HD, NH = a.NH, KV = a.KV, KVD = KV * HD;
@@ -188,10 +254,14 @@ __global__ __launch_bounds__(256) void k_qk_prep_w(AttnArgs a) {
     if (hh >= NH + 2 * KV) return;
     const int b = a.row_b[r], p = a.pos[r];
     float *row = const_cast<float *>(a.qkv) + (size_t)r * a.ld_qkv;
-    float *kdst = a.kc + ((size_t)b * a.S + p) * KVD, *vdst = a.vc + ((size_t)b * a.S + p) * KVD;
+    CT *kdst = reinterpret_cast<CT *>(a.kc) + ((size_t)b * a.S + p) * KVD;
+    CT *vdst = reinterpret_cast<CT *>(a.vc) + ((size_t)b * a.S + p) * KVD;
     if (hh >= NH + KV) {   // v head: copy to the cache
         const int vh = hh - NH - KV;
-        for (int i = l; i < HD; i += 64) vdst[vh * HD + i] = row[(NH + KV) * HD + vh * HD + i];
+        for (int i = l; i < HD; i += 64) {
+            if constexpr (sizeof(CT) == 4) vdst[vh * HD + i] = row[(NH + KV) * HD + vh * HD + i];
+            else vdst[vh * HD + i] = f2bf(row[(NH + KV) * HD + vh * HD + i]);
+        }
         return;
     }
     const float *src = row + hh * HD;
@@ -212,9 +282,19 @@ __global__ __launch_bounds__(256) void k_qk_prep_w(AttnArgs a) {
         const float pn = __shfl_xor(n0, half, 64);
         y0 = l < HD ? (l < half ? n0 * cs[l] - pn * sn[l] : n0 * cs[l] + pn * sn[l]) : 0.f;
     }
-    float *dst = hh < NH ? row + hh * HD : kdst + (hh - NH) * HD;
-    if (HD == 128) { dst[l] = y0; dst[l + 64] = y1; }
-    else if (l < HD) dst[l] = y0;
+    if constexpr (sizeof(CT) == 4) {
+        float *dst = hh < NH ? row + hh * HD : kdst + (hh - NH) * HD;
+        if (HD == 128) { dst[l] = y0; dst[l + 64] = y1; }
+        else if (l < HD) dst[l] = y0;
+    } else if (hh < NH) {
+        float *dst = row + hh * HD;
+        if (HD == 128) { dst[l] = y0; dst[l + 64] = y1; }
+        else if (l < HD) dst[l] = y0;
+    } else {
+        CT *dst = kdst + (hh - NH) * HD;
+        if (HD == 128) { dst[l] = f2bf(y0); dst[l + 64] = f2bf(y1); }
+        else if (l < HD) dst[l] = f2bf(y0);
+    }
 }
 
 // ---------------------------------------------------------------------------
@@ -237,9 +317,18 @@ __global__ __launch_bounds__(256) void k_qk_prep_w(AttnArgs a) {
 // capacity); splits past the live length exit at once.
 // (qkv / pos / kc / vc lead the arguments: preloaded into SGPRs, Makefile --
 // the position load and the cache loads behind it need no kernarg round trip)
-template <int HD, int GPH, int LPK>
-__global__ __launch_bounds__(256) void k_attn_dec(const float *qkv_, const int *pos_, float *kc_, float *vc_,
+// bf16 cache (CT = bf16_t): the same lanes per key, keys per split, score and
+// softmax arithmetic and P.V summation order.  A lane's K slice is DPL / 8
+// 16-byte loads of 8 elements, widened in registers.  P.V: HD/8 lanes x KG key
+// groups x the two query heads (a thread accumulates 8 dims of ONE head, the
+// same FMAs per thread as fp32's 4 dims of both), V rows as 16-byte loads.
+// The token's own k and v are rounded once, stored, and enter the scores and
+// P.V as the rounded values -- what k_attn mode 1 reads back from the cache.
+template <int HD, int GPH, int LPK, typename CT>
+__global__ __launch_bounds__(256) void k_attn_dec(const float *qkv_, const int *pos_, CT *kc_, CT *vc_,
                                                   AttnArgs a) {
+    constexpr bool B16 = sizeof(CT) == 2;
+    static_assert(!B16 || GPH == 2, "bf16 P.V: one query head per half workgroup");
     // LPK lanes per key
     constexpr int DPL = HD / LPK;                  // dims per lane
     constexpr int CH = 256 / LPK;                  // keys per workgroup
@@ -265,8 +354,8 @@ __global__ __launch_bounds__(256) void k_attn_dec(const float *qkv_, const int *
     const int t1 = min(n, t0 + CH);
     const bool owner = (split == nact - 1);        // holds the current token
     const float *row = qkv_ + (size_t)r * a.ld_qkv;
-    const float *Kc = kc_ + (size_t)r * a.S * KVD + kvh * HD;
-    const float *Vc = vc_ + (size_t)r * a.S * KVD + kvh * HD;
+    const CT *Kc = kc_ + (size_t)r * a.S * KVD + kvh * HD;
+    const CT *Vc = vc_ + (size_t)r * a.S * KVD + kvh * HD;
 
     // ---- the token's own inputs first (q / k head values, norm weights, RoPE
     // rows, v): issued behind the cache loads they would wait for all of them
@@ -311,20 +400,28 @@ __global__ __launch_bounds__(256) void k_attn_dec(const float *qkv_, const int *
     const int tk = t0 + kl;
     // (rows past the split or the current token's own read a valid row and
     // are never used: the scores skip t >= t1 and take t == p from LDS)
-    float4 kreg[DPL / 4];
+    // (fp32: float4 = 4 elements per load; bf16: v4u = 8 elements per load)
+    using LD = typename std::conditional<B16, v4u, float4>::type;
+    constexpr int EPL = B16 ? 8 : 4;               // elements per 16-byte load
+    static_assert(DPL % EPL == 0 && HD % EPL == 0, "whole 16-byte loads");
+    LD kreg[DPL / EPL];
     {
-        const float4 *kp = reinterpret_cast<const float4 *>(Kc + (size_t)(tk < t1 ? tk : t0) * KVD + ksub * DPL);
+        const LD *kp = reinterpret_cast<const LD *>(Kc + (size_t)(tk < t1 ? tk : t0) * KVD + ksub * DPL);
 #pragma unroll
-        for (int j = 0; j < DPL / 4; ++j) kreg[j] = kp[j];
+        for (int j = 0; j < DPL / EPL; ++j) kreg[j] = kp[j];
     }
-    const int d4 = tid % D4, kg = tid / D4;
+    // P.V lanes: fp32 (d4, kg) over 256 threads; bf16 (d4 = 8-dim slice, kg, vh
+    // = the query head this thread accumulates) -- both halves load the rows
+    constexpr int DV = HD / EPL;
+    static_assert(!B16 || DV * KG * 2 == 256, "bf16 P.V thread layout");
+    const int d4 = tid % DV, kg = B16 ? (tid / DV) % KG : tid / D4, vh = B16 ? tid / (DV * KG) : 0;
     constexpr int NV = (CH + KG - 1) / KG;
-    float4 vreg[NV];
+    LD vreg[NV];
 #pragma unroll
     for (int j = 0; j < NV; ++j) {
         const int t = t0 + kg + j * KG;
         const bool ok = kg + j * KG < CH && t < t1;   // (t == p: read, then replaced from LDS)
-        vreg[j] = reinterpret_cast<const float4 *>(Vc + (size_t)(ok ? t : t0) * KVD)[d4];
+        vreg[j] = reinterpret_cast<const LD *>(Vc + (size_t)(ok ? t : t0) * KVD)[d4];
     }
 
     // ---- prologue: q heads (waves 0..GPH-1), k head (wave GPH), v ----
@@ -336,8 +433,14 @@ __global__ __launch_bounds__(256) void k_attn_dec(const float *qkv_, const int *
         const float iv = rms_inv(ss, HD, a.eps);
         if constexpr (RREG) {   // normalise and rotate in registers (T.c:150-189)
             const float n0 = hv[0] * iv * hw[0], n1 = hv[1] * iv * hw[1];
-            qk[hh0 * HD + lane] = n0 * rc[0] - n1 * rs[0];
-            qk[hh0 * HD + lane + 64] = n1 * rc[1] + n0 * rs[1];
+            if constexpr (!B16) {
+                qk[hh0 * HD + lane] = n0 * rc[0] - n1 * rs[0];
+                qk[hh0 * HD + lane + 64] = n1 * rc[1] + n0 * rs[1];
+            } else {   // the k head as the cache will hold it
+                const float y0 = n0 * rc[0] - n1 * rs[0], y1 = n1 * rc[1] + n0 * rs[1];
+                qk[hh0 * HD + lane] = hh0 == GPH ? bf_round(y0) : y0;
+                qk[hh0 * HD + lane + 64] = hh0 == GPH ? bf_round(y1) : y1;
+            }
         } else {
 #pragma unroll
             for (int j = 0; j < HJ; ++j) {
@@ -346,7 +449,7 @@ __global__ __launch_bounds__(256) void k_attn_dec(const float *qkv_, const int *
             }
         }
     }
-    if (owner && tid < HD) vv[tid] = vtok;
+    if (owner && tid < HD) vv[tid] = B16 ? bf_round(vtok) : vtok;
     __syncthreads();
     if constexpr (!RREG) {
 #pragma unroll
@@ -356,13 +459,20 @@ __global__ __launch_bounds__(256) void k_attn_dec(const float *qkv_, const int *
                 const int e = i % HD, hb = i - e;
                 constexpr int half = HD / 2;
                 qk[i] = e < half ? xn[i] * rc[j] - xn[hb + e + half] * rs[j] : xn[i] * rc[j] + xn[hb + e - half] * rs[j];
+                if constexpr (B16)
+                    if (i >= GPH * HD) qk[i] = bf_round(qk[i]);   // the k head as the cache will hold it
             }
         }
         __syncthreads();
     }
     if (owner && tid < HD && !(a.skip && a.skip[r])) {
-        kc_[((size_t)r * a.S + p) * KVD + kvh * HD + tid] = qk[GPH * HD + tid];
-        vc_[((size_t)r * a.S + p) * KVD + kvh * HD + tid] = vv[tid];
+        if constexpr (!B16) {
+            kc_[((size_t)r * a.S + p) * KVD + kvh * HD + tid] = qk[GPH * HD + tid];
+            vc_[((size_t)r * a.S + p) * KVD + kvh * HD + tid] = vv[tid];
+        } else {   // (exact: both were rounded above)
+            kc_[((size_t)r * a.S + p) * KVD + kvh * HD + tid] = f2bf(qk[GPH * HD + tid]);
+            vc_[((size_t)r * a.S + p) * KVD + kvh * HD + tid] = f2bf(vv[tid]);
+        }
     }
 
     // ---- scores ----
@@ -376,8 +486,15 @@ __global__ __launch_bounds__(256) void k_attn_dec(const float *qkv_, const int *
         if (t < t1) {
             float4 kv[DPL / 4];
 #pragma unroll
-            for (int j = 0; j < DPL / 4; ++j)
-                kv[j] = (t == p) ? reinterpret_cast<const float4 *>(qk + GPH * HD + sub * DPL)[j] : kreg[j];
+            for (int j = 0; j < DPL / 4; ++j) {
+                if constexpr (!B16) {
+                    kv[j] = (t == p) ? reinterpret_cast<const float4 *>(qk + GPH * HD + sub * DPL)[j] : kreg[j];
+                } else {
+                    const v4u u = kreg[j >> 1];
+                    kv[j] = bf4_widen((j & 1) ? u.z : u.x, (j & 1) ? u.w : u.y);
+                    if (t == p) kv[j] = reinterpret_cast<const float4 *>(qk + GPH * HD + sub * DPL)[j];
+                }
+            }
 #pragma unroll
             for (int g = 0; g < GPH; ++g) {
                 const float4 *q4 = reinterpret_cast<const float4 *>(qk + g * HD + sub * DPL);
@@ -413,7 +530,29 @@ __global__ __launch_bounds__(256) void k_attn_dec(const float *qkv_, const int *
     }
     __syncthreads();
     // ---- P.V ----
-    {
+    if constexpr (B16) {
+        // head vh, dims [8 d4, 8 d4 + 8): per output the same products in the
+        // same order as the fp32 form (keys kg, kg + KG, ... then the KG groups)
+        float4 a0 = make_float4(0.f, 0.f, 0.f, 0.f), a1 = a0;
+#pragma unroll
+        for (int j = 0; j < NV; ++j) {
+            const int k = kg + j * KG;
+            const int t = t0 + k;
+            if (k < CH && t < t1) {
+                const v4u u = vreg[j];
+                float4 v0 = bf4_widen(u.x, u.y), v1 = bf4_widen(u.z, u.w);
+                if (t == p) {
+                    v0 = reinterpret_cast<const float4 *>(vv)[2 * d4];
+                    v1 = reinterpret_cast<const float4 *>(vv)[2 * d4 + 1];
+                }
+                const float pw = sc[vh][k];
+                a0.x += pw * v0.x; a0.y += pw * v0.y; a0.z += pw * v0.z; a0.w += pw * v0.w;
+                a1.x += pw * v1.x; a1.y += pw * v1.y; a1.z += pw * v1.z; a1.w += pw * v1.w;
+            }
+        }
+        reinterpret_cast<float4 *>(red + kg * NO + vh * HD)[2 * d4] = a0;
+        reinterpret_cast<float4 *>(red + kg * NO + vh * HD)[2 * d4 + 1] = a1;
+    } else {
         float4 acc[GPH];
 #pragma unroll
         for (int g = 0; g < GPH; ++g) acc[g] = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -634,7 +773,7 @@ __global__ __launch_bounds__(256) void k_attn_o(const float *rsrc, const int *id
 bool qtts_attn_o_covers(const AttnArgs &a, const bf16_t *Wo) {
     const bool hd_ok = a.HD == 128 || a.HD == 64 || a.HD == 32 || a.HD == 16;
     return a.mode == 0 && a.win == 0 && a.KV > 0 && a.NH == 2 * a.KV && hd_ok && a.S <= 16 && a.nrows >= 1 &&
-           ((uintptr_t)Wo & 15) == 0 && (a.NH * a.HD) % 8 == 0;
+           a.kv_dtype == 0 && ((uintptr_t)Wo & 15) == 0 && (a.NH * a.HD) % 8 == 0;
 }
 
 int qtts_attn_o(const AttnArgs &a, const bf16_t *Wo, int R, float *part, hipStream_t st) {
@@ -685,6 +824,18 @@ int qtts_attention(const AttnArgs &a, hipStream_t st) {
     }
     const int gph = a.NH / a.KV;
     const bool hd_ok = a.HD == 128 || a.HD == 64 || a.HD == 32 || a.HD == 16;
+    if (a.kv_dtype != 0 && a.kv_dtype != 1) {
+        fprintf(stderr, "qtts_attention: unknown cache element type %d\n", a.kv_dtype);
+        return -1;
+    }
+    // bf16 caches: the split decode kernel and the generic kernel only (the
+    // talker); the short / table paths (the sub-talker's) and the sliding
+    // window (the codec's, no bf16 caller and no test of it) are fp32
+    if (a.kv_dtype == 1 &&
+        ((a.mode == 0 && a.win == 0 && gph == 2 && hd_ok && a.S <= 16) || a.qkv_tab || a.xc_dst || a.win != 0)) {
+        fprintf(stderr, "qtts_attention: bf16 cache not covered on the short / table / window paths\n");
+        return -1;
+    }
     if (a.xc_dst && (!(a.mode == 0 && a.win == 0 && gph == 2 && hd_ok && a.S <= 16) || !a.qkv_tab ||
                      (!a.xc_tab && !a.xc_tab16) || a.xc_n % 4 || ((uintptr_t)a.xc_dst & 15))) {
         fprintf(stderr, "qtts_attention: residual copy (xc_dst) only on the short table path\n");
@@ -714,9 +865,15 @@ int qtts_attention(const AttnArgs &a, hipStream_t st) {
         const dim3 grid(a.KV, nsplit, a.nrows);
         const int lpk = attn_lpk(a.HD, a.defer, a.lpk);
 #define QTTS_AD(H, L)                                                                                      \
-        if (a.HD == H && lpk == L) {                                                                       \
-            hipLaunchKernelGGL((k_attn_dec<H, 2, L>), grid, dim3(256), 0, st, a.qkv, a.pos, a.kc, a.vc, a); \
+        if (a.HD == H && lpk == L && a.kv_dtype == 0) {                                                    \
+            hipLaunchKernelGGL((k_attn_dec<H, 2, L, float>), grid, dim3(256), 0, st, a.qkv, a.pos, a.kc, a.vc, a); \
             qtts_last_kernel = "k_attn_dec<" #H ", 2, " #L ">";                                            \
+            return hipGetLastError() == hipSuccess ? 0 : -1;                                               \
+        }                                                                                                  \
+        if (a.HD == H && lpk == L && a.kv_dtype == 1) {                                                    \
+            hipLaunchKernelGGL((k_attn_dec<H, 2, L, bf16_t>), grid, dim3(256), 0, st, a.qkv, a.pos,        \
+                               reinterpret_cast<bf16_t *>(a.kc), reinterpret_cast<bf16_t *>(a.vc), a);     \
+            qtts_last_kernel = "k_attn_dec<" #H ", 2, " #L ", bf16>";                                      \
             return hipGetLastError() == hipSuccess ? 0 : -1;                                               \
         }
         QTTS_AD(128, 4) QTTS_AD(128, 8) QTTS_AD(128, 16) QTTS_AD(64, 2) QTTS_AD(32, 1) QTTS_AD(16, 1)
@@ -725,8 +882,13 @@ int qtts_attention(const AttnArgs &a, hipStream_t st) {
         return -1;
     }
     size_t smem = (size_t)(128 * 3 + 256 + 8 + 8 * 128 + a.S + 4) * sizeof(float);
-    hipLaunchKernelGGL(k_attn, dim3(a.NH, a.nrows), dim3(256), smem, st, a);
-    qtts_last_kernel = "k_attn";
+    if (a.kv_dtype == 1) {
+        hipLaunchKernelGGL(k_attn<bf16_t>, dim3(a.NH, a.nrows), dim3(256), smem, st, a);
+        qtts_last_kernel = "k_attn<bf16>";
+    } else {
+        hipLaunchKernelGGL(k_attn<float>, dim3(a.NH, a.nrows), dim3(256), smem, st, a);
+        qtts_last_kernel = "k_attn";
+    }
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
@@ -735,11 +897,17 @@ int qtts_qk_prep(const AttnArgs &a, hipStream_t st) {
         fprintf(stderr, "qtts_qk_prep: (NH+KV)*HD=%d exceeds 4096\n", (a.NH + a.KV) * a.HD);
         return -1;
     }
+    if (a.kv_dtype != 0 && a.kv_dtype != 1) {
+        fprintf(stderr, "qtts_qk_prep: unknown cache element type %d\n", a.kv_dtype);
+        return -1;
+    }
     if ((a.HD == 128 || (a.HD <= 64 && (a.HD & (a.HD - 1)) == 0))) {
         const dim3 grid(a.nrows, (a.NH + 2 * a.KV + 3) / 4);
-        hipLaunchKernelGGL(k_qk_prep_w, grid, dim3(256), 0, st, a);
+        if (a.kv_dtype == 1) hipLaunchKernelGGL(k_qk_prep_w<bf16_t>, grid, dim3(256), 0, st, a);
+        else hipLaunchKernelGGL(k_qk_prep_w<float>, grid, dim3(256), 0, st, a);
         return hipGetLastError() == hipSuccess ? 0 : -1;
     }
-    hipLaunchKernelGGL(k_qk_prep, dim3(a.nrows), dim3(256), 0, st, a);
+    if (a.kv_dtype == 1) hipLaunchKernelGGL(k_qk_prep<bf16_t>, dim3(a.nrows), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(k_qk_prep<float>, dim3(a.nrows), dim3(256), 0, st, a);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }

@@ -195,6 +195,13 @@ struct AttnArgs {
     // lanes per key of the split kernel at HD 128 (4 / 8 / 16), latched by the
     // model at creation (QTTS_HIP_ATTN_LPK); 0 = the default for HD / defer
     int lpk = 0;
+    // element type of the caches behind kc / vc: 0 fp32, 1 bf16 (the pointers
+    // then address uint16 rows of the same [B][S][KV*HD] layout).  Only the
+    // talker's cache may be bf16: the split decode kernel, the generic k_attn
+    // and the prefill writers have a bf16 form, the short / table / k_attn_o
+    // paths refuse it.  K and V rows are rounded to nearest even as they are
+    // stored, and the token's own k, v enter its attention as the rounded values
+    int kv_dtype = 0;
 };
 // keys per split of the talker decode attention (deferred merge or not; lpk
 // as AttnArgs::lpk)

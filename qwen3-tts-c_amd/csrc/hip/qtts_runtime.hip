@@ -127,6 +127,16 @@ struct qtts_dev {
     int bkz_wide = 1;        // QTTS_HIP_BKZ_WIDE=0: above 8 rows, no extra split-K columns for > 2048-wide slices (bsplit_kz); 2: from 2 rows, up to 4 columns
     float *x_st = nullptr, *qkv_s = nullptr, *att_s = nullptr, *h_s = nullptr, *logits_s = nullptr;
     float *kc = nullptr, *vc = nullptr, *kcs = nullptr, *vcs = nullptr;
+    // element type of the talker cache kc / vc, [L][B][S][KV*HD]: 0 fp32, 1 bf16
+    // (uint16 rows behind the same pointers; kv_layer() takes the slices).
+    // kv_dtype is what the allocated state holds, kv_want what the next
+    // qtts_dev_begin allocates (qtts_dev_set_kv_dtype, QTTS_HIP_KV at creation);
+    // the sub-talker cache kcs / vcs is always fp32
+    int kv_dtype = 0, kv_want = 0;
+    bool te_kv_said = false;   // the "engine not used with bf16 KV" line went out (once per model)
+    // the last talker pass left its last layer's attention output in `att`
+    // (false: batch 1 with the merge deferred to the O projection, or the engine)
+    bool att_own = false;
     int *codes = nullptr, *counts = nullptr, *n_gen = nullptr, *stopped = nullptr, *cur_row = nullptr;
     // [B] the id each slot's last draw produced (every sampler's out_tok): the
     // next sub-talker pass reads its input row by it -- one dependent load
@@ -218,6 +228,11 @@ struct qtts_dev {
 
     int QKV() const { return (d.NH + 2 * d.KV) * d.HD; }
     int QKVs() const { return (d.NHs + 2 * d.KVs) * d.HDs; }
+    size_t kv_esz() const { return kv_dtype == 1 ? 2 : 4; }
+    // layer l's slice [B][S][KV*HD] of a talker cache (kc or vc)
+    float *kv_layer(float *c, int l) const {
+        return reinterpret_cast<float *>(reinterpret_cast<char *>(c) + (size_t)l * nb * S * d.KV * d.HD * kv_esz());
+    }
 };
 
 // ----------------------------------------------------------------- helpers
@@ -466,6 +481,12 @@ extern "C" qtts_dev_t *qtts_dev_create(const qtts_dims_t *dims, int device) {
             hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && ncu >= 256)
             dv->tengine = std::min(3, std::max(1, atoi(te)));
     }
+    // QTTS_HIP_KV=bf16|fp32: the talker KV cache's element type (default fp32)
+    const char *kvd = getenv("QTTS_HIP_KV");
+    if (kvd && *kvd) {
+        if (!strcmp(kvd, "bf16")) dv->kv_want = 1;
+        else if (strcmp(kvd, "fp32")) fprintf(stderr, "qtts: QTTS_HIP_KV=%s ignored (bf16 or fp32)\n", kvd);
+    }
     const char *tb = getenv("QTTS_HIP_TAB0B");
     dv->tab0b = !(tb && !atoi(tb));
     const char *pf = getenv("QTTS_HIP_L2PF");
@@ -508,6 +529,51 @@ extern "C" void qtts_dev_destroy(qtts_dev_t *dv) {
 extern "C" size_t qtts_dev_bytes(const qtts_dev_t *dv, int which) {
     if (!dv) return 0;
     return which == 0 ? dv->wbytes + codec_weight_bytes(&dv->codec) + enc_weight_bytes(&dv->enc) : dv->sbytes;
+}
+
+extern "C" int qtts_dev_set_kv_dtype(qtts_dev_t *dv, int dtype) {
+    if (!dv || (dtype != 0 && dtype != 1)) return -1;
+    dv->kv_want = dtype;   // (the state changes at the next qtts_dev_begin)
+    return 0;
+}
+
+extern "C" int qtts_dev_kv_dtype(const qtts_dev_t *dv) { return dv ? dv->kv_want : -1; }
+
+extern "C" int qtts_dev_get_kv(qtts_dev_t *dv, int layer, int b, int pos0, int n, float *k_host, float *v_host) {
+    if (!dv || !dv->kc || !dv->vc || dv->nb < 1 || layer < 0 || layer >= dv->d.L || b < 0 || b >= dv->nb ||
+        pos0 < 0 || n < 1 || pos0 > dv->S - n)
+        return -1;
+    hipSetDevice(dv->device);
+    const size_t KVD = (size_t)dv->d.KV * dv->d.HD, cnt = (size_t)n * KVD, esz = dv->kv_esz();
+    const size_t off = ((size_t)b * dv->S + pos0) * KVD * esz;
+    CK(hipStreamSynchronize(dv->st));
+    float *caches[2] = {dv->kc, dv->vc}, *outs[2] = {k_host, v_host};
+    std::vector<uint16_t> tmp(dv->kv_dtype == 1 ? cnt : 0);
+    for (int i = 0; i < 2; ++i) {
+        if (!outs[i]) continue;
+        const char *src = reinterpret_cast<const char *>(dv->kv_layer(caches[i], layer)) + off;
+        if (dv->kv_dtype == 1) {
+            CK(hipMemcpy(tmp.data(), src, cnt * 2, hipMemcpyDeviceToHost));
+            for (size_t j = 0; j < cnt; ++j) outs[i][j] = host_bf16(tmp[j]);
+        } else {
+            CK(hipMemcpy(outs[i], src, cnt * 4, hipMemcpyDeviceToHost));
+        }
+    }
+    return 0;
+}
+
+extern "C" int qtts_dev_get_attn(qtts_dev_t *dv, float *qkv_host, float *att_host) {
+    if (!dv || dv->nb < 1 || !dv->qkv || !dv->att) return -1;
+    if (att_host && !dv->att_own) {
+        fprintf(stderr, "qtts_dev_get_attn: the last talker pass left no merged attention output "
+                        "(batch 1 defers the merge to the O projection; QTTS_HIP_ATTN_DEFER=0 keeps it)\n");
+        return -1;
+    }
+    hipSetDevice(dv->device);
+    CK(hipStreamSynchronize(dv->st));
+    if (qkv_host) CK(hipMemcpy(qkv_host, dv->qkv, (size_t)dv->nb * dv->QKV() * 4, hipMemcpyDeviceToHost));
+    if (att_host) CK(hipMemcpy(att_host, dv->att, (size_t)dv->nb * dv->d.NH * dv->d.HD * 4, hipMemcpyDeviceToHost));
+    return 0;
 }
 
 // RoPE tables with the reference's exact libm arithmetic (T.c:97-113)
@@ -619,6 +685,9 @@ extern "C" int qtts_dev_encode_audio(qtts_dev_t *dv, int nb, const float *const 
 static int alloc_state(qtts_dev *dv, int nb, int max_frames, int max_prefill) {
     const qtts_dims_t &d = dv->d;
     free_state(dv);
+    dv->kv_dtype = dv->kv_want;
+    if (dv->kv_dtype == 1 && dv->tengine && !dv->te_kv_said && (dv->te_kv_said = true))
+        fprintf(stderr, "qtts: the persistent talker engine (QTTS_HIP_TENGINE) has no bf16 KV form: not used\n");
     dv->nb = nb;
     dv->nrun = nb;
     dv->max_frames = max_frames;
@@ -649,8 +718,11 @@ static int alloc_state(qtts_dev *dv, int nb, int max_frames, int max_prefill) {
     A(att_s, float, B * d.NHs * d.HDs);
     A(h_s, float, B * d.Is);
     A(logits_s, float, B * d.Vs);
-    A(kc, float, (size_t)d.L * B * dv->S * d.KV * d.HD);
-    A(vc, float, (size_t)d.L * B * dv->S * d.KV * d.HD);
+    {   // (bf16: half the elements' worth of floats; L B S KV HD is even -- HD is a multiple of 8)
+        const size_t kv_floats = (size_t)d.L * B * dv->S * d.KV * d.HD * dv->kv_esz() / 4;
+        A(kc, float, kv_floats);
+        A(vc, float, kv_floats);
+    }
     A(kcs, float, (size_t)d.Ls * B * d.G * d.KVs * d.HDs);
     A(vcs, float, (size_t)d.Ls * B * d.G * d.KVs * d.HDs);
     A(codes, int, B * (max_frames + 1) * d.G);
@@ -1041,7 +1113,7 @@ static L2Prefetch pf_attn_o(const qtts_dev *dv, const bf16_t *Wo, int R, int NH,
 static bool tengine_ok(qtts_dev *dv, int kzo, int kzd) {
     const qtts_dims_t &d = dv->d;
     // (the launch's 32-key splits need nsplit * 32 >= S partial slots; any S)
-    return dv->tengine && dv->te_g && dv->nrun == 1 && !kzo && !kzd && dv->attn_defer &&
+    return dv->tengine && dv->te_g && dv->kv_dtype == 0 && dv->nrun == 1 && !kzo && !kzd && dv->attn_defer &&
            qtts_tlayer_dims_ok(d.H, d.NH, d.KV, d.HD, d.I) && dv->S > 16 && dv->att_nsplit * 32 >= dv->S;
 }
 // layer launches enqueued (or captured) on the engine since the library
@@ -1058,7 +1130,7 @@ static int talker_layers_te(qtts_dev *dv) {
         a.wqkv = ly.wqkv; a.wo = ly.wo; a.wgu = ly.wgu; a.wdown = ly.wdown;
         a.in_norm = ly.in; a.post_norm = ly.post; a.qn_w = ly.qn; a.kn_w = ly.kn;
         a.rope_cos = dv->rope_cos; a.rope_sin = dv->rope_sin;
-        a.kc = dv->kc + (size_t)l * NBA * dv->S * KVD; a.vc = dv->vc + (size_t)l * NBA * dv->S * KVD;
+        a.kc = dv->kv_layer(dv->kc, l); a.vc = dv->kv_layer(dv->vc, l);   // (fp32 only: tengine_ok)
         a.pos = dv->kv_len; a.skip = dv->stopped; a.eps = d.eps;
         a.part = dv->att_part; a.cnt = dv->att_cnt; a.nsplit = dv->att_nsplit;
         a.g_qkv = dv->te_g; a.g_att = dv->te_g + 4096; a.g_x = a.g_att + 2048; a.g_h = a.g_x + 2048;
@@ -1071,6 +1143,7 @@ static int talker_layers_te(qtts_dev *dv) {
         g_tengine_layers.fetch_add(1);
     }
     dv->tk_xfin = dv->x_tk; dv->tk_pend = nullptr; dv->tk_npend = 0;
+    dv->att_own = false;
     return 0;
 }
 
@@ -1093,7 +1166,7 @@ static int talker_layers(qtts_dev *dv) {
         AttnArgs t;
         t.mode = 0; t.qkv = dv->qkv; t.ld_qkv = QKV; t.qn_w = ly.qn; t.kn_w = ly.kn; t.eps = d.eps;
         t.rope_cos = dv->rope_cos; t.rope_sin = dv->rope_sin;
-        t.kc = dv->kc + (size_t)l * NBA * dv->S * KVD; t.vc = dv->vc + (size_t)l * NBA * dv->S * KVD; t.S = dv->S;
+        t.kc = dv->kv_layer(dv->kc, l); t.vc = dv->kv_layer(dv->vc, l); t.S = dv->S; t.kv_dtype = dv->kv_dtype;
         t.pos = dv->kv_len; t.NH = d.NH; t.KV = d.KV; t.HD = d.HD; t.out = dv->att; t.ld_out = AD; t.nrows = nb;
         t.skip = dv->stopped;
         t.part = dv->att_part; t.cnt = dv->att_cnt; t.nsplit = dv->att_nsplit; t.lpk = dv->attn_lpk;
@@ -1101,6 +1174,7 @@ static int talker_layers(qtts_dev *dv) {
         // prologue (one dependent hand-off fewer per layer)
         const bool defer = dv->attn_defer && nb == 1 && qtts_attn_defer_ok(t) && qtts_gemvw_amerge_ok(d.H, AD);
         t.defer = defer;
+        dv->att_own = !defer;
         const bool dbg = dv->gm_dbg && l == dv->gm_dbg_layer;
         if (dbg) a.dbg = dv->gm_dbg;
         // (batch 1: the O projection's slices two launches ahead, the attention in between)
@@ -1408,7 +1482,9 @@ extern "C" int qtts_dev_begin(qtts_dev_t *dv, int nb, int max_frames, int max_pr
     hipSetDevice(dv->device);
     CKI(join_prime(dv));   // a prime left pending by a run that pushed no frames
     if (max_prefill < 16) max_prefill = 16;
-    const bool realloc_ = nb != dv->nb || max_frames > dv->max_frames || max_prefill > dv->p_cap;
+    // (another cache element type: new state, and with it new frame graphs)
+    const bool realloc_ = nb != dv->nb || max_frames > dv->max_frames || max_prefill > dv->p_cap ||
+                          dv->kv_want != dv->kv_dtype;
     if (realloc_) {
         if (dv->cst) CK(hipStreamSynchronize(dv->cst));   // a prime still reading the codec scratch
         dv->prime_pending = false;
@@ -1547,7 +1623,7 @@ static int prefill_rows(qtts_dev *dv, const std::vector<int> &slots, const std::
         AttnArgs t;
         t.mode = 1; t.qkv = dv->pqkv; t.ld_qkv = QKV; t.qn_w = ly.qn; t.kn_w = ly.kn; t.eps = d.eps;
         t.rope_cos = dv->rope_cos; t.rope_sin = dv->rope_sin;
-        t.kc = dv->kc + (size_t)l * dv->nb * dv->S * KVD; t.vc = dv->vc + (size_t)l * dv->nb * dv->S * KVD;
+        t.kc = dv->kv_layer(dv->kc, l); t.vc = dv->kv_layer(dv->vc, l); t.kv_dtype = dv->kv_dtype;
         t.S = dv->S; t.pos = dv->ppos; t.row_b = dv->prow_b; t.NH = d.NH; t.KV = d.KV; t.HD = d.HD;
         t.out = dv->patt; t.ld_out = AD; t.nrows = R;
         CKI(qtts_qk_prep(t, st));
@@ -1648,11 +1724,11 @@ extern "C" int qtts_dev_move_slot(qtts_dev_t *dv, int from, int to) {
     CK(hipStreamSynchronize(st));
     CK(hipMemcpy(&kv, dv->kv_len + from, 4, hipMemcpyDeviceToHost));
     if (kv < 0 || kv >= dv->S) return -1;
-    const size_t KVD = (size_t)d.KV * d.HD, lstride = (size_t)dv->nb * dv->S * KVD * 4;
-    const size_t w = (size_t)(kv + 1) * KVD * 4;   // positions 0 .. kv (the next step writes kv)
+    const size_t KVD = (size_t)d.KV * d.HD, esz = dv->kv_esz(), lstride = (size_t)dv->nb * dv->S * KVD * esz;
+    const size_t w = (size_t)(kv + 1) * KVD * esz;   // positions 0 .. kv (the next step writes kv)
     for (float *c : {dv->kc, dv->vc})
-        CK(hipMemcpy2DAsync((char *)c + (size_t)to * dv->S * KVD * 4, lstride,
-                            (const char *)c + (size_t)from * dv->S * KVD * 4, lstride, w, d.L,
+        CK(hipMemcpy2DAsync((char *)c + (size_t)to * dv->S * KVD * esz, lstride,
+                            (const char *)c + (size_t)from * dv->S * KVD * esz, lstride, w, d.L,
                             hipMemcpyDeviceToDevice, st));
     auto row = [&](void *base, size_t bytes) {
         return hipMemcpyAsync((char *)base + (size_t)to * bytes, (const char *)base + (size_t)from * bytes, bytes,
@@ -1984,6 +2060,9 @@ extern "C" int qtts_dev_talker_prefill_host(qtts_dev_t *dv, const float *embeds,
     if (n > dv->p_cap) {
         qtts_gen_params_t p = dv->par;
         CKI(qtts_dev_begin(dv, dv->nb, dv->max_frames > 4096 ? dv->max_frames : 4096, n, &p));
+    } else if (dv->kv_want != dv->kv_dtype) {   // qtts_dev_set_kv_dtype since the state was allocated
+        qtts_gen_params_t p = dv->par;
+        CKI(qtts_dev_begin(dv, dv->nb, dv->max_frames, dv->p_cap, &p));
     }
     const qtts_dims_t &d = dv->d;
     for (int b = 0; b < dv->nb; ++b) dv->p_len_h[b] = b == 0 ? n : 0;
@@ -2224,6 +2303,39 @@ extern "C" int qtts_hip_sample_top_k(int *out, const float *logits, int vocab, i
     s.logits = logits; s.ld = vocab; s.n = vocab; s.nb = batch; s.top_k = top_k; s.top_p = top_p; s.temp = temp;
     s.mode = 0; s.st_rng = rng_bits; s.out_tok = out;
     return qtts_sample(s, (hipStream_t)stream);
+}
+
+// The talker's decode attention on its own, launched as a talker layer
+// launches it (mode 0, the kernel's own split merge); waits for the result.
+extern "C" int qtts_hip_attn_decode(float *out, const float *qkv, void *kc, void *vc, const float *qn_w,
+                                    const float *kn_w, const float *rope_cos, const float *rope_sin, const int *pos,
+                                    int NH, int KV, int HD, int S, int rows, float eps, int kv_dtype, void *stream) {
+    if (!out || !qkv || !kc || !vc || !qn_w || !kn_w || !rope_cos || !rope_sin || !pos) return -1;
+    if (NH < 1 || KV < 1 || HD < 1 || S < 1 || rows < 1 || rows > 65535 || (kv_dtype != 0 && kv_dtype != 1)) return -1;
+    hipStream_t st = (hipStream_t)stream;
+    // every row's position inside the cache (the kernels index by it unchecked)
+    std::vector<int> ph(rows);
+    CK(hipMemcpyAsync(ph.data(), pos, (size_t)rows * 4, hipMemcpyDeviceToHost, st));
+    CK(hipStreamSynchronize(st));
+    for (int p : ph)
+        if (p < 0 || p >= S) { fprintf(stderr, "qtts_hip_attn_decode: position %d outside [0, %d)\n", p, S); return -1; }
+    AttnArgs t;
+    t.mode = 0; t.qkv = qkv; t.ld_qkv = (NH + 2 * KV) * HD; t.qn_w = qn_w; t.kn_w = kn_w; t.eps = eps;
+    t.rope_cos = rope_cos; t.rope_sin = rope_sin;
+    t.kc = (float *)kc; t.vc = (float *)vc; t.S = S; t.kv_dtype = kv_dtype;
+    t.pos = pos; t.NH = NH; t.KV = KV; t.HD = HD; t.out = out; t.ld_out = NH * HD; t.nrows = rows;
+    const int gph = NH % KV ? 1 : NH / KV, ch = qtts_attn_keys_per_split(HD, false, 0);
+    t.nsplit = (S + ch - 1) / ch;
+    const size_t part_n = (size_t)rows * KV * t.nsplit * (gph * HD + 2 * gph), cnt_n = (size_t)rows * KV;
+    void *scratch = nullptr;
+    CK(hipMalloc(&scratch, part_n * 4 + cnt_n * 4));
+    t.part = (float *)scratch;
+    t.cnt = (int *)(t.part + part_n);
+    int rc = hipMemsetAsync(scratch, 0, part_n * 4 + cnt_n * 4, st) == hipSuccess ? 0 : -1;
+    if (!rc) rc = qtts_attention(t, st);
+    if (hipStreamSynchronize(st) != hipSuccess) rc = -1;
+    hipFree(scratch);
+    return rc;
 }
 
 // One frame run eagerly with an event pair around every kernel launch on the

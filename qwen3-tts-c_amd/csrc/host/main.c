@@ -11,7 +11,8 @@
  * Additions: --device N (HIP device), --batch N (N copies of the prompt in
  * one lock-step batch; the first one's audio is written), --stream N (exact
  * streaming decode: audio delivered after frame 0 and then every N frames;
- * prints "First packet: X ms").
+ * prints "First packet: X ms"), --kv-cache fp32|bf16 (talker KV cache
+ * elements, qwen_tts_set_kv_cache_dtype).
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -43,6 +44,8 @@ static void usage(const char *prog) {
             "  --benchmark-runs N (1)  --benchmark-warmup N (0)\n"
             "  --device N (HIP device, default 0)   --batch N (lock-step batch of N copies, default 1)\n"
             "  --stream N (streaming decode, audio chunks every N frames after the first)\n"
+            "  --kv-cache fp32|bf16 (talker KV cache elements, default fp32; bf16 halves the cache,\n"
+            "                      codes then no longer bit-exact against the reference)\n"
             "voice clone (include/qwen_tts.h qwen_tts_generate_voice_clone[_audio]):\n"
             "  --ref-audio <wav>   reference audio (mono/stereo PCM16 or float WAV; other rates are resampled\n"
             "                      to 24 kHz): encoded on the GPU (12 Hz codes + speaker x-vector)\n"
@@ -167,6 +170,7 @@ static void progress(int step, int total, void *u) {
 int main(int argc, char **argv) {
     const char *dir = NULL, *ids = NULL, *ids_file = NULL, *spk = NULL, *lang = NULL, *out = "output.wav";
     int verbose = 0, runs = 1, warmup = 0, device = -1, batch = 1, stream_chunk = 0, non_streaming = 0;
+    int kv_cache = -1;   /* --kv-cache: -1 = the library's default ($QTTS_HIP_KV or fp32) */
     const char *ref_codes_file = NULL, *ref_text = NULL, *xvec_file = NULL, *text = NULL, *ref_audio = NULL;
     int print_ids = 0, xvec_only = 0;
     float temp = -1, st_temp = -1, top_p = -1, st_top_p = -1, rep = -1;
@@ -199,6 +203,12 @@ int main(int argc, char **argv) {
         else if (ARG("--device")) device = (int)strtol(argv[++i], NULL, 10);
         else if (ARG("--batch")) batch = (int)strtol(argv[++i], NULL, 10);
         else if (ARG("--stream")) stream_chunk = (int)strtol(argv[++i], NULL, 10);
+        else if (ARG("--kv-cache")) {
+            const char *v = argv[++i];
+            if (!strcmp(v, "bf16")) kv_cache = QWEN_TTS_KV_BF16;
+            else if (!strcmp(v, "fp32")) kv_cache = QWEN_TTS_KV_F32;
+            else { fprintf(stderr, "Error: --kv-cache takes fp32 or bf16\n\n"); usage(argv[0]); return 1; }
+        }
         else if (ARG("--ref-codes")) ref_codes_file = argv[++i];
         else if (ARG("--ref-text")) ref_text = argv[++i];
         else if (ARG("--xvector")) xvec_file = argv[++i];
@@ -308,6 +318,11 @@ int main(int argc, char **argv) {
     if (!ctx) {
         fprintf(stderr, "Error: failed to load model\n");
         free(file_ids);
+        return 1;
+    }
+    if (kv_cache >= 0 && qwen_tts_set_kv_cache_dtype(ctx, kv_cache) != 0) {
+        fprintf(stderr, "Error: cannot select the KV cache type\n");
+        qwen_tts_free(ctx); free(ref_codes); free(xvec); free(file_ids);
         return 1;
     }
     if (text && !ids) {   /* -T: the chat-template ids of the text (Qwen2 BPE, bpe.c) */

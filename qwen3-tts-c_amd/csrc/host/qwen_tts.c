@@ -385,6 +385,16 @@ qwen_tts_ctx_t *qwen_tts_load_on(const char *model_dir, int device) {
     return ctx;
 }
 
+int qwen_tts_set_kv_cache_dtype(qwen_tts_ctx_t *ctx, int dtype) {
+    if (!ctx || !ctx->hip) return -1;
+    return qtts_dev_set_kv_dtype((qtts_dev_t *)ctx->hip, dtype);
+}
+
+int qwen_tts_kv_cache_dtype(qwen_tts_ctx_t *ctx) {
+    if (!ctx || !ctx->hip) return -1;
+    return qtts_dev_kv_dtype((qtts_dev_t *)ctx->hip);
+}
+
 /* the per-utterance results of the last qwen_tts_generate_queue */
 static void queue_clear(qwen_tts_ctx_t *ctx) {
     if (ctx->queue_codes)

@@ -89,7 +89,11 @@ EXPORTS = [
     "qtts_dev_codec_async_end", "qtts_dev_codec_multi", "qtts_dev_enc_config", "qtts_dev_enc_available", "qtts_dev_speaker_embed",
     "qtts_dev_encode_audio", "qwen_tts_generate_queue", "qwen_tts_queue_codes", "qtts_dev_reserve", "qtts_dev_refill",
     "qtts_dev_retire", "qtts_dev_frame_stops", "qtts_dev_move_slot", "qtts_dev_set_rows", "qtts_hip_tengine_layers",
+    "qwen_tts_set_kv_cache_dtype", "qwen_tts_kv_cache_dtype", "qtts_dev_set_kv_dtype", "qtts_dev_kv_dtype",
+    "qtts_dev_get_kv", "qtts_dev_get_attn", "qtts_hip_attn_decode",
 ]
+
+KV_F32, KV_BF16 = 0, 1   # QWEN_TTS_KV_F32 / QWEN_TTS_KV_BF16
 
 _LIB = None
 
@@ -207,6 +211,20 @@ def lib():
     L.qtts_dev_speaker_embed.argtypes = [C.c_void_p, C.c_int, C.POINTER(_fp), _ip, _fp, _fp]
     L.qtts_dev_encode_audio.restype = C.c_int
     L.qtts_dev_encode_audio.argtypes = [C.c_void_p, C.c_int, C.POINTER(_fp), _ip, _ip, C.c_int, _ip, _fp]
+    L.qwen_tts_set_kv_cache_dtype.restype = C.c_int
+    L.qwen_tts_set_kv_cache_dtype.argtypes = [C.POINTER(Ctx), C.c_int]
+    L.qwen_tts_kv_cache_dtype.restype = C.c_int
+    L.qwen_tts_kv_cache_dtype.argtypes = [C.POINTER(Ctx)]
+    L.qtts_dev_set_kv_dtype.restype = C.c_int
+    L.qtts_dev_set_kv_dtype.argtypes = [C.c_void_p, C.c_int]
+    L.qtts_dev_kv_dtype.restype = C.c_int
+    L.qtts_dev_kv_dtype.argtypes = [C.c_void_p]
+    L.qtts_dev_get_kv.restype = C.c_int
+    L.qtts_dev_get_kv.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp]
+    L.qtts_dev_get_attn.restype = C.c_int
+    L.qtts_dev_get_attn.argtypes = [C.c_void_p, _fp, _fp]
+    L.qtts_dev_bytes.restype = C.c_size_t
+    L.qtts_dev_bytes.argtypes = [C.c_void_p, C.c_int]
     L.qtts_hip_device_count.restype = C.c_int
     L.qtts_hip_tengine_layers.restype = C.c_longlong
     vp = C.c_void_p
@@ -219,6 +237,8 @@ def lib():
     L.qtts_hip_transposed_conv1d.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]
     L.qtts_hip_snake_beta.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, vp]
     L.qtts_hip_expf_glibc.argtypes = [vp, vp, C.c_int, vp]
+    L.qtts_hip_attn_decode.restype = C.c_int
+    L.qtts_hip_attn_decode.argtypes = [vp] * 9 + [C.c_int] * 5 + [C.c_float, C.c_int, vp]
     _LIB = L
     return L
 
@@ -268,6 +288,46 @@ class QwenTTS:
         c.temperature, c.top_k, c.top_p, c.repetition_penalty = temperature, top_k, top_p, rep
         c.subtalker_temperature, c.subtalker_top_k, c.subtalker_top_p = st_temperature, st_top_k, st_top_p
         c.max_new_tokens, c.fixed_codec_tokens, c.sample_seed = max_tokens, fixed, seed
+
+    def set_kv_cache(self, dtype):
+        """Talker KV cache elements from the next generation on: "fp32" / KV_F32
+        (default, codes bit-exact against the reference) or "bf16" / KV_BF16
+        (half the cache bytes; qwen_tts_set_kv_cache_dtype)."""
+        d = {"fp32": KV_F32, "bf16": KV_BF16}.get(dtype, dtype)
+        if not isinstance(d, int) or lib().qwen_tts_set_kv_cache_dtype(self.ctx, d) != 0:
+            raise ValueError(f"kv cache dtype {dtype!r} (fp32 or bf16)")
+
+    def kv_cache(self):
+        return lib().qwen_tts_kv_cache_dtype(self.ctx)
+
+    def state_bytes(self):
+        """device bytes of the generation state (qtts_dev_bytes(dev, 1))"""
+        return int(lib().qtts_dev_bytes(C.c_void_p(self.c.hip), 1))
+
+    def get_kv(self, layer, b, pos0, n):
+        """(k, v) fp32 [n, kv_heads * head_dim]: talker cache rows [pos0, pos0 + n)
+        of `layer`, slot b (qtts_dev_get_kv; bf16 rows widened exactly)."""
+        w = self.cfg.talker_kv_heads * self.cfg.talker_head_dim
+        k = np.zeros((n, w), np.float32)
+        v = np.zeros((n, w), np.float32)
+        rc = lib().qtts_dev_get_kv(C.c_void_p(self.c.hip), int(layer), int(b), int(pos0), int(n),
+                                   k.ctypes.data_as(_fp), v.ctypes.data_as(_fp))
+        if rc != 0:
+            raise ValueError(f"get_kv(layer={layer}, b={b}, pos0={pos0}, n={n}) out of range")
+        return k, v
+
+    def get_attn(self, slots, att=True):
+        """(qkv [slots, (NH + 2 KV) HD], att [slots, NH HD] or None): the last
+        talker layer's decode attention input / output of the most recent
+        talker pass (qtts_dev_get_attn); `slots` = the slots of that run."""
+        c = self.cfg
+        qkv = np.zeros((slots, (c.talker_heads + 2 * c.talker_kv_heads) * c.talker_head_dim), np.float32)
+        out = np.zeros((slots, c.talker_heads * c.talker_head_dim), np.float32) if att else None
+        rc = lib().qtts_dev_get_attn(C.c_void_p(self.c.hip), qkv.ctypes.data_as(_fp),
+                                     out.ctypes.data_as(_fp) if att else None)
+        if rc != 0:
+            raise RuntimeError("get_attn: no merged attention output from the last talker pass")
+        return qkv, out
 
     def generate(self, ids, speaker=None, language=None):
         csv = ",".join(str(int(i)) for i in ids).encode()
@@ -640,3 +700,12 @@ class Kernels:
     @staticmethod
     def expf_glibc(out, x, n):
         _ok(lib().qtts_hip_expf_glibc(_ptr(out), _ptr(x), n, _stream()), "expf")
+
+    @staticmethod
+    def attn_decode(out, qkv, kc, vc, qn_w, kn_w, rope_cos, rope_sin, pos_i32, NH, KV, HD, S, rows, eps, kv_dtype=0):
+        """The talker's decode attention (qtts_hip_attn_decode): kc / vc
+        [rows, S, KV * HD], float32 for kv_dtype 0, bf16 bit patterns (a 2-byte
+        torch dtype) for kv_dtype 1; row pos[r] of each is written."""
+        _ok(lib().qtts_hip_attn_decode(_ptr(out), _ptr(qkv), _ptr(kc), _ptr(vc), _ptr(qn_w), _ptr(kn_w),
+                                       _ptr(rope_cos), _ptr(rope_sin), _ptr(pos_i32), NH, KV, HD, S, rows, eps,
+                                       kv_dtype, _stream()), "attn_decode")
