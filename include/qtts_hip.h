@@ -295,6 +295,47 @@ int qtts_hip_attn_decode(float *out_dev, const float *qkv_dev, void *kc_dev, voi
                          const float *rope_cos_dev, const float *rope_sin_dev,
                          const int *pos_dev, int NH, int KV, int HD, int S, int rows,
                          float eps, int kv_dtype, void *stream);
+/* The same with AttnArgs::skip: skip_dev [rows] (may be NULL), a nonzero flag
+ * keeps row r from storing its k / v (a stopped slot); its output is still
+ * computed, the token's own k / v included.  qtts_hip_attn_decode forwards
+ * here with NULL.  NH == 2 KV with HD 16 / 32 / 64 / 128 runs the short kernel
+ * (k_attn_short) at S <= 16 and the split kernel above it, everything else
+ * the generic k_attn. */
+int qtts_hip_attn_decode_ex(float *out_dev, const float *qkv_dev, void *kc_dev, void *vc_dev,
+                            const float *qn_w_dev, const float *kn_w_dev,
+                            const float *rope_cos_dev, const float *rope_sin_dev,
+                            const int *pos_dev, int NH, int KV, int HD, int S, int rows,
+                            float eps, int kv_dtype, const int *skip_dev, void *stream);
+/* The cached attention (k_attn mode 1) behind the talker prefill, the codec
+ * transformer and the voice-clone encoder: row r attends keys
+ * [max(0, pos[r] + 1 - win), pos[r]] (win 0: [0, pos[r]]) of slot row_b[r] of
+ * the caches [slots][S][KV*HD].  out_dev [rows][NH HD]; q_dev rows of stride
+ * ld_q floats.
+ * prep 1: the rows are fused q|k|v rows (ld_q >= (NH + 2 KV) HD);
+ *   qtts_qk_prep runs first as the prefill issues it: q heads normalised and
+ *   rotated in place, k (normalised, rotated) and v stored at (row_b[r],
+ *   pos[r]); then the attention.  Needs the norm weights and RoPE tables.
+ * prep 0: q is ready and the caches are filled (the norm weights and tables
+ *   are not read and may be NULL).
+ * pos_dev[r] in [0, S), row_b_dev[r] in [0, slots), HD in {8, 16, 32, 64, 128}.
+ * -1 for kv_dtype 1 with a window (no bf16 window path).  A parity entry as
+ * qtts_hip_attn_decode is. */
+int qtts_hip_attn_cached(float *out_dev, float *q_dev, int ld_q, void *kc_dev, void *vc_dev,
+                         const float *qn_w_dev, const float *kn_w_dev,
+                         const float *rope_cos_dev, const float *rope_sin_dev,
+                         const int *row_b_dev, const int *pos_dev, int NH, int KV, int HD, int S, int slots,
+                         int rows, float eps, int win, int kv_dtype, int prep, void *stream);
+/* The sub-talker's attention + O projection by kv head (k_attn_o), fp32 caches
+ * [rows][S][KV*HD], no id table: part_dev[(g * rows + r) * R + i] =
+ * Wo[i, 2 HD g .. 2 HD (g + 1)) . attention of kv head g's two query heads;
+ * Wo_dev bf16 [R][NH*HD], 16-byte aligned.  Row r's k / v are stored at
+ * pos_dev[r].  Returns 1 (nothing launched) for a shape the kernel does not
+ * cover: NH != 2 KV, S > 16, HD outside 16 / 32 / 64 / 128. */
+int qtts_hip_attn_o(float *part_dev, const float *qkv_dev, float *kc_dev, float *vc_dev,
+                    const float *qn_w_dev, const float *kn_w_dev,
+                    const float *rope_cos_dev, const float *rope_sin_dev, const int *pos_dev,
+                    const uint16_t *Wo_dev, int R, int NH, int KV, int HD, int S, int rows, float eps,
+                    void *stream);
 /* glibc-exact expf replica used by the sampler (for the libm cross-check test) */
 int qtts_hip_expf_glibc(float *out_dev, const float *in_dev, int n, void *stream);
 int qtts_hip_sync(void);

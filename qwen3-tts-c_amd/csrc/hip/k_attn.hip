@@ -822,6 +822,13 @@ int qtts_attention(const AttnArgs &a, hipStream_t st) {
         fprintf(stderr, "qtts_attention: unsupported head config NH=%d KV=%d HD=%d\n", a.NH, a.KV, a.HD);
         return -1;
     }
+    // k_attn's lane groups (HD/8 lanes per key summed by xor shuffles, 256 /
+    // (HD/8) keys per pass, HD/4 lanes per V row) are wrong for a head size
+    // that is no power of two (measured: errors of 0.2 - 0.7 at HD 24 / 40 / 96)
+    if (!qtts_attn_head_ok(a.HD)) {
+        fprintf(stderr, "qtts_attention: unsupported head_dim %d (8, 16, 32, 64 or 128)\n", a.HD);
+        return -1;
+    }
     const int gph = a.NH / a.KV;
     const bool hd_ok = a.HD == 128 || a.HD == 64 || a.HD == 32 || a.HD == 16;
     if (a.kv_dtype != 0 && a.kv_dtype != 1) {
@@ -830,7 +837,7 @@ int qtts_attention(const AttnArgs &a, hipStream_t st) {
     }
     // bf16 caches: the split decode kernel and the generic kernel only (the
     // talker); the short / table paths (the sub-talker's) and the sliding
-    // window (the codec's, no bf16 caller and no test of it) are fp32
+    // window (the codec's and the encoder's: no bf16 caller) are fp32
     if (a.kv_dtype == 1 &&
         ((a.mode == 0 && a.win == 0 && gph == 2 && hd_ok && a.S <= 16) || a.qkv_tab || a.xc_dst || a.win != 0)) {
         fprintf(stderr, "qtts_attention: bf16 cache not covered on the short / table / window paths\n");

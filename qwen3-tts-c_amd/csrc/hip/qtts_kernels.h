@@ -218,6 +218,9 @@ bool qtts_attn_o_covers(const AttnArgs &a, const bf16_t *Wo);
 // Name of the kernel instantiation the last launcher on this thread chose
 // (diagnostics: per-kernel profile rows match rocprofv3's kernel names).
 extern thread_local const char *qtts_last_kernel;
+// head sizes the attention kernels serve: k_attn's lane groups (HD/8 lanes per
+// key, HD/4 per V row) need a power of two, as every specialised kernel does
+inline bool qtts_attn_head_ok(int HD) { return HD == 8 || HD == 16 || HD == 32 || HD == 64 || HD == 128; }
 int qtts_attention(const AttnArgs &a, hipStream_t st);
 // prefill helper: q/k RMSNorm + RoPE in place on qkv rows, k/v -> cache at (row_b, pos)
 int qtts_qk_prep(const AttnArgs &a, hipStream_t st);

@@ -623,7 +623,9 @@ extern "C" int qtts_dev_finalize(qtts_dev_t *dv) {
     }
     if (ok && d.H != d.Hs) ok = need("talker.code_predictor.small_to_mtp_projection.weight");
     if (!ok) return -1;
-    if (d.HD > 128 || d.HDs > 128 || d.G > 32) {
+    // (head sizes: what qtts_attention serves -- its generic kernel is wrong
+    // for a head size that is no power of two)
+    if (!qtts_attn_head_ok(d.HD) || !qtts_attn_head_ok(d.HDs) || d.G > 32) {
         fprintf(stderr, "Error: unsupported head_dim (talker=%d subtalker=%d) or code groups %d\n", d.HD, d.HDs, d.G);
         return -1;
     }
@@ -2305,25 +2307,38 @@ extern "C" int qtts_hip_sample_top_k(int *out, const float *logits, int vocab, i
     return qtts_sample(s, (hipStream_t)stream);
 }
 
+// every rows-long device index vector inside [0, lim) (the kernels index by
+// them unchecked)
+static int attn_ints_ok(const char *who, const char *what, const int *dev, int rows, int lim, hipStream_t st) {
+    std::vector<int> h(rows);
+    CK(hipMemcpyAsync(h.data(), dev, (size_t)rows * 4, hipMemcpyDeviceToHost, st));
+    CK(hipStreamSynchronize(st));
+    for (int v : h)
+        if (v < 0 || v >= lim) { fprintf(stderr, "%s: %s %d outside [0, %d)\n", who, what, v, lim); return -1; }
+    return 0;
+}
+
+static bool attn_dims_ok(int NH, int KV, int HD, int S, int rows, int kv_dtype) {
+    return NH >= 1 && KV >= 1 && HD >= 1 && S >= 1 && rows >= 1 && rows <= 65535 && (kv_dtype == 0 || kv_dtype == 1);
+}
+
 // The talker's decode attention on its own, launched as a talker layer
 // launches it (mode 0, the kernel's own split merge); waits for the result.
-extern "C" int qtts_hip_attn_decode(float *out, const float *qkv, void *kc, void *vc, const float *qn_w,
-                                    const float *kn_w, const float *rope_cos, const float *rope_sin, const int *pos,
-                                    int NH, int KV, int HD, int S, int rows, float eps, int kv_dtype, void *stream) {
+// skip: AttnArgs::skip, per row (may be NULL).
+extern "C" int qtts_hip_attn_decode_ex(float *out, const float *qkv, void *kc, void *vc, const float *qn_w,
+                                       const float *kn_w, const float *rope_cos, const float *rope_sin,
+                                       const int *pos, int NH, int KV, int HD, int S, int rows, float eps,
+                                       int kv_dtype, const int *skip, void *stream) {
     if (!out || !qkv || !kc || !vc || !qn_w || !kn_w || !rope_cos || !rope_sin || !pos) return -1;
-    if (NH < 1 || KV < 1 || HD < 1 || S < 1 || rows < 1 || rows > 65535 || (kv_dtype != 0 && kv_dtype != 1)) return -1;
+    if (!attn_dims_ok(NH, KV, HD, S, rows, kv_dtype)) return -1;
     hipStream_t st = (hipStream_t)stream;
-    // every row's position inside the cache (the kernels index by it unchecked)
-    std::vector<int> ph(rows);
-    CK(hipMemcpyAsync(ph.data(), pos, (size_t)rows * 4, hipMemcpyDeviceToHost, st));
-    CK(hipStreamSynchronize(st));
-    for (int p : ph)
-        if (p < 0 || p >= S) { fprintf(stderr, "qtts_hip_attn_decode: position %d outside [0, %d)\n", p, S); return -1; }
+    CKI(attn_ints_ok("qtts_hip_attn_decode", "position", pos, rows, S, st));
     AttnArgs t;
     t.mode = 0; t.qkv = qkv; t.ld_qkv = (NH + 2 * KV) * HD; t.qn_w = qn_w; t.kn_w = kn_w; t.eps = eps;
     t.rope_cos = rope_cos; t.rope_sin = rope_sin;
     t.kc = (float *)kc; t.vc = (float *)vc; t.S = S; t.kv_dtype = kv_dtype;
     t.pos = pos; t.NH = NH; t.KV = KV; t.HD = HD; t.out = out; t.ld_out = NH * HD; t.nrows = rows;
+    t.skip = skip;
     const int gph = NH % KV ? 1 : NH / KV, ch = qtts_attn_keys_per_split(HD, false, 0);
     t.nsplit = (S + ch - 1) / ch;
     const size_t part_n = (size_t)rows * KV * t.nsplit * (gph * HD + 2 * gph), cnt_n = (size_t)rows * KV;
@@ -2335,6 +2350,63 @@ extern "C" int qtts_hip_attn_decode(float *out, const float *qkv, void *kc, void
     if (!rc) rc = qtts_attention(t, st);
     if (hipStreamSynchronize(st) != hipSuccess) rc = -1;
     hipFree(scratch);
+    return rc;
+}
+
+extern "C" int qtts_hip_attn_decode(float *out, const float *qkv, void *kc, void *vc, const float *qn_w,
+                                    const float *kn_w, const float *rope_cos, const float *rope_sin, const int *pos,
+                                    int NH, int KV, int HD, int S, int rows, float eps, int kv_dtype, void *stream) {
+    return qtts_hip_attn_decode_ex(out, qkv, kc, vc, qn_w, kn_w, rope_cos, rope_sin, pos, NH, KV, HD, S, rows, eps,
+                                   kv_dtype, nullptr, stream);
+}
+
+// The cached attention (mode 1) on its own: prep 1 as prefill_rows issues it
+// (qtts_qk_prep, then qtts_attention, on fused q|k|v rows), prep 0 as the
+// codec transformer and the encoder do (q ready, caches filled, a window).
+extern "C" int qtts_hip_attn_cached(float *out, float *q, int ld_q, void *kc, void *vc, const float *qn_w,
+                                    const float *kn_w, const float *rope_cos, const float *rope_sin,
+                                    const int *row_b, const int *pos, int NH, int KV, int HD, int S, int slots,
+                                    int rows, float eps, int win, int kv_dtype, int prep, void *stream) {
+    if (!out || !q || !kc || !vc || !row_b || !pos) return -1;
+    if (prep != 0 && prep != 1) return -1;
+    if (prep && (!qn_w || !kn_w || !rope_cos || !rope_sin)) return -1;
+    if (!attn_dims_ok(NH, KV, HD, S, rows, kv_dtype) || slots < 1 || win < 0) return -1;
+    if (HD < 8 || HD > 128 || (HD & 7) || NH % KV || !qtts_attn_head_ok(HD)) return -1;   // (qtts_attention's own rule, before the cache writes)
+    if (ld_q < (prep ? NH + 2 * KV : NH) * HD) return -1;
+    if (kv_dtype == 1 && win != 0) return -1;   // (as qtts_attention: no bf16 window path)
+    hipStream_t st = (hipStream_t)stream;
+    CKI(attn_ints_ok("qtts_hip_attn_cached", "position", pos, rows, S, st));
+    CKI(attn_ints_ok("qtts_hip_attn_cached", "slot", row_b, rows, slots, st));
+    AttnArgs t;
+    t.mode = 1; t.qkv = q; t.ld_qkv = ld_q; t.qn_w = qn_w; t.kn_w = kn_w; t.eps = eps;
+    t.rope_cos = rope_cos; t.rope_sin = rope_sin;
+    t.kc = (float *)kc; t.vc = (float *)vc; t.S = S; t.kv_dtype = kv_dtype;
+    t.pos = pos; t.row_b = row_b; t.NH = NH; t.KV = KV; t.HD = HD; t.out = out; t.ld_out = NH * HD; t.nrows = rows;
+    t.win = win;
+    int rc = prep ? qtts_qk_prep(t, st) : 0;
+    if (!rc) rc = qtts_attention(t, st);
+    if (hipStreamSynchronize(st) != hipSuccess) rc = -1;
+    return rc;
+}
+
+// The sub-talker's attention + O projection by kv head (k_attn_o) on its own:
+// fp32 caches [rows][S][KV*HD], no id table; part [KV][rows][R].  1 = a shape
+// qtts_attn_o_covers refuses.
+extern "C" int qtts_hip_attn_o(float *part, const float *qkv, float *kc, float *vc, const float *qn_w,
+                               const float *kn_w, const float *rope_cos, const float *rope_sin, const int *pos,
+                               const uint16_t *Wo, int R, int NH, int KV, int HD, int S, int rows, float eps,
+                               void *stream) {
+    if (!part || !qkv || !kc || !vc || !qn_w || !kn_w || !rope_cos || !rope_sin || !pos || !Wo) return -1;
+    if (!attn_dims_ok(NH, KV, HD, S, rows, 0) || R < 1) return -1;
+    AttnArgs t;
+    t.mode = 0; t.qkv = qkv; t.ld_qkv = (NH + 2 * KV) * HD; t.qn_w = qn_w; t.kn_w = kn_w; t.eps = eps;
+    t.rope_cos = rope_cos; t.rope_sin = rope_sin; t.kc = kc; t.vc = vc; t.S = S;
+    t.pos = pos; t.NH = NH; t.KV = KV; t.HD = HD; t.ld_out = NH * HD; t.nrows = rows;
+    if (!qtts_attn_o_covers(t, Wo)) return 1;
+    hipStream_t st = (hipStream_t)stream;
+    CKI(attn_ints_ok("qtts_hip_attn_o", "position", pos, rows, S, st));
+    int rc = qtts_attn_o(t, Wo, R, part, st);
+    if (hipStreamSynchronize(st) != hipSuccess) rc = -1;
     return rc;
 }
 

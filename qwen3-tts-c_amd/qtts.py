@@ -91,6 +91,7 @@ EXPORTS = [
     "qtts_dev_retire", "qtts_dev_frame_stops", "qtts_dev_move_slot", "qtts_dev_set_rows", "qtts_hip_tengine_layers",
     "qwen_tts_set_kv_cache_dtype", "qwen_tts_kv_cache_dtype", "qtts_dev_set_kv_dtype", "qtts_dev_kv_dtype",
     "qtts_dev_get_kv", "qtts_dev_get_attn", "qtts_hip_attn_decode",
+    "qtts_hip_attn_decode_ex", "qtts_hip_attn_cached", "qtts_hip_attn_o",
 ]
 
 KV_F32, KV_BF16 = 0, 1   # QWEN_TTS_KV_F32 / QWEN_TTS_KV_BF16
@@ -239,6 +240,12 @@ def lib():
     L.qtts_hip_expf_glibc.argtypes = [vp, vp, C.c_int, vp]
     L.qtts_hip_attn_decode.restype = C.c_int
     L.qtts_hip_attn_decode.argtypes = [vp] * 9 + [C.c_int] * 5 + [C.c_float, C.c_int, vp]
+    L.qtts_hip_attn_decode_ex.restype = C.c_int
+    L.qtts_hip_attn_decode_ex.argtypes = [vp] * 9 + [C.c_int] * 5 + [C.c_float, C.c_int, vp, vp]
+    L.qtts_hip_attn_cached.restype = C.c_int
+    L.qtts_hip_attn_cached.argtypes = [vp, vp, C.c_int] + [vp] * 8 + [C.c_int] * 6 + [C.c_float] + [C.c_int] * 3 + [vp]
+    L.qtts_hip_attn_o.restype = C.c_int
+    L.qtts_hip_attn_o.argtypes = [vp] * 10 + [C.c_int] * 6 + [C.c_float, vp]
     _LIB = L
     return L
 
@@ -709,3 +716,35 @@ class Kernels:
         _ok(lib().qtts_hip_attn_decode(_ptr(out), _ptr(qkv), _ptr(kc), _ptr(vc), _ptr(qn_w), _ptr(kn_w),
                                        _ptr(rope_cos), _ptr(rope_sin), _ptr(pos_i32), NH, KV, HD, S, rows, eps,
                                        kv_dtype, _stream()), "attn_decode")
+
+    @staticmethod
+    def attn_decode_ex(out, qkv, kc, vc, qn_w, kn_w, rope_cos, rope_sin, pos_i32, NH, KV, HD, S, rows, eps,
+                       kv_dtype=0, skip_i32=None):
+        """attn_decode with per-row skip flags (qtts_hip_attn_decode_ex): a
+        flagged row stores no k / v, its output is computed all the same."""
+        _ok(lib().qtts_hip_attn_decode_ex(_ptr(out), _ptr(qkv), _ptr(kc), _ptr(vc), _ptr(qn_w), _ptr(kn_w),
+                                          _ptr(rope_cos), _ptr(rope_sin), _ptr(pos_i32), NH, KV, HD, S, rows, eps,
+                                          kv_dtype, _ptr(skip_i32), _stream()), "attn_decode_ex")
+
+    @staticmethod
+    def attn_cached(out, q, ld_q, kc, vc, qn_w, kn_w, rope_cos, rope_sin, row_b_i32, pos_i32, NH, KV, HD, S, slots,
+                    rows, eps, win=0, kv_dtype=0, prep=0):
+        """The cached attention (qtts_hip_attn_cached): kc / vc [slots, S,
+        KV * HD]; prep 1 runs the prefill's q / k norm + RoPE + cache write on
+        fused q|k|v rows first (q rewritten in place), prep 0 takes q and the
+        caches as they are; win > 0 is the sliding window."""
+        _ok(lib().qtts_hip_attn_cached(_ptr(out), _ptr(q), ld_q, _ptr(kc), _ptr(vc), _ptr(qn_w), _ptr(kn_w),
+                                       _ptr(rope_cos), _ptr(rope_sin), _ptr(row_b_i32), _ptr(pos_i32), NH, KV, HD, S,
+                                       slots, rows, eps, win, kv_dtype, prep, _stream()), "attn_cached")
+
+    @staticmethod
+    def attn_o(part, qkv, kc, vc, qn_w, kn_w, rope_cos, rope_sin, pos_i32, Wo_u16, R, NH, KV, HD, S, rows, eps):
+        """The sub-talker's attention + O projection by kv head
+        (qtts_hip_attn_o): part [KV, rows, R].  False where the kernel does
+        not cover the shape (nothing ran)."""
+        rc = lib().qtts_hip_attn_o(_ptr(part), _ptr(qkv), _ptr(kc), _ptr(vc), _ptr(qn_w), _ptr(kn_w), _ptr(rope_cos),
+                                   _ptr(rope_sin), _ptr(pos_i32), _ptr(Wo_u16), R, NH, KV, HD, S, rows, eps, _stream())
+        if rc == 1:
+            return False
+        _ok(rc, "attn_o")
+        return True

@@ -24,23 +24,10 @@ from oracle_py import DEFAULT, GREEDY
 from synth_model import prompt_ids
 
 import qtts
+from attn_ref import EPS, rne_bf16, widen   # (the shared attention test helpers)
+from attn_ref import rope_tables as _rope
 
 pytestmark = pytest.mark.gpu
-
-EPS = 1e-6
-THETA = 1000000.0
-
-
-# ------------------------------------------------------------------ bf16 in numpy
-def rne_bf16(x):
-    """fp32 -> bf16 bit patterns (uint16), round to nearest even -- the rule the
-    cache writers state, restated here"""
-    u = np.ascontiguousarray(x, np.float32).view(np.uint32).astype(np.uint64)
-    return ((u + 0x7FFF + ((u >> 16) & 1)) >> 16).astype(np.uint16)
-
-
-def widen(bits):
-    return (np.ascontiguousarray(bits, np.uint16).astype(np.uint32) << 16).view(np.float32)
 
 
 def test_rne_helper_rounds_ties_to_even():
@@ -59,14 +46,6 @@ SHAPES = [(4, 2, 128, S_BIG), (4, 2, 64, S_BIG), (4, 2, 32, S_BIG), (4, 2, 16, S
 # one split, the 32- / 128- / 256-key split boundaries on both sides, more than
 # 8 splits of 32, and the last position of the S = 320 cache
 POSITIONS = [0, 1, 31, 32, 33, 63, 64, 65, 127, 128, 129, 255, 256, 257, 300, 319]
-
-
-def _rope(S, HD):
-    half = HD // 2
-    freq = (1.0 / np.power(np.float32(THETA), (2 * np.arange(half, dtype=np.float32)) / np.float32(HD))).astype(np.float32)
-    ang = np.arange(S, dtype=np.float32)[:, None] * freq[None, :]
-    c, s = np.cos(ang).astype(np.float32), np.sin(ang).astype(np.float32)
-    return np.concatenate([c, c], 1), np.concatenate([s, s], 1)
 
 
 class Case:
