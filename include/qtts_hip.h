@@ -172,6 +172,40 @@ int qtts_dev_move_slot(qtts_dev_t *dev, int from, int to);
 int qtts_dev_set_rows(qtts_dev_t *dev, int rows);
 /* Copies slot b's codes [n_gen][G] to host. */
 int qtts_dev_get_codes(qtts_dev_t *dev, int b, int *host_codes, int max_frames);
+/* ---- teacher forcing, the free-draw record and logit taps (no c/
+ * counterpart: the reference only samples and continues) ----
+ * All of it lasts for one run: armed after qtts_dev_begin and before frame 0,
+ * cleared (with its buffers: a plain run allocates none) by the next
+ * qtts_dev_begin; the results stay readable until then.  An armed run's frames
+ * are graphs of their own with the forced sampler; the next unarmed run
+ * captures the plain ones again.  While armed, qtts_dev_refill, _move_slot and
+ * _set_rows return -1 (forcing is not defined for the work queue).  Every
+ * failure below returns -1 with a message and launches nothing. */
+/* Forced codes of slot b: codes[n_frames][G], an entry < 0 leaves that draw
+ * free, frames >= n_frames are free.  At draw (f, g) the sampler runs as it
+ * always does -- suppression, repetition penalty, the fixed-mode EOS redraw,
+ * every RNG advance -- and a forced entry then replaces its result: the stored
+ * code, the repetition counts, n_gen, the sub-talker's next input, the next
+ * talker embedding and the stop all follow the replaced id (a forced EOS
+ * stops the slot; a forced non-EOS continues where the free draw was EOS).
+ * n_frames in [0, max_frames]; group-0 ids in [0, V - 1024) or EOS, the other
+ * groups' in [0, Vs). */
+int qtts_dev_force(qtts_dev_t *dev, int b, const int *codes, int n_frames);
+/* Arms one logit tap at draw (frame, group) of slot b; at most 8 per run.
+ * Returns the tap's index (arming order). */
+int qtts_dev_tap(qtts_dev_t *dev, int b, int frame, int group);
+/* Slot b's free-draw record of an armed run: the id the sampler itself
+ * produced at every draw, [frames][G], -1 where no draw happened (after a
+ * stop, the groups after a forced EOS).  Copies up to max_frames rows (the run
+ * holds max_frames + 1 of them) and returns the rows copied; waits for the
+ * context stream.  -1 when the last run was not armed. */
+int qtts_dev_get_drawn(qtts_dev_t *dev, int b, int *host, int max_frames);
+/* Tap i: the values its draw saw -- group 0 after suppression and repetition
+ * penalty, before the temperature division and untouched by the EOS redraw;
+ * groups >= 1 the raw head output; the n real entries, up to max_n copied --
+ * the RNG state before the draw and the free-drawn id (any of the three may be
+ * NULL).  Returns n, or -1 if the draw never happened. */
+int qtts_dev_get_tap(qtts_dev_t *dev, int i, float *logits_host, int max_n, unsigned *rng_bits, int *drawn);
 /* Codec decode of slot b's generated codes (device-resident) into a malloc'd
  * host buffer of T*1920 samples (caller frees). */
 float *qtts_dev_codec_slot(qtts_dev_t *dev, int b, int T, int *out_samples);

@@ -190,6 +190,7 @@ typedef struct {
     long long queue_slot_frames_used; /* sum of frames generated */
     long long queue_rows_launched;    /* sum over launched frames of the slot rows they ran (the tail launches
                                          only the running slots): occupancy = frames_used / rows_launched */
+    void *force;                 /* forced codes / taps armed for the next generation call (one-shot) */
 } qwen_tts_ctx_t;
 
 qwen_tts_ctx_t *qwen_tts_load(const char *model_dir);
@@ -337,6 +338,44 @@ int qwen_tts_last_codes(qwen_tts_ctx_t *ctx, int *codes, int max_frames);
 /* the same for slot `slot` of the last qwen_tts_generate_batch (slot 0 ==
  * qwen_tts_last_codes); -1 on a bad slot */
 int qwen_tts_last_codes_slot(qwen_tts_ctx_t *ctx, int slot, int *codes, int max_frames);
+/* Teacher-forced decode (no c/ counterpart: the reference only samples and
+ * continues).  Resume or extend an utterance from codes already at hand, pin
+ * its first frames, replay a recorded run, or ask what the model would have
+ * drawn under a given history.  Served by every generation call but
+ * qwen_tts_generate_queue (single, batch, stream, voice clone).
+ * qwen_tts_force_codes: slot `slot` of the next call continues on
+ *   codes[n_frames][num_code_groups]; an entry < 0 leaves that draw free, and
+ *   so are the frames >= n_frames.  Every draw still runs exactly as it would
+ *   (suppression, repetition penalty, the fixed-length EOS redraw, every RNG
+ *   advance); a forced entry then replaces its result, and the stored code,
+ *   the repetition counts, the sub-talker's and the talker's next inputs and
+ *   the stop follow the replaced id (a forced EOS stops the slot, a forced
+ *   non-EOS continues where the free draw was EOS).  Group-0 ids must lie in
+ *   [0, vocab - 1024) or be EOS, the other groups' in [0, sub-talker vocab).
+ * qwen_tts_tap_draw: records the sampler's inputs at draw (frame, group) of
+ *   `slot`; at most 8 per run; returns the tap's index.
+ * Arming is ONE-SHOT: the next generate* call consumes it whether it succeeds
+ * or not (qwen_tts_generate_queue refuses with -1 and disarms), so a ctx shared
+ * between callers cannot inherit it.  That call fails before launching when a
+ * slot is >= its batch size, more frames are forced than it generates
+ * (max_new_tokens / fixed_codec_tokens), or a tap lies past them.
+ * qwen_tts_last_drawn: the free-draw record of the last armed call -- the id
+ *   the sampler itself produced at every draw, [frames][num_code_groups], -1
+ *   where no draw happened (after a stop; the groups after a forced EOS).
+ *   With a reference run's codes forced this is a per-draw parity check under
+ *   the reference's own history.  Copies up to max_frames rows, returns the
+ *   rows copied; -1 when the last call was not armed.
+ * qwen_tts_tap_result: tap i's values -- group 0 after suppression and
+ *   repetition penalty, before the temperature division and untouched by the
+ *   EOS redraw; groups >= 1 the raw head output; up to max_n of the n real
+ *   entries -- the RNG state before the draw and the free-drawn id (each may be
+ *   NULL).  Returns n, or -1 if the draw never happened.
+ * Both stay readable until the next generation call.  Errors return -1 with a
+ * message on stderr. */
+int qwen_tts_force_codes(qwen_tts_ctx_t *ctx, int slot, const int *codes, int n_frames);
+int qwen_tts_tap_draw(qwen_tts_ctx_t *ctx, int slot, int frame, int group);
+int qwen_tts_last_drawn(qwen_tts_ctx_t *ctx, int slot, int *codes, int max_frames);
+int qwen_tts_tap_result(qwen_tts_ctx_t *ctx, int i, float *logits, int max_n, unsigned *rng_bits, int *drawn);
 /* Streaming generation (the reference has only a per-step
  * progress callback, c/qwen_tts.h:356): audio is decoded incrementally and
  * exactly (qtts_hip.h codec stream) and handed to `cb` as it is produced --

@@ -248,6 +248,25 @@ struct SampArgs {
 };
 int qtts_sample(const SampArgs &a, hipStream_t st);
 
+// Teacher forcing and logit taps: the extra pointers of the sampler's forced
+// form (qtts_sample_dev.h sample_row_forced).  `forced` and `drawn` have the
+// layout of SampArgs::codes ([b * codes_bstride + frame * G + g]); a forced
+// entry < 0 leaves the draw free, a drawn entry stays -1 where no draw
+// happened.  taps: {slot, frame, group} each, slot -1 unused; tap t's values
+// go to tap_logits + t * tap_ld (the n real entries), its {n, RNG state before
+// the draw, drawn id, 1} to tap_meta + 4 t.
+constexpr int QTTS_MAX_TAPS = 8;
+struct SampForce {
+    const int *forced = nullptr;
+    int *drawn = nullptr;
+    const int *taps = nullptr;
+    float *tap_logits = nullptr;
+    int *tap_meta = nullptr;
+    int tap_ld = 0;
+};
+// qtts_sample with the forced form of the same three launch families
+int qtts_sample_forced(const SampArgs &a, const SampForce &f, hipStream_t st);
+
 struct EmbedSumArgs {
     const int *codes = nullptr;
     int codes_bstride = 0, G = 16;

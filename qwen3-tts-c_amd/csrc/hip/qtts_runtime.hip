@@ -163,7 +163,22 @@ struct qtts_dev {
     // work queue, tail of a run: the talker-first frame graph over the first
     // nrun < nb slots (qtts_dev_set_rows), captured on first use
     hipGraphExec_t gNr[QTTS_MAX_SLOTS + 1] = {};
+    // what g0 / gN hold: -1 nothing valid, 0 no graphs (QTTS_HIP_NO_GRAPH),
+    // 1 the plain frame, 2 the frame with the forced sampler (f_armed); every
+    // arming and every qtts_dev_begin that drops one resets it to -1, so a
+    // graph of either kind is never replayed for the other
     int graph_key = -1;
+    // teacher forcing, the free-draw record and logit taps (qtts_dev_force /
+    // qtts_dev_tap): allocated by the first arming after a qtts_dev_begin,
+    // freed by the next begin -- a plain run holds none of it.  forced / drawn
+    // are laid out like `codes`; f_phase: 0 no run begun, 1 begun and no frame
+    // launched yet (arming is valid), 2 frames launched
+    int *f_forced = nullptr, *f_drawn = nullptr, *f_taps = nullptr, *f_tap_meta = nullptr;
+    float *f_tap_logits = nullptr;
+    int f_tap_ld = 0, f_ntaps = 0, f_phase = 0;
+    int f_run_frames = 0;   // max_frames of the last qtts_dev_begin (the state may hold more)
+    bool f_armed = false;
+    size_t f_bytes = 0;
     // EOS-mode lagged poll: the sampler mirrors each slot's stop into pinned
     // host memory; an event after every frame lets the host wait for frame
     // s - 1 while frame s is already queued (qtts_dev_frame_done)
@@ -274,7 +289,26 @@ static void drop_row_graphs(qtts_dev *dv) {
         if (g) { hipGraphExecDestroy(g); g = nullptr; }
 }
 
+// drops forcing and taps with their buffers (the frame graphs that hold the
+// pointers become invalid with them)
+static void free_force(qtts_dev *dv) {
+    if (!dv->f_armed) return;
+    hipStreamSynchronize(dv->st);
+    for (void *p : {(void *)dv->f_forced, (void *)dv->f_drawn, (void *)dv->f_taps, (void *)dv->f_tap_meta,
+                    (void *)dv->f_tap_logits})
+        if (p) hipFree(p);
+    dv->f_forced = dv->f_drawn = dv->f_taps = dv->f_tap_meta = nullptr;
+    dv->f_tap_logits = nullptr;
+    dv->f_tap_ld = dv->f_ntaps = 0;
+    dv->sbytes -= dv->f_bytes;
+    dv->f_bytes = 0;
+    dv->f_armed = false;
+    dv->graph_key = -1;
+}
+
 static void free_state(qtts_dev *dv) {
+    free_force(dv);
+    dv->f_phase = 0;
     if (dv->g0) { hipGraphExecDestroy(dv->g0); dv->g0 = nullptr; }
     if (dv->gN) { hipGraphExecDestroy(dv->gN); dv->gN = nullptr; }
     drop_row_graphs(dv);
@@ -1217,6 +1251,12 @@ static int talker_layers(qtts_dev *dv) {
 static int head_sample(qtts_dev *dv, const GemvArgs &a, const SampArgs &s, int kind) {
     CKI(pgemv(dv, a, kind));
     ProfScope ps(dv, PK_SAMPLE, 0);
+    if (dv->f_armed) {   // forcing or taps armed: the forced sampler (its own frame graphs, graph_key 2)
+        SampForce f;
+        f.forced = dv->f_forced; f.drawn = dv->f_drawn; f.taps = dv->f_taps;
+        f.tap_logits = dv->f_tap_logits; f.tap_meta = dv->f_tap_meta; f.tap_ld = dv->f_tap_ld;
+        return qtts_sample_forced(s, f, dv->st);
+    }
     return qtts_sample(s, dv->st);
 }
 
@@ -1459,7 +1499,8 @@ static int capture(qtts_dev *dv, bool with_talker, hipGraphExec_t *out) {
 // faster, also in EOS mode (4096-frame capacity, 65 splits): 31.0 / 31.3 vs
 // 31.1 / 30.5 audio-s/s (profiles/r03c_eos_ab.txt).
 static int ensure_graphs(qtts_dev *dv) {
-    if (dv->g0 && dv->gN && dv->graph_key == 1) return 0;
+    const int want = dv->f_armed ? 2 : 1;   // (the forced sampler's frame is another graph)
+    if (dv->g0 && dv->gN && dv->graph_key == want) return 0;
     if (dv->g0) { hipGraphExecDestroy(dv->g0); dv->g0 = nullptr; }
     if (dv->gN) { hipGraphExecDestroy(dv->gN); dv->gN = nullptr; }
     drop_row_graphs(dv);
@@ -1471,8 +1512,16 @@ static int ensure_graphs(qtts_dev *dv) {
     if (!rc) rc = capture(dv, true, &dv->gN);
     dv->nrun = nrun;
     CKI(rc);
-    dv->graph_key = 1;
+    dv->graph_key = want;
     return 0;
+}
+
+// forcing is defined for one utterance per slot: the work queue's slot
+// operations refuse while it is armed
+static bool force_refuses(const qtts_dev *dv, const char *what) {
+    if (!dv->f_armed) return false;
+    fprintf(stderr, "qtts: %s refused: forced codes / taps are armed (not defined for the work queue)\n", what);
+    return true;
 }
 
 static bool same_params(const qtts_gen_params_t &a, const qtts_gen_params_t &b) {
@@ -1483,6 +1532,8 @@ extern "C" int qtts_dev_begin(qtts_dev_t *dv, int nb, int max_frames, int max_pr
     if (!dv || nb < 1 || max_frames < 1) return -1;
     hipSetDevice(dv->device);
     CKI(join_prime(dv));   // a prime left pending by a run that pushed no frames
+    free_force(dv);        // forcing and taps last for one run (and their record until the next begins)
+    dv->f_run_frames = max_frames;
     if (max_prefill < 16) max_prefill = 16;
     // (another cache element type: new state, and with it new frame graphs)
     const bool realloc_ = nb != dv->nb || max_frames > dv->max_frames || max_prefill > dv->p_cap ||
@@ -1499,6 +1550,7 @@ extern "C" int qtts_dev_begin(qtts_dev_t *dv, int nb, int max_frames, int max_pr
     }
     dv->nrun = dv->nb;
     CKI(reset_counters(dv));
+    dv->f_phase = 1;
     return 0;
 }
 
@@ -1674,6 +1726,7 @@ extern "C" int qtts_dev_prefill(qtts_dev_t *dv) {
 // Everything is ordered on the context stream after the frames already queued.
 extern "C" int qtts_dev_refill(qtts_dev_t *dv, int b) {
     if (!dv || b < 0 || b >= dv->nb || dv->p_len_h[b] < 2) return -1;
+    if (force_refuses(dv, "qtts_dev_refill")) return -1;
     hipSetDevice(dv->device);
     const qtts_dims_t &d = dv->d;
     std::vector<int> last;
@@ -1706,7 +1759,7 @@ extern "C" int qtts_dev_retire(qtts_dev_t *dv, int b) {
 extern "C" int qtts_dev_frame_stops(qtts_dev_t *dv, int step, int *stopped) {
     if (!dv || !stopped || !dv->hstop) return -1;
     hipSetDevice(dv->device);
-    if (dv->graph_key == 1) CK(hipEventSynchronize(dv->fev[step & 1]));
+    if (dv->graph_key >= 1) CK(hipEventSynchronize(dv->fev[step & 1]));
     else CK(hipStreamSynchronize(dv->st));
     for (int b = 0; b < dv->nrun; ++b) stopped[b] = ((volatile int *)dv->hstop)[b] != 0;
     return 0;
@@ -1719,6 +1772,7 @@ extern "C" int qtts_dev_frame_stops(qtts_dev_t *dv, int step, int *stopped) {
 // writes either slot).
 extern "C" int qtts_dev_move_slot(qtts_dev_t *dv, int from, int to) {
     if (!dv || from < 0 || to < 0 || from >= dv->nb || to >= dv->nb || from == to) return -1;
+    if (force_refuses(dv, "qtts_dev_move_slot")) return -1;
     hipSetDevice(dv->device);
     const qtts_dims_t &d = dv->d;
     hipStream_t st = dv->st;
@@ -1756,6 +1810,7 @@ extern "C" int qtts_dev_move_slot(qtts_dev_t *dv, int from, int to) {
 // <= the slots of qtts_dev_begin; their own graph per row count).
 extern "C" int qtts_dev_set_rows(qtts_dev_t *dv, int rows) {
     if (!dv || rows < 1 || rows > dv->nb || (rows < dv->nb && rows > QTTS_MAX_SLOTS)) return -1;
+    if (force_refuses(dv, "qtts_dev_set_rows")) return -1;
     dv->nrun = rows;
     return 0;
 }
@@ -1773,6 +1828,7 @@ extern "C" int qtts_dev_frame(qtts_dev_t *dv, int step) {
     hipSetDevice(dv->device);
     CKI(ensure_graphs(dv));
     if (dv->nrun < dv->nb && step == 0) return -1;   // (frame 0 runs every slot)
+    dv->f_phase = 2;
     if (dv->graph_key == 0) return record_frame(dv, step > 0);
     hipGraphExec_t g = step == 0 ? dv->g0 : dv->gN;
     if (dv->nrun < dv->nb) {
@@ -1793,7 +1849,7 @@ extern "C" int qtts_dev_frame(qtts_dev_t *dv, int step) {
 extern "C" int qtts_dev_frame_done(qtts_dev_t *dv, int step, int *all_stopped) {
     if (!dv || !all_stopped || !dv->hstop) return -1;
     hipSetDevice(dv->device);
-    if (dv->graph_key == 1) CK(hipEventSynchronize(dv->fev[step & 1]));
+    if (dv->graph_key >= 1) CK(hipEventSynchronize(dv->fev[step & 1]));
     else CK(hipStreamSynchronize(dv->st));
     int all = 1;
     for (int b = 0; b < dv->nrun; ++b) all &= ((volatile int *)dv->hstop)[b] != 0;
@@ -1885,6 +1941,117 @@ extern "C" int qtts_dev_get_codes(qtts_dev_t *dv, int b, int *host_codes, int ma
                       hipMemcpyDeviceToHost, dv->st));
     CK(hipStreamSynchronize(dv->st));
     return n;
+}
+
+// ----------------------------------------------------------------- teacher forcing, taps
+// first arming after a qtts_dev_begin: the tables (everything free, nothing
+// drawn, no tap) and the tap buffers; the frame graphs are captured anew
+static int arm_force(qtts_dev *dv) {
+    if (dv->f_phase != 1) {
+        fprintf(stderr, "qtts: forced codes / taps are armed after qtts_dev_begin and before frame 0\n");
+        return -1;
+    }
+    if (dv->f_armed) return 0;
+    const qtts_dims_t &d = dv->d;
+    const size_t tab = (size_t)dv->nb * (dv->max_frames + 1) * d.G * sizeof(int);
+    const int ld = d.V > d.Vs ? d.V : d.Vs;
+    const size_t taps = QTTS_MAX_TAPS * 3 * sizeof(int), meta = QTTS_MAX_TAPS * 4 * sizeof(int);
+    const size_t lg = (size_t)QTTS_MAX_TAPS * ld * sizeof(float);
+    dv->f_armed = true;   // (free_force releases whatever was allocated if one of these fails)
+    CK(hipMalloc((void **)&dv->f_forced, tab));
+    CK(hipMalloc((void **)&dv->f_drawn, tab));
+    CK(hipMalloc((void **)&dv->f_taps, taps));
+    CK(hipMalloc((void **)&dv->f_tap_meta, meta));
+    CK(hipMalloc((void **)&dv->f_tap_logits, lg));
+    dv->f_bytes = 2 * tab + taps + meta + lg;
+    dv->sbytes += dv->f_bytes;
+    dv->f_tap_ld = ld;
+    dv->f_ntaps = 0;
+    CK(hipMemsetAsync(dv->f_forced, 0xFF, tab, dv->st));
+    CK(hipMemsetAsync(dv->f_drawn, 0xFF, tab, dv->st));
+    CK(hipMemsetAsync(dv->f_taps, 0xFF, taps, dv->st));
+    CK(hipMemsetAsync(dv->f_tap_meta, 0, meta, dv->st));
+    CK(hipMemsetAsync(dv->f_tap_logits, 0, lg, dv->st));
+    CK(hipStreamSynchronize(dv->st));
+    dv->graph_key = -1;
+    return 0;
+}
+
+extern "C" int qtts_dev_force(qtts_dev_t *dv, int b, const int *codes, int n_frames) {
+    if (!dv) return -1;
+    hipSetDevice(dv->device);
+    const qtts_dims_t &d = dv->d;
+    if (dv->f_phase != 1) return arm_force(dv);   // (refuses with its message)
+    if (b < 0 || b >= dv->nb) {
+        fprintf(stderr, "qtts_dev_force: slot %d out of range (%d slots)\n", b, dv->nb);
+        return -1;
+    }
+    if (n_frames < 0 || n_frames > dv->f_run_frames || (n_frames > 0 && !codes)) {
+        fprintf(stderr, "qtts_dev_force: %d frames outside [0, %d]\n", n_frames, dv->f_run_frames);
+        return -1;
+    }
+    std::vector<int> h((size_t)n_frames * d.G);
+    for (int f = 0; f < n_frames; ++f)
+        for (int g = 0; g < d.G; ++g) {
+            const int id = codes[(size_t)f * d.G + g];
+            const bool ok = id < 0 || (g == 0 ? (id < d.V - 1024 || id == d.eos_id) && id < d.V : id < d.Vs);
+            if (!ok) {
+                fprintf(stderr, "qtts_dev_force: id %d at frame %d, group %d out of range\n", id, f, g);
+                return -1;
+            }
+            h[(size_t)f * d.G + g] = id < 0 ? -1 : id;
+        }
+    CKI(arm_force(dv));
+    // (a slot armed again: the later call replaces the earlier one)
+    int *row = dv->f_forced + (size_t)b * (dv->max_frames + 1) * d.G;
+    CK(hipMemset(row, 0xFF, (size_t)(dv->max_frames + 1) * d.G * sizeof(int)));
+    if (n_frames > 0) CK(hipMemcpy(row, h.data(), h.size() * sizeof(int), hipMemcpyHostToDevice));
+    return 0;
+}
+
+extern "C" int qtts_dev_tap(qtts_dev_t *dv, int b, int frame, int group) {
+    if (!dv) return -1;
+    hipSetDevice(dv->device);
+    if (dv->f_phase != 1) return arm_force(dv);   // (refuses with its message)
+    if (b < 0 || b >= dv->nb || frame < 0 || frame >= dv->f_run_frames || group < 0 || group >= dv->d.G) {
+        fprintf(stderr, "qtts_dev_tap: (slot %d, frame %d, group %d) out of range\n", b, frame, group);
+        return -1;
+    }
+    if (dv->f_armed && dv->f_ntaps >= QTTS_MAX_TAPS) {
+        fprintf(stderr, "qtts_dev_tap: at most %d taps per run\n", QTTS_MAX_TAPS);
+        return -1;
+    }
+    CKI(arm_force(dv));
+    const int t[3] = {b, frame, group};
+    CK(hipMemcpy(dv->f_taps + 3 * dv->f_ntaps, t, sizeof t, hipMemcpyHostToDevice));
+    return dv->f_ntaps++;
+}
+
+extern "C" int qtts_dev_get_drawn(qtts_dev_t *dv, int b, int *host, int max_frames) {
+    if (!dv || !dv->f_armed || b < 0 || b >= dv->nb || !host || max_frames < 0) return -1;
+    hipSetDevice(dv->device);
+    const int n = max_frames < dv->max_frames + 1 ? max_frames : dv->max_frames + 1;
+    CK(hipStreamSynchronize(dv->st));
+    if (n > 0)
+        CK(hipMemcpy(host, dv->f_drawn + (size_t)b * (dv->max_frames + 1) * dv->d.G, (size_t)n * dv->d.G * sizeof(int),
+                     hipMemcpyDeviceToHost));
+    return n;
+}
+
+extern "C" int qtts_dev_get_tap(qtts_dev_t *dv, int i, float *logits_host, int max_n, unsigned *rng_bits, int *drawn) {
+    if (!dv || !dv->f_armed || i < 0 || i >= dv->f_ntaps) return -1;
+    hipSetDevice(dv->device);
+    CK(hipStreamSynchronize(dv->st));
+    int m[4] = {0, 0, 0, 0};
+    CK(hipMemcpy(m, dv->f_tap_meta + 4 * i, sizeof m, hipMemcpyDeviceToHost));
+    if (!m[3]) return -1;   // the draw never happened (the slot had stopped, or the run ended before it)
+    if (rng_bits) *rng_bits = (unsigned)m[1];
+    if (drawn) *drawn = m[2];
+    const int n = m[0] < max_n ? m[0] : max_n;
+    if (logits_host && n > 0)
+        CK(hipMemcpy(logits_host, dv->f_tap_logits + (size_t)i * dv->f_tap_ld, (size_t)n * sizeof(float),
+                     hipMemcpyDeviceToHost));
+    return m[0];
 }
 
 extern "C" float *qtts_dev_codec_slot(qtts_dev_t *dv, int b, int T, int *out_samples) {

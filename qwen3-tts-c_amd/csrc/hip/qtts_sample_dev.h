@@ -942,10 +942,21 @@ __host__ __device__ inline bool fast_path(const SampArgs &a) {
 // The row's input pointers come as parameters (a.logits, a.stopped, the RNG
 // state array of the mode, a.n_gen, a.counts) so that k_sample_w can take
 // them as preloaded kernel arguments.
-template <bool FAST_ONLY, int EM = EMAX, int NT = 256>
+//
+// FORCE (teacher forcing, qtts_kernels.h SampForce): the draw itself runs as
+// above -- suppression, penalty, the EOS redraw and every RNG advance -- and
+// only then (a) a tapped draw stores the values it saw (x[]: group 0 after
+// suppression and penalty, before the temperature division and untouched by
+// the EOS redraw; groups >= 1 the raw head output), the RNG state it started
+// from and its id, (b) the id goes to the free-draw record, and (c) a forced
+// entry >= 0 replaces it, so that the stored code, the counts, n_gen / cur_row
+// / out_tok and the stop all follow the replaced id.  A forced EOS stops the
+// slot in either length mode.  All of it after the draw, from registers: no
+// global read is added in front of it.
+template <bool FAST_ONLY, int EM = EMAX, int NT = 256, bool FORCE = false>
 __device__ __forceinline__ void sample_row(const SampArgs &a, int b, unsigned char *smraw, const float *logits,
                                            const int *stopped_p, const uint32_t *rng_p, const int *ngen_p,
-                                           const int *counts_p) {
+                                           const int *counts_p, const SampForce *f = nullptr) {
 #pragma clang fp contract(off)
     static_assert(NT == 256 || FAST_ONLY, "the full path runs on 256 threads");
     KSmem &U = *reinterpret_cast<KSmem *>(smraw);
@@ -984,6 +995,7 @@ __device__ __forceinline__ void sample_row(const SampArgs &a, int b, unsigned ch
     asm volatile("" :: "v"(stopped), "v"(ng), "v"(rng));
     if (!stopped_p) stopped = 0;
     if (a.mode != 1) ng = 0;
+    const uint32_t rng0 = rng;   // (FORCE: the state a tapped draw started from)
 #pragma unroll
     for (int j = 0; j < EM; ++j) {
         const bool ok = j < E && i0 + j < n;
@@ -1038,10 +1050,34 @@ __device__ __forceinline__ void sample_row(const SampArgs &a, int b, unsigned ch
             tok = sample_any(sm, n, a.top_k, a.top_p, a.temp, rng);
         }
     }
+    bool fstop = false;   // FORCE: a forced EOS
+    if constexpr (FORCE) {
+        const int fr = a.mode == 1 ? ng : a.cur_row[b];
+        const int fg = a.mode == 1 ? 0 : a.g;
+        for (int t = 0; t < QTTS_MAX_TAPS; ++t) {
+            const int *tp = f->taps + 3 * t;
+            if (tp[0] != b || tp[1] != fr || tp[2] != fg) continue;
+            float *dst = f->tap_logits + (size_t)t * f->tap_ld;
+#pragma unroll
+            for (int j = 0; j < EM; ++j)
+                if (j < E && i0 + j < n) dst[i0 + j] = x[j];
+            if (tid == 0) {
+                int *m = f->tap_meta + 4 * t;
+                m[0] = n; m[1] = (int)rng0; m[2] = tok; m[3] = 1;
+            }
+        }
+        if (tid == 0) {
+            const size_t at = (size_t)b * a.codes_bstride + (size_t)fr * a.G + fg;
+            f->drawn[at] = tok;
+            const int fe = f->forced[at];
+            if (fe >= 0) tok = fe;
+            fstop = a.mode == 1 && tok == a.eos;
+        }
+    }
     if (tid == 0) {
         if (a.mode == 1) {
             a.rng[b] = rng;
-            if (a.fixed == 0 && tok == a.eos) {
+            if ((a.fixed == 0 && tok == a.eos) || fstop) {
                 a.stopped[b] = 1;
                 if (a.host_stopped) a.host_stopped[b] = 1;   // the host's lagged poll (qtts_dev_frame_done)
                 if (a.stop_step) a.stop_step[b] = ng;
@@ -1055,7 +1091,7 @@ __device__ __forceinline__ void sample_row(const SampArgs &a, int b, unsigned ch
             // the sub-talker's table readers take this id (pass 1) and keep it
             // for a stopped row (its samplers return early): EOS (>= Vs) would
             // index past the last pass's table, so a stop leaves id 0
-            if (a.out_tok) a.out_tok[b] = (a.fixed == 0 && tok == a.eos) ? 0 : tok;
+            if (a.out_tok) a.out_tok[b] = ((a.fixed == 0 && tok == a.eos) || fstop) ? 0 : tok;
         } else {
             a.st_rng[b] = rng;
             if (a.codes) a.codes[(size_t)b * a.codes_bstride + (size_t)a.cur_row[b] * a.G + a.g] = tok;

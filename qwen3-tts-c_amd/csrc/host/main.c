@@ -12,7 +12,9 @@
  * one lock-step batch; the first one's audio is written), --stream N (exact
  * streaming decode: audio delivered after frame 0 and then every N frames;
  * prints "First packet: X ms"), --kv-cache fp32|bf16 (talker KV cache
- * elements, qwen_tts_set_kv_cache_dtype).
+ * elements, qwen_tts_set_kv_cache_dtype), --force-codes FILE / --dump-drawn
+ * FILE (teacher-forced decode and its free-draw record, qwen_tts_force_codes /
+ * qwen_tts_last_drawn).
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -46,6 +48,10 @@ static void usage(const char *prog) {
             "  --stream N (streaming decode, audio chunks every N frames after the first)\n"
             "  --kv-cache fp32|bf16 (talker KV cache elements, default fp32; bf16 halves the cache,\n"
             "                      codes then no longer bit-exact against the reference)\n"
+            "  --force-codes <file>  continue on these codes, 16 ints per frame as --ref-codes reads them\n"
+            "                      (-1: leave that draw free; later frames are free), qwen_tts_force_codes\n"
+            "  --dump-drawn <file> write the id the sampler itself drew at every draw in that format\n"
+            "                      (-1: no draw happened), qwen_tts_last_drawn\n"
             "voice clone (include/qwen_tts.h qwen_tts_generate_voice_clone[_audio]):\n"
             "  --ref-audio <wav>   reference audio (mono/stereo PCM16 or float WAV; other rates are resampled\n"
             "                      to 24 kHz): encoded on the GPU (12 Hz codes + speaker x-vector)\n"
@@ -173,6 +179,7 @@ int main(int argc, char **argv) {
     int kv_cache = -1;   /* --kv-cache: -1 = the library's default ($QTTS_HIP_KV or fp32) */
     const char *ref_codes_file = NULL, *ref_text = NULL, *xvec_file = NULL, *text = NULL, *ref_audio = NULL;
     int print_ids = 0, xvec_only = 0;
+    const char *force_file = NULL, *drawn_file = NULL;
     float temp = -1, st_temp = -1, top_p = -1, st_top_p = -1, rep = -1;
     int top_k = -1, st_top_k = -1, max_tokens = -1, fixed = -1, seed = -1;
     for (int i = 1; i < argc; i++) {
@@ -210,6 +217,8 @@ int main(int argc, char **argv) {
             else { fprintf(stderr, "Error: --kv-cache takes fp32 or bf16\n\n"); usage(argv[0]); return 1; }
         }
         else if (ARG("--ref-codes")) ref_codes_file = argv[++i];
+        else if (ARG("--force-codes")) force_file = argv[++i];
+        else if (ARG("--dump-drawn")) drawn_file = argv[++i];
         else if (ARG("--ref-text")) ref_text = argv[++i];
         else if (ARG("--xvector")) xvec_file = argv[++i];
         else if (ARG("--ref-audio")) ref_audio = argv[++i];
@@ -251,6 +260,21 @@ int main(int argc, char **argv) {
     if (ids_file) {
         if (!(file_ids = read_ids_file(ids_file))) return 1;
         ids = file_ids;
+    }
+    /* forced codes: read and checked before the model loads */
+    int *force_codes = NULL, n_force = 0;
+    if (force_file) {
+        int n = 0;
+        double *v = read_numbers(force_file, &n);
+        if (!v || n < 16 || n % 16) {
+            fprintf(stderr, "Error: --force-codes needs 16 ints per frame (%d numbers read)\n", v ? n : 0);
+            free(v); free(file_ids);
+            return 1;
+        }
+        n_force = n / 16;
+        force_codes = (int *)malloc((size_t)n * sizeof(int));
+        for (int i = 0; i < n; i++) force_codes[i] = (int)v[i];
+        free(v);
     }
     /* voice clone inputs */
     int *ref_codes = NULL, n_ref = 0;
@@ -365,6 +389,11 @@ int main(int argc, char **argv) {
         float *ra = NULL;
         int rn = 0;
         long total_samples = 0;
+        /* (one-shot: armed again for every run; zero frames arm the record alone) */
+        if ((force_file || drawn_file) && qwen_tts_force_codes(ctx, 0, force_codes, n_force) != 0) {
+            rc = 1;
+            break;
+        }
         if (ref_wav) {
             ra = qwen_tts_generate_voice_clone_audio(ctx, ids, xvec_only ? NULL : ref_text, ref_wav, n_ref_wav, lang,
                                                      xvec_only, non_streaming, &rn);
@@ -432,8 +461,32 @@ int main(int argc, char **argv) {
             }
         }
     }
+    if (rc == 0 && drawn_file) {
+        const int G = ctx->config.num_code_groups;
+        const int cap = (ctx->fixed_codec_tokens > 0 ? ctx->fixed_codec_tokens : ctx->max_new_tokens) + 1;
+        int *d = (int *)malloc((size_t)cap * G * sizeof(int));
+        int rows = d ? qwen_tts_last_drawn(ctx, 0, d, cap) : -1;
+        FILE *f = rows >= 0 ? fopen(drawn_file, "w") : NULL;
+        if (!f) {
+            fprintf(stderr, "Error: cannot write the free-draw record to %s\n", drawn_file);
+            rc = 1;
+        } else {
+            while (rows > 0) {   /* rows after the last draw hold nothing */
+                int any = 0;
+                for (int g = 0; g < G; g++) any |= d[(size_t)(rows - 1) * G + g] >= 0;
+                if (any) break;
+                rows--;
+            }
+            for (int r = 0; r < rows; r++)
+                for (int g = 0; g < G; g++) fprintf(f, g + 1 < G ? "%d " : "%d\n", d[(size_t)r * G + g]);
+            fclose(f);
+            fprintf(stderr, "Wrote %s: %d frames of drawn ids\n", drawn_file, rows);
+        }
+        free(d);
+    }
     free(audio);
     qwen_tts_free(ctx);
+    free(force_codes);
     free(file_ids);
     free(ref_wav);
     free(ref_codes);

@@ -29,6 +29,8 @@
 
 int qwen_tts_verbose = 0;
 
+static void force_disarm(qwen_tts_ctx_t *ctx);   /* (teacher forcing and taps, before run_batch) */
+
 static double now_ms(void) {
     struct timespec ts;
     clock_gettime(CLOCK_MONOTONIC, &ts);
@@ -422,6 +424,7 @@ void qwen_tts_free(qwen_tts_ctx_t *ctx) {
     for (int i = 0; i < ctx->config.n_languages; i++) free(ctx->config.language_names[i]);
     free(ctx->config.language_names);
     free(ctx->config.language_ids);
+    force_disarm(ctx);
     free(ctx->last_codes);
     free(ctx->tk_x);
     queue_clear(ctx);
@@ -676,6 +679,133 @@ static void params_of(const qwen_tts_ctx_t *ctx, qtts_gen_params_t *p) {
     p->st_top_k = ctx->subtalker_top_k; p->fixed_codec_tokens = ctx->fixed_codec_tokens; p->seed = ctx->sample_seed;
 }
 
+/* ------------------------------------------------ teacher forcing and taps */
+/* What qwen_tts_force_codes / qwen_tts_tap_draw armed for the NEXT generation
+ * call (ctx->force).  One-shot: run_batch detaches it on entry, so the call
+ * consumes it whether it succeeds or not and a ctx shared between callers
+ * cannot inherit it; the public entries that can fail before run_batch drop it
+ * themselves (force_disarm). */
+#define FORCE_MAX_TAPS 8
+typedef struct {
+    int slot, n_frames;
+    int *codes;                  /* [n_frames][G], < 0 free */
+} force_slot_t;
+typedef struct {
+    int n_slots;
+    force_slot_t *slots;
+    int n_taps;
+    int taps[FORCE_MAX_TAPS][3]; /* slot, frame, group */
+} force_arm_t;
+
+static void force_free(force_arm_t *a) {
+    if (!a) return;
+    for (int i = 0; i < a->n_slots; i++) free(a->slots[i].codes);
+    free(a->slots);
+    free(a);
+}
+
+static void force_disarm(qwen_tts_ctx_t *ctx) {
+    force_free((force_arm_t *)ctx->force);
+    ctx->force = NULL;
+}
+
+static force_arm_t *force_pending(qwen_tts_ctx_t *ctx) {
+    if (!ctx->force) ctx->force = calloc(1, sizeof(force_arm_t));
+    return (force_arm_t *)ctx->force;
+}
+
+int qwen_tts_force_codes(qwen_tts_ctx_t *ctx, int slot, const int *codes, int n_frames) {
+    if (!ctx || !ctx->hip) return -1;
+    const qwen_tts_config_t *c = &ctx->config;
+    const int G = c->num_code_groups;
+    if (slot < 0 || n_frames < 0 || (n_frames > 0 && !codes)) {
+        fprintf(stderr, "Error: forced codes: bad slot %d or frame count %d\n", slot, n_frames);
+        return -1;
+    }
+    for (int f = 0; f < n_frames; f++)
+        for (int g = 0; g < G; g++) {
+            const int id = codes[(size_t)f * G + g];
+            const int ok = id < 0 || (g == 0 ? (id < c->talker_vocab_size - 1024 || id == c->codec_eos_id) &&
+                                                   id < c->talker_vocab_size
+                                             : id < c->subtalker_vocab_size);
+            if (!ok) {
+                fprintf(stderr, "Error: forced code %d at frame %d, group %d is out of range\n", id, f, g);
+                return -1;
+            }
+        }
+    force_arm_t *a = force_pending(ctx);
+    if (!a) return -1;
+    force_slot_t *fs = NULL;
+    for (int i = 0; i < a->n_slots; i++)
+        if (a->slots[i].slot == slot) fs = &a->slots[i];   /* armed again: the later call replaces */
+    if (!fs) {
+        force_slot_t *ns = (force_slot_t *)realloc(a->slots, (size_t)(a->n_slots + 1) * sizeof(force_slot_t));
+        if (!ns) return -1;
+        a->slots = ns;
+        fs = &a->slots[a->n_slots++];
+        fs->slot = slot;
+        fs->codes = NULL;
+    }
+    free(fs->codes);
+    fs->n_frames = n_frames;
+    fs->codes = (int *)malloc((size_t)(n_frames > 0 ? n_frames : 1) * G * sizeof(int));
+    if (!fs->codes) { fs->n_frames = 0; return -1; }
+    if (n_frames > 0) memcpy(fs->codes, codes, (size_t)n_frames * G * sizeof(int));
+    return 0;
+}
+
+int qwen_tts_tap_draw(qwen_tts_ctx_t *ctx, int slot, int frame, int group) {
+    if (!ctx || !ctx->hip) return -1;
+    if (slot < 0 || frame < 0 || group < 0 || group >= ctx->config.num_code_groups) {
+        fprintf(stderr, "Error: tap (slot %d, frame %d, group %d) is out of range\n", slot, frame, group);
+        return -1;
+    }
+    force_arm_t *a = force_pending(ctx);
+    if (!a) return -1;
+    if (a->n_taps >= FORCE_MAX_TAPS) {
+        fprintf(stderr, "Error: at most %d taps per run\n", FORCE_MAX_TAPS);
+        return -1;
+    }
+    a->taps[a->n_taps][0] = slot; a->taps[a->n_taps][1] = frame; a->taps[a->n_taps][2] = group;
+    return a->n_taps++;
+}
+
+/* Hands the arming to the device for a run of nb slots and max_tokens frames
+ * (after qtts_dev_begin, before anything launches).  A slot >= nb, more forced
+ * frames than max_tokens or a tap past them fails the call. */
+static int force_apply(qtts_dev_t *dev, const force_arm_t *a, int nb, int max_tokens) {
+    if (!a) return 0;
+    for (int i = 0; i < a->n_slots; i++) {
+        const force_slot_t *fs = &a->slots[i];
+        if (fs->slot >= nb || fs->n_frames > max_tokens) {
+            fprintf(stderr, "Error: forced codes for slot %d (%d frames) do not fit a run of %d slots, %d frames\n",
+                    fs->slot, fs->n_frames, nb, max_tokens);
+            return -1;
+        }
+    }
+    for (int i = 0; i < a->n_taps; i++)
+        if (a->taps[i][0] >= nb || a->taps[i][1] >= max_tokens) {
+            fprintf(stderr, "Error: tap (slot %d, frame %d) does not fit a run of %d slots, %d frames\n",
+                    a->taps[i][0], a->taps[i][1], nb, max_tokens);
+            return -1;
+        }
+    for (int i = 0; i < a->n_slots; i++)
+        if (qtts_dev_force(dev, a->slots[i].slot, a->slots[i].codes, a->slots[i].n_frames) != 0) return -1;
+    for (int i = 0; i < a->n_taps; i++)
+        if (qtts_dev_tap(dev, a->taps[i][0], a->taps[i][1], a->taps[i][2]) != i) return -1;
+    return 0;
+}
+
+int qwen_tts_last_drawn(qwen_tts_ctx_t *ctx, int slot, int *codes, int max_frames) {
+    if (!ctx || !ctx->hip || slot < 0 || !codes || max_frames < 0) return -1;
+    return qtts_dev_get_drawn((qtts_dev_t *)ctx->hip, slot, codes, max_frames);
+}
+
+int qwen_tts_tap_result(qwen_tts_ctx_t *ctx, int i, float *logits, int max_n, unsigned *rng_bits, int *drawn) {
+    if (!ctx || !ctx->hip) return -1;
+    return qtts_dev_get_tap((qtts_dev_t *)ctx->hip, i, logits, max_n, rng_bits, drawn);
+}
+
 /* ------------------------------------------------------------- generation */
 /* Runs nb utterances in lock-step frames.  Fills per-slot frame counts and
  * stop info; audio[i] decoded per slot.  Returns 0 on success. */
@@ -692,6 +822,8 @@ static int run_batch(qwen_tts_ctx_t *ctx, int nb, const char *const *texts, cons
     const qwen_tts_config_t *c = &ctx->config;
     const int G = c->num_code_groups;
     int rc = -1;
+    force_arm_t *arm = (force_arm_t *)ctx->force;   /* one-shot: this call consumes it, however it ends */
+    ctx->force = NULL;
     prompt_t *pr = (prompt_t *)calloc(nb, sizeof(prompt_t));
     int max_p = 0;
     for (int b = 0; b < nb; b++) {
@@ -721,6 +853,7 @@ static int run_batch(qwen_tts_ctx_t *ctx, int nb, const char *const *texts, cons
     qtts_gen_params_t gp;
     params_of(ctx, &gp);
     if (qtts_dev_begin(dev, nb, max_tokens, max_p, &gp) != 0) goto out;
+    if (force_apply(dev, arm, nb, max_tokens) != 0) goto out;
     for (int b = 0; b < nb; b++)
         if ((vcs && qtts_dev_prompt_ref(dev, vcs[b].ref_codes, vcs[b].ref_codes ? vcs[b].n_ref : 0, vcs[b].spk) != 0) ||
             qtts_dev_prompt(dev, b, pr[b].text, pr[b].n_text, pr[b].plan, pr[b].nplan, pr[b].p_len,
@@ -928,6 +1061,7 @@ static int run_batch(qwen_tts_ctx_t *ctx, int nb, const char *const *texts, cons
     ctx->perf_total_ms = now_ms() - t_start;
     free(stopped); free(ngen); free(sstep);
 out:
+    force_free(arm);
     for (int b = 0; b < nb; b++) { free(pr[b].text); free(pr[b].plan); }
     free(pr);
     return rc;
@@ -993,6 +1127,11 @@ static void queue_plan_slot(prompt_t *p, int b) {
 int qwen_tts_generate_queue(qwen_tts_ctx_t *ctx, int nq, const char *const *texts, const char *const *speakers,
                             const char *const *languages, int nb, qwen_tts_queue_next_cb next, void *user,
                             float **out_audio, int *out_samples) {
+    if (ctx && ctx->force) {   /* forcing is defined for one utterance per slot, not for the queue */
+        fprintf(stderr, "Error: qwen_tts_generate_queue: forced codes / taps are armed (not supported; disarmed)\n");
+        force_disarm(ctx);
+        return -1;
+    }
     if (!ctx || !ctx->hip || nq < 1 || nb < 1 || !texts || !out_audio || !out_samples) return -1;
     qtts_dev_t *dev = (qtts_dev_t *)ctx->hip;
     const qwen_tts_config_t *c = &ctx->config;
@@ -1225,6 +1364,7 @@ static int vclone_run(qwen_tts_ctx_t *ctx, int nb, const char *const *texts, con
         vc->n_ref = nref;
     }
     if (rc == 0) rc = run_batch(ctx, nb, texts, NULL, languages, out_audio, out_samples, now_ms(), stream, vcs);
+    else force_disarm(ctx);   /* (the call consumes an arming also when it fails before the run) */
     if (vcs)
         for (int b = 0; b < nb; b++) free((void *)vcs[b].ref_ids);
     free(vcs);
@@ -1329,18 +1469,21 @@ int qwen_tts_generate_voice_clone_audio_batch(qwen_tts_ctx_t *ctx, int nb, const
     if (!ctx || !ctx->hip || nb < 1 || nb > 16 || !texts || !ref_wavs || !n_ref_samples || !out_audio ||
         !out_samples) {
         fprintf(stderr, "Error: voice clone from audio needs 1..16 utterances with reference audio\n");
+        if (ctx) force_disarm(ctx);
         return -1;
     }
     for (int b = 0; b < nb; b++) { out_audio[b] = NULL; out_samples[b] = 0; }
     qtts_dev_t *dev = (qtts_dev_t *)ctx->hip;
     if ((qtts_dev_enc_available(dev) & 3) != 3) {
         fprintf(stderr, "Error: the model directory has no speaker encoder / 12 Hz encoder weights\n");
+        force_disarm(ctx);
         return -1;
     }
     for (int b = 0; b < nb; b++)
         if (!x_vector_only || !x_vector_only[b])
             if (!ref_texts || !ref_texts[b] || !ref_texts[b][0]) {
                 fprintf(stderr, "Error: ref_text is required when x_vector_only_mode=False (ICL mode). Bad index=%d\n", b);
+                force_disarm(ctx);
                 return -1;
             }
     double t0 = now_ms();
@@ -1371,6 +1514,8 @@ int qwen_tts_generate_voice_clone_audio_batch(qwen_tts_ctx_t *ctx, int nb, const
         if (!rt) rt = none;
         rc = qwen_tts_generate_voice_clone_batch(ctx, nb, texts, rt, rc_p, nr, sv, languages, non_streaming, out_audio,
                                                  out_samples);
+    } else {
+        force_disarm(ctx);
     }
     free(codes);
     free(xv);
@@ -1386,14 +1531,19 @@ float *qwen_tts_generate_voice_clone_audio_stream(qwen_tts_ctx_t *ctx, const cha
                                                   qwen_tts_audio_cb cb, void *userdata, int *out_samples) {
     if (!out_samples) return NULL;
     *out_samples = 0;
-    if (!ctx || !ctx->hip || !ref_wav || n_ref_samples <= 0) return NULL;
+    if (!ctx || !ctx->hip || !ref_wav || n_ref_samples <= 0) {
+        if (ctx) force_disarm(ctx);
+        return NULL;
+    }
     qtts_dev_t *dev = (qtts_dev_t *)ctx->hip;
     if ((qtts_dev_enc_available(dev) & 3) != 3) {
         fprintf(stderr, "Error: the model directory has no speaker encoder / 12 Hz encoder weights\n");
+        force_disarm(ctx);
         return NULL;
     }
     if (!x_vector_only && (!ref_text || !ref_text[0])) {
         fprintf(stderr, "Error: ref_text is required when x_vector_only_mode=False (ICL mode). Bad index=0\n");
+        force_disarm(ctx);
         return NULL;
     }
     const double t0 = now_ms();
@@ -1411,6 +1561,8 @@ float *qwen_tts_generate_voice_clone_audio_stream(qwen_tts_ctx_t *ctx, const cha
                                                      x_vector_only ? NULL : codes, x_vector_only ? 0 : fr, xv,
                                                      language, non_streaming, chunk_frames, cb, userdata, out_samples);
         if (audio && ctx->perf_first_packet_ms > 0) ctx->perf_first_packet_ms += enc_ms;
+    } else {
+        force_disarm(ctx);
     }
     free(codes);
     free(xv);

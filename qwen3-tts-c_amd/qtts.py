@@ -63,6 +63,7 @@ class Ctx(C.Structure):  # qwen_tts_ctx_t (include/qwen_tts.h)
         ("queue_n", C.c_int), ("queue_codes", C.POINTER(_ip)), ("queue_frames", _ip), ("queue_stop_reason", _ip),
         ("queue_slot", _ip), ("queue_slots", C.c_int), ("queue_frames_launched", C.c_int),
         ("queue_refills", C.c_int), ("queue_slot_frames_used", C.c_longlong), ("queue_rows_launched", C.c_longlong),
+        ("force", C.c_void_p),
     ]
 
 
@@ -92,7 +93,11 @@ EXPORTS = [
     "qwen_tts_set_kv_cache_dtype", "qwen_tts_kv_cache_dtype", "qtts_dev_set_kv_dtype", "qtts_dev_kv_dtype",
     "qtts_dev_get_kv", "qtts_dev_get_attn", "qtts_hip_attn_decode",
     "qtts_hip_attn_decode_ex", "qtts_hip_attn_cached", "qtts_hip_attn_o",
+    "qwen_tts_force_codes", "qwen_tts_tap_draw", "qwen_tts_last_drawn", "qwen_tts_tap_result",
+    "qtts_dev_force", "qtts_dev_tap", "qtts_dev_get_drawn", "qtts_dev_get_tap",
 ]
+
+MAX_TAPS = 8   # taps per run (qwen_tts_tap_draw)
 
 KV_F32, KV_BF16 = 0, 1   # QWEN_TTS_KV_F32 / QWEN_TTS_KV_BF16
 
@@ -226,6 +231,23 @@ def lib():
     L.qtts_dev_get_attn.argtypes = [C.c_void_p, _fp, _fp]
     L.qtts_dev_bytes.restype = C.c_size_t
     L.qtts_dev_bytes.argtypes = [C.c_void_p, C.c_int]
+    _up = C.POINTER(C.c_uint)
+    L.qwen_tts_force_codes.restype = C.c_int
+    L.qwen_tts_force_codes.argtypes = [C.POINTER(Ctx), C.c_int, _ip, C.c_int]
+    L.qwen_tts_tap_draw.restype = C.c_int
+    L.qwen_tts_tap_draw.argtypes = [C.POINTER(Ctx), C.c_int, C.c_int, C.c_int]
+    L.qwen_tts_last_drawn.restype = C.c_int
+    L.qwen_tts_last_drawn.argtypes = [C.POINTER(Ctx), C.c_int, _ip, C.c_int]
+    L.qwen_tts_tap_result.restype = C.c_int
+    L.qwen_tts_tap_result.argtypes = [C.POINTER(Ctx), C.c_int, _fp, C.c_int, _up, _ip]
+    L.qtts_dev_force.restype = C.c_int
+    L.qtts_dev_force.argtypes = [C.c_void_p, C.c_int, _ip, C.c_int]
+    L.qtts_dev_tap.restype = C.c_int
+    L.qtts_dev_tap.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
+    L.qtts_dev_get_drawn.restype = C.c_int
+    L.qtts_dev_get_drawn.argtypes = [C.c_void_p, C.c_int, _ip, C.c_int]
+    L.qtts_dev_get_tap.restype = C.c_int
+    L.qtts_dev_get_tap.argtypes = [C.c_void_p, C.c_int, _fp, C.c_int, _up, _ip]
     L.qtts_hip_device_count.restype = C.c_int
     L.qtts_hip_tengine_layers.restype = C.c_longlong
     vp = C.c_void_p
@@ -310,6 +332,50 @@ class QwenTTS:
     def state_bytes(self):
         """device bytes of the generation state (qtts_dev_bytes(dev, 1))"""
         return int(lib().qtts_dev_bytes(C.c_void_p(self.c.hip), 1))
+
+    # teacher forcing, the free-draw record and logit taps (include/qwen_tts.h).
+    # Arming is one-shot: the next generate* call consumes it.
+    def force_codes(self, codes, slot=0):
+        """Slot `slot` of the next generate* call continues on `codes`
+        [frames, groups] (an entry < 0 leaves that draw free, later frames are
+        free): every draw runs as always, a forced entry then replaces its
+        result.  ValueError when refused (an id out of range)."""
+        c = np.ascontiguousarray(codes, np.int32).reshape(-1, self.cfg.num_code_groups)
+        if lib().qwen_tts_force_codes(self.ctx, int(slot), c.ctypes.data_as(_ip), c.shape[0]) != 0:
+            raise ValueError("force_codes refused (see stderr)")
+
+    def tap_draw(self, frame, group, slot=0):
+        """Record the sampler's inputs at draw (frame, group) of `slot` in the
+        next generate* call; at most MAX_TAPS per run.  Returns the tap index."""
+        i = lib().qwen_tts_tap_draw(self.ctx, int(slot), int(frame), int(group))
+        if i < 0:
+            raise ValueError("tap_draw refused (see stderr)")
+        return i
+
+    def last_drawn(self, slot=0):
+        """The free-draw record of the last armed call for `slot`: the id the
+        sampler itself produced at every draw, int32 [frames, groups], -1 where
+        no draw happened; rows up to the last one with a draw.  None when the
+        last call was not armed."""
+        cap = max(int(self.c.max_new_tokens), int(self.c.fixed_codec_tokens), 1) + 1
+        buf = np.full((cap, self.cfg.num_code_groups), -1, np.int32)
+        k = lib().qwen_tts_last_drawn(self.ctx, int(slot), buf.ctypes.data_as(_ip), cap)
+        if k < 0:
+            return None
+        rows = np.nonzero((buf[:k] >= 0).any(axis=1))[0]
+        return buf[:rows[-1] + 1 if len(rows) else 0].copy()
+
+    def tap_result(self, i):
+        """Tap i of the last armed call: (logits float32 [n], rng_bits, drawn
+        id) -- the values the draw saw, the RNG state before it and the id the
+        sampler produced -- or None if that draw never happened."""
+        n = max(self.cfg.talker_vocab_size, self.cfg.subtalker_vocab_size)
+        buf = np.zeros(n, np.float32)
+        bits, tok = C.c_uint(0), C.c_int(0)
+        k = lib().qwen_tts_tap_result(self.ctx, int(i), buf.ctypes.data_as(_fp), n, C.byref(bits), C.byref(tok))
+        if k < 0:
+            return None
+        return buf[:k].copy(), int(bits.value), int(tok.value)
 
     def get_kv(self, layer, b, pos0, n):
         """(k, v) fp32 [n, kv_heads * head_dim]: talker cache rows [pos0, pos0 + n)
