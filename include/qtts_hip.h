@@ -370,12 +370,41 @@ int qtts_hip_attn_o(float *part_dev, const float *qkv_dev, float *kc_dev, float 
                     const float *rope_cos_dev, const float *rope_sin_dev, const int *pos_dev,
                     const uint16_t *Wo_dev, int R, int NH, int KV, int HD, int S, int rows, float eps,
                     void *stream);
+/* The pair form of k_attn_o: rows 0 and 1 of one slot at positions 0 and 1 in
+ * one launch.  qkv_dev [2][(NH + 2 KV) HD]; caches [S][KV*HD] (S >= 2), rows 0
+ * and 1 are written and no row is read: row 1 takes key 0's k / v from row 0
+ * as staged in the launch.  skip_dev (may be NULL): a nonzero skip_dev[0]
+ * keeps both rows from being stored.  part_dev[(g * 2 + r) * R + i] as
+ * qtts_hip_attn_o with rows = 2.  Returns 1 (nothing launched) for a shape the
+ * kernel does not cover (those of qtts_hip_attn_o, and S < 2). */
+int qtts_hip_attn_o_pair(float *part_dev, const float *qkv_dev, float *kc_dev, float *vc_dev,
+                         const float *qn_w_dev, const float *kn_w_dev,
+                         const float *rope_cos_dev, const float *rope_sin_dev, const int *skip_dev,
+                         const uint16_t *Wo_dev, int R, int NH, int KV, int HD, int S, float eps,
+                         void *stream);
+/* The wave-per-row GEMV of the sub-talker chain with the chain's prologue, on
+ * nrows = 1 (k_gemvw) or nrows = 2 (its pair form: one weight read for both x
+ * rows) rows: x_dev [nrows][cols]; part_dev [n_part][nrows][cols] (NULL: none)
+ * is summed in order and added to x; the sum goes to x_new_dev [nrows][cols]
+ * (NULL: not stored); w_dev NULL: no norm; epi as
+ * qtts_hip_resident_matvec_bf16; out_dev [nrows][rows] (epi 4: rows / 2).
+ * Returns 1 (nothing launched) where the kernel does not cover the shape:
+ * nrows 1 needs cols % 512 == 0 and rows % 1024 == 0; nrows 2 one of
+ * (rows, cols) = (4096 | 6144 | 1024 | 2048, 1024), (1024, 3072); partials
+ * need cols <= 1024. */
+int qtts_hip_resident_matvec_rows_bf16(float *out_dev, const uint16_t *A_dev, const float *x_dev, const float *w_dev,
+                                       float eps, int rows, int cols, int epi, const float *part_dev, int n_part,
+                                       float *x_new_dev, int nrows, void *stream);
 /* glibc-exact expf replica used by the sampler (for the libm cross-check test) */
 int qtts_hip_expf_glibc(float *out_dev, const float *in_dev, int n, void *stream);
 int qtts_hip_sync(void);
 /* Talker layers enqueued (or captured into a frame graph) on the persistent
  * one-launch layer (QTTS_HIP_TENGINE=1) since the library loaded. */
 long long qtts_hip_tengine_layers(void);
+/* Sub-talker pair passes enqueued (or captured into a frame graph) since the
+ * library loaded: positions 0 and 1 run as one two-row pass at batch 1
+ * (QTTS_HIP_ST_PAIR=0 at creation: the 16 single-row passes). */
+long long qtts_hip_st_pair_passes(void);
 
 /* Diagnostics: run ONE frame eagerly on the current generation state with an
  * event pair around every kernel launch on the context stream.  kind[i]:

@@ -215,6 +215,23 @@ int qtts_attn_o(const AttnArgs &a, const bf16_t *Wo, int R, float *part, hipStre
 // true when qtts_attn_o takes these arguments (it returns 1 otherwise)
 bool qtts_attn_o_covers(const AttnArgs &a, const bf16_t *Wo);
 
+// The sub-talker's positions 0 and 1 as one two-row pass at batch 1
+// (k_stpair.hip), each row bit-identical to the single-row launch:
+// the pair form of qtts_gemvw for the default-cache-policy shapes -- a.nb == 2,
+// x rows at a.x + b a.ldx, y rows at a.y + b a.ldy, partials row b of partial p
+// at a.xadd + p a.ld_xadd + b a.ldb_xadd, the new residual rows at a.xcopy +
+// b a.ldxc; epilogues STORE / RESID / SWIGLU; 1 = not covered
+bool qtts_gemvw_pair_covers(int R, int C, int epi);
+int qtts_gemvw_pair(const GemvArgs &a, hipStream_t st);
+// and of qtts_attn_o: rows 0 and 1 of slot 0 at positions 0 and 1 (a.pos
+// unset); row 0 is a.qkv, row 1 a.qkv + a.ld_qkv or, with a.qkv_tab, the
+// table's row a.tab_ids[a.tab_off]; a.kc / a.vc the slot's [S][KV HD] cache
+// (rows 0 and 1 written, none read); a.skip[0] keeps the cache write back;
+// a.xc_dst: row 1's input table row (xc_tab / xc_tab16, xc_n wide) copied
+// there; part [KV][2][R]; 1 = not covered
+bool qtts_attn_o_pair_covers(const AttnArgs &a, const bf16_t *Wo);
+int qtts_attn_o_pair(const AttnArgs &a, const bf16_t *Wo, int R, float *part, hipStream_t st);
+
 // Name of the kernel instantiation the last launcher on this thread chose
 // (diagnostics: per-kernel profile rows match rocprofv3's kernel names).
 extern thread_local const char *qtts_last_kernel;

@@ -212,6 +212,7 @@ struct qtts_dev {
     bool profiling = false;
     bool attn_o = true;      // QTTS_HIP_ATTN_O=0: sub-talker attention and O projection as two kernels
     bool tab0b = true;       // QTTS_HIP_TAB0B=0: batch layer-0 q|k|v by GEMV instead of the table
+    bool st_pair = true;     // QTTS_HIP_ST_PAIR=0: batch-1 sub-talker passes 0 and 1 as two single-row chains
     // QTTS_HIP_L2PF=<mask>: which edges of the batch-1 sub-talker chain carry
     // the next-launch weight prefetch (0 none): 1 q|k|v -> attention + O,
     // 2 attention + O -> gate|up, 4 gate|up -> down, 8 down -> next q|k|v or
@@ -523,6 +524,8 @@ extern "C" qtts_dev_t *qtts_dev_create(const qtts_dims_t *dims, int device) {
     }
     const char *tb = getenv("QTTS_HIP_TAB0B");
     dv->tab0b = !(tb && !atoi(tb));
+    const char *sp = getenv("QTTS_HIP_ST_PAIR");
+    dv->st_pair = !(sp && !atoi(sp));
     const char *pf = getenv("QTTS_HIP_L2PF");
     if (pf) dv->l2pf = atoi(pf);
     const char *pft = getenv("QTTS_HIP_L2PF_TK");
@@ -743,16 +746,18 @@ static int alloc_state(qtts_dev *dv, int nb, int max_frames, int max_prefill) {
     A(hbuf, float, B * d.I);
     A(logits, float, B * d.V);
     A(tk_hid, float, B * d.H);
-    A(x_st, float, B * d.Hs);
-    A(x_st2, float, B * d.Hs);
+    // (two rows at one slot: the batch-1 sub-talker runs positions 0 and 1 as a pair)
+    const size_t B2 = B < 2 ? 2 : B;
+    A(x_st, float, B2 * d.Hs);
+    A(x_st2, float, B2 * d.Hs);
     A(x_tk2, float, B * d.H);
     A(bpo, float, (size_t)4 * B * (d.H > d.Hs ? d.H : d.Hs));
     A(bpd, float, (size_t)4 * B * (d.H > d.Hs ? d.H : d.Hs));
     A(ppart, float, (size_t)4 * 16 * (d.H > d.Hs ? d.H : d.Hs));
-    A(opart, float, (size_t)B * ((size_t)d.KVs * d.Hs > (size_t)d.KV * d.H ? (size_t)d.KVs * d.Hs : (size_t)d.KV * d.H));
-    A(qkv_s, float, B * dv->QKVs());
+    A(opart, float, (size_t)B2 * ((size_t)d.KVs * d.Hs > (size_t)d.KV * d.H ? (size_t)d.KVs * d.Hs : (size_t)d.KV * d.H));
+    A(qkv_s, float, B2 * dv->QKVs());
     A(att_s, float, B * d.NHs * d.HDs);
-    A(h_s, float, B * d.Is);
+    A(h_s, float, B2 * d.Is);
     A(logits_s, float, B * d.Vs);
     {   // (bf16: half the elements' worth of floats; L B S KV HD is even -- HD is a multiple of 8)
         const size_t kv_floats = (size_t)d.L * B * dv->S * d.KV * d.HD * dv->kv_esz() / 4;
@@ -1287,6 +1292,123 @@ static int talker_head_sample(qtts_dev *dv) {
     return head_sample(dv, a, s, PK_GEMV_TALKER);
 }
 
+// Batch 1: passes 0 and 1 as one two-row pass (k_stpair.hip).  Pass 0's input
+// is the talker hidden and pass 1's the table row of the talker's draw
+// (last_tok, written by the talker's sampler before the sub-talker's first
+// launch), so both rows are known up front: positions 0 and 1 are a causal
+// two-token prefill, every matrix is read once for both, and per row the
+// arithmetic is the single-row kernels' (bit-identical codes).
+// pair passes enqueued (or captured) since the library loaded: a test's proof
+// that the pair path, not the 16-pass chain, ran
+static std::atomic<long long> g_st_pair_passes{0};
+extern "C" long long qtts_hip_st_pair_passes(void) { return g_st_pair_passes.load(); }
+
+static AttnArgs st_pair_attn_args(const qtts_dev *dv, int l) {
+    const qtts_dims_t &d = dv->d;
+    const int KVD = d.KVs * d.HDs;
+    const Layer &ly = dv->sl[l];
+    AttnArgs t;
+    t.mode = 0; t.qkv = dv->qkv_s; t.ld_qkv = dv->QKVs(); t.qn_w = ly.qn; t.kn_w = ly.kn; t.eps = d.eps;
+    t.rope_cos = dv->rope_cos_s; t.rope_sin = dv->rope_sin_s;
+    t.kc = dv->kcs + (size_t)l * dv->nb * d.G * KVD; t.vc = dv->vcs + (size_t)l * dv->nb * d.G * KVD; t.S = d.G;
+    t.pos = nullptr; t.pos_const = 0; t.NH = d.NHs; t.KV = d.KVs; t.HD = d.HDs; t.ld_out = d.NHs * d.HDs;
+    t.nrows = 2; t.skip = dv->stopped;
+    if (l == 0) {   // row 1: q|k|v from the load-time table by the talker's draw, its input row to the residual
+        const bool proj = dv->st_proj != nullptr;
+        t.qkv_tab = dv->qkv0_tab; t.tab_ids = dv->last_tok; t.tab_bstride = 1; t.tab_off = 0;
+        t.xc_tab = proj ? dv->codec_ptab : nullptr; t.xc_tab16 = proj ? nullptr : dv->codec_emb;
+        t.xc_dst = dv->x_st + d.Hs; t.xc_n = d.Hs;
+    }
+    return t;
+}
+// where today's fast path runs (fused attention + O, the layer-0 q|k|v table)
+// and the pair kernels cover every shape; everything else keeps the 16 passes
+static bool st_pair_ok(const qtts_dev *dv) {
+    const qtts_dims_t &d = dv->d;
+    if (!dv->st_pair || dv->nrun != 1 || !dv->attn_o || !dv->qkv0_tab || d.G < 2 || d.Ls < 1) return false;
+    if (dv->st_proj && !(dv->st_ptab && dv->codec_ptab)) return false;
+    if (!dv->st_proj && d.H != d.Hs) return false;
+    if (!qtts_gemvw_pair_covers(dv->QKVs(), d.Hs, EPI_STORE) || !qtts_gemvw_pair_covers(2 * d.Is, d.Hs, EPI_SWIGLU) ||
+        !qtts_gemvw_pair_covers(d.Hs, d.Is, EPI_RESID))
+        return false;
+    for (int l = 0; l < d.Ls; ++l)
+        if (!qtts_attn_o_pair_covers(st_pair_attn_args(dv, l), dv->sl[l].wo)) return false;
+    return true;
+}
+static int pgemv_pair(qtts_dev *dv, const GemvArgs &a) {
+    ProfScope ps(dv, PK_GEMV_SUB, gemv_bytes(a));
+    if (qtts_gemvw_pair(a, dv->st) != 0) {
+        fprintf(stderr, "qtts: pair GEMV launch failed (R=%d C=%d)\n", a.R, a.C);
+        return -1;
+    }
+    return 0;
+}
+// the layers of passes 0 and 1; *xfin: the residual rows [2][Hs] after the last layer
+static int subtalker_pair_layers(qtts_dev *dv, int pfm, float **xfin) {
+    const qtts_dims_t &d = dv->d;
+    const int QKV = dv->QKVs(), AD = d.NHs * d.HDs;
+    const bool proj = dv->st_proj != nullptr;
+    float *xa = dv->x_st, *xb = dv->x_st2;
+    if (proj) {   // ST_PROJECT_INPUT of row 0 (T.c:693-702); row 1's projected row is a table row
+        GemvArgs a = gv(dv->st_proj, d.Hs, d.H, dv->tk_hid, d.H, dv->x_st, d.Hs, 1, dv->st_projb ? EPI_BIAS : EPI_STORE);
+        a.bias = dv->st_projb;
+        a.nt = 0;
+        CKI(pgemv(dv, a, PK_GEMV_SUB));
+    }
+    {   // layer-0 q|k|v of row 0 (the single-row kernel; row 1's is the table's)
+        Layer &ly = dv->sl[0];
+        GemvArgs a = gv(ly.wqkv, QKV, d.Hs, xa, d.Hs, dv->qkv_s, QKV, 1, EPI_STORE);
+        a.norm_w = ly.in; a.eps = d.eps; a.nt = 0;
+        if (!proj) { a.x = dv->tk_hid; a.ldx = d.H; a.xcopy = dv->x_st; a.ldxc = d.Hs; a.xcopy_normed = 0; }
+        if (pfm & 1) a.pf = pf_attn_o(dv, ly.wo, d.Hs, d.NHs, d.HDs);
+        CKI(pgemv(dv, a, PK_GEMV_SUB));
+    }
+    for (int l = 0; l < d.Ls; ++l) {
+        Layer &ly = dv->sl[l];
+        // QTTS_HIP_GM_DBG=98: stamps of the pair pass, layer 2's q|k|v / attention + O / gate|up / down
+        const bool sdbg = dv->gm_dbg && dv->gm_dbg_layer == 98 && l == 2;
+        if (l > 0) {
+            GemvArgs a = gv(ly.wqkv, QKV, d.Hs, xa, d.Hs, dv->qkv_s, QKV, 2, EPI_STORE);
+            a.norm_w = ly.in; a.eps = d.eps; a.nt = 0;
+            if (sdbg) a.dbg = dv->gm_dbg;
+            if (pfm & 1) a.pf = pf_attn_o(dv, ly.wo, d.Hs, d.NHs, d.HDs);
+            CKI(pgemv_pair(dv, a));
+        }
+        AttnArgs t = st_pair_attn_args(dv, l);
+        if (pfm & 2) t.pf = pf_gemvw(dv, ly.wgu, 2 * d.Is, d.Hs);
+#ifdef QTTS_STAMPS
+        if (sdbg) t.dbg = dv->gm_dbg + 2048 * 8;
+#endif
+        {
+            ProfScope ps(dv, PK_ATTN, (double)d.Hs * AD * 2);
+            if (qtts_attn_o_pair(t, ly.wo, d.Hs, dv->opart, dv->st) != 0) {
+                fprintf(stderr, "qtts: pair attention + O launch failed (layer %d)\n", l);
+                return -1;
+            }
+        }
+        // gate|up: residual + the per-head O partials of both rows, the new residual to the other buffer
+        GemvArgs a = gv(ly.wgu, 2 * d.Is, d.Hs, xa, d.Hs, dv->h_s, d.Is, 2, EPI_SWIGLU);
+        a.norm_w = ly.post; a.eps = d.eps; a.nt = 0;
+        if (pfm & 4) a.pf = pf_gemvw(dv, ly.wdown, d.Hs, d.Is);
+        add_in(a, dv->opart, d.KVs, d.Hs, 2, xb);
+        if (sdbg) a.dbg = dv->gm_dbg + 2 * 2048 * 8;
+        CKI(pgemv_pair(dv, a));
+        std::swap(xa, xb);
+        // (row 0 in the last layer needs only its k / v store; its MLP rides along)
+        a = gv(ly.wdown, d.Hs, d.Is, dv->h_s, d.Is, xa, d.Hs, 2, EPI_RESID);
+        a.nt = 0;
+        if (pfm & 8) {
+            if (l + 1 < d.Ls) a.pf = pf_gemvw(dv, dv->sl[l + 1].wqkv, QKV, d.Hs);
+            else a.pf = pf_gemvw(dv, dv->lm, d.Vs, d.Hs);
+        }
+        if (sdbg) a.dbg = dv->gm_dbg + 3 * 2048 * 8;
+        CKI(pgemv_pair(dv, a));
+    }
+    *xfin = xa;
+    g_st_pair_passes.fetch_add(1);
+    return 0;
+}
+
 // 16 sub-talker passes (T.c:539-736)
 static int subtalker(qtts_dev *dv) {
     const qtts_dims_t &d = dv->d;
@@ -1304,7 +1426,28 @@ static int subtalker(qtts_dev *dv) {
         if (gn >= 1 && tab0_ok) return pf_attn_o(dv, dv->sl[0].wo, d.Hs, d.NHs, d.HDs);
         return pf_gemvw(dv, dv->sl[0].wqkv, QKV, d.Hs);
     };
-    for (int g = 0; g < d.G; ++g) {
+    // pass g's lm head on residual row(s) x, then its sampler
+    auto pass_head = [&](int g, const float *x, const float *pend, int npend) -> int {
+        GemvArgs a = gv(dv->lm + (size_t)(g - 1) * d.Vs * d.Hs, d.Vs, d.Hs, x, d.Hs, dv->logits_s, d.Vs, nb,
+                        EPI_STORE);
+        a.norm_w = dv->st_norm; a.eps = d.eps; a.nt = 0;
+        if (pend) add_in(a, pend, npend, d.Hs, nb, nullptr);
+        if (pfm & 16) a.pf = first_op_pf(g + 1);   // (two launches ahead: the sampler runs in between)
+        SampArgs s;
+        s.logits = dv->logits_s; s.ld = d.Vs; s.n = d.Vs; s.nb = nb;
+        s.top_k = dv->par.st_top_k; s.top_p = dv->par.st_top_p; s.temp = dv->par.st_temperature;
+        s.mode = 0; s.st_rng = dv->st_rng; s.stopped = dv->stopped; s.cur_row = dv->cur_row;
+        s.codes = dv->codes; s.codes_bstride = cstride; s.G = d.G; s.g = g; s.out_tok = dv->last_tok;
+        return head_sample(dv, a, s, PK_GEMV_SUB);
+    };
+    int g0 = 0;
+    if (st_pair_ok(dv)) {   // passes 0 and 1 as one two-row pass; pass 1's head reads row 1
+        float *xfin = nullptr;
+        CKI(subtalker_pair_layers(dv, pfm, &xfin));
+        CKI(pass_head(1, xfin + d.Hs, nullptr, 0));
+        g0 = 2;
+    }
+    for (int g = g0; g < d.G; ++g) {
         // input source for this pass
         GemvArgs src;  // x / table description only
         src.nb = nb;
@@ -1441,17 +1584,7 @@ static int subtalker(qtts_dev *dv) {
             CKI(pgemv(dv, a, PK_GEMV_SUB));
         }
         if (g == 0) continue;  // pass 0 produces no logits
-        GemvArgs a = gv(dv->lm + (size_t)(g - 1) * d.Vs * d.Hs, d.Vs, d.Hs, xa, d.Hs, dv->logits_s, d.Vs, nb,
-                        EPI_STORE);
-        a.norm_w = dv->st_norm; a.eps = d.eps; a.nt = 0;
-        if (pend) add_in(a, pend, npend, d.Hs, nb, nullptr);
-        if (pfm & 16) a.pf = first_op_pf(g + 1);   // (two launches ahead: the sampler runs in between)
-        SampArgs s;
-        s.logits = dv->logits_s; s.ld = d.Vs; s.n = d.Vs; s.nb = nb;
-        s.top_k = dv->par.st_top_k; s.top_p = dv->par.st_top_p; s.temp = dv->par.st_temperature;
-        s.mode = 0; s.st_rng = dv->st_rng; s.stopped = dv->stopped; s.cur_row = dv->cur_row;
-        s.codes = dv->codes; s.codes_bstride = cstride; s.G = d.G; s.g = g; s.out_tok = dv->last_tok;
-        CKI(head_sample(dv, a, s, PK_GEMV_SUB));
+        CKI(pass_head(g, xa, pend, npend));
     }
     return 0;
 }
@@ -2575,6 +2708,45 @@ extern "C" int qtts_hip_attn_o(float *part, const float *qkv, float *kc, float *
     int rc = qtts_attn_o(t, Wo, R, part, st);
     if (hipStreamSynchronize(st) != hipSuccess) rc = -1;
     return rc;
+}
+
+// The pair form of k_attn_o on its own: rows 0 and 1 of one slot at positions
+// 0 and 1, both from qkv [2][(NH + 2 KV) HD] (no id table); caches [S][KV*HD];
+// part [KV][2][R].  1 = a shape qtts_attn_o_pair_covers refuses.
+extern "C" int qtts_hip_attn_o_pair(float *part, const float *qkv, float *kc, float *vc, const float *qn_w,
+                                    const float *kn_w, const float *rope_cos, const float *rope_sin, const int *skip,
+                                    const uint16_t *Wo, int R, int NH, int KV, int HD, int S, float eps,
+                                    void *stream) {
+    if (!part || !qkv || !kc || !vc || !qn_w || !kn_w || !rope_cos || !rope_sin || !Wo) return -1;
+    if (!attn_dims_ok(NH, KV, HD, S, 2, 0) || R < 1) return -1;
+    AttnArgs t;
+    t.mode = 0; t.qkv = qkv; t.ld_qkv = (NH + 2 * KV) * HD; t.qn_w = qn_w; t.kn_w = kn_w; t.eps = eps;
+    t.rope_cos = rope_cos; t.rope_sin = rope_sin; t.kc = kc; t.vc = vc; t.S = S;
+    t.pos = nullptr; t.NH = NH; t.KV = KV; t.HD = HD; t.ld_out = NH * HD; t.nrows = 2; t.skip = skip;
+    if (!qtts_attn_o_pair_covers(t, Wo)) return 1;
+    hipStream_t st = (hipStream_t)stream;
+    int rc = qtts_attn_o_pair(t, Wo, R, part, st);
+    if (hipStreamSynchronize(st) != hipSuccess) rc = -1;
+    return rc;
+}
+
+// k_gemvw (nrows 1) or its pair form (nrows 2) for the default-cache-policy
+// shapes, with the sub-talker chain's prologue: x [nrows][cols] + the partials
+// part [n_part][nrows][cols] summed in order (part NULL: none), the sum stored
+// to x_new [nrows][cols] (NULL: not stored), RMSNorm by w (NULL: none).
+// 1 = a shape the kernel does not cover.
+extern "C" int qtts_hip_resident_matvec_rows_bf16(float *out, const uint16_t *A, const float *x, const float *w,
+                                                  float eps, int rows, int cols, int epi, const float *part,
+                                                  int n_part, float *x_new, int nrows, void *stream) {
+    if (!out || !A || !x || rows < 1 || cols < 1 || (nrows != 1 && nrows != 2)) return -1;
+    if (epi != EPI_STORE && epi != EPI_RESID && epi != EPI_SWIGLU) return -1;
+    if (part && n_part < 1) return -1;
+    if (part && cols > 1024) return 1;   // (the kernels hold the partials in registers up to 1024 columns)
+    GemvArgs a = gv(A, rows, cols, x, cols, out, epi == EPI_SWIGLU ? rows / 2 : rows, nrows, epi);
+    a.norm_w = w; a.eps = eps; a.nt = 0;
+    if (part) { a.xadd = part; a.n_xadd = n_part; a.ld_xadd = nrows * cols; a.ldb_xadd = cols; }
+    if (x_new) { a.xcopy = x_new; a.ldxc = cols; a.xcopy_normed = 0; }
+    return nrows == 2 ? qtts_gemvw_pair(a, (hipStream_t)stream) : qtts_gemvw(a, (hipStream_t)stream);
 }
 
 // One frame run eagerly with an event pair around every kernel launch on the

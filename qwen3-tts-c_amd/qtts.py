@@ -93,6 +93,7 @@ EXPORTS = [
     "qwen_tts_set_kv_cache_dtype", "qwen_tts_kv_cache_dtype", "qtts_dev_set_kv_dtype", "qtts_dev_kv_dtype",
     "qtts_dev_get_kv", "qtts_dev_get_attn", "qtts_hip_attn_decode",
     "qtts_hip_attn_decode_ex", "qtts_hip_attn_cached", "qtts_hip_attn_o",
+    "qtts_hip_attn_o_pair", "qtts_hip_resident_matvec_rows_bf16", "qtts_hip_st_pair_passes",
     "qwen_tts_force_codes", "qwen_tts_tap_draw", "qwen_tts_last_drawn", "qwen_tts_tap_result",
     "qtts_dev_force", "qtts_dev_tap", "qtts_dev_get_drawn", "qtts_dev_get_tap",
 ]
@@ -268,6 +269,14 @@ def lib():
     L.qtts_hip_attn_cached.argtypes = [vp, vp, C.c_int] + [vp] * 8 + [C.c_int] * 6 + [C.c_float] + [C.c_int] * 3 + [vp]
     L.qtts_hip_attn_o.restype = C.c_int
     L.qtts_hip_attn_o.argtypes = [vp] * 10 + [C.c_int] * 6 + [C.c_float, vp]
+    # (an older build named by QTTS_LIB for a same-box A/B has no pair entries; build() checks EXPORTS)
+    if hasattr(L, "qtts_hip_st_pair_passes"):
+        L.qtts_hip_st_pair_passes.restype = C.c_longlong
+        L.qtts_hip_attn_o_pair.restype = C.c_int
+        L.qtts_hip_attn_o_pair.argtypes = [vp] * 10 + [C.c_int] * 5 + [C.c_float, vp]
+        L.qtts_hip_resident_matvec_rows_bf16.restype = C.c_int
+        L.qtts_hip_resident_matvec_rows_bf16.argtypes = ([vp] * 4 + [C.c_float] + [C.c_int] * 3 + [vp, C.c_int, vp,
+                                                                                                C.c_int, vp])
     _LIB = L
     return L
 
@@ -813,4 +822,31 @@ class Kernels:
         if rc == 1:
             return False
         _ok(rc, "attn_o")
+        return True
+
+    @staticmethod
+    def attn_o_pair(part, qkv, kc, vc, qn_w, kn_w, rope_cos, rope_sin, Wo_u16, R, NH, KV, HD, S, eps, skip_i32=None):
+        """The pair form of attn_o (qtts_hip_attn_o_pair): qkv [2, (NH + 2 KV) HD]
+        at positions 0 and 1 of one slot, kc / vc [S, KV * HD], part [KV, 2, R].
+        False where the kernel does not cover the shape (nothing ran)."""
+        rc = lib().qtts_hip_attn_o_pair(_ptr(part), _ptr(qkv), _ptr(kc), _ptr(vc), _ptr(qn_w), _ptr(kn_w),
+                                        _ptr(rope_cos), _ptr(rope_sin), _ptr(skip_i32), _ptr(Wo_u16), R, NH, KV, HD,
+                                        S, eps, _stream())
+        if rc == 1:
+            return False
+        _ok(rc, "attn_o_pair")
+        return True
+
+    @staticmethod
+    def resident_matvec_rows_bf16(out, A_u16, x, w, eps, rows, cols, epi=0, part=None, x_new=None, nrows=1):
+        """k_gemvw (nrows 1) or its pair form (nrows 2) with the sub-talker
+        chain's prologue (qtts_hip_resident_matvec_rows_bf16): x [nrows, cols],
+        part [n_part, nrows, cols] added in order, the sum stored to x_new.
+        False where the kernel does not cover the shape (nothing ran)."""
+        rc = lib().qtts_hip_resident_matvec_rows_bf16(_ptr(out), _ptr(A_u16), _ptr(x), _ptr(w), eps, rows, cols, epi,
+                                                      _ptr(part), 0 if part is None else int(part.shape[0]),
+                                                      _ptr(x_new), nrows, _stream())
+        if rc == 1:
+            return False
+        _ok(rc, "resident_matvec_rows")
         return True

@@ -5,9 +5,10 @@ tracer-widened gap, profiles/r05f_mb_launch_rocprof.txt, so the line also
 carries the span the stamps measure).
 
 Runs `bench.py --full --steps 1 --warmup 0` on the stamp build (lib_s: `make -C
-qwen3-tts-c_amd VARIANT=_s EXTRA=-DQTTS_STAMPS`) twice -- QTTS_HIP_GM_DBG=99
+qwen3-tts-c_amd VARIANT=_s EXTRA=-DQTTS_STAMPS`) three times -- QTTS_HIP_GM_DBG=99
 (sub-talker pass 5, layer 2: q|k|v GEMV, attention + O, gate|up, down) and
-QTTS_HIP_GM_DBG=5 (talker layer 5: q|k|v, O with the merge, gate|up, down) --
+QTTS_HIP_GM_DBG=98 (the sub-talker's pair pass, positions 0 and 1, layer 2: the
+pair forms of the same four launches) and QTTS_HIP_GM_DBG=5 (talker layer 5: q|k|v, O with the merge, gate|up, down) --
 parses the `[gm_dbg]` lines of the last frame and writes
 
   {kernel: {"span_us": first workgroup start -> last stamp,
@@ -25,7 +26,9 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB_S = os.path.join(ROOT, "qwen3-tts-c_amd", "lib_s", "libqwen_tts_amd.so")
 # stamped slot -> kernel instantiation (1.7B, batch 1)
-NAMES = {"99": {"q|k|v": "k_gemvw<4, 2, false>", "O / -": "k_attn_o<128>", "gate|up": "k_gemvw<6, 2, false>",
+NAMES = {"98": {"q|k|v": "k_gemvw2<4, 2>", "O / -": "k_attn_o2<128>", "gate|up": "k_gemvw2<6, 2>",
+                "down": "k_gemvw2<1, 6>"},
+         "99": {"q|k|v": "k_gemvw<4, 2, false>", "O / -": "k_attn_o<128>", "gate|up": "k_gemvw<6, 2, false>",
                 "down": "k_gemvw<1, 6, false>"},
          "5": {"q|k|v": "k_gemvw<4, 4, true>", "O / -": "k_gemvw<2, 4, true, 8>", "gate|up": "k_gemvw<6, 4, true>",
                "down": "k_gemvw<2, 12, true>"}}
@@ -46,14 +49,15 @@ def run(layer):
         nxt = got[i + 1][1] if i + 1 < len(got) else None
         out[NAMES[layer].get(slot, slot)] = {"slot": slot, "span_us": span, "launch_at_us": at,
                                              "period_us": round(nxt - at, 2) if nxt is not None else None,
-                                             "group": "sub-talker pass 5 layer 2" if layer == "99" else "talker layer 5"}
+                                             "group": {"98": "sub-talker pair pass (positions 0 and 1) layer 2",
+                                                       "99": "sub-talker pass 5 layer 2"}.get(layer, "talker layer 5")}
     return out, r.stderr
 
 
 def main():
     res = {}
     logs = []
-    for layer in ("99", "5"):
+    for layer in ("98", "99", "5"):
         o, err = run(layer)
         res.update(o)
         logs.append("\n".join(l for l in err.splitlines() if l.startswith("[gm_dbg]")))
