@@ -395,6 +395,63 @@ int qtts_hip_attn_o_pair(float *part_dev, const float *qkv_dev, float *kc_dev, f
 int qtts_hip_resident_matvec_rows_bf16(float *out_dev, const uint16_t *A_dev, const float *x_dev, const float *w_dev,
                                        float eps, int rows, int cols, int epi, const float *part_dev, int n_part,
                                        float *x_new_dev, int nrows, void *stream);
+/* One contraction of the codec's GEMM family (k_codec.hip: qtts_xgemm), as the
+ * codec describes it to its dispatcher.  Modes (qtts_codec.h):
+ *   amode 0 rows A[m*lda+k], 1 trans A[k*lda+m], 2 transposed-conv weights [ci][co][Kw];
+ *   bmode 0 weights B[n*ldb+k], 1 causal conv over x[ic*ldb+t], 2 transposed conv;
+ *   emode 0 store, 1 +bias[n], 2 gelu(+bias[n]), 3 silu(aux)*acc, 4 C += acc*vec[n],
+ *         5 out[n][m] = acc+bias[n], 6 out[n][m] = (acc+bias[n])*vec[n]+res[n][m],
+ *         7 conv +bias[m] (bias may be NULL), 8 +bias[m]+res[m][n], 9 snake(acc+bias[m]; ea, eb).
+ * Convs: M = co, N = L, K = ci*Kw (causal) or ci*(Kw/stride) (transposed);
+ * input columns t in [tmin, L) are read (tmin <= 0: history left of B).  All
+ * pointers are device pointers. */
+typedef struct {
+    int M, N, K;
+    int amode, bmode, emode;
+    const float *A; int lda;
+    const float *B; int ldb;
+    int Kw, dil, pad, L, stride, tmin, co;
+    const float *sa, *sb;             /* SnakeBeta (alpha, inv_beta) on the input channels, or NULL */
+    float *C; int ldc;
+    const float *bias, *vec, *aux, *res;
+    int ldaux, ldres;
+    const float *ea, *eb;             /* emode 9 */
+} qtts_xgemm_desc_t;
+/* kernels of the family, as path / path_out below */
+enum {
+    QTTS_XP_CONVB2 = 0,   /* k_convb<Kw,2>: bf16 3-plane conv, 64 x 128 tile */
+    QTTS_XP_CONVB4 = 1,   /* k_convb<Kw,4>: 64 x 256 tile */
+    QTTS_XP_CONV = 2,     /* k_conv<Kw>: fp32 MFMA conv */
+    QTTS_XP_XLIN = 3,     /* k_xlin: bf16 3-plane linear */
+    QTTS_XP_XGEMV = 4,    /* k_xgemv: linear at <= 4 rows */
+    QTTS_XP_XGEMM = 5,    /* k_xgemm: generic */
+};
+/* The dispatcher's plan for the contraction with a split workspace of
+ * part_elems floats (0: none): which kernel (path_out) and how many splits
+ * (splits_out: input-channel splits of the conv kernels, K splits of k_xlin /
+ * k_xgemm, summed by k_conv_reduce / k_xg_reduce; k_xgemv's in-block K slots).
+ * force_path -1: the dispatcher's own choice; else that kernel if its
+ * predicate covers the shape, 1 if not.  Transposed convs (bmode 2) are
+ * planned as the model runs them: all phases in one conv launch, or one
+ * k_xgemm per phase.  Host only: no pointer is dereferenced (their alignment
+ * is looked at) and no device is needed. */
+int qtts_hip_xgemm_plan(const qtts_xgemm_desc_t *d, size_t part_elems, int force_path, int *path_out,
+                        int *splits_out);
+/* Runs the contraction through that plan: allocates the workspace exactly
+ * part_elems large, makes the re-laid conv weights and their bf16 planes as
+ * qtts_hip_causal_conv1d does, launches, synchronises, frees.  Returns 1 and
+ * launches nothing where force_path does not cover the shape, -1 on an error
+ * (among them an epilogue operand the mode needs that is NULL).  A parity
+ * entry, not a timing one. */
+int qtts_hip_xgemm_case(const qtts_xgemm_desc_t *d, size_t part_elems, int force_path, int *path_out,
+                        int *splits_out, void *stream);
+/* snake(x) = x + inv_beta[c] * sin^2(x * alpha[c]) with the codec GEMMs' own
+ * sin^2 (sin2 in k_codec.hip; qtts_hip_snake_beta runs sinf), and the fp32
+ * expf / tanhf the GELU and SiLU epilogues call: fn 0 snake (needs alpha /
+ * inv_beta per channel, x [channels][length]), 1 expf, 2 tanhf (channels = 1).
+ * For measuring those functions against float64. */
+int qtts_hip_xgemm_func(float *out_dev, const float *x_dev, const float *alpha_dev, const float *inv_beta_dev,
+                        int channels, int length, int fn, void *stream);
 /* glibc-exact expf replica used by the sampler (for the libm cross-check test) */
 int qtts_hip_expf_glibc(float *out_dev, const float *in_dev, int n, void *stream);
 int qtts_hip_sync(void);

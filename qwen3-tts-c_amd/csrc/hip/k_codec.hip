@@ -829,12 +829,15 @@ __global__ void k_iota(int *p, int n, int zero) {
 // come in whole stages, the window halo fits and the output fills the chip
 // (small first-packet decodes keep the split-K GEMM).
 static int conv_splits(const XGemm &g);
+// the shapes the conv kernels were written for
+static bool conv_shape_ok(const XGemm &g) {
+    return g.wt && g.bmode == XB_CONV && g.amode == XA_ROWS &&
+           (g.Kw == 1 || g.Kw == 2 || g.Kw == 3 || g.Kw == 7) && (g.K / g.Kw) % CV_BC == 0 &&
+           (g.Kw - 1) * g.dil <= CV_HALO && !((uintptr_t)g.wt & 15);
+}
 static bool conv_ok(const XGemm &g) {
     constexpr int min_tiles = 96;
-    if (!g.wt || g.bmode != XB_CONV || g.amode != XA_ROWS ||
-        !(g.Kw == 1 || g.Kw == 2 || g.Kw == 3 || g.Kw == 7) || (g.K / g.Kw) % CV_BC ||
-        (g.Kw - 1) * g.dil > CV_HALO || ((uintptr_t)g.wt & 15))
-        return false;
+    if (!conv_shape_ok(g)) return false;
     const int tiles = ((g.N + CV_BN - 1) / CV_BN) * ((g.M + CV_BM - 1) / CV_BM) * (g.stride > 1 ? g.stride : 1);
     return tiles >= min_tiles || (g.part && conv_splits(g) > 1);
 }
@@ -853,33 +856,137 @@ static int conv_splits(const XGemm &g) {
     return nz;
 }
 
-static int conv_launch(const XGemm &gin, int nph, hipStream_t st) {
+// which conv kernel runs a conv the conv kernels cover, on kz channel splits:
+// the bf16 3-plane MFMA path, except a SnakeBeta prologue over more input
+// channels than its staging covers (then the fp32 MFMA k_conv)
+static int conv_path(const XGemm &g, int kz) {
+    const bool bf = !g.sa || g.K / g.Kw / (kz > 1 ? kz : 1) <= CB_SNAKE_MAX;
+    if (!bf) return QTTS_XP_CONV;
+    // 256-column tiles where the grid still holds >= 2 workgroups per CU
+    // (the two column blocks' MFMA chains interleaved measured the same:
+    // codec 7.9 ms per 128 frames either way, profiles/r05st_ab_codec.txt)
+    const int nph = g.stride > 1 ? g.stride : 1;
+    const int tiles4 = ((g.N + 255) / 256) * ((g.M + CV_BM - 1) / CV_BM) * nph * kz;
+    return tiles4 >= 512 ? QTTS_XP_CONVB4 : QTTS_XP_CONVB2;
+}
+
+// k_xgemv covers a linear at <= 4 rows
+static bool xgemv_ok(const XGemm &g) {
+    return g.M <= 4 && g.bmode == XB_WT && (g.amode == XA_ROWS || g.amode == XA_TRANS) && g.K % 256 == 0 &&
+           g.ldb % 4 == 0 && ((uintptr_t)g.B & 15) == 0 && (size_t)4 * g.K * 4 + 512 <= 64 * 1024;
+}
+
+// k_xlin covers plain fp32 linears above k_xgemv's 4 rows with 16-B rows
+static bool xlin_ok(const XGemm &g) {
+    return g.amode == XA_ROWS && g.bmode == XB_WT && g.M > 4 && g.N % 64 == 0 && g.K % XL_KS == 0 &&
+           g.lda % 4 == 0 && g.ldb % 4 == 0 && ((uintptr_t)g.A & 15) == 0 && ((uintptr_t)g.B & 15) == 0;
+}
+
+// k_xlin's split-K where the tiles would not fill the chip: >= 1 stage each,
+// partials within the workspace
+static int xlin_splits(const XGemm &g) {
+    const int tiles = (g.N / 64) * ((g.M + 63) / 64), nst = g.K / XL_KS;
+    int nz = 1;
+    if (g.part && tiles < 256) {
+        nz = (256 + tiles - 1) / tiles;
+        if (nz > nst) nz = nst;
+        while (nz > 1 && (size_t)nz * g.M * g.N > g.part_elems) --nz;
+    }
+    return nz;
+}
+
+// k_xgemv's KSPLIT: grid >= 512 workgroups, >= 1 block per lane, and the K / 32
+// blocks dealt evenly: a slot takes K / 32 / ks of them, so a remainder would
+// be left out of the sum (K = 3840 on 16 or 32 slots lost 24 of its 120 blocks)
+static int xgemv_ks(const XGemm &g) {
+    int ks = 1;
+    while (ks < 32 && (g.N + 32 / ks - 1) / (32 / ks) < 512 && g.K / 32 / (2 * ks) >= 1 && g.K / 32 % (2 * ks) == 0)
+        ks *= 2;
+    return ks;
+}
+
+// k_xgemm's split-K when the output has too few tiles to fill the chip (first-
+// packet sized decodes): z ranges of >= 8 K-steps, partials in g.part
+static int xgemm_splits(const XGemm &g) {
+    const int tiles = ((g.N + BN - 1) / BN) * ((g.M + BM - 1) / BM), ksteps = (g.K + BK - 1) / BK;
+    int nz = 1;
+    if (g.part && tiles < 192 && ksteps >= 16) {
+        nz = (256 + tiles - 1) / tiles;
+        if (nz > ksteps / 8) nz = ksteps / 8;
+        if (nz > 32) nz = 32;
+        while (nz > 1 && (size_t)nz * g.M * g.N > g.part_elems) --nz;
+    }
+    return nz;
+}
+
+// The dispatcher in two halves.  xg_plan is pure: which kernel runs g, on how
+// many splits (conv kernels: input-channel splits summed by k_conv_reduce;
+// k_xlin / k_xgemm: K splits summed by k_xg_reduce; k_xgemv: K slots inside
+// the workgroup).  xg_launch runs a plan.
+struct XPlan {
+    int path = QTTS_XP_XGEMM, splits = 1;
+};
+
+static XPlan xg_plan(const XGemm &g) {
+    static const bool xl_on = [] { const char *e = getenv("QTTS_HIP_XLIN"); return !(e && !atoi(e)); }();
+    XPlan p;
+    if (xl_on && xlin_ok(g)) {
+        p.path = QTTS_XP_XLIN;
+        p.splits = xlin_splits(g);
+    } else if (xgemv_ok(g)) {
+        p.path = QTTS_XP_XGEMV;
+        p.splits = xgemv_ks(g);
+    } else if (conv_ok(g)) {
+        p.splits = conv_splits(g);
+        p.path = conv_path(g, p.splits);
+    } else {
+        p.path = QTTS_XP_XGEMM;
+        p.splits = xgemm_splits(g);
+    }
+    return p;
+}
+
+// the plan that runs g on `path` (the kernel-level parity entry): false where
+// that kernel was not written for the shape.  The splits are the dispatcher's.
+static bool xg_plan_forced(const XGemm &g, int path, XPlan *p) {
+    p->path = path;
+    switch (path) {
+        case QTTS_XP_CONVB2:
+        case QTTS_XP_CONVB4:
+        case QTTS_XP_CONV:
+            if (!conv_shape_ok(g)) return false;
+            p->splits = conv_splits(g);
+            // k_convb takes a SnakeBeta prologue up to CB_SNAKE_MAX channels per split
+            return path == QTTS_XP_CONV || conv_path(g, p->splits) != QTTS_XP_CONV;
+        case QTTS_XP_XLIN: p->splits = xlin_splits(g); return xlin_ok(g);
+        case QTTS_XP_XGEMV: p->splits = xgemv_ks(g); return xgemv_ok(g);
+        case QTTS_XP_XGEMM:
+            p->splits = xgemm_splits(g);
+            // (a transposed conv's all-phase conv form has no A operand: conv kernels only)
+            return g.A != nullptr;
+    }
+    return false;
+}
+
+static int conv_launch(const XGemm &gin, const XPlan &p, hipStream_t st) {
     XGemm g = gin;
-    g.kz = conv_splits(g);
+    const int nph = g.stride > 1 ? g.stride : 1;
+    g.kz = p.splits;
     const dim3 cg((g.N + CV_BN - 1) / CV_BN, (g.M + CV_BM - 1) / CV_BM, nph * g.kz);
-    // bf16 3-plane MFMA path, except a SnakeBeta prologue over more input
-    // channels than its staging covers (then the fp32 MFMA k_conv)
-    const bool bf = !g.sa || g.K / g.Kw / (g.kz > 1 ? g.kz : 1) <= CB_SNAKE_MAX;
-    if (bf) {
-        // 256-column tiles where the grid still holds >= 2 workgroups per CU
-        // (the two column blocks' MFMA chains interleaved measured the same:
-        // codec 7.9 ms per 128 frames either way, profiles/r05st_ab_codec.txt)
-        const int tiles4 = ((g.N + 255) / 256) * cg.y * cg.z;
-        if (tiles4 >= 512) {
-            const dim3 c4((g.N + 255) / 256, cg.y, cg.z);
-            switch (g.Kw) {
-                case 7: hipLaunchKernelGGL((k_convb<7, 4>), c4, dim3(512), 0, st, g); break;
-                case 3: hipLaunchKernelGGL((k_convb<3, 4>), c4, dim3(512), 0, st, g); break;
-                case 2: hipLaunchKernelGGL((k_convb<2, 4>), c4, dim3(512), 0, st, g); break;
-                default: hipLaunchKernelGGL((k_convb<1, 4>), c4, dim3(512), 0, st, g); break;
-            }
-        } else {
-            switch (g.Kw) {
-                case 7: hipLaunchKernelGGL((k_convb<7, 2>), cg, dim3(256), 0, st, g); break;
-                case 3: hipLaunchKernelGGL((k_convb<3, 2>), cg, dim3(256), 0, st, g); break;
-                case 2: hipLaunchKernelGGL((k_convb<2, 2>), cg, dim3(256), 0, st, g); break;
-                default: hipLaunchKernelGGL((k_convb<1, 2>), cg, dim3(256), 0, st, g); break;
-            }
+    if (p.path == QTTS_XP_CONVB4) {
+        const dim3 c4((g.N + 255) / 256, cg.y, cg.z);
+        switch (g.Kw) {
+            case 7: hipLaunchKernelGGL((k_convb<7, 4>), c4, dim3(512), 0, st, g); break;
+            case 3: hipLaunchKernelGGL((k_convb<3, 4>), c4, dim3(512), 0, st, g); break;
+            case 2: hipLaunchKernelGGL((k_convb<2, 4>), c4, dim3(512), 0, st, g); break;
+            default: hipLaunchKernelGGL((k_convb<1, 4>), c4, dim3(512), 0, st, g); break;
+        }
+    } else if (p.path == QTTS_XP_CONVB2) {
+        switch (g.Kw) {
+            case 7: hipLaunchKernelGGL((k_convb<7, 2>), cg, dim3(256), 0, st, g); break;
+            case 3: hipLaunchKernelGGL((k_convb<3, 2>), cg, dim3(256), 0, st, g); break;
+            case 2: hipLaunchKernelGGL((k_convb<2, 2>), cg, dim3(256), 0, st, g); break;
+            default: hipLaunchKernelGGL((k_convb<1, 2>), cg, dim3(256), 0, st, g); break;
         }
     } else {
         switch (g.Kw) {
@@ -896,67 +1003,43 @@ static int conv_launch(const XGemm &gin, int nph, hipStream_t st) {
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
-// k_xgemv covers a linear at <= 4 rows
-static bool xgemv_ok(const XGemm &g) {
-    return g.M <= 4 && g.bmode == XB_WT && (g.amode == XA_ROWS || g.amode == XA_TRANS) && g.K % 256 == 0 &&
-           g.ldb % 4 == 0 && ((uintptr_t)g.B & 15) == 0 && (size_t)4 * g.K * 4 + 512 <= 64 * 1024;
-}
-
-// k_xlin covers plain fp32 linears above k_xgemv's 4 rows with 16-B rows
-static bool xlin_ok(const XGemm &g) {
-    return g.amode == XA_ROWS && g.bmode == XB_WT && g.M > 4 && g.N % 64 == 0 && g.K % XL_KS == 0 &&
-           g.lda % 4 == 0 && g.ldb % 4 == 0 && ((uintptr_t)g.A & 15) == 0 && ((uintptr_t)g.B & 15) == 0;
-}
-
-int qtts_xgemm(const XGemm &g, hipStream_t st) {
-    if (g.M <= 0 || g.N <= 0 || g.K <= 0) return 0;
-    static const bool xl_on = [] { const char *e = getenv("QTTS_HIP_XLIN"); return !(e && !atoi(e)); }();
-    if (xl_on && xlin_ok(g)) {
-        dim3 grid(g.N / 64, (g.M + 63) / 64, 1);
-        // split-K where the tiles would not fill the chip: >= 1 stage each,
-        // partials within the workspace
-        const int tiles = grid.x * grid.y, nst = g.K / XL_KS;
-        int nz = 1;
-        if (g.part && tiles < 256) {
-            nz = (256 + tiles - 1) / tiles;
-            if (nz > nst) nz = nst;
-            while (nz > 1 && (size_t)nz * g.M * g.N > g.part_elems) --nz;
+static int xg_launch(const XGemm &g, const XPlan &p, hipStream_t st) {
+    const int nz = p.splits;
+    switch (p.path) {
+        case QTTS_XP_XLIN: {
+            hipLaunchKernelGGL(k_xlin, dim3(g.N / 64, (g.M + 63) / 64, nz), dim3(256), 0, st, g);
+            break;
         }
-        grid.z = nz;
-        hipLaunchKernelGGL(k_xlin, grid, dim3(256), 0, st, g);
-        if (nz > 1) {
-            const size_t n = (size_t)g.M * g.N;
-            hipLaunchKernelGGL(k_xg_reduce, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, g, nz);
+        case QTTS_XP_XGEMV: {
+            const int rpw = 32 / nz;
+            hipLaunchKernelGGL(k_xgemv, dim3((g.N + rpw - 1) / rpw), dim3(256), (size_t)(4 * g.K + 128) * 4, st, g, nz);
+            return hipGetLastError() == hipSuccess ? 0 : -1;
         }
-        return hipGetLastError() == hipSuccess ? 0 : -1;
+        case QTTS_XP_XGEMM: {
+            hipLaunchKernelGGL(k_xgemm, dim3((g.N + BN - 1) / BN, (g.M + BM - 1) / BM, nz), dim3(256), 0, st, g);
+            break;
+        }
+        default: return conv_launch(g, p, st);
     }
-    if (xgemv_ok(g)) {
-        int ks = 1;   // KSPLIT: grid >= 512 workgroups, >= 1 block per lane
-        while (ks < 32 && (g.N + 32 / ks - 1) / (32 / ks) < 512 && g.K / 32 / (2 * ks) >= 1) ks *= 2;
-        const int rpw = 32 / ks;
-        hipLaunchKernelGGL(k_xgemv, dim3((g.N + rpw - 1) / rpw), dim3(256), (size_t)(4 * g.K + 128) * 4, st, g, ks);
-        return hipGetLastError() == hipSuccess ? 0 : -1;
-    }
-    if (conv_ok(g)) return conv_launch(g, g.stride > 1 ? g.stride : 1, st);
-    dim3 grid((g.N + BN - 1) / BN, (g.M + BM - 1) / BM, 1);
-    // split-K when the output has too few tiles to fill the chip (first-packet
-    // sized decodes): z ranges of >= 8 K-steps, partials in g.part
-    const int tiles = grid.x * grid.y, ksteps = (g.K + BK - 1) / BK;
-    int nz = 1;
-    if (g.part && tiles < 192 && ksteps >= 16) {
-        nz = (256 + tiles - 1) / tiles;
-        if (nz > ksteps / 8) nz = ksteps / 8;
-        if (nz > 32) nz = 32;
-        while (nz > 1 && (size_t)nz * g.M * g.N > g.part_elems) --nz;
-    }
-    grid.z = nz;
-    hipLaunchKernelGGL(k_xgemm, grid, dim3(256), 0, st, g);
     if (nz > 1) {
         const size_t n = (size_t)g.M * g.N;
         hipLaunchKernelGGL(k_xg_reduce, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, g, nz);
     }
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
+
+// force -1: the dispatcher's plan; else that kernel, 1 (nothing launched) where
+// it does not cover g.  ran (optional): the plan that ran.
+static int xgemm_run(const XGemm &g, hipStream_t st, int force, XPlan *ran) {
+    if (g.M <= 0 || g.N <= 0 || g.K <= 0) return 0;
+    XPlan p;
+    if (force < 0) p = xg_plan(g);
+    else if (!xg_plan_forced(g, force, &p)) return 1;
+    if (ran) *ran = p;
+    return xg_launch(g, p, st);
+}
+
+int qtts_xgemm(const XGemm &g, hipStream_t st) { return xgemm_run(g, st, -1, nullptr); }
 
 // ===================================================================== model
 static float *cw(CodecModel *m, const std::string &n) {
@@ -1231,10 +1314,11 @@ static int ensure_codec_state(CodecModel *m, int T) {
 #define KCK(x) do { if ((x) != 0) return -1; } while (0)
 
 // codec GEMMs get the split-K workspace
-static int xgm(CodecModel *m, XGemm g, hipStream_t st) {
+// (force / ran: the kernel-level parity entry's forced path and its report, xgemm_run)
+static int xgm(CodecModel *m, XGemm g, hipStream_t st, int force = -1, XPlan *ran = nullptr) {
     g.part = m->xg_part;   // nullptr (kernel-level entries' stateless model): no split
     g.part_elems = m->xg_part_elems;
-    return qtts_xgemm(g, st);
+    return xgemm_run(g, st, force, ran);
 }
 
 static XGemm lin(const float *A, int M, int K, const float *W, int N, float *C, int emode) {
@@ -1278,21 +1362,41 @@ static const float *ctwt(CodecModel *m, const float *w, int ci, int co, int Kw, 
 // a transposed conv (kernel Kw = ntap*s, stride s) as s causal convs of ntap
 // taps over the same input, one per output phase, in one k_conv launch
 // (grid z = phase) when k_conv covers it; else one implicit GEMM per phase
-static int tconv_run(CodecModel *m, const XGemm &g, hipStream_t st) {
-    const int s = g.stride, nt = g.Kw / s, ci = g.K / nt;
+// its all-phase conv form (g.part / g.part_elems: the workspace it would get)
+static XGemm tconv_conv_form(const XGemm &g) {
+    const int nt = g.Kw / g.stride;
     XGemm c = g;
     c.amode = XA_ROWS; c.A = nullptr; c.bmode = XB_CONV; c.Kw = nt; c.dil = 1; c.pad = nt - 1; c.phase = 0;
     c.wt = (const float *)16;  // shape-only probe before the relayout is made
-    c.part = m->xg_part;
-    c.part_elems = m->xg_part_elems;
-    if (conv_ok(c)) {
+    return c;
+}
+// which form runs and its plan (force as xgemm_run: 1 where that kernel does
+// not cover the transposed conv; the generic kernel takes the per-phase form)
+static int tconv_plan(const XGemm &g, int force, bool *as_conv, XPlan *p) {
+    const XGemm c = tconv_conv_form(g);
+    *as_conv = force < 0 ? conv_ok(c) : force != QTTS_XP_XGEMM;
+    if (force >= 0) return xg_plan_forced(*as_conv ? c : g, force, p) ? 0 : 1;
+    *p = xg_plan(*as_conv ? c : g);
+    return 0;
+}
+static int tconv_run(CodecModel *m, const XGemm &gin, hipStream_t st, int force = -1, XPlan *ran = nullptr) {
+    XGemm g = gin;
+    g.part = m->xg_part;
+    g.part_elems = m->xg_part_elems;
+    const int s = g.stride, nt = g.Kw / s, ci = g.K / nt;
+    bool as_conv;
+    XPlan p;
+    if (tconv_plan(g, force, &as_conv, &p)) return 1;
+    if (as_conv) {
+        XGemm c = tconv_conv_form(g);
         c.wt = ctwt(m, g.A, ci, g.co, g.Kw, s, st);
-        if (c.wt) return xgm(m, c, st);
+        if (c.wt) return xgm(m, c, st, force, ran);
+        if (force >= 0) return -1;
     }
     for (int ph = 0; ph < s; ++ph) {
-        XGemm p = g;
-        p.phase = ph;
-        KCK(xgm(m, p, st));
+        XGemm q = g;
+        q.phase = ph;
+        KCK(xgm(m, q, st, force, ran));
     }
     return 0;
 }
@@ -1603,6 +1707,131 @@ extern "C" int qtts_hip_snake_beta(float *out, const float *x, const float *alph
 
 extern "C" int qtts_hip_expf_glibc(float *out, const float *in, int n, void *stream) {
     hipLaunchKernelGGL(k_expf_glibc, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, in, out, n);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+// ---- one contraction of the family through the dispatcher's planner and launcher
+static int xcase_gemm(const qtts_xgemm_desc_t *d, XGemm *out) {
+    if (!d || d->M <= 0 || d->N <= 0 || d->K <= 0 || !d->A || !d->B || !d->C) return -1;
+    if (d->amode < XA_ROWS || d->amode > XA_TCONV_W || d->bmode < XB_WT || d->bmode > XB_TCONV ||
+        d->emode < XE_STORE || d->emode > XE_BIAS_M_SNAKE)
+        return -1;
+    // operands the modes read
+    if ((d->sa == nullptr) != (d->sb == nullptr)) return -1;
+    const int e = d->emode;
+    if ((e == XE_BIAS_N || e == XE_BIAS_N_GELU || e == XE_BIAS_T || e == XE_BIAS_GAMMA_RES_T || e == XE_BIAS_M_RES ||
+         e == XE_BIAS_M_SNAKE) && !d->bias)
+        return -1;
+    if ((e == XE_SCALE_RESID_N || e == XE_BIAS_GAMMA_RES_T) && !d->vec) return -1;
+    if (e == XE_SILU_MUL && !d->aux) return -1;
+    if ((e == XE_BIAS_GAMMA_RES_T || e == XE_BIAS_M_RES) && !d->res) return -1;
+    if (e == XE_BIAS_M_SNAKE && (!d->ea || !d->eb)) return -1;
+    // the pairings the codec makes: conv operands come with conv epilogues
+    const bool tc = d->bmode == XB_TCONV;
+    if ((d->amode == XA_TCONV_W) != tc) return -1;
+    if (d->bmode != XB_WT) {
+        if (d->Kw < 1 || d->dil < 1 || d->L < d->N || d->tmin > 0 || e < XE_BIAS_M) return -1;
+        if (tc) {
+            if (e != XE_BIAS_M || d->stride < 1 || d->Kw % d->stride || d->K % (d->Kw / d->stride) || d->co != d->M ||
+                d->tmin < -(d->Kw / d->stride - 1))
+                return -1;
+        } else if (d->amode != XA_ROWS || d->lda != d->K || d->stride != 1 || d->K % d->Kw ||
+                   d->pad != (d->Kw - 1) * d->dil || d->tmin < -d->pad) {
+            return -1;
+        }
+    } else if (d->stride != 1) {
+        return -1;
+    }
+    XGemm g;
+    g.M = d->M; g.N = d->N; g.K = d->K; g.amode = d->amode; g.bmode = d->bmode; g.emode = d->emode;
+    g.A = d->A; g.lda = d->lda; g.B = d->B; g.ldb = d->ldb;
+    g.Kw = d->Kw; g.dil = d->dil; g.pad = d->pad; g.L = d->L; g.stride = d->stride; g.tmin = d->tmin; g.co = d->co;
+    g.sa = d->sa; g.sb = d->sb; g.C = d->C; g.ldc = d->ldc;
+    g.bias = d->bias; g.vec = d->vec; g.aux = d->aux; g.res = d->res; g.ldaux = d->ldaux; g.ldres = d->ldres;
+    g.ea = d->ea; g.eb = d->eb;
+    *out = g;
+    return 0;
+}
+
+extern "C" int qtts_hip_xgemm_plan(const qtts_xgemm_desc_t *d, size_t part_elems, int force_path, int *path_out,
+                                   int *splits_out) {
+    XGemm g;
+    if (xcase_gemm(d, &g)) return -1;
+    g.part = part_elems ? (float *)16 : nullptr;   // never dereferenced here
+    g.part_elems = part_elems;
+    XPlan p;
+    if (g.bmode == XB_TCONV) {
+        bool as_conv;
+        if (tconv_plan(g, force_path, &as_conv, &p)) return 1;
+    } else {
+        if (g.bmode == XB_CONV) g.wt = (const float *)16;   // the relayout the run makes
+        if (force_path < 0) p = xg_plan(g);
+        else if (!xg_plan_forced(g, force_path, &p)) return 1;
+    }
+    if (path_out) *path_out = p.path;
+    if (splits_out) *splits_out = p.splits;
+    return 0;
+}
+
+extern "C" int qtts_hip_xgemm_case(const qtts_xgemm_desc_t *d, size_t part_elems, int force_path, int *path_out,
+                                   int *splits_out, void *stream) {
+    hipStream_t st = (hipStream_t)stream;
+    int pp = 0, ps = 0;
+    const int prc = qtts_hip_xgemm_plan(d, part_elems, force_path, &pp, &ps);
+    if (prc) return prc;   // nothing launched
+    XGemm g;
+    xcase_gemm(d, &g);
+    CodecModel dummy;   // holds the workspace and the re-laid weights of this one call
+    if (part_elems) {
+        if (hipMalloc(&dummy.xg_part, part_elems * sizeof(float)) != hipSuccess) return -1;
+        dummy.xg_part_elems = part_elems;
+    }
+    XPlan ran;
+    ran.path = -1;
+    int rc = 0;
+    if (g.bmode == XB_TCONV) {
+        rc = tconv_run(&dummy, g, st, force_path, &ran);
+    } else {
+        if (g.bmode == XB_CONV) {
+            float *t = nullptr;
+            const size_t cnt = (size_t)g.M * g.K;
+            if (hipMalloc(&t, cnt * 10) != hipSuccess) rc = -1;
+            if (!rc) {
+                hipLaunchKernelGGL(k_wt_relayout, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, g.A, g.M,
+                                   g.K / g.Kw, g.Kw, t);
+                wt_planes(t, cnt, st);
+                dummy.wt["xcase"] = t;
+                g.wt = t;
+            }
+        }
+        if (!rc) rc = xgm(&dummy, g, st, force_path, &ran);
+    }
+    if (hipStreamSynchronize(st) != hipSuccess) rc = -1;
+    for (auto &kv : dummy.wt) hipFree(kv.second);
+    dummy.wt.clear();
+    if (dummy.xg_part) hipFree(dummy.xg_part);
+    dummy.xg_part = nullptr;
+    if (!rc && (ran.path != pp || ran.splits != ps)) rc = -1;   // the launcher ran what the planner said
+    if (path_out) *path_out = ran.path;
+    if (splits_out) *splits_out = ran.splits;
+    return rc;
+}
+
+namespace {
+__global__ void k_xg_func(const float *x, const float *a, const float *ib, int C, int L, int fn, float *y) {
+    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (size_t)C * L) return;
+    const int c = (int)(idx / L);
+    const float v = x[idx];
+    y[idx] = fn == 0 ? snake1(v, a[c], ib[c]) : fn == 1 ? expf(v) : tanhf(v);
+}
+}  // namespace
+
+extern "C" int qtts_hip_xgemm_func(float *out, const float *x, const float *alpha, const float *inv_beta, int channels,
+                                   int length, int fn, void *stream) {
+    if (fn < 0 || fn > 2 || channels <= 0 || length <= 0 || (fn == 0 && (!alpha || !inv_beta))) return -1;
+    hipLaunchKernelGGL(k_xg_func, dim3((unsigned)(((size_t)channels * length + 255) / 256)), dim3(256), 0,
+                       (hipStream_t)stream, x, alpha, inv_beta, channels, length, fn, out);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

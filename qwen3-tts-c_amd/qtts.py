@@ -96,7 +96,34 @@ EXPORTS = [
     "qtts_hip_attn_o_pair", "qtts_hip_resident_matvec_rows_bf16", "qtts_hip_st_pair_passes",
     "qwen_tts_force_codes", "qwen_tts_tap_draw", "qwen_tts_last_drawn", "qwen_tts_tap_result",
     "qtts_dev_force", "qtts_dev_tap", "qtts_dev_get_drawn", "qtts_dev_get_tap",
+    "qtts_hip_xgemm_plan", "qtts_hip_xgemm_case", "qtts_hip_xgemm_func",
 ]
+
+class XGemmDesc(C.Structure):
+    """qtts_xgemm_desc_t (include/qtts_hip.h): one contraction of the codec's
+    GEMM family; the pointers are device addresses."""
+    _fields_ = [
+        ("M", C.c_int), ("N", C.c_int), ("K", C.c_int),
+        ("amode", C.c_int), ("bmode", C.c_int), ("emode", C.c_int),
+        ("A", C.c_void_p), ("lda", C.c_int),
+        ("B", C.c_void_p), ("ldb", C.c_int),
+        ("Kw", C.c_int), ("dil", C.c_int), ("pad", C.c_int), ("L", C.c_int), ("stride", C.c_int),
+        ("tmin", C.c_int), ("co", C.c_int),
+        ("sa", C.c_void_p), ("sb", C.c_void_p),
+        ("C", C.c_void_p), ("ldc", C.c_int),
+        ("bias", C.c_void_p), ("vec", C.c_void_p), ("aux", C.c_void_p), ("res", C.c_void_p),
+        ("ldaux", C.c_int), ("ldres", C.c_int),
+        ("ea", C.c_void_p), ("eb", C.c_void_p),
+    ]
+
+
+# XGemm modes and kernels (qtts_codec.h, QTTS_XP_* of qtts_hip.h)
+XA_ROWS, XA_TRANS, XA_TCONV_W = 0, 1, 2
+XB_WT, XB_CONV, XB_TCONV = 0, 1, 2
+(XE_STORE, XE_BIAS_N, XE_BIAS_N_GELU, XE_SILU_MUL, XE_SCALE_RESID_N, XE_BIAS_T, XE_BIAS_GAMMA_RES_T, XE_BIAS_M,
+ XE_BIAS_M_RES, XE_BIAS_M_SNAKE) = range(10)
+XP_CONVB2, XP_CONVB4, XP_CONV, XP_XLIN, XP_XGEMV, XP_XGEMM = range(6)
+XP_NAMES = ["k_convb<Kw,2>", "k_convb<Kw,4>", "k_conv<Kw>", "k_xlin", "k_xgemv", "k_xgemm"]
 
 MAX_TAPS = 8   # taps per run (qwen_tts_tap_draw)
 
@@ -277,6 +304,13 @@ def lib():
         L.qtts_hip_resident_matvec_rows_bf16.restype = C.c_int
         L.qtts_hip_resident_matvec_rows_bf16.argtypes = ([vp] * 4 + [C.c_float] + [C.c_int] * 3 + [vp, C.c_int, vp,
                                                                                                 C.c_int, vp])
+    if hasattr(L, "qtts_hip_xgemm_case"):
+        L.qtts_hip_xgemm_plan.restype = C.c_int
+        L.qtts_hip_xgemm_plan.argtypes = [C.POINTER(XGemmDesc), C.c_size_t, C.c_int, _ip, _ip]
+        L.qtts_hip_xgemm_case.restype = C.c_int
+        L.qtts_hip_xgemm_case.argtypes = [C.POINTER(XGemmDesc), C.c_size_t, C.c_int, _ip, _ip, vp]
+        L.qtts_hip_xgemm_func.restype = C.c_int
+        L.qtts_hip_xgemm_func.argtypes = [vp] * 4 + [C.c_int] * 3 + [vp]
     _LIB = L
     return L
 
@@ -850,3 +884,37 @@ class Kernels:
             return False
         _ok(rc, "resident_matvec_rows")
         return True
+
+    @staticmethod
+    def xgemm_plan(desc, part_elems=0, force_path=-1):
+        """The codec dispatcher's plan for one contraction (qtts_hip_xgemm_plan;
+        host only, no device needed): (path, splits), or None where force_path
+        does not cover the shape."""
+        path, splits = C.c_int(-1), C.c_int(0)
+        rc = lib().qtts_hip_xgemm_plan(C.byref(desc), part_elems, force_path, C.byref(path), C.byref(splits))
+        if rc == 1:
+            return None
+        _ok(rc, "xgemm_plan")
+        return path.value, splits.value
+
+    @staticmethod
+    def xgemm_case(desc, part_elems=0, force_path=-1):
+        """Runs one contraction of the codec's GEMM family (qtts_hip_xgemm_case)
+        with a split workspace of exactly part_elems floats: (path, splits)
+        that ran, or None where force_path does not cover the shape (nothing
+        ran)."""
+        path, splits = C.c_int(-1), C.c_int(0)
+        rc = lib().qtts_hip_xgemm_case(C.byref(desc), part_elems, force_path, C.byref(path), C.byref(splits),
+                                       _stream())
+        if rc == 1:
+            return None
+        _ok(rc, "xgemm_case")
+        return path.value, splits.value
+
+    @staticmethod
+    def xgemm_func(out, x, fn, alpha=None, inv_beta=None):
+        """The codec GEMMs' own device functions elementwise (qtts_hip_xgemm_func):
+        fn 0 snake with its sin^2 (x [C, L], alpha / inv_beta [C]), 1 expf, 2 tanhf."""
+        ch, ln = (x.shape[0], x.shape[1]) if fn == 0 else (1, x.numel())
+        _ok(lib().qtts_hip_xgemm_func(_ptr(out), _ptr(x), _ptr(alpha), _ptr(inv_beta), ch, ln, fn, _stream()),
+            "xgemm_func")

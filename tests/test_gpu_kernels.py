@@ -3,8 +3,12 @@ the reference's golden I/O and the CPU oracle.
 
 Bars: integer outputs (sampled ids, RNG state) bit-exact; fp32 GEMV within
 |err| <= 2e-6 * sum|a_i x_i| + 1e-6 (accumulation order differs: 8-lane
-partials + KSPLIT slots vs the reference's sequential loop); codec convs on
-the fp32 MFMA path within 2e-5 abs + 1e-4 rel.
+partials + KSPLIT slots vs the reference's sequential loop); codec convs and
+transposed convs (the bf16 3-plane k_convb kernels, or k_xgemm where the
+dispatcher sends a small shape there) within 2e-5 abs + 1e-4 rel of the
+golden / float64 output and within xgemm_ref.py's float64 bound
+(2e-6 * sum|w x| + 1e-6 and the epilogue's 2e-7), which test_gpu_xgemm.py holds
+every kernel of that family to path by path.
 """
 import ctypes as C
 
@@ -16,9 +20,17 @@ from oracle_py import fptr
 from qtts_io import f32_to_bf16
 
 import qtts
+from xgemm_ref import conv_reference
 
 pytestmark = pytest.mark.gpu
 K = golden("kernels.npz")
+
+
+def assert_conv_bound(got, x, w, b, k, dil=1, stride=0):
+    """every element within the codec contraction bound of the float64 conv"""
+    ref, bound = conv_reference(x, w, b, k, dil, stride)
+    err = np.abs(got.astype(np.float64) - ref)
+    assert np.all(err <= bound), float(np.max(err / bound))
 
 
 def T(a, dev, dtype=None):
@@ -253,6 +265,8 @@ def test_causal_conv1d_golden(gpu, i):
                                ci, co, k, L, d, g)
     torch.cuda.synchronize()
     np.testing.assert_allclose(out.cpu().numpy().reshape(co, L), K[f"conv{i}_y"], atol=2e-5, rtol=1e-4)
+    if g == 1:   # (the depthwise cases run k_dwconv, not the contraction family)
+        assert_conv_bound(out.cpu().numpy().reshape(co, L), K[f"conv{i}_x"], K[f"conv{i}_w"], K[f"conv{i}_b"], k, d)
 
 
 @pytest.mark.parametrize("ci,co,k,L,d", [(96, 96, 7, 8192, 9), (64, 192, 3, 4096, 1), (32, 128, 1, 6144, 1),
@@ -275,6 +289,7 @@ def test_causal_conv1d_vocoder_shapes(gpu, ci, co, k, L, d):
     for tap in range(k):
         ref += w[:, :, tap].astype(np.float64) @ xp[:, tap * d: tap * d + L]
     np.testing.assert_allclose(out.cpu().numpy().reshape(co, L), ref, atol=2e-5, rtol=1e-4)
+    assert_conv_bound(out.cpu().numpy().reshape(co, L), x, w, b, k, d)
 
 
 @pytest.mark.parametrize("i", range(5))
@@ -286,6 +301,7 @@ def test_transposed_conv1d_golden(gpu, i):
                                    T(K[f"tconv{i}_b"], gpu), ci, co, k, s, L)
     torch.cuda.synchronize()
     np.testing.assert_allclose(out.cpu().numpy().reshape(co, L * s), K[f"tconv{i}_y"], atol=2e-5, rtol=1e-4)
+    assert_conv_bound(out.cpu().numpy().reshape(co, L * s), K[f"tconv{i}_x"], K[f"tconv{i}_w"], K[f"tconv{i}_b"], k, 1, s)
 
 
 @pytest.mark.parametrize("ci,co,k,s,L", [(1536, 768, 16, 8, 512), (192, 96, 6, 3, 8192), (768, 384, 10, 5, 1024),
@@ -308,6 +324,7 @@ def test_transposed_conv1d_vocoder_shapes(gpu, ci, co, k, s, L):
         full[:, j: j + (L - 1) * s + 1: s] += w[:, :, j].astype(np.float64).T @ xd
     ref = full[:, :L * s] + b.astype(np.float64)[:, None]
     np.testing.assert_allclose(out.cpu().numpy().reshape(co, L * s), ref, atol=2e-5, rtol=1e-4)
+    assert_conv_bound(out.cpu().numpy().reshape(co, L * s), x, w, b, k, 1, s)
 
 
 def test_snake_golden(gpu):
