@@ -112,8 +112,15 @@ int qtts_dev_get_kv(qtts_dev_t *dev, int layer, int b, int pos0, int n, float *k
 int qtts_dev_get_attn(qtts_dev_t *dev, float *qkv_host, float *att_host);
 
 /* ---- generation (batch of nb utterances in lock-step frames) ---- */
-/* Allocates state for nb slots, max_frames frames (KV capacity = max_prefill
- * + max_frames), resets counters / RNG, (re)captures the frame graphs. */
+/* Lock-step slots per context: 1 plain decode, 2..16 the 16-row matrix-core
+ * batch kernels, 17..64 the wide batch kernel (one weight read per GEMV for
+ * every slot). */
+#define QTTS_HIP_MAX_BATCH 64
+/* Allocates state for nb slots (1..QTTS_HIP_MAX_BATCH), max_frames frames (KV
+ * capacity = max_prefill + max_frames), resets counters / RNG, (re)captures
+ * the frame graphs.  -1 with one line on stderr, before anything is
+ * allocated, for more slots than that, and above 16 slots for a model with a
+ * decode weight shape the wide batch kernel does not take (named). */
 int qtts_dev_begin(qtts_dev_t *dev, int nb, int max_frames, int max_prefill, const qtts_gen_params_t *p);
 /* Prompt for slot b (layout built by the host, c/qwen_tts.c:1147-1243):
  *   text_ids[n_text]  text tokens to embed+project (text_embedding -> fc1 ->
@@ -291,7 +298,9 @@ int qtts_hip_matvec_bf16(float *out_dev, const uint16_t *A_dev, const float *x_d
 int qtts_hip_rmsnorm_matvec_bf16(float *out_dev, const uint16_t *A_dev, const float *x_dev, const float *w_dev,
                                  float eps, int rows, int cols, int batch, void *stream);
 /* the decode-loop GEMV dispatcher on `batch` lock-step rows (w_dev NULL: no norm):
- * batch 1 -> the batch-1 weight stream, 2..16 -> the matrix-core batch kernel
+ * batch 1 -> the batch-1 weight stream, 2..16 -> the matrix-core batch kernel,
+ * 17..64 -> the wide matrix-core batch kernel (one launch, one weight read for
+ * all rows; -1 where it does not cover the shape: rows % 16, cols % 32)
  * (c/qwen_tts_kernels.c:27 + :95 per row) */
 int qtts_hip_decode_matvec_bf16(float *out_dev, const uint16_t *A_dev, const float *x_dev, const float *w_dev,
                                 float eps, int rows, int cols, int batch, void *stream);
@@ -395,6 +404,45 @@ int qtts_hip_attn_o_pair(float *part_dev, const float *qkv_dev, float *kc_dev, f
 int qtts_hip_resident_matvec_rows_bf16(float *out_dev, const uint16_t *A_dev, const float *x_dev, const float *w_dev,
                                        float eps, int rows, int cols, int epi, const float *part_dev, int n_part,
                                        float *x_new_dev, int nrows, void *stream);
+/* One lock-step batch decode GEMV with everything the decode frame hands the
+ * batch kernels, on its own (a parity entry as qtts_hip_attn_decode is: it
+ * allocates its split-K scratch, launches, synchronises, frees):
+ *   y[b][r] = epi( inv[b] * sum_c A[r][c] * (xin[b][c] * norm_w[c]) ),  b < batch
+ * batch 2..16 runs k_gemvb (else k_gemvm), 17..64 the wide kernel k_gemvx.
+ *   src 0: xin = x_dev rows (stride ldx) + part_in_dev [n_part_in][batch][cols]
+ *          summed in order first (NULL: none; 1..4);
+ *   src 1 / 2: xin = row id(b) of a bf16 / fp32 table [*][cols], id(b) =
+ *          ids_dev[ids_off + b * ids_bstride + row_sel_dev[b] * ids_rstride]
+ *          (row_sel_dev NULL: no selector term).
+ *   norm_w_dev NULL: no RMSNorm (inv = 1, norm_w = 1).  xcopy_dev [batch][cols]
+ *   (NULL: none): xin as read (xcopy_normed 0) or normalised (1).
+ *   epi 0 store, 1 +bias, 2 SiLU(+bias), 3 residual (y += ...), 4 SwiGLU over
+ *   interleaved gate|up row quads (rows / 2 outputs); y rows at stride ldy.
+ *   kz 0: no split-K; 2..4 workgroup columns over cols (epi 3 and src 0 without
+ *   norm / xcopy only): self_reduce 1 -- the last column to finish a row block
+ *   adds the partials in order into y (tickets kept by the library between
+ *   calls, left zero by every launch); 0 -- consumer-add: the raw partials go
+ *   to part_out_dev [kz][batch][rows] and y is not touched.
+ * Returns 1 (nothing launched) where no batch kernel covers the case, -1 on an
+ * argument or launch error. */
+typedef struct {
+    int rows, cols, batch;
+    const uint16_t *A;                /* bf16 [rows][cols] */
+    int src;
+    const float *x; int ldx;
+    const void *table;
+    const int *ids; int ids_bstride, ids_rstride, ids_off;
+    const int *row_sel;
+    const float *part_in; int n_part_in;
+    const float *norm_w; float eps;
+    float *xcopy; int xcopy_normed;
+    int epi;
+    const float *bias;
+    float *y; int ldy;
+    int kz, self_reduce;
+    float *part_out;
+} qtts_bgemv_desc_t;
+int qtts_hip_batch_matvec_case(const qtts_bgemv_desc_t *d, void *stream);
 /* One contraction of the codec's GEMM family (k_codec.hip: qtts_xgemm), as the
  * codec describes it to its dispatcher.  Modes (qtts_codec.h):
  *   amode 0 rows A[m*lda+k], 1 trans A[k*lda+m], 2 transposed-conv weights [ci][co][Kw];
@@ -462,6 +510,10 @@ long long qtts_hip_tengine_layers(void);
  * library loaded: positions 0 and 1 run as one two-row pass at batch 1
  * (QTTS_HIP_ST_PAIR=0 at creation: the 16 single-row passes). */
 long long qtts_hip_st_pair_passes(void);
+/* Launches of the wide batch GEMV (k_gemvx, 17..64 rows) enqueued (or captured
+ * into a frame graph) since the library loaded: one per decode GEMV whatever
+ * the slot count, none at 16 slots or fewer. */
+long long qtts_hip_gemv_wide_launches(void);
 
 /* Diagnostics: run ONE frame eagerly on the current generation state with an
  * event pair around every kernel launch on the context stream.  kind[i]:

@@ -233,13 +233,20 @@ qwen_tts_ctx_t *qwen_tts_load_on(const char *model_dir, int device);
 #define QWEN_TTS_KV_BF16 1
 int qwen_tts_set_kv_cache_dtype(qwen_tts_ctx_t *ctx, int dtype);
 int qwen_tts_kv_cache_dtype(qwen_tts_ctx_t *ctx);
-/* nb utterances in lock-step frames on this ctx's GPU (weights read once per
- * frame for all of them).  out_audio[i] malloc'd (caller frees), out_samples[i]
- * set; returns 0 when every utterance produced audio. */
+/* Most lock-step slots of one ctx (qwen_tts_generate_batch, the slots of
+ * qwen_tts_generate_queue, qwen_tts_generate_voice_clone_batch): up to 16 run
+ * on the 16-row matrix-core batch kernels, 17..64 on the wide batch kernel. */
+#define QWEN_TTS_MAX_BATCH 64
+/* nb (1..QWEN_TTS_MAX_BATCH) utterances in lock-step frames on this ctx's GPU
+ * (weights read once per frame for all of them).  out_audio[i] malloc'd
+ * (caller frees), out_samples[i] set; returns 0 when every utterance produced
+ * audio, -1 with a message for nb above the limit, before the device is
+ * touched. */
 int qwen_tts_generate_batch(qwen_tts_ctx_t *ctx, int nb, const char *const *texts, const char *const *speakers,
                             const char *const *languages, float **out_audio, int *out_samples);
 /* Work queue (no c/ counterpart): nq utterances on at most nb
- * lock-step slots.  When a slot's utterance stops (EOS, or max_new_tokens /
+ * (1..QWEN_TTS_MAX_BATCH; -1 with a message above it, before the device is
+ * touched) lock-step slots.  When a slot's utterance stops (EOS, or max_new_tokens /
  * fixed_codec_tokens frames), the next queued utterance is prefilled into that
  * slot inside the live batch, so a batch of EOS-variable lengths keeps its
  * slots busy instead of riding stopped rows to the longest one.  Each
@@ -281,8 +288,9 @@ float *qwen_tts_generate_voice_clone(qwen_tts_ctx_t *ctx, const char *text, cons
  * reference ++ generated decode).  The non-streamed call cuts at the Python
  * reference's float position int(ref / total * samples), which for ~5 % of
  * (ref, total) pairs is one sample earlier. */
-/* nb voice-clone utterances in lock-step frames (BASELINE C5: batch 8 on one
- * GPU); per-slot arrays as above (ref_codes[b] / spk_embeds[b] may be NULL).
+/* nb (1..QWEN_TTS_MAX_BATCH; -1 with a message above it) voice-clone
+ * utterances in lock-step frames (BASELINE C5: batch 8 on one GPU); per-slot
+ * arrays as above (ref_codes[b] / spk_embeds[b] may be NULL).
  * Returns 0 when every utterance produced audio. */
 int qwen_tts_generate_voice_clone_batch(qwen_tts_ctx_t *ctx, int nb, const char *const *texts,
                                         const char *const *ref_texts, const int *const *ref_codes,
@@ -305,7 +313,10 @@ int qwen_tts_generate_voice_clone_batch(qwen_tts_ctx_t *ctx, int nb, const char 
  *   codebooks), malloc'd [ceil(n / 1920)][16] ints, *out_frames set.
  * qwen_tts_generate_voice_clone_audio[_batch]: encode (all references in one
  *   zero-padded batch, as the tokenizer does) + qwen_tts_generate_voice_clone
- *   [_batch]; ICL mode needs ref_text, x_vector_only drops the codes.
+ *   [_batch]; ICL mode needs ref_text, x_vector_only drops the codes.  The
+ *   batch form stays at 1..16 utterances, the encoders' batch (not
+ *   QWEN_TTS_MAX_BATCH): encode larger sets in groups and decode them with
+ *   qwen_tts_generate_voice_clone_batch.
  * All return NULL / -1 on error with a message on stderr; buffers are the
  * caller's to free(). */
 float *qwen_tts_speaker_embedding(qwen_tts_ctx_t *ctx, const float *wav, int n_samples, int *out_dim);

@@ -436,6 +436,11 @@ static void wide_config(int R, int C, int epi, int &ks_out, int &nthr_out) {
 
 int qtts_gemv(const GemvArgs &in, hipStream_t st) {
     GemvArgs a = in;
+    if (a.nb > 16 && a.nb <= 64) {   // wide lock-step batch: one launch for all rows (k_gemvx.hip), or none
+        const int rc = qtts_gemvx(a, st);
+        if (rc == 1) fprintf(stderr, "qtts_gemv: the wide batch kernel does not cover R=%d C=%d nb=%d\n", a.R, a.C, a.nb);
+        return rc ? -1 : 0;
+    }
     if (a.C % 64 || a.nb < 1 || a.nb > 16 || a.R < 1) {
         fprintf(stderr, "qtts_gemv: unsupported shape R=%d C=%d nb=%d\n", a.R, a.C, a.nb);
         return -1;

@@ -107,6 +107,11 @@ bool qtts_gemvw_amerge_ok(int R, int C);
 int qtts_gemvm(const GemvArgs &a, hipStream_t st);
 // the same with the x rows sliced per wave (k_gemvb.hip, tried first); 1 = not covered
 int qtts_gemvb(const GemvArgs &a, hipStream_t st);
+// wide lock-step batch (17..64 rows): one moving 32-column K step per wave over
+// all rows (k_gemvx.hip); 1 = not covered.  qtts_gemvx_shape_ok: the weight
+// shapes it takes (qtts_dev_begin refuses a model with another above 16 slots)
+int qtts_gemvx(const GemvArgs &a, hipStream_t st);
+bool qtts_gemvx_shape_ok(int R, int C);
 // multi-row (2..64) projection on the bf16 matrix cores (k_mgemm.hip); 1 = not covered
 int qtts_mgemm(const GemvArgs &a, float *inv_scratch, hipStream_t st, float *part = nullptr, size_t part_elems = 0);
 // split-K partial floats qtts_mgemm may use for `rows` activation rows and outputs <= widest

@@ -1661,8 +1661,41 @@ static bool same_params(const qtts_gen_params_t &a, const qtts_gen_params_t &b) 
     return memcmp(&a, &b, sizeof a) == 0;
 }
 
+// Above 16 slots every decode GEMV is one launch of the wide batch kernel
+// (k_gemvx.hip) or nothing: a model with a weight shape it does not take is
+// refused here, by name, instead of at the frame graph's capture.
+static bool wide_shapes_ok(const qtts_dev *dv) {
+    const qtts_dims_t &d = dv->d;
+    const struct { const char *name; int R, C; bool used; } sh[] = {
+        {"talker q|k|v", dv->QKV(), d.H, true},
+        {"talker O", d.H, d.NH * d.HD, true},
+        {"talker gate|up", 2 * d.I, d.H, true},
+        {"talker down", d.H, d.I, true},
+        {"codec head", d.V, d.H, true},
+        {"sub-talker input projection", d.Hs, d.H, dv->st_proj != nullptr},
+        {"sub-talker q|k|v", dv->QKVs(), d.Hs, true},
+        {"sub-talker O", d.Hs, d.NHs * d.HDs, true},
+        {"sub-talker gate|up", 2 * d.Is, d.Hs, true},
+        {"sub-talker down", d.Hs, d.Is, true},
+        {"sub-talker lm head", d.Vs, d.Hs, true},
+    };
+    for (const auto &s : sh)
+        if (s.used && !qtts_gemvx_shape_ok(s.R, s.C)) {
+            fprintf(stderr, "qtts_dev_begin: more than 16 slots refused: the wide batch GEMV does not take the %s "
+                            "weights [%d][%d] (rows %% 16, columns %% 32)\n", s.name, s.R, s.C);
+            return false;
+        }
+    return true;
+}
+
 extern "C" int qtts_dev_begin(qtts_dev_t *dv, int nb, int max_frames, int max_prefill, const qtts_gen_params_t *p) {
     if (!dv || nb < 1 || max_frames < 1) return -1;
+    if (nb > QTTS_HIP_MAX_BATCH) {
+        fprintf(stderr, "qtts_dev_begin: %d slots refused (at most %d lock-step slots per context)\n", nb,
+                QTTS_HIP_MAX_BATCH);
+        return -1;
+    }
+    if (nb > 16 && !wide_shapes_ok(dv)) return -1;
     hipSetDevice(dv->device);
     CKI(join_prime(dv));   // a prime left pending by a run that pushed no frames
     free_force(dv);        // forcing and taps last for one run (and their record until the next begins)
@@ -2583,7 +2616,7 @@ extern "C" int qtts_hip_rmsnorm_matvec_bf16(float *out, const uint16_t *A, const
 }
 
 // the decode dispatcher itself (qtts_gemv): batch 1 -> k_gemv1, 2..16 ->
-// k_gemvm (matrix cores) where covered, else k_gemv
+// k_gemvm (matrix cores) where covered, else k_gemv, 17..64 -> k_gemvx
 extern "C" int qtts_hip_decode_matvec_bf16(float *out, const uint16_t *A, const float *x, const float *w, float eps,
                                            int rows, int cols, int batch, void *stream) {
     GemvArgs a = gv(A, rows, cols, x, cols, out, rows, batch, EPI_STORE);
@@ -2747,6 +2780,59 @@ extern "C" int qtts_hip_resident_matvec_rows_bf16(float *out, const uint16_t *A,
     if (part) { a.xadd = part; a.n_xadd = n_part; a.ld_xadd = nrows * cols; a.ldb_xadd = cols; }
     if (x_new) { a.xcopy = x_new; a.ldxc = cols; a.xcopy_normed = 0; }
     return nrows == 2 ? qtts_gemvw_pair(a, (hipStream_t)stream) : qtts_gemvw(a, (hipStream_t)stream);
+}
+
+// One lock-step batch GEMV (2..16 rows: k_gemvb, else k_gemvm; 17..64:
+// k_gemvx) with everything the decode frame can ask of it, on its own.  The
+// split-K scratch is allocated here; the tickets of the self-reducing form
+// live as long as the library (zeroed once: every launch leaves them zero, as
+// the frame graph relies on).  1 = no batch kernel covers the case.
+extern "C" int qtts_hip_batch_matvec_case(const qtts_bgemv_desc_t *d, void *stream) {
+    if (!d || !d->A || d->rows < 1 || d->cols < 1 || d->batch < 2 || d->batch > QTTS_HIP_MAX_BATCH) return -1;
+    if (d->epi < EPI_STORE || d->epi > EPI_SWIGLU || d->src < 0 || d->src > 2) return -1;
+    if ((d->epi == EPI_BIAS || d->epi == EPI_BIAS_SILU) && !d->bias) return -1;
+    if (d->src == 0 ? !d->x : (!d->table || !d->ids)) return -1;
+    if (d->part_in && (d->src != 0 || d->n_part_in < 1 || d->n_part_in > 4)) return -1;
+    if (d->kz < 0 || d->kz == 1 || d->kz > 4) return -1;
+    if (d->kz >= 2 && (d->self_reduce ? !d->y : !d->part_out)) return -1;
+    if (d->kz < 2 && !d->y) return -1;
+    hipStream_t st = (hipStream_t)stream;
+    GemvArgs a = gv(d->A, d->rows, d->cols, d->src == 0 ? d->x : nullptr, d->ldx, d->y, d->ldy, d->batch, d->epi);
+    if (d->src == 1) a.table = (const bf16_t *)d->table;
+    if (d->src == 2) a.table_f32 = (const float *)d->table;
+    a.ids = d->ids; a.ids_bstride = d->ids_bstride; a.ids_rstride = d->ids_rstride; a.ids_off = d->ids_off;
+    a.row_sel = d->row_sel;
+    if (d->part_in) {
+        a.xadd = d->part_in; a.n_xadd = d->n_part_in; a.ld_xadd = d->batch * d->cols; a.ldb_xadd = d->cols;
+    }
+    a.norm_w = d->norm_w; a.eps = d->eps;
+    if (d->xcopy) { a.xcopy = d->xcopy; a.ldxc = d->cols; a.xcopy_normed = d->xcopy_normed; }
+    a.bias = d->bias;
+    float *scratch = nullptr;
+    static int *ticks = nullptr;   // (one device: the parity entry of a test process)
+    if (d->kz >= 2) {
+        a.kz = d->kz; a.ld_ypart = (size_t)d->batch * d->rows;
+        if (d->self_reduce) {
+            if (!ticks) {
+                CK(hipMalloc((void **)&ticks, QTTS_GM_TICKS * sizeof(int)));
+                CK(hipMemset(ticks, 0, QTTS_GM_TICKS * sizeof(int)));
+            }
+            CK(hipMalloc((void **)&scratch, (size_t)d->kz * a.ld_ypart * 4));
+            a.ypart = scratch; a.tick = ticks;
+        } else {
+            a.ypart = d->part_out; a.y = nullptr;
+        }
+    }
+    int rc;
+    if (d->batch > 16) {
+        rc = qtts_gemvx(a, st);
+    } else {
+        rc = qtts_gemvb(a, st);
+        if (rc == 1) rc = qtts_gemvm(a, st);
+    }
+    if (hipStreamSynchronize(st) != hipSuccess) rc = -1;
+    if (scratch) hipFree(scratch);
+    return rc;
 }
 
 // One frame run eagerly with an event pair around every kernel launch on the

@@ -1090,9 +1090,19 @@ float *qwen_tts_generate(qwen_tts_ctx_t *ctx, const char *text, const char *spea
     return audio;
 }
 
+/* more lock-step slots than a ctx runs: refused at the door (an arming is
+ * consumed as by every failed call) */
+static int batch_refused(qwen_tts_ctx_t *ctx, const char *who, int nb) {
+    if (nb <= QWEN_TTS_MAX_BATCH) return 0;
+    fprintf(stderr, "Error: %s: %d slots, at most %d per context\n", who, nb, QWEN_TTS_MAX_BATCH);
+    force_disarm(ctx);
+    return 1;
+}
+
 int qwen_tts_generate_batch(qwen_tts_ctx_t *ctx, int nb, const char *const *texts, const char *const *speakers,
                             const char *const *languages, float **out_audio, int *out_samples) {
     if (!ctx || nb < 1 || !texts || !out_audio || !out_samples) return -1;
+    if (batch_refused(ctx, "qwen_tts_generate_batch", nb)) return -1;
     return run_batch(ctx, nb, texts, speakers, languages, out_audio, out_samples, now_ms(), NULL, NULL);
 }
 
@@ -1133,6 +1143,7 @@ int qwen_tts_generate_queue(qwen_tts_ctx_t *ctx, int nq, const char *const *text
         return -1;
     }
     if (!ctx || !ctx->hip || nq < 1 || nb < 1 || !texts || !out_audio || !out_samples) return -1;
+    if (batch_refused(ctx, "qwen_tts_generate_queue", nb)) return -1;
     qtts_dev_t *dev = (qtts_dev_t *)ctx->hip;
     const qwen_tts_config_t *c = &ctx->config;
     const int G = c->num_code_groups;
@@ -1330,6 +1341,7 @@ static int vclone_run(qwen_tts_ctx_t *ctx, int nb, const char *const *texts, con
                       const char *const *languages, int non_streaming, float **out_audio, int *out_samples,
                       const stream_t *stream) {
     if (!ctx || nb < 1 || !texts || !out_audio || !out_samples || (stream && nb != 1)) return -1;
+    if (batch_refused(ctx, "qwen_tts_generate_voice_clone_batch", nb)) return -1;
     for (int b = 0; b < nb; b++) { out_audio[b] = NULL; out_samples[b] = 0; }
     vclone_t *vcs = (vclone_t *)calloc(nb, sizeof(vclone_t));
     int rc = vcs ? 0 : -1;

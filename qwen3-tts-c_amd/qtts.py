@@ -97,7 +97,33 @@ EXPORTS = [
     "qwen_tts_force_codes", "qwen_tts_tap_draw", "qwen_tts_last_drawn", "qwen_tts_tap_result",
     "qtts_dev_force", "qtts_dev_tap", "qtts_dev_get_drawn", "qtts_dev_get_tap",
     "qtts_hip_xgemm_plan", "qtts_hip_xgemm_case", "qtts_hip_xgemm_func",
+    "qtts_hip_batch_matvec_case", "qtts_hip_gemv_wide_launches",
 ]
+
+MAX_BATCH = 64   # QWEN_TTS_MAX_BATCH / QTTS_HIP_MAX_BATCH: lock-step slots per context
+
+
+class BGemvDesc(C.Structure):
+    """qtts_bgemv_desc_t (include/qtts_hip.h): one lock-step batch decode GEMV;
+    the pointers are device addresses."""
+    _fields_ = [
+        ("rows", C.c_int), ("cols", C.c_int), ("batch", C.c_int),
+        ("A", C.c_void_p),
+        ("src", C.c_int),
+        ("x", C.c_void_p), ("ldx", C.c_int),
+        ("table", C.c_void_p),
+        ("ids", C.c_void_p), ("ids_bstride", C.c_int), ("ids_rstride", C.c_int), ("ids_off", C.c_int),
+        ("row_sel", C.c_void_p),
+        ("part_in", C.c_void_p), ("n_part_in", C.c_int),
+        ("norm_w", C.c_void_p), ("eps", C.c_float),
+        ("xcopy", C.c_void_p), ("xcopy_normed", C.c_int),
+        ("epi", C.c_int),
+        ("bias", C.c_void_p),
+        ("y", C.c_void_p), ("ldy", C.c_int),
+        ("kz", C.c_int), ("self_reduce", C.c_int),
+        ("part_out", C.c_void_p),
+    ]
+
 
 class XGemmDesc(C.Structure):
     """qtts_xgemm_desc_t (include/qtts_hip.h): one contraction of the codec's
@@ -311,6 +337,11 @@ def lib():
         L.qtts_hip_xgemm_case.argtypes = [C.POINTER(XGemmDesc), C.c_size_t, C.c_int, _ip, _ip, vp]
         L.qtts_hip_xgemm_func.restype = C.c_int
         L.qtts_hip_xgemm_func.argtypes = [vp] * 4 + [C.c_int] * 3 + [vp]
+    if hasattr(L, "qtts_hip_batch_matvec_case"):
+        L.qtts_hip_batch_matvec_case.restype = C.c_int
+        L.qtts_hip_batch_matvec_case.argtypes = [C.POINTER(BGemvDesc), vp]
+        L.qtts_hip_gemv_wide_launches.restype = C.c_longlong
+        L.qtts_hip_gemv_wide_launches.argtypes = []
     _LIB = L
     return L
 
@@ -884,6 +915,46 @@ class Kernels:
             return False
         _ok(rc, "resident_matvec_rows")
         return True
+
+    @staticmethod
+    def batch_matvec_case(A_u16, batch, y, x=None, table=None, ids_i32=None, ids_bstride=1, ids_rstride=0, ids_off=0,
+                          row_sel_i32=None, part_in=None, norm_w=None, eps=1e-6, xcopy=None, xcopy_normed=False,
+                          epi=0, bias=None, kz=0, self_reduce=True, part_out=None):
+        """One lock-step batch decode GEMV (qtts_hip_batch_matvec_case) on
+        `batch` rows (2..16: k_gemvb / k_gemvm, 17..64: k_gemvx).  A_u16 [rows,
+        cols] bf16 bits.  Source: x [batch, cols] fp32 (+ part_in [n, batch,
+        cols] added in order), or a bf16-bit / fp32 table [*, cols] gathered by
+        ids_i32[ids_off + b * ids_bstride + row_sel_i32[b] * ids_rstride].
+        y [batch, rows] (epi 4: rows / 2).  kz >= 2: split-K, self-reducing
+        into y (epi 3) or, self_reduce False, raw partials to part_out [kz,
+        batch, rows].  False where no batch kernel covers the case."""
+        d = BGemvDesc()
+        d.rows, d.cols, d.batch = int(A_u16.shape[0]), int(A_u16.shape[1]), int(batch)
+        d.A = _ptr(A_u16)
+        if table is not None:
+            d.src = 1 if table.element_size() == 2 else 2
+            d.table, d.ids = _ptr(table), _ptr(ids_i32)
+            d.ids_bstride, d.ids_rstride, d.ids_off = ids_bstride, ids_rstride, ids_off
+            d.row_sel = _ptr(row_sel_i32)
+        else:
+            d.src, d.x, d.ldx = 0, _ptr(x), int(x.stride(0))
+        if part_in is not None:
+            d.part_in, d.n_part_in = _ptr(part_in), int(part_in.shape[0])
+        d.norm_w, d.eps = _ptr(norm_w), eps
+        d.xcopy, d.xcopy_normed = _ptr(xcopy), int(bool(xcopy_normed))
+        d.epi, d.bias = epi, _ptr(bias)
+        d.y, d.ldy = _ptr(y), (int(y.stride(0)) if y is not None else 0)
+        d.kz, d.self_reduce, d.part_out = kz, int(bool(self_reduce)), _ptr(part_out)
+        rc = lib().qtts_hip_batch_matvec_case(C.byref(d), _stream())
+        if rc == 1:
+            return False
+        _ok(rc, "batch_matvec_case")
+        return True
+
+    @staticmethod
+    def gemv_wide_launches():
+        """Wide batch GEMV (k_gemvx) launches enqueued or captured since the library loaded."""
+        return int(lib().qtts_hip_gemv_wide_launches())
 
     @staticmethod
     def xgemm_plan(desc, part_elems=0, force_path=-1):
