@@ -298,9 +298,11 @@ int qtts_hip_matvec_bf16(float *out_dev, const uint16_t *A_dev, const float *x_d
 int qtts_hip_rmsnorm_matvec_bf16(float *out_dev, const uint16_t *A_dev, const float *x_dev, const float *w_dev,
                                  float eps, int rows, int cols, int batch, void *stream);
 /* the decode-loop GEMV dispatcher on `batch` lock-step rows (w_dev NULL: no norm):
- * batch 1 -> the batch-1 weight stream, 2..16 -> the matrix-core batch kernel,
- * 17..64 -> the wide matrix-core batch kernel (one launch, one weight read for
- * all rows; -1 where it does not cover the shape: rows % 16, cols % 32)
+ * batch 1 -> the batch-1 weight stream, 2..16 -> the batch GEMV planner's
+ * choice of k_gemvb, else k_gemvm, on the matrix cores (else the generic
+ * k_gemv), 17..64 -> the wide matrix-core batch kernel k_gemvx (one launch,
+ * one weight read for all rows; -1 where it does not cover the shape: rows %
+ * 16, cols % 32); qtts_hip_batch_matvec_plan reports the batch kernels' plan
  * (c/qwen_tts_kernels.c:27 + :95 per row) */
 int qtts_hip_decode_matvec_bf16(float *out_dev, const uint16_t *A_dev, const float *x_dev, const float *w_dev,
                                 float eps, int rows, int cols, int batch, void *stream);
@@ -443,6 +445,24 @@ typedef struct {
     float *part_out;
 } qtts_bgemv_desc_t;
 int qtts_hip_batch_matvec_case(const qtts_bgemv_desc_t *d, void *stream);
+/* The planner's answer for that case: which batch kernel (kernel: 0 none, 1
+ * k_gemvm, 2 k_gemvb, 4 k_gemvx), its n_tmpl template integers in the kernel's
+ * order (the last is the source kind: 0 x rows, 1 x + partials, 2 bf16 table,
+ * 3 fp32 table, 4 decided at run time), the launch geometry and the dynamic LDS
+ * bytes; tpw / cch are k_gemvm's run-time arguments (tiles per workgroup,
+ * staged column chunk; 0 for the others).  The same descriptor and the same
+ * results as qtts_hip_batch_matvec_case (0 planned, 1 not covered, -1 error).
+ * Host only: no pointer is dereferenced (their alignment is looked at) and no
+ * device is needed. */
+typedef struct {
+    int kernel;
+    int n_tmpl, tmpl[5];
+    int src;
+    int grid_x, grid_y, block;
+    size_t lds_bytes;
+    int tpw, cch;
+} qtts_bgemv_plan_t;
+int qtts_hip_batch_matvec_plan(const qtts_bgemv_desc_t *d, qtts_bgemv_plan_t *out);
 /* One contraction of the codec's GEMM family (k_codec.hip: qtts_xgemm), as the
  * codec describes it to its dispatcher.  Modes (qtts_codec.h):
  *   amode 0 rows A[m*lda+k], 1 trans A[k*lda+m], 2 transposed-conv weights [ci][co][Kw];

@@ -437,7 +437,7 @@ static void wide_config(int R, int C, int epi, int &ks_out, int &nthr_out) {
 int qtts_gemv(const GemvArgs &in, hipStream_t st) {
     GemvArgs a = in;
     if (a.nb > 16 && a.nb <= 64) {   // wide lock-step batch: one launch for all rows (k_gemvx.hip), or none
-        const int rc = qtts_gemvx(a, st);
+        const int rc = qtts_bgemv(a, st);
         if (rc == 1) fprintf(stderr, "qtts_gemv: the wide batch kernel does not cover R=%d C=%d nb=%d\n", a.R, a.C, a.nb);
         return rc ? -1 : 0;
     }
@@ -490,8 +490,7 @@ int qtts_gemv(const GemvArgs &in, hipStream_t st) {
         return hipGetLastError() == hipSuccess ? 0 : -1;
     }
     if (a.nb >= 2) {   // lock-step batch: the matrix-core kernels (k_gemvb.hip, k_gemvm.hip) where they cover the shape
-        int rc = qtts_gemvb(a, st);
-        if (rc == 1) rc = qtts_gemvm(a, st);
+        const int rc = qtts_bgemv(a, st);
         if (rc != 1) return rc;
     }
     if (a.ypart || (a.xadd && a.nb >= 2)) {

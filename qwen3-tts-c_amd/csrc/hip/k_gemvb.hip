@@ -35,22 +35,13 @@
 // differs from the reference's (x * inv) * w by that reassociation only
 // (fp32, within the GEMV bar of tests/test_gpu_kernels.py); the products are
 // exact (3 x bf16 planes, as k_gemvm / k_mgemm).
-#include <algorithm>
+#include <string>
 
-#include "qtts_gemvm_dev.h"
+#include "qtts_bgemv_dev.h"
 
 namespace {
 
 using namespace qtts_gm;
-
-enum { GB_SRC_X = 0, GB_SRC_XADD = 1, GB_SRC_TAB = 2, GB_SRC_TABF = 3 };
-
-// id of the table row that batch row b reads (ids: a.ids + a.ids_off)
-__device__ __forceinline__ unsigned gb_row_id(const GemvArgs &a, const int *ids, int b) {
-    const int *p = ids + (size_t)b * a.ids_bstride;
-    if (a.row_sel) p += (size_t)a.row_sel[b] * a.ids_rstride;
-    return (unsigned)*p;
-}
 
 // SPW: 32-column K steps per wave; TPW: 16-row tiles per workgroup; NBC: 8 or
 // 16 (batch rows covered: the x units per lane are SPW * NBC / 8); PM:
@@ -117,11 +108,11 @@ __global__ __launch_bounds__(1024) void k_gemvb(const void *src, const int *ids,
     float4 xv[XQ];
     float4 pv[XQ][PM > 0 ? PM : 1];
     uint2 tq[XQ];
-    if constexpr (SRC == GB_SRC_TAB || SRC == GB_SRC_TABF) {
+    if constexpr (SRC == BG_SRC_TAB || SRC == BG_SRC_TABF) {
         unsigned id[XQ];
 #pragma unroll
-        for (int q = 0; q < XQ; ++q) id[q] = gb_row_id(a, ids, urow[q]);
-        if constexpr (SRC == GB_SRC_TAB) {
+        for (int q = 0; q < XQ; ++q) id[q] = row_id(a, ids, urow[q]);
+        if constexpr (SRC == BG_SRC_TAB) {
             const auto rt = rsrc(src);
 #pragma unroll
             for (int q = 0; q < XQ; ++q) {
@@ -137,7 +128,7 @@ __global__ __launch_bounds__(1024) void k_gemvb(const void *src, const int *ids,
         const auto rx = rsrc(src);
 #pragma unroll
         for (int q = 0; q < XQ; ++q) xv[q] = ld4(rx, (unsigned)urow[q] * (unsigned)a.ldx + (unsigned)(c0 + ucol));
-        if constexpr (SRC == GB_SRC_XADD) {
+        if constexpr (SRC == BG_SRC_XADD) {
             const auto rp = rsrc(xadd);
             const int np = a.n_xadd;
 #pragma unroll
@@ -174,9 +165,9 @@ __global__ __launch_bounds__(1024) void k_gemvb(const void *src, const int *ids,
 #pragma unroll
     for (int q = 0; q < XQ; ++q) {
         float4 v;
-        if constexpr (SRC == GB_SRC_TAB) v = make_float4(lo_f(tq[q].x), hi_f(tq[q].x), lo_f(tq[q].y), hi_f(tq[q].y));
+        if constexpr (SRC == BG_SRC_TAB) v = make_float4(lo_f(tq[q].x), hi_f(tq[q].x), lo_f(tq[q].y), hi_f(tq[q].y));
         else v = xv[q];
-        if constexpr (SRC == GB_SRC_XADD) {   // x + (p0 + p1 + ...), as GemvArgs::xadd prescribes
+        if constexpr (SRC == BG_SRC_XADD) {   // x + (p0 + p1 + ...), as GemvArgs::xadd prescribes
             const int np = a.n_xadd;
             float4 s = pv[q][0];
 #pragma unroll
@@ -325,106 +316,31 @@ __global__ __launch_bounds__(1024) void k_gemvb(const void *src, const int *ids,
 
 }  // namespace
 
-// Returns 1 when the shape is not covered (the caller uses k_gemvm), 0 ok,
-// -1 launch error.  QTTS_HIP_GEMVB=0 keeps k_gemvm for every shape (A/B).
-struct GbGeom { int SPW, TPW, W, NBC, PM, src; size_t smem; dim3 grid; };
-static bool gemvb_geom(const GemvArgs &a, GbGeom &g) {
-    if (a.nb < 2 || a.nb > 16 || a.R % 16 || a.C % 32 || (size_t)a.R * a.C * 2 >= ((size_t)1 << 31)) return false;
-    const bool tab = a.table != nullptr, tabf = !tab && a.table_f32 != nullptr;
-    if (tab) {
-        if (a.C % 4) return false;
-    } else if (tabf) {
-        if ((uintptr_t)a.table_f32 & 15 || a.C % 4) return false;
-    } else if (!a.x || a.ldx % 4 || ((uintptr_t)a.x & 15)) {
-        return false;
-    }
-    if (a.norm_w && ((uintptr_t)a.norm_w & 15)) return false;
-    if (a.xcopy && (a.ldxc % 4 || ((uintptr_t)a.xcopy & 15))) return false;
-    const bool xadd = !tab && !tabf && a.xadd != nullptr;
-    if (a.xadd && (tab || tabf || ((uintptr_t)a.xadd & 15) || a.ld_xadd % 4 || a.ldb_xadd % 4 || a.n_xadd < 1 ||
-                   a.n_xadd > 4))
-        return false;
-    const int kz = a.ypart ? a.kz : 1;
-    if (a.ypart && (kz < 2 || (a.tick && kz > 4) || a.norm_w || tab || tabf || a.xcopy || a.C % (32 * kz) ||
-                    ((uintptr_t)a.ypart & 3)))
-        return false;
-    if (a.tick && (!a.ypart || !a.y || a.epi != EPI_RESID)) return false;
-    // K slice per wave: the fewest steps that keep <= wmax waves (16; the
-    // QTTS_HIP_GB_W=8 A/B switch: 512-thread workgroups, two per CU, one tile each)
-    const char *gbw = getenv("QTTS_HIP_GB_W");
-    const int wmax = gbw && atoi(gbw) == 8 ? 8 : 16;
-    const int S = a.C / kz / 32;
-    int SPW = 1;
-    while (SPW < 8 && (S / SPW > wmax || S % SPW)) SPW *= 2;
-    if (S % SPW || S / SPW > 16) return false;
-    const int W = S / SPW;
-    const int NBC = a.nb <= 8 ? 8 : 16;
-    const int PM = xadd ? (a.n_xadd <= 2 ? 2 : 4) : 0;
-    // tiles per workgroup: about one round of workgroups over the 256 CUs,
-    // within the register file (estimate below) and W >= TPW epilogue waves
-    const int T = a.R / 16;
-    int TPW = wmax == 8 && W <= 8 ? 1 : (T * kz + 128) / 256;
-    TPW = std::max(1, std::min(TPW, 3));
-    if (SPW == 8 && TPW > 2) TPW = 2;
-    if (SPW <= 2 && TPW > 2) TPW = 2;
-    if (SPW == 1) TPW = 1;
-    // instantiations whose partials would not fit the 128 registers of a
-    // 1024-thread workgroup (hipcc -Rpass-analysis=kernel-resource-usage
-    // reports scratch for exactly these): k_gemvm takes those shapes
-    auto spills = [&](int tpw) {
-        if (PM == 0) return false;
-        if (NBC == 16) return SPW >= 4;
-        if (SPW == 8) return !(tpw == 1 && PM == 2);
-        return SPW == 4 && tpw == 3 && PM == 4;
-    };
-    while (TPW > 1 && (spills(TPW) || W < TPW)) --TPW;
-    if (spills(TPW) || W < TPW) return false;
-    const int wreg = std::max(a.nb * (32 * SPW + 4), TPW * 256);
-    const size_t smem = ((size_t)W * wreg + (size_t)W * 16) * sizeof(float);
-    if (smem > 160 * 1024) return false;
-    const dim3 grid((T + TPW - 1) / TPW, kz);
-    if (a.tick && (int)grid.x > QTTS_GM_TICKS) return false;
-    const int src = tab ? GB_SRC_TAB : tabf ? GB_SRC_TABF : xadd ? GB_SRC_XADD : GB_SRC_X;
-    g.SPW = SPW; g.TPW = TPW; g.W = W; g.NBC = NBC; g.PM = PM; g.src = src; g.smem = smem; g.grid = grid;
-    return true;
-}
-
+// (rocprofv3's spelling of the instantiation, built once per instantiation: the
+// bench looks its profile rows up by it)
 template <int SP, int TP, int NC, int PP, int SS>
-static void launch_gb(dim3 grid, dim3 block, size_t smem, hipStream_t st, const void *srcp, const int *idsp,
-                      const GemvArgs &a) {
-    hipLaunchKernelGGL((k_gemvb<SP, TP, NC, PP, SS>), grid, block, smem, st, srcp, idsp, a.W, a.xadd, a);
-    // (rocprofv3's spelling of the instantiation: the bench looks its profile rows up by it)
-    static char nm[64];
-    snprintf(nm, sizeof nm, "k_gemvb<%d, %d, %d, %d, %d>", SP, TP, NC, PP, SS);
-    qtts_last_kernel = nm;
+static void launch_gb(const BgPlan &p, hipStream_t st, const void *srcp, const int *idsp, const GemvArgs &a) {
+    hipLaunchKernelGGL((k_gemvb<SP, TP, NC, PP, SS>), p.grid, p.block, p.smem, st, srcp, idsp, a.W, a.xadd, a);
+    static const std::string nm = "k_gemvb<" + std::to_string(SP) + ", " + std::to_string(TP) + ", " +
+                                  std::to_string(NC) + ", " + std::to_string(PP) + ", " + std::to_string(SS) + ">";
+    qtts_last_kernel = nm.c_str();
 }
 
-int qtts_gemvb(const GemvArgs &in, hipStream_t st) {
-    // (read per call: launches happen at graph capture, and tests switch it
-    // per model instance)
-    const char *ge = getenv("QTTS_HIP_GEMVB");
-    if (ge && !atoi(ge)) return 1;
-    const GemvArgs &a = in;
-    GbGeom g;
-    if (!gemvb_geom(a, g)) return 1;
-    const int SPW = g.SPW, TPW = g.TPW, W = g.W, NBC = g.NBC, PM = g.PM, src = g.src;
-    const size_t smem = g.smem;
-    const dim3 grid = g.grid;
-    const bool tab = a.table != nullptr, tabf = !tab && a.table_f32 != nullptr;
-    const void *srcp = tab ? (const void *)a.table : tabf ? (const void *)a.table_f32 : (const void *)a.x;
-    const int *idsp = (tab || tabf) ? a.ids + a.ids_off : nullptr;
-    const dim3 block(64 * W);
-#define QTTS_GB(SP, TP, NC, PP, SS) launch_gb<SP, TP, NC, PP, SS>(grid, block, smem, st, srcp, idsp, a);
+// the launch of a k_gemvb plan (qtts_bgemv_plan): 0 ok, -1 launch error
+int qtts_gemvb_launch(const GemvArgs &a, const BgPlan &p, hipStream_t st) {
+    const int SPW = p.t[0], TPW = p.t[1], NBC = p.t[2], PM = p.t[3], src = p.src;
+    const void *srcp = qtts_gm::src_base(a, src);
+    const int *idsp = qtts_gm::src_ids(a, src);
+#define QTTS_GB(SP, TP, NC, PP, SS) launch_gb<SP, TP, NC, PP, SS>(p, st, srcp, idsp, a);
 #define QTTS_GB_SRC(SP, TP, NC)                                                                        \
-    if (src == GB_SRC_X) QTTS_GB(SP, TP, NC, 0, GB_SRC_X)                                              \
-    else if (src == GB_SRC_TAB) QTTS_GB(SP, TP, NC, 0, GB_SRC_TAB)                                     \
-    else if (src == GB_SRC_TABF) QTTS_GB(SP, TP, NC, 0, GB_SRC_TABF)                                   \
-    else if (PM == 2) QTTS_GB(SP, TP, NC, 2, GB_SRC_XADD)                                              \
-    else QTTS_GB(SP, TP, NC, 4, GB_SRC_XADD)
+    if (src == BG_SRC_X) QTTS_GB(SP, TP, NC, 0, BG_SRC_X)                                              \
+    else if (src == BG_SRC_TAB) QTTS_GB(SP, TP, NC, 0, BG_SRC_TAB)                                     \
+    else if (src == BG_SRC_TABF) QTTS_GB(SP, TP, NC, 0, BG_SRC_TABF)                                   \
+    else if (PM == 2) QTTS_GB(SP, TP, NC, 2, BG_SRC_XADD)                                              \
+    else QTTS_GB(SP, TP, NC, 4, BG_SRC_XADD)
 #define QTTS_GB_NB(SP, TP)                                                                             \
     if (NBC == 8) QTTS_GB_SRC(SP, TP, 8) else QTTS_GB_SRC(SP, TP, 16)
-    const int key = SPW * 10 + TPW;
-    switch (key) {
+    switch (SPW * 10 + TPW) {
         case 11: QTTS_GB_NB(1, 1) break;
         case 21: QTTS_GB_NB(2, 1) break;
         case 22: QTTS_GB_NB(2, 2) break;
@@ -433,7 +349,7 @@ int qtts_gemvb(const GemvArgs &in, hipStream_t st) {
         case 43: QTTS_GB_NB(4, 3) break;
         case 81: QTTS_GB_NB(8, 1) break;
         case 82: QTTS_GB_NB(8, 2) break;
-        default: return 1;
+        default: return -1;
     }
 #undef QTTS_GB_NB
 #undef QTTS_GB_SRC

@@ -32,7 +32,7 @@
 // issued before it): x rows / table rows, split-K partials and norm weights
 // first, then the weight group, all through buffer descriptors (32-bit
 // offsets) and with no branch between them -- the kernel is specialised on
-// the source kind (GM_SRC_*), because a branch between differently-loading
+// the source kind (BG_SRC_*, qtts_bgemv_dev.h), because a branch between differently-loading
 // paths makes the compiler drain every outstanding load, the weights
 // included, at the join.  (The former per-unit loader did exactly that for
 // every x unit: batch 8 117.1 -> 123.4 audio-s/s.)
@@ -43,9 +43,7 @@
 // Whole rows up to 16 float4 per thread go through registers (one barrier
 // for the statistics); longer ones (the down projections at B >= 8) are staged
 // in column chunks after a statistics pre-pass.
-#include <algorithm>
-
-#include "qtts_gemvm_dev.h"
+#include "qtts_bgemv_dev.h"
 
 namespace {
 
@@ -53,13 +51,6 @@ using qtts_gm::lo_f;
 using qtts_gm::hi_f;
 #define gm_rsrc qtts_gm::rsrc
 #define gm_ld4 qtts_gm::ld4
-
-// id of the table row that batch row b reads
-__device__ __forceinline__ int gm_row_id(const GemvArgs &a, int b) {
-    const int *p = a.ids + (size_t)b * a.ids_bstride + a.ids_off;
-    if (a.row_sel) p += (size_t)a.row_sel[b] * a.ids_rstride;
-    return *p;
-}
 
 // x = x1 + x2 + x3 (each bf16, exact) for 4 values -> the three planes
 __device__ __forceinline__ void split_store(float4 v, unsigned short *hp, int plane_stride) {
@@ -84,20 +75,15 @@ struct NoIssue { __device__ __forceinline__ void operator()() const {} };
 // and added to the residual, as GemvArgs::xadd prescribes.
 // (buffer-descriptor loads: qtts_gm::rsrc / ld4, 32-bit offsets, cdna_hip_programming.md T8 / T20)
 
-// Source kinds (GM_SRC_*): a kernel specialised on one has no branch between
-// its loads, so the compiler's vmcnt bookkeeping stays exact (a uniform
-// branch between source kinds that issue different loads into different
-// registers makes it wait for every outstanding load -- the weights
-// included -- at the join); GM_SRC_ANY decides at run time (generic path).
-enum { GM_SRC_X = 0, GM_SRC_XADD = 1, GM_SRC_TAB = 2, GM_SRC_TABF = 3, GM_SRC_ANY = 4 };
-
+// the source kind of this launch: the kernel's own (BG_SRC_*), or decided at
+// run time (BG_SRC_ANY, the generic path)
 template <int SRC>
 __device__ __forceinline__ bool gm_is(const GemvArgs &a, int kind) {
-    if constexpr (SRC != GM_SRC_ANY) return SRC == kind;
+    if constexpr (SRC != BG_SRC_ANY) return SRC == kind;
     switch (kind) {
-        case GM_SRC_TAB: return a.table != nullptr;
-        case GM_SRC_TABF: return a.table == nullptr && a.table_f32 != nullptr;
-        case GM_SRC_XADD: return !a.table && !a.table_f32 && a.xadd != nullptr;
+        case BG_SRC_TAB: return a.table != nullptr;
+        case BG_SRC_TABF: return a.table == nullptr && a.table_f32 != nullptr;
+        case BG_SRC_XADD: return !a.table && !a.table_f32 && a.xadd != nullptr;
         default: return !a.table && !a.table_f32 && a.xadd == nullptr;
     }
 }
@@ -114,7 +100,7 @@ __device__ __forceinline__ void gm_fetch(const GemvArgs &a, int i0, int step, in
         b[u] = (unsigned)(i / n4);
         c[u] = (unsigned)(c0 + 4 * (i - (int)b[u] * n4));
     }
-    const bool tab = gm_is<SRC>(a, GM_SRC_TAB), tabf = gm_is<SRC>(a, GM_SRC_TABF), xadd = gm_is<SRC>(a, GM_SRC_XADD);
+    const bool tab = gm_is<SRC>(a, BG_SRC_TAB), tabf = gm_is<SRC>(a, BG_SRC_TABF), xadd = gm_is<SRC>(a, BG_SRC_XADD);
     const int np = xadd ? a.n_xadd : 0;
     float4 pv[N][PM];
     uint2 tq[N];
@@ -208,7 +194,7 @@ __device__ __forceinline__ void gm_stage(const GemvArgs &a, const float *inv, un
     const int n4 = CCH / 4, nu = a.nb * n4, nt = blockDim.x;
     for (int i0 = threadIdx.x; i0 < nu; i0 += 2 * nt) {
         float4 v[2], nw[2];
-        gm_fetch<GM_SRC_ANY, 2, 1, true>(a, i0, nt, nu, n4, c0, v, nw, NoIssue());
+        gm_fetch<BG_SRC_ANY, 2, 1, true>(a, i0, nt, nu, n4, c0, v, nw, NoIssue());
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
             const int i = i0 + nt * u;
@@ -333,7 +319,7 @@ __global__ __launch_bounds__(1024) void k_gemvm(GemvArgs a, int tpw) {
                 float ss = 0.f;
                 for (int k0 = lane; k0 < n4; k0 += 4 * 64) {   // columns 4 k, k = k0 + 64 u, in order
                     float4 v[4], nwd[4];
-                    gm_fetch<GM_SRC_ANY, 4, 1, false>(a, bb * n4 + k0, 64, bb * n4 + n4, n4, 0, v, nwd, NoIssue());
+                    gm_fetch<BG_SRC_ANY, 4, 1, false>(a, bb * n4 + k0, 64, bb * n4 + n4, n4, 0, v, nwd, NoIssue());
 #pragma unroll
                     for (int u = 0; u < 4; ++u)
                         if (k0 + 64 * u < n4) ss += v[u].x * v[u].x + v[u].y * v[u].y + v[u].z * v[u].z + v[u].w * v[u].w;
@@ -434,98 +420,28 @@ __global__ __launch_bounds__(1024) void k_gemvm(GemvArgs a, int tpw) {
 
 }  // namespace
 
-// LDS budget for the three bf16 planes of the staged x rows (bytes): one
-// workgroup per CU at the largest.
-static constexpr int GM_PLANES_MAX = 150 * 1024;
-static int gm_planes(int nb, int cch) { return 3 * nb * (cch + 8) * 2; }
-
-// Returns 1 when the shape is not covered (the caller uses k_gemv), 0 ok,
-// -1 launch error.
-int qtts_gemvm(const GemvArgs &in, hipStream_t st) {
+// the launch of a k_gemvm plan (qtts_bgemv_plan): 0 ok, -1 launch error
+int qtts_gemvm_launch(const GemvArgs &in, const BgPlan &p, hipStream_t st) {
     GemvArgs a = in;
-    if (a.nb < 2 || a.nb > 16 || a.R % 16 || a.C % 32 || (size_t)a.R * a.C * 2 >= ((size_t)1 << 31)) return 1;
-    if (a.table) {
-        if (a.C % 4) return 1;
-    } else if (a.table_f32) {
-        if ((uintptr_t)a.table_f32 & 15) return 1;
-    } else if (!a.x || a.ldx % 4 || ((uintptr_t)a.x & 15)) {
-        return 1;
-    }
-    if (a.norm_w && ((uintptr_t)a.norm_w & 15)) return 1;
-    if (a.xcopy && (a.ldxc % 4 || ((uintptr_t)a.xcopy & 15))) return 1;
-    if (a.xadd && (a.table || a.table_f32 || ((uintptr_t)a.xadd & 15) || a.ld_xadd % 4 || a.ldb_xadd % 4 ||
-                   a.n_xadd < 1))
-        return 1;
-    const int kz = a.ypart ? a.kz : 1;
-    if (a.ypart && (kz < 2 || (a.tick && kz > 4) || a.norm_w || a.table || a.table_f32 || a.xcopy || a.C % (32 * kz) ||
-                    ((uintptr_t)a.ypart & 3)))
-        return 1;
-    const int Cfull = a.C;
-    a.C /= kz;   // the K extent one workgroup column takes (host-side configuration only)
-    // 16 waves per workgroup where the shape allows (one workgroup per CU):
-    // KS waves per tile keep >= 2 K steps each; TPW tiles per workgroup bring
-    // the grid to about one round over the 256 CUs (the x prologue is paid
-    // once per workgroup)
-    const int nsteps = a.C / 32, T = a.R / 16;
-    int tpw = (T + 255) / 256;
-    if (tpw > 4) tpw = 4;
-    int KS = 16 / (tpw == 3 ? 4 : tpw);
-    while (KS > 4 && nsteps < 2 * KS) KS /= 2;
-    if (tpw * KS > 16) tpw = 16 / KS;
-    // three tiles x 4 waves leave 768 threads, so > 4 x units per thread at
-    // batch >= 8 (whose registers, with the partials and the weight group in
-    // flight, spill): four tiles per 1024-thread workgroup instead
-    if (tpw == 3 && (a.nb * a.C / 4 + 767) / 768 > 4) { tpw = 4; KS = 4; }
-    // column chunk: the whole row when it fits, else the fewest equal chunks
-    // of whole 32 x KS-column step rounds with an even step count per wave
-    int cch = a.C;
-    if (gm_planes(a.nb, a.C) > GM_PLANES_MAX) {
-        const int unit = 32 * KS;
-        if (a.C % unit) return 1;
-        int n = 2;
-        for (; n <= a.C / unit; ++n)
-            if ((a.C / unit) % n == 0 && gm_planes(a.nb, a.C / n) <= GM_PLANES_MAX && (a.C / unit / n) % 2 == 0)
-                break;
-        if (n > a.C / unit) return 1;
-        cch = a.C / n;
-    }
-    a.cch = cch;
-    int U;
-    if (cch < a.C) {
-        const int spc = cch / 32 / KS;
-        U = spc % 8 == 0 ? 8 : spc % 4 == 0 ? 4 : 2;
-    } else {
-        const int J = (nsteps + KS - 1) / KS;
-        U = J <= 2 ? 2 : J <= 4 ? 4 : 8;
-    }
-    const int nthr = 64 * KS * tpw, nu = a.nb * a.C / 4;
-    const int xu = (cch == a.C && a.C % 256 == 0) ? (nu + nthr - 1) / nthr : 0;
-    const int XU = xu == 0 || xu > 8 ? 0 : xu <= 1 ? 1 : xu <= 2 ? 2 : xu <= 4 ? 4 : xu <= 6 ? 6 : 8;
-    const int region = std::max(gm_planes(a.nb, cch), nthr / 64 * 64 * 16);
-    const size_t smem = (size_t)region + (16 + (a.nb * a.C / 256 > 64 ? a.nb * a.C / 256 : 64)) * 4;
-    const dim3 grid((T + tpw - 1) / tpw, kz);
-    a.C = Cfull;
-    if (a.tick && (!a.ypart || !a.y || a.epi != EPI_RESID || (int)grid.x > QTTS_GM_TICKS)) {
-        fprintf(stderr, "qtts_gemvm: self-reducing split-K needs ypart, y, EPI_RESID and <= %d row blocks\n",
-                QTTS_GM_TICKS);
-        return -1;
-    }
-    const int src = a.table ? GM_SRC_TAB : a.table_f32 ? GM_SRC_TABF : a.xadd ? GM_SRC_XADD : GM_SRC_X;
+    a.cch = p.cch;
+    const int U = p.t[0], XU = p.t[1], KS = p.t[2], src = p.src, tpw = p.tpw, nthr = p.block.x;
+    const dim3 grid = p.grid;
+    const size_t smem = p.smem;
 #define QTTS_GMS(UU, XX, KK, SS)                                                                              \
-    hipLaunchKernelGGL((k_gemvm<UU, XX, KK, SS>), grid, dim3(nthr), smem, st, a, tpw);                        \
-    qtts_last_kernel = "k_gemvm<" #UU ", " #XX ", " #KK ", " #SS ">";
+    hipLaunchKernelGGL((k_gemvm<UU, XX, KK, BG_SRC_##SS>), grid, dim3(nthr), smem, st, a, tpw);               \
+    qtts_last_kernel = "k_gemvm<" #UU ", " #XX ", " #KK ", GM_SRC_" #SS ">";   /* (the spelling the profiles know) */
 #define QTTS_GM(UU, XX, KK)                                                                                   \
-    if (src == GM_SRC_X) { QTTS_GMS(UU, XX, KK, GM_SRC_X) }                                                   \
-    else if (src == GM_SRC_XADD) { QTTS_GMS(UU, XX, KK, GM_SRC_XADD) }                                        \
-    else if (src == GM_SRC_TAB) { QTTS_GMS(UU, XX, KK, GM_SRC_TAB) }                                          \
-    else { QTTS_GMS(UU, XX, KK, GM_SRC_TABF) }
+    if (src == BG_SRC_X) { QTTS_GMS(UU, XX, KK, X) }                                                   \
+    else if (src == BG_SRC_XADD) { QTTS_GMS(UU, XX, KK, XADD) }                                        \
+    else if (src == BG_SRC_TAB) { QTTS_GMS(UU, XX, KK, TAB) }                                          \
+    else { QTTS_GMS(UU, XX, KK, TABF) }
 #define QTTS_GMX(UU, KK)                                       \
     if (XU == 1) { QTTS_GM(UU, 1, KK) }                        \
     else if (XU == 2) { QTTS_GM(UU, 2, KK) }                   \
     else if (XU == 4) { QTTS_GM(UU, 4, KK) }                   \
     else if (XU == 6) { QTTS_GM(UU, 6, KK) }                   \
     else if (XU == 8) { QTTS_GM(UU, 8, KK) }                   \
-    else { QTTS_GMS(UU, 0, KK, GM_SRC_ANY) }
+    else { QTTS_GMS(UU, 0, KK, ANY) }
 #define QTTS_GMK(UU)                                           \
     if (KS == 16) { QTTS_GMX(UU, 16) }                         \
     else if (KS == 8) { QTTS_GMX(UU, 8) }                      \

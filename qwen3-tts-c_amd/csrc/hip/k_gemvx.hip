@@ -37,18 +37,16 @@
 // summation order only (the GEMV bar of tests/test_gpu_kernels.py).
 //
 // x comes from L2 once per workgroup: nb / (8 TPW) bytes per weight byte.
-#include <algorithm>
 #include <atomic>
+#include <string>
 
-#include "qtts_gemvm_dev.h"
+#include "qtts_bgemv_dev.h"
 
 namespace {
 
 using namespace qtts_gm;
 
-enum { GX_SRC_X = 0, GX_SRC_XADD = 1, GX_SRC_TAB = 2, GX_SRC_TABF = 3 };
-constexpr int GX_W = 8;      // waves per workgroup
-constexpr int GX_LDX = 36;   // staged row stride (floats; +4: fragment reads spread over banks)
+constexpr int GX_W = QTTS_GX_W, GX_LDX = QTTS_GX_LDX;   // waves per workgroup, staged row stride (qtts_bgemv_dev.h)
 
 // (src -- a.x, a.table or a.table_f32 by SRC --, ids, W and xadd lead the
 // arguments: preloaded into SGPRs, Makefile)
@@ -57,7 +55,7 @@ __global__ __launch_bounds__(64 * GX_W) void k_gemvx(const void *src, const int 
                                                       const float *xadd, GemvArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     constexpr int W = GX_W, LDX = GX_LDX, PM = 4;
-    constexpr bool AHEAD = SRC != GX_SRC_XADD;   // x of the next step loaded with its weights
+    constexpr bool AHEAD = SRC != BG_SRC_XADD;   // x of the next step loaded with its weights
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int nb = a.nb;
     const int kz = gridDim.y, Ck = a.C / kz, woff = blockIdx.y * Ck;
@@ -84,18 +82,14 @@ __global__ __launch_bounds__(64 * GX_W) void k_gemvx(const void *src, const int 
             urow[m][q] = b < nb ? b : 0;             // clamped: every load is unconditional
             uid[m][q] = 0;
         }
-    if constexpr (SRC == GX_SRC_TAB || SRC == GX_SRC_TABF) {
+    if constexpr (SRC == BG_SRC_TAB || SRC == BG_SRC_TABF) {
 #pragma unroll
         for (int m = 0; m < MT; ++m)
 #pragma unroll
-            for (int q = 0; q < 2; ++q) {
-                const int *p = ids + (size_t)urow[m][q] * a.ids_bstride;
-                if (a.row_sel) p += (size_t)a.row_sel[urow[m][q]] * a.ids_rstride;
-                uid[m][q] = (unsigned)*p;
-            }
+            for (int q = 0; q < 2; ++q) uid[m][q] = row_id(a, ids, urow[m][q]);
     }
     const auto rx = rsrc(src);
-    const auto rp = rsrc(SRC == GX_SRC_XADD ? (const void *)xadd : src);
+    const auto rp = rsrc(SRC == BG_SRC_XADD ? (const void *)xadd : src);
     const auto rn = rsrc(norm ? (const void *)a.norm_w : src);
     const auto rw = rsrc(Wt);
     unsigned wo[TPW];
@@ -120,10 +114,10 @@ __global__ __launch_bounds__(64 * GX_W) void k_gemvx(const void *src, const int 
             for (int m = 0; m < MT; ++m)
 #pragma unroll
                 for (int q = 0; q < 2; ++q) {
-                    if constexpr (SRC == GX_SRC_TAB) {
+                    if constexpr (SRC == BG_SRC_TAB) {
                         const auto v = __builtin_amdgcn_raw_buffer_load_b64(rx, (uid[m][q] * (unsigned)a.C + c0) * 2u, 0, 0);
                         tn[m][q] = make_uint2(v[0], v[1]);
-                    } else if constexpr (SRC == GX_SRC_TABF) {
+                    } else if constexpr (SRC == BG_SRC_TABF) {
                         xn[m][q] = ld4(rx, uid[m][q] * (unsigned)a.C + c0);
                     } else {
                         xn[m][q] = ld4(rx, (unsigned)urow[m][q] * (unsigned)a.ldx + c0);
@@ -180,7 +174,7 @@ __global__ __launch_bounds__(64 * GX_W) void k_gemvx(const void *src, const int 
             for (int m = 0; m < MT; ++m)
 #pragma unroll
                 for (int q = 0; q < 2; ++q) {
-                    if constexpr (SRC == GX_SRC_TAB) put(m, q, make_float4(lo_f(tc_[m][q].x), hi_f(tc_[m][q].x), lo_f(tc_[m][q].y), hi_f(tc_[m][q].y)));
+                    if constexpr (SRC == BG_SRC_TAB) put(m, q, make_float4(lo_f(tc_[m][q].x), hi_f(tc_[m][q].x), lo_f(tc_[m][q].y), hi_f(tc_[m][q].y)));
                     else put(m, q, xc_[m][q]);
                 }
         } else {
@@ -324,54 +318,13 @@ __global__ __launch_bounds__(64 * GX_W) void k_gemvx(const void *src, const int 
 
 std::atomic<long long> g_wide_launches{0};
 
-struct GxGeom { int MT, TPW, src; size_t smem; dim3 grid; };
-
-bool gemvx_geom(const GemvArgs &a, GxGeom &g) {
-    if (a.nb < 17 || a.nb > 64 || a.R < 16 || a.R % 16 || a.C < 32 || a.C % 32 ||
-        (size_t)a.R * a.C * 2 >= ((size_t)1 << 31))
-        return false;
-    const bool tab = a.table != nullptr, tabf = !tab && a.table_f32 != nullptr;
-    if (tab) {
-        if (!a.ids) return false;
-    } else if (tabf) {
-        if (((uintptr_t)a.table_f32 & 15) || !a.ids) return false;
-    } else if (!a.x || a.ldx % 4 || ((uintptr_t)a.x & 15)) {
-        return false;
-    }
-    if (a.norm_w && ((uintptr_t)a.norm_w & 15)) return false;
-    if (a.xcopy && (a.ldxc % 4 || ((uintptr_t)a.xcopy & 15))) return false;
-    const bool xadd = !tab && !tabf && a.xadd != nullptr;
-    if (a.xadd && (tab || tabf || ((uintptr_t)a.xadd & 15) || a.ld_xadd % 4 || a.ldb_xadd % 4 || a.n_xadd < 1 ||
-                   a.n_xadd > 4))
-        return false;
-    if (a.amerge) return false;
-    const int kz = a.ypart ? a.kz : 1;
-    if (a.ypart && (kz < 2 || kz > 4 || a.norm_w || tab || tabf || a.xcopy || a.C % (32 * kz) ||
-                    ((uintptr_t)a.ypart & 3)))
-        return false;
-    if (a.tick && (!a.ypart || !a.y || a.epi != EPI_RESID)) return false;
-    if (!a.ypart && !a.y) return false;
-    // tiles per workgroup: about one round of workgroups over the 256 CUs
-    const int T = a.R / 16;
-    const int TPW = std::max(1, std::min((T * kz + 128) / 256, 3));
-    const int wreg = std::max(a.nb * GX_LDX, TPW * 256);
-    g.smem = ((size_t)GX_W * wreg + (size_t)GX_W * 64 + 64 + 4) * sizeof(float);
-    if (g.smem > 160 * 1024) return false;
-    g.grid = dim3((T + TPW - 1) / TPW, kz);
-    if (a.tick && (int)g.grid.x > QTTS_GM_TICKS) return false;
-    g.MT = (a.nb + 15) / 16;
-    g.TPW = TPW;
-    g.src = tab ? GX_SRC_TAB : tabf ? GX_SRC_TABF : xadd ? GX_SRC_XADD : GX_SRC_X;
-    return true;
-}
-
+// (rocprofv3's spelling of the instantiation, built once per instantiation: the
+// bench looks its profile rows up by it)
 template <int MT, int TP, int SS>
-void launch_gx(const GxGeom &g, hipStream_t st, const void *srcp, const int *idsp, const GemvArgs &a) {
-    hipLaunchKernelGGL((k_gemvx<MT, TP, SS>), g.grid, dim3(64 * GX_W), g.smem, st, srcp, idsp, a.W, a.xadd, a);
-    // (rocprofv3's spelling of the instantiation: the bench looks its profile rows up by it)
-    static char nm[64];
-    snprintf(nm, sizeof nm, "k_gemvx<%d, %d, %d>", MT, TP, SS);
-    qtts_last_kernel = nm;
+void launch_gx(const BgPlan &p, hipStream_t st, const void *srcp, const int *idsp, const GemvArgs &a) {
+    hipLaunchKernelGGL((k_gemvx<MT, TP, SS>), p.grid, p.block, p.smem, st, srcp, idsp, a.W, a.xadd, a);
+    static const std::string nm = "k_gemvx<" + std::to_string(MT) + ", " + std::to_string(TP) + ", " + std::to_string(SS) + ">";
+    qtts_last_kernel = nm.c_str();
 }
 
 }  // namespace
@@ -380,28 +333,22 @@ void launch_gx(const GxGeom &g, hipStream_t st, const void *srcp, const int *ids
 // test's proof that one launch, not one per 16 rows, served a wide batch
 extern "C" long long qtts_hip_gemv_wide_launches(void) { return g_wide_launches.load(); }
 
-bool qtts_gemvx_shape_ok(int R, int C) {
-    return R >= 16 && R % 16 == 0 && C >= 32 && C % 32 == 0 && (size_t)R * C * 2 < ((size_t)1 << 31);
-}
-
-// Returns 1 when the arguments are not covered, 0 ok, -1 launch error.
-int qtts_gemvx(const GemvArgs &a, hipStream_t st) {
-    GxGeom g;
-    if (!gemvx_geom(a, g)) return 1;
-    const bool tab = a.table != nullptr, tabf = !tab && a.table_f32 != nullptr;
-    const void *srcp = tab ? (const void *)a.table : tabf ? (const void *)a.table_f32 : (const void *)a.x;
-    const int *idsp = (tab || tabf) ? a.ids + a.ids_off : nullptr;
-#define QTTS_GX(MM, TP, SS) launch_gx<MM, TP, SS>(g, st, srcp, idsp, a);
-#define QTTS_GX_SRC(MM, TP)                                          \
-    if (g.src == GX_SRC_X) QTTS_GX(MM, TP, GX_SRC_X)                 \
-    else if (g.src == GX_SRC_XADD) QTTS_GX(MM, TP, GX_SRC_XADD)      \
-    else if (g.src == GX_SRC_TAB) QTTS_GX(MM, TP, GX_SRC_TAB)        \
-    else QTTS_GX(MM, TP, GX_SRC_TABF)
-#define QTTS_GX_T(MM)                                                \
-    if (g.TPW == 1) { QTTS_GX_SRC(MM, 1) }                           \
-    else if (g.TPW == 2) { QTTS_GX_SRC(MM, 2) }                      \
+// the launch of a k_gemvx plan (qtts_bgemv_plan): 0 ok, -1 launch error
+int qtts_gemvx_launch(const GemvArgs &a, const BgPlan &p, hipStream_t st) {
+    const int MT = p.t[0], TPW = p.t[1], src = p.src;
+    const void *srcp = qtts_gm::src_base(a, src);
+    const int *idsp = qtts_gm::src_ids(a, src);
+#define QTTS_GX(MM, TP, SS) launch_gx<MM, TP, SS>(p, st, srcp, idsp, a);
+#define QTTS_GX_SRC(MM, TP)                                        \
+    if (src == BG_SRC_X) QTTS_GX(MM, TP, BG_SRC_X)                 \
+    else if (src == BG_SRC_XADD) QTTS_GX(MM, TP, BG_SRC_XADD)      \
+    else if (src == BG_SRC_TAB) QTTS_GX(MM, TP, BG_SRC_TAB)        \
+    else QTTS_GX(MM, TP, BG_SRC_TABF)
+#define QTTS_GX_T(MM)                                              \
+    if (TPW == 1) { QTTS_GX_SRC(MM, 1) }                           \
+    else if (TPW == 2) { QTTS_GX_SRC(MM, 2) }                      \
     else { QTTS_GX_SRC(MM, 3) }
-    switch (g.MT) {
+    switch (MT) {
         case 2: QTTS_GX_T(2) break;
         case 3: QTTS_GX_T(3) break;
         default: QTTS_GX_T(4) break;

@@ -1,7 +1,17 @@
-// qtts_gemvm_dev.h - device helpers shared by the lock-step batch GEMVs
-// (k_gemvm.hip: x planes staged per workgroup; k_gemvb.hip: x slices per
-// wave): bf16 packing, the exact 3-plane split, buffer-descriptor loads and
-// the self-reducing split-K tail.
+// qtts_bgemv_dev.h - the device layer of the three lock-step batch GEMVs
+// (k_gemvm.hip: 2..16 rows, x planes staged per workgroup; k_gemvb.hip: 2..16
+// rows, x slices per wave; k_gemvx.hip: 17..64 rows, a moving K step per
+// wave): the source kinds, the table-row lookup, bf16 packing, the exact
+// 3-plane split, buffer-descriptor loads, the epilogue and the self-reducing
+// split-K tail.
+// The staging of an x unit, the weight-fragment offsets, the partial sum, the
+// 3-plane MFMA step and the D-tile output stay written out in each kernel,
+// although k_gemvb and k_gemvx share the text: as __forceinline__ helpers they
+// change every instruction stream (the callee is canonicalised on its own
+// before it is inlined), the sum of squares beside them can be contracted as
+// fma(y, y, x x) for fma(x, x, y y) (k_gemvb<1, 1, 8, 0, 0>, <1, 1, 8, 0, 3>:
+// other bits), and the variant that kept every bit measured 0.2 % (8 rows) and
+// 0.6 % (32, 64 rows) slower end to end: profiles/bgemv_refactor_bench.txt.
 #pragma once
 #include "qtts_common.h"
 #include "qtts_kernels.h"
@@ -9,7 +19,34 @@
 typedef short bf16x8 __attribute__((ext_vector_type(8)));
 typedef float floatx4 __attribute__((ext_vector_type(4)));
 
+// Source kinds: a kernel specialised on one has no branch between its loads,
+// so the compiler's vmcnt bookkeeping stays exact (a uniform branch between
+// source kinds that issue different loads into different registers makes it
+// wait for every outstanding load -- the weights included -- at the join);
+// BG_SRC_ANY decides at run time (k_gemvm's generic path).
+enum { BG_SRC_X = 0, BG_SRC_XADD = 1, BG_SRC_TAB = 2, BG_SRC_TABF = 3, BG_SRC_ANY = 4 };
+
+// k_gemvx's workgroup: waves, and the staged row stride in floats (32 columns
+// + 4: fragment reads spread over banks); the planner sizes its LDS by them
+constexpr int QTTS_GX_W = 8, QTTS_GX_LDX = 36;
+
 namespace qtts_gm {
+
+// the leading (preloaded) kernel arguments of k_gemvb / k_gemvx: the source's
+// base by kind, and the ids of a table source
+inline const void *src_base(const GemvArgs &a, int src) {
+    return src == BG_SRC_TAB ? (const void *)a.table : src == BG_SRC_TABF ? (const void *)a.table_f32 : (const void *)a.x;
+}
+inline const int *src_ids(const GemvArgs &a, int src) {
+    return src == BG_SRC_TAB || src == BG_SRC_TABF ? a.ids + a.ids_off : nullptr;
+}
+
+// id of the table row that batch row b reads (ids: a.ids + a.ids_off)
+__device__ __forceinline__ unsigned row_id(const GemvArgs &a, const int *ids, int b) {
+    const int *p = ids + (size_t)b * a.ids_bstride;
+    if (a.row_sel) p += (size_t)a.row_sel[b] * a.ids_rstride;
+    return (unsigned)*p;
+}
 
 // two f32 -> packed bf16 (round to nearest even: v_cvt_pk_bf16_f32)
 __device__ __forceinline__ uint32_t pk_bf16(float lo, float hi) {

@@ -35,7 +35,7 @@ struct GemvArgs {
     const bf16_t *W = nullptr;  // [R, C] bf16 row-major
     int R = 0, C = 0;
     int ksplit = 0;             // 0 = auto
-    int cch = 0;                // set by launcher
+    int cch = 0;                // set by the launcher (k_gemv, k_gemvm: BgPlan::cch)
     int nt = 1;                 // non-temporal weight loads
     int nb = 1;                 // batch rows
     // x source: fp32 rows, or bf16 / fp32 table rows gathered by id
@@ -55,20 +55,22 @@ struct GemvArgs {
     // in order first) -- the O projection's per-head partials (qtts_attn_o)
     const float *xadd = nullptr;
     int n_xadd = 0, ld_xadd = 0;
-    int ldb_xadd = 0;               // batch path (k_gemvm): row b of partial p at xadd + p*ld_xadd + b*ldb_xadd
-    // batch-1 prologue only: x = the decode attention's output, merged here
-    // from its split partials (AttnArgs::defer): amerge [KV][am_nsplit][GPH*HD
+    // batch GEMV (k_gemvb / k_gemvm / k_gemvx): the same prologue per row, at
+    // most 4 partials, row b of partial p at xadd + p*ld_xadd + b*ldb_xadd
+    int ldb_xadd = 0;
+    // batch-1 prologue only (the batch GEMV's planner refuses it): x = the
+    // decode attention's output, merged here from its split partials (AttnArgs::defer): amerge [KV][am_nsplit][GPH*HD
     // + 2*GPH], am_ch keys per split, the live key count am_pos[0] + 1
     const float *amerge = nullptr;
     const int *am_pos = nullptr;
     int am_nsplit = 0, am_ch = 0, am_hd = 0, am_gph = 0;
-    // batch path split-K producer (k_gemvm): kz > 1 workgroup columns each take
+    // batch GEMV split-K producer (all three kernels): kz > 1 workgroup columns each take
     // C / kz of K and store raw partials ypart[z*ld_ypart + b*R + r] (the
     // consumer adds them with the residual through xadd); y / epi unused
     float *ypart = nullptr;
     size_t ld_ypart = 0;
     int kz = 1;
-    // self-reducing split-K (EPI_RESID only): one zeroed ticket per grid.x
+    // self-reducing split-K (batch GEMV, EPI_RESID only, kz <= 4): one zeroed ticket per grid.x
     // workgroup; the last of the kz columns to finish a row block adds the
     // partials in order to the residual, y = y + (p0 + p1 + ...), and resets
     // its ticket, so the next GEMV reads y alone (no xadd)
@@ -103,14 +105,33 @@ int qtts_gemv(const GemvArgs &a, hipStream_t st);
 int qtts_gemvw(const GemvArgs &a, hipStream_t st);
 // shapes whose batch-1 GEMV takes the decode attention's merge in its prologue (GemvArgs::amerge)
 bool qtts_gemvw_amerge_ok(int R, int C);
-// lock-step batch (2..16 rows) on the bf16 matrix cores (k_gemvm.hip); 1 = not covered
-int qtts_gemvm(const GemvArgs &a, hipStream_t st);
-// the same with the x rows sliced per wave (k_gemvb.hip, tried first); 1 = not covered
-int qtts_gemvb(const GemvArgs &a, hipStream_t st);
-// wide lock-step batch (17..64 rows): one moving 32-column K step per wave over
-// all rows (k_gemvx.hip); 1 = not covered.  qtts_gemvx_shape_ok: the weight
-// shapes it takes (qtts_dev_begin refuses a model with another above 16 slots)
-int qtts_gemvx(const GemvArgs &a, hipStream_t st);
+// The lock-step batch GEMV (2..64 rows) on the bf16 matrix cores: three kernels,
+//   k_gemvb (2..16 rows, x sliced per wave; tried first),
+//   k_gemvm (2..16 rows, x staged as bf16 planes per workgroup),
+//   k_gemvx (17..64 rows, one moving 32-column K step per wave),
+// one planner and one router (qtts_bgemv.hip).  BG_* name a kernel and, or-ed,
+// the kernels a caller allows.
+enum { BG_NONE = 0, BG_GEMVM = 1, BG_GEMVB = 2, BG_GEMVX = 4, BG_ALL = 7 };
+struct BgPlan {
+    int kernel = BG_NONE;
+    int nt = 0, t[5] = {0, 0, 0, 0, 0};   // the template integers, in the kernel's order (the last: the source kind)
+    int src = 0;                          // BG_SRC_* (qtts_bgemv_dev.h)
+    dim3 grid, block;
+    size_t smem = 0;                      // dynamic LDS bytes
+    int tpw = 0, cch = 0;                 // k_gemvm's run-time arguments: tiles per workgroup, staged column chunk
+};
+// The plan for `a` among the `allowed` kernels: pure host code, nothing is
+// launched and no pointer dereferenced; depends on its arguments and on
+// QTTS_HIP_GEMVB / QTTS_HIP_GB_W (read per call) only.  0 = planned, 1 = not
+// covered, -1 = an argument error.
+int qtts_bgemv_plan(const GemvArgs &a, BgPlan &p, unsigned allowed = BG_ALL);
+// the planner, then the launch of its plan: the planner's results, -1 on a launch error too
+int qtts_bgemv(const GemvArgs &a, hipStream_t st, unsigned allowed = BG_ALL);
+// the launch switch over each file's own instantiations (0 ok, -1 launch error)
+int qtts_gemvm_launch(const GemvArgs &a, const BgPlan &p, hipStream_t st);
+int qtts_gemvb_launch(const GemvArgs &a, const BgPlan &p, hipStream_t st);
+int qtts_gemvx_launch(const GemvArgs &a, const BgPlan &p, hipStream_t st);
+// the weight shapes k_gemvx takes (qtts_dev_begin refuses a model with another above 16 slots)
 bool qtts_gemvx_shape_ok(int R, int C);
 // multi-row (2..64) projection on the bf16 matrix cores (k_mgemm.hip); 1 = not covered
 int qtts_mgemm(const GemvArgs &a, float *inv_scratch, hipStream_t st, float *part = nullptr, size_t part_elems = 0);

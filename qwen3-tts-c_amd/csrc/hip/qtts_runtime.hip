@@ -967,10 +967,10 @@ static int rows_proj(qtts_dev *dv, GemvArgs a, int rows, bool prefill = false) {
             c.C % (32 * psk) == 0 && c.R <= (dv->d.H > dv->d.Hs ? dv->d.H : dv->d.Hs)) {
             GemvArgs k = c;
             k.ypart = dv->ppart; k.kz = psk; k.ld_ypart = (size_t)nr * k.R; k.tick = dv->btick;
-            rc = qtts_gemvb(k, dv->st);
+            rc = qtts_bgemv(k, dv->st, BG_GEMVB);
         }
-        if (rc == 1 && nr >= 2 && nr <= 16 && pgb) rc = qtts_gemvb(c, dv->st);
-        if (rc == 1 && nr >= 2 && nr <= 16) rc = qtts_gemvm(c, dv->st);
+        // (never k_gemvx: above 16 rows the prefill GEMM below; the planner answers 1 outside 2..16 rows)
+        if (rc == 1) rc = qtts_bgemv(c, dv->st, pgb ? BG_GEMVB | BG_GEMVM : BG_GEMVM);
         if (rc == 1 && nr >= 2) rc = qtts_mgemm(c, dv->pinv, dv->st, dv->mpart, dv->mpart_elems);
         if (rc < 0) return -1;
         if (rc == 1) {
@@ -2615,8 +2615,9 @@ extern "C" int qtts_hip_rmsnorm_matvec_bf16(float *out, const uint16_t *A, const
     return matvec_any(a, (hipStream_t)stream);
 }
 
-// the decode dispatcher itself (qtts_gemv): batch 1 -> k_gemv1, 2..16 ->
-// k_gemvm (matrix cores) where covered, else k_gemv, 17..64 -> k_gemvx
+// the decode dispatcher itself (qtts_gemv): batch 1 -> k_gemvw / k_gemv1;
+// 2..16 -> the batch GEMV's plan (qtts_bgemv: k_gemvb, else k_gemvm, on the
+// matrix cores) where it covers the shape, else k_gemv; 17..64 -> k_gemvx or -1
 extern "C" int qtts_hip_decode_matvec_bf16(float *out, const uint16_t *A, const float *x, const float *w, float eps,
                                            int rows, int cols, int batch, void *stream) {
     GemvArgs a = gv(A, rows, cols, x, cols, out, rows, batch, EPI_STORE);
@@ -2782,12 +2783,10 @@ extern "C" int qtts_hip_resident_matvec_rows_bf16(float *out, const uint16_t *A,
     return nrows == 2 ? qtts_gemvw_pair(a, (hipStream_t)stream) : qtts_gemvw(a, (hipStream_t)stream);
 }
 
-// One lock-step batch GEMV (2..16 rows: k_gemvb, else k_gemvm; 17..64:
-// k_gemvx) with everything the decode frame can ask of it, on its own.  The
-// split-K scratch is allocated here; the tickets of the self-reducing form
-// live as long as the library (zeroed once: every launch leaves them zero, as
-// the frame graph relies on).  1 = no batch kernel covers the case.
-extern "C" int qtts_hip_batch_matvec_case(const qtts_bgemv_desc_t *d, void *stream) {
+// qtts_bgemv_desc_t checked and translated to the batch kernels' arguments
+// (the split-K scratch and tickets are the caller's: ypart / tick stay unset).
+// No pointer is dereferenced.  -1 = a bad descriptor.
+static int bgemv_desc_args(const qtts_bgemv_desc_t *d, GemvArgs &a) {
     if (!d || !d->A || d->rows < 1 || d->cols < 1 || d->batch < 2 || d->batch > QTTS_HIP_MAX_BATCH) return -1;
     if (d->epi < EPI_STORE || d->epi > EPI_SWIGLU || d->src < 0 || d->src > 2) return -1;
     if ((d->epi == EPI_BIAS || d->epi == EPI_BIAS_SILU) && !d->bias) return -1;
@@ -2796,8 +2795,7 @@ extern "C" int qtts_hip_batch_matvec_case(const qtts_bgemv_desc_t *d, void *stre
     if (d->kz < 0 || d->kz == 1 || d->kz > 4) return -1;
     if (d->kz >= 2 && (d->self_reduce ? !d->y : !d->part_out)) return -1;
     if (d->kz < 2 && !d->y) return -1;
-    hipStream_t st = (hipStream_t)stream;
-    GemvArgs a = gv(d->A, d->rows, d->cols, d->src == 0 ? d->x : nullptr, d->ldx, d->y, d->ldy, d->batch, d->epi);
+    a = gv(d->A, d->rows, d->cols, d->src == 0 ? d->x : nullptr, d->ldx, d->y, d->ldy, d->batch, d->epi);
     if (d->src == 1) a.table = (const bf16_t *)d->table;
     if (d->src == 2) a.table_f32 = (const float *)d->table;
     a.ids = d->ids; a.ids_bstride = d->ids_bstride; a.ids_rstride = d->ids_rstride; a.ids_off = d->ids_off;
@@ -2808,31 +2806,53 @@ extern "C" int qtts_hip_batch_matvec_case(const qtts_bgemv_desc_t *d, void *stre
     a.norm_w = d->norm_w; a.eps = d->eps;
     if (d->xcopy) { a.xcopy = d->xcopy; a.ldxc = d->cols; a.xcopy_normed = d->xcopy_normed; }
     a.bias = d->bias;
-    float *scratch = nullptr;
-    static int *ticks = nullptr;   // (one device: the parity entry of a test process)
     if (d->kz >= 2) {
         a.kz = d->kz; a.ld_ypart = (size_t)d->batch * d->rows;
-        if (d->self_reduce) {
-            if (!ticks) {
-                CK(hipMalloc((void **)&ticks, QTTS_GM_TICKS * sizeof(int)));
-                CK(hipMemset(ticks, 0, QTTS_GM_TICKS * sizeof(int)));
-            }
-            CK(hipMalloc((void **)&scratch, (size_t)d->kz * a.ld_ypart * 4));
-            a.ypart = scratch; a.tick = ticks;
-        } else {
-            a.ypart = d->part_out; a.y = nullptr;
+        if (!d->self_reduce) { a.ypart = d->part_out; a.y = nullptr; }
+    }
+    return 0;
+}
+
+// One lock-step batch GEMV (qtts_bgemv: 2..16 rows k_gemvb, else k_gemvm;
+// 17..64 k_gemvx) with everything the decode frame can ask of it, on its own.  The
+// split-K scratch is allocated here; the tickets of the self-reducing form
+// live as long as the library (zeroed once: every launch leaves them zero, as
+// the frame graph relies on).  1 = no batch kernel covers the case.
+extern "C" int qtts_hip_batch_matvec_case(const qtts_bgemv_desc_t *d, void *stream) {
+    GemvArgs a;
+    if (bgemv_desc_args(d, a)) return -1;
+    hipStream_t st = (hipStream_t)stream;
+    float *scratch = nullptr;
+    static int *ticks = nullptr;   // (one device: the parity entry of a test process)
+    if (d->kz >= 2 && d->self_reduce) {
+        if (!ticks) {
+            CK(hipMalloc((void **)&ticks, QTTS_GM_TICKS * sizeof(int)));
+            CK(hipMemset(ticks, 0, QTTS_GM_TICKS * sizeof(int)));
         }
+        CK(hipMalloc((void **)&scratch, (size_t)d->kz * a.ld_ypart * 4));
+        a.ypart = scratch; a.tick = ticks;
     }
-    int rc;
-    if (d->batch > 16) {
-        rc = qtts_gemvx(a, st);
-    } else {
-        rc = qtts_gemvb(a, st);
-        if (rc == 1) rc = qtts_gemvm(a, st);
-    }
+    int rc = qtts_bgemv(a, st);
     if (hipStreamSynchronize(st) != hipSuccess) rc = -1;
     if (scratch) hipFree(scratch);
     return rc;
+}
+
+// The plan qtts_hip_batch_matvec_case would launch (qtts_bgemv_plan), host
+// only: the self-reducing form's scratch and tickets are stand-in addresses.
+extern "C" int qtts_hip_batch_matvec_plan(const qtts_bgemv_desc_t *d, qtts_bgemv_plan_t *out) {
+    GemvArgs a;
+    if (!out || bgemv_desc_args(d, a)) return -1;
+    if (d->kz >= 2 && d->self_reduce) { a.ypart = (float *)(uintptr_t)256; a.tick = (int *)(uintptr_t)256; }
+    BgPlan p;
+    const int rc = qtts_bgemv_plan(a, p);
+    *out = qtts_bgemv_plan_t();
+    if (rc) return rc;
+    out->kernel = p.kernel; out->n_tmpl = p.nt;
+    for (int i = 0; i < p.nt; ++i) out->tmpl[i] = p.t[i];
+    out->src = p.src; out->grid_x = (int)p.grid.x; out->grid_y = (int)p.grid.y; out->block = (int)p.block.x;
+    out->lds_bytes = p.smem; out->tpw = p.tpw; out->cch = p.cch;
+    return 0;
 }
 
 // One frame run eagerly with an event pair around every kernel launch on the

@@ -97,7 +97,7 @@ EXPORTS = [
     "qwen_tts_force_codes", "qwen_tts_tap_draw", "qwen_tts_last_drawn", "qwen_tts_tap_result",
     "qtts_dev_force", "qtts_dev_tap", "qtts_dev_get_drawn", "qtts_dev_get_tap",
     "qtts_hip_xgemm_plan", "qtts_hip_xgemm_case", "qtts_hip_xgemm_func",
-    "qtts_hip_batch_matvec_case", "qtts_hip_gemv_wide_launches",
+    "qtts_hip_batch_matvec_case", "qtts_hip_gemv_wide_launches", "qtts_hip_batch_matvec_plan",
 ]
 
 MAX_BATCH = 64   # QWEN_TTS_MAX_BATCH / QTTS_HIP_MAX_BATCH: lock-step slots per context
@@ -123,6 +123,21 @@ class BGemvDesc(C.Structure):
         ("kz", C.c_int), ("self_reduce", C.c_int),
         ("part_out", C.c_void_p),
     ]
+
+
+class BGemvPlan(C.Structure):
+    """qtts_bgemv_plan_t (include/qtts_hip.h): the batch GEMV planner's answer."""
+    _fields_ = [
+        ("kernel", C.c_int),
+        ("n_tmpl", C.c_int), ("tmpl", C.c_int * 5),
+        ("src", C.c_int),
+        ("grid_x", C.c_int), ("grid_y", C.c_int), ("block", C.c_int),
+        ("lds_bytes", C.c_size_t),
+        ("tpw", C.c_int), ("cch", C.c_int),
+    ]
+
+
+BGEMV_KERNELS = {1: "k_gemvm", 2: "k_gemvb", 4: "k_gemvx"}   # qtts_bgemv_plan_t.kernel
 
 
 class XGemmDesc(C.Structure):
@@ -342,6 +357,9 @@ def lib():
         L.qtts_hip_batch_matvec_case.argtypes = [C.POINTER(BGemvDesc), vp]
         L.qtts_hip_gemv_wide_launches.restype = C.c_longlong
         L.qtts_hip_gemv_wide_launches.argtypes = []
+    if hasattr(L, "qtts_hip_batch_matvec_plan"):
+        L.qtts_hip_batch_matvec_plan.restype = C.c_int
+        L.qtts_hip_batch_matvec_plan.argtypes = [C.POINTER(BGemvDesc), C.POINTER(BGemvPlan)]
     _LIB = L
     return L
 
@@ -917,17 +935,16 @@ class Kernels:
         return True
 
     @staticmethod
-    def batch_matvec_case(A_u16, batch, y, x=None, table=None, ids_i32=None, ids_bstride=1, ids_rstride=0, ids_off=0,
-                          row_sel_i32=None, part_in=None, norm_w=None, eps=1e-6, xcopy=None, xcopy_normed=False,
-                          epi=0, bias=None, kz=0, self_reduce=True, part_out=None):
-        """One lock-step batch decode GEMV (qtts_hip_batch_matvec_case) on
-        `batch` rows (2..16: k_gemvb / k_gemvm, 17..64: k_gemvx).  A_u16 [rows,
-        cols] bf16 bits.  Source: x [batch, cols] fp32 (+ part_in [n, batch,
-        cols] added in order), or a bf16-bit / fp32 table [*, cols] gathered by
-        ids_i32[ids_off + b * ids_bstride + row_sel_i32[b] * ids_rstride].
-        y [batch, rows] (epi 4: rows / 2).  kz >= 2: split-K, self-reducing
-        into y (epi 3) or, self_reduce False, raw partials to part_out [kz,
-        batch, rows].  False where no batch kernel covers the case."""
+    def bgemv_desc(A_u16, batch, y, x=None, table=None, ids_i32=None, ids_bstride=1, ids_rstride=0, ids_off=0,
+                   row_sel_i32=None, part_in=None, norm_w=None, eps=1e-6, xcopy=None, xcopy_normed=False,
+                   epi=0, bias=None, kz=0, self_reduce=True, part_out=None):
+        """The BGemvDesc of one lock-step batch decode GEMV on `batch` rows.
+        A_u16 [rows, cols] bf16 bits.  Source: x [batch, cols] fp32 (+ part_in
+        [n, batch, cols] added in order), or a bf16-bit / fp32 table [*, cols]
+        gathered by ids_i32[ids_off + b * ids_bstride + row_sel_i32[b] *
+        ids_rstride].  y [batch, rows] (epi 4: rows / 2).  kz >= 2: split-K,
+        self-reducing into y (epi 3) or, self_reduce False, raw partials to
+        part_out [kz, batch, rows]."""
         d = BGemvDesc()
         d.rows, d.cols, d.batch = int(A_u16.shape[0]), int(A_u16.shape[1]), int(batch)
         d.A = _ptr(A_u16)
@@ -945,11 +962,34 @@ class Kernels:
         d.epi, d.bias = epi, _ptr(bias)
         d.y, d.ldy = _ptr(y), (int(y.stride(0)) if y is not None else 0)
         d.kz, d.self_reduce, d.part_out = kz, int(bool(self_reduce)), _ptr(part_out)
+        return d
+
+    @staticmethod
+    def batch_matvec_case(A_u16, batch, y, **kw):
+        """One lock-step batch decode GEMV (qtts_hip_batch_matvec_case; 2..16
+        rows: k_gemvb / k_gemvm, 17..64: k_gemvx) described as bgemv_desc takes
+        it.  False where no batch kernel covers the case."""
+        d = Kernels.bgemv_desc(A_u16, batch, y, **kw)
         rc = lib().qtts_hip_batch_matvec_case(C.byref(d), _stream())
         if rc == 1:
             return False
         _ok(rc, "batch_matvec_case")
         return True
+
+    @staticmethod
+    def batch_matvec_plan(desc):
+        """The batch GEMV planner's answer for a BGemvDesc
+        (qtts_hip_batch_matvec_plan; host only, no device needed, the pointers
+        only need their alignment): a dict with the kernel's name, its template
+        integers, grid, block, LDS bytes and k_gemvm's run-time tpw / cch, or
+        None where no batch kernel covers the case."""
+        p = BGemvPlan()
+        rc = lib().qtts_hip_batch_matvec_plan(C.byref(desc), C.byref(p))
+        if rc == 1:
+            return None
+        _ok(rc, "batch_matvec_plan")
+        return dict(kernel=BGEMV_KERNELS[p.kernel], tmpl=list(p.tmpl[:p.n_tmpl]), grid=[p.grid_x, p.grid_y],
+                    block=p.block, lds=int(p.lds_bytes), tpw=p.tpw, cch=p.cch)
 
     @staticmethod
     def gemv_wide_launches():

@@ -10,7 +10,7 @@ import subprocess
 import qtts
 from conftest import ROOT
 
-NEW_SYMBOLS = ["qtts_hip_batch_matvec_case", "qtts_hip_gemv_wide_launches"]
+NEW_SYMBOLS = ["qtts_hip_batch_matvec_case", "qtts_hip_gemv_wide_launches", "qtts_hip_batch_matvec_plan"]
 
 
 def _define(header, name):
@@ -34,15 +34,18 @@ def test_library_exports_and_binding_declares_the_wide_batch_symbols():
     assert lib.qtts_hip_gemv_wide_launches.restype is C.c_longlong
     assert lib.qtts_hip_batch_matvec_case.argtypes[0] is C.POINTER(qtts.BGemvDesc)
     assert callable(qtts.Kernels.batch_matvec_case) and callable(qtts.Kernels.gemv_wide_launches)
-    # the descriptor mirrors qtts_bgemv_desc_t field for field
+    assert lib.qtts_hip_batch_matvec_plan.argtypes == [C.POINTER(qtts.BGemvDesc), C.POINTER(qtts.BGemvPlan)]
+    assert callable(qtts.Kernels.batch_matvec_plan)
+    # the descriptor and the plan mirror qtts_bgemv_desc_t / qtts_bgemv_plan_t field for field
     txt = open(os.path.join(ROOT, "include", "qtts_hip.h")).read()
-    body = re.search(r"typedef struct \{([^}]*)\} qtts_bgemv_desc_t;", txt).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    names = []
-    for decl in body.split(";"):
-        parts = [p.strip() for p in decl.split(",") if p.strip()]
-        names += [re.sub(r"^.*[\s\*]", "", p) for p in parts]
-    assert names == [f[0] for f in qtts.BGemvDesc._fields_], names
+    for ctype, mirror in (("qtts_bgemv_desc_t", qtts.BGemvDesc), ("qtts_bgemv_plan_t", qtts.BGemvPlan)):
+        body = re.search(r"typedef struct \{([^}]*)\} %s;" % ctype, txt).group(1)
+        body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+        names = []
+        for decl in body.split(";"):
+            parts = [p.strip() for p in decl.split(",") if p.strip()]
+            names += [re.sub(r"\[\d+\]$", "", re.sub(r"^.*[\s\*]", "", p)) for p in parts]
+        assert names == [f[0] for f in mirror._fields_], names
 
 
 def test_batch_matvec_case_refuses_bad_arguments_before_any_device_work():
@@ -65,6 +68,9 @@ def test_batch_matvec_case_refuses_bad_arguments_before_any_device_work():
                 dict(kz=1), dict(kz=5), dict(kz=-2),
                 dict(kz=2, self_reduce=0), dict(kz=2, self_reduce=1, y=None)):
         assert lib.qtts_hip_batch_matvec_case(C.byref(desc(**bad)), None) == -1, bad
+        assert lib.qtts_hip_batch_matvec_plan(C.byref(desc(**bad)), C.byref(qtts.BGemvPlan())) == -1, bad
+    assert lib.qtts_hip_batch_matvec_plan(C.byref(desc()), None) == -1
+    assert lib.qtts_hip_batch_matvec_plan(C.byref(desc()), C.byref(qtts.BGemvPlan())) == 0
 
 
 def test_slot_limit_refused_before_the_device(capfd):

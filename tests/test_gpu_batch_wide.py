@@ -1,6 +1,7 @@
 """Lock-step decode of 17..64 slots: the wide batch GEMV (k_gemvx, through
 qtts_hip_batch_matvec_case) against float64, its row independence bit for
-bit, its split-K tickets, and the model on 17..64 slots against the oracle's
+bit, its split-K tickets, the same float64 bar under the 2..16-row kernels
+(k_gemvb and k_gemvm), and the model on 17..64 slots against the oracle's
 single runs (lock step, EOS queue with tail compaction across 16 rows, bf16
 KV, teacher forcing, the 64-slot limit, one weight pass per GEMV).
 
@@ -54,11 +55,12 @@ def _epilogue(acc, bound, epi, y0, bias):
 
 
 def run_case(dev, R, Cc, B, *, norm=False, epi=STORE, src="x", n_part=0, xcopy=None, kz=0, self_reduce=True,
-             row_sel=False, seed=0, x_override=None):
+             row_sel=False, seed=0, x_override=None, kernel=None):
     """One qtts_hip_batch_matvec_case against float64.  Returns (got, ref,
     bound) of y (or of the summed consumer-add partials), after asserting the
     xcopy output.  Inputs and partials are of order 1, so a dropped partial or
-    row is far outside the bound."""
+    row is far outside the bound.  kernel: the kernel the planner must have
+    chosen for the case (qtts_hip_batch_matvec_plan on the same arguments)."""
     import torch
     rng = np.random.default_rng(seed + R + 3 * Cc + 7 * B)
     A = _weights(R, Cc)
@@ -106,10 +108,14 @@ def run_case(dev, R, Cc, B, *, norm=False, epi=STORE, src="x", n_part=0, xcopy=N
     part_out = None
     if kz and not self_reduce:
         part_out = torch.full((kz, B, R), float("nan"), device=dev)
-    ok = qtts.Kernels.batch_matvec_case(T(A, dev, torch.int16), B, y, eps=EPS, xcopy=xc,
-                                        xcopy_normed=xcopy == "normed", epi=epi,
-                                        bias=T(bias, dev) if bias is not None else None, kz=kz,
-                                        self_reduce=self_reduce, part_out=part_out, **kw)
+    kw.update(eps=EPS, xcopy=xc, xcopy_normed=xcopy == "normed", epi=epi,
+              bias=T(bias, dev) if bias is not None else None, kz=kz, self_reduce=self_reduce, part_out=part_out)
+    Ad = T(A, dev, torch.int16)
+    if kernel is not None:
+        plan = qtts.Kernels.batch_matvec_plan(qtts.Kernels.bgemv_desc(Ad, B, y, **kw))
+        assert plan is not None, "no batch kernel covers the case"
+        assert plan["kernel"] == kernel, plan
+    ok = qtts.Kernels.batch_matvec_case(Ad, B, y, **kw)
     assert ok, "no batch kernel covers the case"
     torch.cuda.synchronize()
     if xcopy:
@@ -187,6 +193,56 @@ REAL = [
 def test_wide_real_shapes(gpu, name, R, Cc, kw, B):
     """the 1.7B talker's and sub-talker's decode GEMVs, once each at 24 and 64 rows"""
     check(*run_case(gpu, R, Cc, B, **kw))
+
+
+# ---------------------------------------------------------------- 1b. the same bar under the 2..16-row kernels
+NARROW = [2, 7, 8, 9, 16]
+NARROW_KERNELS = [("k_gemvb", None), ("k_gemvm", "0")]   # (kernel planned, QTTS_HIP_GEMVB)
+
+
+@pytest.fixture(params=NARROW_KERNELS, ids=[k for k, _ in NARROW_KERNELS])
+def narrow_kernel(request, monkeypatch):
+    """the planner's default at 2..16 rows (k_gemvb takes every case below),
+    then k_gemvm through QTTS_HIP_GEMVB=0; run_case asserts the plan"""
+    kernel, env = request.param
+    if env is None:
+        monkeypatch.delenv("QTTS_HIP_GEMVB", raising=False)
+    else:
+        monkeypatch.setenv("QTTS_HIP_GEMVB", env)
+    monkeypatch.delenv("QTTS_HIP_GB_W", raising=False)
+    return kernel
+
+
+@pytest.mark.parametrize("B", NARROW)
+@pytest.mark.parametrize("R,Cc", SMALL)
+def test_narrow_small_shapes(gpu, narrow_kernel, R, Cc, B):
+    """the five forms of test_wide_small_shapes at 2..16 rows, on k_gemvb and on k_gemvm"""
+    k = narrow_kernel
+    check(*run_case(gpu, R, Cc, B, kernel=k))
+    check(*run_case(gpu, R, Cc, B, norm=True, xcopy="normed", kernel=k))
+    check(*run_case(gpu, R, Cc, B, epi=RESID, xcopy="raw", kernel=k))
+    check(*run_case(gpu, R, Cc, B, norm=True, epi=BIAS_SILU, kernel=k))
+    check(*run_case(gpu, R, Cc, B, epi=BIAS, kernel=k))
+
+
+@pytest.mark.parametrize("B", NARROW)
+@pytest.mark.parametrize("src,row_sel", [("tab16", False), ("tab16", True), ("tabf", True)])
+def test_narrow_table_sources(gpu, narrow_kernel, B, src, row_sel):
+    """the forms of test_wide_table_sources at 2..16 rows, on k_gemvb and on k_gemvm"""
+    k = narrow_kernel
+    check(*run_case(gpu, 256, 128, B, norm=True, src=src, row_sel=row_sel, xcopy="raw", kernel=k))
+    check(*run_case(gpu, 256, 128, B, norm=True, epi=SWIGLU, src=src, row_sel=row_sel, kernel=k))
+
+
+@pytest.mark.parametrize("B", NARROW)
+def test_narrow_small_split_k_and_partials(gpu, narrow_kernel, B):
+    """the forms of test_wide_small_split_k_and_partials at 2..16 rows, on k_gemvb and on k_gemvm"""
+    k = narrow_kernel
+    for n in (1, 2, 3, 4):
+        check(*run_case(gpu, 256, 128, B, norm=True, epi=SWIGLU, n_part=n, xcopy="raw", kernel=k))
+    for kz in (2, 4):
+        check(*run_case(gpu, 256, 128, B, epi=RESID, kz=kz, self_reduce=True, kernel=k))
+        check(*run_case(gpu, 256, 128, B, epi=RESID, kz=kz, self_reduce=False, kernel=k))
 
 
 # ---------------------------------------------------------------- 2. row independence, bitwise
