@@ -213,6 +213,41 @@ int qtts_dev_get_drawn(qtts_dev_t *dev, int b, int *host, int max_frames);
  * the RNG state before the draw and the free-drawn id (any of the three may be
  * NULL).  Returns n, or -1 if the draw never happened. */
 int qtts_dev_get_tap(qtts_dev_t *dev, int i, float *logits_host, int max_n, unsigned *rng_bits, int *drawn);
+/* ---- per-slot sampling parameters and seeds (no c/ counterpart: the reference
+ * decodes one utterance per call with the ctx's parameters) ----
+ * A run samples every slot with qtts_dev_begin's parameters until the first
+ * qtts_dev_slot_params after that begin.  That call arms a device table of one
+ * 32-byte row per slot, every row first filled from begin's parameters, and
+ * from then on the frames hold the per-slot samplers (k_sample_p.hip), whose
+ * workgroup b draws with row b: the talker draw with temperature / top_p /
+ * repetition_penalty / top_k, resetting the slot's sub-talker RNG to the row's
+ * seed each frame, the sub-talker draws with the st_ values.  temperature <= 0
+ * becomes 1e-5, top_k <= 0 or >= the vocabulary means no top-k, as in the
+ * reference.  fixed_codec_tokens and the frame limit stay run-wide.
+ * Which kernel family the frames hold is decided for the run: the fast-only
+ * 1024-thread family while every row set so far takes the fast path for both
+ * draws (top_p >= 1 and 0 < top_k <= 1024 below the vocabulary), the general
+ * 256-thread kernel (fast or full per row) from the first row that does not;
+ * a refill that admits such a row mid-run makes the next frame capture the
+ * general graphs, and the run never goes back.
+ * Before frame 0 the call also sets slot b's two RNG states to the row's
+ * seed; later in a run it is ordered on the context stream and the next
+ * qtts_dev_refill(dev, b) starts the slot from the row's seed;
+ * qtts_dev_move_slot carries the row with the slot.  The next qtts_dev_begin
+ * disarms and frees the table (a run that never arms allocates nothing).
+ * -1 with a message, and nothing launched, for a call before any
+ * qtts_dev_begin, a bad slot, a non-finite value, top_p / st_top_p <= 0 or
+ * repetition_penalty <= 0, and when forced codes / taps are armed for the run
+ * (qtts_dev_force / qtts_dev_tap likewise return -1 once this is armed: the
+ * combination is left out). */
+typedef struct {
+    float temperature, top_p, repetition_penalty;
+    int top_k;
+    float st_temperature, st_top_p;
+    int st_top_k;
+    int seed;
+} qtts_slot_params_t;
+int qtts_dev_slot_params(qtts_dev_t *dev, int b, const qtts_slot_params_t *p);
 /* Codec decode of slot b's generated codes (device-resident) into a malloc'd
  * host buffer of T*1920 samples (caller frees). */
 float *qtts_dev_codec_slot(qtts_dev_t *dev, int b, int T, int *out_samples);
@@ -316,6 +351,14 @@ int qtts_hip_resident_matvec_bf16(float *out_dev, const uint16_t *A_dev, const f
  * holds the float-bit xorshift state per row (updated in place). */
 int qtts_hip_sample_top_k(int *out_dev, const float *logits_dev, int vocab, int top_k, float top_p,
                           float temperature, uint32_t *rng_bits_dev, int batch, void *stream);
+/* The same with one parameter set per row: top_k / top_p / temperature are
+ * HOST arrays of `batch` entries.  Builds the per-slot parameter table and
+ * launches the per-slot sampler family a run with these rows would hold
+ * (fast-only when every row is fast-path eligible, else the general kernel;
+ * QTTS_HIP_SAMPLE_W=0: always the general one); waits for the launch. */
+int qtts_hip_sample_top_k_rows(int *out_dev, const float *logits_dev, int vocab, const int *top_k,
+                               const float *top_p, const float *temperature, uint32_t *rng_bits_dev, int batch,
+                               void *stream);
 /* kernel_causal_conv1d (c/qwen_tts_kernels.c:659): [ci, L] -> [co, L] */
 int qtts_hip_causal_conv1d(float *out_dev, const float *in_dev, const float *w_dev, const float *b_dev, int ci,
                            int co, int k, int L, int dilation, int groups, void *stream);
@@ -534,6 +577,11 @@ long long qtts_hip_st_pair_passes(void);
  * into a frame graph) since the library loaded: one per decode GEMV whatever
  * the slot count, none at 16 slots or fewer. */
 long long qtts_hip_gemv_wide_launches(void);
+/* Launches of the per-slot sampler (qtts_dev_slot_params) enqueued (or captured
+ * into a frame graph) since the library loaded: one per code group and frame
+ * with launch-per-op frames (QTTS_HIP_NO_GRAPH), none in a run that never
+ * armed the table. */
+long long qtts_hip_sample_slot_launches(void);
 
 /* Diagnostics: run ONE frame eagerly on the current generation state with an
  * event pair around every kernel launch on the context stream.  kind[i]:

@@ -190,6 +190,9 @@ typedef struct {
     long long queue_slot_frames_used; /* sum of frames generated */
     long long queue_rows_launched;    /* sum over launched frames of the slot rows they ran (the tail launches
                                          only the running slots): occupancy = frames_used / rows_launched */
+    void *sampling;              /* per-utterance sampling armed for the next generation call (one-shot;
+                                    qwen_tts_set_utterance_sampling).  It sits in front of `force`, which
+                                    stays the struct's last field */
     void *force;                 /* forced codes / taps armed for the next generation call (one-shot) */
 } qwen_tts_ctx_t;
 
@@ -387,6 +390,37 @@ int qwen_tts_force_codes(qwen_tts_ctx_t *ctx, int slot, const int *codes, int n_
 int qwen_tts_tap_draw(qwen_tts_ctx_t *ctx, int slot, int frame, int group);
 int qwen_tts_last_drawn(qwen_tts_ctx_t *ctx, int slot, int *codes, int max_frames);
 int qwen_tts_tap_result(qwen_tts_ctx_t *ctx, int i, float *logits, int max_n, unsigned *rng_bits, int *drawn);
+/* Per-utterance sampling parameters and seeds (no c/ counterpart: the
+ * reference decodes one utterance per call with the ctx's parameters).  N
+ * takes of one prompt with N seeds, or requests with different temperature /
+ * top-k / top-p / repetition penalty, share one lock-step batch or one work
+ * queue; every utterance decodes bit for bit as it would alone with its own
+ * parameters and seed, whatever slot it lands in and whatever the other slots
+ * draw.  max_new_tokens and fixed_codec_tokens stay the ctx's for all.
+ * qwen_tts_sampling_defaults: fills *s from the ctx's current fields (the
+ *   values an unarmed call uses).
+ * qwen_tts_set_utterance_sampling: per[i] is for utterance i of the NEXT
+ *   generation call -- slot i of a batch / voice-clone batch, utterance i
+ *   (input order, whatever slot and admission order) of
+ *   qwen_tts_generate_queue, per[0] of the single-utterance and stream calls.
+ *   The values are checked here: -1 with a message for n < 1, a non-finite
+ *   value, top_p / subtalker_top_p <= 0 or repetition_penalty <= 0 (an earlier
+ *   arming stays as it was).  temperature <= 0 samples at 1e-5, top_k <= 0 or
+ *   >= the vocabulary means no top-k, as in the reference.
+ * Arming is ONE-SHOT, as for qwen_tts_force_codes: the next generate* call
+ * consumes it whether it succeeds or not.  That call fails with -1 before the
+ * device is touched when n differs from its utterance count (nb, nq, or 1), or
+ * when forced codes / taps are armed as well (both are disarmed: the
+ * combination is not supported). */
+typedef struct {
+    float temperature, top_p, repetition_penalty;
+    int top_k;
+    float subtalker_temperature, subtalker_top_p;
+    int subtalker_top_k;
+    int sample_seed;
+} qwen_tts_sampling_t;
+int qwen_tts_sampling_defaults(const qwen_tts_ctx_t *ctx, qwen_tts_sampling_t *s);
+int qwen_tts_set_utterance_sampling(qwen_tts_ctx_t *ctx, int n, const qwen_tts_sampling_t *per);
 /* Streaming generation (the reference has only a per-step
  * progress callback, c/qwen_tts.h:356): audio is decoded incrementally and
  * exactly (qtts_hip.h codec stream) and handed to `cb` as it is produced --

@@ -198,6 +198,18 @@ __device__ __forceinline__ float expf_glibc_wave(float x, uint64_t tab_lane) {
         return ((uint64_t)hi << 32) | lo;
     });
 }
+// expf_glibc_wave for arguments outside expf's finite range as well.  A lane
+// of expf_glibc_wave whose argument under- or overflows returns before the
+// table's cross-lane reads and so drops out of them: the lanes that read ITS
+// table entry then get an undefined value.  Here such a lane runs the core on
+// 0 and selects its 0 / inf afterwards, so every lane takes part in every
+// read.  (The per-slot sampler uses this one: candidates at -1e9 reach the
+// top-k of a small vocabulary.)
+__device__ __forceinline__ float expf_glibc_wave_all(float x, uint64_t tab_lane) {
+    const bool over = x > 0x1.62e42ep6f, under = x < -0x1.9fe368p6f;
+    const float y = expf_glibc_wave((over || under) ? 0.0f : x, tab_lane);
+    return over ? __builtin_inff() : under ? 0.0f : y;
+}
 
 // Write-through ("sc1") 4-byte store / load at agent scope: the hand-off form
 // of cdna_hip_programming.md Guideline 16 R1 for data another workgroup of the

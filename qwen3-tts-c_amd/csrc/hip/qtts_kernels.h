@@ -310,6 +310,33 @@ struct SampForce {
 // qtts_sample with the forced form of the same three launch families
 int qtts_sample_forced(const SampArgs &a, const SampForce &f, hipStream_t st);
 
+// Per-slot sampling parameters (qtts_dev_slot_params): one 32-byte row per
+// slot, which the per-slot sampler's workgroup b loads as two dwordx4 with its
+// first loads (k_sample_p.hip).  Talker draws take temp / top_p / rep / top_k
+// and reset st_rng[b] to seed_bits, sub-talker draws take the st_ values; the
+// same fields of SampArgs are then unused.
+struct alignas(16) SampSlotRow {
+    float temp, top_p, rep;
+    int top_k;
+    float st_temp, st_top_p;
+    int st_top_k;
+    uint32_t seed_bits;
+};
+static_assert(sizeof(SampSlotRow) == 32, "two dwordx4 loads cover a row");
+// the row's draw of mode `mode` (1 talker, 0 sub-talker) over n logits is
+// fast-path eligible (qtts_sample_dev.h fast_path)
+bool qtts_sample_row_fast(const SampSlotRow &r, int mode, int n);
+// The per-slot sampler: the fast-only 1024-thread family k_sample_pw when
+// every row of the run is fast-path eligible in both modes (all_fast; never
+// otherwise) and QTTS_HIP_SAMPLE_W is not 0, else the general 256-thread
+// kernel k_sample_p, which picks fast or full per row.
+int qtts_sample_slots(const SampArgs &a, const SampSlotRow *tab, bool all_fast, hipStream_t st);
+// its launches enqueued (or captured) since the library loaded (qtts_hip_sample_slot_launches)
+long long qtts_sample_slot_launches();
+// writes row b of the table, stream-ordered; rng / st_rng non-null: the slot's
+// RNG states start from the row's seed as well
+int qtts_slot_row_set(SampSlotRow *tab, int b, const SampSlotRow &r, uint32_t *rng, uint32_t *st_rng, hipStream_t st);
+
 struct EmbedSumArgs {
     const int *codes = nullptr;
     int codes_bstride = 0, G = 16;

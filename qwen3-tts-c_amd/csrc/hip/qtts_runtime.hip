@@ -164,9 +164,10 @@ struct qtts_dev {
     // nrun < nb slots (qtts_dev_set_rows), captured on first use
     hipGraphExec_t gNr[QTTS_MAX_SLOTS + 1] = {};
     // what g0 / gN hold: -1 nothing valid, 0 no graphs (QTTS_HIP_NO_GRAPH),
-    // 1 the plain frame, 2 the frame with the forced sampler (f_armed); every
-    // arming and every qtts_dev_begin that drops one resets it to -1, so a
-    // graph of either kind is never replayed for the other
+    // 1 the plain frame, 2 the frame with the forced sampler (f_armed), 3 / 4
+    // the frame with the per-slot sampler, fast-only / general (sp_armed);
+    // every arming and every qtts_dev_begin that drops one resets it to -1, so
+    // a graph of one kind is never replayed for another
     int graph_key = -1;
     // teacher forcing, the free-draw record and logit taps (qtts_dev_force /
     // qtts_dev_tap): allocated by the first arming after a qtts_dev_begin,
@@ -179,6 +180,16 @@ struct qtts_dev {
     int f_run_frames = 0;   // max_frames of the last qtts_dev_begin (the state may hold more)
     bool f_armed = false;
     size_t f_bytes = 0;
+    // per-slot sampling parameters (qtts_dev_slot_params): one SampSlotRow per
+    // slot on the device with its host mirror, allocated by the first call
+    // after a qtts_dev_begin and freed by the next begin -- a plain run holds
+    // none of it.  While armed the frames hold the per-slot samplers (graph_key
+    // 3: the fast-only family; 4: the general kernel, from the first row of the
+    // run that is not fast-path eligible in both modes on -- sp_general never
+    // goes back within a run)
+    SampSlotRow *sp_tab = nullptr;
+    std::vector<SampSlotRow> sp_host;
+    bool sp_armed = false, sp_general = false;
     // EOS-mode lagged poll: the sampler mirrors each slot's stop into pinned
     // host memory; an event after every frame lets the host wait for frame
     // s - 1 while frame s is already queued (qtts_dev_frame_done)
@@ -307,8 +318,24 @@ static void free_force(qtts_dev *dv) {
     dv->graph_key = -1;
 }
 
+// drops the per-slot parameter table (the frame graphs that hold its pointer
+// become invalid with it)
+static void free_slot_params(qtts_dev *dv) {
+    if (!dv->sp_armed) return;
+    hipStreamSynchronize(dv->st);
+    if (dv->sp_tab) {
+        hipFree(dv->sp_tab);
+        dv->sbytes -= dv->sp_host.size() * sizeof(SampSlotRow);
+    }
+    dv->sp_tab = nullptr;
+    dv->sp_host.clear();
+    dv->sp_armed = dv->sp_general = false;
+    dv->graph_key = -1;
+}
+
 static void free_state(qtts_dev *dv) {
     free_force(dv);
+    free_slot_params(dv);
     dv->f_phase = 0;
     if (dv->g0) { hipGraphExecDestroy(dv->g0); dv->g0 = nullptr; }
     if (dv->gN) { hipGraphExecDestroy(dv->gN); dv->gN = nullptr; }
@@ -1262,6 +1289,8 @@ static int head_sample(qtts_dev *dv, const GemvArgs &a, const SampArgs &s, int k
         f.tap_logits = dv->f_tap_logits; f.tap_meta = dv->f_tap_meta; f.tap_ld = dv->f_tap_ld;
         return qtts_sample_forced(s, f, dv->st);
     }
+    // per-slot parameters: the per-slot sampler (its own frame graphs, graph_key 3 / 4)
+    if (dv->sp_armed) return qtts_sample_slots(s, dv->sp_tab, !dv->sp_general, dv->st);
     return qtts_sample(s, dv->st);
 }
 
@@ -1632,8 +1661,11 @@ static int capture(qtts_dev *dv, bool with_talker, hipGraphExec_t *out) {
 // faster, also in EOS mode (4096-frame capacity, 65 splits): 31.0 / 31.3 vs
 // 31.1 / 30.5 audio-s/s (profiles/r03c_eos_ab.txt).
 static int ensure_graphs(qtts_dev *dv) {
-    const int want = dv->f_armed ? 2 : 1;   // (the forced sampler's frame is another graph)
+    // (the forced sampler's frame is another graph, and so is each per-slot family's)
+    const int want = dv->f_armed ? 2 : dv->sp_armed ? (dv->sp_general ? 4 : 3) : 1;
     if (dv->g0 && dv->gN && dv->graph_key == want) return 0;
+    // (mid-run: a refill admitted the run's first row that needs the full path)
+    if (dv->f_phase == 2 && (dv->g0 || dv->gN)) CK(hipStreamSynchronize(dv->st));
     if (dv->g0) { hipGraphExecDestroy(dv->g0); dv->g0 = nullptr; }
     if (dv->gN) { hipGraphExecDestroy(dv->gN); dv->gN = nullptr; }
     drop_row_graphs(dv);
@@ -1699,6 +1731,7 @@ extern "C" int qtts_dev_begin(qtts_dev_t *dv, int nb, int max_frames, int max_pr
     hipSetDevice(dv->device);
     CKI(join_prime(dv));   // a prime left pending by a run that pushed no frames
     free_force(dv);        // forcing and taps last for one run (and their record until the next begins)
+    free_slot_params(dv);  // and so do per-slot sampling parameters
     dv->f_run_frames = max_frames;
     if (max_prefill < 16) max_prefill = 16;
     // (another cache element type: new state, and with it new frame graphs)
@@ -1902,7 +1935,8 @@ extern "C" int qtts_dev_refill(qtts_dev_t *dv, int b) {
     r.row = dv->prefill + ((size_t)b * dv->p_cap + r.pos) * d.H;
     r.x = dv->x_tk; r.kv_len = dv->kv_len; r.n_gen = dv->n_gen; r.cur_row = dv->cur_row; r.stopped = dv->stopped;
     r.stop_step = dv->stop_step; r.last_tok = dv->last_tok; r.counts = dv->counts;
-    r.rng = dv->rng; r.st_rng = dv->st_rng; r.seed_bits = seed_bits(dv->par.seed);
+    r.rng = dv->rng; r.st_rng = dv->st_rng;
+    r.seed_bits = dv->sp_armed ? dv->sp_host[b].seed_bits : seed_bits(dv->par.seed);   // (the slot's own row)
     CKI(qtts_slot_reset(r, dv->st));
     CK(hipStreamSynchronize(dv->st));   // (the prefill's row lists are host vectors)
     // the host's stop mirror: no queued frame writes it for this slot (it was
@@ -1964,6 +1998,10 @@ extern "C" int qtts_dev_move_slot(qtts_dev_t *dv, int from, int to) {
         CK(row(p, 4));
     CK(row(dv->rng, 4));
     CK(row(dv->st_rng, 4));
+    if (dv->sp_armed) {   // the slot's sampling parameters travel with it
+        CK(row(dv->sp_tab, sizeof(SampSlotRow)));
+        dv->sp_host[to] = dv->sp_host[from];
+    }
     CK(hipStreamSynchronize(st));
     dv->p_len_h[to] = dv->p_len_h[from];
     dv->n_tr_h[to] = dv->n_tr_h[from];
@@ -2118,6 +2156,10 @@ static int arm_force(qtts_dev *dv) {
         return -1;
     }
     if (dv->f_armed) return 0;
+    if (dv->sp_armed) {
+        fprintf(stderr, "qtts: forced codes / taps refused: per-slot sampling parameters are armed for this run\n");
+        return -1;
+    }
     const qtts_dims_t &d = dv->d;
     const size_t tab = (size_t)dv->nb * (dv->max_frames + 1) * d.G * sizeof(int);
     const int ld = d.V > d.Vs ? d.V : d.Vs;
@@ -2381,6 +2423,81 @@ extern "C" int qtts_dev_codec_async_end(qtts_dev_t *dv, float *host_out, int fra
     return frames * 1920;
 }
 
+// ----------------------------------------------------------------- per-slot sampling parameters
+static SampSlotRow slot_row_of(const qtts_slot_params_t &p) {
+    SampSlotRow r;
+    r.temp = p.temperature; r.top_p = p.top_p; r.rep = p.repetition_penalty; r.top_k = p.top_k;
+    r.st_temp = p.st_temperature; r.st_top_p = p.st_top_p; r.st_top_k = p.st_top_k; r.seed_bits = seed_bits(p.seed);
+    return r;
+}
+
+static bool slot_params_ok(const char *who, const qtts_slot_params_t &p) {
+    const float f[5] = {p.temperature, p.top_p, p.repetition_penalty, p.st_temperature, p.st_top_p};
+    for (float v : f)
+        if (!std::isfinite(v)) {
+            fprintf(stderr, "%s: a non-finite sampling parameter\n", who);
+            return false;
+        }
+    if (p.top_p <= 0.0f || p.st_top_p <= 0.0f || p.repetition_penalty <= 0.0f) {
+        fprintf(stderr, "%s: top_p %g / %g and repetition_penalty %g must be > 0\n", who, p.top_p, p.st_top_p,
+                p.repetition_penalty);
+        return false;
+    }
+    return true;
+}
+
+// both of the row's draws (talker over V ids, sub-talker over Vs) take the fast path
+static bool slot_row_fast(const qtts_dev *dv, const SampSlotRow &r) {
+    return qtts_sample_row_fast(r, 1, dv->d.V) && qtts_sample_row_fast(r, 0, dv->d.Vs);
+}
+
+extern "C" int qtts_dev_slot_params(qtts_dev_t *dv, int b, const qtts_slot_params_t *p) {
+    if (!dv || !p) return -1;
+    if (dv->f_phase < 1) {
+        fprintf(stderr, "qtts_dev_slot_params: no run begun (call qtts_dev_begin first)\n");
+        return -1;
+    }
+    if (b < 0 || b >= dv->nb) {
+        fprintf(stderr, "qtts_dev_slot_params: slot %d out of range (%d slots)\n", b, dv->nb);
+        return -1;
+    }
+    if (!slot_params_ok("qtts_dev_slot_params", *p)) return -1;
+    if (dv->f_armed) {
+        fprintf(stderr, "qtts_dev_slot_params: refused: forced codes / taps are armed for this run\n");
+        return -1;
+    }
+    hipSetDevice(dv->device);
+    if (!dv->sp_armed) {   // the first call of the run: every row from begin's parameters
+        qtts_slot_params_t q;
+        q.temperature = dv->par.temperature; q.top_p = dv->par.top_p; q.repetition_penalty = dv->par.repetition_penalty;
+        q.top_k = dv->par.top_k; q.st_temperature = dv->par.st_temperature; q.st_top_p = dv->par.st_top_p;
+        q.st_top_k = dv->par.st_top_k; q.seed = dv->par.seed;
+        const SampSlotRow r0 = slot_row_of(q);
+        std::vector<SampSlotRow> h((size_t)dv->nb, r0);
+        SampSlotRow *t = nullptr;
+        CK(hipMalloc((void **)&t, h.size() * sizeof(SampSlotRow)));
+        if (hipMemcpy(t, h.data(), h.size() * sizeof(SampSlotRow), hipMemcpyHostToDevice) != hipSuccess) {
+            hipFree(t);
+            return -1;
+        }
+        // (the frames in flight, if any, hold the plain samplers: the new graphs are captured after them)
+        dv->sp_tab = t;
+        dv->sp_host.swap(h);
+        dv->sbytes += dv->sp_host.size() * sizeof(SampSlotRow);
+        dv->sp_armed = true;
+        dv->sp_general = !slot_row_fast(dv, r0);
+        dv->graph_key = -1;
+    }
+    const SampSlotRow r = slot_row_of(*p);
+    if (!slot_row_fast(dv, r)) dv->sp_general = true;   // (ensure_graphs: the frames switch to the general kernel)
+    const bool fresh = dv->f_phase == 1;   // before frame 0: the slot's RNG states start from this seed
+    CKI(qtts_slot_row_set(dv->sp_tab, b, r, fresh ? dv->rng : nullptr, fresh ? dv->st_rng : nullptr, dv->st));
+    dv->sp_host[b] = r;
+    return 0;
+}
+
+extern "C" long long qtts_hip_sample_slot_launches(void) { return qtts_sample_slot_launches(); }
+
 // ----------------------------------------------------------------- host-pointer stage wrappers
 static int ensure_slot0(qtts_dev *dv) {
     if (dv->nb >= 1) return 0;
@@ -2639,6 +2756,39 @@ extern "C" int qtts_hip_sample_top_k(int *out, const float *logits, int vocab, i
     s.logits = logits; s.ld = vocab; s.n = vocab; s.nb = batch; s.top_k = top_k; s.top_p = top_p; s.temp = temp;
     s.mode = 0; s.st_rng = rng_bits; s.out_tok = out;
     return qtts_sample(s, (hipStream_t)stream);
+}
+
+// qtts_hip_sample_top_k with one parameter set per row: the table is built
+// here, the launch family is the one a run with these rows would capture
+extern "C" int qtts_hip_sample_top_k_rows(int *out, const float *logits, int vocab, const int *top_k,
+                                          const float *top_p, const float *temp, uint32_t *rng_bits, int batch,
+                                          void *stream) {
+    if (!out || !logits || !top_k || !top_p || !temp || !rng_bits || batch < 1 || batch > 65535) return -1;
+    std::vector<SampSlotRow> h((size_t)batch);
+    bool all_fast = true;
+    for (int b = 0; b < batch; ++b) {
+        if (!std::isfinite(top_p[b]) || !std::isfinite(temp[b]) || top_p[b] <= 0.0f) {
+            fprintf(stderr, "qtts_hip_sample_top_k_rows: row %d: top_p %g, temperature %g\n", b, top_p[b], temp[b]);
+            return -1;
+        }
+        SampSlotRow &r = h[b];
+        r.temp = r.st_temp = temp[b]; r.top_p = r.st_top_p = top_p[b]; r.top_k = r.st_top_k = top_k[b];
+        r.rep = 1.0f; r.seed_bits = 0;
+        all_fast = all_fast && qtts_sample_row_fast(r, 0, vocab);
+    }
+    hipStream_t st = (hipStream_t)stream;
+    SampSlotRow *t = nullptr;
+    CK(hipMalloc((void **)&t, h.size() * sizeof(SampSlotRow)));
+    int rc = hipMemcpyAsync(t, h.data(), h.size() * sizeof(SampSlotRow), hipMemcpyHostToDevice, st) == hipSuccess ? 0 : -1;
+    if (!rc) {
+        SampArgs s;
+        s.logits = logits; s.ld = vocab; s.n = vocab; s.nb = batch;
+        s.mode = 0; s.st_rng = rng_bits; s.out_tok = out;
+        rc = qtts_sample_slots(s, t, all_fast, st);
+    }
+    if (hipStreamSynchronize(st) != hipSuccess) rc = -1;   // (h and t live until the launch finished)
+    hipFree(t);
+    return rc;
 }
 
 // every rows-long device index vector inside [0, lim) (the kernels index by

@@ -168,6 +168,68 @@ __device__ __forceinline__ int sample_any(SampSmem &sm, int n, int k, float top_
     return sample_full(sm, n, k, top_p, temp, rng);
 }
 
+// The reference's top-k list draw (K.c:419-477: top_p >= 1, 0 < k < n) for a k
+// the register fast path does not take (k > KFAST; the reference's list has no
+// cap): v = logit / T, the eligible ids (v > -FLT_MAX) sorted by (value desc,
+// index asc) -- the order its strict '>' insertion leaves -- p_j = expf(v_j -
+// v_0) for the first k (an unfilled slot adds 0), summed sequentially in that
+// order, r = u * sum, the first j whose running sum reaches r.  256 threads,
+// sm.lg holds the logits and is left as it is (the fixed-mode EOS redraw).
+// Used by the per-slot sampler (sample_row_p); `temp` is already > 0.
+__device__ __forceinline__ int sample_list(SampSmem &sm, int n, int k, float temp, uint32_t &rng) {
+#pragma clang fp contract(off)
+    const int tid = threadIdx.x;
+    for (int i = tid; i < n; i += 256) sm.v[i] = div_rn(sm.lg[i], temp);
+    __syncthreads();
+    int N2 = 1;
+    while (N2 < n) N2 <<= 1;
+    for (int i = tid; i < N2; i += 256) {
+        unsigned long long key = 0ull;   // (ineligible and padding: below every real key)
+        if (i < n && sm.v[i] > -FLT_MAX) key = ((unsigned long long)okey(sm.v[i]) << 32) | (0xFFFFFFFFu - (uint32_t)i);
+        sm.srt[i] = key;
+    }
+    __syncthreads();
+    bitonic_desc(sm, N2);
+    const unsigned long long k0 = sm.srt[0];
+    const float v0 = k0 ? sm.v[0xFFFFFFFFu - (uint32_t)(k0 & 0xFFFFFFFFull)] : 0.0f;
+    constexpr int PT = NMAX / 256;   // ranks per thread: j = tid + 256 t (k < n <= NMAX)
+    float p[PT];
+#pragma unroll
+    for (int t = 0; t < PT; ++t) {
+        const int j = tid + 256 * t;
+        p[t] = 0.0f;
+        if (j < k) {
+            const unsigned long long key = sm.srt[j];
+            if (key) p[t] = expf_glibc(sm.v[0xFFFFFFFFu - (uint32_t)(key & 0xFFFFFFFFull)] - v0);
+        }
+    }
+    __syncthreads();   // every v_j is read: sm.v takes the p_j in rank order
+#pragma unroll
+    for (int t = 0; t < PT; ++t) {
+        const int j = tid + 256 * t;
+        if (j < k) sm.v[j] = p[t];
+    }
+    __syncthreads();
+    if (tid == 0) {
+        float sum = 0.0f;
+        for (int j = 0; j < k; ++j) sum += sm.v[j];
+        int out = 0;
+        if (sum > 0.0f) {
+            const float r = rand_uniform(rng) * sum;
+            float c = 0.0f;
+            for (int j = 0; j < k; ++j) {
+                c += sm.v[j];
+                if (c >= r) { out = (int)(0xFFFFFFFFu - (uint32_t)(sm.srt[j] & 0xFFFFFFFFull)); break; }
+            }
+        } else if (k0) {
+            out = (int)(0xFFFFFFFFu - (uint32_t)(k0 & 0xFFFFFFFFull));
+        }
+        sm.misc[8] = out;
+    }
+    __syncthreads();
+    return sm.misc[8];
+}
+
 // ---------------------------------------------------------------------------
 // Fast path on registers (top_p >= 1, 0 < k < n): thread t owns the
 // contiguous ids [t*E, t*E + E), E = ceil(n / 256) <= EMAX.
@@ -279,7 +341,9 @@ __device__ __forceinline__ void block_scan2(FastSmem &fs, int x, int y, int &ex,
 // and the first j whose running sum reaches r (K.c:451-477), every lane
 // walking the same broadcast values.  Lane 0 owns the RNG.  Returns the id
 // (all lanes).  (v_readlane per step measured 2-3x slower than the LDS reads.)
-template <class FS>
+// (XS, here and in the draws below: expf_glibc_wave_all for expf_glibc_wave --
+// the per-slot sampler's instantiations, sample_row_p)
+template <class FS, bool XS = false>
 __device__ __forceinline__ int wave_sort_draw(FS &fs, int ke, uint32_t &rng, uint64_t etab) {
 #pragma clang fp contract(off)
     const int lane = threadIdx.x & 63;
@@ -310,7 +374,10 @@ __device__ __forceinline__ int wave_sort_draw(FS &fs, int ke, uint32_t &rng, uin
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     const float v0 = pv[0];
     {   // every lane active for the table's cross-lane reads
-        const float ee = expf_glibc_wave(lane < ke ? pv[lane] - v0 : 0.f, etab);
+        const float xe = lane < ke ? pv[lane] - v0 : 0.f;
+        float ee;
+        if constexpr (XS) ee = expf_glibc_wave_all(xe, etab);
+        else ee = expf_glibc_wave(xe, etab);
         if (lane < ke) e = ee;
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -377,7 +444,7 @@ __device__ __forceinline__ float key_val(uint32_t k) {
 // thread when more than KC keys share the bins through B (ties, a very dense
 // boundary bin): the caller then runs the radix select after a barrier.
 // (STOP < 4: the micro-benchmark's phase cut, tools/mb_sample.hip)
-template <int EM, int STOP = 4>
+template <int EM, int STOP = 4, bool XS = false>
 __device__ __forceinline__ int sample_dist(FastSmem &fs, const float (&v)[EM], const uint32_t (&kk)[EM], int E, int k,
                                            uint32_t &rng, uint64_t etab) {
 #pragma clang fp contract(off)
@@ -456,7 +523,10 @@ __device__ __forceinline__ int sample_dist(FastSmem &fs, const float (&v)[EM], c
     const unsigned long long key = lane < nc ? fs.cand[ww][off] : 0ull;   // 0: below every real key
     fs.rk[lane] = key;
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // one wave: LDS is in order once the writes landed
-    const float e = expf_glibc_wave(lane < nc ? key_val((uint32_t)(key >> 32)) - M : 0.f, etab);
+    const float xe = lane < nc ? key_val((uint32_t)(key >> 32)) - M : 0.f;
+    float e;
+    if constexpr (XS) e = expf_glibc_wave_all(xe, etab);
+    else e = expf_glibc_wave(xe, etab);
     int rank = 0;
     for (int t0 = 0; t0 < nc; t0 += 8) {
         unsigned long long kt[8];
@@ -489,7 +559,7 @@ __device__ __forceinline__ int sample_dist(FastSmem &fs, const float (&v)[EM], c
 
 // Returns the sampled id: in wave 0 (the callers that need it in every wave
 // broadcast it).  v[]: logits / temperature.
-template <int EM>
+template <int EM, bool XS = false>
 __device__ __forceinline__ int sample_fast_regs(FastSmem &fs, const float (&v)[EM], int E, int n, int k, uint32_t &rng,
                                                 uint64_t etab) {
 #pragma clang fp contract(off)
@@ -498,7 +568,7 @@ __device__ __forceinline__ int sample_fast_regs(FastSmem &fs, const float (&v)[E
 #pragma unroll
     for (int j = 0; j < EM; ++j) kk[j] = (j < E && tid * E + j < n && v[j] > -FLT_MAX) ? okey(v[j]) : 0u;
     if (k <= KC) {
-        const int t = sample_dist<EM>(fs, v, kk, E, k, rng, etab);
+        const int t = sample_dist<EM, 4, XS>(fs, v, kk, E, k, rng, etab);
         if (t != -1) return t;
         __syncthreads();   // the radix select below rewrites the histograms the other waves read
     }
@@ -533,7 +603,7 @@ __device__ __forceinline__ int sample_fast_regs(FastSmem &fs, const float (&v)[E
     __syncthreads();
     if (ke <= 64) {   // the common case (top-k 50): one wave sorts and draws
         if (tid < 64) {
-            const int t = wave_sort_draw(fs, ke, rng, etab);
+            const int t = wave_sort_draw<FastSmem, XS>(fs, ke, rng, etab);
             if (tid == 0) fs.misc[0] = t;
         }
         __syncthreads();
@@ -686,7 +756,7 @@ __device__ __forceinline__ void radix_select_nt(FastSmemNT<NT> &fs, const uint32
 // Top-k draw for k <= KC (see sample_dist): returns the id in wave 0 (0 in
 // the other waves), or -1 in every thread when more than KC keys share the
 // bins through the k-th key's.  Four barriers.
-template <int NT, int EM, int STOP = 9>
+template <int NT, int EM, int STOP = 9, bool XS = false>
 __device__ __forceinline__ int sample_dist_nt(FastSmemNT<NT> &fs, const float (&v)[EM], const uint32_t (&kk)[EM],
                                               const int (&id)[EM], int k, uint32_t &rng, uint64_t etab) {
 #pragma clang fp contract(off)
@@ -791,7 +861,11 @@ __device__ __forceinline__ int sample_dist_nt(FastSmemNT<NT> &fs, const float (&
         if (lane < nc && r > 0) atomicAdd(&fs.crank[lane], r);
     }
     float e = 0.f;
-    if (w == 0) e = expf_glibc_wave(lane < nc ? key_val((uint32_t)(key >> 32)) - M : 0.f, etab);
+    if (w == 0) {
+        const float xe = lane < nc ? key_val((uint32_t)(key >> 32)) - M : 0.f;
+        if constexpr (XS) e = expf_glibc_wave_all(xe, etab);
+        else e = expf_glibc_wave(xe, etab);
+    }
     __syncthreads();                                                   // 4
     if (w != 0) return 0;
     if constexpr (STOP == 4) return fs.crank[lane];
@@ -832,7 +906,7 @@ __device__ __forceinline__ int sample_dist_nt(FastSmemNT<NT> &fs, const float (&
 }
 
 // sample_fast_regs on NT threads: thread t owns ids id[j] = t*E + j (j < E).
-template <int NT, int EM>
+template <int NT, int EM, bool XS = false>
 __device__ __forceinline__ int sample_fast_nt(FastSmemNT<NT> &fs, const float (&v)[EM], int E, int n, int k,
                                               uint32_t &rng, uint64_t etab) {
 #pragma clang fp contract(off)
@@ -845,7 +919,7 @@ __device__ __forceinline__ int sample_fast_nt(FastSmemNT<NT> &fs, const float (&
         kk[j] = (j < E && id[j] < n && v[j] > -FLT_MAX) ? okey(v[j]) : 0u;
     }
     if (k <= KC) {
-        const int t = sample_dist_nt<NT, EM>(fs, v, kk, id, k, rng, etab);
+        const int t = sample_dist_nt<NT, EM, 9, XS>(fs, v, kk, id, k, rng, etab);
         if (t != -1) return t;
         __syncthreads();   // (every thread returned -1 at the same point; hist 0 / 1 were zeroed before barrier 1)
     } else {
@@ -882,7 +956,7 @@ __device__ __forceinline__ int sample_fast_nt(FastSmemNT<NT> &fs, const float (&
     __syncthreads();
     if (ke <= 64) {
         if (tid < 64) {
-            const int t = wave_sort_draw(fs, ke, rng, etab);
+            const int t = wave_sort_draw<FastSmemNT<NT>, XS>(fs, ke, rng, etab);
             if (tid == 0) fs.misc[0] = t;
         }
         __syncthreads();
@@ -1092,6 +1166,153 @@ __device__ __forceinline__ void sample_row(const SampArgs &a, int b, unsigned ch
             // for a stopped row (its samplers return early): EOS (>= Vs) would
             // index past the last pass's table, so a stop leaves id 0
             if (a.out_tok) a.out_tok[b] = ((a.fixed == 0 && tok == a.eos) || fstop) ? 0 : tok;
+        } else {
+            a.st_rng[b] = rng;
+            if (a.codes) a.codes[(size_t)b * a.codes_bstride + (size_t)a.cur_row[b] * a.G + a.g] = tok;
+            if (a.out_tok) a.out_tok[b] = tok;
+        }
+    }
+}
+
+// the same for one row of the per-slot table (SampSlotRow)
+__host__ __device__ inline bool fast_path_row(float top_p, int top_k, int n) {
+    return top_p >= 1.0f && top_k > 0 && top_k < n && top_k <= KFAST && n <= NMAX;
+}
+
+// sample_row with per-slot parameters (qtts_kernels.h SampSlotRow; used by
+// k_sample_p.hip): top_k, top_p, the temperature, the repetition penalty and
+// the seed the talker resets st_rng to come from row b of `tab` instead of
+// `a`; everything else is sample_row's, statement for statement (a function of
+// its own so that the plain and forced kernels compile to what they were).
+// The load discipline holds: the row is this kernel's FIRST load, two dwordx4
+// vector loads from an unconditional address (through an opaque zero offset,
+// as the flags: a scalar fetch would be waited for before the logit loads
+// issue), and no later load depends on it -- the counts are read whenever the
+// mode has them and dropped afterwards for a row with penalty 1.  Once all
+// loads landed the row's words become uniform (readfirstlane), so fast or
+// full is a workgroup-uniform branch.  With FAST_ONLY the caller guarantees
+// that every row is fast-path eligible in this mode.
+template <bool FAST_ONLY, int EM = EMAX, int NT = 256>
+__device__ __forceinline__ void sample_row_p(const SampArgs &a, const SampSlotRow *tab, int b, unsigned char *smraw,
+                                             const float *logits, const int *stopped_p, const uint32_t *rng_p,
+                                             const int *ngen_p, const int *counts_p) {
+#pragma clang fp contract(off)
+    static_assert(NT == 256 || FAST_ONLY, "the full path runs on 256 threads");
+    KSmem &U = *reinterpret_cast<KSmem *>(smraw);
+    int *misc = NT == 256 ? U.fast.misc : reinterpret_cast<FastSmemNT<NT> *>(smraw)->misc;
+    const int tid = threadIdx.x, n = a.n;
+    int zr;
+    asm volatile("v_mov_b32 %0, 0" : "=v"(zr));
+    const uint4 *tp = reinterpret_cast<const uint4 *>(tab + b);
+    const uint4 r0 = tp[zr], r1 = tp[zr + 1];
+    const int E = (n + NT - 1) / NT;
+    const float *lg = logits + (size_t)b * a.ld;
+    const int i0 = tid * E;
+    float x[EM];
+    int cnt[EM];
+    const bool pen = a.mode == 1 && counts_p;
+    const int *cbase = pen ? counts_p + (size_t)b * n : reinterpret_cast<const int *>(lg);
+#pragma unroll
+    for (int j = 0; j < EM; ++j) {
+        const int i = i0 + j < n ? i0 + j : n - 1;
+        x[j] = lg[i];
+        cnt[j] = cbase[i];
+    }
+    int z0;
+    asm volatile("v_mov_b32 %0, 0" : "=v"(z0));
+    const int *sp = stopped_p ? stopped_p + b : reinterpret_cast<const int *>(lg);
+    const int *np = a.mode == 1 ? ngen_p + b : reinterpret_cast<const int *>(lg);
+    const uint32_t *rp = rng_p + b;
+    int stopped = sp[z0];
+    int ng = np[z0];
+    uint32_t rng = rp[z0];
+    const uint64_t etab = kExp2fTab[tid & 31];
+    asm volatile("" :: "v"(stopped), "v"(ng), "v"(rng));
+    asm volatile("" :: "v"(r0.x), "v"(r0.y), "v"(r0.z), "v"(r0.w), "v"(r1.x), "v"(r1.y), "v"(r1.z), "v"(r1.w));
+    const bool tk = a.mode == 1;
+    const float temp_in = __uint_as_float(__builtin_amdgcn_readfirstlane(tk ? r0.x : r1.x));
+    const float top_p = __uint_as_float(__builtin_amdgcn_readfirstlane(tk ? r0.y : r1.y));
+    const int top_k = (int)__builtin_amdgcn_readfirstlane(tk ? r0.w : r1.z);
+    const float rep = __uint_as_float(__builtin_amdgcn_readfirstlane(r0.z));
+    const uint32_t seed_bits = __builtin_amdgcn_readfirstlane(r1.w);
+    const bool pen_on = pen && rep != 1.0f;
+    if (!stopped_p) stopped = 0;
+    if (a.mode != 1) ng = 0;
+#pragma unroll
+    for (int j = 0; j < EM; ++j) {
+        const bool ok = j < E && i0 + j < n;
+        if (!ok) x[j] = -INFINITY;
+        if (!(ok && pen_on)) cnt[j] = 0;
+    }
+    if (stopped) return;
+    if (a.mode == 1) {
+#pragma unroll
+        for (int j = 0; j < EM; ++j) {
+            const int i = i0 + j;
+            float v = x[j];
+            if (i >= a.suppress_lo && i != a.eos) v = -1e9f;
+            for (int c = 0; c < cnt[j]; ++c) v = v > 0 ? div_rn(v, rep) : v * rep;
+            x[j] = (j < E && i < n) ? v : -INFINITY;
+        }
+    }
+    float temp = temp_in;
+    if (temp <= 0.0f) temp = 1e-5f;
+    const bool fast = FAST_ONLY || fast_path_row(top_p, top_k, n);
+    int tok = 0;
+    if (fast) {
+        float v[EM];
+#pragma unroll
+        for (int j = 0; j < EM; ++j) v[j] = div_rn(x[j], temp);
+        auto draw = [&]() {   // (wave 0's id)
+            if constexpr (NT == 256) return sample_fast_regs<EM, true>(U.fast, v, E, n, top_k, rng, etab);
+            else return sample_fast_nt<NT, EM, true>(*reinterpret_cast<FastSmemNT<NT> *>(smraw), v, E, n, top_k, rng,
+                                                     etab);
+        };
+        tok = draw();
+        if (a.mode == 1 && a.fixed > 0 && ng < a.fixed) {   // Q.c:1315-1321: an EOS draw is redrawn
+            if (tid == 0) misc[3] = tok;
+            __syncthreads();
+            tok = misc[3];
+            if (tok == a.eos) {
+#pragma unroll
+                for (int j = 0; j < EM; ++j)
+                    if (i0 + j == a.eos) v[j] = div_rn(-1e9f, temp);
+                tok = draw();
+            }
+        }
+    } else if constexpr (!FAST_ONLY) {
+        SampSmem &sm = U.full;
+#pragma unroll
+        for (int j = 0; j < EM; ++j)
+            if (j < E && i0 + j < n) sm.lg[i0 + j] = x[j];
+        __syncthreads();
+        // (not fast: a list draw here has k > KFAST -- the reference's list path all the same)
+        const bool list = top_p >= 1.0f && top_k > 0 && top_k < n;
+        auto draw = [&]() {
+            return list ? sample_list(sm, n, top_k, temp, rng) : sample_any(sm, n, top_k, top_p, temp_in, rng);
+        };
+        tok = draw();
+        if (a.mode == 1 && a.fixed > 0 && tok == a.eos && ng < a.fixed) {
+            if (tid == 0) sm.lg[a.eos] = -1e9f;
+            __syncthreads();
+            tok = draw();
+        }
+    }
+    if (tid == 0) {
+        if (a.mode == 1) {
+            a.rng[b] = rng;
+            if (a.fixed == 0 && tok == a.eos) {
+                a.stopped[b] = 1;
+                if (a.host_stopped) a.host_stopped[b] = 1;
+                if (a.stop_step) a.stop_step[b] = ng;
+            } else {
+                a.cur_row[b] = ng;
+                a.codes[(size_t)b * a.codes_bstride + (size_t)ng * a.G + 0] = tok;
+                if (a.counts) a.counts[(size_t)b * n + tok] += 1;
+                a.n_gen[b] = ng + 1;
+                a.st_rng[b] = seed_bits;
+            }
+            if (a.out_tok) a.out_tok[b] = (a.fixed == 0 && tok == a.eos) ? 0 : tok;   // (see sample_row)
         } else {
             a.st_rng[b] = rng;
             if (a.codes) a.codes[(size_t)b * a.codes_bstride + (size_t)a.cur_row[b] * a.G + a.g] = tok;

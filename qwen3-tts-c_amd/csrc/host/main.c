@@ -14,7 +14,8 @@
  * prints "First packet: X ms"), --kv-cache fp32|bf16 (talker KV cache
  * elements, qwen_tts_set_kv_cache_dtype), --force-codes FILE / --dump-drawn
  * FILE (teacher-forced decode and its free-draw record, qwen_tts_force_codes /
- * qwen_tts_last_drawn).
+ * qwen_tts_last_drawn), --seed-step K (with --batch N: slot b samples with seed
+ * + b K, qwen_tts_set_utterance_sampling, and every slot's audio is written).
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -45,6 +46,8 @@ static void usage(const char *prog) {
             "  --subtalker-temperature F (0.9)   --subtalker-top-k N (50)   --subtalker-top-p F (1.0)\n"
             "  --benchmark-runs N (1)  --benchmark-warmup N (0)\n"
             "  --device N (HIP device, default 0)   --batch N (lock-step batch of N copies, default 1)\n"
+            "  --seed-step K (with --batch N: slot b samples with seed + b*K -- N takes of the prompt -- and\n"
+            "                      every slot is written: slot 0 to -o's path, slot b to <stem>_<b>.wav)\n"
             "  --stream N (streaming decode, audio chunks every N frames after the first)\n"
             "  --kv-cache fp32|bf16 (talker KV cache elements, default fp32; bf16 halves the cache,\n"
             "                      codes then no longer bit-exact against the reference)\n"
@@ -180,6 +183,7 @@ int main(int argc, char **argv) {
     const char *ref_codes_file = NULL, *ref_text = NULL, *xvec_file = NULL, *text = NULL, *ref_audio = NULL;
     int print_ids = 0, xvec_only = 0;
     const char *force_file = NULL, *drawn_file = NULL;
+    int seed_step = 0, seed_step_set = 0;
     float temp = -1, st_temp = -1, top_p = -1, st_top_p = -1, rep = -1;
     int top_k = -1, st_top_k = -1, max_tokens = -1, fixed = -1, seed = -1;
     for (int i = 1; i < argc; i++) {
@@ -209,6 +213,7 @@ int main(int argc, char **argv) {
         else if (ARG("--benchmark-warmup")) warmup = (int)strtol(argv[++i], NULL, 10);
         else if (ARG("--device")) device = (int)strtol(argv[++i], NULL, 10);
         else if (ARG("--batch")) batch = (int)strtol(argv[++i], NULL, 10);
+        else if (ARG("--seed-step")) { seed_step = (int)strtol(argv[++i], NULL, 10); seed_step_set = 1; }
         else if (ARG("--stream")) stream_chunk = (int)strtol(argv[++i], NULL, 10);
         else if (ARG("--kv-cache")) {
             const char *v = argv[++i];
@@ -384,6 +389,10 @@ int main(int argc, char **argv) {
     }
     float *audio = NULL;
     int n_samples = 0, rc = 0;
+    /* --seed-step with --batch N: the audio of slots 1 .. N-1 of the last run */
+    const int takes = seed_step_set && batch > 1 && !ref_wav && !clone;
+    float **take_audio = takes ? (float **)calloc(batch, sizeof(float *)) : NULL;
+    int *take_n = takes ? (int *)calloc(batch, sizeof(int)) : NULL;
     for (int run = 0; run < warmup + runs; run++) {
         const double t0 = now_ms();
         float *ra = NULL;
@@ -414,12 +423,31 @@ int main(int argc, char **argv) {
             float **au = (float **)calloc(batch, sizeof(float *));
             int *ns = (int *)calloc(batch, sizeof(int));
             for (int b = 0; b < batch; b++) { tx[b] = ids; sp[b] = spk; lg[b] = lang; }
-            if (qwen_tts_generate_batch(ctx, batch, tx, sp, lg, au, ns) == 0) {
+            int armed = 0;
+            if (takes) {   /* (one-shot: armed again for every run) */
+                qwen_tts_sampling_t *per = (qwen_tts_sampling_t *)calloc(batch, sizeof(qwen_tts_sampling_t));
+                armed = per != NULL;
+                for (int b = 0; b < batch && armed; b++) {
+                    armed = qwen_tts_sampling_defaults(ctx, &per[b]) == 0;
+                    per[b].sample_seed += b * seed_step;
+                }
+                armed = armed && qwen_tts_set_utterance_sampling(ctx, batch, per) == 0;
+                free(per);
+            }
+            if ((!takes || armed) && qwen_tts_generate_batch(ctx, batch, tx, sp, lg, au, ns) == 0) {
                 ra = au[0];
                 rn = ns[0];
                 for (int b = 0; b < batch; b++) total_samples += ns[b];
             }
-            for (int b = 1; b < batch; b++) free(au[b]);
+            for (int b = 1; b < batch; b++) {
+                if (takes && ra) {
+                    free(take_audio[b]);
+                    take_audio[b] = au[b];
+                    take_n[b] = ns[b];
+                } else {
+                    free(au[b]);
+                }
+            }
             free(tx); free(sp); free(lg); free(au); free(ns);
         }
         const double el = now_ms() - t0;
@@ -461,6 +489,23 @@ int main(int argc, char **argv) {
             }
         }
     }
+    for (int b = 1; takes && rc == 0 && b < batch; b++) {
+        /* slot b's take beside -o's file: <stem>_<b>.wav */
+        const size_t lo = strlen(out);
+        const int has_ext = lo >= 4 && !strcmp(out + lo - 4, ".wav");
+        char *path = (char *)malloc(lo + 32);
+        if (!path) { rc = 1; break; }
+        snprintf(path, lo + 32, "%.*s_%d.wav", (int)(has_ext ? lo - 4 : lo), out, b);
+        if (!take_audio[b] || take_n[b] <= 0 ||
+            qwen_tts_write_wav(path, take_audio[b], take_n[b], QWEN_TTS_SAMPLE_RATE) != 0) {
+            fprintf(stderr, "Error: failed to write %s\n", path);
+            rc = 1;
+        } else {
+            fprintf(stderr, "Wrote %s: %.2f seconds (%d samples at %d Hz)\n", path,
+                    (float)take_n[b] / QWEN_TTS_SAMPLE_RATE, take_n[b], QWEN_TTS_SAMPLE_RATE);
+        }
+        free(path);
+    }
     if (rc == 0 && drawn_file) {
         const int G = ctx->config.num_code_groups;
         const int cap = (ctx->fixed_codec_tokens > 0 ? ctx->fixed_codec_tokens : ctx->max_new_tokens) + 1;
@@ -485,6 +530,9 @@ int main(int argc, char **argv) {
         free(d);
     }
     free(audio);
+    for (int b = 1; takes && b < batch; b++) free(take_audio[b]);
+    free(take_audio);
+    free(take_n);
     qwen_tts_free(ctx);
     free(force_codes);
     free(file_ids);

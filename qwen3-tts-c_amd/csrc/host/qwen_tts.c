@@ -15,6 +15,7 @@
 
 #include <dirent.h>
 #include <fcntl.h>
+#include <math.h>
 #include <stdlib.h>
 #include <string.h>
 #include <strings.h>
@@ -704,9 +705,103 @@ static void force_free(force_arm_t *a) {
     free(a);
 }
 
+/* ------------------------------------------- per-utterance sampling (one-shot) */
+/* What qwen_tts_set_utterance_sampling armed for the NEXT generation call
+ * (ctx->sampling): detached on entry by run_batch / qwen_tts_generate_queue
+ * (sampling_take), dropped with the forcing by every entry that fails before
+ * them (force_disarm). */
+typedef struct {
+    int n;
+    qwen_tts_sampling_t *per;   /* [n] */
+} sampling_arm_t;
+
+static void sampling_free(sampling_arm_t *a) {
+    if (!a) return;
+    free(a->per);
+    free(a);
+}
+
+static sampling_arm_t *sampling_take(qwen_tts_ctx_t *ctx) {
+    sampling_arm_t *a = (sampling_arm_t *)ctx->sampling;
+    ctx->sampling = NULL;
+    return a;
+}
+
+static int sampling_ok(const qwen_tts_sampling_t *s, int i) {
+    const float f[5] = {s->temperature, s->top_p, s->repetition_penalty, s->subtalker_temperature, s->subtalker_top_p};
+    for (int k = 0; k < 5; k++)
+        if (!isfinite(f[k])) {
+            fprintf(stderr, "Error: utterance sampling %d: a non-finite value\n", i);
+            return 0;
+        }
+    if (s->top_p <= 0.0f || s->subtalker_top_p <= 0.0f || s->repetition_penalty <= 0.0f) {
+        fprintf(stderr, "Error: utterance sampling %d: top_p %g / %g and repetition_penalty %g must be > 0\n", i,
+                s->top_p, s->subtalker_top_p, s->repetition_penalty);
+        return 0;
+    }
+    return 1;
+}
+
+int qwen_tts_sampling_defaults(const qwen_tts_ctx_t *ctx, qwen_tts_sampling_t *s) {
+    if (!ctx || !ctx->hip || !s) return -1;
+    s->temperature = ctx->temperature; s->top_p = ctx->top_p; s->repetition_penalty = ctx->repetition_penalty;
+    s->top_k = ctx->top_k; s->subtalker_temperature = ctx->subtalker_temperature;
+    s->subtalker_top_p = ctx->subtalker_top_p; s->subtalker_top_k = ctx->subtalker_top_k;
+    s->sample_seed = ctx->sample_seed;
+    return 0;
+}
+
+int qwen_tts_set_utterance_sampling(qwen_tts_ctx_t *ctx, int n, const qwen_tts_sampling_t *per) {
+    if (!ctx || !ctx->hip) return -1;
+    if (n < 1 || !per) {
+        fprintf(stderr, "Error: utterance sampling: %d parameter sets\n", n);
+        return -1;
+    }
+    for (int i = 0; i < n; i++)
+        if (!sampling_ok(&per[i], i)) return -1;
+    sampling_arm_t *a = (sampling_arm_t *)calloc(1, sizeof(sampling_arm_t));
+    if (!a) return -1;
+    a->per = (qwen_tts_sampling_t *)malloc((size_t)n * sizeof(qwen_tts_sampling_t));
+    if (!a->per) { free(a); return -1; }
+    memcpy(a->per, per, (size_t)n * sizeof(qwen_tts_sampling_t));
+    a->n = n;
+    sampling_free((sampling_arm_t *)ctx->sampling);   /* armed again: the later call replaces */
+    ctx->sampling = a;
+    return 0;
+}
+
+/* utterance u's row on slot b of the device (after qtts_dev_begin) */
+static int sampling_apply(qtts_dev_t *dev, const sampling_arm_t *a, int u, int b) {
+    const qwen_tts_sampling_t *s = &a->per[u];
+    qtts_slot_params_t p;
+    p.temperature = s->temperature; p.top_p = s->top_p; p.repetition_penalty = s->repetition_penalty;
+    p.top_k = s->top_k; p.st_temperature = s->subtalker_temperature; p.st_top_p = s->subtalker_top_p;
+    p.st_top_k = s->subtalker_top_k; p.seed = s->sample_seed;
+    return qtts_dev_slot_params(dev, b, &p);
+}
+
+/* the entry checks of a generation call of `n` utterances: 0 to go on */
+static int sampling_refused(const char *who, const sampling_arm_t *sa, const void *force, int n) {
+    if (!sa) return 0;
+    if (force) {
+        fprintf(stderr, "Error: %s: per-utterance sampling and forced codes / taps are both armed "
+                        "(not supported; both disarmed)\n", who);
+        return 1;
+    }
+    if (sa->n != n) {
+        fprintf(stderr, "Error: %s: %d utterance sampling sets armed for a call of %d utterances (disarmed)\n", who,
+                sa->n, n);
+        return 1;
+    }
+    return 0;
+}
+
+/* drops whatever is armed for the next call: forcing / taps and per-utterance
+ * sampling (every entry that fails before its run consumes both) */
 static void force_disarm(qwen_tts_ctx_t *ctx) {
     force_free((force_arm_t *)ctx->force);
     ctx->force = NULL;
+    sampling_free(sampling_take(ctx));
 }
 
 static force_arm_t *force_pending(qwen_tts_ctx_t *ctx) {
@@ -824,6 +919,12 @@ static int run_batch(qwen_tts_ctx_t *ctx, int nb, const char *const *texts, cons
     int rc = -1;
     force_arm_t *arm = (force_arm_t *)ctx->force;   /* one-shot: this call consumes it, however it ends */
     ctx->force = NULL;
+    sampling_arm_t *sarm = sampling_take(ctx);      /* and the per-utterance sampling */
+    if (sampling_refused("generate", sarm, arm, nb)) {
+        force_free(arm);
+        sampling_free(sarm);
+        return -1;
+    }
     prompt_t *pr = (prompt_t *)calloc(nb, sizeof(prompt_t));
     int max_p = 0;
     for (int b = 0; b < nb; b++) {
@@ -854,6 +955,9 @@ static int run_batch(qwen_tts_ctx_t *ctx, int nb, const char *const *texts, cons
     params_of(ctx, &gp);
     if (qtts_dev_begin(dev, nb, max_tokens, max_p, &gp) != 0) goto out;
     if (force_apply(dev, arm, nb, max_tokens) != 0) goto out;
+    if (sarm)
+        for (int b = 0; b < nb; b++)
+            if (sampling_apply(dev, sarm, b, b) != 0) goto out;
     for (int b = 0; b < nb; b++)
         if ((vcs && qtts_dev_prompt_ref(dev, vcs[b].ref_codes, vcs[b].ref_codes ? vcs[b].n_ref : 0, vcs[b].spk) != 0) ||
             qtts_dev_prompt(dev, b, pr[b].text, pr[b].n_text, pr[b].plan, pr[b].nplan, pr[b].p_len,
@@ -1062,6 +1166,7 @@ static int run_batch(qwen_tts_ctx_t *ctx, int nb, const char *const *texts, cons
     free(stopped); free(ngen); free(sstep);
 out:
     force_free(arm);
+    sampling_free(sarm);
     for (int b = 0; b < nb; b++) { free(pr[b].text); free(pr[b].plan); }
     free(pr);
     return rc;
@@ -1142,8 +1247,16 @@ int qwen_tts_generate_queue(qwen_tts_ctx_t *ctx, int nq, const char *const *text
         force_disarm(ctx);
         return -1;
     }
-    if (!ctx || !ctx->hip || nq < 1 || nb < 1 || !texts || !out_audio || !out_samples) return -1;
+    if (!ctx || !ctx->hip || nq < 1 || nb < 1 || !texts || !out_audio || !out_samples) {
+        if (ctx) force_disarm(ctx);
+        return -1;
+    }
     if (batch_refused(ctx, "qwen_tts_generate_queue", nb)) return -1;
+    sampling_arm_t *sarm = sampling_take(ctx);   /* one-shot: this call consumes it, however it ends */
+    if (sampling_refused("qwen_tts_generate_queue", sarm, NULL, nq)) {
+        sampling_free(sarm);
+        return -1;
+    }
     qtts_dev_t *dev = (qtts_dev_t *)ctx->hip;
     const qwen_tts_config_t *c = &ctx->config;
     const int G = c->num_code_groups;
@@ -1204,7 +1317,10 @@ int qwen_tts_generate_queue(qwen_tts_ctx_t *ctx, int nq, const char *const *text
     params_of(ctx, &gp);
     if (qtts_dev_begin(dev, ns, max_tokens, max_p, &gp) != 0 || qtts_dev_reserve(dev, max_tr) != 0) goto out;
     /* (a plan row's 4th int is the destination slot: set when the slot is known) */
+    /* (the admitted utterance's sampling row goes in with its prompt: before
+     * the initial prefill and before every qtts_dev_refill) */
 #define PROMPT(b, u) (queue_plan_slot(&pr[u], (b)), \
+                      (sarm && sampling_apply(dev, sarm, (u), (b)) != 0) ? -1 : \
                       qtts_dev_prompt(dev, (b), pr[u].text, pr[u].n_text, pr[u].plan, pr[u].nplan, pr[u].p_len, \
                                       pr[u].n_trailing, pr[u].pad_row))
     for (int b = 0; b < ns; b++)
@@ -1326,6 +1442,7 @@ out:
     if (pr)
         for (int i = 0; i < nq; i++) { free(pr[i].text); free(pr[i].plan); }
     free(pr); free(taken); free(cur); free(first); free(retired); free(hst); free(cbuf);
+    sampling_free(sarm);
     return rc;
 }
 

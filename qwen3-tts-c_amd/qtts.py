@@ -63,8 +63,20 @@ class Ctx(C.Structure):  # qwen_tts_ctx_t (include/qwen_tts.h)
         ("queue_n", C.c_int), ("queue_codes", C.POINTER(_ip)), ("queue_frames", _ip), ("queue_stop_reason", _ip),
         ("queue_slot", _ip), ("queue_slots", C.c_int), ("queue_frames_launched", C.c_int),
         ("queue_refills", C.c_int), ("queue_slot_frames_used", C.c_longlong), ("queue_rows_launched", C.c_longlong),
-        ("force", C.c_void_p),
+        ("sampling", C.c_void_p), ("force", C.c_void_p),
     ]
+
+
+class Sampling(C.Structure):  # qwen_tts_sampling_t (include/qwen_tts.h)
+    _fields_ = [("temperature", C.c_float), ("top_p", C.c_float), ("repetition_penalty", C.c_float),
+                ("top_k", C.c_int), ("subtalker_temperature", C.c_float), ("subtalker_top_p", C.c_float),
+                ("subtalker_top_k", C.c_int), ("sample_seed", C.c_int)]
+
+
+class SlotParams(C.Structure):  # qtts_slot_params_t (include/qtts_hip.h)
+    _fields_ = [("temperature", C.c_float), ("top_p", C.c_float), ("repetition_penalty", C.c_float),
+                ("top_k", C.c_int), ("st_temperature", C.c_float), ("st_top_p", C.c_float), ("st_top_k", C.c_int),
+                ("seed", C.c_int)]
 
 
 # Every symbol include/qwen_tts.h and include/qtts_hip.h declare (checked by tests/test_host.py)
@@ -98,6 +110,8 @@ EXPORTS = [
     "qtts_dev_force", "qtts_dev_tap", "qtts_dev_get_drawn", "qtts_dev_get_tap",
     "qtts_hip_xgemm_plan", "qtts_hip_xgemm_case", "qtts_hip_xgemm_func",
     "qtts_hip_batch_matvec_case", "qtts_hip_gemv_wide_launches", "qtts_hip_batch_matvec_plan",
+    "qwen_tts_sampling_defaults", "qwen_tts_set_utterance_sampling", "qtts_dev_slot_params",
+    "qtts_hip_sample_slot_launches", "qtts_hip_sample_top_k_rows",
 ]
 
 MAX_BATCH = 64   # QWEN_TTS_MAX_BATCH / QTTS_HIP_MAX_BATCH: lock-step slots per context
@@ -357,6 +371,17 @@ def lib():
         L.qtts_hip_batch_matvec_case.argtypes = [C.POINTER(BGemvDesc), vp]
         L.qtts_hip_gemv_wide_launches.restype = C.c_longlong
         L.qtts_hip_gemv_wide_launches.argtypes = []
+    if hasattr(L, "qtts_dev_slot_params"):
+        L.qwen_tts_sampling_defaults.restype = C.c_int
+        L.qwen_tts_sampling_defaults.argtypes = [C.POINTER(Ctx), C.POINTER(Sampling)]
+        L.qwen_tts_set_utterance_sampling.restype = C.c_int
+        L.qwen_tts_set_utterance_sampling.argtypes = [C.POINTER(Ctx), C.c_int, C.POINTER(Sampling)]
+        L.qtts_dev_slot_params.restype = C.c_int
+        L.qtts_dev_slot_params.argtypes = [C.c_void_p, C.c_int, C.POINTER(SlotParams)]
+        L.qtts_hip_sample_slot_launches.restype = C.c_longlong
+        L.qtts_hip_sample_slot_launches.argtypes = []
+        L.qtts_hip_sample_top_k_rows.restype = C.c_int
+        L.qtts_hip_sample_top_k_rows.argtypes = [vp, vp, C.c_int, _ip, _fp, _fp, vp, C.c_int, vp]
     if hasattr(L, "qtts_hip_batch_matvec_plan"):
         L.qtts_hip_batch_matvec_plan.restype = C.c_int
         L.qtts_hip_batch_matvec_plan.argtypes = [C.POINTER(BGemvDesc), C.POINTER(BGemvPlan)]
@@ -424,6 +449,29 @@ class QwenTTS:
     def state_bytes(self):
         """device bytes of the generation state (qtts_dev_bytes(dev, 1))"""
         return int(lib().qtts_dev_bytes(C.c_void_p(self.c.hip), 1))
+
+    # per-utterance sampling parameters and seeds (include/qwen_tts.h); one-shot like forcing
+    _SAMPLING_KEYS = {"temperature": "temperature", "top_k": "top_k", "top_p": "top_p", "rep": "repetition_penalty",
+                      "st_temperature": "subtalker_temperature", "st_top_k": "subtalker_top_k",
+                      "st_top_p": "subtalker_top_p", "seed": "sample_seed"}
+
+    def set_utterance_sampling(self, per):
+        """per[i]: a dict for utterance i of the next generate* call (slot i of
+        a batch, utterance i in input order of generate_queue) with the keys of
+        set_params -- temperature, top_k, top_p, rep, st_temperature, st_top_k,
+        st_top_p, seed; missing keys take the ctx's current values.
+        ValueError when refused (no sets, a non-finite value, top_p <= 0,
+        rep <= 0, an unknown key)."""
+        arr = (Sampling * max(len(per), 1))()
+        for i, d in enumerate(per):
+            if lib().qwen_tts_sampling_defaults(self.ctx, C.byref(arr[i])) != 0:
+                raise ValueError("set_utterance_sampling: no device model")
+            for k, v in d.items():
+                if k not in self._SAMPLING_KEYS:
+                    raise ValueError(f"set_utterance_sampling: unknown key {k!r}")
+                setattr(arr[i], self._SAMPLING_KEYS[k], v)
+        if lib().qwen_tts_set_utterance_sampling(self.ctx, len(per), arr) != 0:
+            raise ValueError("set_utterance_sampling refused (see stderr)")
 
     # teacher forcing, the free-draw record and logit taps (include/qwen_tts.h).
     # Arming is one-shot: the next generate* call consumes it.
@@ -990,6 +1038,24 @@ class Kernels:
         _ok(rc, "batch_matvec_plan")
         return dict(kernel=BGEMV_KERNELS[p.kernel], tmpl=list(p.tmpl[:p.n_tmpl]), grid=[p.grid_x, p.grid_y],
                     block=p.block, lds=int(p.lds_bytes), tpw=p.tpw, cch=p.cch)
+
+    @staticmethod
+    def sample_top_k_rows(out_i32, logits, vocab, top_k, top_p, temperature, rng_u32, batch=1):
+        """sample_top_k with one parameter set per row: top_k / top_p /
+        temperature are host sequences of `batch` entries (the per-slot
+        sampler, qtts_hip_sample_top_k_rows)."""
+        k = np.ascontiguousarray(top_k, np.int32)
+        p = np.ascontiguousarray(top_p, np.float32)
+        t = np.ascontiguousarray(temperature, np.float32)
+        assert k.shape == p.shape == t.shape == (batch,)
+        _ok(lib().qtts_hip_sample_top_k_rows(_ptr(out_i32), _ptr(logits), vocab, k.ctypes.data_as(_ip),
+                                             p.ctypes.data_as(_fp), t.ctypes.data_as(_fp), _ptr(rng_u32), batch,
+                                             _stream()), "sample_top_k_rows")
+
+    @staticmethod
+    def sample_slot_launches():
+        """per-slot sampler launches enqueued or captured since the library loaded (qtts_hip_sample_slot_launches)"""
+        return int(lib().qtts_hip_sample_slot_launches())
 
     @staticmethod
     def gemv_wide_launches():
