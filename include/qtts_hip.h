@@ -288,6 +288,30 @@ int qtts_dev_codec_stream_prime(qtts_dev_t *dev, const int *codes, int T);
 int qtts_dev_codec_stream_push_slot(qtts_dev_t *dev, int b, int frame0, int T, float *host_out);
 int qtts_dev_codec_stream_push_host(qtts_dev_t *dev, const int *codes, int T, float *host_out);
 
+/* n independent exact streams beside the single one (which these calls leave
+ * alone), decoded together: a push runs the codec ONCE over the stacked
+ * streams, so its kernel launches do not grow with n and every codec weight is
+ * read once.  begin (n_streams 1..QWEN_TTS_MAX_BATCH) resets
+ * every stream to position 0; on an active state of the same size it only
+ * clears the carried state.  chunk_frames as qtts_dev_codec_stream_begin_ex
+ * (internal passes of 16 frames by default, fewer where n_streams planes of
+ * scratch would pass 2 GiB).  A push decodes T more frames of the n distinct
+ * streams streams[0..n), which must all be at the same position, into T * 1920
+ * host samples each (host_out[i] for streams[i]); the codes are slot slots[i]'s
+ * generated frames [frame0, frame0 + T) on the device, or host codes
+ * [n][T][16].  Returns the samples per stream, or -1 with a message, nothing
+ * launched and the state untouched, for: n outside 1..n_streams, a stream
+ * index out of range, a stream listed twice, streams at different positions,
+ * T < 1, a push past max_frames, a push without begin (a re-allocation of the
+ * context's state, e.g. another batch size, ends the streams: begin again).
+ * pos: frames decoded so far of a stream, -1 for a bad index or no begin. */
+int qtts_dev_codec_mstream_begin(qtts_dev_t *dev, int n_streams, int max_frames, int chunk_frames);
+int qtts_dev_codec_mstream_push_slots(qtts_dev_t *dev, int n, const int *streams, const int *slots, int frame0, int T,
+                                      float *const *host_out);
+int qtts_dev_codec_mstream_push_host(qtts_dev_t *dev, int n, const int *streams, const int *codes, int T,
+                                     float *const *host_out);
+int qtts_dev_codec_mstream_pos(qtts_dev_t *dev, int stream);
+
 /* The same exact streaming decode overlapped with the decode loop: it runs on
  * a second (low-priority) HIP stream; push orders itself after the frames
  * already enqueued on the context stream (an event), decodes slot b's frames
@@ -556,6 +580,16 @@ int qtts_hip_xgemm_plan(const qtts_xgemm_desc_t *d, size_t part_elems, int force
  * entry, not a timing one. */
 int qtts_hip_xgemm_case(const qtts_xgemm_desc_t *d, size_t part_elems, int force_path, int *path_out,
                         int *splits_out, void *stream);
+/* The same over the conv forms' stream axis (the multi-stream codec): nseg
+ * independent column segments of d->N columns each in one launch; segment s
+ * reads its input at B + s*seg_ldb and writes C + s*seg_ldc (floats; an
+ * in-place res moves with C).  A tile never holds two segments and taps left
+ * of a segment read that segment's own margin.  The segments count as tiles
+ * for the plan, so path_out / splits_out may differ from the single-segment
+ * plan; nseg 1 is qtts_hip_xgemm_case.  Linear forms (bmode 0) take nseg 1
+ * only.  Returns as qtts_hip_xgemm_case (1: force_path does not cover). */
+int qtts_hip_xgemm_seg_case(const qtts_xgemm_desc_t *d, int nseg, int seg_ldb, int seg_ldc, size_t part_elems,
+                            int force_path, int *path_out, int *splits_out, void *stream);
 /* snake(x) = x + inv_beta[c] * sin^2(x * alpha[c]) with the codec GEMMs' own
  * sin^2 (sin2 in k_codec.hip; qtts_hip_snake_beta runs sinf), and the fp32
  * expf / tanhf the GELU and SiLU epilogues call: fn 0 snake (needs alpha /

@@ -440,6 +440,37 @@ float *qwen_tts_generate_voice_clone_stream(qwen_tts_ctx_t *ctx, const char *tex
 int qwen_tts_codec_stream_begin(qwen_tts_ctx_t *ctx, int max_frames);
 int qwen_tts_codec_stream_push(qwen_tts_ctx_t *ctx, const int *codes, int time_steps, float *out);
 
+/* Streaming for every utterance of a lock-step batch.  Semantics are
+ * qwen_tts_generate_batch's (the same prompts, decode loop and codes bit for
+ * bit, the same nb limit and refusals, forced codes / taps and per-utterance
+ * sampling consumed the same way); the audio comes as qwen_tts_generate_stream
+ * delivers it, per utterance: cb(i, pcm, n, userdata) after frame 0, then every
+ * chunk_frames frames, then the tail.  All utterances' chunks of one poll are
+ * decoded together by the multi-stream exact codec (qtts_hip.h), so the codec
+ * work per chunk does not multiply its kernel launches by nb.  In EOS mode an
+ * utterance that stops gets its remaining frames at the next poll and no
+ * callback after that; the call returns when every utterance has stopped.
+ * out_audio[i] (malloc'd, caller frees) is the concatenation of utterance i's
+ * chunks.  perf_first_packet_ms: entry -> the last callback of the first
+ * chunks; perf_codec_ms: time in the codec pushes (perf_talker_ms excludes it).
+ * qwen_tts_generate_queue and the voice-clone batch calls do not stream: the
+ * queue needs streams at independent positions and voice clone a ragged
+ * priming of the reference frames, which the multi-stream codec does not do
+ * yet. */
+typedef void (*qwen_tts_batch_audio_cb)(int utterance, const float *pcm, int n_samples, void *userdata);
+int qwen_tts_generate_batch_stream(qwen_tts_ctx_t *ctx, int nb, const char *const *texts,
+                                   const char *const *speakers, const char *const *languages, int chunk_frames,
+                                   qwen_tts_batch_audio_cb cb, void *userdata, float **out_audio, int *out_samples);
+/* Incremental codec decode of n_streams (1..QWEN_TTS_MAX_BATCH) independent
+ * code sequences at once: begin, then pushes of time_steps frames for the n
+ * distinct streams streams[0..n) (all at the same position), codes
+ * [n][time_steps][16]; out[i] receives time_steps * 1920 samples of streams[i].
+ * Returns that count, or -1 (message; nothing decoded, the streams unchanged).
+ * Each stream's concatenation equals qwen_tts_codec_decode of its frames. */
+int qwen_tts_codec_mstream_begin(qwen_tts_ctx_t *ctx, int n_streams, int max_frames);
+int qwen_tts_codec_mstream_push(qwen_tts_ctx_t *ctx, int n, const int *streams, const int *codes, int time_steps,
+                                float *const *out);
+
 /* Text input (the reference's TODO at c/qwen_tts.c:1071-1077,
  * its browser front end tokenizes with @huggingface/transformers,
  * web/wasm/app.js:241-267): Qwen2 byte-level BPE over the model directory's

@@ -16,6 +16,8 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
+
 #include "qtts_codec.h"
 #include "qtts_common.h"
 #include "qtts_kernels.h"
@@ -49,6 +51,31 @@ __device__ __forceinline__ float sin2(float r) {
 
 __device__ __forceinline__ float snake1(float x, float a, float ib) { return x + ib * sin2(x * a); }
 
+// stream axis (XGemm::nseg / seg_m).  Conv forms: workgroup column bx of the
+// grid is tile bx % tiles of segment bx / tiles; xg_seg moves the operands to
+// that segment (nz: the main kernel's grid z, whose partials a segment owns).
+__device__ __forceinline__ void xg_seg(XGemm &g, int sg, int nz) {
+    g.B += (size_t)sg * g.seg_ldb;
+    g.C += (size_t)sg * g.seg_ldc;
+    if (g.res) g.res += (size_t)sg * g.seg_ldres;
+    if (g.part) g.part += (size_t)sg * nz * g.M * g.N;
+}
+__device__ __forceinline__ int xg_seg_tile(XGemm &g) {
+    int bx = blockIdx.x;
+    if (g.nseg > 1) {
+        const int tps = gridDim.x / g.nseg, sg = bx / tps;
+        bx -= sg * tps;
+        xg_seg(g, sg, gridDim.z);
+    }
+    return bx;
+}
+// stacked rows: where row m of a per-segment operand lies (ld: its segment stride)
+__device__ __forceinline__ size_t xg_srow(const XGemm &g, int m, int ld) {
+    if (!g.seg_m) return (size_t)m;
+    const int sg = m / g.seg_m;
+    return (size_t)sg * ld + (m - sg * g.seg_m);
+}
+
 __device__ __forceinline__ float loadB(const XGemm &g, int k, int n) {
     if (k >= g.K || n >= g.N) return 0.f;
     if (g.bmode == XB_WT) return g.B[(size_t)n * g.ldb + k];
@@ -70,7 +97,7 @@ __device__ __forceinline__ float loadB(const XGemm &g, int k, int n) {
 __device__ __forceinline__ float loadA(const XGemm &g, int m, int k) {
     if (m >= g.M || k >= g.K) return 0.f;
     if (g.amode == XA_ROWS) return g.A[(size_t)m * g.lda + k];
-    if (g.amode == XA_TRANS) return g.A[(size_t)k * g.lda + m];
+    if (g.amode == XA_TRANS) return g.A[(size_t)k * g.lda + xg_srow(g, m, g.seg_lda)];
     const int ntap = g.Kw / g.stride;  // tconv weight [ci][co][Kw], k = ic*ntap + j
     const int ic = k / ntap, j = k - ic * ntap;
     return g.A[((size_t)ic * g.co + m) * g.Kw + g.phase + j * g.stride];
@@ -91,9 +118,10 @@ __device__ __forceinline__ void xg_epi(const XGemm &g, int m, int n, float v) {
             break;
         }
         case XE_SCALE_RESID_N: g.C[(size_t)m * g.ldc + n] += v * g.vec[n]; break;
-        case XE_BIAS_T: g.C[(size_t)n * g.ldc + m] = v + g.bias[n]; break;
+        case XE_BIAS_T: g.C[(size_t)n * g.ldc + xg_srow(g, m, g.seg_ldc)] = v + g.bias[n]; break;
         case XE_BIAS_GAMMA_RES_T:
-            g.C[(size_t)n * g.ldc + m] = (v + g.bias[n]) * g.vec[n] + g.res[(size_t)n * g.ldres + m];
+            g.C[(size_t)n * g.ldc + xg_srow(g, m, g.seg_ldc)] =
+                (v + g.bias[n]) * g.vec[n] + g.res[(size_t)n * g.ldres + xg_srow(g, m, g.seg_ldres)];
             break;
         case XE_BIAS_M: {
             float y = v + (g.bias ? g.bias[m] : 0.f);
@@ -117,7 +145,7 @@ __global__ __launch_bounds__(256) void k_xgemm(XGemm g) {
     __shared__ float Bs[BN][BK + 1];
     constexpr int NA = (BM * BK) / 256, NB_ = (BN * BK) / 256;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int m0 = blockIdx.y * BM, n0 = blockIdx.x * BN;
+    const int m0 = blockIdx.y * BM, n0 = xg_seg_tile(g) * BN;
     const int wm = (wave >> 1) * 32, wn = (wave & 1) * 32;
     const int nz = gridDim.z, z = blockIdx.z;
     const int ksteps = (g.K + BK - 1) / BK;
@@ -214,7 +242,7 @@ __global__ __launch_bounds__(256) void k_conv(XGemm g) {
     __shared__ float Bs[CV_BC][NBW + 1];
     (void)NA4;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int m0 = blockIdx.y * CV_BM, n0 = blockIdx.x * CV_BN;
+    const int m0 = blockIdx.y * CV_BM, n0 = xg_seg_tile(g) * CV_BN;
     const int wm = (wave >> 1) * 32, wn = (wave & 1) * 64;
     const int ci = g.K / KW, dil = g.dil, t0 = n0 - g.pad;
     const int cpz = ci / nzk, cbeg = kzi * cpz, cend = cbeg + cpz;   // this split's input channels
@@ -356,7 +384,7 @@ __global__ __launch_bounds__(128 * WN, QTTS_CONVB_MINB) void k_convb(XGemm g) {
     __shared__ __attribute__((aligned(16))) unsigned short As[3 * KW * CV_BM * 16];
     __shared__ __attribute__((aligned(16))) unsigned short Bs[3 * NBW * 16];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int m0 = blockIdx.y * CV_BM, n0 = blockIdx.x * BNT;
+    const int m0 = blockIdx.y * CV_BM, n0 = xg_seg_tile(g) * BNT;
     const int wm = (wave / WN) * 32, wn = (wave % WN) * 64;
     const int dil = g.dil, t0 = n0 - g.pad;
     const int cpz = ci / nzk, cbeg = kzi * cpz, cend = cbeg + cpz;
@@ -589,6 +617,7 @@ __global__ void k_wt_split(const float *w, size_t n, unsigned short *planes) {
 __global__ void k_conv_reduce(XGemm g, int nph) {
     const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x, mn = (size_t)g.M * g.N;
     if (idx >= mn * nph) return;
+    if (g.nseg > 1) xg_seg(g, blockIdx.y, nph * g.kz);
     const int ph = (int)(idx / mn);
     const size_t e = idx - (size_t)ph * mn;
     const float *p = g.part + (size_t)ph * g.kz * mn + e;
@@ -628,7 +657,7 @@ __global__ __launch_bounds__(256) void k_xgemv(XGemm g, int ks) {
     load(0);
     for (int i = tid; i < M * K; i += 256) {
         const int m = i / K, k = i - m * K;
-        xs[i] = g.amode == XA_TRANS ? g.A[(size_t)k * g.lda + m] : g.A[(size_t)m * g.lda + k];
+        xs[i] = g.amode == XA_TRANS ? g.A[(size_t)k * g.lda + xg_srow(g, m, g.seg_lda)] : g.A[(size_t)m * g.lda + k];
     }
     __syncthreads();
     float acc[4] = {0.f, 0.f, 0.f, 0.f};
@@ -697,6 +726,7 @@ __global__ void k_wt_tconv(const float *w, int ci, int co, int Kw, int s, float 
 __global__ void k_xg_reduce(XGemm g, int nz) {
     const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (idx >= (size_t)g.M * g.N) return;
+    if (g.nseg > 1) xg_seg(g, blockIdx.y, nz);
     float v = 0.f;
     for (int z = 0; z < nz; ++z) v += g.part[(size_t)z * g.M * g.N + idx];
     xg_epi(g, (int)(idx / g.N), (int)(idx % g.N), v);
@@ -829,6 +859,9 @@ __global__ void k_iota(int *p, int n, int zero) {
 // come in whole stages, the window halo fits and the output fills the chip
 // (small first-packet decodes keep the split-K GEMM).
 static int conv_splits(const XGemm &g);
+// column segments of a conv form (the stream axis): they multiply the tiles a
+// plan counts and the partials it needs; 1 everywhere outside the multi-stream codec
+static int xg_nseg(const XGemm &g) { return g.bmode != XB_WT && g.nseg > 1 ? g.nseg : 1; }
 // the shapes the conv kernels were written for
 static bool conv_shape_ok(const XGemm &g) {
     return g.wt && g.bmode == XB_CONV && g.amode == XA_ROWS &&
@@ -838,7 +871,8 @@ static bool conv_shape_ok(const XGemm &g) {
 static bool conv_ok(const XGemm &g) {
     constexpr int min_tiles = 96;
     if (!conv_shape_ok(g)) return false;
-    const int tiles = ((g.N + CV_BN - 1) / CV_BN) * ((g.M + CV_BM - 1) / CV_BM) * (g.stride > 1 ? g.stride : 1);
+    const int tiles =
+        ((g.N + CV_BN - 1) / CV_BN) * ((g.M + CV_BM - 1) / CV_BM) * (g.stride > 1 ? g.stride : 1) * xg_nseg(g);
     return tiles >= min_tiles || (g.part && conv_splits(g) > 1);
 }
 
@@ -847,11 +881,12 @@ static bool conv_ok(const XGemm &g) {
 static int conv_splits(const XGemm &g) {
     if (!g.part) return 1;
     const int nph = g.stride > 1 ? g.stride : 1;
-    const int tiles = ((g.N + CV_BN - 1) / CV_BN) * ((g.M + CV_BM - 1) / CV_BM) * nph;
+    const int ns = xg_nseg(g);
+    const int tiles = ((g.N + CV_BN - 1) / CV_BN) * ((g.M + CV_BM - 1) / CV_BM) * nph * ns;
     const int ci = g.K / g.Kw;
     int nz = 1;
     while (tiles * nz * 2 <= 1024 && (ci / CV_BC) % (nz * 2) == 0 && ci / CV_BC / (nz * 2) >= 2 &&
-           (size_t)nz * 2 * nph * g.M * g.N <= g.part_elems)
+           (size_t)nz * 2 * nph * ns * g.M * g.N <= g.part_elems)
         nz *= 2;
     return nz;
 }
@@ -866,7 +901,7 @@ static int conv_path(const XGemm &g, int kz) {
     // (the two column blocks' MFMA chains interleaved measured the same:
     // codec 7.9 ms per 128 frames either way, profiles/r05st_ab_codec.txt)
     const int nph = g.stride > 1 ? g.stride : 1;
-    const int tiles4 = ((g.N + 255) / 256) * ((g.M + CV_BM - 1) / CV_BM) * nph * kz;
+    const int tiles4 = ((g.N + 255) / 256) * ((g.M + CV_BM - 1) / CV_BM) * nph * kz * xg_nseg(g);
     return tiles4 >= 512 ? QTTS_XP_CONVB4 : QTTS_XP_CONVB2;
 }
 
@@ -908,13 +943,14 @@ static int xgemv_ks(const XGemm &g) {
 // k_xgemm's split-K when the output has too few tiles to fill the chip (first-
 // packet sized decodes): z ranges of >= 8 K-steps, partials in g.part
 static int xgemm_splits(const XGemm &g) {
-    const int tiles = ((g.N + BN - 1) / BN) * ((g.M + BM - 1) / BM), ksteps = (g.K + BK - 1) / BK;
+    const int ns = xg_nseg(g);
+    const int tiles = ((g.N + BN - 1) / BN) * ((g.M + BM - 1) / BM) * ns, ksteps = (g.K + BK - 1) / BK;
     int nz = 1;
     if (g.part && tiles < 192 && ksteps >= 16) {
         nz = (256 + tiles - 1) / tiles;
         if (nz > ksteps / 8) nz = ksteps / 8;
         if (nz > 32) nz = 32;
-        while (nz > 1 && (size_t)nz * g.M * g.N > g.part_elems) --nz;
+        while (nz > 1 && (size_t)nz * ns * g.M * g.N > g.part_elems) --nz;
     }
     return nz;
 }
@@ -972,9 +1008,10 @@ static int conv_launch(const XGemm &gin, const XPlan &p, hipStream_t st) {
     XGemm g = gin;
     const int nph = g.stride > 1 ? g.stride : 1;
     g.kz = p.splits;
-    const dim3 cg((g.N + CV_BN - 1) / CV_BN, (g.M + CV_BM - 1) / CV_BM, nph * g.kz);
+    const int ns = xg_nseg(g);   // grid x: the segments' column tiles one after another
+    const dim3 cg((g.N + CV_BN - 1) / CV_BN * ns, (g.M + CV_BM - 1) / CV_BM, nph * g.kz);
     if (p.path == QTTS_XP_CONVB4) {
-        const dim3 c4((g.N + 255) / 256, cg.y, cg.z);
+        const dim3 c4((g.N + 255) / 256 * ns, cg.y, cg.z);
         switch (g.Kw) {
             case 7: hipLaunchKernelGGL((k_convb<7, 4>), c4, dim3(512), 0, st, g); break;
             case 3: hipLaunchKernelGGL((k_convb<3, 4>), c4, dim3(512), 0, st, g); break;
@@ -998,13 +1035,14 @@ static int conv_launch(const XGemm &gin, const XPlan &p, hipStream_t st) {
     }
     if (g.kz > 1) {
         const size_t n = (size_t)nph * g.M * g.N;
-        hipLaunchKernelGGL(k_conv_reduce, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, g, nph);
+        hipLaunchKernelGGL(k_conv_reduce, dim3((unsigned)((n + 255) / 256), ns), dim3(256), 0, st, g, nph);
     }
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
 static int xg_launch(const XGemm &g, const XPlan &p, hipStream_t st) {
-    const int nz = p.splits;
+    const int nz = p.splits, ns = xg_nseg(g);
+    if (g.nseg > 1 && g.bmode == XB_WT) return -1;   // (linears stack their rows: seg_m)
     switch (p.path) {
         case QTTS_XP_XLIN: {
             hipLaunchKernelGGL(k_xlin, dim3(g.N / 64, (g.M + 63) / 64, nz), dim3(256), 0, st, g);
@@ -1016,14 +1054,14 @@ static int xg_launch(const XGemm &g, const XPlan &p, hipStream_t st) {
             return hipGetLastError() == hipSuccess ? 0 : -1;
         }
         case QTTS_XP_XGEMM: {
-            hipLaunchKernelGGL(k_xgemm, dim3((g.N + BN - 1) / BN, (g.M + BM - 1) / BM, nz), dim3(256), 0, st, g);
+            hipLaunchKernelGGL(k_xgemm, dim3((g.N + BN - 1) / BN * ns, (g.M + BM - 1) / BM, nz), dim3(256), 0, st, g);
             break;
         }
         default: return conv_launch(g, p, st);
     }
     if (nz > 1) {
         const size_t n = (size_t)g.M * g.N;
-        hipLaunchKernelGGL(k_xg_reduce, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, g, nz);
+        hipLaunchKernelGGL(k_xg_reduce, dim3((unsigned)((n + 255) / 256), ns), dim3(256), 0, st, g, nz);
     }
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
@@ -1089,12 +1127,16 @@ void codec_free_state(CodecModel *m) {
     // state (codec_stream_begin's reuse path) must re-create it, never reuse it
     m->xg_part = nullptr;
     m->xg_part_elems = 0;
+    // the multi-stream state goes with it (a context's slots were re-allocated:
+    // its streams belonged to the old batch); codec_mstream_begin makes a new one
+    codec_mstream_free(m);
 }
 
 void codec_destroy(CodecModel *m) {
     for (hipEvent_t &e : m->tev)
         if (e) { hipEventDestroy(e); e = nullptr; }
     codec_stream_free(m);
+    codec_mstream_free(m);
     codec_free_state(m);
     for (auto &kv : m->w) hipFree(kv.second);
     m->w.clear();
@@ -1773,14 +1815,20 @@ extern "C" int qtts_hip_xgemm_plan(const qtts_xgemm_desc_t *d, size_t part_elems
     return 0;
 }
 
-extern "C" int qtts_hip_xgemm_case(const qtts_xgemm_desc_t *d, size_t part_elems, int force_path, int *path_out,
-                                   int *splits_out, void *stream) {
-    hipStream_t st = (hipStream_t)stream;
+// nseg > 1: the conv forms' stream axis (segment s reads B + s*seg_ldb, writes
+// C + s*seg_ldc; an in-place res moves with C); the single-segment plan only
+// says whether the kernel covers the shape, the segments' own plan is reported
+static int xcase_run(const qtts_xgemm_desc_t *d, int nseg, int seg_ldb, int seg_ldc, size_t part_elems,
+                     int force_path, int *path_out, int *splits_out, hipStream_t st) {
     int pp = 0, ps = 0;
     const int prc = qtts_hip_xgemm_plan(d, part_elems, force_path, &pp, &ps);
     if (prc) return prc;   // nothing launched
     XGemm g;
     xcase_gemm(d, &g);
+    if (nseg > 1) {
+        if (g.bmode == XB_WT) return -1;
+        g.nseg = nseg; g.seg_ldb = seg_ldb; g.seg_ldc = seg_ldc; g.seg_ldres = seg_ldc;
+    }
     CodecModel dummy;   // holds the workspace and the re-laid weights of this one call
     if (part_elems) {
         if (hipMalloc(&dummy.xg_part, part_elems * sizeof(float)) != hipSuccess) return -1;
@@ -1811,10 +1859,22 @@ extern "C" int qtts_hip_xgemm_case(const qtts_xgemm_desc_t *d, size_t part_elems
     dummy.wt.clear();
     if (dummy.xg_part) hipFree(dummy.xg_part);
     dummy.xg_part = nullptr;
-    if (!rc && (ran.path != pp || ran.splits != ps)) rc = -1;   // the launcher ran what the planner said
+    if (!rc && nseg <= 1 && (ran.path != pp || ran.splits != ps)) rc = -1;   // the launcher ran what the planner said
     if (path_out) *path_out = ran.path;
     if (splits_out) *splits_out = ran.splits;
     return rc;
+}
+
+extern "C" int qtts_hip_xgemm_case(const qtts_xgemm_desc_t *d, size_t part_elems, int force_path, int *path_out,
+                                   int *splits_out, void *stream) {
+    return xcase_run(d, 1, 0, 0, part_elems, force_path, path_out, splits_out, (hipStream_t)stream);
+}
+
+extern "C" int qtts_hip_xgemm_seg_case(const qtts_xgemm_desc_t *d, int nseg, int seg_ldb, int seg_ldc,
+                                       size_t part_elems, int force_path, int *path_out, int *splits_out,
+                                       void *stream) {
+    if (nseg < 1 || (nseg > 1 && (!d || d->bmode == XB_WT))) return -1;
+    return xcase_run(d, nseg, seg_ldb, seg_ldc, part_elems, force_path, path_out, splits_out, (hipStream_t)stream);
 }
 
 namespace {
@@ -2196,4 +2256,613 @@ int codec_stream_push_to(CodecModel *m, const int *codes, int ldc_codes, int Tto
     }
     if (host && hipStreamSynchronize(st) != hipSuccess) return -1;
     return written;
+}
+
+// ===================================================================== multi-stream streaming decode
+// n independent exact streams, one launch sequence per push whatever n
+// (DESIGN.md 7).  Every channel-major activation holds one plane per stream
+// of the push, [C][hm + L] as the single stream lays it out, planes one
+// after another (plane stride C * ld); the conv kernels take the plane as a
+// grid-x segment (XGemm::nseg), the element-wise kernels as grid y.  The
+// transformer and the ConvNeXt pointwise convs stack the streams' rows
+// (M = n * T): the linear kernels are row-independent, so the weights are
+// read once, and XGemm::seg_m sends the transposed operands to the planes.
+namespace {
+constexpr size_t kMsScratchBudget = (size_t)2 << 30;   // bytes of the four activation buffers
+
+void *msalloc(CodecMStream &S, size_t bytes) {
+    void *p = nullptr;
+    const hipError_t e = hipMalloc(&p, bytes ? bytes : 16);
+    if (e != hipSuccess) {
+        fprintf(stderr, "qtts codec mstream: hipMalloc(%zu) failed: %s\n", bytes, hipGetErrorName(e));
+        return nullptr;
+    }
+    hipMemset(p, 0, bytes ? bytes : 16);
+    S.allocs.push_back(p);
+    return p;
+}
+
+// k_rvq_sum over the stacked rows r = s * T + t of a push: stream s's codes
+// start at codes + coff[s], frame t0 + t
+__global__ void k_rvq_sum_ms(const int *codes, const long long *coff, int ldc, int t0, int T, int n, int Q, int CB,
+                             int vq, const float *cb, float *ss, float *as) {
+#pragma clang fp contract(off)
+    const int r = blockIdx.x, s = r / T, t = r - s * T, k = threadIdx.x;
+    if (k >= vq) return;
+    const int *row = codes + coff[s] + (size_t)(t0 + t) * ldc;
+    float sm = 0.f, a = 0.f;
+    for (int q = 0; q < Q; ++q) {
+        int c = row[q];
+        if (c < 0 || c >= CB) c = 0;
+        const float e = cb[((size_t)q * CB + c) * vq + k];
+        if (q == 0) sm += e;
+        else a += e;
+    }
+    ss[(size_t)k * n * T + r] = sm;
+    as[(size_t)k * n * T + r] = a;
+}
+// k_rvq_proj: output (o, r) to stream r / T's plane (plane stride seg)
+__global__ void k_rvq_proj_ms(const float *ps, const float *pa, const float *ss, const float *as, int vq, int half,
+                              int T, int n, int ldo, size_t seg, float *out) {
+    const int idx = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63, nt = n * T;
+    if (idx >= half * nt) return;
+    const int o = idx / nt, r = idx - o * nt, s = r / T, t = r - s * T;
+    float s1 = 0.f, s2 = 0.f;
+    for (int k = lane; k < vq; k += 64) {
+        s1 = fmaf(ps[(size_t)o * vq + k], ss[(size_t)k * nt + r], s1);
+        s2 = fmaf(pa[(size_t)o * vq + k], as[(size_t)k * nt + r], s2);
+    }
+    s1 = wave_sum(s1);
+    s2 = wave_sum(s2);
+    if (lane == 0) out[s * seg + (size_t)o * ldo + t] = s1 + s2;
+}
+// history of every stream of the push in one launch (grid y = stream of the
+// push): out 0: slot[sid[s]] -> the H columns left of plane s's rows; out 1:
+// the last H columns of [margin | L) -> slot[sid[s]].  hist: [streams][C][H]
+__global__ void k_hist_ms(float *hist, const int *sid, float *x, size_t seg, int ldx, int C, int H, int L, int out) {
+    const int idx = blockIdx.x * 256 + threadIdx.x, s = blockIdx.y;
+    if (idx >= C * H) return;
+    const int c = idx / H, h = idx - c * H;
+    float *hp = hist + ((size_t)sid[s] * C + c) * H + h;
+    float *xp = x + s * seg + (size_t)c * ldx;
+    if (out) *hp = xp[L - H + h];
+    else xp[h - H] = *hp;
+}
+// rotate-half RoPE (k_rope_rows' arithmetic) of the stacked q rows in place and
+// of the k rows into stream sid[s]'s cache at row hl + t; the v rows beside them
+__global__ void k_rope_kv_ms(float *q, int hid, int nh, const float *k, const float *v, int kvd, int nkv, int hd,
+                             const float *cs, const float *sn, int T, const int *sid, int hl, float *kc, float *vc,
+                             int S) {
+    const int r = blockIdx.x, s = r / T, t = r - s * T;
+    const int half = hd / 2;
+    const float *c = cs + (size_t)t * hd, *sv = sn + (size_t)t * hd;
+    for (int i = threadIdx.x; i < nh * half; i += blockDim.x) {
+        const int h = i / half, e = i - h * half;
+        float *qq = q + (size_t)r * hid + h * hd;
+        const float a = qq[e], bb = qq[e + half];
+        qq[e] = a * c[e] - bb * sv[e];
+        qq[e + half] = bb * c[e + half] + a * sv[e + half];
+    }
+    const size_t dst = ((size_t)sid[s] * S + hl + t) * kvd;
+    for (int i = threadIdx.x; i < nkv * half; i += blockDim.x) {
+        const int h = i / half, e = i - h * half;
+        const float *kk = k + (size_t)r * kvd + h * hd;
+        float *kd = kc + dst + h * hd;
+        const float a = kk[e], bb = kk[e + half];
+        kd[e] = a * c[e] - bb * sv[e];
+        kd[e + half] = bb * c[e + half] + a * sv[e + half];
+    }
+    for (int i = threadIdx.x; i < kvd; i += blockDim.x) vc[dst + i] = v[(size_t)r * kvd + i];
+}
+// the window keep-shift of every layer's K and V of every stream of the push
+// in one launch: rows [shift, shift + keep) -> [0, keep).  One thread per
+// column walks its rows upwards (row i is read before any thread writes it:
+// the thread owns the column), so no second buffer.  kv: [nl2][streams][S][kvd]
+__global__ void k_kv_shift_ms(float *kv, const int *sid, int n, int ns, int S, int kvd, int nl2, int shift, int keep) {
+    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (size_t)nl2 * n * kvd) return;
+    const int col = (int)(idx % kvd), s = (int)((idx / kvd) % n), l2 = (int)(idx / ((size_t)kvd * n));
+    float *p = kv + (((size_t)l2 * ns + sid[s]) * S) * kvd + col;
+    for (int i = 0; i < keep; ++i) p[(size_t)i * kvd] = p[(size_t)(i + shift) * kvd];
+}
+// attention rows of a pass: stacked row r = s * T + t -> cache sid[s], position hl + t
+__global__ void k_ms_index(const int *sid, int n, int T, int hl, int *row_b, int *pos) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n * T) return;
+    row_b[i] = sid[i / T];
+    pos[i] = hl + i % T;
+}
+// k_dwconv per plane (grid y)
+__global__ void k_dwconv_ms(const float *x, size_t segx, int ldx, int tmin, const float *w, const float *b, int C,
+                            int L, int K, float *y, size_t segy, int ldy) {
+#pragma clang fp contract(off)
+    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (size_t)C * L) return;
+    x += blockIdx.y * segx;
+    y += blockIdx.y * segy;
+    const int c = (int)(idx / L), t = (int)(idx - (size_t)c * L);
+    float acc = b ? b[c] : 0.f;
+    for (int k = 0; k < K; ++k) {
+        const int ti = t - (K - 1) + k;
+        if (ti >= tmin) acc += w[(size_t)c * K + k] * x[(size_t)c * ldx + ti];
+    }
+    y[(size_t)c * ldy + t] = acc;
+}
+// k_ln_t: column t of plane s -> stacked time-major row s * L + t
+__global__ __launch_bounds__(256) void k_ln_t_ms(const float *x, size_t segx, int ldx, int L, int C, const float *w,
+                                                 const float *b, float eps, float *y) {
+    __shared__ float red[8];
+    const int r = blockIdx.x, s = r / L, t = r - s * L;
+    x += s * segx;
+    float sm = 0.f;
+    for (int c = threadIdx.x; c < C; c += 256) sm += x[(size_t)c * ldx + t];
+    const float mean = block_sum256(sm, red) / (float)C;
+    float v = 0.f;
+    for (int c = threadIdx.x; c < C; c += 256) { const float d = x[(size_t)c * ldx + t] - mean; v += d * d; }
+    const float var = block_sum256(v, red + 4) / (float)C;
+    const float inv = div_rn(1.0f, sqrt_rn(var + eps));
+    for (int c = threadIdx.x; c < C; c += 256) {
+        float o = (x[(size_t)c * ldx + t] - mean) * inv;
+        o *= w[c];
+        y[(size_t)r * C + c] = o + b[c];
+    }
+}
+// clamp of every plane's waveform row into the compact [n][L] output
+__global__ void k_clamp_ms(const float *x, size_t seg, int L, float *y) {
+    const int i = blockIdx.x * 256 + threadIdx.x, s = blockIdx.y;
+    if (i >= L) return;
+    float v = x[s * seg + i];
+    if (v < -1.0f) v = -1.0f;
+    if (v > 1.0f) v = 1.0f;
+    y[(size_t)s * L + i] = v;
+}
+
+void ms_hist(CodecModel *m, int n, int slot, float *x, size_t seg, int ldx, int L, int out) {
+    CodecMStream &S = m->ms;
+    const int C = S.hist_c[slot], H = S.hist_h[slot];
+    hipLaunchKernelGGL(k_hist_ms, dim3((C * H + 255) / 256, n), dim3(256), 0, m->st, S.hist[slot], S.sid, x, seg, ldx,
+                       C, H, L, out);
+}
+
+// sconv / stconv over n planes: input plane stride ci * ldx, output co * ldo
+int ms_sconv(CodecModel *m, int n, int slot, float *x, int ldx, int ci, int L, const std::string &wn,
+             const std::string &bn, int co, int K, int dil, float *out, int ldo, int emode, const float *sa,
+             const float *sb, const float *res, const float *ea = nullptr, const float *eb = nullptr) {
+    const int H = (K - 1) * dil;
+    const size_t segx = (size_t)ci * ldx;
+    if (H > 0) ms_hist(m, n, slot, x, segx, ldx, L, 0);
+    XGemm g;
+    g.M = co; g.N = L; g.K = ci * K;
+    g.amode = XA_ROWS; g.A = cw(m, wn); g.lda = ci * K; g.wt = cwt(m, wn, co, ci, K);
+    g.bmode = XB_CONV; g.B = x; g.ldb = ldx; g.Kw = K; g.dil = dil; g.pad = H; g.L = L; g.tmin = -H;
+    g.sa = sa; g.sb = sb;
+    g.C = out; g.ldc = ldo; g.emode = emode; g.bias = bn.empty() ? nullptr : cw(m, bn); g.res = res; g.ldres = ldo;
+    g.ea = ea; g.eb = eb;
+    g.nseg = n; g.seg_ldb = ci * ldx; g.seg_ldc = co * ldo; g.seg_ldres = co * ldo;
+    if (!g.A) return -1;
+    KCK(xgm(m, g, m->st));
+    if (H > 0) ms_hist(m, n, slot, x, segx, ldx, L, 1);
+    return 0;
+}
+
+int ms_stconv(CodecModel *m, int n, int slot, float *x, int ldx, int ci, int L, const float *w, const float *bias,
+              int co, int Kw, int s, float *out, int ldo, const float *sa, const float *sb) {
+    const int H = Kw / s - 1;
+    const size_t segx = (size_t)ci * ldx;
+    if (H > 0) ms_hist(m, n, slot, x, segx, ldx, L, 0);
+    XGemm g;
+    g.M = co; g.N = L; g.K = ci * (Kw / s);
+    g.amode = XA_TCONV_W; g.A = w; g.co = co; g.Kw = Kw; g.stride = s;
+    g.bmode = XB_TCONV; g.B = x; g.ldb = ldx; g.L = L; g.tmin = -H; g.sa = sa; g.sb = sb;
+    g.C = out; g.ldc = ldo; g.emode = XE_BIAS_M; g.bias = bias;
+    g.nseg = n; g.seg_ldb = ci * ldx; g.seg_ldc = co * ldo;
+    KCK(tconv_run(m, g, m->st));
+    if (H > 0) ms_hist(m, n, slot, x, segx, ldx, L, 1);
+    return 0;
+}
+
+// the transformer over the stacked rows M = n * T of a pass; pc / out: planes
+// [lat][ldp] / [lat][ldo]; every stream of the pass is at pos0 with hl history rows
+int ms_transformer(CodecModel *m, int n, const float *pc, int ldp, int T, float *out, int ldo, int pos0, int hl) {
+    CodecMStream &S = m->ms;
+    const qtts_dims_t &d = m->d;
+    const int lat = d.clat, hid = d.chid, nh = d.cheads, nkv = d.ckv, hd = hid / nh, kvd = nkv * hd, I = d.cinter;
+    const int keepmax = d.cwin - 1, M = n * T;
+    hipStream_t st = m->st;
+    const std::string P = "decoder.pre_transformer.";
+    XGemm g;
+    g.M = M; g.N = hid; g.K = lat; g.amode = XA_TRANS; g.A = pc; g.lda = ldp; g.bmode = XB_WT;
+    g.B = cw(m, P + "input_proj.weight"); g.ldb = lat; g.C = S.tx; g.ldc = hid;
+    g.bias = cw(m, P + "input_proj.bias");
+    g.emode = g.bias ? XE_BIAS_N : XE_STORE;
+    g.seg_m = T; g.seg_lda = lat * ldp;
+    KCK(xgm(m, g, st));
+    const float *cs = S.rope_cos + (size_t)pos0 * hd, *sn = S.rope_sin + (size_t)pos0 * hd;
+    hipLaunchKernelGGL(k_ms_index, dim3((M + 255) / 256), dim3(256), 0, st, S.sid, n, T, hl, S.row_b, S.pos);
+    const size_t lsz = (size_t)S.ns * S.S * kvd;   // one layer's K (or V) of every stream
+    for (int l = 0; l < d.clayers; ++l) {
+        const std::string p = P + "layers." + std::to_string(l) + ".";
+        float *kcl = S.kv + (size_t)(2 * l) * lsz, *vcl = kcl + lsz;
+        hipLaunchKernelGGL(k_rms_rows, dim3(M), dim3(256), 0, st, S.tx, hid, cw(m, p + "input_layernorm.weight"),
+                           d.ceps, S.txn);
+        KCK(xgm(m, lin(S.txn, M, hid, cw(m, p + "self_attn.q_proj.weight"), hid, S.tq, XE_STORE), st));
+        KCK(xgm(m, lin(S.txn, M, hid, cw(m, p + "self_attn.k_proj.weight"), kvd, S.tk, XE_STORE), st));
+        KCK(xgm(m, lin(S.txn, M, hid, cw(m, p + "self_attn.v_proj.weight"), kvd, S.tv, XE_STORE), st));
+        hipLaunchKernelGGL(k_rope_kv_ms, dim3(M), dim3(256), 0, st, S.tq, hid, nh, S.tk, S.tv, kvd, nkv, hd, cs, sn, T,
+                           S.sid, hl, kcl, vcl, S.S);
+        AttnArgs a;
+        a.mode = 1; a.qkv = S.tq; a.ld_qkv = hid; a.kc = kcl; a.vc = vcl; a.S = S.S; a.pos = S.pos;
+        a.row_b = S.row_b; a.NH = nh; a.KV = nkv; a.HD = hd; a.out = S.tatt; a.ld_out = hid;
+        a.nrows = M; a.win = d.cwin;
+        KCK(qtts_attention(a, st));
+        const float *ls1 = cw(m, p + "self_attn_layer_scale.scale");
+        if (!ls1) return -1;
+        XGemm o = lin(S.tatt, M, hid, cw(m, p + "self_attn.o_proj.weight"), hid, S.tx, XE_SCALE_RESID_N);
+        o.vec = ls1;
+        KCK(xgm(m, o, st));
+        hipLaunchKernelGGL(k_rms_rows, dim3(M), dim3(256), 0, st, S.tx, hid,
+                           cw(m, p + "post_attention_layernorm.weight"), d.ceps, S.txn);
+        KCK(xgm(m, lin(S.txn, M, hid, cw(m, p + "mlp.gate_proj.weight"), I, S.tg, XE_STORE), st));
+        XGemm u = lin(S.txn, M, hid, cw(m, p + "mlp.up_proj.weight"), I, S.tu, XE_SILU_MUL);
+        u.aux = S.tg; u.ldaux = I;
+        KCK(xgm(m, u, st));
+        const float *ls2 = cw(m, p + "mlp_layer_scale.scale");
+        if (!ls2) return -1;
+        XGemm dn = lin(S.tu, M, I, cw(m, p + "mlp.down_proj.weight"), hid, S.tx, XE_SCALE_RESID_N);
+        dn.vec = ls2;
+        KCK(xgm(m, dn, st));
+    }
+    // keep the last window-1 rows of every layer for the next pass
+    const int tot = hl + T, keep = tot < keepmax ? tot : keepmax;
+    if (keep > 0 && tot > keep) {
+        const size_t cols = (size_t)2 * d.clayers * n * kvd;
+        hipLaunchKernelGGL(k_kv_shift_ms, dim3((unsigned)((cols + 255) / 256)), dim3(256), 0, st, S.kv, S.sid, n, S.ns,
+                           S.S, kvd, 2 * d.clayers, tot - keep, keep);
+    }
+    const float *fn = cw(m, P + "norm.weight");
+    const float *xin = S.tx;
+    if (fn) {
+        hipLaunchKernelGGL(k_rms_rows, dim3(M), dim3(256), 0, st, S.tx, hid, fn, d.ceps, S.txn);
+        xin = S.txn;
+    }
+    XGemm og = lin(xin, M, hid, cw(m, P + "output_proj.weight"), lat, out, XE_BIAS_T);
+    og.bias = cw(m, P + "output_proj.bias");
+    og.ldc = ldo;
+    og.seg_m = T; og.seg_ldc = lat * ldo;
+    if (!og.bias) return -1;
+    return xgm(m, og, st);
+}
+
+int ms_add_slot(CodecMStream &S, int c, int h) {
+    S.hist_c.push_back(c);
+    S.hist_h.push_back(h);
+    const size_t bytes = (size_t)S.ns * c * (h > 0 ? h : 1) * 4;
+    S.hist.push_back((float *)msalloc(S, bytes));
+    S.state_bytes += bytes;
+    return S.hist.back() ? 0 : -1;
+}
+
+// largest per-stream plane (elements) over the stages at tc frames: codec_stream_begin's sizing
+size_t ms_plane_elems(const qtts_dims_t &d, int tc, int hm) {
+    size_t L = (size_t)tc * d.ratios[0] * d.ratios[1];
+    size_t mx = (size_t)d.clat * L * 4 + (size_t)4 * d.clat * hm;
+    if ((size_t)d.cdec * (L + hm) > mx) mx = (size_t)d.cdec * (L + hm);
+    int C = d.cdec;
+    for (int b = 0; b < 4; ++b) {
+        L *= d.rates[b];
+        C /= 2;
+        if ((size_t)C * (L + hm) > mx) mx = (size_t)C * (L + hm);
+    }
+    if ((size_t)d.clat * (tc + hm) > mx) mx = (size_t)d.clat * (tc + hm);
+    return mx;
+}
+
+// frames per internal pass for n streams: the chunk asked for, lowered until
+// the four activation buffers of n planes fit the budget
+int ms_chunk(const qtts_dims_t &d, int n, int chunk, int hm) {
+    int tc = chunk > kStreamChunk ? (chunk < kStreamChunkMax ? chunk : kStreamChunkMax) : kStreamChunk;
+    while (tc > 1 && 4 * (size_t)n * ms_plane_elems(d, tc, hm) * 4 > kMsScratchBudget) --tc;
+    return tc;
+}
+
+int ms_samples_per_frame(const qtts_dims_t &d) {
+    int f = d.ratios[0] * d.ratios[1];
+    for (int b = 0; b < 4; ++b) f *= d.rates[b];
+    return f;
+}
+
+// one pass: T <= tc frames of the n streams of the push, audio to S.wav [n][T * spf]
+int ms_pass(CodecModel *m, int n, const int *codes, int ldc_codes, int t0, int T, int pos0, int hl, int *L_out) {
+    CodecMStream &S = m->ms;
+    const qtts_dims_t &d = m->d;
+    hipStream_t st = m->st;
+    const int lat = d.clat, vq = d.ccbdim / 2, half = lat / 2, hm = S.hm;
+    float *A = S.bufA + hm, *B = S.bufB + hm, *Cb = S.bufC, *D = S.bufD;
+    int L = T, ld = hm + L;
+    // 1. RVQ dequantise -> A planes [half][T]
+    hipLaunchKernelGGL(k_rvq_sum_ms, dim3(n * T), dim3(vq < 64 ? 64 : (vq + 63) / 64 * 64), 0, st, codes, S.coff,
+                       ldc_codes, t0, T, n, d.cq, d.ccb, vq, m->cb, S.rvq_s, S.rvq_a);
+    hipLaunchKernelGGL(k_rvq_proj_ms, dim3((half * n * T + 3) / 4), dim3(256), 0, st,
+                       cw(m, "decoder.quantizer.rvq_first.output_proj.weight"),
+                       cw(m, "decoder.quantizer.rvq_rest.output_proj.weight"), S.rvq_s, S.rvq_a, vq, half, T, n, ld,
+                       (size_t)d.ccbdim * ld, A);
+    // 2. pre-conv k3 -> B
+    KCK(ms_sconv(m, n, 0, A, ld, d.ccbdim, L, "decoder.pre_conv.conv.weight", "decoder.pre_conv.conv.bias", lat, 3, 1,
+                 B, ld, XE_BIAS_M, nullptr, nullptr, nullptr));
+    // 3. transformer -> A
+    KCK(ms_transformer(m, n, B, ld, T, A, ld, pos0, hl));
+    // 4. upsample x2: tconv (K = s, no history) + ConvNeXt
+    float *cur = A;
+    for (int s = 0; s < 2; ++s) {
+        const int f = d.ratios[s];
+        const std::string p = "decoder.upsample." + std::to_string(s) + ".";
+        float *up = cur == A ? B : A;
+        const int ldu = hm + L * f;
+        KCK(ms_stconv(m, n, -1, cur, ld, lat, L, cw(m, p + "0.conv.weight"), cw(m, p + "0.conv.bias"), lat, f, f, up,
+                      ldu, nullptr, nullptr));
+        L *= f;
+        ld = ldu;
+        cur = up;
+        const size_t seg = (size_t)lat * ld;
+        ms_hist(m, n, 1 + s, cur, seg, ld, L, 0);
+        hipLaunchKernelGGL(k_dwconv_ms, dim3((unsigned)(((size_t)lat * L + 255) / 256), n), dim3(256), 0, st, cur, seg,
+                           ld, -6, cw(m, p + "1.dwconv.conv.weight"), cw(m, p + "1.dwconv.conv.bias"), lat, L, 7, Cb,
+                           (size_t)lat * L, L);
+        ms_hist(m, n, 1 + s, cur, seg, ld, L, 1);
+        hipLaunchKernelGGL(k_ln_t_ms, dim3(n * L), dim3(256), 0, st, Cb, (size_t)lat * L, L, L, lat,
+                           cw(m, p + "1.norm.weight"), cw(m, p + "1.norm.bias"), 1e-6f, D);
+        XGemm g1 = lin(D, n * L, lat, cw(m, p + "1.pwconv1.weight"), 4 * lat, Cb, XE_BIAS_N_GELU);
+        g1.bias = cw(m, p + "1.pwconv1.bias");
+        KCK(xgm(m, g1, st));
+        XGemm g2 = lin(Cb, n * L, 4 * lat, cw(m, p + "1.pwconv2.weight"), lat, cur, XE_BIAS_GAMMA_RES_T);
+        g2.bias = cw(m, p + "1.pwconv2.bias");
+        g2.vec = cw(m, p + "1.gamma");
+        g2.res = cur; g2.ldres = ld; g2.ldc = ld;
+        g2.seg_m = L; g2.seg_ldc = lat * ld; g2.seg_ldres = lat * ld;
+        KCK(xgm(m, g2, st));
+    }
+    // 5. vocoder
+    float *voc = cur == A ? B : A;
+    KCK(ms_sconv(m, n, 3, cur, ld, lat, L, "decoder.decoder.0.conv.weight", "decoder.decoder.0.conv.bias", d.cdec, 7, 1,
+                 voc, ld, XE_BIAS_M, nullptr, nullptr, nullptr));
+    int C = d.cdec, slot = 4;
+    static const int dil[3] = {1, 3, 9};
+    for (int b = 0; b < 4; ++b) {
+        const int r = d.rates[b], co = C / 2;
+        const std::string p = "decoder.decoder." + std::to_string(b + 1) + ".block.";
+        float *nx = voc == A ? B : A;
+        const int ldn = hm + L * r;
+        KCK(ms_stconv(m, n, slot++, voc, ld, C, L, cw(m, p + "1.conv.weight"), cw(m, p + "1.conv.bias"), co, 2 * r, r,
+                      nx, ldn, cw(m, p + "0.alpha"), cw(m, p + "0.beta")));
+        L *= r;
+        ld = ldn;
+        C = co;
+        voc = nx;
+        for (int u = 0; u < 3; ++u) {
+            const std::string q = p + std::to_string(u + 2) + ".";
+            KCK(ms_sconv(m, n, slot++, voc, ld, C, L, q + "conv1.conv.weight", q + "conv1.conv.bias", C, 7, dil[u], Cb,
+                         L, XE_BIAS_M_SNAKE, cw(m, q + "act1.alpha"), cw(m, q + "act1.beta"), nullptr,
+                         cw(m, q + "act2.alpha"), cw(m, q + "act2.beta")));
+            KCK(ms_sconv(m, n, -1, Cb, L, C, L, q + "conv2.conv.weight", q + "conv2.conv.bias", C, 1, 1, voc, ld,
+                         XE_BIAS_M_RES, nullptr, nullptr, voc));
+        }
+    }
+    float *wav = voc == A ? B : A;
+    KCK(ms_sconv(m, n, slot, voc, ld, C, L, "decoder.decoder.6.conv.weight", "decoder.decoder.6.conv.bias", 1, 7, 1, wav,
+                 ld, XE_BIAS_M, cw(m, "decoder.decoder.5.alpha"), cw(m, "decoder.decoder.5.beta"), nullptr));
+    hipLaunchKernelGGL(k_clamp_ms, dim3((L + 255) / 256, n), dim3(256), 0, st, wav, (size_t)ld, L, S.wav);
+    *L_out = L;
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+}  // namespace
+
+void codec_mstream_free(CodecModel *m) {
+    CodecMStream &S = m->ms;
+    for (void *p : S.allocs) hipFree(p);
+    S = CodecMStream();
+}
+
+int codec_mstream_pos(const CodecModel *m, int stream) {
+    const CodecMStream &S = m->ms;
+    if (!S.active || stream < 0 || stream >= S.ns) return -1;
+    return S.pos0[stream];
+}
+
+int codec_mstream_begin(CodecModel *m, int n_streams, int max_frames, int chunk) {
+    const qtts_dims_t &d = m->d;
+    if (n_streams < 1 || n_streams > 64 || max_frames < 1) {
+        fprintf(stderr, "qtts codec mstream: begin needs 1..64 streams and max_frames >= 1 (got %d, %d)\n", n_streams,
+                max_frames);
+        return -1;
+    }
+    // the split-K workspace belongs to the codec state (codec_stream_begin has
+    // the story): re-create it first; a re-allocation of that state frees this
+    // one too, so look at it only afterwards
+    if (ensure_codec_state(m, 1)) return -1;
+    const int tc = ms_chunk(d, n_streams, chunk, m->ms.hm);
+    CodecMStream &S0 = m->ms;
+    if (S0.active && S0.ns == n_streams && S0.tc == tc && max_frames + tc <= S0.rope_cap) {
+        // reuse the buffers: zero histories, no K/V rows, position 0
+        for (size_t i = 0; i < S0.hist.size(); ++i)
+            if (hipMemsetAsync(S0.hist[i], 0, (size_t)S0.ns * S0.hist_c[i] * (S0.hist_h[i] > 0 ? S0.hist_h[i] : 1) * 4,
+                               m->st) != hipSuccess)
+                return -1;
+        std::fill(S0.pos0.begin(), S0.pos0.end(), 0);
+        std::fill(S0.hl.begin(), S0.hl.end(), 0);
+        S0.max_frames = max_frames;
+        return 0;
+    }
+    if (hipStreamSynchronize(m->st) != hipSuccess) return -1;
+    codec_mstream_free(m);
+    CodecMStream &S = m->ms;
+    S.ns = n_streams;
+    S.tc = tc;
+    S.max_frames = max_frames;
+    S.pos0.assign(n_streams, 0);
+    S.hl.assign(n_streams, 0);
+    const int hm = S.hm, ns = n_streams;
+    const size_t rows = (size_t)ns * tc;
+    S.buf_elems = ms_plane_elems(d, tc, hm);
+    const size_t bbytes = ((size_t)ns * S.buf_elems + hm) * 4;
+    S.bufA = (float *)msalloc(S, bbytes);
+    S.bufB = (float *)msalloc(S, bbytes);
+    S.bufC = (float *)msalloc(S, bbytes);
+    S.bufD = (float *)msalloc(S, bbytes);
+    const int hid = d.chid, hd = hid / d.cheads, kvd = d.ckv * hd, keep = d.cwin - 1, vq = d.ccbdim / 2;
+    S.tx = (float *)msalloc(S, rows * hid * 4);
+    S.txn = (float *)msalloc(S, rows * hid * 4);
+    S.tq = (float *)msalloc(S, rows * hid * 4);
+    S.tk = (float *)msalloc(S, rows * kvd * 4);
+    S.tv = (float *)msalloc(S, rows * kvd * 4);
+    S.tatt = (float *)msalloc(S, rows * hid * 4);
+    S.tg = (float *)msalloc(S, rows * d.cinter * 4);
+    S.tu = (float *)msalloc(S, rows * d.cinter * 4);
+    S.rvq_s = (float *)msalloc(S, rows * vq * 4);
+    S.rvq_a = (float *)msalloc(S, rows * vq * 4);
+    const int spf = ms_samples_per_frame(d);
+    S.wav = (float *)msalloc(S, rows * spf * 4);
+    S.scratch_bytes = 4 * bbytes + rows * ((size_t)4 * hid + 2 * kvd + 2 * d.cinter + 2 * vq + spf) * 4;
+    S.S = keep + tc;
+    const size_t kvbytes = (size_t)2 * d.clayers * ns * S.S * kvd * 4;
+    S.kv = (float *)msalloc(S, kvbytes);
+    S.state_bytes = kvbytes;
+    // RoPE table for absolute positions [0, max_frames + tc) (theta 1e4, Cd.c:309)
+    S.rope_cap = max_frames + tc;
+    const int half = hd / 2;
+    std::vector<float> c((size_t)S.rope_cap * hd), s((size_t)S.rope_cap * hd);
+    for (int p = 0; p < S.rope_cap; ++p)
+        for (int i = 0; i < half; ++i) {
+            float freq = 1.0f / powf(10000.0f, (float)(2 * i) / (float)hd);
+            float ang = (float)p * freq;
+            c[(size_t)p * hd + i] = c[(size_t)p * hd + i + half] = cosf(ang);
+            s[(size_t)p * hd + i] = s[(size_t)p * hd + i + half] = sinf(ang);
+        }
+    S.rope_cos = (float *)msalloc(S, c.size() * 4);
+    S.rope_sin = (float *)msalloc(S, s.size() * 4);
+    S.sid = (int *)msalloc(S, (size_t)ns * 4);
+    S.row_b = (int *)msalloc(S, rows * 4);
+    S.pos = (int *)msalloc(S, rows * 4);
+    S.coff = (long long *)msalloc(S, (size_t)ns * 8);
+    for (void *p : S.allocs)
+        if (!p) return -1;
+    if (!S.bufA || !S.bufB || !S.bufC || !S.bufD || !S.kv || !S.wav || !S.rope_cos || !S.rope_sin || !S.sid ||
+        !S.row_b || !S.pos || !S.coff || !S.tx || !S.txn || !S.tq || !S.tk || !S.tv || !S.tatt || !S.tg || !S.tu ||
+        !S.rvq_s || !S.rvq_a)
+        return -1;
+    if (hipMemcpy(S.rope_cos, c.data(), c.size() * 4, hipMemcpyHostToDevice) != hipSuccess) return -1;
+    if (hipMemcpy(S.rope_sin, s.data(), s.size() * 4, hipMemcpyHostToDevice) != hipSuccess) return -1;
+    // history slots, in codec_stream_begin's order, each [ns][C][H]
+    int rc = 0;
+    rc |= ms_add_slot(S, d.ccbdim, 2);                  // 0 pre-conv k3
+    rc |= ms_add_slot(S, d.clat, 6);                    // 1 upsample 0 dwconv k7
+    rc |= ms_add_slot(S, d.clat, 6);                    // 2 upsample 1 dwconv k7
+    rc |= ms_add_slot(S, d.clat, 6);                    // 3 vocoder conv0 k7
+    int C = d.cdec;
+    static const int dil[3] = {1, 3, 9};
+    for (int b = 0; b < 4; ++b) {
+        rc |= ms_add_slot(S, C, 1);                     // block tconv (K = 2r): last input frame
+        for (int u = 0; u < 3; ++u) rc |= ms_add_slot(S, C / 2, 6 * dil[u]);   // ResUnit conv1 k7 dil
+        C /= 2;
+    }
+    rc |= ms_add_slot(S, C, 6);                         // final conv k7
+    if (rc) return -1;
+    if (hipDeviceSynchronize() != hipSuccess) return -1;
+    S.active = true;
+    return 0;
+}
+
+int codec_mstream_check(CodecModel *m, int n, const int *streams, int T) {
+    const CodecMStream &S = m->ms;
+    if (!S.active) {
+        fprintf(stderr, "qtts codec mstream: push without begin\n");
+        return -1;
+    }
+    if (n < 1 || n > S.ns || !streams) {
+        fprintf(stderr, "qtts codec mstream: a push takes 1..%d streams (got %d)\n", S.ns, n);
+        return -1;
+    }
+    if (T < 1) {
+        fprintf(stderr, "qtts codec mstream: a push takes T >= 1 frames (got %d)\n", T);
+        return -1;
+    }
+    unsigned long long seen = 0;
+    for (int i = 0; i < n; ++i) {
+        const int s = streams[i];
+        if (s < 0 || s >= S.ns) {
+            fprintf(stderr, "qtts codec mstream: stream %d out of range (0..%d)\n", s, S.ns - 1);
+            return -1;
+        }
+        if (seen >> s & 1) {
+            fprintf(stderr, "qtts codec mstream: stream %d listed twice\n", s);
+            return -1;
+        }
+        seen |= 1ull << s;
+        if (S.pos0[s] != S.pos0[streams[0]]) {
+            fprintf(stderr, "qtts codec mstream: streams %d and %d are at different positions (%d, %d)\n", streams[0],
+                    s, S.pos0[streams[0]], S.pos0[s]);
+            return -1;
+        }
+    }
+    if (S.pos0[streams[0]] + T > S.max_frames) {
+        fprintf(stderr, "qtts codec mstream: %d frames exceed the stream capacity %d\n", S.pos0[streams[0]] + T,
+                S.max_frames);
+        return -1;
+    }
+    if (!m->xg_part) {   // freed with the codec state and not re-created (codec_mstream_begin re-creates it)
+        fprintf(stderr, "qtts codec mstream: split-K workspace missing (not begun after a state re-allocation)\n");
+        return -1;
+    }
+    return 0;
+}
+
+int codec_mstream_push(CodecModel *m, int n, const int *streams, const int *codes_base, const long long *code_off,
+                       int ldc_codes, int Ttot, float *const *host_out) {
+    CodecMStream &S = m->ms;
+    const qtts_dims_t &d = m->d;
+    if (codec_mstream_check(m, n, streams, Ttot)) return -1;
+    if (!codes_base || !code_off || !host_out || ldc_codes < d.cq) return -1;
+    for (int i = 0; i < n; ++i)
+        if (!host_out[i]) return -1;
+    hipStream_t st = m->st;
+    const int spf = ms_samples_per_frame(d);
+    S.hwav.resize((size_t)n * Ttot * spf);
+    // (the caller's index arrays are read by these copies: the stream is drained before returning)
+    int rc = 0;
+    if (hipMemcpyAsync(S.sid, streams, (size_t)n * 4, hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipMemcpyAsync(S.coff, code_off, (size_t)n * 8, hipMemcpyHostToDevice, st) != hipSuccess)
+        rc = -1;
+    int pos0 = S.pos0[streams[0]], hl = S.hl[streams[0]];
+    const int keepmax = d.cwin - 1;
+    size_t done = 0;   // floats of hwav filled: pass after pass, each [n][T * spf]
+    for (int t0 = 0; t0 < Ttot && !rc; t0 += S.tc) {
+        const int T = Ttot - t0 < S.tc ? Ttot - t0 : S.tc;
+        int L = 0;
+        if (ms_pass(m, n, codes_base, ldc_codes, t0, T, pos0, hl, &L) || L != T * spf ||
+            hipMemcpyAsync(S.hwav.data() + done, S.wav, (size_t)n * L * 4, hipMemcpyDeviceToHost, st) != hipSuccess) {
+            rc = -1;
+            break;
+        }
+        done += (size_t)n * L;
+        pos0 += T;
+        hl = hl + T < keepmax ? hl + T : keepmax;
+    }
+    if (hipStreamSynchronize(st) != hipSuccess) rc = -1;
+    if (rc) {
+        // a pass failed part-way: the carried state of these streams is no longer one position
+        fprintf(stderr, "qtts codec mstream: push failed; begin again before the next push\n");
+        S.active = false;
+        return -1;
+    }
+    done = 0;
+    for (int t0 = 0; t0 < Ttot; t0 += S.tc) {
+        const int T = Ttot - t0 < S.tc ? Ttot - t0 : S.tc;
+        const size_t L = (size_t)T * spf;
+        for (int i = 0; i < n; ++i) memcpy(host_out[i] + (size_t)t0 * spf, S.hwav.data() + done + i * L, L * 4);
+        done += n * L;
+    }
+    for (int i = 0; i < n; ++i) {
+        S.pos0[streams[i]] = pos0;
+        S.hl[streams[i]] = hl;
+    }
+    return Ttot * spf;
 }

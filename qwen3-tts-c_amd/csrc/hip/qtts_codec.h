@@ -35,6 +35,37 @@ struct CodecStream {
     std::vector<void *> allocs;
 };
 
+// n independent exact streaming states decoded in one launch sequence per
+// push (codec_mstream_*).  Carried per stream: the 21 history slots, the
+// per-layer K/V rows, pos0 and hl.  Shared by the streams of a push: the
+// activation scratch (one [C][hm + L] plane per stream, planes one after
+// another), the RoPE table and the index rows.
+struct CodecMStream {
+    bool active = false;
+    int ns = 0;                    // streams
+    int tc = 0;                    // frames per internal pass (<= 16, fewer where ns planes would pass the scratch budget)
+    int hm = 64;                   // left margin (columns) of every plane's rows
+    int max_frames = 0;
+    std::vector<int> pos0, hl;     // per stream: frames decoded, valid K/V history rows
+    std::vector<float *> hist;     // slot -> [ns][C][H]
+    std::vector<int> hist_c, hist_h;
+    float *kv = nullptr;           // [layers][2][ns][S][kvd]
+    int S = 0;                     // K/V rows per stream and layer: (win - 1) + tc
+    float *bufA = nullptr, *bufB = nullptr, *bufC = nullptr, *bufD = nullptr;
+    size_t buf_elems = 0;          // per stream
+    float *tx = nullptr, *txn = nullptr, *tq = nullptr, *tk = nullptr, *tv = nullptr, *tatt = nullptr, *tg = nullptr,
+          *tu = nullptr;           // [ns * tc] stacked rows
+    float *rvq_s = nullptr, *rvq_a = nullptr;
+    float *rope_cos = nullptr, *rope_sin = nullptr;
+    int rope_cap = 0;
+    int *sid = nullptr, *row_b = nullptr, *pos = nullptr;   // [ns], [ns * tc], [ns * tc]
+    long long *coff = nullptr;     // [ns] offset (ints) of each stream's codes from the push's base
+    float *wav = nullptr;          // [ns][tc * samples per frame], compact
+    std::vector<float> hwav;       // its host copy
+    size_t state_bytes = 0, scratch_bytes = 0;
+    std::vector<void *> allocs;
+};
+
 struct CodecModel {
     qtts_dims_t d{};
     hipStream_t st = nullptr;
@@ -57,6 +88,7 @@ struct CodecModel {
     float *xg_part = nullptr;                  // split-K workspace of the codec GEMMs
     size_t xg_part_elems = 0;
     CodecStream cs;
+    CodecMStream ms;
     // per-stage timing of codec_decode (the reference's -v -v "Codec stages
     // (ms)" line, c/qwen_tts_codec.c:743-746): events around rvq / preconv /
     // transformer / upsample / vocoder when `timing` is on
@@ -92,6 +124,19 @@ int codec_stream_push(CodecModel *m, const int *codes_dev, int ldc, int T, float
 // m->st only, nothing waited for)
 int codec_stream_push_to(CodecModel *m, const int *codes_dev, int ldc, int T, float *out, bool host);
 void codec_stream_free(CodecModel *m);
+// n independent streams, one launch sequence per push whatever n.  begin
+// (n_streams 1..64) resets every stream; a begin the active state already
+// covers re-uses its buffers.  push decodes T more frames of the n distinct
+// streams `streams` (all at the same position) from the device codes
+// codes_base + code_off[i] (rows of ldc ints), T * samples-per-frame floats
+// each into host_out[i].  Every refusal is -1 with a message before anything
+// is launched or changed.  pos: frames decoded of a stream, -1 for a bad one.
+int codec_mstream_begin(CodecModel *m, int n_streams, int max_frames, int chunk = 0);
+int codec_mstream_check(CodecModel *m, int n, const int *streams, int T);
+int codec_mstream_push(CodecModel *m, int n, const int *streams, const int *codes_base, const long long *code_off,
+                       int ldc, int T, float *const *host_out);
+int codec_mstream_pos(const CodecModel *m, int stream);
+void codec_mstream_free(CodecModel *m);
 
 // ---- generic fp32 implicit GEMM (exported for the kernel-level C-ABI) ----
 // C(m, n) = sum_k A(m, k) * B(k, n), fp32 products on v_mfma_f32_32x32x2_f32.
@@ -127,5 +172,15 @@ struct XGemm {
                                                // streaming history kept in the buffer's left margin)
     const float *wt = nullptr;                 // XB_CONV: the weights as [Kw][M][K/Kw] (k_conv's layout)
     int kz = 0;                                // k_conv split over input channels (set by the launcher)
+    // stream axis (the multi-stream codec; the defaults are the single-segment case).
+    // Conv forms (XB_CONV / XB_TCONV): nseg independent column segments of N
+    // columns each on grid x; segment s reads B + s*seg_ldb, writes C + s*seg_ldc
+    // (res + s*seg_ldres), so a tile never holds two segments and the taps left
+    // of column 0 read that segment's own margin.
+    // Linear forms over stacked rows (M = segments x seg_m): the operands that
+    // are laid out per segment, XA_TRANS's A and the XE_*_T outputs / res, take
+    // row m at segment m / seg_m, column m % seg_m (seg_lda / seg_ldc / seg_ldres).
+    int nseg = 1, seg_m = 0;
+    int seg_lda = 0, seg_ldb = 0, seg_ldc = 0, seg_ldres = 0;
 };
 int qtts_xgemm(const XGemm &g, hipStream_t st);

@@ -2375,6 +2375,58 @@ extern "C" int qtts_dev_codec_stream_push_host(qtts_dev_t *dv, const int *codes,
     return codec_stream_push(&dv->codec, dv->push_codes, dv->d.cq, T, host_out);
 }
 
+// ----------------------------------------------------------------- multi-stream codec (n exact streams, one pass)
+extern "C" int qtts_dev_codec_mstream_begin(qtts_dev_t *dv, int n_streams, int max_frames, int chunk_frames) {
+    if (!dv) return -1;
+    hipSetDevice(dv->device);
+    CKI(join_prime(dv));
+    CK(hipStreamSynchronize(dv->st));
+    return codec_mstream_begin(&dv->codec, n_streams, max_frames, chunk_frames);
+}
+
+extern "C" int qtts_dev_codec_mstream_push_slots(qtts_dev_t *dv, int n, const int *streams, const int *slots,
+                                                 int frame0, int T, float *const *host_out) {
+    if (!dv) return -1;
+    hipSetDevice(dv->device);
+    // every refusal before anything is enqueued
+    if (codec_mstream_check(&dv->codec, n, streams, T)) return -1;
+    if (!slots || !host_out || frame0 < 0 || frame0 + T > dv->max_frames + 1) {
+        fprintf(stderr, "qtts codec mstream: frames [%d, %d) are outside the slots' %d\n", frame0, frame0 + T,
+                dv->max_frames + 1);
+        return -1;
+    }
+    long long off[64];   // (the check bounds n by the begin's 1..64 streams)
+    for (int i = 0; i < n; ++i) {
+        if (slots[i] < 0 || slots[i] >= dv->nb) {
+            fprintf(stderr, "qtts codec mstream: slot %d out of range (0..%d)\n", slots[i], dv->nb - 1);
+            return -1;
+        }
+        off[i] = ((long long)slots[i] * (dv->max_frames + 1) + frame0) * dv->d.G;
+    }
+    CKI(join_prime(dv));
+    return codec_mstream_push(&dv->codec, n, streams, dv->codes, off, dv->d.G, T, host_out);
+}
+
+extern "C" int qtts_dev_codec_mstream_push_host(qtts_dev_t *dv, int n, const int *streams, const int *codes, int T,
+                                                float *const *host_out) {
+    if (!dv) return -1;
+    hipSetDevice(dv->device);
+    if (codec_mstream_check(&dv->codec, n, streams, T)) return -1;
+    if (!codes || !host_out) return -1;
+    CKI(join_prime(dv));
+    const size_t per = (size_t)T * dv->d.cq;
+    CKI(ensure_push_codes(dv, per * n));
+    long long off[64];   // (the check bounds n by the begin's 1..64 streams)
+    for (int i = 0; i < n; ++i) off[i] = (long long)(i * per);
+    CK(hipMemcpyAsync(dv->push_codes, codes, per * n * 4, hipMemcpyHostToDevice, dv->codec.st));
+    return codec_mstream_push(&dv->codec, n, streams, dv->push_codes, off, dv->d.cq, T, host_out);
+}
+
+extern "C" int qtts_dev_codec_mstream_pos(qtts_dev_t *dv, int stream) {
+    if (!dv) return -1;
+    return codec_mstream_pos(&dv->codec, stream);
+}
+
 // ----------------------------------------------------------------- codec overlapped with the decode
 // The exact streaming decode (codec_stream_*), run on a second stream while
 // the frame graphs continue on the context stream: each push waits (event)

@@ -11,7 +11,8 @@
  * Additions: --device N (HIP device), --batch N (N copies of the prompt in
  * one lock-step batch; the first one's audio is written), --stream N (exact
  * streaming decode: audio delivered after frame 0 and then every N frames;
- * prints "First packet: X ms"), --kv-cache fp32|bf16 (talker KV cache
+ * prints "First packet: X ms"; with --batch N every slot is streamed,
+ * qwen_tts_generate_batch_stream), --kv-cache fp32|bf16 (talker KV cache
  * elements, qwen_tts_set_kv_cache_dtype), --force-codes FILE / --dump-drawn
  * FILE (teacher-forced decode and its free-draw record, qwen_tts_force_codes /
  * qwen_tts_last_drawn), --seed-step K (with --batch N: slot b samples with seed
@@ -48,7 +49,8 @@ static void usage(const char *prog) {
             "  --device N (HIP device, default 0)   --batch N (lock-step batch of N copies, default 1)\n"
             "  --seed-step K (with --batch N: slot b samples with seed + b*K -- N takes of the prompt -- and\n"
             "                      every slot is written: slot 0 to -o's path, slot b to <stem>_<b>.wav)\n"
-            "  --stream N (streaming decode, audio chunks every N frames after the first)\n"
+            "  --stream N (streaming decode, audio chunks every N frames after the first; with --batch\n"
+            "                      every slot is streamed through the multi-stream codec)\n"
             "  --kv-cache fp32|bf16 (talker KV cache elements, default fp32; bf16 halves the cache,\n"
             "                      codes then no longer bit-exact against the reference)\n"
             "  --force-codes <file>  continue on these codes, 16 ints per frame as --ref-codes reads them\n"
@@ -434,7 +436,12 @@ int main(int argc, char **argv) {
                 armed = armed && qwen_tts_set_utterance_sampling(ctx, batch, per) == 0;
                 free(per);
             }
-            if ((!takes || armed) && qwen_tts_generate_batch(ctx, batch, tx, sp, lg, au, ns) == 0) {
+            /* --stream K with --batch N: every slot streamed (the chunks are dropped here: the
+             * returned audio is their concatenation; "First packet:" is printed at -v) */
+            if ((!takes || armed) &&
+                (stream_chunk > 0
+                     ? qwen_tts_generate_batch_stream(ctx, batch, tx, sp, lg, stream_chunk, NULL, NULL, au, ns)
+                     : qwen_tts_generate_batch(ctx, batch, tx, sp, lg, au, ns)) == 0) {
                 ra = au[0];
                 rn = ns[0];
                 for (int b = 0; b < batch; b++) total_samples += ns[b];

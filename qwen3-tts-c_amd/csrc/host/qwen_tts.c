@@ -904,11 +904,51 @@ int qwen_tts_tap_result(qwen_tts_ctx_t *ctx, int i, float *logits, int max_n, un
 /* ------------------------------------------------------------- generation */
 /* Runs nb utterances in lock-step frames.  Fills per-slot frame counts and
  * stop info; audio[i] decoded per slot.  Returns 0 on success. */
-typedef struct {                 /* streaming output of run_batch (nb == 1) */
-    qwen_tts_audio_cb cb;
+typedef struct {                 /* streaming output of run_batch */
+    qwen_tts_audio_cb cb;        /* nb == 1: the single exact stream */
     void *user;
     int chunk;
+    int multi;                   /* every slot through the multi-stream codec, chunks to bcb */
+    qwen_tts_batch_audio_cb bcb;
 } stream_t;
+
+static void free_bufs(float **v, int n) {
+    if (!v) return;
+    for (int i = 0; i < n; i++) free(v[i]);
+    free(v);
+}
+
+/* One poll's new frames of every slot through the multi-stream codec.  The
+ * slots decode in lock step and a slot that stopped was brought up to date by
+ * the poll that saw it stop, so every slot with new frames is at the same
+ * position; they differ only in how many frames are new (a short tail): one
+ * push per distinct count.  sdone[b]: frames of slot b delivered so far. */
+static int batch_stream_flush(qtts_dev_t *dev, int nb, const stream_t *stream, const int *ngen, int *sdone,
+                              float **sbufs, double *t_stream) {
+    int todo[QWEN_TTS_MAX_BATCH];
+    for (int b = 0; b < nb; b++) todo[b] = ngen[b] - sdone[b];
+    for (;;) {
+        int T = 0, n = 0, ids[QWEN_TTS_MAX_BATCH];
+        float *outs[QWEN_TTS_MAX_BATCH];
+        for (int b = 0; b < nb && !T; b++)
+            if (todo[b] > 0) T = todo[b];
+        if (!T) return 0;
+        for (int b = 0; b < nb; b++)
+            if (todo[b] == T) {
+                ids[n] = b;
+                outs[n++] = sbufs[b] + (size_t)sdone[b] * 1920;
+            }
+        const double t0 = now_ms();
+        const int r = qtts_dev_codec_mstream_push_slots(dev, n, ids, ids, sdone[ids[0]], T, outs);
+        if (r < 0) return -1;
+        *t_stream += now_ms() - t0;
+        for (int i = 0; i < n; i++) {
+            if (stream->bcb) stream->bcb(ids[i], outs[i], r, stream->user);
+            sdone[ids[i]] += T;
+            todo[ids[i]] = 0;
+        }
+    }
+}
 
 static int run_batch(qwen_tts_ctx_t *ctx, int nb, const char *const *texts, const char *const *speakers,
                      const char *const *languages, float **audio, int *samples, double t_start,
@@ -969,8 +1009,11 @@ static int run_batch(qwen_tts_ctx_t *ctx, int nb, const char *const *texts, cons
      * boundary.  They run on a second HIP stream in one chunk while the
      * prefill runs (qtts_dev_codec_stream_prime); later pushes wait for them. */
     const int sref = stream && vcs && vcs[0].ref_codes && vcs[0].n_ref > 0 ? vcs[0].n_ref : 0;
-    if (stream && (qtts_dev_codec_stream_begin_ex(dev, max_tokens + sref, sref) != 0 ||
-                   (sref && qtts_dev_codec_stream_prime(dev, vcs[0].ref_codes, sref) != 0)))
+    const int multi = stream && stream->multi;
+    if (multi) {
+        if (qtts_dev_codec_mstream_begin(dev, nb, max_tokens, 0) != 0) goto out;
+    } else if (stream && (qtts_dev_codec_stream_begin_ex(dev, max_tokens + sref, sref) != 0 ||
+                          (sref && qtts_dev_codec_stream_prime(dev, vcs[0].ref_codes, sref) != 0)))
         goto out;
     double t_prefill = now_ms();
     if (qtts_dev_prefill(dev) != 0) goto out;
@@ -986,7 +1029,15 @@ static int run_batch(qwen_tts_ctx_t *ctx, int nb, const char *const *texts, cons
     float *sbuf = NULL;
     int streamed = 0;
     double t_stream = 0;
-    if (stream) {
+    float **sbufs = NULL;   /* multi: one buffer per slot, and the frames delivered of each */
+    int *sdone = NULL;
+    if (multi) {
+        sbufs = (float **)calloc(nb, sizeof(float *));
+        sdone = (int *)calloc(nb, sizeof(int));
+        int ok = sbufs && sdone;
+        for (int b = 0; b < nb && ok; b++) ok = (sbufs[b] = (float *)malloc((size_t)max_tokens * 1920 * sizeof(float))) != NULL;
+        if (!ok) { free_bufs(sbufs, nb); free(sdone); free(stopped); free(ngen); free(sstep); goto out; }
+    } else if (stream) {
         sbuf = (float *)malloc((size_t)max_tokens * 1920 * sizeof(float));
         if (!sbuf) { free(stopped); free(ngen); free(sstep); goto out; }
     }
@@ -997,7 +1048,7 @@ static int run_batch(qwen_tts_ctx_t *ctx, int nb, const char *const *texts, cons
     const int lagged = fixed == 0 && !stream;
     int step = 0;
     for (; step < max_tokens; step++) {
-        if (qtts_dev_frame(dev, step) != 0) { free(sbuf); free(stopped); free(ngen); free(sstep); goto out; }
+        if (qtts_dev_frame(dev, step) != 0) { free_bufs(sbufs, nb); free(sdone); free(sbuf); free(stopped); free(ngen); free(sstep); goto out; }
         if (step == 0) {
             qtts_dev_poll(dev, NULL, NULL, NULL);
             ctx->perf_first_frame_ms = now_ms() - t_start;
@@ -1006,7 +1057,7 @@ static int run_batch(qwen_tts_ctx_t *ctx, int nb, const char *const *texts, cons
         if (lagged) {   /* EOS mode: frame step is queued; stop once every slot had stopped by frame step - 1 */
             int done = 0;
             if (step >= 1 && qtts_dev_frame_done(dev, step - 1, &done) != 0) {
-                free(sbuf); free(stopped); free(ngen); free(sstep); goto out;
+                free_bufs(sbufs, nb); free(sdone); free(sbuf); free(stopped); free(ngen); free(sstep); goto out;
             }
             if (qwen_tts_verbose >= 1 && step > 0 && step % 10 == 0)
                 fprintf(stderr, "\r  Token %d (%.1f ms/token)...", step, (now_ms() - t_gen) / step);
@@ -1016,11 +1067,18 @@ static int run_batch(qwen_tts_ctx_t *ctx, int nb, const char *const *texts, cons
         const int want_stream = stream && (step == 0 || step + 1 - streamed >= stream->chunk || step + 1 == max_tokens);
         if (want_stream || (poll_every && ((step + 1) % poll_every == 0 || step + 1 == max_tokens))) {
             qtts_dev_poll(dev, stopped, ngen, sstep);
-            if (stream && ngen[0] > streamed) {
+            if (multi) {
+                if (batch_stream_flush(dev, nb, stream, ngen, sdone, sbufs, &t_stream) != 0) {
+                    free_bufs(sbufs, nb); free(sdone); free(sbuf); free(stopped); free(ngen); free(sstep); goto out;
+                }
+                if (streamed == 0) ctx->perf_first_packet_ms = now_ms() - t_start;
+                for (int b = 0; b < nb; b++)
+                    if (sdone[b] > streamed) streamed = sdone[b];
+            } else if (stream && ngen[0] > streamed) {
                 const double t0 = now_ms();
                 const int n = qtts_dev_codec_stream_push_slot(dev, 0, streamed, ngen[0] - streamed,
                                                               sbuf + (size_t)streamed * 1920);
-                if (n < 0) { free(sbuf); free(stopped); free(ngen); free(sstep); goto out; }
+                if (n < 0) { free_bufs(sbufs, nb); free(sdone); free(sbuf); free(stopped); free(ngen); free(sstep); goto out; }
                 t_stream += now_ms() - t0;
                 if (stream->cb) stream->cb(sbuf + (size_t)streamed * 1920, n, stream->user);
                 if (streamed == 0) ctx->perf_first_packet_ms = now_ms() - t_start;
@@ -1034,11 +1092,16 @@ static int run_batch(qwen_tts_ctx_t *ctx, int nb, const char *const *texts, cons
         }
     }
     qtts_dev_poll(dev, stopped, ngen, sstep);
-    if (stream && ngen[0] > streamed) {
+    if (multi) {
+        if (batch_stream_flush(dev, nb, stream, ngen, sdone, sbufs, &t_stream) != 0) {
+            free_bufs(sbufs, nb); free(sdone); free(sbuf); free(stopped); free(ngen); free(sstep); goto out;
+        }
+        if (streamed == 0) ctx->perf_first_packet_ms = now_ms() - t_start;
+    } else if (stream && ngen[0] > streamed) {
         const double t0 = now_ms();
         const int n = qtts_dev_codec_stream_push_slot(dev, 0, streamed, ngen[0] - streamed,
                                                       sbuf + (size_t)streamed * 1920);
-        if (n < 0) { free(sbuf); free(stopped); free(ngen); free(sstep); goto out; }
+        if (n < 0) { free_bufs(sbufs, nb); free(sdone); free(sbuf); free(stopped); free(ngen); free(sstep); goto out; }
         t_stream += now_ms() - t0;
         if (stream->cb) stream->cb(sbuf + (size_t)streamed * 1920, n, stream->user);
         if (streamed == 0) ctx->perf_first_packet_ms = now_ms() - t_start;
@@ -1067,7 +1130,16 @@ static int run_batch(qwen_tts_ctx_t *ctx, int nb, const char *const *texts, cons
     }
     double t_codec = now_ms();
     rc = 0;
-    if (stream) {   /* the streamed chunks already are the utterance */
+    if (multi) {    /* each slot's chunks already are its utterance */
+        for (int b = 0; b < nb; b++) {
+            audio[b] = sbufs[b];
+            samples[b] = sdone[b] * 1920;
+            if (sdone[b] <= 0) { free(sbufs[b]); audio[b] = NULL; rc = -1; }
+        }
+        free(sbufs);
+        free(sdone);
+        ctx->perf_codec_ms = t_stream;
+    } else if (stream) {   /* the streamed chunks already are the utterance */
         audio[0] = sbuf;
         samples[0] = streamed * 1920;
         if (streamed <= 0) { free(sbuf); audio[0] = NULL; rc = -1; }
@@ -1739,6 +1811,36 @@ float *qwen_tts_generate_stream(qwen_tts_ctx_t *ctx, const char *text, const cha
     }
     *out_samples = n;
     return audio;
+}
+
+int qwen_tts_generate_batch_stream(qwen_tts_ctx_t *ctx, int nb, const char *const *texts,
+                                   const char *const *speakers, const char *const *languages, int chunk_frames,
+                                   qwen_tts_batch_audio_cb cb, void *userdata, float **out_audio, int *out_samples) {
+    if (!ctx || nb < 1 || !texts || !out_audio || !out_samples) return -1;
+    if (batch_refused(ctx, "qwen_tts_generate_batch_stream", nb)) return -1;
+    const double t_start = now_ms();
+    stream_t st = {NULL, userdata, chunk_frames > 0 ? chunk_frames : 1, 1, cb};
+    ctx->perf_first_packet_ms = 0;
+    const int rc = run_batch(ctx, nb, texts, speakers, languages, out_audio, out_samples, t_start, &st, NULL);
+    if (rc == 0 && qwen_tts_verbose >= 1) {
+        double secs = 0;
+        for (int b = 0; b < nb; b++) secs += (double)out_samples[b] / QWEN_TTS_SAMPLE_RATE;
+        fprintf(stderr, "First packet: %.1f ms\n", ctx->perf_first_packet_ms);
+        fprintf(stderr, "Total: %.1f ms (%.2f s audio over %d utterances, %.2fx realtime)\n", ctx->perf_total_ms, secs,
+                nb, secs / (ctx->perf_total_ms / 1000.0));
+    }
+    return rc;
+}
+
+int qwen_tts_codec_mstream_begin(qwen_tts_ctx_t *ctx, int n_streams, int max_frames) {
+    if (!ctx || !ctx->hip) return -1;
+    return qtts_dev_codec_mstream_begin((qtts_dev_t *)ctx->hip, n_streams, max_frames, 0);
+}
+
+int qwen_tts_codec_mstream_push(qwen_tts_ctx_t *ctx, int n, const int *streams, const int *codes, int time_steps,
+                                float *const *out) {
+    if (!ctx || !ctx->hip || !streams || !codes || !out) return -1;
+    return qtts_dev_codec_mstream_push_host((qtts_dev_t *)ctx->hip, n, streams, codes, time_steps, out);
 }
 
 int qwen_tts_codec_stream_begin(qwen_tts_ctx_t *ctx, int max_frames) {

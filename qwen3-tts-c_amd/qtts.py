@@ -26,6 +26,7 @@ _ip = C.POINTER(C.c_int)
 PROGRESS_CB = C.CFUNCTYPE(None, C.c_int, C.c_int, C.c_void_p)
 QUEUE_NEXT_CB = C.CFUNCTYPE(C.c_int, C.c_void_p)
 AUDIO_CB = C.CFUNCTYPE(None, C.POINTER(C.c_float), C.c_int, C.c_void_p)
+BATCH_AUDIO_CB = C.CFUNCTYPE(None, C.c_int, C.POINTER(C.c_float), C.c_int, C.c_void_p)
 
 
 class Config(C.Structure):  # qwen_tts_config_t (include/qwen_tts.h)
@@ -112,6 +113,9 @@ EXPORTS = [
     "qtts_hip_batch_matvec_case", "qtts_hip_gemv_wide_launches", "qtts_hip_batch_matvec_plan",
     "qwen_tts_sampling_defaults", "qwen_tts_set_utterance_sampling", "qtts_dev_slot_params",
     "qtts_hip_sample_slot_launches", "qtts_hip_sample_top_k_rows",
+    "qwen_tts_generate_batch_stream", "qwen_tts_codec_mstream_begin", "qwen_tts_codec_mstream_push",
+    "qtts_dev_codec_mstream_begin", "qtts_dev_codec_mstream_push_slots", "qtts_dev_codec_mstream_push_host",
+    "qtts_dev_codec_mstream_pos", "qtts_hip_xgemm_seg_case",
 ]
 
 MAX_BATCH = 64   # QWEN_TTS_MAX_BATCH / QTTS_HIP_MAX_BATCH: lock-step slots per context
@@ -278,6 +282,21 @@ def lib():
                                                       C.POINTER(C.c_char_p), C.c_int, C.POINTER(C.c_void_p), _ip]
     L.qwen_tts_codec_stream_begin.argtypes = [C.POINTER(Ctx), C.c_int]
     L.qwen_tts_codec_stream_push.argtypes = [C.POINTER(Ctx), _ip, C.c_int, _fp]
+    # (an older build named by QTTS_LIB for a same-box A/B has no multi-stream entries; build() checks EXPORTS)
+    if hasattr(L, "qwen_tts_generate_batch_stream"):
+        L.qwen_tts_generate_batch_stream.argtypes = [C.POINTER(Ctx), C.c_int, C.POINTER(C.c_char_p),
+                                                     C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.c_int,
+                                                     BATCH_AUDIO_CB, C.c_void_p, C.POINTER(C.c_void_p), _ip]
+        L.qwen_tts_codec_mstream_begin.argtypes = [C.POINTER(Ctx), C.c_int, C.c_int]
+        L.qwen_tts_codec_mstream_push.argtypes = [C.POINTER(Ctx), C.c_int, _ip, _ip, C.c_int, C.POINTER(_fp)]
+        L.qtts_dev_codec_mstream_begin.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
+        L.qtts_dev_codec_mstream_push_slots.argtypes = [C.c_void_p, C.c_int, _ip, _ip, C.c_int, C.c_int,
+                                                        C.POINTER(_fp)]
+        L.qtts_dev_codec_mstream_push_host.argtypes = [C.c_void_p, C.c_int, _ip, _ip, C.c_int, C.POINTER(_fp)]
+        L.qtts_dev_codec_mstream_pos.argtypes = [C.c_void_p, C.c_int]
+        L.qtts_hip_xgemm_seg_case.restype = C.c_int
+        L.qtts_hip_xgemm_seg_case.argtypes = [C.POINTER(XGemmDesc), C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_int,
+                                              _ip, _ip, C.c_void_p]
     L.qwen_tts_speaker_embedding.restype = C.c_void_p
     L.qwen_tts_speaker_embedding.argtypes = [C.POINTER(Ctx), _fp, C.c_int, _ip]
     L.qwen_tts_encode_audio.restype = C.c_void_p
@@ -807,6 +826,66 @@ class QwenTTS:
             outs.append(o)
         return outs
 
+    def generate_batch_stream(self, id_lists, speakers=None, languages=None, chunk_frames=4, on_chunk=None):
+        """generate_batch with every utterance streamed (qwen_tts_generate_batch_stream):
+        on_chunk(i, np.ndarray) gets utterance i's chunks as they are decoded.
+        Returns (rc, [audio])."""
+        nb = len(id_lists)
+        tx = (C.c_char_p * nb)(*[",".join(str(int(i)) for i in ids).encode() for ids in id_lists])
+        sp = (C.c_char_p * nb)(*[(s.encode() if s else None) for s in (speakers or [None] * nb)])
+        lg = (C.c_char_p * nb)(*[(s.encode() if s else None) for s in (languages or [None] * nb)])
+        out = (C.c_void_p * nb)()
+        ns = (C.c_int * nb)()
+
+        def _cb(i, p, k, u):
+            if on_chunk is not None:
+                on_chunk(int(i), np.ctypeslib.as_array(p, shape=(k,)).copy())
+        cb = BATCH_AUDIO_CB(_cb)
+        rc = lib().qwen_tts_generate_batch_stream(self.ctx, nb, tx, sp, lg, int(chunk_frames), cb, None, out, ns)
+        self._last_nb = nb
+        return rc, [_take_audio(out[i], ns[i]) for i in range(nb)]
+
+    def codec_mstream_begin(self, n_streams, max_frames=4096):
+        """(re)start n_streams independent exact codec streams; 0 or -1"""
+        return lib().qwen_tts_codec_mstream_begin(self.ctx, int(n_streams), int(max_frames))
+
+    def codec_mstream_push(self, streams, codes):
+        """T more frames of the distinct streams `streams` (all at one position),
+        codes [n, T, 16]: [T * 1920 samples] per stream, or None where the
+        library refuses the push (-1; nothing decoded)."""
+        st = np.ascontiguousarray(streams, np.int32)
+        c = np.ascontiguousarray(codes, np.int32)
+        n = len(st)
+        T = c.shape[1] if c.ndim == 3 else 0
+        outs = [np.zeros(max(T, 1) * 1920, np.float32) for _ in range(n)]
+        po = (_fp * max(n, 1))(*[o.ctypes.data_as(_fp) for o in outs])
+        k = lib().qwen_tts_codec_mstream_push(self.ctx, n, st.ctypes.data_as(_ip), c.ctypes.data_as(_ip), T, po)
+        if k < 0:
+            return None
+        if k != T * 1920:
+            raise RuntimeError(f"codec mstream push returned {k}")
+        return outs
+
+    def codec_mstream_pos(self, stream):
+        """frames decoded so far of a stream (-1: no such stream)"""
+        return lib().qtts_dev_codec_mstream_pos(self.c.hip, int(stream))
+
+    def codec_mstream(self, chunk_lists, max_frames=4096):
+        """Exact incremental decode of several code sequences at once:
+        chunk_lists[s] is stream s's list of [t, 16] code arrays, the same t
+        schedule for every stream.  Returns per stream its list of audio chunks."""
+        n = len(chunk_lists)
+        if self.codec_mstream_begin(n, max_frames) != 0:
+            raise RuntimeError("codec mstream begin failed")
+        outs = [[] for _ in range(n)]
+        for k in range(len(chunk_lists[0])):
+            o = self.codec_mstream_push(np.arange(n), np.stack([np.asarray(cl[k], np.int32) for cl in chunk_lists]))
+            if o is None:
+                raise RuntimeError("codec mstream push failed")
+            for s in range(n):
+                outs[s].append(o[s])
+        return outs
+
     def last_codes(self):
         G = self.cfg.num_code_groups
         n = self.c.last_frames
@@ -1086,6 +1165,19 @@ class Kernels:
         if rc == 1:
             return None
         _ok(rc, "xgemm_case")
+        return path.value, splits.value
+
+    @staticmethod
+    def xgemm_seg_case(desc, nseg, seg_ldb, seg_ldc, part_elems=0, force_path=-1):
+        """The same over the conv forms' stream axis (qtts_hip_xgemm_seg_case):
+        nseg column segments of desc.N columns in one launch, segment s at
+        B + s * seg_ldb -> C + s * seg_ldc (floats)."""
+        path, splits = C.c_int(-1), C.c_int(0)
+        rc = lib().qtts_hip_xgemm_seg_case(C.byref(desc), int(nseg), int(seg_ldb), int(seg_ldc), part_elems,
+                                           force_path, C.byref(path), C.byref(splits), _stream())
+        if rc == 1:
+            return None
+        _ok(rc, "xgemm_seg_case")
         return path.value, splits.value
 
     @staticmethod
