@@ -311,6 +311,25 @@ int qtts_dev_codec_mstream_push_slots(qtts_dev_t *dev, int n, const int *streams
 int qtts_dev_codec_mstream_push_host(qtts_dev_t *dev, int n, const int *streams, const int *codes, int T,
                                      float *const *host_out);
 int qtts_dev_codec_mstream_pos(qtts_dev_t *dev, int stream);
+/* The streams of one push at independent positions (the work queue: a
+ * refilled slot's stream restarts at 0 while its neighbours continue).  Still
+ * one launch sequence and one T for every stream of the push; each stacked
+ * row takes its RoPE row, its K/V cache row and its attention window from its
+ * own stream's position.  _push_host_any and _push_slots_at are _push_host and
+ * _push_slots without the same-position refusal: the capacity is checked per
+ * stream (a push in which any listed stream would pass max_frames is refused
+ * and names that stream), and _push_slots_at takes slot slots[i]'s frames
+ * [frame0[i], frame0[i] + T).  With every stream at one position they decode
+ * bit for bit what _push_host / _push_slots decode.
+ * reset: one stream back to position 0 (zero conv histories, no K/V rows),
+ * stream-ordered, its neighbours untouched; 0, or -1 with a message and
+ * nothing changed for a bad stream index or no begin (also after a
+ * re-allocation of the context's state). */
+int qtts_dev_codec_mstream_push_slots_at(qtts_dev_t *dev, int n, const int *streams, const int *slots,
+                                         const int *frame0, int T, float *const *host_out);
+int qtts_dev_codec_mstream_push_host_any(qtts_dev_t *dev, int n, const int *streams, const int *codes, int T,
+                                         float *const *host_out);
+int qtts_dev_codec_mstream_reset(qtts_dev_t *dev, int stream);
 
 /* The same exact streaming decode overlapped with the decode loop: it runs on
  * a second (low-priority) HIP stream; push orders itself after the frames

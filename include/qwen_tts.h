@@ -453,10 +453,9 @@ int qwen_tts_codec_stream_push(qwen_tts_ctx_t *ctx, const int *codes, int time_s
  * out_audio[i] (malloc'd, caller frees) is the concatenation of utterance i's
  * chunks.  perf_first_packet_ms: entry -> the last callback of the first
  * chunks; perf_codec_ms: time in the codec pushes (perf_talker_ms excludes it).
- * qwen_tts_generate_queue and the voice-clone batch calls do not stream: the
- * queue needs streams at independent positions and voice clone a ragged
- * priming of the reference frames, which the multi-stream codec does not do
- * yet. */
+ * The work queue streams through qwen_tts_generate_queue_stream below.  The
+ * voice-clone batch calls do not stream: they need a ragged priming of the
+ * reference frames, which the multi-stream codec does not do yet. */
 typedef void (*qwen_tts_batch_audio_cb)(int utterance, const float *pcm, int n_samples, void *userdata);
 int qwen_tts_generate_batch_stream(qwen_tts_ctx_t *ctx, int nb, const char *const *texts,
                                    const char *const *speakers, const char *const *languages, int chunk_frames,
@@ -470,6 +469,37 @@ int qwen_tts_generate_batch_stream(qwen_tts_ctx_t *ctx, int nb, const char *cons
 int qwen_tts_codec_mstream_begin(qwen_tts_ctx_t *ctx, int n_streams, int max_frames);
 int qwen_tts_codec_mstream_push(qwen_tts_ctx_t *ctx, int n, const int *streams, const int *codes, int time_steps,
                                 float *const *out);
+/* The same push for streams at different positions: arguments, return value
+ * and refusals are qwen_tts_codec_mstream_push's without the same-position
+ * one, and the capacity is each stream's own (a push in which any listed
+ * stream would pass max_frames is refused, naming it; no stream changes).
+ * qwen_tts_codec_mstream_reset puts one stream back to position 0 and leaves
+ * the others alone: 0, or -1 with a message and nothing changed for a bad
+ * stream, a reset without begin or after a re-allocation of the state. */
+int qwen_tts_codec_mstream_push_any(qwen_tts_ctx_t *ctx, int n, const int *streams, const int *codes, int time_steps,
+                                    float *const *out);
+int qwen_tts_codec_mstream_reset(qwen_tts_ctx_t *ctx, int stream);
+/* qwen_tts_generate_queue with every utterance streamed.  Prompts, admission
+ * (`next`), refill, retire, tail compaction, the ctx->queue_* results,
+ * per-utterance sampling and the refusal (and disarming) of armed forcing are
+ * the queue's; the codes are the queue's bit for bit.  Each slot's frames go
+ * through a multi-stream codec stream of its own as they are decoded, all due
+ * slots in one push whatever their positions: cb(u, pcm, n, cb_userdata), u
+ * the utterance's index in input order, after its frame 0 (1920 samples),
+ * then one short chunk up to the call's cadence (every chunk_frames frames of
+ * the loop, for all slots at once), then chunk_frames frames each, then its
+ * tail.  A slot that stops is flushed before its slot is refilled and its
+ * stream reset; an utterance gets no callback after its last frame.
+ * out_audio[u] (malloc'd, caller frees) is the concatenation of u's chunks; no
+ * codec pass runs at the end.  perf_first_packet_ms: entry -> the first
+ * callback of the call; perf_codec_ms: time in the pushes (perf_talker_ms
+ * excludes it).  A caller that wants the first-packet latency per utterance
+ * stamps the admission in `next` and the first chunk in `cb`.  A failed push
+ * fails the call with -1 (nothing returned). */
+int qwen_tts_generate_queue_stream(qwen_tts_ctx_t *ctx, int nq, const char *const *texts, const char *const *speakers,
+                                   const char *const *languages, int nb, qwen_tts_queue_next_cb next, void *userdata,
+                                   int chunk_frames, qwen_tts_batch_audio_cb cb, void *cb_userdata, float **out_audio,
+                                   int *out_samples);
 
 /* Text input (the reference's TODO at c/qwen_tts.c:1071-1077,
  * its browser front end tokenizes with @huggingface/transformers,

@@ -2329,13 +2329,17 @@ __global__ void k_hist_ms(float *hist, const int *sid, float *x, size_t seg, int
     else xp[h - H] = *hp;
 }
 // rotate-half RoPE (k_rope_rows' arithmetic) of the stacked q rows in place and
-// of the k rows into stream sid[s]'s cache at row hl + t; the v rows beside them
+// of the k rows into their stream's cache; the v rows beside them.  Row
+// r = s * T + t of the pass rotates with table row pos0[s] + t and lands at
+// cache row hl[s] + t of stream sid[s]: the streams of a pass are at
+// independent positions (cs / sn: the whole table, row 0 first)
 __global__ void k_rope_kv_ms(float *q, int hid, int nh, const float *k, const float *v, int kvd, int nkv, int hd,
-                             const float *cs, const float *sn, int T, const int *sid, int hl, float *kc, float *vc,
-                             int S) {
+                             const float *cs, const float *sn, int T, const int *sid, const int *pos0, const int *hl,
+                             float *kc, float *vc, int S) {
     const int r = blockIdx.x, s = r / T, t = r - s * T;
+    const int p0 = pos0[s], h0 = hl[s], sd = sid[s];   // the stream's values, uniform over the workgroup
     const int half = hd / 2;
-    const float *c = cs + (size_t)t * hd, *sv = sn + (size_t)t * hd;
+    const float *c = cs + (size_t)(p0 + t) * hd, *sv = sn + (size_t)(p0 + t) * hd;
     for (int i = threadIdx.x; i < nh * half; i += blockDim.x) {
         const int h = i / half, e = i - h * half;
         float *qq = q + (size_t)r * hid + h * hd;
@@ -2343,7 +2347,7 @@ __global__ void k_rope_kv_ms(float *q, int hid, int nh, const float *k, const fl
         qq[e] = a * c[e] - bb * sv[e];
         qq[e + half] = bb * c[e + half] + a * sv[e + half];
     }
-    const size_t dst = ((size_t)sid[s] * S + hl + t) * kvd;
+    const size_t dst = ((size_t)sd * S + h0 + t) * kvd;
     for (int i = threadIdx.x; i < nkv * half; i += blockDim.x) {
         const int h = i / half, e = i - h * half;
         const float *kk = k + (size_t)r * kvd + h * hd;
@@ -2354,23 +2358,38 @@ __global__ void k_rope_kv_ms(float *q, int hid, int nh, const float *k, const fl
     }
     for (int i = threadIdx.x; i < kvd; i += blockDim.x) vc[dst + i] = v[(size_t)r * kvd + i];
 }
-// the window keep-shift of every layer's K and V of every stream of the push
-// in one launch: rows [shift, shift + keep) -> [0, keep).  One thread per
-// column walks its rows upwards (row i is read before any thread writes it:
-// the thread owns the column), so no second buffer.  kv: [nl2][streams][S][kvd]
-__global__ void k_kv_shift_ms(float *kv, const int *sid, int n, int ns, int S, int kvd, int nl2, int shift, int keep) {
-    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= (size_t)nl2 * n * kvd) return;
-    const int col = (int)(idx % kvd), s = (int)((idx / kvd) % n), l2 = (int)(idx / ((size_t)kvd * n));
-    float *p = kv + (((size_t)l2 * ns + sid[s]) * S) * kvd + col;
+// the window keep-shift of every layer's K and V of every stream of the pass
+// in one launch (grid: column blocks x streams of the pass x layers * 2).
+// Stream s holds hl[s] + T rows after the pass and keeps the last
+// keep = min(hl[s] + T, keepmax): rows [shift, shift + keep) -> [0, keep); a
+// stream whose window is not full yet (shift 0) moves nothing.  One thread
+// per column walks its rows upwards (row i is read before any thread writes
+// it: the thread owns the column), so no second buffer.
+// kv: [nl2][streams][S][kvd]
+__global__ void k_kv_shift_ms(float *kv, const int *sid, const int *hl, int ns, int S, int kvd, int T, int keepmax) {
+    const int s = blockIdx.y, l2 = blockIdx.z;
+    const int tot = hl[s] + T, sd = sid[s];            // uniform over the workgroup
+    const int keep = tot < keepmax ? tot : keepmax, shift = tot - keep;
+    if (shift == 0) return;
+    const int col = blockIdx.x * 256 + threadIdx.x;
+    if (col >= kvd) return;
+    float *p = kv + (((size_t)l2 * ns + sd) * S) * kvd + col;
     for (int i = 0; i < keep; ++i) p[(size_t)i * kvd] = p[(size_t)(i + shift) * kvd];
 }
-// attention rows of a pass: stacked row r = s * T + t -> cache sid[s], position hl + t
-__global__ void k_ms_index(const int *sid, int n, int T, int hl, int *row_b, int *pos) {
+// attention rows of a pass: stacked row r = s * T + t -> cache sid[s], position hl[s] + t
+__global__ void k_ms_index(const int *sid, const int *hl, int n, int T, int *row_b, int *pos) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n * T) return;
-    row_b[i] = sid[i / T];
-    pos[i] = hl + i % T;
+    const int s = i / T;
+    row_b[i] = sid[s];
+    pos[i] = hl[s] + (i - s * T);
+}
+// reset of one stream: its [C][H] block of every history slot to zero in one
+// launch (grid y = slot; base / elems: the slots' device table)
+__global__ void k_hist_reset_ms(float *const *base, const int *elems, int stream) {
+    const int n = elems[blockIdx.y];
+    float *p = base[blockIdx.y] + (size_t)stream * n;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) p[i] = 0.f;
 }
 // k_dwconv per plane (grid y)
 __global__ void k_dwconv_ms(const float *x, size_t segx, int ldx, int tmin, const float *w, const float *b, int C,
@@ -2462,8 +2481,10 @@ int ms_stconv(CodecModel *m, int n, int slot, float *x, int ldx, int ci, int L, 
 }
 
 // the transformer over the stacked rows M = n * T of a pass; pc / out: planes
-// [lat][ldp] / [lat][ldo]; every stream of the pass is at pos0 with hl history rows
-int ms_transformer(CodecModel *m, int n, const float *pc, int ldp, int T, float *out, int ldo, int pos0, int hl) {
+// [lat][ldp] / [lat][ldo]; stream i of the pass is at dpos0[i] with dhl[i] history
+// rows (device arrays); shifts: some stream's window runs over in this pass
+int ms_transformer(CodecModel *m, int n, const float *pc, int ldp, int T, float *out, int ldo, const int *dpos0,
+                   const int *dhl, bool shifts) {
     CodecMStream &S = m->ms;
     const qtts_dims_t &d = m->d;
     const int lat = d.clat, hid = d.chid, nh = d.cheads, nkv = d.ckv, hd = hid / nh, kvd = nkv * hd, I = d.cinter;
@@ -2477,8 +2498,7 @@ int ms_transformer(CodecModel *m, int n, const float *pc, int ldp, int T, float 
     g.emode = g.bias ? XE_BIAS_N : XE_STORE;
     g.seg_m = T; g.seg_lda = lat * ldp;
     KCK(xgm(m, g, st));
-    const float *cs = S.rope_cos + (size_t)pos0 * hd, *sn = S.rope_sin + (size_t)pos0 * hd;
-    hipLaunchKernelGGL(k_ms_index, dim3((M + 255) / 256), dim3(256), 0, st, S.sid, n, T, hl, S.row_b, S.pos);
+    hipLaunchKernelGGL(k_ms_index, dim3((M + 255) / 256), dim3(256), 0, st, S.sid, dhl, n, T, S.row_b, S.pos);
     const size_t lsz = (size_t)S.ns * S.S * kvd;   // one layer's K (or V) of every stream
     for (int l = 0; l < d.clayers; ++l) {
         const std::string p = P + "layers." + std::to_string(l) + ".";
@@ -2488,8 +2508,8 @@ int ms_transformer(CodecModel *m, int n, const float *pc, int ldp, int T, float 
         KCK(xgm(m, lin(S.txn, M, hid, cw(m, p + "self_attn.q_proj.weight"), hid, S.tq, XE_STORE), st));
         KCK(xgm(m, lin(S.txn, M, hid, cw(m, p + "self_attn.k_proj.weight"), kvd, S.tk, XE_STORE), st));
         KCK(xgm(m, lin(S.txn, M, hid, cw(m, p + "self_attn.v_proj.weight"), kvd, S.tv, XE_STORE), st));
-        hipLaunchKernelGGL(k_rope_kv_ms, dim3(M), dim3(256), 0, st, S.tq, hid, nh, S.tk, S.tv, kvd, nkv, hd, cs, sn, T,
-                           S.sid, hl, kcl, vcl, S.S);
+        hipLaunchKernelGGL(k_rope_kv_ms, dim3(M), dim3(256), 0, st, S.tq, hid, nh, S.tk, S.tv, kvd, nkv, hd, S.rope_cos,
+                           S.rope_sin, T, S.sid, dpos0, dhl, kcl, vcl, S.S);
         AttnArgs a;
         a.mode = 1; a.qkv = S.tq; a.ld_qkv = hid; a.kc = kcl; a.vc = vcl; a.S = S.S; a.pos = S.pos;
         a.row_b = S.row_b; a.NH = nh; a.KV = nkv; a.HD = hd; a.out = S.tatt; a.ld_out = hid;
@@ -2512,13 +2532,10 @@ int ms_transformer(CodecModel *m, int n, const float *pc, int ldp, int T, float 
         dn.vec = ls2;
         KCK(xgm(m, dn, st));
     }
-    // keep the last window-1 rows of every layer for the next pass
-    const int tot = hl + T, keep = tot < keepmax ? tot : keepmax;
-    if (keep > 0 && tot > keep) {
-        const size_t cols = (size_t)2 * d.clayers * n * kvd;
-        hipLaunchKernelGGL(k_kv_shift_ms, dim3((unsigned)((cols + 255) / 256)), dim3(256), 0, st, S.kv, S.sid, n, S.ns,
-                           S.S, kvd, 2 * d.clayers, tot - keep, keep);
-    }
+    // keep the last window-1 rows of every layer for the next pass (each stream by its own count)
+    if (keepmax > 0 && shifts)
+        hipLaunchKernelGGL(k_kv_shift_ms, dim3((kvd + 255) / 256, n, 2 * d.clayers), dim3(256), 0, st, S.kv, S.sid, dhl,
+                           S.ns, S.S, kvd, T, keepmax);
     const float *fn = cw(m, P + "norm.weight");
     const float *xin = S.tx;
     if (fn) {
@@ -2572,7 +2589,8 @@ int ms_samples_per_frame(const qtts_dims_t &d) {
 }
 
 // one pass: T <= tc frames of the n streams of the push, audio to S.wav [n][T * spf]
-int ms_pass(CodecModel *m, int n, const int *codes, int ldc_codes, int t0, int T, int pos0, int hl, int *L_out) {
+int ms_pass(CodecModel *m, int n, const int *codes, int ldc_codes, int t0, int T, const int *dpos0, const int *dhl,
+            bool shifts, int *L_out) {
     CodecMStream &S = m->ms;
     const qtts_dims_t &d = m->d;
     hipStream_t st = m->st;
@@ -2590,7 +2608,7 @@ int ms_pass(CodecModel *m, int n, const int *codes, int ldc_codes, int t0, int T
     KCK(ms_sconv(m, n, 0, A, ld, d.ccbdim, L, "decoder.pre_conv.conv.weight", "decoder.pre_conv.conv.bias", lat, 3, 1,
                  B, ld, XE_BIAS_M, nullptr, nullptr, nullptr));
     // 3. transformer -> A
-    KCK(ms_transformer(m, n, B, ld, T, A, ld, pos0, hl));
+    KCK(ms_transformer(m, n, B, ld, T, A, ld, dpos0, dhl, shifts));
     // 4. upsample x2: tconv (K = s, no history) + ConvNeXt
     float *cur = A;
     for (int s = 0; s < 2; ++s) {
@@ -2743,6 +2761,8 @@ int codec_mstream_begin(CodecModel *m, int n_streams, int max_frames, int chunk)
     S.row_b = (int *)msalloc(S, rows * 4);
     S.pos = (int *)msalloc(S, rows * 4);
     S.coff = (long long *)msalloc(S, (size_t)ns * 8);
+    S.pp_passes = (max_frames + tc - 1) / tc;   // a push holds at most max_frames frames
+    S.pp = (int *)msalloc(S, (size_t)S.pp_passes * 2 * ns * 4);
     for (void *p : S.allocs)
         if (!p) return -1;
     if (!S.bufA || !S.bufB || !S.bufC || !S.bufD || !S.kv || !S.wav || !S.rope_cos || !S.rope_sin || !S.sid ||
@@ -2766,12 +2786,21 @@ int codec_mstream_begin(CodecModel *m, int n_streams, int max_frames, int chunk)
     }
     rc |= ms_add_slot(S, C, 6);                         // final conv k7
     if (rc) return -1;
+    // the slots' table for the per-stream reset
+    const size_t nsl = S.hist.size();
+    std::vector<int> he(nsl);
+    for (size_t i = 0; i < nsl; ++i) he[i] = S.hist_c[i] * (S.hist_h[i] > 0 ? S.hist_h[i] : 1);
+    S.hist_base = (float **)msalloc(S, nsl * sizeof(float *));
+    S.hist_elems = (int *)msalloc(S, nsl * 4);
+    if (!S.hist_base || !S.hist_elems) return -1;
+    if (hipMemcpy(S.hist_base, S.hist.data(), nsl * sizeof(float *), hipMemcpyHostToDevice) != hipSuccess) return -1;
+    if (hipMemcpy(S.hist_elems, he.data(), nsl * 4, hipMemcpyHostToDevice) != hipSuccess) return -1;
     if (hipDeviceSynchronize() != hipSuccess) return -1;
     S.active = true;
     return 0;
 }
 
-int codec_mstream_check(CodecModel *m, int n, const int *streams, int T) {
+int codec_mstream_check(CodecModel *m, int n, const int *streams, int T, bool any) {
     const CodecMStream &S = m->ms;
     if (!S.active) {
         fprintf(stderr, "qtts codec mstream: push without begin\n");
@@ -2797,13 +2826,19 @@ int codec_mstream_check(CodecModel *m, int n, const int *streams, int T) {
             return -1;
         }
         seen |= 1ull << s;
-        if (S.pos0[s] != S.pos0[streams[0]]) {
+        if (any) {   // capacity is each stream's own
+            if (S.pos0[s] + T > S.max_frames) {
+                fprintf(stderr, "qtts codec mstream: stream %d: %d frames exceed the stream capacity %d\n", s,
+                        S.pos0[s] + T, S.max_frames);
+                return -1;
+            }
+        } else if (S.pos0[s] != S.pos0[streams[0]]) {
             fprintf(stderr, "qtts codec mstream: streams %d and %d are at different positions (%d, %d)\n", streams[0],
                     s, S.pos0[streams[0]], S.pos0[s]);
             return -1;
         }
     }
-    if (S.pos0[streams[0]] + T > S.max_frames) {
+    if (!any && S.pos0[streams[0]] + T > S.max_frames) {
         fprintf(stderr, "qtts codec mstream: %d frames exceed the stream capacity %d\n", S.pos0[streams[0]] + T,
                 S.max_frames);
         return -1;
@@ -2816,39 +2851,58 @@ int codec_mstream_check(CodecModel *m, int n, const int *streams, int T) {
 }
 
 int codec_mstream_push(CodecModel *m, int n, const int *streams, const int *codes_base, const long long *code_off,
-                       int ldc_codes, int Ttot, float *const *host_out) {
+                       int ldc_codes, int Ttot, float *const *host_out, bool any) {
     CodecMStream &S = m->ms;
     const qtts_dims_t &d = m->d;
-    if (codec_mstream_check(m, n, streams, Ttot)) return -1;
+    if (codec_mstream_check(m, n, streams, Ttot, any)) return -1;
     if (!codes_base || !code_off || !host_out || ldc_codes < d.cq) return -1;
     for (int i = 0; i < n; ++i)
         if (!host_out[i]) return -1;
     hipStream_t st = m->st;
     const int spf = ms_samples_per_frame(d);
     S.hwav.resize((size_t)n * Ttot * spf);
+    // every pass's positions of every stream of the push, known up front: a
+    // pass of T frames takes stream s from (pos0, hl) to (pos0 + T, min(hl + T, win - 1))
+    const int keepmax = d.cwin - 1, passes = (Ttot + S.tc - 1) / S.tc;
+    if (passes > S.pp_passes) return -1;   // (the check bounds Ttot by max_frames)
+    S.hpp.resize((size_t)(passes + 1) * 2 * n);   // (the last pair: the streams after the push)
+    for (int i = 0; i < n; ++i) {
+        S.hpp[i] = S.pos0[streams[i]];
+        S.hpp[n + i] = S.hl[streams[i]];
+    }
+    std::vector<char> shift_of(passes, 0);   // pass p: some stream's window runs over
+    for (int p = 0, t0 = 0; p < passes; ++p, t0 += S.tc) {
+        const int T = Ttot - t0 < S.tc ? Ttot - t0 : S.tc;
+        const int *c0 = S.hpp.data() + (size_t)2 * p * n;
+        int *c1 = S.hpp.data() + (size_t)2 * (p + 1) * n;
+        for (int i = 0; i < n; ++i) {
+            const int tot = c0[n + i] + T;
+            if (tot > keepmax) shift_of[p] = 1;
+            c1[i] = c0[i] + T;
+            c1[n + i] = tot < keepmax ? tot : keepmax;
+        }
+    }
     // (the caller's index arrays are read by these copies: the stream is drained before returning)
     int rc = 0;
     if (hipMemcpyAsync(S.sid, streams, (size_t)n * 4, hipMemcpyHostToDevice, st) != hipSuccess ||
-        hipMemcpyAsync(S.coff, code_off, (size_t)n * 8, hipMemcpyHostToDevice, st) != hipSuccess)
+        hipMemcpyAsync(S.coff, code_off, (size_t)n * 8, hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipMemcpyAsync(S.pp, S.hpp.data(), (size_t)passes * 2 * n * 4, hipMemcpyHostToDevice, st) != hipSuccess)
         rc = -1;
-    int pos0 = S.pos0[streams[0]], hl = S.hl[streams[0]];
-    const int keepmax = d.cwin - 1;
     size_t done = 0;   // floats of hwav filled: pass after pass, each [n][T * spf]
-    for (int t0 = 0; t0 < Ttot && !rc; t0 += S.tc) {
+    for (int t0 = 0, p = 0; t0 < Ttot && !rc; t0 += S.tc, ++p) {
         const int T = Ttot - t0 < S.tc ? Ttot - t0 : S.tc;
+        const int *dp = S.pp + (size_t)2 * p * n;
         int L = 0;
-        if (ms_pass(m, n, codes_base, ldc_codes, t0, T, pos0, hl, &L) || L != T * spf ||
+        if (ms_pass(m, n, codes_base, ldc_codes, t0, T, dp, dp + n, shift_of[p] != 0, &L) || L != T * spf ||
             hipMemcpyAsync(S.hwav.data() + done, S.wav, (size_t)n * L * 4, hipMemcpyDeviceToHost, st) != hipSuccess) {
             rc = -1;
             break;
         }
         done += (size_t)n * L;
-        pos0 += T;
-        hl = hl + T < keepmax ? hl + T : keepmax;
     }
     if (hipStreamSynchronize(st) != hipSuccess) rc = -1;
     if (rc) {
-        // a pass failed part-way: the carried state of these streams is no longer one position
+        // a pass failed part-way: the carried state of these streams no longer matches their positions
         fprintf(stderr, "qtts codec mstream: push failed; begin again before the next push\n");
         S.active = false;
         return -1;
@@ -2860,9 +2914,36 @@ int codec_mstream_push(CodecModel *m, int n, const int *streams, const int *code
         for (int i = 0; i < n; ++i) memcpy(host_out[i] + (size_t)t0 * spf, S.hwav.data() + done + i * L, L * 4);
         done += n * L;
     }
+    const int *end = S.hpp.data() + (size_t)2 * passes * n;
     for (int i = 0; i < n; ++i) {
-        S.pos0[streams[i]] = pos0;
-        S.hl[streams[i]] = hl;
+        S.pos0[streams[i]] = end[i];
+        S.hl[streams[i]] = end[n + i];
     }
     return Ttot * spf;
+}
+
+int codec_mstream_reset(CodecModel *m, int stream) {
+    CodecMStream &S = m->ms;
+    if (!S.active || !m->xg_part) {   // (a re-allocation of the codec state frees the streams with it)
+        fprintf(stderr, "qtts codec mstream: reset without begin\n");
+        return -1;
+    }
+    if (stream < 0 || stream >= S.ns) {
+        fprintf(stderr, "qtts codec mstream: stream %d out of range (0..%d)\n", stream, S.ns - 1);
+        return -1;
+    }
+    // zero histories are what begin gives at position 0; the K/V rows stay:
+    // with hl = 0 no old row is inside a new row's window
+    int most = 0;
+    for (size_t i = 0; i < S.hist.size(); ++i) {
+        const int e = S.hist_c[i] * (S.hist_h[i] > 0 ? S.hist_h[i] : 1);
+        if (e > most) most = e;
+    }
+    const int gx = (most + 255) / 256 < 64 ? (most + 255) / 256 : 64;
+    hipLaunchKernelGGL(k_hist_reset_ms, dim3(gx > 0 ? gx : 1, (unsigned)S.hist.size()), dim3(256), 0, m->st, S.hist_base,
+                       S.hist_elems, stream);
+    if (hipGetLastError() != hipSuccess) return -1;
+    S.pos0[stream] = 0;
+    S.hl[stream] = 0;
+    return 0;
 }

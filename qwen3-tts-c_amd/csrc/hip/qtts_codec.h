@@ -60,6 +60,14 @@ struct CodecMStream {
     int rope_cap = 0;
     int *sid = nullptr, *row_b = nullptr, *pos = nullptr;   // [ns], [ns * tc], [ns * tc]
     long long *coff = nullptr;     // [ns] offset (ints) of each stream's codes from the push's base
+    // positions of a push's streams, pass after pass: pass p's pos0 at
+    // pp + 2 p n, its hl at pp + (2 p + 1) n (n streams in the push), uploaded
+    // once before the first pass.  pp_passes: passes the buffer holds
+    int *pp = nullptr;
+    int pp_passes = 0;
+    std::vector<int> hpp;          // its host copy
+    float **hist_base = nullptr;   // device table of the history slots' base pointers and
+    int *hist_elems = nullptr;     // per-stream sizes (C * H), for the reset of one stream
     float *wav = nullptr;          // [ns][tc * samples per frame], compact
     std::vector<float> hwav;       // its host copy
     size_t state_bytes = 0, scratch_bytes = 0;
@@ -127,14 +135,20 @@ void codec_stream_free(CodecModel *m);
 // n independent streams, one launch sequence per push whatever n.  begin
 // (n_streams 1..64) resets every stream; a begin the active state already
 // covers re-uses its buffers.  push decodes T more frames of the n distinct
-// streams `streams` (all at the same position) from the device codes
-// codes_base + code_off[i] (rows of ldc ints), T * samples-per-frame floats
-// each into host_out[i].  Every refusal is -1 with a message before anything
-// is launched or changed.  pos: frames decoded of a stream, -1 for a bad one.
+// streams `streams` from the device codes codes_base + code_off[i] (rows of
+// ldc ints), T * samples-per-frame floats each into host_out[i].  The streams
+// of a push may be at different positions (each row rotates, lands in its
+// cache and attends by its own stream's position); any = false keeps the
+// older contract and refuses that.  Every refusal is -1 with a message before
+// anything is launched or changed.  pos: frames decoded of a stream, -1 for a
+// bad one.  reset: one stream back to position 0 (zero histories, no K/V
+// rows), stream-ordered on m->st, the other streams untouched; -1 with a
+// message for a bad stream or no begin.
 int codec_mstream_begin(CodecModel *m, int n_streams, int max_frames, int chunk = 0);
-int codec_mstream_check(CodecModel *m, int n, const int *streams, int T);
+int codec_mstream_check(CodecModel *m, int n, const int *streams, int T, bool any = false);
 int codec_mstream_push(CodecModel *m, int n, const int *streams, const int *codes_base, const long long *code_off,
-                       int ldc, int T, float *const *host_out);
+                       int ldc, int T, float *const *host_out, bool any = false);
+int codec_mstream_reset(CodecModel *m, int stream);
 int codec_mstream_pos(const CodecModel *m, int stream);
 void codec_mstream_free(CodecModel *m);
 

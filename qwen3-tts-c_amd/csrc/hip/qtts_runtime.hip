@@ -2422,6 +2422,54 @@ extern "C" int qtts_dev_codec_mstream_push_host(qtts_dev_t *dv, int n, const int
     return codec_mstream_push(&dv->codec, n, streams, dv->push_codes, off, dv->d.cq, T, host_out);
 }
 
+// The same two pushes for streams at independent positions (the work queue's
+// slots: a refilled slot's stream restarts at 0 beside its neighbours): slot
+// slots[i]'s frames [frame0[i], frame0[i] + T), or host codes [n][T][16].
+extern "C" int qtts_dev_codec_mstream_push_slots_at(qtts_dev_t *dv, int n, const int *streams, const int *slots,
+                                                    const int *frame0, int T, float *const *host_out) {
+    if (!dv) return -1;
+    hipSetDevice(dv->device);
+    // every refusal before anything is enqueued
+    if (codec_mstream_check(&dv->codec, n, streams, T, true)) return -1;
+    if (!slots || !frame0 || !host_out) return -1;
+    long long off[64];   // (the check bounds n by the begin's 1..64 streams)
+    for (int i = 0; i < n; ++i) {
+        if (slots[i] < 0 || slots[i] >= dv->nb) {
+            fprintf(stderr, "qtts codec mstream: slot %d out of range (0..%d)\n", slots[i], dv->nb - 1);
+            return -1;
+        }
+        if (frame0[i] < 0 || frame0[i] + T > dv->max_frames + 1) {
+            fprintf(stderr, "qtts codec mstream: frames [%d, %d) are outside slot %d's %d\n", frame0[i], frame0[i] + T,
+                    slots[i], dv->max_frames + 1);
+            return -1;
+        }
+        off[i] = ((long long)slots[i] * (dv->max_frames + 1) + frame0[i]) * dv->d.G;
+    }
+    CKI(join_prime(dv));
+    return codec_mstream_push(&dv->codec, n, streams, dv->codes, off, dv->d.G, T, host_out, true);
+}
+
+extern "C" int qtts_dev_codec_mstream_push_host_any(qtts_dev_t *dv, int n, const int *streams, const int *codes, int T,
+                                                    float *const *host_out) {
+    if (!dv) return -1;
+    hipSetDevice(dv->device);
+    if (codec_mstream_check(&dv->codec, n, streams, T, true)) return -1;
+    if (!codes || !host_out) return -1;
+    CKI(join_prime(dv));
+    const size_t per = (size_t)T * dv->d.cq;
+    CKI(ensure_push_codes(dv, per * n));
+    long long off[64];   // (the check bounds n by the begin's 1..64 streams)
+    for (int i = 0; i < n; ++i) off[i] = (long long)(i * per);
+    CK(hipMemcpyAsync(dv->push_codes, codes, per * n * 4, hipMemcpyHostToDevice, dv->codec.st));
+    return codec_mstream_push(&dv->codec, n, streams, dv->push_codes, off, dv->d.cq, T, host_out, true);
+}
+
+extern "C" int qtts_dev_codec_mstream_reset(qtts_dev_t *dv, int stream) {
+    if (!dv) return -1;
+    hipSetDevice(dv->device);
+    return codec_mstream_reset(&dv->codec, stream);
+}
+
 extern "C" int qtts_dev_codec_mstream_pos(qtts_dev_t *dv, int stream) {
     if (!dv) return -1;
     return codec_mstream_pos(&dv->codec, stream);

@@ -1311,11 +1311,62 @@ static void queue_plan_slot(prompt_t *p, int b) {
     for (int k = 0; k < p->nplan; k++) p->plan[5 * k + 3] = b;
 }
 
-int qwen_tts_generate_queue(qwen_tts_ctx_t *ctx, int nq, const char *const *texts, const char *const *speakers,
-                            const char *const *languages, int nb, qwen_tts_queue_next_cb next, void *user,
-                            float **out_audio, int *out_samples) {
+/* The streaming queue (stream != NULL; qwen_tts_generate_queue_stream): every
+ * slot's frames go through a multi-stream codec stream of its own as they are
+ * decoded.  Slot b's stream is stream_of_slot[b]: a refill resets it, the
+ * tail compaction moves the map entry, never codec state.  After the wait for
+ * frame step - 1, slot b has avail = min(step - first[b], its frame count if
+ * it stopped) finished frames, sdone[b] of them delivered.  A slot is due when
+ * it has delivered nothing and has a frame (the first packet: one frame), when
+ * its utterance is complete (the tail: everything, before the slot's codes
+ * rows are reused), or at the call's cadence (step % chunk == 0); the due
+ * slots go in one push per distinct frame count, whatever their positions. */
+typedef struct {
+    const stream_t *stream;
+    int *stream_of_slot, *sdone;     /* [slots] */
+    float **sbuf;                    /* [slots] max_tokens * 1920 samples each */
+    double t_stream, t_start;
+    int delivered;                   /* callbacks so far */
+} qstream_t;
+
+static int queue_stream_flush(qwen_tts_ctx_t *ctx, qtts_dev_t *dev, qstream_t *q, int ns, const int *cur,
+                              const int *avail, const int *complete, int cadence) {
+    for (;;) {
+        int todo[QWEN_TTS_MAX_BATCH], T = 0;
+        for (int b = 0; b < ns; b++) {
+            todo[b] = 0;
+            if (cur[b] < 0 || avail[b] <= q->sdone[b]) continue;
+            if (q->sdone[b] == 0) todo[b] = 1;
+            else if (complete[b] || cadence) todo[b] = avail[b] - q->sdone[b];
+            if (todo[b] > 0 && !T) T = todo[b];
+        }
+        if (!T) return 0;
+        int n = 0, ids[QWEN_TTS_MAX_BATCH], sl[QWEN_TTS_MAX_BATCH], f0[QWEN_TTS_MAX_BATCH];
+        float *outs[QWEN_TTS_MAX_BATCH];
+        for (int b = 0; b < ns; b++)
+            if (todo[b] == T) {
+                ids[n] = q->stream_of_slot[b];
+                sl[n] = b;
+                f0[n] = q->sdone[b];
+                outs[n++] = q->sbuf[b] + (size_t)q->sdone[b] * 1920;
+            }
+        const double t0 = now_ms();
+        const int r = qtts_dev_codec_mstream_push_slots_at(dev, n, ids, sl, f0, T, outs);
+        if (r < 0) return -1;
+        q->t_stream += now_ms() - t0;
+        for (int i = 0; i < n; i++) {
+            if (q->delivered++ == 0) ctx->perf_first_packet_ms = now_ms() - q->t_start;
+            if (q->stream->bcb) q->stream->bcb(cur[sl[i]], outs[i], r, q->stream->user);
+            q->sdone[sl[i]] += T;
+        }
+    }
+}
+
+static int queue_run(qwen_tts_ctx_t *ctx, const char *who, int nq, const char *const *texts,
+                     const char *const *speakers, const char *const *languages, int nb, qwen_tts_queue_next_cb next,
+                     void *user, float **out_audio, int *out_samples, const stream_t *stream) {
     if (ctx && ctx->force) {   /* forcing is defined for one utterance per slot, not for the queue */
-        fprintf(stderr, "Error: qwen_tts_generate_queue: forced codes / taps are armed (not supported; disarmed)\n");
+        fprintf(stderr, "Error: %s: forced codes / taps are armed (not supported; disarmed)\n", who);
         force_disarm(ctx);
         return -1;
     }
@@ -1323,9 +1374,9 @@ int qwen_tts_generate_queue(qwen_tts_ctx_t *ctx, int nq, const char *const *text
         if (ctx) force_disarm(ctx);
         return -1;
     }
-    if (batch_refused(ctx, "qwen_tts_generate_queue", nb)) return -1;
+    if (batch_refused(ctx, who, nb)) return -1;
     sampling_arm_t *sarm = sampling_take(ctx);   /* one-shot: this call consumes it, however it ends */
-    if (sampling_refused("qwen_tts_generate_queue", sarm, NULL, nq)) {
+    if (sampling_refused(who, sarm, NULL, nq)) {
         sampling_free(sarm);
         return -1;
     }
@@ -1345,6 +1396,8 @@ int qwen_tts_generate_queue(qwen_tts_ctx_t *ctx, int nq, const char *const *text
     int *cur = (int *)malloc(nb * sizeof(int)), *first = (int *)calloc(nb, sizeof(int));
     int *retired = (int *)calloc(nb, sizeof(int)), *hst = (int *)calloc(nb, sizeof(int));
     int *cbuf = NULL;
+    qstream_t qs = {stream, NULL, NULL, NULL, 0, t_start, 0};
+    int *avail = NULL, *complete = NULL, *ngen = NULL, finished = 0;
     if (!pr || !taken || !ctx->queue_codes || !ctx->queue_frames || !ctx->queue_stop_reason || !ctx->queue_slot ||
         !cur || !first || !retired || !hst)
         goto out;
@@ -1388,6 +1441,20 @@ int qwen_tts_generate_queue(qwen_tts_ctx_t *ctx, int nq, const char *const *text
     qtts_gen_params_t gp;
     params_of(ctx, &gp);
     if (qtts_dev_begin(dev, ns, max_tokens, max_p, &gp) != 0 || qtts_dev_reserve(dev, max_tr) != 0) goto out;
+    if (stream) {
+        if (qtts_dev_codec_mstream_begin(dev, ns, max_tokens, 0) != 0) goto out;
+        qs.stream_of_slot = (int *)malloc(ns * sizeof(int));
+        qs.sdone = (int *)calloc(ns, sizeof(int));
+        qs.sbuf = (float **)calloc(ns, sizeof(float *));
+        avail = (int *)calloc(ns, sizeof(int));
+        complete = (int *)calloc(ns, sizeof(int));
+        ngen = (int *)calloc(ns, sizeof(int));
+        if (!qs.stream_of_slot || !qs.sdone || !qs.sbuf || !avail || !complete || !ngen) goto out;
+        for (int b = 0; b < ns; b++) {
+            qs.stream_of_slot[b] = b;
+            if (!(qs.sbuf[b] = (float *)malloc((size_t)max_tokens * 1920 * sizeof(float)))) goto out;
+        }
+    }
     /* (a plan row's 4th int is the destination slot: set when the slot is known) */
     /* (the admitted utterance's sampling row goes in with its prompt: before
      * the initial prefill and before every qtts_dev_refill) */
@@ -1426,6 +1493,22 @@ int qwen_tts_generate_queue(qwen_tts_ctx_t *ctx, int nq, const char *const *text
         if (step < 1) continue;
         /* frame step is queued: which slots had stopped by frame step - 1 */
         if (qtts_dev_frame_stops(dev, step - 1, hst) != 0) goto out;
+        if (stream) {
+            /* what every slot has finished by frame step - 1, and the due slots' pushes:
+             * before a complete slot's codes rows are reused or moved below */
+            int any_complete = 0;
+            for (int b = 0; b < ns; b++) {
+                complete[b] = cur[b] >= 0 && (hst[b] || step - first[b] >= max_tokens);
+                any_complete |= complete[b];
+            }
+            if (any_complete && qtts_dev_poll(dev, NULL, ngen, NULL) != 0) goto out;
+            const int cadence = step % stream->chunk == 0;
+            for (int b = 0; b < ns; b++) {
+                avail[b] = cur[b] < 0 ? 0 : complete[b] ? ngen[b] : step - first[b];
+                if (avail[b] > max_tokens) avail[b] = max_tokens;
+            }
+            if (queue_stream_flush(ctx, dev, &qs, ns, cur, avail, complete, cadence) != 0) goto out;
+        }
         for (int b = 0; b < ns; b++) {
             if (cur[b] < 0) continue;
             const int capped = step - first[b] >= max_tokens;
@@ -1445,10 +1528,20 @@ int qwen_tts_generate_queue(qwen_tts_ctx_t *ctx, int nq, const char *const *text
             if (qwen_tts_verbose >= 1)
                 fprintf(stderr, "Queue: utterance %d on slot %d: %s at step %d (frame %d)\n", u, b,
                         hst[b] ? "eos" : "max_tokens", n, step - 1);
+            if (stream) {   /* its chunks already are the utterance (flushed above) */
+                if (qs.sdone[b] != n) goto out;
+                if (n > 0) {
+                    if (!(out_audio[u] = (float *)malloc((size_t)n * 1920 * sizeof(float)))) goto out;
+                    memcpy(out_audio[u], qs.sbuf[b], (size_t)n * 1920 * sizeof(float));
+                    out_samples[u] = n * 1920;
+                }
+                qs.sdone[b] = 0;
+            }
             cur[b] = -1;
             active--;
             const int u2 = exhausted ? -1 : queue_pull(nq, taken, &next_seq, next, user);
             if (u2 < 0) { exhausted = 1; continue; }
+            if (stream && qtts_dev_codec_mstream_reset(dev, qs.stream_of_slot[b]) != 0) goto out;
             if (PROMPT(b, u2) != 0 || qtts_dev_refill(dev, b) != 0) goto out;
             cur[b] = u2;
             first[b] = step + 1;   /* its frame 0 is the next frame launched */
@@ -1468,6 +1561,13 @@ int qwen_tts_generate_queue(qwen_tts_ctx_t *ctx, int nq, const char *const *text
                 if (qtts_dev_move_slot(dev, j, i) != 0) goto out;
                 cur[i] = cur[j]; first[i] = first[j]; retired[i] = retired[j];
                 cur[j] = -1;
+                if (stream) {   /* the slot's stream, frames delivered and chunk buffer travel with it */
+                    const int sw = qs.stream_of_slot[i];
+                    float *bw = qs.sbuf[i];
+                    qs.stream_of_slot[i] = qs.stream_of_slot[j]; qs.stream_of_slot[j] = sw;
+                    qs.sbuf[i] = qs.sbuf[j]; qs.sbuf[j] = bw;
+                    qs.sdone[i] = qs.sdone[j]; qs.sdone[j] = 0;
+                }
             }
             rows = active;
             if (qtts_dev_set_rows(dev, rows) != 0) goto out;
@@ -1476,8 +1576,14 @@ int qwen_tts_generate_queue(qwen_tts_ctx_t *ctx, int nq, const char *const *text
     }
 #undef PROMPT
     ctx->queue_frames_launched = step + 1;
-    ctx->perf_talker_ms = now_ms() - t_gen;
-    {
+    ctx->perf_talker_ms = now_ms() - t_gen - qs.t_stream;
+    if (stream) {
+        rc = 0;
+        finished = 1;
+        for (int u = 0; u < nq; u++)
+            if (ctx->queue_frames[u] == 0) rc = -1;   /* (taken, no frame: no audio) */
+        ctx->perf_codec_ms = qs.t_stream;
+    } else {
         /* every finished utterance's codec pass, several side by side */
         int nj = 0;
         int *uj = (int *)malloc(nq * sizeof(int)), *tj = (int *)malloc(nq * sizeof(int));
@@ -1514,8 +1620,21 @@ out:
     if (pr)
         for (int i = 0; i < nq; i++) { free(pr[i].text); free(pr[i].plan); }
     free(pr); free(taken); free(cur); free(first); free(retired); free(hst); free(cbuf);
+    if (stream) {
+        if (!finished)   /* a run that failed part-way returns nothing */
+            for (int u = 0; u < nq; u++) { free(out_audio[u]); out_audio[u] = NULL; out_samples[u] = 0; }
+        free_bufs(qs.sbuf, ctx->queue_slots);
+        free(qs.stream_of_slot); free(qs.sdone); free(avail); free(complete); free(ngen);
+    }
     sampling_free(sarm);
     return rc;
+}
+
+int qwen_tts_generate_queue(qwen_tts_ctx_t *ctx, int nq, const char *const *texts, const char *const *speakers,
+                            const char *const *languages, int nb, qwen_tts_queue_next_cb next, void *user,
+                            float **out_audio, int *out_samples) {
+    return queue_run(ctx, "qwen_tts_generate_queue", nq, texts, speakers, languages, nb, next, user, out_audio,
+                     out_samples, NULL);
 }
 
 int qwen_tts_queue_codes(qwen_tts_ctx_t *ctx, int i, int *codes, int max_frames) {
@@ -1841,6 +1960,37 @@ int qwen_tts_codec_mstream_push(qwen_tts_ctx_t *ctx, int n, const int *streams, 
                                 float *const *out) {
     if (!ctx || !ctx->hip || !streams || !codes || !out) return -1;
     return qtts_dev_codec_mstream_push_host((qtts_dev_t *)ctx->hip, n, streams, codes, time_steps, out);
+}
+
+int qwen_tts_codec_mstream_push_any(qwen_tts_ctx_t *ctx, int n, const int *streams, const int *codes, int time_steps,
+                                    float *const *out) {
+    if (!ctx || !ctx->hip || !streams || !codes || !out) return -1;
+    return qtts_dev_codec_mstream_push_host_any((qtts_dev_t *)ctx->hip, n, streams, codes, time_steps, out);
+}
+
+int qwen_tts_codec_mstream_reset(qwen_tts_ctx_t *ctx, int stream) {
+    if (!ctx || !ctx->hip) return -1;
+    return qtts_dev_codec_mstream_reset((qtts_dev_t *)ctx->hip, stream);
+}
+
+int qwen_tts_generate_queue_stream(qwen_tts_ctx_t *ctx, int nq, const char *const *texts, const char *const *speakers,
+                                   const char *const *languages, int nb, qwen_tts_queue_next_cb next, void *userdata,
+                                   int chunk_frames, qwen_tts_batch_audio_cb cb, void *cb_userdata, float **out_audio,
+                                   int *out_samples) {
+    static const char who[] = "qwen_tts_generate_queue_stream";
+    /* (the slot limit is named whatever else is wrong with the call: before the device is looked at) */
+    if (ctx && !ctx->force && batch_refused(ctx, who, nb)) return -1;
+    stream_t st = {NULL, cb_userdata, chunk_frames > 0 ? chunk_frames : 1, 1, cb};
+    if (ctx) ctx->perf_first_packet_ms = 0;
+    const int rc = queue_run(ctx, who, nq, texts, speakers, languages, nb, next, userdata, out_audio, out_samples, &st);
+    if (rc == 0 && qwen_tts_verbose >= 1) {
+        double secs = 0;
+        for (int u = 0; u < nq; u++) secs += (double)out_samples[u] / QWEN_TTS_SAMPLE_RATE;
+        fprintf(stderr, "First packet: %.1f ms\n", ctx->perf_first_packet_ms);
+        fprintf(stderr, "Total: %.1f ms (%.2f s audio over %d utterances, %.2fx realtime)\n", ctx->perf_total_ms, secs,
+                nq, secs / (ctx->perf_total_ms / 1000.0));
+    }
+    return rc;
 }
 
 int qwen_tts_codec_stream_begin(qwen_tts_ctx_t *ctx, int max_frames) {

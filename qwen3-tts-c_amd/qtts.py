@@ -116,6 +116,8 @@ EXPORTS = [
     "qwen_tts_generate_batch_stream", "qwen_tts_codec_mstream_begin", "qwen_tts_codec_mstream_push",
     "qtts_dev_codec_mstream_begin", "qtts_dev_codec_mstream_push_slots", "qtts_dev_codec_mstream_push_host",
     "qtts_dev_codec_mstream_pos", "qtts_hip_xgemm_seg_case",
+    "qwen_tts_generate_queue_stream", "qwen_tts_codec_mstream_push_any", "qwen_tts_codec_mstream_reset",
+    "qtts_dev_codec_mstream_push_host_any", "qtts_dev_codec_mstream_push_slots_at", "qtts_dev_codec_mstream_reset",
 ]
 
 MAX_BATCH = 64   # QWEN_TTS_MAX_BATCH / QTTS_HIP_MAX_BATCH: lock-step slots per context
@@ -297,6 +299,19 @@ def lib():
         L.qtts_hip_xgemm_seg_case.restype = C.c_int
         L.qtts_hip_xgemm_seg_case.argtypes = [C.POINTER(XGemmDesc), C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_int,
                                               _ip, _ip, C.c_void_p]
+    # (nor the streaming queue's)
+    if hasattr(L, "qwen_tts_generate_queue_stream"):
+        L.qwen_tts_generate_queue_stream.restype = C.c_int
+        L.qwen_tts_generate_queue_stream.argtypes = [C.POINTER(Ctx), C.c_int, C.POINTER(C.c_char_p),
+                                                     C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.c_int,
+                                                     QUEUE_NEXT_CB, C.c_void_p, C.c_int, BATCH_AUDIO_CB, C.c_void_p,
+                                                     C.POINTER(C.c_void_p), _ip]
+        L.qwen_tts_codec_mstream_push_any.argtypes = [C.POINTER(Ctx), C.c_int, _ip, _ip, C.c_int, C.POINTER(_fp)]
+        L.qwen_tts_codec_mstream_reset.argtypes = [C.POINTER(Ctx), C.c_int]
+        L.qtts_dev_codec_mstream_push_host_any.argtypes = [C.c_void_p, C.c_int, _ip, _ip, C.c_int, C.POINTER(_fp)]
+        L.qtts_dev_codec_mstream_push_slots_at.argtypes = [C.c_void_p, C.c_int, _ip, _ip, _ip, C.c_int,
+                                                           C.POINTER(_fp)]
+        L.qtts_dev_codec_mstream_reset.argtypes = [C.c_void_p, C.c_int]
     L.qwen_tts_speaker_embedding.restype = C.c_void_p
     L.qwen_tts_speaker_embedding.argtypes = [C.POINTER(Ctx), _fp, C.c_int, _ip]
     L.qwen_tts_encode_audio.restype = C.c_void_p
@@ -753,6 +768,27 @@ class QwenTTS:
         rc = lib().qwen_tts_generate_queue(self.ctx, nq, tx, sp, lg, int(slots), cb, None, out, ns)
         return rc, [_take_audio(out[i], ns[i]) for i in range(nq)]
 
+    def generate_queue_stream(self, id_lists, speakers=None, languages=None, slots=8, next_fn=None, chunk_frames=4,
+                              on_chunk=None):
+        """generate_queue with every utterance streamed (qwen_tts_generate_queue_stream):
+        on_chunk(u, np.ndarray) gets utterance u's chunks (u in input order) as
+        they are decoded, whatever slot it runs on.  Returns (rc, [audio or None])."""
+        nq = len(id_lists)
+        tx = (C.c_char_p * nq)(*[",".join(str(int(i)) for i in ids).encode() for ids in id_lists])
+        sp = (C.c_char_p * nq)(*[(s.encode() if s else None) for s in (speakers or [None] * nq)])
+        lg = (C.c_char_p * nq)(*[(s.encode() if s else None) for s in (languages or [None] * nq)])
+        out = (C.c_void_p * nq)()
+        ns = (C.c_int * nq)()
+        ncb = QUEUE_NEXT_CB(lambda u: int(next_fn())) if next_fn is not None else QUEUE_NEXT_CB()
+
+        def _cb(i, p, k, u):
+            if on_chunk is not None:
+                on_chunk(int(i), np.ctypeslib.as_array(p, shape=(k,)).copy())
+        cb = BATCH_AUDIO_CB(_cb)
+        rc = lib().qwen_tts_generate_queue_stream(self.ctx, nq, tx, sp, lg, int(slots), ncb, None, int(chunk_frames),
+                                                  cb, None, out, ns)
+        return rc, [_take_audio(out[i], ns[i]) for i in range(nq)]
+
     def queue_codes(self, i):
         """codes [frames, groups] of utterance i of the last generate_queue (None: not decoded here)"""
         n = lib().qwen_tts_queue_codes(self.ctx, int(i), None, 1 << 30)
@@ -849,7 +885,7 @@ class QwenTTS:
         """(re)start n_streams independent exact codec streams; 0 or -1"""
         return lib().qwen_tts_codec_mstream_begin(self.ctx, int(n_streams), int(max_frames))
 
-    def codec_mstream_push(self, streams, codes):
+    def codec_mstream_push(self, streams, codes, any_position=False):
         """T more frames of the distinct streams `streams` (all at one position),
         codes [n, T, 16]: [T * 1920 samples] per stream, or None where the
         library refuses the push (-1; nothing decoded)."""
@@ -859,12 +895,22 @@ class QwenTTS:
         T = c.shape[1] if c.ndim == 3 else 0
         outs = [np.zeros(max(T, 1) * 1920, np.float32) for _ in range(n)]
         po = (_fp * max(n, 1))(*[o.ctypes.data_as(_fp) for o in outs])
-        k = lib().qwen_tts_codec_mstream_push(self.ctx, n, st.ctypes.data_as(_ip), c.ctypes.data_as(_ip), T, po)
+        fn = lib().qwen_tts_codec_mstream_push_any if any_position else lib().qwen_tts_codec_mstream_push
+        k = fn(self.ctx, n, st.ctypes.data_as(_ip), c.ctypes.data_as(_ip), T, po)
         if k < 0:
             return None
         if k != T * 1920:
             raise RuntimeError(f"codec mstream push returned {k}")
         return outs
+
+    def codec_mstream_push_any(self, streams, codes):
+        """codec_mstream_push for streams at different positions
+        (qwen_tts_codec_mstream_push_any): the same arguments and result"""
+        return self.codec_mstream_push(streams, codes, any_position=True)
+
+    def codec_mstream_reset(self, stream):
+        """one stream back to position 0, the others untouched; 0 or -1"""
+        return lib().qwen_tts_codec_mstream_reset(self.ctx, int(stream))
 
     def codec_mstream_pos(self, stream):
         """frames decoded so far of a stream (-1: no such stream)"""
