@@ -330,6 +330,33 @@ int qtts_dev_codec_mstream_push_slots_at(qtts_dev_t *dev, int n, const int *stre
 int qtts_dev_codec_mstream_push_host_any(qtts_dev_t *dev, int n, const int *streams, const int *codes, int T,
                                          float *const *host_out);
 int qtts_dev_codec_mstream_reset(qtts_dev_t *dev, int stream);
+/* Ragged pushes: stream i of the push advances by its own counts[i] >= 1
+ * frames, still in ONE launch sequence per internal pass whatever n and
+ * however the counts differ ("Ragged pushes": a pass runs at the largest count
+ * left, shorter streams are padded on the right of their plane, and the
+ * codec's causality keeps the padding out of every valid column and out of
+ * the carried state; a stream that has run out is no part of later passes).
+ * _push_host_ragged: host codes [n][ld_frames][16], stream i's first
+ * counts[i] rows; _push_slots_ragged: slot slots[i]'s frames [frame0[i],
+ * frame0[i] + count[i]).  host_out[i] receives counts[i] * 1920 samples and
+ * nothing beyond them.  Returns the LARGEST count times 1920.  With all counts
+ * equal this is _push_host_any / _push_slots_at, the same code path, bit for
+ * bit.  Refusals (-1, a message, nothing launched, no state changed) are
+ * _push_host_any's, and: counts NULL, a count < 1, a count > ld_frames (slots:
+ * frames outside the slot), a stream that would pass max_frames with its own
+ * count (named).
+ * _prime: the _push_host_ragged push with the audio dropped, enqueued on the
+ * second HIP stream and not waited for: the reference frames of a
+ * voice-clone batch, overlapped with the prefill as qtts_dev_codec_stream_prime
+ * overlaps one utterance's.  Every later multi-stream (and codec) call on the
+ * context joins it by event first; qtts_dev_codec_mstream_pos counts the primed
+ * frames at once.  0 or -1 (the same refusals). */
+int qtts_dev_codec_mstream_push_host_ragged(qtts_dev_t *dev, int n, const int *streams, const int *codes,
+                                            const int *counts, int ld_frames, float *const *host_out);
+int qtts_dev_codec_mstream_push_slots_ragged(qtts_dev_t *dev, int n, const int *streams, const int *slots,
+                                             const int *frame0, const int *count, float *const *host_out);
+int qtts_dev_codec_mstream_prime(qtts_dev_t *dev, int n, const int *streams, const int *codes, const int *counts,
+                                 int ld_frames);
 
 /* The same exact streaming decode overlapped with the decode loop: it runs on
  * a second (low-priority) HIP stream; push orders itself after the frames

@@ -453,13 +453,41 @@ int qwen_tts_codec_stream_push(qwen_tts_ctx_t *ctx, const int *codes, int time_s
  * out_audio[i] (malloc'd, caller frees) is the concatenation of utterance i's
  * chunks.  perf_first_packet_ms: entry -> the last callback of the first
  * chunks; perf_codec_ms: time in the codec pushes (perf_talker_ms excludes it).
- * The work queue streams through qwen_tts_generate_queue_stream below.  The
- * voice-clone batch calls do not stream: they need a ragged priming of the
- * reference frames, which the multi-stream codec does not do yet. */
+ * The work queue streams through qwen_tts_generate_queue_stream below, the
+ * voice-clone batch through qwen_tts_generate_voice_clone_batch_stream. */
 typedef void (*qwen_tts_batch_audio_cb)(int utterance, const float *pcm, int n_samples, void *userdata);
 int qwen_tts_generate_batch_stream(qwen_tts_ctx_t *ctx, int nb, const char *const *texts,
                                    const char *const *speakers, const char *const *languages, int chunk_frames,
                                    qwen_tts_batch_audio_cb cb, void *userdata, float **out_audio, int *out_samples);
+/* qwen_tts_generate_voice_clone_batch with every utterance streamed.  Prompts,
+ * decode loop, the nb limit, refusals and the one-shot armings are that
+ * call's and the codes are its codes bit for bit; the delivery per utterance
+ * is qwen_tts_generate_batch_stream's (frame 0, then every chunk_frames
+ * frames, then the tail; the perf_* fields defined the same way).  Each slot
+ * has a multi-stream codec stream of its own; the reference frames of all ICL
+ * slots are run through them first, their audio dropped, in ONE ragged push
+ * (every slot by its own reference length) that overlaps the prefill, so each
+ * stream carries the state of decoding reference ++ generated; an
+ * x-vector-only slot has no reference frames and starts at position 0.
+ * out_audio[b] is the concatenation of b's chunks and starts at sample
+ * n_ref_frames[b] * 1920 of the reference ++ generated decode: the
+ * frame-boundary cut of qwen_tts_generate_voice_clone_stream, not the float
+ * cut of the non-streamed call (they differ by at most one sample).
+ * The _audio_ form encodes the reference audio first (1..16 utterances, as
+ * qwen_tts_generate_voice_clone_audio_batch) and then does the same;
+ * perf_first_packet_ms counts from its entry, the encoders included. */
+int qwen_tts_generate_voice_clone_batch_stream(qwen_tts_ctx_t *ctx, int nb, const char *const *texts,
+                                               const char *const *ref_texts, const int *const *ref_codes,
+                                               const int *n_ref_frames, const float *const *spk_embeds,
+                                               const char *const *languages, int non_streaming, int chunk_frames,
+                                               qwen_tts_batch_audio_cb cb, void *userdata, float **out_audio,
+                                               int *out_samples);
+int qwen_tts_generate_voice_clone_audio_batch_stream(qwen_tts_ctx_t *ctx, int nb, const char *const *texts,
+                                                     const char *const *ref_texts, const float *const *ref_wavs,
+                                                     const int *n_ref_samples, const char *const *languages,
+                                                     const int *x_vector_only, int non_streaming, int chunk_frames,
+                                                     qwen_tts_batch_audio_cb cb, void *userdata, float **out_audio,
+                                                     int *out_samples);
 /* Incremental codec decode of n_streams (1..QWEN_TTS_MAX_BATCH) independent
  * code sequences at once: begin, then pushes of time_steps frames for the n
  * distinct streams streams[0..n) (all at the same position), codes
@@ -479,6 +507,17 @@ int qwen_tts_codec_mstream_push(qwen_tts_ctx_t *ctx, int n, const int *streams, 
 int qwen_tts_codec_mstream_push_any(qwen_tts_ctx_t *ctx, int n, const int *streams, const int *codes, int time_steps,
                                     float *const *out);
 int qwen_tts_codec_mstream_reset(qwen_tts_ctx_t *ctx, int stream);
+/* The ragged push: streams[i] advances by its own counts[i] >= 1 frames in one
+ * launch sequence per internal pass, whatever n and however the counts differ.
+ * codes is [n][ld_frames][16] (stream i's first counts[i] rows are read);
+ * out[i] receives counts[i] * 1920 samples, nothing is written beyond them.
+ * Returns the LARGEST count times 1920, or -1 with a message, nothing decoded
+ * and no stream changed, for qwen_tts_codec_mstream_push_any's refusals and for
+ * counts NULL, a count < 1, a count > ld_frames, or a stream that would pass
+ * max_frames with its own count (named).  Equal counts decode bit for bit what
+ * qwen_tts_codec_mstream_push_any decodes. */
+int qwen_tts_codec_mstream_push_ragged(qwen_tts_ctx_t *ctx, int n, const int *streams, const int *codes,
+                                       const int *counts, int ld_frames, float *const *out);
 /* qwen_tts_generate_queue with every utterance streamed.  Prompts, admission
  * (`next`), refill, retire, tail compaction, the ctx->queue_* results,
  * per-utterance sampling and the refusal (and disarming) of armed forcing are

@@ -2283,13 +2283,16 @@ void *msalloc(CodecMStream &S, size_t bytes) {
 }
 
 // k_rvq_sum over the stacked rows r = s * T + t of a push: stream s's codes
-// start at codes + coff[s], frame t0 + t
+// start at codes + coff[s], frame t0 + t.  Stream s has tv[s] >= 1 frames in
+// this pass: a pad row (t >= tv[s]) fetches the stream's last valid frame, so
+// nothing is read past a stream's codes
 __global__ void k_rvq_sum_ms(const int *codes, const long long *coff, int ldc, int t0, int T, int n, int Q, int CB,
-                             int vq, const float *cb, float *ss, float *as) {
+                             int vq, const float *cb, float *ss, float *as, const int *tv) {
 #pragma clang fp contract(off)
     const int r = blockIdx.x, s = r / T, t = r - s * T, k = threadIdx.x;
     if (k >= vq) return;
-    const int *row = codes + coff[s] + (size_t)(t0 + t) * ldc;
+    const int tl = tv[s] - 1, tf = t < tl ? t : tl;    // uniform over the workgroup
+    const int *row = codes + coff[s] + (size_t)(t0 + tf) * ldc;
     float sm = 0.f, a = 0.f;
     for (int q = 0; q < Q; ++q) {
         int c = row[q];
@@ -2318,24 +2321,30 @@ __global__ void k_rvq_proj_ms(const float *ps, const float *pa, const float *ss,
 }
 // history of every stream of the push in one launch (grid y = stream of the
 // push): out 0: slot[sid[s]] -> the H columns left of plane s's rows; out 1:
-// the last H columns of [margin | L) -> slot[sid[s]].  hist: [streams][C][H]
-__global__ void k_hist_ms(float *hist, const int *sid, float *x, size_t seg, int ldx, int C, int H, int L, int out) {
+// the last H valid columns of [margin | Ls) -> slot[sid[s]], Ls = tv[s] * mul
+// (mul: this stage's columns per frame): the columns right of Ls are padding
+// and never become history; where Ls < H the save reaches into the margin,
+// the history that out 0 put there.  hist: [streams][C][H]
+__global__ void k_hist_ms(float *hist, const int *sid, float *x, size_t seg, int ldx, int C, int H, const int *tv,
+                          int mul, int out) {
     const int idx = blockIdx.x * 256 + threadIdx.x, s = blockIdx.y;
     if (idx >= C * H) return;
     const int c = idx / H, h = idx - c * H;
     float *hp = hist + ((size_t)sid[s] * C + c) * H + h;
     float *xp = x + s * seg + (size_t)c * ldx;
-    if (out) *hp = xp[L - H + h];
+    if (out) *hp = xp[tv[s] * mul - H + h];
     else xp[h - H] = *hp;
 }
 // rotate-half RoPE (k_rope_rows' arithmetic) of the stacked q rows in place and
 // of the k rows into their stream's cache; the v rows beside them.  Row
 // r = s * T + t of the pass rotates with table row pos0[s] + t and lands at
 // cache row hl[s] + t of stream sid[s]: the streams of a pass are at
-// independent positions (cs / sn: the whole table, row 0 first)
+// independent positions (cs / sn: the whole table, row 0 first).  A pad row
+// (t >= tv[s]) rotates its q, which only its own output row sees, and stores
+// no K / V: the cache keeps nothing of it (the table has tc spare rows)
 __global__ void k_rope_kv_ms(float *q, int hid, int nh, const float *k, const float *v, int kvd, int nkv, int hd,
                              const float *cs, const float *sn, int T, const int *sid, const int *pos0, const int *hl,
-                             float *kc, float *vc, int S) {
+                             const int *tv, float *kc, float *vc, int S) {
     const int r = blockIdx.x, s = r / T, t = r - s * T;
     const int p0 = pos0[s], h0 = hl[s], sd = sid[s];   // the stream's values, uniform over the workgroup
     const int half = hd / 2;
@@ -2347,6 +2356,7 @@ __global__ void k_rope_kv_ms(float *q, int hid, int nh, const float *k, const fl
         qq[e] = a * c[e] - bb * sv[e];
         qq[e + half] = bb * c[e + half] + a * sv[e + half];
     }
+    if (t >= tv[s]) return;                            // uniform over the workgroup
     const size_t dst = ((size_t)sd * S + h0 + t) * kvd;
     for (int i = threadIdx.x; i < nkv * half; i += blockDim.x) {
         const int h = i / half, e = i - h * half;
@@ -2360,15 +2370,17 @@ __global__ void k_rope_kv_ms(float *q, int hid, int nh, const float *k, const fl
 }
 // the window keep-shift of every layer's K and V of every stream of the pass
 // in one launch (grid: column blocks x streams of the pass x layers * 2).
-// Stream s holds hl[s] + T rows after the pass and keeps the last
-// keep = min(hl[s] + T, keepmax): rows [shift, shift + keep) -> [0, keep); a
-// stream whose window is not full yet (shift 0) moves nothing.  One thread
+// Stream s holds hl[s] + tv[s] rows after the pass (its valid frames only: a
+// stream whose padding alone would cross the window edge does not shift) and
+// keeps the last keep = min(hl[s] + tv[s], keepmax): rows [shift, shift + keep)
+// -> [0, keep); a stream whose window is not full yet (shift 0) moves nothing.  One thread
 // per column walks its rows upwards (row i is read before any thread writes
 // it: the thread owns the column), so no second buffer.
 // kv: [nl2][streams][S][kvd]
-__global__ void k_kv_shift_ms(float *kv, const int *sid, const int *hl, int ns, int S, int kvd, int T, int keepmax) {
+__global__ void k_kv_shift_ms(float *kv, const int *sid, const int *hl, const int *tv, int ns, int S, int kvd,
+                              int keepmax) {
     const int s = blockIdx.y, l2 = blockIdx.z;
-    const int tot = hl[s] + T, sd = sid[s];            // uniform over the workgroup
+    const int tot = hl[s] + tv[s], sd = sid[s];        // uniform over the workgroup
     const int keep = tot < keepmax ? tot : keepmax, shift = tot - keep;
     if (shift == 0) return;
     const int col = blockIdx.x * 256 + threadIdx.x;
@@ -2426,10 +2438,11 @@ __global__ __launch_bounds__(256) void k_ln_t_ms(const float *x, size_t segx, in
         y[(size_t)r * C + c] = o + b[c];
     }
 }
-// clamp of every plane's waveform row into the compact [n][L] output
-__global__ void k_clamp_ms(const float *x, size_t seg, int L, float *y) {
+// clamp of every plane's waveform row into the compact [n][L] output: the
+// tv[s] * spf valid samples of stream s, nothing of its padding
+__global__ void k_clamp_ms(const float *x, size_t seg, int L, float *y, const int *tv, int spf) {
     const int i = blockIdx.x * 256 + threadIdx.x, s = blockIdx.y;
-    if (i >= L) return;
+    if (i >= L || i >= tv[s] * spf) return;
     float v = x[s * seg + i];
     if (v < -1.0f) v = -1.0f;
     if (v > 1.0f) v = 1.0f;
@@ -2440,7 +2453,7 @@ void ms_hist(CodecModel *m, int n, int slot, float *x, size_t seg, int ldx, int 
     CodecMStream &S = m->ms;
     const int C = S.hist_c[slot], H = S.hist_h[slot];
     hipLaunchKernelGGL(k_hist_ms, dim3((C * H + 255) / 256, n), dim3(256), 0, m->st, S.hist[slot], S.sid, x, seg, ldx,
-                       C, H, L, out);
+                       C, H, S.pass_tv, L / S.pass_T, out);   // (L: a whole number of columns per frame)
 }
 
 // sconv / stconv over n planes: input plane stride ci * ldx, output co * ldo
@@ -2482,9 +2495,10 @@ int ms_stconv(CodecModel *m, int n, int slot, float *x, int ldx, int ci, int L, 
 
 // the transformer over the stacked rows M = n * T of a pass; pc / out: planes
 // [lat][ldp] / [lat][ldo]; stream i of the pass is at dpos0[i] with dhl[i] history
-// rows (device arrays); shifts: some stream's window runs over in this pass
+// rows and has dtv[i] valid frames (device arrays); shifts: some stream's window
+// runs over in this pass
 int ms_transformer(CodecModel *m, int n, const float *pc, int ldp, int T, float *out, int ldo, const int *dpos0,
-                   const int *dhl, bool shifts) {
+                   const int *dhl, const int *dtv, bool shifts) {
     CodecMStream &S = m->ms;
     const qtts_dims_t &d = m->d;
     const int lat = d.clat, hid = d.chid, nh = d.cheads, nkv = d.ckv, hd = hid / nh, kvd = nkv * hd, I = d.cinter;
@@ -2509,7 +2523,7 @@ int ms_transformer(CodecModel *m, int n, const float *pc, int ldp, int T, float 
         KCK(xgm(m, lin(S.txn, M, hid, cw(m, p + "self_attn.k_proj.weight"), kvd, S.tk, XE_STORE), st));
         KCK(xgm(m, lin(S.txn, M, hid, cw(m, p + "self_attn.v_proj.weight"), kvd, S.tv, XE_STORE), st));
         hipLaunchKernelGGL(k_rope_kv_ms, dim3(M), dim3(256), 0, st, S.tq, hid, nh, S.tk, S.tv, kvd, nkv, hd, S.rope_cos,
-                           S.rope_sin, T, S.sid, dpos0, dhl, kcl, vcl, S.S);
+                           S.rope_sin, T, S.sid, dpos0, dhl, dtv, kcl, vcl, S.S);
         AttnArgs a;
         a.mode = 1; a.qkv = S.tq; a.ld_qkv = hid; a.kc = kcl; a.vc = vcl; a.S = S.S; a.pos = S.pos;
         a.row_b = S.row_b; a.NH = nh; a.KV = nkv; a.HD = hd; a.out = S.tatt; a.ld_out = hid;
@@ -2535,7 +2549,7 @@ int ms_transformer(CodecModel *m, int n, const float *pc, int ldp, int T, float 
     // keep the last window-1 rows of every layer for the next pass (each stream by its own count)
     if (keepmax > 0 && shifts)
         hipLaunchKernelGGL(k_kv_shift_ms, dim3((kvd + 255) / 256, n, 2 * d.clayers), dim3(256), 0, st, S.kv, S.sid, dhl,
-                           S.ns, S.S, kvd, T, keepmax);
+                           dtv, S.ns, S.S, kvd, keepmax);
     const float *fn = cw(m, P + "norm.weight");
     const float *xin = S.tx;
     if (fn) {
@@ -2588,10 +2602,13 @@ int ms_samples_per_frame(const qtts_dims_t &d) {
     return f;
 }
 
-// one pass: T <= tc frames of the n streams of the push, audio to S.wav [n][T * spf]
+// one pass: T <= tc frames of the n streams of the pass (the first n of the
+// push), dtv[i] <= T of them valid, audio to S.wav [n][T * spf]
 int ms_pass(CodecModel *m, int n, const int *codes, int ldc_codes, int t0, int T, const int *dpos0, const int *dhl,
-            bool shifts, int *L_out) {
+            const int *dtv, bool shifts, int *L_out) {
     CodecMStream &S = m->ms;
+    S.pass_tv = dtv;
+    S.pass_T = T;
     const qtts_dims_t &d = m->d;
     hipStream_t st = m->st;
     const int lat = d.clat, vq = d.ccbdim / 2, half = lat / 2, hm = S.hm;
@@ -2599,7 +2616,7 @@ int ms_pass(CodecModel *m, int n, const int *codes, int ldc_codes, int t0, int T
     int L = T, ld = hm + L;
     // 1. RVQ dequantise -> A planes [half][T]
     hipLaunchKernelGGL(k_rvq_sum_ms, dim3(n * T), dim3(vq < 64 ? 64 : (vq + 63) / 64 * 64), 0, st, codes, S.coff,
-                       ldc_codes, t0, T, n, d.cq, d.ccb, vq, m->cb, S.rvq_s, S.rvq_a);
+                       ldc_codes, t0, T, n, d.cq, d.ccb, vq, m->cb, S.rvq_s, S.rvq_a, dtv);
     hipLaunchKernelGGL(k_rvq_proj_ms, dim3((half * n * T + 3) / 4), dim3(256), 0, st,
                        cw(m, "decoder.quantizer.rvq_first.output_proj.weight"),
                        cw(m, "decoder.quantizer.rvq_rest.output_proj.weight"), S.rvq_s, S.rvq_a, vq, half, T, n, ld,
@@ -2608,7 +2625,7 @@ int ms_pass(CodecModel *m, int n, const int *codes, int ldc_codes, int t0, int T
     KCK(ms_sconv(m, n, 0, A, ld, d.ccbdim, L, "decoder.pre_conv.conv.weight", "decoder.pre_conv.conv.bias", lat, 3, 1,
                  B, ld, XE_BIAS_M, nullptr, nullptr, nullptr));
     // 3. transformer -> A
-    KCK(ms_transformer(m, n, B, ld, T, A, ld, dpos0, dhl, shifts));
+    KCK(ms_transformer(m, n, B, ld, T, A, ld, dpos0, dhl, dtv, shifts));
     // 4. upsample x2: tconv (K = s, no history) + ConvNeXt
     float *cur = A;
     for (int s = 0; s < 2; ++s) {
@@ -2668,7 +2685,8 @@ int ms_pass(CodecModel *m, int n, const int *codes, int ldc_codes, int t0, int T
     float *wav = voc == A ? B : A;
     KCK(ms_sconv(m, n, slot, voc, ld, C, L, "decoder.decoder.6.conv.weight", "decoder.decoder.6.conv.bias", 1, 7, 1, wav,
                  ld, XE_BIAS_M, cw(m, "decoder.decoder.5.alpha"), cw(m, "decoder.decoder.5.beta"), nullptr));
-    hipLaunchKernelGGL(k_clamp_ms, dim3((L + 255) / 256, n), dim3(256), 0, st, wav, (size_t)ld, L, S.wav);
+    hipLaunchKernelGGL(k_clamp_ms, dim3((L + 255) / 256, n), dim3(256), 0, st, wav, (size_t)ld, L, S.wav,
+                       dtv, L / T);
     *L_out = L;
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
@@ -2762,7 +2780,7 @@ int codec_mstream_begin(CodecModel *m, int n_streams, int max_frames, int chunk)
     S.pos = (int *)msalloc(S, rows * 4);
     S.coff = (long long *)msalloc(S, (size_t)ns * 8);
     S.pp_passes = (max_frames + tc - 1) / tc;   // a push holds at most max_frames frames
-    S.pp = (int *)msalloc(S, (size_t)S.pp_passes * 2 * ns * 4);
+    S.pp = (int *)msalloc(S, (size_t)S.pp_passes * 3 * ns * 4);
     for (void *p : S.allocs)
         if (!p) return -1;
     if (!S.bufA || !S.bufB || !S.bufC || !S.bufD || !S.kv || !S.wav || !S.rope_cos || !S.rope_sin || !S.sid ||
@@ -2850,76 +2868,149 @@ int codec_mstream_check(CodecModel *m, int n, const int *streams, int T, bool an
     return 0;
 }
 
-int codec_mstream_push(CodecModel *m, int n, const int *streams, const int *codes_base, const long long *code_off,
-                       int ldc_codes, int Ttot, float *const *host_out, bool any) {
-    CodecMStream &S = m->ms;
-    const qtts_dims_t &d = m->d;
-    if (codec_mstream_check(m, n, streams, Ttot, any)) return -1;
-    if (!codes_base || !code_off || !host_out || ldc_codes < d.cq) return -1;
-    for (int i = 0; i < n; ++i)
-        if (!host_out[i]) return -1;
-    hipStream_t st = m->st;
-    const int spf = ms_samples_per_frame(d);
-    S.hwav.resize((size_t)n * Ttot * spf);
-    // every pass's positions of every stream of the push, known up front: a
-    // pass of T frames takes stream s from (pos0, hl) to (pos0 + T, min(hl + T, win - 1))
-    const int keepmax = d.cwin - 1, passes = (Ttot + S.tc - 1) / S.tc;
-    if (passes > S.pp_passes) return -1;   // (the check bounds Ttot by max_frames)
-    S.hpp.resize((size_t)(passes + 1) * 2 * n);   // (the last pair: the streams after the push)
-    for (int i = 0; i < n; ++i) {
-        S.hpp[i] = S.pos0[streams[i]];
-        S.hpp[n + i] = S.hl[streams[i]];
+int codec_mstream_check_ragged(CodecModel *m, int n, const int *streams, const int *counts, int ld_frames) {
+    const CodecMStream &S = m->ms;
+    if (codec_mstream_check(m, n, streams, 1, true)) return -1;
+    if (!counts) {
+        fprintf(stderr, "qtts codec mstream: a ragged push takes one frame count per stream (got NULL)\n");
+        return -1;
     }
-    std::vector<char> shift_of(passes, 0);   // pass p: some stream's window runs over
-    for (int p = 0, t0 = 0; p < passes; ++p, t0 += S.tc) {
-        const int T = Ttot - t0 < S.tc ? Ttot - t0 : S.tc;
-        const int *c0 = S.hpp.data() + (size_t)2 * p * n;
-        int *c1 = S.hpp.data() + (size_t)2 * (p + 1) * n;
-        for (int i = 0; i < n; ++i) {
-            const int tot = c0[n + i] + T;
-            if (tot > keepmax) shift_of[p] = 1;
-            c1[i] = c0[i] + T;
-            c1[n + i] = tot < keepmax ? tot : keepmax;
+    for (int i = 0; i < n; ++i) {
+        if (counts[i] < 1 || counts[i] > ld_frames) {
+            fprintf(stderr, "qtts codec mstream: stream %d: a ragged push takes 1..%d frames per stream (got %d)\n",
+                    streams[i], ld_frames, counts[i]);
+            return -1;
+        }
+        if (S.pos0[streams[i]] + counts[i] > S.max_frames) {
+            fprintf(stderr, "qtts codec mstream: stream %d: %d frames exceed the stream capacity %d\n", streams[i],
+                    S.pos0[streams[i]] + counts[i], S.max_frames);
+            return -1;
         }
     }
-    // (the caller's index arrays are read by these copies: the stream is drained before returning)
+    return 0;
+}
+
+namespace {
+// the push behind every entry (the caller has checked): stream i of the push
+// advances by counts[i] frames.  The streams are taken longest count first
+// (stable: equal counts keep the caller's order), so the streams that still
+// have frames in a pass are the first nl of them and a stream that has run
+// out is no part of the later passes.  A pass runs at T = min(tc, the
+// largest count left); stream i has tv = min(its count left, T) valid frames
+// at the left of its plane and stacked rows, the rest is padding ("Ragged pushes")
+int ms_push(CodecModel *m, int n, const int *streams, const int *codes_base, const long long *code_off, int ldc_codes,
+            const int *counts, float *const *host_out) {
+    CodecMStream &S = m->ms;
+    const qtts_dims_t &d = m->d;
+    hipStream_t st = m->st;
+    const int spf = ms_samples_per_frame(d);
+    S.hord.resize(n);
+    for (int i = 0; i < n; ++i) S.hord[i] = i;
+    std::stable_sort(S.hord.begin(), S.hord.end(), [&](int a, int b) { return counts[a] > counts[b]; });
+    const int Tmax = counts[S.hord[0]];
+    S.hsid.resize(n);
+    S.hcoff.resize(n);
+    for (int i = 0; i < n; ++i) {
+        S.hsid[i] = streams[S.hord[i]];
+        S.hcoff[i] = code_off[S.hord[i]];
+    }
+    auto cnt = [&](int i) { return counts[S.hord[i]]; };
+    // every pass's positions and counts of every stream of the push, known up
+    // front: a pass takes stream s from (pos0, hl) to (pos0 + tv, min(hl + tv, win - 1))
+    const int keepmax = d.cwin - 1, passes = (Tmax + S.tc - 1) / S.tc;
+    if (passes > S.pp_passes) return -1;   // (the check bounds every count by max_frames)
+    S.hpp.assign((size_t)passes * 3 * n, 0);
+    S.hend.resize((size_t)2 * n);          // the streams after the push
+    for (int i = 0; i < n; ++i) {
+        S.hend[i] = S.pos0[S.hsid[i]];
+        S.hend[n + i] = S.hl[S.hsid[i]];
+    }
+    std::vector<char> shift_of(passes, 0);   // pass p: some stream's window runs over
+    std::vector<int> nl_of(passes, 0);       // pass p: streams that still have frames
+    size_t total = 0;                        // floats of hwav: pass after pass, each [nl][T * spf]
+    for (int p = 0, t0 = 0; p < passes; ++p, t0 += S.tc) {
+        const int T = Tmax - t0 < S.tc ? Tmax - t0 : S.tc;
+        int *c = S.hpp.data() + (size_t)3 * p * n;
+        int nl = 0;
+        while (nl < n && cnt(nl) > t0) ++nl;
+        nl_of[p] = nl;
+        for (int i = 0; i < nl; ++i) {
+            const int tv = cnt(i) - t0 < T ? cnt(i) - t0 : T;
+            c[i] = S.hend[i];
+            c[n + i] = S.hend[n + i];
+            c[2 * n + i] = tv;
+            const int tot = S.hend[n + i] + tv;
+            if (tot > keepmax) shift_of[p] = 1;
+            S.hend[i] += tv;
+            S.hend[n + i] = tot < keepmax ? tot : keepmax;
+        }
+        total += (size_t)nl * T * spf;
+    }
+    if (host_out) S.hwav.resize(total);
     int rc = 0;
-    if (hipMemcpyAsync(S.sid, streams, (size_t)n * 4, hipMemcpyHostToDevice, st) != hipSuccess ||
-        hipMemcpyAsync(S.coff, code_off, (size_t)n * 8, hipMemcpyHostToDevice, st) != hipSuccess ||
-        hipMemcpyAsync(S.pp, S.hpp.data(), (size_t)passes * 2 * n * 4, hipMemcpyHostToDevice, st) != hipSuccess)
+    if (hipMemcpyAsync(S.sid, S.hsid.data(), (size_t)n * 4, hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipMemcpyAsync(S.coff, S.hcoff.data(), (size_t)n * 8, hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipMemcpyAsync(S.pp, S.hpp.data(), (size_t)passes * 3 * n * 4, hipMemcpyHostToDevice, st) != hipSuccess)
         rc = -1;
-    size_t done = 0;   // floats of hwav filled: pass after pass, each [n][T * spf]
-    for (int t0 = 0, p = 0; t0 < Ttot && !rc; t0 += S.tc, ++p) {
-        const int T = Ttot - t0 < S.tc ? Ttot - t0 : S.tc;
-        const int *dp = S.pp + (size_t)2 * p * n;
+    size_t done = 0;
+    for (int t0 = 0, p = 0; t0 < Tmax && !rc; t0 += S.tc, ++p) {
+        const int T = Tmax - t0 < S.tc ? Tmax - t0 : S.tc, nl = nl_of[p];
+        const int *dp = S.pp + (size_t)3 * p * n;
         int L = 0;
-        if (ms_pass(m, n, codes_base, ldc_codes, t0, T, dp, dp + n, shift_of[p] != 0, &L) || L != T * spf ||
-            hipMemcpyAsync(S.hwav.data() + done, S.wav, (size_t)n * L * 4, hipMemcpyDeviceToHost, st) != hipSuccess) {
+        if (ms_pass(m, nl, codes_base, ldc_codes, t0, T, dp, dp + n, dp + 2 * n, shift_of[p] != 0, &L) ||
+            L != T * spf ||
+            (host_out && hipMemcpyAsync(S.hwav.data() + done, S.wav, (size_t)nl * L * 4, hipMemcpyDeviceToHost, st) !=
+                             hipSuccess)) {
             rc = -1;
             break;
         }
-        done += (size_t)n * L;
+        done += (size_t)nl * L;
     }
-    if (hipStreamSynchronize(st) != hipSuccess) rc = -1;
+    if (host_out && hipStreamSynchronize(st) != hipSuccess) rc = -1;
     if (rc) {
         // a pass failed part-way: the carried state of these streams no longer matches their positions
         fprintf(stderr, "qtts codec mstream: push failed; begin again before the next push\n");
         S.active = false;
         return -1;
     }
-    done = 0;
-    for (int t0 = 0; t0 < Ttot; t0 += S.tc) {
-        const int T = Ttot - t0 < S.tc ? Ttot - t0 : S.tc;
-        const size_t L = (size_t)T * spf;
-        for (int i = 0; i < n; ++i) memcpy(host_out[i] + (size_t)t0 * spf, S.hwav.data() + done + i * L, L * 4);
-        done += n * L;
+    if (host_out) {
+        done = 0;
+        for (int t0 = 0, p = 0; t0 < Tmax; t0 += S.tc, ++p) {
+            const int T = Tmax - t0 < S.tc ? Tmax - t0 : S.tc, nl = nl_of[p];
+            const size_t L = (size_t)T * spf;
+            for (int i = 0; i < nl; ++i) {
+                const int tv = cnt(i) - t0 < T ? cnt(i) - t0 : T;
+                memcpy(host_out[S.hord[i]] + (size_t)t0 * spf, S.hwav.data() + done + i * L, (size_t)tv * spf * 4);
+            }
+            done += nl * L;
+        }
     }
-    const int *end = S.hpp.data() + (size_t)2 * passes * n;
     for (int i = 0; i < n; ++i) {
-        S.pos0[streams[i]] = end[i];
-        S.hl[streams[i]] = end[n + i];
+        S.pos0[S.hsid[i]] = S.hend[i];
+        S.hl[S.hsid[i]] = S.hend[n + i];
     }
-    return Ttot * spf;
+    return Tmax * spf;
+}
+}  // namespace
+
+int codec_mstream_push(CodecModel *m, int n, const int *streams, const int *codes_base, const long long *code_off,
+                       int ldc_codes, int Ttot, float *const *host_out, bool any) {
+    if (codec_mstream_check(m, n, streams, Ttot, any)) return -1;
+    if (!codes_base || !code_off || !host_out || ldc_codes < m->d.cq) return -1;
+    for (int i = 0; i < n; ++i)
+        if (!host_out[i]) return -1;
+    int counts[64];   // (the check bounds n by the begin's 1..64 streams)
+    for (int i = 0; i < n; ++i) counts[i] = Ttot;
+    return ms_push(m, n, streams, codes_base, code_off, ldc_codes, counts, host_out);
+}
+
+int codec_mstream_push_ragged(CodecModel *m, int n, const int *streams, const int *codes_base,
+                              const long long *code_off, int ldc_codes, const int *counts, float *const *host_out) {
+    if (codec_mstream_check_ragged(m, n, streams, counts, m->ms.max_frames)) return -1;
+    if (!codes_base || !code_off || ldc_codes < m->d.cq) return -1;
+    for (int i = 0; host_out && i < n; ++i)
+        if (!host_out[i]) return -1;
+    return ms_push(m, n, streams, codes_base, code_off, ldc_codes, counts, host_out);
 }
 
 int codec_mstream_reset(CodecModel *m, int stream) {

@@ -61,11 +61,17 @@ struct CodecMStream {
     int *sid = nullptr, *row_b = nullptr, *pos = nullptr;   // [ns], [ns * tc], [ns * tc]
     long long *coff = nullptr;     // [ns] offset (ints) of each stream's codes from the push's base
     // positions of a push's streams, pass after pass: pass p's pos0 at
-    // pp + 2 p n, its hl at pp + (2 p + 1) n (n streams in the push), uploaded
-    // once before the first pass.  pp_passes: passes the buffer holds
+    // pp + 3 p n, its hl at pp + (3 p + 1) n, its valid frame counts tv at
+    // pp + (3 p + 2) n (n streams in the push, longest count first, so the
+    // streams of a pass are the first ones of the push), uploaded once before
+    // the first pass.  pp_passes: passes the buffer holds
     int *pp = nullptr;
     int pp_passes = 0;
     std::vector<int> hpp;          // its host copy
+    std::vector<int> hsid, hord, hend;   // a push's stream ids in pass order, their places in the caller's order, end state
+    std::vector<long long> hcoff;
+    const int *pass_tv = nullptr;  // the running pass's tv (device) and frames, for its history saves
+    int pass_T = 1;
     float **hist_base = nullptr;   // device table of the history slots' base pointers and
     int *hist_elems = nullptr;     // per-stream sizes (C * H), for the reset of one stream
     float *wav = nullptr;          // [ns][tc * samples per frame], compact
@@ -139,8 +145,15 @@ void codec_stream_free(CodecModel *m);
 // ldc ints), T * samples-per-frame floats each into host_out[i].  The streams
 // of a push may be at different positions (each row rotates, lands in its
 // cache and attends by its own stream's position); any = false keeps the
-// older contract and refuses that.  Every refusal is -1 with a message before
-// anything is launched or changed.  pos: frames decoded of a stream, -1 for a
+// older contract and refuses that.  push_ragged: stream i advances by its own
+// counts[i] >= 1 frames (its codes hold at least counts[i] rows), counts[i] *
+// samples-per-frame floats into host_out[i]; still one launch sequence per
+// pass whatever the counts ("Ragged pushes"); returns the largest count times
+// samples-per-frame.  host_out nullptr: the audio is dropped and nothing is
+// waited for (everything enqueued on m->st; the priming of reference
+// frames).  check_ragged: its refusals (push_any's, and counts NULL, a count
+// < 1 or > ld_frames, a stream passing its capacity, named).  Every refusal
+// is -1 with a message before anything is launched or changed.  pos: frames decoded of a stream, -1 for a
 // bad one.  reset: one stream back to position 0 (zero histories, no K/V
 // rows), stream-ordered on m->st, the other streams untouched; -1 with a
 // message for a bad stream or no begin.
@@ -148,6 +161,9 @@ int codec_mstream_begin(CodecModel *m, int n_streams, int max_frames, int chunk 
 int codec_mstream_check(CodecModel *m, int n, const int *streams, int T, bool any = false);
 int codec_mstream_push(CodecModel *m, int n, const int *streams, const int *codes_base, const long long *code_off,
                        int ldc, int T, float *const *host_out, bool any = false);
+int codec_mstream_check_ragged(CodecModel *m, int n, const int *streams, const int *counts, int ld_frames);
+int codec_mstream_push_ragged(CodecModel *m, int n, const int *streams, const int *codes_base,
+                              const long long *code_off, int ldc, const int *counts, float *const *host_out);
 int codec_mstream_reset(CodecModel *m, int stream);
 int codec_mstream_pos(const CodecModel *m, int stream);
 void codec_mstream_free(CodecModel *m);

@@ -2464,9 +2464,88 @@ extern "C" int qtts_dev_codec_mstream_push_host_any(qtts_dev_t *dv, int n, const
     return codec_mstream_push(&dv->codec, n, streams, dv->push_codes, off, dv->d.cq, T, host_out, true);
 }
 
+// The ragged pushes: stream i advances by its own count (one launch sequence
+// per pass whatever the counts, DESIGN.md 7, "Ragged pushes").  Host codes [n][ld_frames][16],
+// of which stream i's first counts[i] rows are read; or slot slots[i]'s
+// frames [frame0[i], frame0[i] + count[i]).  counts[i] * 1920 samples reach
+// host_out[i]; returns the largest count times 1920.
+extern "C" int qtts_dev_codec_mstream_push_host_ragged(qtts_dev_t *dv, int n, const int *streams, const int *codes,
+                                                       const int *counts, int ld_frames, float *const *host_out) {
+    if (!dv) return -1;
+    hipSetDevice(dv->device);
+    // every refusal before anything is enqueued
+    if (codec_mstream_check_ragged(&dv->codec, n, streams, counts, ld_frames)) return -1;
+    if (!codes || !host_out) return -1;
+    for (int i = 0; i < n; ++i)
+        if (!host_out[i]) return -1;
+    CKI(join_prime(dv));
+    const size_t per = (size_t)ld_frames * dv->d.cq;
+    CKI(ensure_push_codes(dv, per * n));
+    long long off[64];   // (the check bounds n by the begin's 1..64 streams)
+    for (int i = 0; i < n; ++i) off[i] = (long long)(i * per);
+    CK(hipMemcpyAsync(dv->push_codes, codes, per * n * 4, hipMemcpyHostToDevice, dv->codec.st));
+    return codec_mstream_push_ragged(&dv->codec, n, streams, dv->push_codes, off, dv->d.cq, counts, host_out);
+}
+
+extern "C" int qtts_dev_codec_mstream_push_slots_ragged(qtts_dev_t *dv, int n, const int *streams, const int *slots,
+                                                        const int *frame0, const int *count,
+                                                        float *const *host_out) {
+    if (!dv) return -1;
+    hipSetDevice(dv->device);
+    if (codec_mstream_check_ragged(&dv->codec, n, streams, count, dv->max_frames + 1)) return -1;
+    if (!slots || !frame0 || !host_out) return -1;
+    long long off[64];   // (the check bounds n by the begin's 1..64 streams)
+    for (int i = 0; i < n; ++i) {
+        if (!host_out[i]) return -1;
+        if (slots[i] < 0 || slots[i] >= dv->nb) {
+            fprintf(stderr, "qtts codec mstream: slot %d out of range (0..%d)\n", slots[i], dv->nb - 1);
+            return -1;
+        }
+        if (frame0[i] < 0 || frame0[i] + count[i] > dv->max_frames + 1) {
+            fprintf(stderr, "qtts codec mstream: frames [%d, %d) are outside slot %d's %d\n", frame0[i],
+                    frame0[i] + count[i], slots[i], dv->max_frames + 1);
+            return -1;
+        }
+        off[i] = ((long long)slots[i] * (dv->max_frames + 1) + frame0[i]) * dv->d.G;
+    }
+    CKI(join_prime(dv));
+    return codec_mstream_push_ragged(&dv->codec, n, streams, dv->codes, off, dv->d.G, count, host_out);
+}
+
+// Push host codes of ragged lengths ([n][ld_frames][16], counts[i] rows of
+// stream i) through the streams on the second stream (cst) without waiting:
+// their audio is dropped, the carried state is what later pushes continue
+// from.  The reference frames of a voice-clone batch go this way while the
+// prefill runs on the context stream, as qtts_dev_codec_stream_prime's do
+// for one utterance; every later multi-stream call joins it by event.
+extern "C" int qtts_dev_codec_mstream_prime(qtts_dev_t *dv, int n, const int *streams, const int *codes,
+                                            const int *counts, int ld_frames) {
+    if (!dv) return -1;
+    hipSetDevice(dv->device);
+    if (codec_mstream_check_ragged(&dv->codec, n, streams, counts, ld_frames)) return -1;
+    if (!codes) return -1;
+    CKI(join_prime(dv));
+    CKI(ensure_cst(dv));
+    const size_t per = (size_t)ld_frames * dv->d.cq;
+    CKI(ensure_push_codes(dv, per * n));
+    long long off[64];   // (the check bounds n by the begin's 1..64 streams)
+    for (int i = 0; i < n; ++i) off[i] = (long long)(i * per);
+    CK(hipEventRecord(dv->cev, dv->st));          // after the begin's resets on st
+    CK(hipStreamWaitEvent(dv->cst, dv->cev, 0));
+    CK(hipMemcpyAsync(dv->push_codes, codes, per * n * 4, hipMemcpyHostToDevice, dv->cst));
+    dv->codec.st = dv->cst;
+    const int r = codec_mstream_push_ragged(&dv->codec, n, streams, dv->push_codes, off, dv->d.cq, counts, nullptr);
+    dv->codec.st = dv->st;
+    if (r < 0) return -1;
+    CK(hipEventRecord(dv->cev, dv->cst));
+    dv->prime_pending = true;
+    return 0;
+}
+
 extern "C" int qtts_dev_codec_mstream_reset(qtts_dev_t *dv, int stream) {
     if (!dv) return -1;
     hipSetDevice(dv->device);
+    CKI(join_prime(dv));   // a pending prime owns the histories until joined
     return codec_mstream_reset(&dv->codec, stream);
 }
 

@@ -12,7 +12,8 @@
  * one lock-step batch; the first one's audio is written), --stream N (exact
  * streaming decode: audio delivered after frame 0 and then every N frames;
  * prints "First packet: X ms"; with --batch N every slot is streamed,
- * qwen_tts_generate_batch_stream), --kv-cache fp32|bf16 (talker KV cache
+ * qwen_tts_generate_batch_stream, a voice clone's slots through
+ * qwen_tts_generate_voice_clone_batch_stream), --kv-cache fp32|bf16 (talker KV cache
  * elements, qwen_tts_set_kv_cache_dtype), --force-codes FILE / --dump-drawn
  * FILE (teacher-forced decode and its free-draw record, qwen_tts_force_codes /
  * qwen_tts_last_drawn), --seed-step K (with --batch N: slot b samples with seed
@@ -57,7 +58,8 @@ static void usage(const char *prog) {
             "                      (-1: leave that draw free; later frames are free), qwen_tts_force_codes\n"
             "  --dump-drawn <file> write the id the sampler itself drew at every draw in that format\n"
             "                      (-1: no draw happened), qwen_tts_last_drawn\n"
-            "voice clone (include/qwen_tts.h qwen_tts_generate_voice_clone[_audio]):\n"
+            "voice clone (include/qwen_tts.h qwen_tts_generate_voice_clone[_audio]; at --batch 1 without --stream,\n"
+            "or N copies at --batch N --stream K, every slot streamed: ..._voice_clone[_audio]_batch_stream):\n"
             "  --ref-audio <wav>   reference audio (mono/stereo PCM16 or float WAV; other rates are resampled\n"
             "                      to 24 kHz): encoded on the GPU (12 Hz codes + speaker x-vector)\n"
             "  --x-vector-only     with --ref-audio: x-vector only (no reference codes / ref text)\n"
@@ -315,8 +317,8 @@ int main(int argc, char **argv) {
             return 1;
         }
     }
-    if (clone && (batch != 1 || stream_chunk > 0)) {
-        fprintf(stderr, "Error: voice clone runs at --batch 1 without --stream\n");
+    if (clone && (batch > 1) != (stream_chunk > 0)) {
+        fprintf(stderr, "Error: voice clone runs at --batch 1 without --stream, or at --batch N (N > 1) with --stream K\n");
         free(file_ids);
         return 1;
     }
@@ -405,7 +407,39 @@ int main(int argc, char **argv) {
             rc = 1;
             break;
         }
-        if (ref_wav) {
+        if (clone && batch > 1) {
+            /* --batch N --stream K: N copies of the voice clone, every slot streamed (the chunks
+             * are dropped here: the returned audio is their concatenation); slot 0 is written */
+            const char **tx = (const char **)malloc(batch * sizeof(char *));
+            const char **rt = (const char **)malloc(batch * sizeof(char *));
+            const char **lg = (const char **)malloc(batch * sizeof(char *));
+            const int **rcs = (const int **)malloc(batch * sizeof(int *));
+            const float **fv = (const float **)malloc(batch * sizeof(float *));
+            int *nr = (int *)calloc(batch, sizeof(int)), *xo = (int *)calloc(batch, sizeof(int));
+            float **au = (float **)calloc(batch, sizeof(float *));
+            int *ns = (int *)calloc(batch, sizeof(int));
+            for (int b = 0; b < batch; b++) {
+                tx[b] = ids; lg[b] = lang;
+                rt[b] = ref_wav && xvec_only ? NULL : ref_text;
+                rcs[b] = ref_codes; fv[b] = ref_wav ? ref_wav : xvec;
+                nr[b] = ref_wav ? n_ref_wav : n_ref; xo[b] = xvec_only;
+            }
+            const int r = ref_wav ? qwen_tts_generate_voice_clone_audio_batch_stream(ctx, batch, tx, rt, fv, nr, lg, xo,
+                                                                                   non_streaming, stream_chunk, NULL,
+                                                                                   NULL, au, ns)
+                                  : qwen_tts_generate_voice_clone_batch_stream(ctx, batch, tx, rt, rcs, nr, fv, lg,
+                                                                             non_streaming, stream_chunk, NULL, NULL,
+                                                                             au, ns);
+            if (r == 0) {
+                ra = au[0];
+                rn = ns[0];
+                for (int b = 0; b < batch; b++) total_samples += ns[b];
+            } else {
+                free(au[0]);
+            }
+            for (int b = 1; b < batch; b++) free(au[b]);
+            free(tx); free(rt); free(lg); free(rcs); free(fv); free(nr); free(xo); free(au); free(ns);
+        } else if (ref_wav) {
             ra = qwen_tts_generate_voice_clone_audio(ctx, ids, xvec_only ? NULL : ref_text, ref_wav, n_ref_wav, lang,
                                                      xvec_only, non_streaming, &rn);
             total_samples = rn;

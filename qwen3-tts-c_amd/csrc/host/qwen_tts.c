@@ -924,9 +924,37 @@ static void free_bufs(float **v, int n) {
  * position; they differ only in how many frames are new (a short tail): one
  * push per distinct count.  sdone[b]: frames of slot b delivered so far. */
 static int batch_stream_flush(qtts_dev_t *dev, int nb, const stream_t *stream, const int *ngen, int *sdone,
-                              float **sbufs, double *t_stream) {
+                              float **sbufs, double *t_stream, const int *sref) {
     int todo[QWEN_TTS_MAX_BATCH];
     for (int b = 0; b < nb; b++) todo[b] = ngen[b] - sdone[b];
+    if (sref) {
+        /* voice clone: stream b stands at sref[b] + sdone[b], its primed
+         * reference frames ahead of its own, so the slots go through the
+         * per-position form; the mixed tail lengths of one poll through the
+         * ragged form, in one push either way */
+        int n = 0, T = 0, same = 1, ids[QWEN_TTS_MAX_BATCH], f0[QWEN_TTS_MAX_BATCH], cnt[QWEN_TTS_MAX_BATCH];
+        float *outs[QWEN_TTS_MAX_BATCH];
+        for (int b = 0; b < nb; b++)
+            if (todo[b] > 0) {
+                ids[n] = b;
+                f0[n] = sdone[b];
+                cnt[n] = todo[b];
+                outs[n++] = sbufs[b] + (size_t)sdone[b] * 1920;
+                if (!T) T = todo[b];
+                same &= todo[b] == T;
+            }
+        if (!n) return 0;
+        const double t0 = now_ms();
+        const int r = same ? qtts_dev_codec_mstream_push_slots_at(dev, n, ids, ids, f0, T, outs)
+                           : qtts_dev_codec_mstream_push_slots_ragged(dev, n, ids, ids, f0, cnt, outs);
+        if (r < 0) return -1;
+        *t_stream += now_ms() - t0;
+        for (int i = 0; i < n; i++) {
+            if (stream->bcb) stream->bcb(ids[i], outs[i], cnt[i] * 1920, stream->user);
+            sdone[ids[i]] += cnt[i];
+        }
+        return 0;
+    }
     for (;;) {
         int T = 0, n = 0, ids[QWEN_TTS_MAX_BATCH];
         float *outs[QWEN_TTS_MAX_BATCH];
@@ -966,6 +994,7 @@ static int run_batch(qwen_tts_ctx_t *ctx, int nb, const char *const *texts, cons
         return -1;
     }
     prompt_t *pr = (prompt_t *)calloc(nb, sizeof(prompt_t));
+    int *prime_codes = NULL;   /* the reference frames of a streamed voice-clone batch, kept until the run ends */
     int max_p = 0;
     for (int b = 0; b < nb; b++) {
         int *ids = NULL;
@@ -1010,7 +1039,28 @@ static int run_batch(qwen_tts_ctx_t *ctx, int nb, const char *const *texts, cons
      * prefill runs (qtts_dev_codec_stream_prime); later pushes wait for them. */
     const int sref = stream && vcs && vcs[0].ref_codes && vcs[0].n_ref > 0 ? vcs[0].n_ref : 0;
     const int multi = stream && stream->multi;
-    if (multi) {
+    /* a streamed voice-clone batch: the same for every ICL slot, all their
+     * reference frames in ONE ragged push of the multi-stream codec
+     * (qtts_dev_codec_mstream_prime); an x-vector-only slot has none and its
+     * stream stays at position 0 */
+    int mref[QWEN_TTS_MAX_BATCH], *msref = NULL;
+    if (multi && vcs) {
+        int n = 0, ld = 0, ids[QWEN_TTS_MAX_BATCH], cnt[QWEN_TTS_MAX_BATCH];
+        for (int b = 0; b < nb; b++) {
+            mref[b] = vcs[b].ref_codes && vcs[b].n_ref > 0 ? vcs[b].n_ref : 0;
+            if (mref[b] > ld) ld = mref[b];
+            if (mref[b]) { ids[n] = b; cnt[n++] = mref[b]; }
+        }
+        msref = mref;
+        if (qtts_dev_codec_mstream_begin(dev, nb, max_tokens + ld, 0) != 0) goto out;
+        if (n) {
+            prime_codes = (int *)calloc((size_t)n * ld * 16, sizeof(int));
+            if (!prime_codes) goto out;
+            for (int i = 0; i < n; i++)
+                memcpy(prime_codes + (size_t)i * ld * 16, vcs[ids[i]].ref_codes, (size_t)cnt[i] * 16 * sizeof(int));
+            if (qtts_dev_codec_mstream_prime(dev, n, ids, prime_codes, cnt, ld) != 0) goto out;
+        }
+    } else if (multi) {
         if (qtts_dev_codec_mstream_begin(dev, nb, max_tokens, 0) != 0) goto out;
     } else if (stream && (qtts_dev_codec_stream_begin_ex(dev, max_tokens + sref, sref) != 0 ||
                           (sref && qtts_dev_codec_stream_prime(dev, vcs[0].ref_codes, sref) != 0)))
@@ -1068,7 +1118,7 @@ static int run_batch(qwen_tts_ctx_t *ctx, int nb, const char *const *texts, cons
         if (want_stream || (poll_every && ((step + 1) % poll_every == 0 || step + 1 == max_tokens))) {
             qtts_dev_poll(dev, stopped, ngen, sstep);
             if (multi) {
-                if (batch_stream_flush(dev, nb, stream, ngen, sdone, sbufs, &t_stream) != 0) {
+                if (batch_stream_flush(dev, nb, stream, ngen, sdone, sbufs, &t_stream, msref) != 0) {
                     free_bufs(sbufs, nb); free(sdone); free(sbuf); free(stopped); free(ngen); free(sstep); goto out;
                 }
                 if (streamed == 0) ctx->perf_first_packet_ms = now_ms() - t_start;
@@ -1093,7 +1143,7 @@ static int run_batch(qwen_tts_ctx_t *ctx, int nb, const char *const *texts, cons
     }
     qtts_dev_poll(dev, stopped, ngen, sstep);
     if (multi) {
-        if (batch_stream_flush(dev, nb, stream, ngen, sdone, sbufs, &t_stream) != 0) {
+        if (batch_stream_flush(dev, nb, stream, ngen, sdone, sbufs, &t_stream, msref) != 0) {
             free_bufs(sbufs, nb); free(sdone); free(sbuf); free(stopped); free(ngen); free(sstep); goto out;
         }
         if (streamed == 0) ctx->perf_first_packet_ms = now_ms() - t_start;
@@ -1239,6 +1289,7 @@ static int run_batch(qwen_tts_ctx_t *ctx, int nb, const char *const *texts, cons
 out:
     force_free(arm);
     sampling_free(sarm);
+    free(prime_codes);
     for (int b = 0; b < nb; b++) { free(pr[b].text); free(pr[b].plan); }
     free(pr);
     return rc;
@@ -1647,9 +1698,11 @@ int qwen_tts_queue_codes(qwen_tts_ctx_t *ctx, int i, int *codes, int max_frames)
 static int vclone_run(qwen_tts_ctx_t *ctx, int nb, const char *const *texts, const char *const *ref_texts,
                       const int *const *ref_codes, const int *n_ref_frames, const float *const *spk_embeds,
                       const char *const *languages, int non_streaming, float **out_audio, int *out_samples,
-                      const stream_t *stream) {
-    if (!ctx || nb < 1 || !texts || !out_audio || !out_samples || (stream && nb != 1)) return -1;
-    if (batch_refused(ctx, "qwen_tts_generate_voice_clone_batch", nb)) return -1;
+                      const stream_t *stream, double t_start) {
+    if (!ctx || nb < 1 || !texts || !out_audio || !out_samples || (stream && !stream->multi && nb != 1)) return -1;
+    if (batch_refused(ctx, stream && stream->multi ? "qwen_tts_generate_voice_clone_batch_stream"
+                                                   : "qwen_tts_generate_voice_clone_batch", nb))
+        return -1;
     for (int b = 0; b < nb; b++) { out_audio[b] = NULL; out_samples[b] = 0; }
     vclone_t *vcs = (vclone_t *)calloc(nb, sizeof(vclone_t));
     int rc = vcs ? 0 : -1;
@@ -1683,7 +1736,9 @@ static int vclone_run(qwen_tts_ctx_t *ctx, int nb, const char *const *texts, con
         vc->ref_codes = codes;
         vc->n_ref = nref;
     }
-    if (rc == 0) rc = run_batch(ctx, nb, texts, NULL, languages, out_audio, out_samples, now_ms(), stream, vcs);
+    if (rc == 0)
+        rc = run_batch(ctx, nb, texts, NULL, languages, out_audio, out_samples, t_start > 0 ? t_start : now_ms(), stream,
+                       vcs);
     else force_disarm(ctx);   /* (the call consumes an arming also when it fails before the run) */
     if (vcs)
         for (int b = 0; b < nb; b++) free((void *)vcs[b].ref_ids);
@@ -1697,7 +1752,36 @@ int qwen_tts_generate_voice_clone_batch(qwen_tts_ctx_t *ctx, int nb, const char 
                                         const char *const *languages, int non_streaming, float **out_audio,
                                         int *out_samples) {
     return vclone_run(ctx, nb, texts, ref_texts, ref_codes, n_ref_frames, spk_embeds, languages, non_streaming,
-                      out_audio, out_samples, NULL);
+                      out_audio, out_samples, NULL, 0);
+}
+
+static int vclone_batch_stream(qwen_tts_ctx_t *ctx, int nb, const char *const *texts, const char *const *ref_texts,
+                               const int *const *ref_codes, const int *n_ref_frames, const float *const *spk_embeds,
+                               const char *const *languages, int non_streaming, int chunk_frames,
+                               qwen_tts_batch_audio_cb cb, void *userdata, float **out_audio, int *out_samples,
+                               double t_start) {
+    stream_t st = {NULL, userdata, chunk_frames > 0 ? chunk_frames : 1, 1, cb};
+    if (ctx) ctx->perf_first_packet_ms = 0;
+    const int rc = vclone_run(ctx, nb, texts, ref_texts, ref_codes, n_ref_frames, spk_embeds, languages, non_streaming,
+                              out_audio, out_samples, &st, t_start);
+    if (rc == 0 && qwen_tts_verbose >= 1) {
+        double secs = 0;
+        for (int b = 0; b < nb; b++) secs += (double)out_samples[b] / QWEN_TTS_SAMPLE_RATE;
+        fprintf(stderr, "First packet: %.1f ms\n", ctx->perf_first_packet_ms);
+        fprintf(stderr, "Total: %.1f ms (%.2f s audio over %d utterances, %.2fx realtime)\n", ctx->perf_total_ms, secs,
+                nb, secs / (ctx->perf_total_ms / 1000.0));
+    }
+    return rc;
+}
+
+int qwen_tts_generate_voice_clone_batch_stream(qwen_tts_ctx_t *ctx, int nb, const char *const *texts,
+                                               const char *const *ref_texts, const int *const *ref_codes,
+                                               const int *n_ref_frames, const float *const *spk_embeds,
+                                               const char *const *languages, int non_streaming, int chunk_frames,
+                                               qwen_tts_batch_audio_cb cb, void *userdata, float **out_audio,
+                                               int *out_samples) {
+    return vclone_batch_stream(ctx, nb, texts, ref_texts, ref_codes, n_ref_frames, spk_embeds, languages,
+                               non_streaming, chunk_frames, cb, userdata, out_audio, out_samples, now_ms());
 }
 
 float *qwen_tts_generate_voice_clone_stream(qwen_tts_ctx_t *ctx, const char *text, const char *ref_text,
@@ -1714,7 +1798,8 @@ float *qwen_tts_generate_voice_clone_stream(qwen_tts_ctx_t *ctx, const char *tex
     const int nr1[1] = {n_ref_frames};
     const float *sv1[1] = {spk_embed};
     ctx->perf_first_packet_ms = 0;
-    if (vclone_run(ctx, 1, texts, rt, rc1, nr1, sv1, lang, non_streaming, &audio, &n, &st) != 0 || !audio || n <= 0) {
+    if (vclone_run(ctx, 1, texts, rt, rc1, nr1, sv1, lang, non_streaming, &audio, &n, &st, 0) != 0 || !audio ||
+        n <= 0) {
         free(audio);
         return NULL;
     }
@@ -1781,11 +1866,16 @@ int *qwen_tts_encode_audio(qwen_tts_ctx_t *ctx, const float *wav, int n_samples,
  * encode, :427), each x-vector on its own audio (:446), then the codes /
  * x-vector voice clone above.  x_vector_only[b] (NULL: all 0) drops the codes
  * of slot b (ref_code=None, :451). */
-int qwen_tts_generate_voice_clone_audio_batch(qwen_tts_ctx_t *ctx, int nb, const char *const *texts,
-                                              const char *const *ref_texts, const float *const *ref_wavs,
-                                              const int *n_ref_samples, const char *const *languages,
-                                              const int *x_vector_only, int non_streaming, float **out_audio,
-                                              int *out_samples) {
+typedef struct {                 /* the streamed form's extra arguments */
+    int chunk_frames;
+    qwen_tts_batch_audio_cb cb;
+    void *userdata;
+} vc_bstream_t;
+
+static int vclone_audio_run(qwen_tts_ctx_t *ctx, int nb, const char *const *texts, const char *const *ref_texts,
+                            const float *const *ref_wavs, const int *n_ref_samples, const char *const *languages,
+                            const int *x_vector_only, int non_streaming, float **out_audio, int *out_samples,
+                            const vc_bstream_t *bs) {
     if (!ctx || !ctx->hip || nb < 1 || nb > 16 || !texts || !ref_wavs || !n_ref_samples || !out_audio ||
         !out_samples) {
         fprintf(stderr, "Error: voice clone from audio needs 1..16 utterances with reference audio\n");
@@ -1832,14 +1922,39 @@ int qwen_tts_generate_voice_clone_audio_batch(qwen_tts_ctx_t *ctx, int nb, const
         const char *const *rt = ref_texts;
         const char *none[16] = {NULL};
         if (!rt) rt = none;
-        rc = qwen_tts_generate_voice_clone_batch(ctx, nb, texts, rt, rc_p, nr, sv, languages, non_streaming, out_audio,
-                                                 out_samples);
+        /* (streamed: the first packet counts from this call's entry, the encoders included) */
+        if (bs)
+            rc = vclone_batch_stream(ctx, nb, texts, rt, rc_p, nr, sv, languages, non_streaming, bs->chunk_frames,
+                                     bs->cb, bs->userdata, out_audio, out_samples, t0);
+        else
+            rc = qwen_tts_generate_voice_clone_batch(ctx, nb, texts, rt, rc_p, nr, sv, languages, non_streaming,
+                                                     out_audio, out_samples);
     } else {
         force_disarm(ctx);
     }
     free(codes);
     free(xv);
     return rc;
+}
+
+int qwen_tts_generate_voice_clone_audio_batch(qwen_tts_ctx_t *ctx, int nb, const char *const *texts,
+                                              const char *const *ref_texts, const float *const *ref_wavs,
+                                              const int *n_ref_samples, const char *const *languages,
+                                              const int *x_vector_only, int non_streaming, float **out_audio,
+                                              int *out_samples) {
+    return vclone_audio_run(ctx, nb, texts, ref_texts, ref_wavs, n_ref_samples, languages, x_vector_only,
+                            non_streaming, out_audio, out_samples, NULL);
+}
+
+int qwen_tts_generate_voice_clone_audio_batch_stream(qwen_tts_ctx_t *ctx, int nb, const char *const *texts,
+                                                     const char *const *ref_texts, const float *const *ref_wavs,
+                                                     const int *n_ref_samples, const char *const *languages,
+                                                     const int *x_vector_only, int non_streaming, int chunk_frames,
+                                                     qwen_tts_batch_audio_cb cb, void *userdata, float **out_audio,
+                                                     int *out_samples) {
+    const vc_bstream_t bs = {chunk_frames, cb, userdata};
+    return vclone_audio_run(ctx, nb, texts, ref_texts, ref_wavs, n_ref_samples, languages, x_vector_only,
+                            non_streaming, out_audio, out_samples, &bs);
 }
 
 /* streaming form of qwen_tts_generate_voice_clone_audio: the reference audio
@@ -1966,6 +2081,13 @@ int qwen_tts_codec_mstream_push_any(qwen_tts_ctx_t *ctx, int n, const int *strea
                                     float *const *out) {
     if (!ctx || !ctx->hip || !streams || !codes || !out) return -1;
     return qtts_dev_codec_mstream_push_host_any((qtts_dev_t *)ctx->hip, n, streams, codes, time_steps, out);
+}
+
+int qwen_tts_codec_mstream_push_ragged(qwen_tts_ctx_t *ctx, int n, const int *streams, const int *codes,
+                                       const int *counts, int ld_frames, float *const *out) {
+    if (!ctx || !ctx->hip || !streams || !codes || !out) return -1;
+    /* (a NULL counts is the device layer's refusal, with its message) */
+    return qtts_dev_codec_mstream_push_host_ragged((qtts_dev_t *)ctx->hip, n, streams, codes, counts, ld_frames, out);
 }
 
 int qwen_tts_codec_mstream_reset(qwen_tts_ctx_t *ctx, int stream) {

@@ -118,6 +118,9 @@ EXPORTS = [
     "qtts_dev_codec_mstream_pos", "qtts_hip_xgemm_seg_case",
     "qwen_tts_generate_queue_stream", "qwen_tts_codec_mstream_push_any", "qwen_tts_codec_mstream_reset",
     "qtts_dev_codec_mstream_push_host_any", "qtts_dev_codec_mstream_push_slots_at", "qtts_dev_codec_mstream_reset",
+    "qwen_tts_codec_mstream_push_ragged", "qtts_dev_codec_mstream_push_host_ragged",
+    "qtts_dev_codec_mstream_push_slots_ragged", "qtts_dev_codec_mstream_prime",
+    "qwen_tts_generate_voice_clone_batch_stream", "qwen_tts_generate_voice_clone_audio_batch_stream",
 ]
 
 MAX_BATCH = 64   # QWEN_TTS_MAX_BATCH / QTTS_HIP_MAX_BATCH: lock-step slots per context
@@ -312,6 +315,24 @@ def lib():
         L.qtts_dev_codec_mstream_push_slots_at.argtypes = [C.c_void_p, C.c_int, _ip, _ip, _ip, C.c_int,
                                                            C.POINTER(_fp)]
         L.qtts_dev_codec_mstream_reset.argtypes = [C.c_void_p, C.c_int]
+    # (nor the ragged pushes)
+    if hasattr(L, "qwen_tts_codec_mstream_push_ragged"):
+        L.qwen_tts_codec_mstream_push_ragged.argtypes = [C.POINTER(Ctx), C.c_int, _ip, _ip, _ip, C.c_int,
+                                                         C.POINTER(_fp)]
+        L.qtts_dev_codec_mstream_push_host_ragged.argtypes = [C.c_void_p, C.c_int, _ip, _ip, _ip, C.c_int,
+                                                              C.POINTER(_fp)]
+        L.qtts_dev_codec_mstream_push_slots_ragged.argtypes = [C.c_void_p, C.c_int, _ip, _ip, _ip, _ip,
+                                                               C.POINTER(_fp)]
+        L.qtts_dev_codec_mstream_prime.argtypes = [C.c_void_p, C.c_int, _ip, _ip, _ip, C.c_int]
+        L.qwen_tts_generate_voice_clone_batch_stream.restype = C.c_int
+        L.qwen_tts_generate_voice_clone_batch_stream.argtypes = [
+            C.POINTER(Ctx), C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.POINTER(_ip), _ip,
+            C.POINTER(_fp), C.POINTER(C.c_char_p), C.c_int, C.c_int, BATCH_AUDIO_CB, C.c_void_p,
+            C.POINTER(C.c_void_p), _ip]
+        L.qwen_tts_generate_voice_clone_audio_batch_stream.restype = C.c_int
+        L.qwen_tts_generate_voice_clone_audio_batch_stream.argtypes = [
+            C.POINTER(Ctx), C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.POINTER(_fp), _ip,
+            C.POINTER(C.c_char_p), _ip, C.c_int, C.c_int, BATCH_AUDIO_CB, C.c_void_p, C.POINTER(C.c_void_p), _ip]
     L.qwen_tts_speaker_embedding.restype = C.c_void_p
     L.qwen_tts_speaker_embedding.argtypes = [C.POINTER(Ctx), _fp, C.c_int, _ip]
     L.qwen_tts_encode_audio.restype = C.c_void_p
@@ -619,6 +640,58 @@ class QwenTTS:
                                                       ns)
         return r, [_take_audio(out[i], ns[i]) for i in range(nb)]
 
+    def generate_voice_clone_batch_stream(self, id_lists, ref_id_lists, ref_codes, spk_embeds=None, languages=None,
+                                          non_streaming=False, chunk_frames=4, on_chunk=None):
+        """generate_voice_clone_batch with every utterance streamed
+        (qwen_tts_generate_voice_clone_batch_stream): on_chunk(b, np.ndarray)
+        gets slot b's chunks as they are decoded.  Returns (rc, [audio])."""
+        nb = len(id_lists)
+        enc = lambda ids: ",".join(str(int(i)) for i in ids).encode() if ids is not None else None
+        tx = (C.c_char_p * nb)(*[enc(i) for i in id_lists])
+        rt = (C.c_char_p * nb)(*[enc(i) for i in (ref_id_lists or [None] * nb)])
+        keep = [None if c is None else np.ascontiguousarray(c, np.int32) for c in (ref_codes or [None] * nb)]
+        rc = (_ip * nb)(*[None if c is None else c.ctypes.data_as(_ip) for c in keep])
+        nr = (C.c_int * nb)(*[0 if c is None else c.shape[0] for c in keep])
+        sk = [None if v is None else np.ascontiguousarray(v, np.float32) for v in (spk_embeds or [None] * nb)]
+        sv = (_fp * nb)(*[None if v is None else v.ctypes.data_as(_fp) for v in sk])
+        lg = (C.c_char_p * nb)(*[(s.encode() if s else None) for s in (languages or [None] * nb)])
+        out = (C.c_void_p * nb)()
+        ns = (C.c_int * nb)()
+
+        def _cb(i, p, k, u):
+            if on_chunk is not None:
+                on_chunk(int(i), np.ctypeslib.as_array(p, shape=(k,)).copy())
+        cb = BATCH_AUDIO_CB(_cb)
+        r = lib().qwen_tts_generate_voice_clone_batch_stream(self.ctx, nb, tx, rt, rc, nr, sv, lg, int(non_streaming),
+                                                             int(chunk_frames), cb, None, out, ns)
+        self._last_nb = nb
+        return r, [_take_audio(out[i], ns[i]) for i in range(nb)]
+
+    def generate_voice_clone_audio_batch_stream(self, id_lists, ref_wavs, ref_id_lists=None, languages=None,
+                                                x_vector_only=None, non_streaming=False, chunk_frames=4,
+                                                on_chunk=None):
+        """generate_voice_clone_audio_batch with every utterance streamed
+        (qwen_tts_generate_voice_clone_audio_batch_stream).  Returns (rc, [audio])."""
+        nb = len(id_lists)
+        enc = lambda ids: ",".join(str(int(i)) for i in ids).encode() if ids is not None else None
+        tx = (C.c_char_p * nb)(*[enc(i) for i in id_lists])
+        rt = (C.c_char_p * nb)(*[enc(i) for i in (ref_id_lists or [None] * nb)])
+        ws, wp, ns = self._wav_args(ref_wavs)
+        lg = (C.c_char_p * nb)(*[(s.encode() if s else None) for s in (languages or [None] * nb)])
+        xo = (C.c_int * nb)(*[int(bool(v)) for v in (x_vector_only or [False] * nb)])
+        out = (C.c_void_p * nb)()
+        on = (C.c_int * nb)()
+
+        def _cb(i, p, k, u):
+            if on_chunk is not None:
+                on_chunk(int(i), np.ctypeslib.as_array(p, shape=(k,)).copy())
+        cb = BATCH_AUDIO_CB(_cb)
+        r = lib().qwen_tts_generate_voice_clone_audio_batch_stream(self.ctx, nb, tx, rt, wp, ns, lg, xo,
+                                                                   int(non_streaming), int(chunk_frames), cb, None,
+                                                                   out, on)
+        self._last_nb = nb
+        return r, [_take_audio(out[i], on[i]) for i in range(nb)]
+
     # ---- voice-clone audio encoders (include/qtts_hip.h qtts_dev_speaker_embed / _encode_audio)
     def encoders_available(self):
         """bit 0: speaker encoder, bit 1: 12 Hz encoder."""
@@ -907,6 +980,34 @@ class QwenTTS:
         """codec_mstream_push for streams at different positions
         (qwen_tts_codec_mstream_push_any): the same arguments and result"""
         return self.codec_mstream_push(streams, codes, any_position=True)
+
+    def codec_mstream_push_ragged(self, streams, code_list, counts=None, ld_frames=None, fill=0.0):
+        """Stream streams[i] advances by its own number of frames in one push
+        (qwen_tts_codec_mstream_push_ragged): code_list[i] is its [t_i, 16]
+        codes.  Returns [t_i * 1920 samples] per stream, or None where the
+        library refuses the push (-1; nothing decoded).  counts / ld_frames
+        override what the lists imply (the refusal tests); each output buffer
+        is ld_frames * 1920 long, filled with `fill` beforehand, and cut to
+        counts[i] * 1920 only when counts is not given."""
+        st = np.ascontiguousarray(streams, np.int32)
+        n = len(st)
+        cl = [np.asarray(c, np.int32).reshape(-1, 16) for c in code_list]
+        ld = int(ld_frames) if ld_frames is not None else max([len(c) for c in cl] + [1])
+        codes = np.zeros((max(n, 1), ld, 16), np.int32)
+        for i, c in enumerate(cl):
+            codes[i, :min(len(c), ld)] = c[:ld]
+        cn = None if counts is None else np.ascontiguousarray(counts, np.int32)
+        cnt = np.asarray([len(c) for c in cl], np.int32) if cn is None else cn
+        outs = [np.full(ld * 1920, fill, np.float32) for _ in range(n)]
+        po = (_fp * max(n, 1))(*[o.ctypes.data_as(_fp) for o in outs])
+        cp = cnt.ctypes.data_as(_ip) if counts is None or len(cnt) else None
+        k = lib().qwen_tts_codec_mstream_push_ragged(self.ctx, n, st.ctypes.data_as(_ip), codes.ctypes.data_as(_ip),
+                                                     cp, ld, po)
+        if k < 0:
+            return None
+        if k != int(cnt.max()) * 1920:
+            raise RuntimeError(f"codec mstream ragged push returned {k}")
+        return outs if counts is not None else [o[:int(c) * 1920] for o, c in zip(outs, cnt)]
 
     def codec_mstream_reset(self, stream):
         """one stream back to position 0, the others untouched; 0 or -1"""
