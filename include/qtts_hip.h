@@ -357,6 +357,34 @@ int qtts_dev_codec_mstream_push_slots_ragged(qtts_dev_t *dev, int n, const int *
                                              const int *frame0, const int *count, float *const *host_out);
 int qtts_dev_codec_mstream_prime(qtts_dev_t *dev, int n, const int *streams, const int *codes, const int *counts,
                                  int ld_frames);
+/* One stream's carried state saved and restored ("Snapshots"): a
+ * stream primed once with a voice's reference frames is put into any stream
+ * of any later begin in one launch instead of being primed again.  A snapshot
+ * is a compact device buffer (the stream's planes of the 21 history slots,
+ * then K / V rows 0..hl-1 of every layer, each part padded to 4 floats: 0.54 MB
+ * + at most 4.65 MB at the 1.7B codec dims) and a host header (position, hl,
+ * the codec dims, the device).  It holds nothing that depends on the stream
+ * count or the pass size, so it survives a begin with other ones.
+ * _save: a new snapshot of `stream`, the stream untouched; NULL on refusal.
+ * _restore: writes the history planes and K/V rows 0..hl-1 of `stream` and
+ *   takes over the snapshot's position and hl; rows at hl and above stay (as
+ *   after a reset, none is inside a new row's window).
+ * Both are ONE launch on the context stream, after a pending prime is joined
+ * by event, and wait for nothing on the host.  Refusals (NULL / -1, a message,
+ * nothing launched, stream and snapshot as they were): no begin or a state
+ * re-allocated since; a bad stream index; a NULL or freed snapshot; a snapshot
+ * saved on another context (or whose codec dims or device differ); a restore
+ * whose position exceeds the begin's max_frames.
+ * _snapshot_free: releases one (NULL, a freed pointer: nothing happens).
+ * qtts_dev_destroy releases the device memory of the context's live snapshots;
+ * they stay refusable and freeable.  _snapshot_pos / _snapshot_bytes: the
+ * frames it stands at / its device bytes; -1 for a NULL, freed or orphaned one. */
+typedef struct qtts_codec_snapshot qtts_codec_snapshot_t;
+qtts_codec_snapshot_t *qtts_dev_codec_mstream_save(qtts_dev_t *dev, int stream);
+int qtts_dev_codec_mstream_restore(qtts_dev_t *dev, int stream, const qtts_codec_snapshot_t *snap);
+void qtts_dev_codec_snapshot_free(qtts_codec_snapshot_t *snap);
+int qtts_dev_codec_snapshot_pos(const qtts_codec_snapshot_t *snap);
+long long qtts_dev_codec_snapshot_bytes(const qtts_codec_snapshot_t *snap);
 
 /* The same exact streaming decode overlapped with the decode loop: it runs on
  * a second (low-priority) HIP stream; push orders itself after the frames

@@ -540,6 +540,76 @@ int qwen_tts_generate_queue_stream(qwen_tts_ctx_t *ctx, int nq, const char *cons
                                    int chunk_frames, qwen_tts_batch_audio_cb cb, void *cb_userdata, float **out_audio,
                                    int *out_samples);
 
+/* One multi-stream codec stream's carried state saved and restored
+ * (qtts_hip.h qtts_dev_codec_mstream_save / _restore; DESIGN.md 7,
+ * "Snapshots").  save: a snapshot of `stream` (the stream untouched), NULL on
+ * refusal; restore: `stream` continues from the snapshot's position, whatever
+ * it held before and whatever begin (stream count, max_frames) is active; both
+ * one launch, stream-ordered, no host wait.  -1 / NULL with a message, nothing
+ * launched and nothing changed for: no begin, a bad stream, a NULL or freed
+ * snapshot, a snapshot of another context, a position beyond max_frames.
+ * snapshot_free releases one (NULL / already freed: nothing happens);
+ * qwen_tts_free releases the device memory of its context's live snapshots
+ * (they are then refused and may still be freed).  snapshot_pos: the frames
+ * it stands at, -1 for a NULL, freed or orphaned one. */
+typedef struct qtts_codec_snapshot qwen_tts_codec_snapshot_t;
+qwen_tts_codec_snapshot_t *qwen_tts_codec_mstream_save(qwen_tts_ctx_t *ctx, int stream);
+int qwen_tts_codec_mstream_restore(qwen_tts_ctx_t *ctx, int stream, const qwen_tts_codec_snapshot_t *snap);
+void qwen_tts_codec_snapshot_free(qwen_tts_codec_snapshot_t *snap);
+int qwen_tts_codec_snapshot_pos(const qwen_tts_codec_snapshot_t *snap);
+
+/* Voice handles: a cloned voice made once and used by any number of later
+ * calls on the same context.  A handle owns copies of the reference text ids,
+ * the reference codes and the speaker x-vector, and -- for an ICL voice, made
+ * by the first streamed call that uses it -- one codec snapshot of its
+ * reference frames, which every later streamed call restores instead of
+ * pushing the reference frames through the codec again.
+ * qwen_tts_voice_create: ref_text / ref_codes [n_ref_frames][16] / spk_embed
+ *   [hidden] as qwen_tts_generate_voice_clone takes them, with its checks and
+ *   messages (codes or an embedding; ICL needs >= 5 reference ids, in range).
+ *   No device work.  NULL on error.
+ * qwen_tts_voice_create_audio: runs the 12 Hz encoder and the speaker encoder
+ *   once on ref_wav (24 kHz mono), then the same; x_vector_only drops the codes.
+ * qwen_tts_voice_info: the reference frames (0: x-vector only) and whether the
+ *   primed snapshot exists (each may be NULL); 0, or -1 for a NULL handle.
+ * qwen_tts_voice_free: releases the handle and its snapshot (also after its
+ *   context was freed).
+ * A handle is refused by a context other than the one that made it. */
+typedef struct qwen_tts_voice qwen_tts_voice_t;
+qwen_tts_voice_t *qwen_tts_voice_create(qwen_tts_ctx_t *ctx, const char *ref_text, const int *ref_codes,
+                                        int n_ref_frames, const float *spk_embed);
+qwen_tts_voice_t *qwen_tts_voice_create_audio(qwen_tts_ctx_t *ctx, const char *ref_text, const float *ref_wav,
+                                              int n_ref_samples, int x_vector_only);
+int qwen_tts_voice_info(const qwen_tts_voice_t *v, int *n_ref_frames, int *primed);
+void qwen_tts_voice_free(qwen_tts_voice_t *v);
+/* The voice-clone work queue: qwen_tts_generate_queue / _queue_stream with
+ * utterance i spoken in voices[i] (one handle per utterance, repeats allowed)
+ * through the ICL prompt of qwen_tts_generate_voice_clone.  Admission (`next`),
+ * refill, retire, tail compaction, the ctx->queue_* results,
+ * qwen_tts_queue_codes (generated frames only), per-utterance sampling by
+ * input index and the refusal of armed forcing are the queue's; every
+ * utterance's codes are those of qwen_tts_generate_voice_clone run alone.  A
+ * NULL entry of voices or a handle of another context fails the call before
+ * the device is touched.
+ * Plain form: each utterance's codec pass at the end decodes reference ++
+ *   generated codes and cuts at the float position of
+ *   qwen_tts_generate_voice_clone_batch.
+ * Streamed form: the call's ICL voices that have no snapshot yet are primed
+ *   first (at most `nb` at a time in one ragged push, audio dropped) and saved;
+ *   an admission, initial or refill, resets the slot's stream and restores its
+ *   voice's snapshot (an x-vector-only voice: the reset alone).  Delivery is
+ *   qwen_tts_generate_queue_stream's; out_audio[u] starts at the reference
+ *   boundary (the frame-boundary cut of qwen_tts_generate_voice_clone_stream). */
+int qwen_tts_generate_voice_queue(qwen_tts_ctx_t *ctx, int nq, const char *const *texts,
+                                  const qwen_tts_voice_t *const *voices, const char *const *languages,
+                                  int non_streaming, int nb, qwen_tts_queue_next_cb next, void *userdata,
+                                  float **out_audio, int *out_samples);
+int qwen_tts_generate_voice_queue_stream(qwen_tts_ctx_t *ctx, int nq, const char *const *texts,
+                                         const qwen_tts_voice_t *const *voices, const char *const *languages,
+                                         int non_streaming, int nb, qwen_tts_queue_next_cb next, void *userdata,
+                                         int chunk_frames, qwen_tts_batch_audio_cb cb, void *cb_userdata,
+                                         float **out_audio, int *out_samples);
+
 /* Text input (the reference's TODO at c/qwen_tts.c:1071-1077,
  * its browser front end tokenizes with @huggingface/transformers,
  * web/wasm/app.js:241-267): Qwen2 byte-level BPE over the model directory's

@@ -2403,6 +2403,38 @@ __global__ void k_hist_reset_ms(float *const *base, const int *elems, int stream
     float *p = base[blockIdx.y] + (size_t)stream * n;
     for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) p[i] = 0.f;
 }
+// save / restore of one stream's carried state ("Snapshots"):
+// grid y = part, the nh history parts (elems[y] floats of the stream's plane)
+// then the K/V planes (kvn = hl * kvd floats from the top of the stream's S
+// rows; elems[y] is the plane stride there).  Part y sits in the snapshot at
+// soff[y] (history) or soff[nh] + (y - nh) * kvpad (K/V), each a multiple of 4
+// floats.  16-byte accesses where both sides are aligned, the last n % 4
+// floats (or a misaligned part) one by one
+__device__ __forceinline__ void ms_part_copy(float *dst, const float *src, int n) {
+    const int tid = blockIdx.x * 256 + threadIdx.x, nt = gridDim.x * 256;
+    int nv = 0;
+    if ((((uintptr_t)dst | (uintptr_t)src) & 15) == 0) {
+        nv = n >> 2;
+        const float4 *s4 = (const float4 *)src;
+        float4 *d4 = (float4 *)dst;
+        for (int i = tid; i < nv; i += nt) d4[i] = s4[i];
+    }
+    for (int i = 4 * nv + tid; i < n; i += nt) dst[i] = src[i];
+}
+__global__ void k_ms_state_save(float *const *base, const int *elems, const int *soff, int nh, int stream, int kvn,
+                                int kvpad, float *snap) {
+    const int y = blockIdx.y, n = y < nh ? elems[y] : kvn;
+    const float *state = base[y] + (size_t)stream * elems[y];
+    float *part = snap + (y < nh ? (size_t)soff[y] : (size_t)soff[nh] + (size_t)(y - nh) * kvpad);
+    ms_part_copy(part, state, n);
+}
+__global__ void k_ms_state_load(float *const *base, const int *elems, const int *soff, int nh, int stream, int kvn,
+                                int kvpad, const float *snap) {
+    const int y = blockIdx.y, n = y < nh ? elems[y] : kvn;
+    float *state = base[y] + (size_t)stream * elems[y];
+    const float *part = snap + (y < nh ? (size_t)soff[y] : (size_t)soff[nh] + (size_t)(y - nh) * kvpad);
+    ms_part_copy(state, part, n);
+}
 // k_dwconv per plane (grid y)
 __global__ void k_dwconv_ms(const float *x, size_t segx, int ldx, int tmin, const float *w, const float *b, int C,
                             int L, int K, float *y, size_t segy, int ldy) {
@@ -2804,15 +2836,29 @@ int codec_mstream_begin(CodecModel *m, int n_streams, int max_frames, int chunk)
     }
     rc |= ms_add_slot(S, C, 6);                         // final conv k7
     if (rc) return -1;
-    // the slots' table for the per-stream reset
-    const size_t nsl = S.hist.size();
-    std::vector<int> he(nsl);
-    for (size_t i = 0; i < nsl; ++i) he[i] = S.hist_c[i] * (S.hist_h[i] > 0 ? S.hist_h[i] : 1);
-    S.hist_base = (float **)msalloc(S, nsl * sizeof(float *));
-    S.hist_elems = (int *)msalloc(S, nsl * 4);
-    if (!S.hist_base || !S.hist_elems) return -1;
-    if (hipMemcpy(S.hist_base, S.hist.data(), nsl * sizeof(float *), hipMemcpyHostToDevice) != hipSuccess) return -1;
-    if (hipMemcpy(S.hist_elems, he.data(), nsl * 4, hipMemcpyHostToDevice) != hipSuccess) return -1;
+    // the carried parts' table: the slots for the per-stream reset, then the
+    // K/V planes for the save / restore of one stream
+    const size_t nsl = S.hist.size(), npart = nsl + (size_t)2 * d.clayers;
+    std::vector<float *> pb(S.hist);
+    std::vector<int> he(npart), so(nsl + 1);
+    int off = 0;
+    for (size_t i = 0; i < nsl; ++i) {
+        he[i] = S.hist_c[i] * (S.hist_h[i] > 0 ? S.hist_h[i] : 1);
+        so[i] = off;
+        off += (he[i] + 3) / 4 * 4;
+    }
+    so[nsl] = S.snap_hist_elems = off;
+    for (size_t i = nsl; i < npart; ++i) {
+        pb.push_back(S.kv + (i - nsl) * (size_t)ns * S.S * kvd);
+        he[i] = S.S * kvd;
+    }
+    S.hist_base = (float **)msalloc(S, npart * sizeof(float *));
+    S.hist_elems = (int *)msalloc(S, npart * 4);
+    S.snap_off = (int *)msalloc(S, (nsl + 1) * 4);
+    if (!S.hist_base || !S.hist_elems || !S.snap_off) return -1;
+    if (hipMemcpy(S.hist_base, pb.data(), npart * sizeof(float *), hipMemcpyHostToDevice) != hipSuccess) return -1;
+    if (hipMemcpy(S.hist_elems, he.data(), npart * 4, hipMemcpyHostToDevice) != hipSuccess) return -1;
+    if (hipMemcpy(S.snap_off, so.data(), (nsl + 1) * 4, hipMemcpyHostToDevice) != hipSuccess) return -1;
     if (hipDeviceSynchronize() != hipSuccess) return -1;
     S.active = true;
     return 0;
@@ -3037,4 +3083,108 @@ int codec_mstream_reset(CodecModel *m, int stream) {
     S.pos0[stream] = 0;
     S.hl[stream] = 0;
     return 0;
+}
+
+// ---- one stream's carried state, saved and restored ("Snapshots")
+namespace {
+// the refusals the two calls share; what: "save" / "restore"
+int ms_state_check(const CodecModel *m, int stream, const char *what) {
+    const CodecMStream &S = m->ms;
+    if (!S.active || !m->xg_part) {   // (a re-allocation of the codec state frees the streams with it)
+        fprintf(stderr, "qtts codec mstream: %s without begin\n", what);
+        return -1;
+    }
+    if (stream < 0 || stream >= S.ns) {
+        fprintf(stderr, "qtts codec mstream: stream %d out of range (0..%d)\n", stream, S.ns - 1);
+        return -1;
+    }
+    return 0;
+}
+
+int ms_kvd(const qtts_dims_t &d) { return d.ckv * (d.chid / d.cheads); }
+
+// grid of the state copy: x over the largest part in 16-byte units (at most 64 groups), y over the parts
+dim3 ms_state_grid(const CodecMStream &S, const qtts_dims_t &d, int kvn) {
+    int most = kvn;
+    for (size_t i = 0; i < S.hist.size(); ++i) {
+        const int e = S.hist_c[i] * (S.hist_h[i] > 0 ? S.hist_h[i] : 1);
+        if (e > most) most = e;
+    }
+    const int gx = (most / 4 + 255) / 256;
+    return dim3(gx < 1 ? 1 : gx > 64 ? 64 : gx, (unsigned)(S.hist.size() + 2 * d.clayers));
+}
+}  // namespace
+
+int codec_mstream_save(CodecModel *m, int stream, CodecSnapshot *snap) {
+    CodecMStream &S = m->ms;
+    const qtts_dims_t &d = m->d;
+    if (ms_state_check(m, stream, "save")) return -1;
+    if (!snap || snap->dev) {
+        fprintf(stderr, "qtts codec mstream: save takes an empty snapshot (got %s)\n", snap ? "one in use" : "NULL");
+        return -1;
+    }
+    const int kvd = ms_kvd(d), hl = S.hl[stream], kvn = hl * kvd, kvpad = (kvn + 3) / 4 * 4;
+    const size_t elems = (size_t)S.snap_hist_elems + (size_t)2 * d.clayers * kvpad;
+    int dev = -1;
+    float *buf = nullptr;
+    if (hipGetDevice(&dev) != hipSuccess || hipMalloc(&buf, (elems ? elems : 4) * 4) != hipSuccess) {
+        fprintf(stderr, "qtts codec mstream: save: no device memory for %zu bytes\n", elems * 4);
+        return -1;
+    }
+    hipLaunchKernelGGL(k_ms_state_save, ms_state_grid(S, d, kvn), dim3(256), 0, m->st, S.hist_base, S.hist_elems,
+                       S.snap_off, (int)S.hist.size(), stream, kvn, kvpad, buf);
+    if (hipGetLastError() != hipSuccess) {
+        hipFree(buf);
+        return -1;
+    }
+    snap->dev = buf;
+    snap->elems = elems;
+    snap->pos0 = S.pos0[stream];
+    snap->hl = hl;
+    snap->layers = d.clayers;
+    snap->kvd = kvd;
+    snap->win = d.cwin;
+    snap->slot_elems.resize(S.hist.size());
+    for (size_t i = 0; i < S.hist.size(); ++i) snap->slot_elems[i] = S.hist_c[i] * (S.hist_h[i] > 0 ? S.hist_h[i] : 1);
+    snap->device = dev;
+    return 0;
+}
+
+int codec_mstream_restore(CodecModel *m, int stream, const CodecSnapshot *snap) {
+    CodecMStream &S = m->ms;
+    const qtts_dims_t &d = m->d;
+    if (ms_state_check(m, stream, "restore")) return -1;
+    if (!snap || !snap->dev) {
+        fprintf(stderr, "qtts codec mstream: restore takes a saved snapshot (got %s)\n", snap ? "an empty one" : "NULL");
+        return -1;
+    }
+    const int kvd = ms_kvd(d);
+    int dev = -1;
+    bool same = hipGetDevice(&dev) == hipSuccess && dev == snap->device && snap->layers == d.clayers &&
+                snap->kvd == kvd && snap->win == d.cwin && snap->slot_elems.size() == S.hist.size();
+    for (size_t i = 0; same && i < S.hist.size(); ++i)
+        same = snap->slot_elems[i] == S.hist_c[i] * (S.hist_h[i] > 0 ? S.hist_h[i] : 1);
+    const int kvn = snap->hl * kvd, kvpad = (kvn + 3) / 4 * 4;
+    if (!same || snap->hl < 0 || snap->hl > d.cwin - 1 || snap->hl > snap->pos0 ||
+        snap->elems != (size_t)S.snap_hist_elems + (size_t)2 * d.clayers * kvpad) {
+        fprintf(stderr, "qtts codec mstream: restore: the snapshot is of another codec or device\n");
+        return -1;
+    }
+    if (snap->pos0 > S.max_frames) {
+        fprintf(stderr, "qtts codec mstream: stream %d: the snapshot's %d frames exceed the stream capacity %d\n",
+                stream, snap->pos0, S.max_frames);
+        return -1;
+    }
+    hipLaunchKernelGGL(k_ms_state_load, ms_state_grid(S, d, kvn), dim3(256), 0, m->st, S.hist_base, S.hist_elems,
+                       S.snap_off, (int)S.hist.size(), stream, kvn, kvpad, snap->dev);
+    if (hipGetLastError() != hipSuccess) return -1;
+    S.pos0[stream] = snap->pos0;
+    S.hl[stream] = snap->hl;
+    return 0;
+}
+
+void codec_snapshot_release(CodecSnapshot *snap) {
+    if (!snap) return;
+    if (snap->dev) hipFree(snap->dev);
+    *snap = CodecSnapshot();
 }

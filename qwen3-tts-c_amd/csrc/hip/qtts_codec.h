@@ -72,12 +72,33 @@ struct CodecMStream {
     std::vector<long long> hcoff;
     const int *pass_tv = nullptr;  // the running pass's tv (device) and frames, for its history saves
     int pass_T = 1;
-    float **hist_base = nullptr;   // device table of the history slots' base pointers and
-    int *hist_elems = nullptr;     // per-stream sizes (C * H), for the reset of one stream
+    // device table of the carried parts of one stream: the history slots'
+    // base pointers and per-stream sizes (C * H), for the reset of one stream,
+    // then the 2 * layers K/V planes (base of stream 0's rows, per-stream
+    // stride S * kvd), for the save / restore of one stream; snap_off: where
+    // each history part starts in a snapshot (floats), the total last
+    float **hist_base = nullptr;
+    int *hist_elems = nullptr;
+    int *snap_off = nullptr;
+    int snap_hist_elems = 0;       // floats of a snapshot's history parts (each padded to 4)
     float *wav = nullptr;          // [ns][tc * samples per frame], compact
     std::vector<float> hwav;       // its host copy
     size_t state_bytes = 0, scratch_bytes = 0;
     std::vector<void *> allocs;
+};
+
+// One stream's carried state outside the multi-stream state (codec_mstream_save
+// / _restore; DESIGN.md 7, "Snapshots"): a compact device buffer of the 21
+// history parts, then layers x 2 K/V parts of hl * kvd floats, every part
+// padded to a multiple of 4 floats, and the host header that says what it is.
+// It holds nothing that depends on the stream count or the pass size.
+struct CodecSnapshot {
+    float *dev = nullptr;
+    size_t elems = 0;              // floats allocated
+    int pos0 = 0, hl = 0;
+    int layers = 0, kvd = 0, win = 0;
+    std::vector<int> slot_elems;   // the history parts' sizes (C * H)
+    int device = -1;               // the HIP device that owns dev
 };
 
 struct CodecModel {
@@ -165,6 +186,19 @@ int codec_mstream_check_ragged(CodecModel *m, int n, const int *streams, const i
 int codec_mstream_push_ragged(CodecModel *m, int n, const int *streams, const int *codes_base,
                               const long long *code_off, int ldc, const int *counts, float *const *host_out);
 int codec_mstream_reset(CodecModel *m, int stream);
+// save: one stream's carried state into the empty snapshot `snap` (its device
+// buffer is allocated here; codec_snapshot_release frees it), one launch, the
+// stream untouched.  restore: the inverse into any stream of any begin of the
+// same codec (history planes and K/V rows 0..hl-1 written, then pos0 / hl
+// taken over; rows >= hl stay: none is inside a new row's window).  Both are
+// stream-ordered on m->st and wait for nothing on the host.  -1 with a
+// message, nothing launched and neither side changed for: no begin (or a
+// state re-allocated since), a bad stream, a NULL / empty (save: non-empty)
+// snapshot, a snapshot of other codec dims or another device, a restore
+// whose position exceeds max_frames.
+int codec_mstream_save(CodecModel *m, int stream, CodecSnapshot *snap);
+int codec_mstream_restore(CodecModel *m, int stream, const CodecSnapshot *snap);
+void codec_snapshot_release(CodecSnapshot *snap);
 int codec_mstream_pos(const CodecModel *m, int stream);
 void codec_mstream_free(CodecModel *m);
 

@@ -23,6 +23,7 @@
 
 #include <algorithm>
 #include <map>
+#include <mutex>
 #include <set>
 #include <string>
 #include <atomic>
@@ -208,6 +209,9 @@ struct qtts_dev {
     bool prime_pending = false;   // a qtts_dev_codec_stream_prime push runs on cst (cev marks its end)
     float *pwav = nullptr;        // the prime's discarded audio (never the codec_async output cwav)
     size_t pwav_cap = 0;
+    // the live codec snapshots saved on this context (qtts_dev_codec_mstream_save):
+    // destroy releases their device memory
+    std::vector<qtts_codec_snapshot_t *> snaps;
     // a batch's codec passes side by side (qtts_dev_codec_multi): lanes 1.. with
     // their own scratch and stream (lane 0 is `codec`), the waveforms and the
     // host-given codes staged on the device
@@ -565,11 +569,33 @@ extern "C" qtts_dev_t *qtts_dev_create(const qtts_dims_t *dims, int device) {
     return dv;
 }
 
+// A codec snapshot as the C-ABI hands it out: the codec's snapshot and the
+// context that saved it.  Every live one is in g_snaps, so a pointer that was
+// freed (or never was a snapshot) is refused by look-up, never dereferenced.
+// A snapshot outlives its context as a dead one (owner NULL, no device
+// memory) until it is freed.
+struct qtts_codec_snapshot {
+    CodecSnapshot s;
+    qtts_dev *owner = nullptr;
+};
+static std::mutex g_snaps_mu;
+static std::set<const qtts_codec_snapshot_t *> g_snaps;
+
+static void snapshots_orphan(qtts_dev *dv) {
+    std::lock_guard<std::mutex> lk(g_snaps_mu);
+    for (qtts_codec_snapshot_t *p : dv->snaps) {
+        codec_snapshot_release(&p->s);
+        p->owner = nullptr;
+    }
+    dv->snaps.clear();
+}
+
 extern "C" void qtts_dev_destroy(qtts_dev_t *dv) {
     if (!dv) return;
     hipSetDevice(dv->device);
     hipStreamSynchronize(dv->st);
     free_state(dv);
+    snapshots_orphan(dv);
     codec_destroy(&dv->codec);
     enc_destroy(&dv->enc);
     if (dv->cst) hipStreamSynchronize(dv->cst);
@@ -2552,6 +2578,71 @@ extern "C" int qtts_dev_codec_mstream_reset(qtts_dev_t *dv, int stream) {
 extern "C" int qtts_dev_codec_mstream_pos(qtts_dev_t *dv, int stream) {
     if (!dv) return -1;
     return codec_mstream_pos(&dv->codec, stream);
+}
+
+// One stream's carried state saved and restored ("Snapshots").
+// Both are one launch on the context stream after a pending prime is joined,
+// and wait for nothing on the host.
+extern "C" qtts_codec_snapshot_t *qtts_dev_codec_mstream_save(qtts_dev_t *dv, int stream) {
+    if (!dv) return nullptr;
+    hipSetDevice(dv->device);
+    if (join_prime(dv)) return nullptr;
+    qtts_codec_snapshot_t *p = new qtts_codec_snapshot_t();
+    if (codec_mstream_save(&dv->codec, stream, &p->s)) {
+        delete p;
+        return nullptr;
+    }
+    p->owner = dv;
+    std::lock_guard<std::mutex> lk(g_snaps_mu);
+    g_snaps.insert(p);
+    dv->snaps.push_back(p);
+    return p;
+}
+
+extern "C" int qtts_dev_codec_mstream_restore(qtts_dev_t *dv, int stream, const qtts_codec_snapshot_t *snap) {
+    if (!dv) return -1;
+    {
+        std::lock_guard<std::mutex> lk(g_snaps_mu);
+        if (!snap || !g_snaps.count(snap)) {
+            fprintf(stderr, "qtts codec mstream: restore takes a live snapshot (got %s)\n",
+                    snap ? "a freed one" : "NULL");
+            return -1;
+        }
+        if (snap->owner != dv) {
+            fprintf(stderr, "qtts codec mstream: restore: the snapshot belongs to %s\n",
+                    snap->owner ? "another context" : "a context that was freed");
+            return -1;
+        }
+    }
+    hipSetDevice(dv->device);
+    CKI(join_prime(dv));
+    return codec_mstream_restore(&dv->codec, stream, &snap->s);
+}
+
+extern "C" void qtts_dev_codec_snapshot_free(qtts_codec_snapshot_t *snap) {
+    std::lock_guard<std::mutex> lk(g_snaps_mu);
+    if (!snap || !g_snaps.count(snap)) return;
+    g_snaps.erase(snap);
+    if (qtts_dev *dv = snap->owner) {
+        hipSetDevice(dv->device);
+        hipStreamSynchronize(dv->st);   // a restore that reads it may still be queued
+        if (dv->cst) hipStreamSynchronize(dv->cst);
+        dv->snaps.erase(std::remove(dv->snaps.begin(), dv->snaps.end(), snap), dv->snaps.end());
+        codec_snapshot_release(&snap->s);
+    }
+    delete snap;
+}
+
+extern "C" int qtts_dev_codec_snapshot_pos(const qtts_codec_snapshot_t *snap) {
+    std::lock_guard<std::mutex> lk(g_snaps_mu);
+    if (!snap || !g_snaps.count(snap) || !snap->owner) return -1;
+    return snap->s.pos0;
+}
+
+extern "C" long long qtts_dev_codec_snapshot_bytes(const qtts_codec_snapshot_t *snap) {
+    std::lock_guard<std::mutex> lk(g_snaps_mu);
+    if (!snap || !g_snaps.count(snap) || !snap->owner) return -1;
+    return (long long)snap->s.elems * 4;
 }
 
 // ----------------------------------------------------------------- codec overlapped with the decode

@@ -1413,9 +1413,74 @@ static int queue_stream_flush(qwen_tts_ctx_t *ctx, qtts_dev_t *dev, qstream_t *q
     }
 }
 
+/* A voice handle (qwen_tts_voice_*): a cloned voice's prompt inputs, copied,
+ * and for an ICL voice the codec snapshot of its reference frames, made by
+ * the first streamed call that uses the handle */
+struct qwen_tts_voice {
+    qwen_tts_ctx_t *ctx;             /* the context that made it, and that context's device */
+    void *hip;
+    int *ref_ids, n_ref_ids;         /* ICL: ids of the reference text's chat template */
+    int *ref_codes, n_ref;           /* [n_ref][16]; NULL / 0: x-vector only */
+    float *spk;                      /* [hidden] or NULL */
+    qtts_codec_snapshot_t *snap;     /* the primed reference frames, or NULL */
+};
+
+static int voice_primed(const qwen_tts_voice_t *v) {
+    return v->snap && qtts_dev_codec_snapshot_pos(v->snap) == v->n_ref;
+}
+
+/* The streamed voice queue's priming: every distinct ICL voice of the call
+ * that has no snapshot yet goes through the codec streams once, at most ns
+ * voices at a time in one ragged push with the audio dropped, is saved, and
+ * the streams are reset.  Leaves every stream at position 0. */
+static int voices_prime(qtts_dev_t *dev, int nq, const qwen_tts_voice_t *const *voices, int ns, int max_ref,
+                        int **codes_keep /* the staged reference frames: the caller frees them when the run ends */) {
+    qwen_tts_voice_t **todo = (qwen_tts_voice_t **)calloc(nq, sizeof(*todo));
+    int nt = 0, rc = todo ? 0 : -1;
+    for (int i = 0; i < nq && todo; i++) {
+        qwen_tts_voice_t *v = (qwen_tts_voice_t *)voices[i];   /* (the handle gains its snapshot here) */
+        int seen = v->n_ref <= 0 || voice_primed(v);
+        for (int k = 0; k < nt && !seen; k++) seen = todo[k] == v;
+        if (seen) continue;
+        if (v->snap) {   /* a dead one (its context's state is gone): make it again */
+            qtts_dev_codec_snapshot_free(v->snap);
+            v->snap = NULL;
+        }
+        todo[nt++] = v;
+    }
+    int *codes = nt > 0 ? (int *)calloc((size_t)nt * max_ref * 16, sizeof(int)) : NULL;
+    *codes_keep = codes;
+    if (nt > 0 && !codes) rc = -1;
+    for (int g = 0; g < nt && rc == 0; g += ns) {
+        const int n = nt - g < ns ? nt - g : ns;
+        int ids[QWEN_TTS_MAX_BATCH], cnt[QWEN_TTS_MAX_BATCH];
+        int *gc = codes + (size_t)g * max_ref * 16;
+        for (int k = 0; k < n; k++) {
+            ids[k] = k;
+            cnt[k] = todo[g + k]->n_ref;
+            memcpy(gc + (size_t)k * max_ref * 16, todo[g + k]->ref_codes, (size_t)cnt[k] * 16 * sizeof(int));
+        }
+        if (qtts_dev_codec_mstream_prime(dev, n, ids, gc, cnt, max_ref) != 0) rc = -1;
+        for (int k = 0; k < n && rc == 0; k++)
+            if (!(todo[g + k]->snap = qtts_dev_codec_mstream_save(dev, k)) ||
+                qtts_dev_codec_mstream_reset(dev, k) != 0)
+                rc = -1;
+    }
+    free(todo);
+    return rc;
+}
+
+/* an admission of the streamed voice queue: the slot's stream from the
+ * voice's primed state (an x-vector-only voice: from position 0) */
+static int voice_admit(qtts_dev_t *dev, int stream, const qwen_tts_voice_t *v) {
+    if (qtts_dev_codec_mstream_reset(dev, stream) != 0) return -1;
+    return v->n_ref > 0 ? qtts_dev_codec_mstream_restore(dev, stream, v->snap) : 0;
+}
+
 static int queue_run(qwen_tts_ctx_t *ctx, const char *who, int nq, const char *const *texts,
                      const char *const *speakers, const char *const *languages, int nb, qwen_tts_queue_next_cb next,
-                     void *user, float **out_audio, int *out_samples, const stream_t *stream) {
+                     void *user, float **out_audio, int *out_samples, const stream_t *stream,
+                     const qwen_tts_voice_t *const *voices /* NULL: preset speakers */, int non_streaming) {
     if (ctx && ctx->force) {   /* forcing is defined for one utterance per slot, not for the queue */
         fprintf(stderr, "Error: %s: forced codes / taps are armed (not supported; disarmed)\n", who);
         force_disarm(ctx);
@@ -1428,6 +1493,13 @@ static int queue_run(qwen_tts_ctx_t *ctx, const char *who, int nq, const char *c
     if (batch_refused(ctx, who, nb)) return -1;
     sampling_arm_t *sarm = sampling_take(ctx);   /* one-shot: this call consumes it, however it ends */
     if (sampling_refused(who, sarm, NULL, nq)) {
+        sampling_free(sarm);
+        return -1;
+    }
+    for (int i = 0; voices && i < nq; i++) {
+        if (voices[i] && voices[i]->ctx == ctx && voices[i]->hip == ctx->hip) continue;
+        fprintf(stderr, "Error: %s: utterance %d: %s\n", who, i,
+                voices[i] ? "the voice handle belongs to another context" : "no voice handle (NULL)");
         sampling_free(sarm);
         return -1;
     }
@@ -1449,9 +1521,20 @@ static int queue_run(qwen_tts_ctx_t *ctx, const char *who, int nq, const char *c
     int *cbuf = NULL;
     qstream_t qs = {stream, NULL, NULL, NULL, 0, t_start, 0};
     int *avail = NULL, *complete = NULL, *ngen = NULL, finished = 0;
+    /* the voice queue: utterance i's prompt inputs, from its handle */
+    vclone_t *vcs = voices ? (vclone_t *)calloc(nq, sizeof(vclone_t)) : NULL;
+    int *prime_codes = NULL, max_ref = 0;
     if (!pr || !taken || !ctx->queue_codes || !ctx->queue_frames || !ctx->queue_stop_reason || !ctx->queue_slot ||
-        !cur || !first || !retired || !hst)
+        !cur || !first || !retired || !hst || (voices && !vcs))
         goto out;
+    for (int i = 0; voices && i < nq; i++) {
+        const qwen_tts_voice_t *v = voices[i];
+        vcs[i].ref_ids = v->ref_ids; vcs[i].n_ref_ids = v->n_ref_ids;
+        vcs[i].ref_codes = v->n_ref > 0 ? v->ref_codes : NULL; vcs[i].n_ref = v->n_ref > 0 ? v->n_ref : 0;
+        vcs[i].spk = v->spk;
+        vcs[i].non_streaming = non_streaming;
+        if (vcs[i].n_ref > max_ref) max_ref = vcs[i].n_ref;
+    }
     ctx->queue_n = nq;
     for (int i = 0; i < nq; i++) { ctx->queue_frames[i] = -1; ctx->queue_slot[i] = -1; }
     /* every prompt up front (the prefill and trailing capacities cover all) */
@@ -1472,7 +1555,8 @@ static int queue_run(qwen_tts_ctx_t *ctx, const char *who, int nq, const char *c
             }
         int spk, lang;
         lookup(ctx, speakers ? speakers[i] : NULL, languages ? languages[i] : NULL, &spk, &lang);
-        build_prompt(ctx, ids, n, spk, lang, 0, &pr[i]);
+        if (vcs) build_icl_prompt(ctx, ids, n, &vcs[i], lang, 0, &pr[i]);
+        else build_prompt(ctx, ids, n, spk, lang, 0, &pr[i]);
         free(ids);
         if (pr[i].p_len > max_p) max_p = pr[i].p_len;
         if (pr[i].n_trailing > max_tr) max_tr = pr[i].n_trailing;
@@ -1493,7 +1577,10 @@ static int queue_run(qwen_tts_ctx_t *ctx, const char *who, int nq, const char *c
     params_of(ctx, &gp);
     if (qtts_dev_begin(dev, ns, max_tokens, max_p, &gp) != 0 || qtts_dev_reserve(dev, max_tr) != 0) goto out;
     if (stream) {
-        if (qtts_dev_codec_mstream_begin(dev, ns, max_tokens, 0) != 0) goto out;
+        /* (voices: a stream stands at its reference frames + its own; the
+         * voices without a snapshot are primed and saved once, here) */
+        if (qtts_dev_codec_mstream_begin(dev, ns, max_tokens + max_ref, 0) != 0) goto out;
+        if (voices && voices_prime(dev, nq, voices, ns, max_ref, &prime_codes) != 0) goto out;
         qs.stream_of_slot = (int *)malloc(ns * sizeof(int));
         qs.sdone = (int *)calloc(ns, sizeof(int));
         qs.sbuf = (float **)calloc(ns, sizeof(float *));
@@ -1509,12 +1596,15 @@ static int queue_run(qwen_tts_ctx_t *ctx, const char *who, int nq, const char *c
     /* (a plan row's 4th int is the destination slot: set when the slot is known) */
     /* (the admitted utterance's sampling row goes in with its prompt: before
      * the initial prefill and before every qtts_dev_refill) */
+    /* (a voice's reference codes and x-vector go in before its prompt, which consumes them) */
 #define PROMPT(b, u) (queue_plan_slot(&pr[u], (b)), \
                       (sarm && sampling_apply(dev, sarm, (u), (b)) != 0) ? -1 : \
+                      (vcs && qtts_dev_prompt_ref(dev, vcs[u].ref_codes, vcs[u].n_ref, vcs[u].spk) != 0) ? -1 : \
                       qtts_dev_prompt(dev, (b), pr[u].text, pr[u].n_text, pr[u].plan, pr[u].nplan, pr[u].p_len, \
                                       pr[u].n_trailing, pr[u].pad_row))
     for (int b = 0; b < ns; b++)
-        if (PROMPT(b, cur[b]) != 0) goto out;
+        if (PROMPT(b, cur[b]) != 0 || (stream && voices && voice_admit(dev, qs.stream_of_slot[b], voices[cur[b]]) != 0))
+            goto out;
     double t_prefill = now_ms();
     if (qtts_dev_prefill(dev) != 0) goto out;
     ctx->perf_prefill_ms = now_ms() - t_prefill;
@@ -1592,7 +1682,9 @@ static int queue_run(qwen_tts_ctx_t *ctx, const char *who, int nq, const char *c
             active--;
             const int u2 = exhausted ? -1 : queue_pull(nq, taken, &next_seq, next, user);
             if (u2 < 0) { exhausted = 1; continue; }
-            if (stream && qtts_dev_codec_mstream_reset(dev, qs.stream_of_slot[b]) != 0) goto out;
+            if (stream && (voices ? voice_admit(dev, qs.stream_of_slot[b], voices[u2])
+                                  : qtts_dev_codec_mstream_reset(dev, qs.stream_of_slot[b])) != 0)
+                goto out;
             if (PROMPT(b, u2) != 0 || qtts_dev_refill(dev, b) != 0) goto out;
             cur[b] = u2;
             first[b] = step + 1;   /* its frame 0 is the next frame launched */
@@ -1650,13 +1742,29 @@ static int queue_run(qwen_tts_ctx_t *ctx, const char *who, int nq, const char *c
             if (ctx->queue_frames[u] < 0) continue;   /* not taken by this ctx */
             if (ctx->queue_frames[u] == 0) { rc = -1; continue; }
             uj[nj] = u; tj[nj] = ctx->queue_frames[u]; hc[nj] = ctx->queue_codes[u];
+            if (vcs && vcs[u].n_ref > 0) {
+                /* an ICL voice decodes reference ++ generated codes and keeps the part after the reference */
+                int *all = (int *)malloc((size_t)(vcs[u].n_ref + tj[nj]) * G * sizeof(int));
+                if (!all) { rc = -1; continue; }
+                memcpy(all, vcs[u].ref_codes, (size_t)vcs[u].n_ref * G * sizeof(int));
+                memcpy(all + (size_t)vcs[u].n_ref * G, ctx->queue_codes[u], (size_t)tj[nj] * G * sizeof(int));
+                hc[nj] = all;
+                tj[nj] += vcs[u].n_ref;
+            }
             nj++;
         }
         const double t_codec = now_ms();
         if (nj > 0 && qtts_dev_codec_multi(dev, nj, hc, sl, tj, aj, sj) != 0) rc = -1;
         for (int j = 0; j < nj; j++) {
-            out_audio[uj[j]] = aj[j];
-            out_samples[uj[j]] = aj[j] ? sj[j] : 0;
+            const int u = uj[j];
+            if (vcs && vcs[u].n_ref > 0) {
+                cut_reference(aj[j], sj[j], vcs[u].n_ref, tj[j], &out_audio[u], &out_samples[u]);
+                free((void *)hc[j]);
+                if (!out_audio[u]) rc = -1;
+                continue;
+            }
+            out_audio[u] = aj[j];
+            out_samples[u] = aj[j] ? sj[j] : 0;
             if (!aj[j] || sj[j] <= 0) rc = -1;
         }
         ctx->perf_codec_ms = now_ms() - t_codec;
@@ -1678,6 +1786,8 @@ out:
         free(qs.stream_of_slot); free(qs.sdone); free(avail); free(complete); free(ngen);
     }
     sampling_free(sarm);
+    free(vcs);
+    free(prime_codes);
     return rc;
 }
 
@@ -1685,8 +1795,121 @@ int qwen_tts_generate_queue(qwen_tts_ctx_t *ctx, int nq, const char *const *text
                             const char *const *languages, int nb, qwen_tts_queue_next_cb next, void *user,
                             float **out_audio, int *out_samples) {
     return queue_run(ctx, "qwen_tts_generate_queue", nq, texts, speakers, languages, nb, next, user, out_audio,
-                     out_samples, NULL);
+                     out_samples, NULL, NULL, 0);
 }
+
+int qwen_tts_generate_voice_queue(qwen_tts_ctx_t *ctx, int nq, const char *const *texts,
+                                  const qwen_tts_voice_t *const *voices, const char *const *languages,
+                                  int non_streaming, int nb, qwen_tts_queue_next_cb next, void *user,
+                                  float **out_audio, int *out_samples) {
+    if (!voices) {
+        if (ctx) force_disarm(ctx);
+        return -1;
+    }
+    return queue_run(ctx, "qwen_tts_generate_voice_queue", nq, texts, NULL, languages, nb, next, user, out_audio,
+                     out_samples, NULL, voices, non_streaming);
+}
+
+/* ------------------------------------------------------------- voice handles */
+static qwen_tts_voice_t *voice_new(qwen_tts_ctx_t *ctx, const char *ref_text, const int *ref_codes, int n_ref,
+                                   const float *spk) {
+    if (!ctx || !ctx->hip) return NULL;
+    const int icl = ref_codes && n_ref > 0, H = ctx->config.talker_hidden;
+    if (!icl && !spk) {
+        fprintf(stderr, "Error: voice clone needs reference codes or a speaker embedding\n");
+        return NULL;
+    }
+    qwen_tts_voice_t *v = (qwen_tts_voice_t *)calloc(1, sizeof(*v));
+    if (!v) return NULL;
+    v->ctx = ctx;
+    v->hip = ctx->hip;
+    if (icl) {
+        v->n_ref_ids = ref_text ? parse_ids(ref_text, &v->ref_ids) : 0;
+        if (v->n_ref_ids < 5) {
+            fprintf(stderr, "Error: ICL voice clone needs the reference text ids (chat template, >= 5 ids)\n");
+            qwen_tts_voice_free(v);
+            return NULL;
+        }
+        for (int i = 0; i < v->n_ref_ids; i++)
+            if (v->ref_ids[i] < 0 || v->ref_ids[i] >= ctx->config.talker_text_vocab) {
+                fprintf(stderr, "Error: text token id %d out of range\n", v->ref_ids[i]);
+                qwen_tts_voice_free(v);
+                return NULL;
+            }
+        v->ref_codes = (int *)malloc((size_t)n_ref * 16 * sizeof(int));
+        if (v->ref_codes) memcpy(v->ref_codes, ref_codes, (size_t)n_ref * 16 * sizeof(int));
+        v->n_ref = n_ref;
+    }
+    if (spk) {
+        v->spk = (float *)malloc((size_t)H * sizeof(float));
+        if (v->spk) memcpy(v->spk, spk, (size_t)H * sizeof(float));
+    }
+    if ((icl && !v->ref_codes) || (spk && !v->spk)) {
+        qwen_tts_voice_free(v);
+        return NULL;
+    }
+    return v;
+}
+
+qwen_tts_voice_t *qwen_tts_voice_create(qwen_tts_ctx_t *ctx, const char *ref_text, const int *ref_codes,
+                                        int n_ref_frames, const float *spk_embed) {
+    return voice_new(ctx, ref_text, ref_codes, n_ref_frames, spk_embed);
+}
+
+qwen_tts_voice_t *qwen_tts_voice_create_audio(qwen_tts_ctx_t *ctx, const char *ref_text, const float *ref_wav,
+                                              int n_ref_samples, int x_vector_only) {
+    if (!ctx || !ctx->hip || !ref_wav || n_ref_samples <= 0) return NULL;
+    qtts_dev_t *dev = (qtts_dev_t *)ctx->hip;
+    if ((qtts_dev_enc_available(dev) & 3) != 3) {
+        fprintf(stderr, "Error: the model directory has no speaker encoder / 12 Hz encoder weights\n");
+        return NULL;
+    }
+    if (!x_vector_only && (!ref_text || !ref_text[0])) {
+        fprintf(stderr, "Error: ref_text is required when x_vector_only_mode=False (ICL mode). Bad index=0\n");
+        return NULL;
+    }
+    const int T = (n_ref_samples + 1919) / 1920, H = ctx->config.talker_hidden;
+    int *codes = (int *)malloc((size_t)T * 16 * sizeof(int));
+    float *xv = (float *)malloc((size_t)H * sizeof(float));
+    const float *w[1] = {ref_wav};
+    const int n[1] = {n_ref_samples};
+    int fr = 0;
+    qwen_tts_voice_t *v = NULL;
+    if (codes && xv && qtts_dev_encode_audio(dev, 1, w, n, codes, T, &fr, NULL) == 0 &&
+        qtts_dev_speaker_embed(dev, 1, w, n, xv, NULL) == 0)
+        v = voice_new(ctx, x_vector_only ? NULL : ref_text, x_vector_only ? NULL : codes, x_vector_only ? 0 : fr, xv);
+    free(codes);
+    free(xv);
+    return v;
+}
+
+int qwen_tts_voice_info(const qwen_tts_voice_t *v, int *n_ref_frames, int *primed) {
+    if (!v) return -1;
+    if (n_ref_frames) *n_ref_frames = v->n_ref;
+    if (primed) *primed = v->n_ref > 0 && voice_primed(v);
+    return 0;
+}
+
+void qwen_tts_voice_free(qwen_tts_voice_t *v) {
+    if (!v) return;
+    qtts_dev_codec_snapshot_free(v->snap);
+    free(v->ref_ids); free(v->ref_codes); free(v->spk);
+    free(v);
+}
+
+qwen_tts_codec_snapshot_t *qwen_tts_codec_mstream_save(qwen_tts_ctx_t *ctx, int stream) {
+    if (!ctx || !ctx->hip) return NULL;
+    return qtts_dev_codec_mstream_save((qtts_dev_t *)ctx->hip, stream);
+}
+
+int qwen_tts_codec_mstream_restore(qwen_tts_ctx_t *ctx, int stream, const qwen_tts_codec_snapshot_t *snap) {
+    if (!ctx || !ctx->hip) return -1;
+    return qtts_dev_codec_mstream_restore((qtts_dev_t *)ctx->hip, stream, snap);
+}
+
+void qwen_tts_codec_snapshot_free(qwen_tts_codec_snapshot_t *snap) { qtts_dev_codec_snapshot_free(snap); }
+
+int qwen_tts_codec_snapshot_pos(const qwen_tts_codec_snapshot_t *snap) { return qtts_dev_codec_snapshot_pos(snap); }
 
 int qwen_tts_queue_codes(qwen_tts_ctx_t *ctx, int i, int *codes, int max_frames) {
     if (!ctx || i < 0 || i >= ctx->queue_n || !ctx->queue_codes || !ctx->queue_codes[i] || max_frames < 0) return -1;
@@ -2095,16 +2318,17 @@ int qwen_tts_codec_mstream_reset(qwen_tts_ctx_t *ctx, int stream) {
     return qtts_dev_codec_mstream_reset((qtts_dev_t *)ctx->hip, stream);
 }
 
-int qwen_tts_generate_queue_stream(qwen_tts_ctx_t *ctx, int nq, const char *const *texts, const char *const *speakers,
-                                   const char *const *languages, int nb, qwen_tts_queue_next_cb next, void *userdata,
-                                   int chunk_frames, qwen_tts_batch_audio_cb cb, void *cb_userdata, float **out_audio,
-                                   int *out_samples) {
-    static const char who[] = "qwen_tts_generate_queue_stream";
+static int queue_stream_run(qwen_tts_ctx_t *ctx, const char *who, int nq, const char *const *texts,
+                            const char *const *speakers, const qwen_tts_voice_t *const *voices,
+                            const char *const *languages, int non_streaming, int nb, qwen_tts_queue_next_cb next,
+                            void *userdata, int chunk_frames, qwen_tts_batch_audio_cb cb, void *cb_userdata,
+                            float **out_audio, int *out_samples) {
     /* (the slot limit is named whatever else is wrong with the call: before the device is looked at) */
     if (ctx && !ctx->force && batch_refused(ctx, who, nb)) return -1;
     stream_t st = {NULL, cb_userdata, chunk_frames > 0 ? chunk_frames : 1, 1, cb};
     if (ctx) ctx->perf_first_packet_ms = 0;
-    const int rc = queue_run(ctx, who, nq, texts, speakers, languages, nb, next, userdata, out_audio, out_samples, &st);
+    const int rc = queue_run(ctx, who, nq, texts, speakers, languages, nb, next, userdata, out_audio, out_samples, &st,
+                             voices, non_streaming);
     if (rc == 0 && qwen_tts_verbose >= 1) {
         double secs = 0;
         for (int u = 0; u < nq; u++) secs += (double)out_samples[u] / QWEN_TTS_SAMPLE_RATE;
@@ -2113,6 +2337,27 @@ int qwen_tts_generate_queue_stream(qwen_tts_ctx_t *ctx, int nq, const char *cons
                 nq, secs / (ctx->perf_total_ms / 1000.0));
     }
     return rc;
+}
+
+int qwen_tts_generate_queue_stream(qwen_tts_ctx_t *ctx, int nq, const char *const *texts, const char *const *speakers,
+                                   const char *const *languages, int nb, qwen_tts_queue_next_cb next, void *userdata,
+                                   int chunk_frames, qwen_tts_batch_audio_cb cb, void *cb_userdata, float **out_audio,
+                                   int *out_samples) {
+    return queue_stream_run(ctx, "qwen_tts_generate_queue_stream", nq, texts, speakers, NULL, languages, 0, nb, next,
+                            userdata, chunk_frames, cb, cb_userdata, out_audio, out_samples);
+}
+
+int qwen_tts_generate_voice_queue_stream(qwen_tts_ctx_t *ctx, int nq, const char *const *texts,
+                                         const qwen_tts_voice_t *const *voices, const char *const *languages,
+                                         int non_streaming, int nb, qwen_tts_queue_next_cb next, void *userdata,
+                                         int chunk_frames, qwen_tts_batch_audio_cb cb, void *cb_userdata,
+                                         float **out_audio, int *out_samples) {
+    if (!voices) {
+        if (ctx) force_disarm(ctx);
+        return -1;
+    }
+    return queue_stream_run(ctx, "qwen_tts_generate_voice_queue_stream", nq, texts, NULL, voices, languages,
+                            non_streaming, nb, next, userdata, chunk_frames, cb, cb_userdata, out_audio, out_samples);
 }
 
 int qwen_tts_codec_stream_begin(qwen_tts_ctx_t *ctx, int max_frames) {

@@ -121,6 +121,11 @@ EXPORTS = [
     "qwen_tts_codec_mstream_push_ragged", "qtts_dev_codec_mstream_push_host_ragged",
     "qtts_dev_codec_mstream_push_slots_ragged", "qtts_dev_codec_mstream_prime",
     "qwen_tts_generate_voice_clone_batch_stream", "qwen_tts_generate_voice_clone_audio_batch_stream",
+    "qtts_dev_codec_mstream_save", "qtts_dev_codec_mstream_restore", "qtts_dev_codec_snapshot_free",
+    "qtts_dev_codec_snapshot_pos", "qtts_dev_codec_snapshot_bytes",
+    "qwen_tts_codec_mstream_save", "qwen_tts_codec_mstream_restore", "qwen_tts_codec_snapshot_free",
+    "qwen_tts_codec_snapshot_pos", "qwen_tts_voice_create", "qwen_tts_voice_create_audio", "qwen_tts_voice_info",
+    "qwen_tts_voice_free", "qwen_tts_generate_voice_queue", "qwen_tts_generate_voice_queue_stream",
 ]
 
 MAX_BATCH = 64   # QWEN_TTS_MAX_BATCH / QTTS_HIP_MAX_BATCH: lock-step slots per context
@@ -333,6 +338,38 @@ def lib():
         L.qwen_tts_generate_voice_clone_audio_batch_stream.argtypes = [
             C.POINTER(Ctx), C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.POINTER(_fp), _ip,
             C.POINTER(C.c_char_p), _ip, C.c_int, C.c_int, BATCH_AUDIO_CB, C.c_void_p, C.POINTER(C.c_void_p), _ip]
+    # (nor the codec snapshots, the voice handles and the voice queue)
+    if hasattr(L, "qwen_tts_voice_create"):
+        L.qtts_dev_codec_mstream_save.restype = C.c_void_p
+        L.qtts_dev_codec_mstream_save.argtypes = [C.c_void_p, C.c_int]
+        L.qtts_dev_codec_mstream_restore.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        L.qtts_dev_codec_snapshot_free.restype = None
+        L.qtts_dev_codec_snapshot_free.argtypes = [C.c_void_p]
+        L.qtts_dev_codec_snapshot_pos.argtypes = [C.c_void_p]
+        L.qtts_dev_codec_snapshot_bytes.restype = C.c_longlong
+        L.qtts_dev_codec_snapshot_bytes.argtypes = [C.c_void_p]
+        L.qwen_tts_codec_mstream_save.restype = C.c_void_p
+        L.qwen_tts_codec_mstream_save.argtypes = [C.POINTER(Ctx), C.c_int]
+        L.qwen_tts_codec_mstream_restore.argtypes = [C.POINTER(Ctx), C.c_int, C.c_void_p]
+        L.qwen_tts_codec_snapshot_free.restype = None
+        L.qwen_tts_codec_snapshot_free.argtypes = [C.c_void_p]
+        L.qwen_tts_codec_snapshot_pos.argtypes = [C.c_void_p]
+        L.qwen_tts_voice_create.restype = C.c_void_p
+        L.qwen_tts_voice_create.argtypes = [C.POINTER(Ctx), C.c_char_p, _ip, C.c_int, _fp]
+        L.qwen_tts_voice_create_audio.restype = C.c_void_p
+        L.qwen_tts_voice_create_audio.argtypes = [C.POINTER(Ctx), C.c_char_p, _fp, C.c_int, C.c_int]
+        L.qwen_tts_voice_info.argtypes = [C.c_void_p, _ip, _ip]
+        L.qwen_tts_voice_free.restype = None
+        L.qwen_tts_voice_free.argtypes = [C.c_void_p]
+        L.qwen_tts_generate_voice_queue.restype = C.c_int
+        L.qwen_tts_generate_voice_queue.argtypes = [C.POINTER(Ctx), C.c_int, C.POINTER(C.c_char_p),
+                                                    C.POINTER(C.c_void_p), C.POINTER(C.c_char_p), C.c_int, C.c_int,
+                                                    QUEUE_NEXT_CB, C.c_void_p, C.POINTER(C.c_void_p), _ip]
+        L.qwen_tts_generate_voice_queue_stream.restype = C.c_int
+        L.qwen_tts_generate_voice_queue_stream.argtypes = [C.POINTER(Ctx), C.c_int, C.POINTER(C.c_char_p),
+                                                           C.POINTER(C.c_void_p), C.POINTER(C.c_char_p), C.c_int,
+                                                           C.c_int, QUEUE_NEXT_CB, C.c_void_p, C.c_int, BATCH_AUDIO_CB,
+                                                           C.c_void_p, C.POINTER(C.c_void_p), _ip]
     L.qwen_tts_speaker_embedding.restype = C.c_void_p
     L.qwen_tts_speaker_embedding.argtypes = [C.POINTER(Ctx), _fp, C.c_int, _ip]
     L.qwen_tts_encode_audio.restype = C.c_void_p
@@ -1016,6 +1053,93 @@ class QwenTTS:
     def codec_mstream_pos(self, stream):
         """frames decoded so far of a stream (-1: no such stream)"""
         return lib().qtts_dev_codec_mstream_pos(self.c.hip, int(stream))
+
+    def codec_mstream_save(self, stream):
+        """a snapshot (opaque handle) of one stream's carried state, the stream
+        untouched (qwen_tts_codec_mstream_save); None where the library refuses"""
+        p = lib().qwen_tts_codec_mstream_save(self.ctx, int(stream))
+        return p or None
+
+    def codec_mstream_restore(self, stream, snap):
+        """`stream` continues from the snapshot (qwen_tts_codec_mstream_restore); 0 or -1"""
+        return lib().qwen_tts_codec_mstream_restore(self.ctx, int(stream), snap)
+
+    @staticmethod
+    def codec_snapshot_free(snap):
+        lib().qwen_tts_codec_snapshot_free(snap)
+
+    @staticmethod
+    def codec_snapshot_pos(snap):
+        """frames the snapshot stands at (-1: NULL, freed, or its context is gone)"""
+        return lib().qwen_tts_codec_snapshot_pos(snap)
+
+    # ---- voice handles and the voice-clone work queue (include/qwen_tts.h qwen_tts_voice_*)
+    def voice_create(self, ref_ids=None, ref_codes=None, spk_embed=None):
+        """A voice handle from reference codes [T, 16] (+ the reference text
+        ids) and / or a speaker x-vector; None where the library refuses."""
+        rcsv = ",".join(str(int(i)) for i in ref_ids).encode() if ref_ids is not None else None
+        rc = None if ref_codes is None else np.ascontiguousarray(ref_codes, np.int32)
+        sv = None if spk_embed is None else np.ascontiguousarray(spk_embed, np.float32)
+        p = lib().qwen_tts_voice_create(self.ctx, rcsv, None if rc is None else rc.ctypes.data_as(_ip),
+                                        0 if rc is None else rc.shape[0],
+                                        None if sv is None else sv.ctypes.data_as(_fp))
+        return p or None
+
+    def voice_create_audio(self, ref_wav, ref_ids=None, x_vector_only=False):
+        """A voice handle from 24 kHz reference audio: the two encoders run once."""
+        rcsv = ",".join(str(int(i)) for i in ref_ids).encode() if ref_ids is not None else None
+        w = np.ascontiguousarray(ref_wav, np.float32)
+        p = lib().qwen_tts_voice_create_audio(self.ctx, rcsv, w.ctypes.data_as(_fp), w.shape[0], int(x_vector_only))
+        return p or None
+
+    @staticmethod
+    def voice_info(voice):
+        """{n_ref_frames, primed} of a handle, None for a NULL one"""
+        n, pr = C.c_int(0), C.c_int(0)
+        if lib().qwen_tts_voice_info(voice, C.byref(n), C.byref(pr)) != 0:
+            return None
+        return {"n_ref_frames": n.value, "primed": pr.value}
+
+    @staticmethod
+    def voice_free(voice):
+        lib().qwen_tts_voice_free(voice)
+
+    def generate_voice_queue(self, id_lists, voices, languages=None, non_streaming=False, slots=8, next_fn=None):
+        """generate_queue with utterance i spoken in the cloned voice voices[i]
+        (handles of voice_create*, repeats allowed; qwen_tts_generate_voice_queue).
+        Returns (rc, [audio or None])."""
+        nq = len(id_lists)
+        tx = (C.c_char_p * nq)(*[",".join(str(int(i)) for i in ids).encode() for ids in id_lists])
+        vs = (C.c_void_p * nq)(*voices) if voices is not None else None
+        lg = (C.c_char_p * nq)(*[(s.encode() if s else None) for s in (languages or [None] * nq)])
+        out = (C.c_void_p * nq)()
+        ns = (C.c_int * nq)()
+        cb = QUEUE_NEXT_CB(lambda u: int(next_fn())) if next_fn is not None else QUEUE_NEXT_CB()
+        rc = lib().qwen_tts_generate_voice_queue(self.ctx, nq, tx, vs, lg, int(non_streaming), int(slots), cb, None,
+                                                 out, ns)
+        return rc, [_take_audio(out[i], ns[i]) for i in range(nq)]
+
+    def generate_voice_queue_stream(self, id_lists, voices, languages=None, non_streaming=False, slots=8,
+                                    next_fn=None, chunk_frames=4, on_chunk=None):
+        """generate_voice_queue with every utterance streamed
+        (qwen_tts_generate_voice_queue_stream): on_chunk(u, np.ndarray) as
+        generate_queue_stream; the audio starts at the reference boundary.
+        Returns (rc, [audio or None])."""
+        nq = len(id_lists)
+        tx = (C.c_char_p * nq)(*[",".join(str(int(i)) for i in ids).encode() for ids in id_lists])
+        vs = (C.c_void_p * nq)(*voices) if voices is not None else None
+        lg = (C.c_char_p * nq)(*[(s.encode() if s else None) for s in (languages or [None] * nq)])
+        out = (C.c_void_p * nq)()
+        ns = (C.c_int * nq)()
+        ncb = QUEUE_NEXT_CB(lambda u: int(next_fn())) if next_fn is not None else QUEUE_NEXT_CB()
+
+        def _cb(i, p, k, u):
+            if on_chunk is not None:
+                on_chunk(int(i), np.ctypeslib.as_array(p, shape=(k,)).copy())
+        cb = BATCH_AUDIO_CB(_cb)
+        rc = lib().qwen_tts_generate_voice_queue_stream(self.ctx, nq, tx, vs, lg, int(non_streaming), int(slots), ncb,
+                                                        None, int(chunk_frames), cb, None, out, ns)
+        return rc, [_take_audio(out[i], ns[i]) for i in range(nq)]
 
     def codec_mstream(self, chunk_lists, max_frames=4096):
         """Exact incremental decode of several code sequences at once:
