@@ -2410,162 +2410,148 @@ extern "C" int qtts_dev_codec_mstream_begin(qtts_dev_t *dv, int n_streams, int m
     return codec_mstream_begin(&dv->codec, n_streams, max_frames, chunk_frames);
 }
 
-extern "C" int qtts_dev_codec_mstream_push_slots(qtts_dev_t *dv, int n, const int *streams, const int *slots,
-                                                 int frame0, int T, float *const *host_out) {
+// One push of n streams, behind the seven entries below.  The codes come from
+// the slots' generated frames on the device or from host codes staged on the
+// codec's stream; every stream advances by T frames or stream i by counts[i]
+// (ragged: one launch sequence per pass whatever the counts, DESIGN.md 7,
+// "Ragged pushes"); `any`: the streams may stand at independent positions (the
+// work queue's slots: a refilled slot's stream restarts at 0 beside its
+// neighbours; a ragged push always may).  A prime is the ragged host push on
+// the second stream (cst), its audio dropped, not waited for: the carried state
+// is what later pushes continue from.  The reference frames of a voice-clone
+// batch go this way while the prefill runs on the context stream, as
+// qtts_dev_codec_stream_prime's do for one utterance; every later multi-stream
+// call joins it by event.
+enum MsSrc { MS_SLOTS, MS_SLOTS_AT, MS_HOST };
+struct MsPush {
+    MsSrc src;
+    const int *slots;      // MS_SLOTS / MS_SLOTS_AT: slot slots[i]'s frames from
+    int frame0;            //   MS_SLOTS: frame0, the same for every stream
+    const int *frame0s;    //   MS_SLOTS_AT: frame0s[i]
+    const int *codes;      // MS_HOST: [n][ld][16], stream i's first T / counts[i] rows
+    int ld;
+    bool ragged;
+    const int *counts;
+    int T;
+    bool any;
+    bool prime;
+};
+
+static int mstream_push(qtts_dev_t *dv, int n, const int *streams, const MsPush &p, float *const *host_out) {
     if (!dv) return -1;
     hipSetDevice(dv->device);
+    const int cap = dv->max_frames + 1;   // frames a slot holds
     // every refusal before anything is enqueued
-    if (codec_mstream_check(&dv->codec, n, streams, T)) return -1;
-    if (!slots || !host_out || frame0 < 0 || frame0 + T > dv->max_frames + 1) {
-        fprintf(stderr, "qtts codec mstream: frames [%d, %d) are outside the slots' %d\n", frame0, frame0 + T,
-                dv->max_frames + 1);
+    if (p.ragged ? codec_mstream_check_ragged(&dv->codec, n, streams, p.counts, p.src == MS_HOST ? p.ld : cap)
+                 : codec_mstream_check(&dv->codec, n, streams, p.T, p.any))
+        return -1;
+    if (p.src == MS_HOST) {
+        if (!p.codes || (!p.prime && !host_out)) return -1;
+    } else if (p.src == MS_SLOTS) {
+        if (!p.slots || !host_out || p.frame0 < 0 || p.frame0 + p.T > cap) {
+            fprintf(stderr, "qtts codec mstream: frames [%d, %d) are outside the slots' %d\n", p.frame0,
+                    p.frame0 + p.T, cap);
+            return -1;
+        }
+    } else if (!p.slots || !p.frame0s || !host_out) {
         return -1;
     }
+    const size_t per = (size_t)(p.ragged ? p.ld : p.T) * dv->d.cq;   // MS_HOST: the staged codes of one stream
     long long off[64];   // (the check bounds n by the begin's 1..64 streams)
     for (int i = 0; i < n; ++i) {
-        if (slots[i] < 0 || slots[i] >= dv->nb) {
-            fprintf(stderr, "qtts codec mstream: slot %d out of range (0..%d)\n", slots[i], dv->nb - 1);
+        if (p.ragged && !p.prime && !host_out[i]) return -1;
+        if (p.src == MS_HOST) {
+            off[i] = (long long)(i * per);
+            continue;
+        }
+        if (p.slots[i] < 0 || p.slots[i] >= dv->nb) {
+            fprintf(stderr, "qtts codec mstream: slot %d out of range (0..%d)\n", p.slots[i], dv->nb - 1);
             return -1;
         }
-        off[i] = ((long long)slots[i] * (dv->max_frames + 1) + frame0) * dv->d.G;
+        const int f0 = p.src == MS_SLOTS ? p.frame0 : p.frame0s[i], c = p.ragged ? p.counts[i] : p.T;
+        if (f0 < 0 || f0 + c > cap) {   // (MS_SLOTS: refused above for all)
+            fprintf(stderr, "qtts codec mstream: frames [%d, %d) are outside slot %d's %d\n", f0, f0 + c, p.slots[i],
+                    cap);
+            return -1;
+        }
+        off[i] = ((long long)p.slots[i] * cap + f0) * dv->d.G;
     }
     CKI(join_prime(dv));
-    return codec_mstream_push(&dv->codec, n, streams, dv->codes, off, dv->d.G, T, host_out);
-}
-
-extern "C" int qtts_dev_codec_mstream_push_host(qtts_dev_t *dv, int n, const int *streams, const int *codes, int T,
-                                                float *const *host_out) {
-    if (!dv) return -1;
-    hipSetDevice(dv->device);
-    if (codec_mstream_check(&dv->codec, n, streams, T)) return -1;
-    if (!codes || !host_out) return -1;
-    CKI(join_prime(dv));
-    const size_t per = (size_t)T * dv->d.cq;
-    CKI(ensure_push_codes(dv, per * n));
-    long long off[64];   // (the check bounds n by the begin's 1..64 streams)
-    for (int i = 0; i < n; ++i) off[i] = (long long)(i * per);
-    CK(hipMemcpyAsync(dv->push_codes, codes, per * n * 4, hipMemcpyHostToDevice, dv->codec.st));
-    return codec_mstream_push(&dv->codec, n, streams, dv->push_codes, off, dv->d.cq, T, host_out);
-}
-
-// The same two pushes for streams at independent positions (the work queue's
-// slots: a refilled slot's stream restarts at 0 beside its neighbours): slot
-// slots[i]'s frames [frame0[i], frame0[i] + T), or host codes [n][T][16].
-extern "C" int qtts_dev_codec_mstream_push_slots_at(qtts_dev_t *dv, int n, const int *streams, const int *slots,
-                                                    const int *frame0, int T, float *const *host_out) {
-    if (!dv) return -1;
-    hipSetDevice(dv->device);
-    // every refusal before anything is enqueued
-    if (codec_mstream_check(&dv->codec, n, streams, T, true)) return -1;
-    if (!slots || !frame0 || !host_out) return -1;
-    long long off[64];   // (the check bounds n by the begin's 1..64 streams)
-    for (int i = 0; i < n; ++i) {
-        if (slots[i] < 0 || slots[i] >= dv->nb) {
-            fprintf(stderr, "qtts codec mstream: slot %d out of range (0..%d)\n", slots[i], dv->nb - 1);
-            return -1;
+    const int *base = dv->codes;
+    int ldc = dv->d.G;
+    if (p.src == MS_HOST) {
+        if (p.prime) CKI(ensure_cst(dv));
+        CKI(ensure_push_codes(dv, per * n));   // persistent staging buffer: no allocation per push
+        if (p.prime) {
+            CK(hipEventRecord(dv->cev, dv->st));          // after the begin's resets on st
+            CK(hipStreamWaitEvent(dv->cst, dv->cev, 0));
         }
-        if (frame0[i] < 0 || frame0[i] + T > dv->max_frames + 1) {
-            fprintf(stderr, "qtts codec mstream: frames [%d, %d) are outside slot %d's %d\n", frame0[i], frame0[i] + T,
-                    slots[i], dv->max_frames + 1);
-            return -1;
-        }
-        off[i] = ((long long)slots[i] * (dv->max_frames + 1) + frame0[i]) * dv->d.G;
+        // ordered on the codec's stream before the push reads it
+        CK(hipMemcpyAsync(dv->push_codes, p.codes, per * n * 4, hipMemcpyHostToDevice, p.prime ? dv->cst : dv->codec.st));
+        base = dv->push_codes;
+        ldc = dv->d.cq;
     }
-    CKI(join_prime(dv));
-    return codec_mstream_push(&dv->codec, n, streams, dv->codes, off, dv->d.G, T, host_out, true);
-}
-
-extern "C" int qtts_dev_codec_mstream_push_host_any(qtts_dev_t *dv, int n, const int *streams, const int *codes, int T,
-                                                    float *const *host_out) {
-    if (!dv) return -1;
-    hipSetDevice(dv->device);
-    if (codec_mstream_check(&dv->codec, n, streams, T, true)) return -1;
-    if (!codes || !host_out) return -1;
-    CKI(join_prime(dv));
-    const size_t per = (size_t)T * dv->d.cq;
-    CKI(ensure_push_codes(dv, per * n));
-    long long off[64];   // (the check bounds n by the begin's 1..64 streams)
-    for (int i = 0; i < n; ++i) off[i] = (long long)(i * per);
-    CK(hipMemcpyAsync(dv->push_codes, codes, per * n * 4, hipMemcpyHostToDevice, dv->codec.st));
-    return codec_mstream_push(&dv->codec, n, streams, dv->push_codes, off, dv->d.cq, T, host_out, true);
-}
-
-// The ragged pushes: stream i advances by its own count (one launch sequence
-// per pass whatever the counts, DESIGN.md 7, "Ragged pushes").  Host codes [n][ld_frames][16],
-// of which stream i's first counts[i] rows are read; or slot slots[i]'s
-// frames [frame0[i], frame0[i] + count[i]).  counts[i] * 1920 samples reach
-// host_out[i]; returns the largest count times 1920.
-extern "C" int qtts_dev_codec_mstream_push_host_ragged(qtts_dev_t *dv, int n, const int *streams, const int *codes,
-                                                       const int *counts, int ld_frames, float *const *host_out) {
-    if (!dv) return -1;
-    hipSetDevice(dv->device);
-    // every refusal before anything is enqueued
-    if (codec_mstream_check_ragged(&dv->codec, n, streams, counts, ld_frames)) return -1;
-    if (!codes || !host_out) return -1;
-    for (int i = 0; i < n; ++i)
-        if (!host_out[i]) return -1;
-    CKI(join_prime(dv));
-    const size_t per = (size_t)ld_frames * dv->d.cq;
-    CKI(ensure_push_codes(dv, per * n));
-    long long off[64];   // (the check bounds n by the begin's 1..64 streams)
-    for (int i = 0; i < n; ++i) off[i] = (long long)(i * per);
-    CK(hipMemcpyAsync(dv->push_codes, codes, per * n * 4, hipMemcpyHostToDevice, dv->codec.st));
-    return codec_mstream_push_ragged(&dv->codec, n, streams, dv->push_codes, off, dv->d.cq, counts, host_out);
-}
-
-extern "C" int qtts_dev_codec_mstream_push_slots_ragged(qtts_dev_t *dv, int n, const int *streams, const int *slots,
-                                                        const int *frame0, const int *count,
-                                                        float *const *host_out) {
-    if (!dv) return -1;
-    hipSetDevice(dv->device);
-    if (codec_mstream_check_ragged(&dv->codec, n, streams, count, dv->max_frames + 1)) return -1;
-    if (!slots || !frame0 || !host_out) return -1;
-    long long off[64];   // (the check bounds n by the begin's 1..64 streams)
-    for (int i = 0; i < n; ++i) {
-        if (!host_out[i]) return -1;
-        if (slots[i] < 0 || slots[i] >= dv->nb) {
-            fprintf(stderr, "qtts codec mstream: slot %d out of range (0..%d)\n", slots[i], dv->nb - 1);
-            return -1;
-        }
-        if (frame0[i] < 0 || frame0[i] + count[i] > dv->max_frames + 1) {
-            fprintf(stderr, "qtts codec mstream: frames [%d, %d) are outside slot %d's %d\n", frame0[i],
-                    frame0[i] + count[i], slots[i], dv->max_frames + 1);
-            return -1;
-        }
-        off[i] = ((long long)slots[i] * (dv->max_frames + 1) + frame0[i]) * dv->d.G;
-    }
-    CKI(join_prime(dv));
-    return codec_mstream_push_ragged(&dv->codec, n, streams, dv->codes, off, dv->d.G, count, host_out);
-}
-
-// Push host codes of ragged lengths ([n][ld_frames][16], counts[i] rows of
-// stream i) through the streams on the second stream (cst) without waiting:
-// their audio is dropped, the carried state is what later pushes continue
-// from.  The reference frames of a voice-clone batch go this way while the
-// prefill runs on the context stream, as qtts_dev_codec_stream_prime's do
-// for one utterance; every later multi-stream call joins it by event.
-extern "C" int qtts_dev_codec_mstream_prime(qtts_dev_t *dv, int n, const int *streams, const int *codes,
-                                            const int *counts, int ld_frames) {
-    if (!dv) return -1;
-    hipSetDevice(dv->device);
-    if (codec_mstream_check_ragged(&dv->codec, n, streams, counts, ld_frames)) return -1;
-    if (!codes) return -1;
-    CKI(join_prime(dv));
-    CKI(ensure_cst(dv));
-    const size_t per = (size_t)ld_frames * dv->d.cq;
-    CKI(ensure_push_codes(dv, per * n));
-    long long off[64];   // (the check bounds n by the begin's 1..64 streams)
-    for (int i = 0; i < n; ++i) off[i] = (long long)(i * per);
-    CK(hipEventRecord(dv->cev, dv->st));          // after the begin's resets on st
-    CK(hipStreamWaitEvent(dv->cst, dv->cev, 0));
-    CK(hipMemcpyAsync(dv->push_codes, codes, per * n * 4, hipMemcpyHostToDevice, dv->cst));
-    dv->codec.st = dv->cst;
-    const int r = codec_mstream_push_ragged(&dv->codec, n, streams, dv->push_codes, off, dv->d.cq, counts, nullptr);
+    if (p.prime) dv->codec.st = dv->cst;
+    const int r = p.ragged ? codec_mstream_push_ragged(&dv->codec, n, streams, base, off, ldc, p.counts,
+                                                       p.prime ? nullptr : host_out)
+                           : codec_mstream_push(&dv->codec, n, streams, base, off, ldc, p.T, host_out, p.any);
+    if (!p.prime) return r;
     dv->codec.st = dv->st;
     if (r < 0) return -1;
     CK(hipEventRecord(dv->cev, dv->cst));
     dv->prime_pending = true;
     return 0;
+}
+
+extern "C" int qtts_dev_codec_mstream_push_slots(qtts_dev_t *dv, int n, const int *streams, const int *slots,
+                                                 int frame0, int T, float *const *host_out) {
+    MsPush p{};
+    p.src = MS_SLOTS; p.slots = slots; p.frame0 = frame0; p.T = T;
+    return mstream_push(dv, n, streams, p, host_out);
+}
+
+extern "C" int qtts_dev_codec_mstream_push_host(qtts_dev_t *dv, int n, const int *streams, const int *codes, int T,
+                                                float *const *host_out) {
+    MsPush p{};
+    p.src = MS_HOST; p.codes = codes; p.T = T;
+    return mstream_push(dv, n, streams, p, host_out);
+}
+
+extern "C" int qtts_dev_codec_mstream_push_slots_at(qtts_dev_t *dv, int n, const int *streams, const int *slots,
+                                                    const int *frame0, int T, float *const *host_out) {
+    MsPush p{};
+    p.src = MS_SLOTS_AT; p.slots = slots; p.frame0s = frame0; p.T = T; p.any = true;
+    return mstream_push(dv, n, streams, p, host_out);
+}
+
+extern "C" int qtts_dev_codec_mstream_push_host_any(qtts_dev_t *dv, int n, const int *streams, const int *codes, int T,
+                                                    float *const *host_out) {
+    MsPush p{};
+    p.src = MS_HOST; p.codes = codes; p.T = T; p.any = true;
+    return mstream_push(dv, n, streams, p, host_out);
+}
+
+// counts[i] * 1920 samples reach host_out[i]; returns the largest count times 1920
+extern "C" int qtts_dev_codec_mstream_push_host_ragged(qtts_dev_t *dv, int n, const int *streams, const int *codes,
+                                                       const int *counts, int ld_frames, float *const *host_out) {
+    MsPush p{};
+    p.src = MS_HOST; p.codes = codes; p.ld = ld_frames; p.ragged = true; p.counts = counts;
+    return mstream_push(dv, n, streams, p, host_out);
+}
+
+extern "C" int qtts_dev_codec_mstream_push_slots_ragged(qtts_dev_t *dv, int n, const int *streams, const int *slots,
+                                                        const int *frame0, const int *count,
+                                                        float *const *host_out) {
+    MsPush p{};
+    p.src = MS_SLOTS_AT; p.slots = slots; p.frame0s = frame0; p.ragged = true; p.counts = count;
+    return mstream_push(dv, n, streams, p, host_out);
+}
+
+extern "C" int qtts_dev_codec_mstream_prime(qtts_dev_t *dv, int n, const int *streams, const int *codes,
+                                            const int *counts, int ld_frames) {
+    MsPush p{};
+    p.src = MS_HOST; p.codes = codes; p.ld = ld_frames; p.ragged = true; p.counts = counts; p.prime = true;
+    return mstream_push(dv, n, streams, p, nullptr);
 }
 
 extern "C" int qtts_dev_codec_mstream_reset(qtts_dev_t *dv, int stream) {

@@ -640,6 +640,49 @@ static void lookup(const qwen_tts_ctx_t *ctx, const char *speaker, const char *l
     }
 }
 
+static int ids_in_range(const qwen_tts_ctx_t *ctx, const int *ids, int n) {
+    for (int i = 0; i < n; i++)
+        if (ids[i] < 0 || ids[i] >= ctx->config.talker_text_vocab) {
+            fprintf(stderr, "Error: text token id %d out of range\n", ids[i]);
+            return 0;
+        }
+    return 1;
+}
+
+/* the reference text of an ICL voice: its ids (malloc'd) and their count, or -1 with the message */
+static int ref_text_ids(const qwen_tts_ctx_t *ctx, const char *ref_text, int **ids) {
+    *ids = NULL;
+    const int n = ref_text ? parse_ids(ref_text, ids) : 0;
+    if (n < 5) fprintf(stderr, "Error: ICL voice clone needs the reference text ids (chat template, >= 5 ids)\n");
+    else if (ids_in_range(ctx, *ids, n)) return n;
+    free(*ids);
+    *ids = NULL;
+    return -1;
+}
+
+/* Prompt intake of every generate path: one utterance's text ids, checked,
+ * its speaker / language looked up, laid out for slot b (vc: the voice-clone
+ * layout, the speaker name unused).  -1 with the message on a refusal. */
+static int prompt_make(const qwen_tts_ctx_t *ctx, const char *text, const char *speaker, const char *language,
+                       const vclone_t *vc, int b, prompt_t *pr) {
+    int *ids = NULL, rc = -1;
+    const int n = parse_ids(text, &ids);
+    if (n < 8) {
+        if (n >= 0) fprintf(stderr, "Error: need at least 8 text tokens (chat template format)\n");
+    } else if (ids_in_range(ctx, ids, n)) {
+        int spk, lang;
+        lookup(ctx, speaker, language, &spk, &lang);
+        rc = vc ? build_icl_prompt(ctx, ids, n, vc, lang, b, pr) : build_prompt(ctx, ids, n, spk, lang, b, pr);
+    }
+    free(ids);
+    return rc;
+}
+
+static void prompts_free(prompt_t *pr, int n) {
+    for (int i = 0; pr && i < n; i++) { free(pr[i].text); free(pr[i].plan); }
+    free(pr);
+}
+
 /* the reference codec's stderr lines around one full decode
  * (c/qwen_tts_codec.c:598-599 at -v, 740-746 at -v / -v -v) */
 static void codec_log_begin(qwen_tts_ctx_t *ctx, int T) {
@@ -902,82 +945,189 @@ int qwen_tts_tap_result(qwen_tts_ctx_t *ctx, int i, float *logits, int max_n, un
 }
 
 /* ------------------------------------------------------------- generation */
-/* Runs nb utterances in lock-step frames.  Fills per-slot frame counts and
- * stop info; audio[i] decoded per slot.  Returns 0 on success. */
-typedef struct {                 /* streaming output of run_batch */
-    qwen_tts_audio_cb cb;        /* nb == 1: the single exact stream */
+typedef struct {                 /* streaming arguments of a generate call */
+    qwen_tts_audio_cb cb;        /* the single exact stream of one utterance */
     void *user;
     int chunk;
     int multi;                   /* every slot through the multi-stream codec, chunks to bcb */
     qwen_tts_batch_audio_cb bcb;
 } stream_t;
 
-static void free_bufs(float **v, int n) {
-    if (!v) return;
-    for (int i = 0; i < n; i++) free(v[i]);
-    free(v);
+/* Streaming delivery, shared by the lock-step run and the work queue: the
+ * per-run state, and the one routine that pushes new frames through a codec
+ * stream and hands the audio on.  The two loops differ only in how they decide
+ * which slots are due (batch_flush, queue_flush). */
+typedef struct {
+    const stream_t *stream;
+    int n;                       /* slots */
+    float **buf;                 /* [n] the slot's utterance so far, max_tokens * 1920 samples each */
+    int *done;                   /* [n] frames of it delivered */
+    int *stream_of_slot;         /* [n] (the queue's tail compaction moves the entry, never codec state) */
+    double t_stream, t_start;    /* time in the pushes / the first packet's origin */
+    int delivered;               /* callbacks so far */
+    int stamp_first_cb;          /* the queue: the first packet is stamped before the call's first callback
+                                    (a lock-step run stamps it once its first flush is over: batch_flush) */
+} sstate_t;
+
+static void sstate_free(sstate_t *s) {
+    for (int b = 0; s->buf && b < s->n; b++) free(s->buf[b]);
+    free(s->buf); free(s->done); free(s->stream_of_slot);
+    memset(s, 0, sizeof *s);
 }
 
-/* One poll's new frames of every slot through the multi-stream codec.  The
+static int sstate_init(sstate_t *s, const stream_t *stream, int n, int max_tokens, double t_start, int stamp_first_cb) {
+    memset(s, 0, sizeof *s);
+    s->stream = stream;
+    s->n = n;
+    s->t_start = t_start;
+    s->stamp_first_cb = stamp_first_cb;
+    s->buf = (float **)calloc(n, sizeof(float *));
+    s->done = (int *)calloc(n, sizeof(int));
+    s->stream_of_slot = (int *)malloc(n * sizeof(int));
+    int ok = s->buf && s->done && s->stream_of_slot;
+    for (int b = 0; b < n && ok; b++) {
+        s->stream_of_slot[b] = b;
+        ok = (s->buf[b] = (float *)malloc((size_t)max_tokens * 1920 * sizeof(float))) != NULL;
+    }
+    return ok ? 0 : -1;
+}
+
+/* One push: slot slots[i]'s next cnt[i] frames (from done[slot] on) through
+ * its stream, into its buffer; the time goes to t_stream, the queue's first
+ * packet is stamped, every slot's callback gets the pointer into its buffer, its sample
+ * count and utt[slot] (NULL: the slot index).  The entry: the single stream
+ * for a non-multi call; _push_slots for slots at equal positions with equal
+ * counts (!at_positions); else _push_slots_at, or _push_slots_ragged when the
+ * counts differ. */
+static int stream_deliver(qwen_tts_ctx_t *ctx, qtts_dev_t *dev, sstate_t *s, int n, const int *slots, const int *cnt,
+                          int at_positions, const int *utt) {
+    const stream_t *st = s->stream;
+    int ids[QWEN_TTS_MAX_BATCH], f0[QWEN_TTS_MAX_BATCH], same = 1, r;
+    float *outs[QWEN_TTS_MAX_BATCH];
+    for (int i = 0; i < n; i++) {
+        ids[i] = s->stream_of_slot[slots[i]];
+        f0[i] = s->done[slots[i]];
+        outs[i] = s->buf[slots[i]] + (size_t)f0[i] * 1920;
+        same &= cnt[i] == cnt[0];
+    }
+    const double t0 = now_ms();
+    if (!st->multi) r = qtts_dev_codec_stream_push_slot(dev, slots[0], f0[0], cnt[0], outs[0]);
+    else if (!at_positions) r = qtts_dev_codec_mstream_push_slots(dev, n, ids, slots, f0[0], cnt[0], outs);
+    else if (same) r = qtts_dev_codec_mstream_push_slots_at(dev, n, ids, slots, f0, cnt[0], outs);
+    else r = qtts_dev_codec_mstream_push_slots_ragged(dev, n, ids, slots, f0, cnt, outs);
+    if (r < 0) return -1;
+    s->t_stream += now_ms() - t0;
+    const int first = s->delivered == 0;
+    for (int i = 0; i < n; i++) {
+        if (first && i == 0 && s->stamp_first_cb) ctx->perf_first_packet_ms = now_ms() - s->t_start;
+        if (!st->multi) { if (st->cb) st->cb(outs[i], r, st->user); }
+        else if (st->bcb) st->bcb(utt ? utt[slots[i]] : slots[i], outs[i], same ? r : cnt[i] * 1920, st->user);
+        s->done[slots[i]] += cnt[i];
+    }
+    s->delivered += n;
+    return 0;
+}
+
+/* What a lock-step run delivers after a poll: every slot's new frames.  The
  * slots decode in lock step and a slot that stopped was brought up to date by
  * the poll that saw it stop, so every slot with new frames is at the same
- * position; they differ only in how many frames are new (a short tail): one
- * push per distinct count.  sdone[b]: frames of slot b delivered so far. */
-static int batch_stream_flush(qtts_dev_t *dev, int nb, const stream_t *stream, const int *ngen, int *sdone,
-                              float **sbufs, double *t_stream, const int *sref) {
+ * position; they differ only in how many are new (a short tail): one push per
+ * distinct count, in first-seen order.  at_positions (a voice-clone batch:
+ * each stream stands at its primed reference frames + its own): one push for
+ * all, whatever the counts.  The first packet is stamped when a flush that
+ * began with nothing delivered is over: every slot then has its first chunk
+ * (the single stream: only if it pushed). */
+static int batch_flush(qwen_tts_ctx_t *ctx, qtts_dev_t *dev, sstate_t *s, const int *ngen, int at_positions) {
     int todo[QWEN_TTS_MAX_BATCH];
-    for (int b = 0; b < nb; b++) todo[b] = ngen[b] - sdone[b];
-    if (sref) {
-        /* voice clone: stream b stands at sref[b] + sdone[b], its primed
-         * reference frames ahead of its own, so the slots go through the
-         * per-position form; the mixed tail lengths of one poll through the
-         * ragged form, in one push either way */
-        int n = 0, T = 0, same = 1, ids[QWEN_TTS_MAX_BATCH], f0[QWEN_TTS_MAX_BATCH], cnt[QWEN_TTS_MAX_BATCH];
-        float *outs[QWEN_TTS_MAX_BATCH];
-        for (int b = 0; b < nb; b++)
-            if (todo[b] > 0) {
-                ids[n] = b;
-                f0[n] = sdone[b];
-                cnt[n] = todo[b];
-                outs[n++] = sbufs[b] + (size_t)sdone[b] * 1920;
-                if (!T) T = todo[b];
-                same &= todo[b] == T;
-            }
-        if (!n) return 0;
-        const double t0 = now_ms();
-        const int r = same ? qtts_dev_codec_mstream_push_slots_at(dev, n, ids, ids, f0, T, outs)
-                           : qtts_dev_codec_mstream_push_slots_ragged(dev, n, ids, ids, f0, cnt, outs);
-        if (r < 0) return -1;
-        *t_stream += now_ms() - t0;
-        for (int i = 0; i < n; i++) {
-            if (stream->bcb) stream->bcb(ids[i], outs[i], cnt[i] * 1920, stream->user);
-            sdone[ids[i]] += cnt[i];
-        }
-        return 0;
-    }
+    const int first = s->delivered == 0;
+    for (int b = 0; b < s->n; b++) todo[b] = ngen[b] - s->done[b];
     for (;;) {
-        int T = 0, n = 0, ids[QWEN_TTS_MAX_BATCH];
-        float *outs[QWEN_TTS_MAX_BATCH];
-        for (int b = 0; b < nb && !T; b++)
-            if (todo[b] > 0) T = todo[b];
-        if (!T) return 0;
-        for (int b = 0; b < nb; b++)
-            if (todo[b] == T) {
-                ids[n] = b;
-                outs[n++] = sbufs[b] + (size_t)sdone[b] * 1920;
+        int n = 0, T = 0, slots[QWEN_TTS_MAX_BATCH], cnt[QWEN_TTS_MAX_BATCH];
+        for (int b = 0; b < s->n; b++)
+            if (todo[b] > 0 && (at_positions || !T || todo[b] == T)) {
+                if (!T) T = todo[b];
+                slots[n] = b;
+                cnt[n++] = todo[b];
+                todo[b] = 0;
             }
-        const double t0 = now_ms();
-        const int r = qtts_dev_codec_mstream_push_slots(dev, n, ids, ids, sdone[ids[0]], T, outs);
-        if (r < 0) return -1;
-        *t_stream += now_ms() - t0;
-        for (int i = 0; i < n; i++) {
-            if (stream->bcb) stream->bcb(ids[i], outs[i], r, stream->user);
-            sdone[ids[i]] += T;
-            todo[ids[i]] = 0;
-        }
+        if (!n) break;
+        if (stream_deliver(ctx, dev, s, n, slots, cnt, at_positions, NULL) != 0) return -1;
     }
+    if (first && (s->stream->multi || s->delivered)) ctx->perf_first_packet_ms = now_ms() - s->t_start;
+    return 0;
 }
 
+/* The final codec pass of several utterances, side by side on the codec lanes
+ * (qtts_dev_codec_multi).  Job j fills audio[utt] / samples[utt] from n_gen
+ * generated frames: host `codes`, or (NULL) device slot `slot`'s.  An ICL
+ * voice's job carries its reference codes: it decodes reference ++ generated
+ * and keeps the part after the reference (cut_reference).  A job whose codes
+ * cannot be put together, or that comes back without audio, leaves its output
+ * NULL and makes the result -1; the others still decode.  log: the per-job -v
+ * lines of a lock-step batch (the -v -v stage times are a lone decode's only:
+ * the lanes run side by side). */
+typedef struct {
+    int utt, slot, n_gen;
+    const int *codes;
+    const int *ref;
+    int n_ref;
+} codec_job_t;
+
+static int codec_finish(qwen_tts_ctx_t *ctx, qtts_dev_t *dev, int nj, const codec_job_t *jobs, int log,
+                        float **audio, int *samples) {
+    const int G = ctx->config.num_code_groups;
+    const int **hc = (const int **)calloc(nj, sizeof(int *));
+    int **own = (int **)calloc(nj, sizeof(int *));
+    int *slot = (int *)calloc(nj, sizeof(int)), *T = (int *)calloc(nj, sizeof(int));
+    int *of = (int *)calloc(nj, sizeof(int)), *sj = (int *)calloc(nj, sizeof(int));
+    float **aj = (float **)calloc(nj, sizeof(float *));
+    int n = 0, rc = hc && own && slot && T && of && sj && aj ? 0 : -1;
+    for (int j = 0; j < nj && rc == 0; j++) {
+        const codec_job_t *jb = &jobs[j];
+        const int tot = jb->n_ref + jb->n_gen;
+        hc[n] = jb->codes;
+        if (jb->n_ref > 0) {
+            int *all = (int *)malloc((size_t)tot * G * sizeof(int));
+            if (!all) continue;   /* (the job has no audio: -1 below) */
+            int *gen = all + (size_t)jb->n_ref * G;
+            if (jb->codes) {
+                memcpy(gen, jb->codes, (size_t)jb->n_gen * G * sizeof(int));
+            } else if (qtts_dev_get_codes(dev, jb->slot, gen, jb->n_gen) != jb->n_gen) {
+                free(all);
+                continue;
+            }
+            memcpy(all, jb->ref, (size_t)jb->n_ref * G * sizeof(int));
+            hc[n] = own[n] = all;
+        }
+        slot[n] = jb->slot;
+        T[n] = tot;
+        of[n] = j;
+        if (log && qwen_tts_verbose >= 1)
+            fprintf(stderr, "Codec decode: %d timesteps, %d quantizers\n", tot, ctx->config.codec_num_quantizers);
+        n++;
+    }
+    if (rc == 0 && n < nj) rc = -1;
+    if (n > 0 && qtts_dev_codec_multi(dev, n, hc, slot, T, aj, sj) != 0) rc = -1;
+    for (int k = 0; k < n; k++) {
+        const codec_job_t *jb = &jobs[of[k]];
+        if (log && qwen_tts_verbose >= 1 && aj[k] && sj[k] > 0)
+            fprintf(stderr, "Codec decode complete: %d samples (%.2f seconds)\n", sj[k],
+                    (float)sj[k] / QWEN_TTS_SAMPLE_RATE);
+        if (jb->n_ref > 0) {
+            cut_reference(aj[k], sj[k], jb->n_ref, T[k], &audio[jb->utt], &samples[jb->utt]);
+        } else {
+            audio[jb->utt] = aj[k];
+            samples[jb->utt] = aj[k] ? sj[k] : 0;
+        }
+        if (!audio[jb->utt] || samples[jb->utt] <= 0) rc = -1;
+        free(own[k]);
+    }
+    free(hc); free(own); free(slot); free(T); free(of); free(sj); free(aj);
+    return rc;
+}
+
+/* Runs nb utterances in lock-step frames.  Fills per-slot frame counts and
+ * stop info; audio[i] decoded per slot.  Returns 0 on success. */
 static int run_batch(qwen_tts_ctx_t *ctx, int nb, const char *const *texts, const char *const *speakers,
                      const char *const *languages, float **audio, int *samples, double t_start,
                      const stream_t *stream, const vclone_t *vcs /* [nb] or NULL */) {
@@ -988,33 +1138,20 @@ static int run_batch(qwen_tts_ctx_t *ctx, int nb, const char *const *texts, cons
     force_arm_t *arm = (force_arm_t *)ctx->force;   /* one-shot: this call consumes it, however it ends */
     ctx->force = NULL;
     sampling_arm_t *sarm = sampling_take(ctx);      /* and the per-utterance sampling */
-    if (sampling_refused("generate", sarm, arm, nb)) {
-        force_free(arm);
-        sampling_free(sarm);
-        return -1;
-    }
-    prompt_t *pr = (prompt_t *)calloc(nb, sizeof(prompt_t));
+    /* what the run owns: freed at `out`, whichever way it is reached */
+    prompt_t *pr = NULL;
     int *prime_codes = NULL;   /* the reference frames of a streamed voice-clone batch, kept until the run ends */
+    int *stopped = NULL, *ngen = NULL, *sstep = NULL;
+    codec_job_t *jobs = NULL;
+    sstate_t ss;               /* streaming: exact incremental codec decode of the frames produced so far */
+    memset(&ss, 0, sizeof ss);
+    if (sampling_refused("generate", sarm, arm, nb)) goto out;
+    if (!(pr = (prompt_t *)calloc(nb, sizeof(prompt_t)))) goto out;
     int max_p = 0;
     for (int b = 0; b < nb; b++) {
-        int *ids = NULL;
-        int n = parse_ids(texts[b], &ids);
-        if (n < 8) {
-            if (n >= 0) fprintf(stderr, "Error: need at least 8 text tokens (chat template format)\n");
-            free(ids);
+        if (prompt_make(ctx, texts[b], speakers ? speakers[b] : NULL, languages ? languages[b] : NULL,
+                        vcs ? &vcs[b] : NULL, b, &pr[b]) != 0)
             goto out;
-        }
-        for (int i = 0; i < n; i++)
-            if (ids[i] < 0 || ids[i] >= c->talker_text_vocab) {
-                fprintf(stderr, "Error: text token id %d out of range\n", ids[i]);
-                free(ids);
-                goto out;
-            }
-        int spk, lang;
-        lookup(ctx, speakers ? speakers[b] : NULL, languages ? languages[b] : NULL, &spk, &lang);
-        if (vcs) build_icl_prompt(ctx, ids, n, &vcs[b], lang, b, &pr[b]);
-        else build_prompt(ctx, ids, n, spk, lang, b, &pr[b]);
-        free(ids);
         if (pr[b].p_len > max_p) max_p = pr[b].p_len;
     }
     const int fixed = ctx->fixed_codec_tokens > 0 ? ctx->fixed_codec_tokens : 0;
@@ -1043,15 +1180,13 @@ static int run_batch(qwen_tts_ctx_t *ctx, int nb, const char *const *texts, cons
      * reference frames in ONE ragged push of the multi-stream codec
      * (qtts_dev_codec_mstream_prime); an x-vector-only slot has none and its
      * stream stays at position 0 */
-    int mref[QWEN_TTS_MAX_BATCH], *msref = NULL;
     if (multi && vcs) {
         int n = 0, ld = 0, ids[QWEN_TTS_MAX_BATCH], cnt[QWEN_TTS_MAX_BATCH];
         for (int b = 0; b < nb; b++) {
-            mref[b] = vcs[b].ref_codes && vcs[b].n_ref > 0 ? vcs[b].n_ref : 0;
-            if (mref[b] > ld) ld = mref[b];
-            if (mref[b]) { ids[n] = b; cnt[n++] = mref[b]; }
+            const int nr = vcs[b].ref_codes && vcs[b].n_ref > 0 ? vcs[b].n_ref : 0;
+            if (nr > ld) ld = nr;
+            if (nr) { ids[n] = b; cnt[n++] = nr; }
         }
-        msref = mref;
         if (qtts_dev_codec_mstream_begin(dev, nb, max_tokens + ld, 0) != 0) goto out;
         if (n) {
             prime_codes = (int *)calloc((size_t)n * ld * 16, sizeof(int));
@@ -1073,24 +1208,13 @@ static int run_batch(qwen_tts_ctx_t *ctx, int nb, const char *const *texts, cons
         fprintf(stderr, "Talker prefill complete: %d tokens\n", pr[0].p_len);
         fprintf(stderr, "Prefill: %d tokens in %.1f ms\n", pr[0].p_len, t_prefill_done - t_prefill);
     }
-    int *stopped = (int *)calloc(nb, sizeof(int)), *ngen = (int *)calloc(nb, sizeof(int));
-    int *sstep = (int *)calloc(nb, sizeof(int));
-    /* streaming: exact incremental codec decode of the frames produced so far */
-    float *sbuf = NULL;
-    int streamed = 0;
-    double t_stream = 0;
-    float **sbufs = NULL;   /* multi: one buffer per slot, and the frames delivered of each */
-    int *sdone = NULL;
-    if (multi) {
-        sbufs = (float **)calloc(nb, sizeof(float *));
-        sdone = (int *)calloc(nb, sizeof(int));
-        int ok = sbufs && sdone;
-        for (int b = 0; b < nb && ok; b++) ok = (sbufs[b] = (float *)malloc((size_t)max_tokens * 1920 * sizeof(float))) != NULL;
-        if (!ok) { free_bufs(sbufs, nb); free(sdone); free(stopped); free(ngen); free(sstep); goto out; }
-    } else if (stream) {
-        sbuf = (float *)malloc((size_t)max_tokens * 1920 * sizeof(float));
-        if (!sbuf) { free(stopped); free(ngen); free(sstep); goto out; }
-    }
+    stopped = (int *)calloc(nb, sizeof(int));
+    ngen = (int *)calloc(nb, sizeof(int));
+    sstep = (int *)calloc(nb, sizeof(int));
+    if (!stopped || !ngen || !sstep) goto out;
+    if (stream && sstate_init(&ss, stream, nb, max_tokens, t_start, 0) != 0) goto out;
+    const int at_positions = multi && vcs;
+    int streamed = 0;   /* frames of the furthest slot delivered */
     double t_gen = now_ms();
     const int poll_every = fixed > 0 ? 0 : 8;
     /* EOS mode without streaming: a lagged poll per frame (qtts_dev_frame_done)
@@ -1098,7 +1222,7 @@ static int run_batch(qwen_tts_ctx_t *ctx, int nb, const char *const *texts, cons
     const int lagged = fixed == 0 && !stream;
     int step = 0;
     for (; step < max_tokens; step++) {
-        if (qtts_dev_frame(dev, step) != 0) { free_bufs(sbufs, nb); free(sdone); free(sbuf); free(stopped); free(ngen); free(sstep); goto out; }
+        if (qtts_dev_frame(dev, step) != 0) goto out;
         if (step == 0) {
             qtts_dev_poll(dev, NULL, NULL, NULL);
             ctx->perf_first_frame_ms = now_ms() - t_start;
@@ -1106,9 +1230,7 @@ static int run_batch(qwen_tts_ctx_t *ctx, int nb, const char *const *texts, cons
         if (ctx->progress_cb) ctx->progress_cb(step + 1, max_tokens, ctx->progress_cb_userdata);
         if (lagged) {   /* EOS mode: frame step is queued; stop once every slot had stopped by frame step - 1 */
             int done = 0;
-            if (step >= 1 && qtts_dev_frame_done(dev, step - 1, &done) != 0) {
-                free_bufs(sbufs, nb); free(sdone); free(sbuf); free(stopped); free(ngen); free(sstep); goto out;
-            }
+            if (step >= 1 && qtts_dev_frame_done(dev, step - 1, &done) != 0) goto out;
             if (qwen_tts_verbose >= 1 && step > 0 && step % 10 == 0)
                 fprintf(stderr, "\r  Token %d (%.1f ms/token)...", step, (now_ms() - t_gen) / step);
             if (done) break;
@@ -1117,22 +1239,10 @@ static int run_batch(qwen_tts_ctx_t *ctx, int nb, const char *const *texts, cons
         const int want_stream = stream && (step == 0 || step + 1 - streamed >= stream->chunk || step + 1 == max_tokens);
         if (want_stream || (poll_every && ((step + 1) % poll_every == 0 || step + 1 == max_tokens))) {
             qtts_dev_poll(dev, stopped, ngen, sstep);
-            if (multi) {
-                if (batch_stream_flush(dev, nb, stream, ngen, sdone, sbufs, &t_stream, msref) != 0) {
-                    free_bufs(sbufs, nb); free(sdone); free(sbuf); free(stopped); free(ngen); free(sstep); goto out;
-                }
-                if (streamed == 0) ctx->perf_first_packet_ms = now_ms() - t_start;
+            if (stream) {
+                if (batch_flush(ctx, dev, &ss, ngen, at_positions) != 0) goto out;
                 for (int b = 0; b < nb; b++)
-                    if (sdone[b] > streamed) streamed = sdone[b];
-            } else if (stream && ngen[0] > streamed) {
-                const double t0 = now_ms();
-                const int n = qtts_dev_codec_stream_push_slot(dev, 0, streamed, ngen[0] - streamed,
-                                                              sbuf + (size_t)streamed * 1920);
-                if (n < 0) { free_bufs(sbufs, nb); free(sdone); free(sbuf); free(stopped); free(ngen); free(sstep); goto out; }
-                t_stream += now_ms() - t0;
-                if (stream->cb) stream->cb(sbuf + (size_t)streamed * 1920, n, stream->user);
-                if (streamed == 0) ctx->perf_first_packet_ms = now_ms() - t_start;
-                streamed = ngen[0];
+                    if (ss.done[b] > streamed) streamed = ss.done[b];
             }
             int all = 1;
             for (int b = 0; b < nb; b++) all &= stopped[b];
@@ -1142,29 +1252,16 @@ static int run_batch(qwen_tts_ctx_t *ctx, int nb, const char *const *texts, cons
         }
     }
     qtts_dev_poll(dev, stopped, ngen, sstep);
-    if (multi) {
-        if (batch_stream_flush(dev, nb, stream, ngen, sdone, sbufs, &t_stream, msref) != 0) {
-            free_bufs(sbufs, nb); free(sdone); free(sbuf); free(stopped); free(ngen); free(sstep); goto out;
-        }
-        if (streamed == 0) ctx->perf_first_packet_ms = now_ms() - t_start;
-    } else if (stream && ngen[0] > streamed) {
-        const double t0 = now_ms();
-        const int n = qtts_dev_codec_stream_push_slot(dev, 0, streamed, ngen[0] - streamed,
-                                                      sbuf + (size_t)streamed * 1920);
-        if (n < 0) { free_bufs(sbufs, nb); free(sdone); free(sbuf); free(stopped); free(ngen); free(sstep); goto out; }
-        t_stream += now_ms() - t0;
-        if (stream->cb) stream->cb(sbuf + (size_t)streamed * 1920, n, stream->user);
-        if (streamed == 0) ctx->perf_first_packet_ms = now_ms() - t_start;
-        streamed = ngen[0];
-    }
+    if (stream && batch_flush(ctx, dev, &ss, ngen, at_positions) != 0) goto out;
     double t_gen_done = now_ms();
-    ctx->perf_talker_ms = t_gen_done - t_gen - t_stream;
+    ctx->perf_talker_ms = t_gen_done - t_gen - ss.t_stream;
     ctx->perf_codec_tokens = ngen[0];
     ctx->last_stop_reason = stopped[0] ? 1 : 2;
     ctx->last_stop_step = stopped[0] ? sstep[0] : max_tokens;
     free(ctx->last_codes);
     ctx->last_codes = (int *)malloc((size_t)(ngen[0] > 0 ? ngen[0] : 1) * G * sizeof(int));
-    ctx->last_frames = ngen[0] > 0 ? qtts_dev_get_codes(dev, 0, ctx->last_codes, ngen[0]) : 0;
+    ctx->last_frames = ngen[0] > 0 && ctx->last_codes ? qtts_dev_get_codes(dev, 0, ctx->last_codes, ngen[0]) : 0;
+    if (ctx->last_frames < 0) ctx->last_frames = 0;   /* (codes that could not be read: none, not a negative count) */
     if (qwen_tts_verbose >= 1) {
         if (stopped[0]) fprintf(stderr, "EOS at step %d\n", sstep[0]);
         fprintf(stderr, "\r                                        \r");
@@ -1180,20 +1277,14 @@ static int run_batch(qwen_tts_ctx_t *ctx, int nb, const char *const *texts, cons
     }
     double t_codec = now_ms();
     rc = 0;
-    if (multi) {    /* each slot's chunks already are its utterance */
+    if (stream) {   /* each slot's chunks already are its utterance: the buffer goes to the caller */
         for (int b = 0; b < nb; b++) {
-            audio[b] = sbufs[b];
-            samples[b] = sdone[b] * 1920;
-            if (sdone[b] <= 0) { free(sbufs[b]); audio[b] = NULL; rc = -1; }
+            audio[b] = ss.buf[b];
+            ss.buf[b] = NULL;
+            samples[b] = ss.done[b] * 1920;
+            if (ss.done[b] <= 0) { free(audio[b]); audio[b] = NULL; rc = -1; }
         }
-        free(sbufs);
-        free(sdone);
-        ctx->perf_codec_ms = t_stream;
-    } else if (stream) {   /* the streamed chunks already are the utterance */
-        audio[0] = sbuf;
-        samples[0] = streamed * 1920;
-        if (streamed <= 0) { free(sbuf); audio[0] = NULL; rc = -1; }
-        ctx->perf_codec_ms = t_stream;
+        ctx->perf_codec_ms = ss.t_stream;
     } else if (nb == 1) {
         audio[0] = NULL;
         samples[0] = 0;
@@ -1221,78 +1312,63 @@ static int run_batch(qwen_tts_ctx_t *ctx, int nb, const char *const *texts, cons
             if (!audio[0] || samples[0] <= 0) rc = -1;
         }
     } else {
-        /* a batch: every slot's codec pass in one call, several side by side
-         * (qtts_dev_codec_multi); a voice-clone slot decodes its reference ++
-         * generated codes and keeps the part after the reference */
-        int **hc = (int **)calloc(nb, sizeof(int *));
-        int *slot = (int *)calloc(nb, sizeof(int)), *tj = (int *)calloc(nb, sizeof(int));
-        int *bj = (int *)calloc(nb, sizeof(int));
-        float **aj = (float **)calloc(nb, sizeof(float *));
-        int *sj = (int *)calloc(nb, sizeof(int));
+        /* a batch: every slot's codec pass in one call (codec_finish); a slot
+         * without frames gets no audio and makes the call return -1 */
         int nj = 0;
         for (int b = 0; b < nb; b++) {
             audio[b] = NULL;
             samples[b] = 0;
         }
-        if (!hc || !slot || !tj || !bj || !aj || !sj) rc = -1;
-        /* a slot without frames (or whose codes could not be read) gets no
-         * audio and makes the call return -1; the other slots still decode */
-        for (int b = 0; b < nb && hc && slot && tj && bj && aj && sj; b++) {
+        if (!(jobs = (codec_job_t *)calloc(nb, sizeof(codec_job_t)))) rc = -1;
+        for (int b = 0; b < nb && jobs; b++) {
             if (ngen[b] <= 0) { rc = -1; continue; }
-            const vclone_t *vc = vcs && vcs[b].ref_codes && vcs[b].n_ref > 0 ? &vcs[b] : NULL;
-            slot[nj] = b;
-            bj[nj] = b;
-            tj[nj] = (vc ? vc->n_ref : 0) + ngen[b];
-            if (vc) {
-                hc[nj] = (int *)malloc((size_t)tj[nj] * G * sizeof(int));
-                if (!hc[nj] || qtts_dev_get_codes(dev, b, hc[nj] + (size_t)vc->n_ref * G, ngen[b]) != ngen[b]) {
-                    free(hc[nj]);
-                    hc[nj] = NULL;
-                    rc = -1;
-                    continue;
-                }
-                memcpy(hc[nj], vc->ref_codes, (size_t)vc->n_ref * G * sizeof(int));
-            }
-            /* (-v lines per slot; the -v -v stage times are taken for a lone
-             * decode only: the lanes of a batch run side by side) */
-            if (qwen_tts_verbose >= 1)
-                fprintf(stderr, "Codec decode: %d timesteps, %d quantizers\n", tj[nj], c->codec_num_quantizers);
-            nj++;
+            const int icl = vcs && vcs[b].ref_codes && vcs[b].n_ref > 0;
+            const codec_job_t jb = {b, b, ngen[b], NULL, icl ? vcs[b].ref_codes : NULL, icl ? vcs[b].n_ref : 0};
+            jobs[nj++] = jb;
         }
-        if (nj > 0 && qtts_dev_codec_multi(dev, nj, (const int *const *)hc, slot, tj, aj, sj) != 0) rc = -1;
-        for (int j = 0; j < nj; j++) {
-            const int b = bj[j];
-            if (qwen_tts_verbose >= 1 && aj[j] && sj[j] > 0)
-                fprintf(stderr, "Codec decode complete: %d samples (%.2f seconds)\n", sj[j],
-                        (float)sj[j] / QWEN_TTS_SAMPLE_RATE);
-            if (hc[j]) {
-                cut_reference(aj[j], sj[j], vcs[b].n_ref, tj[j], &audio[b], &samples[b]);
-                aj[j] = NULL;
-            } else {
-                audio[b] = aj[j];
-                samples[b] = sj[j];
-                aj[j] = NULL;
-            }
-            if (!audio[b] || samples[b] <= 0) rc = -1;
-        }
-        for (int j = 0; j < nb; j++) {
-            if (hc) free(hc[j]);
-            if (aj) free(aj[j]);
-        }
-        free(hc); free(slot); free(tj); free(bj); free(aj); free(sj);
+        if (nj > 0 && codec_finish(ctx, dev, nj, jobs, 1, audio, samples) != 0) rc = -1;
     }
     if (!stream) {
         ctx->perf_codec_ms = now_ms() - t_codec;
     }
     ctx->perf_total_ms = now_ms() - t_start;
-    free(stopped); free(ngen); free(sstep);
 out:
     force_free(arm);
     sampling_free(sarm);
     free(prime_codes);
-    for (int b = 0; b < nb; b++) { free(pr[b].text); free(pr[b].plan); }
-    free(pr);
+    free(stopped); free(ngen); free(sstep);
+    free(jobs);
+    sstate_free(&ss);
+    prompts_free(pr, nb);
     return rc;
+}
+
+/* how every single-utterance entry ends: the one output of its batch form, or NULL */
+static float *one_result(int rc, float *audio, int n, int *out_samples) {
+    *out_samples = 0;
+    if (rc != 0 || !audio || n <= 0) {
+        free(audio);
+        return NULL;
+    }
+    *out_samples = n;
+    return audio;
+}
+
+/* the -v lines that end a call of n utterances: streamed: the first packet
+ * first; batch: the audio summed over the utterances */
+static void log_totals(const qwen_tts_ctx_t *ctx, int streamed, int batch, int n, const int *samples) {
+    if (qwen_tts_verbose < 1) return;
+    if (streamed) fprintf(stderr, "First packet: %.1f ms\n", ctx->perf_first_packet_ms);
+    if (!batch) {
+        fprintf(stderr, "Total: %.1f ms (%.2f s audio, %.2fx realtime)\n", ctx->perf_total_ms,
+                (float)samples[0] / QWEN_TTS_SAMPLE_RATE,
+                ((float)samples[0] / QWEN_TTS_SAMPLE_RATE) / (ctx->perf_total_ms / 1000.0));
+        return;
+    }
+    double secs = 0;
+    for (int i = 0; i < n; i++) secs += (double)samples[i] / QWEN_TTS_SAMPLE_RATE;
+    fprintf(stderr, "Total: %.1f ms (%.2f s audio over %d utterances, %.2fx realtime)\n", ctx->perf_total_ms, secs, n,
+            secs / (ctx->perf_total_ms / 1000.0));
 }
 
 float *qwen_tts_generate(qwen_tts_ctx_t *ctx, const char *text, const char *speaker, const char *language,
@@ -1303,18 +1379,10 @@ float *qwen_tts_generate(qwen_tts_ctx_t *ctx, const char *text, const char *spea
     float *audio = NULL;
     int n = 0;
     const char *texts[1] = {text}, *spk[1] = {speaker}, *lang[1] = {language};
-    int rc = run_batch(ctx, 1, texts, spk, lang, &audio, &n, t_start, NULL, NULL);
-    if (rc != 0 || !audio || n <= 0) {
-        free(audio);
-        *out_samples = 0;
-        return NULL;
-    }
-    if (qwen_tts_verbose >= 1) {
-        fprintf(stderr, "Codec decode: %d samples in %.1f ms\n", n, ctx->perf_codec_ms);
-        fprintf(stderr, "Total: %.1f ms (%.2f s audio, %.2fx realtime)\n", ctx->perf_total_ms,
-                (float)n / QWEN_TTS_SAMPLE_RATE, ((float)n / QWEN_TTS_SAMPLE_RATE) / (ctx->perf_total_ms / 1000.0));
-    }
-    *out_samples = n;
+    const int rc = run_batch(ctx, 1, texts, spk, lang, &audio, &n, t_start, NULL, NULL);
+    audio = one_result(rc, audio, n, out_samples);
+    if (audio && qwen_tts_verbose >= 1) fprintf(stderr, "Codec decode: %d samples in %.1f ms\n", n, ctx->perf_codec_ms);
+    if (audio) log_totals(ctx, 0, 0, 1, &n);
     return audio;
 }
 
@@ -1364,52 +1432,29 @@ static void queue_plan_slot(prompt_t *p, int b) {
 
 /* The streaming queue (stream != NULL; qwen_tts_generate_queue_stream): every
  * slot's frames go through a multi-stream codec stream of its own as they are
- * decoded.  Slot b's stream is stream_of_slot[b]: a refill resets it, the
- * tail compaction moves the map entry, never codec state.  After the wait for
+ * decoded (sstate_t).  Slot b's stream is stream_of_slot[b]: a refill resets it,
+ * the tail compaction moves the map entry, never codec state.  After the wait for
  * frame step - 1, slot b has avail = min(step - first[b], its frame count if
- * it stopped) finished frames, sdone[b] of them delivered.  A slot is due when
+ * it stopped) finished frames, done[b] of them delivered.  A slot is due when
  * it has delivered nothing and has a frame (the first packet: one frame), when
  * its utterance is complete (the tail: everything, before the slot's codes
  * rows are reused), or at the call's cadence (step % chunk == 0); the due
- * slots go in one push per distinct frame count, whatever their positions. */
-typedef struct {
-    const stream_t *stream;
-    int *stream_of_slot, *sdone;     /* [slots] */
-    float **sbuf;                    /* [slots] max_tokens * 1920 samples each */
-    double t_stream, t_start;
-    int delivered;                   /* callbacks so far */
-} qstream_t;
-
-static int queue_stream_flush(qwen_tts_ctx_t *ctx, qtts_dev_t *dev, qstream_t *q, int ns, const int *cur,
-                              const int *avail, const int *complete, int cadence) {
+ * slots go in one push per distinct frame count, whatever their positions
+ * (stream_deliver; the callback gets the utterance's index cur[slot]). */
+static int queue_flush(qwen_tts_ctx_t *ctx, qtts_dev_t *dev, sstate_t *s, const int *cur, const int *avail,
+                       const int *complete, int cadence) {
     for (;;) {
-        int todo[QWEN_TTS_MAX_BATCH], T = 0;
-        for (int b = 0; b < ns; b++) {
-            todo[b] = 0;
-            if (cur[b] < 0 || avail[b] <= q->sdone[b]) continue;
-            if (q->sdone[b] == 0) todo[b] = 1;
-            else if (complete[b] || cadence) todo[b] = avail[b] - q->sdone[b];
-            if (todo[b] > 0 && !T) T = todo[b];
+        int n = 0, T = 0, slots[QWEN_TTS_MAX_BATCH], cnt[QWEN_TTS_MAX_BATCH];
+        for (int b = 0; b < s->n; b++) {
+            int todo = 0;
+            if (cur[b] < 0 || avail[b] <= s->done[b]) continue;
+            if (s->done[b] == 0) todo = 1;
+            else if (complete[b] || cadence) todo = avail[b] - s->done[b];
+            if (todo > 0 && !T) T = todo;
+            if (todo > 0 && todo == T) { slots[n] = b; cnt[n++] = T; }
         }
-        if (!T) return 0;
-        int n = 0, ids[QWEN_TTS_MAX_BATCH], sl[QWEN_TTS_MAX_BATCH], f0[QWEN_TTS_MAX_BATCH];
-        float *outs[QWEN_TTS_MAX_BATCH];
-        for (int b = 0; b < ns; b++)
-            if (todo[b] == T) {
-                ids[n] = q->stream_of_slot[b];
-                sl[n] = b;
-                f0[n] = q->sdone[b];
-                outs[n++] = q->sbuf[b] + (size_t)q->sdone[b] * 1920;
-            }
-        const double t0 = now_ms();
-        const int r = qtts_dev_codec_mstream_push_slots_at(dev, n, ids, sl, f0, T, outs);
-        if (r < 0) return -1;
-        q->t_stream += now_ms() - t0;
-        for (int i = 0; i < n; i++) {
-            if (q->delivered++ == 0) ctx->perf_first_packet_ms = now_ms() - q->t_start;
-            if (q->stream->bcb) q->stream->bcb(cur[sl[i]], outs[i], r, q->stream->user);
-            q->sdone[sl[i]] += T;
-        }
+        if (!n) return 0;
+        if (stream_deliver(ctx, dev, s, n, slots, cnt, 1, cur) != 0) return -1;
     }
 }
 
@@ -1519,7 +1564,9 @@ static int queue_run(qwen_tts_ctx_t *ctx, const char *who, int nq, const char *c
     int *cur = (int *)malloc(nb * sizeof(int)), *first = (int *)calloc(nb, sizeof(int));
     int *retired = (int *)calloc(nb, sizeof(int)), *hst = (int *)calloc(nb, sizeof(int));
     int *cbuf = NULL;
-    qstream_t qs = {stream, NULL, NULL, NULL, 0, t_start, 0};
+    sstate_t qs;
+    memset(&qs, 0, sizeof qs);
+    codec_job_t *jobs = NULL;
     int *avail = NULL, *complete = NULL, *ngen = NULL, finished = 0;
     /* the voice queue: utterance i's prompt inputs, from its handle */
     vclone_t *vcs = voices ? (vclone_t *)calloc(nq, sizeof(vclone_t)) : NULL;
@@ -1540,24 +1587,9 @@ static int queue_run(qwen_tts_ctx_t *ctx, const char *who, int nq, const char *c
     /* every prompt up front (the prefill and trailing capacities cover all) */
     int max_p = 0, max_tr = 0;
     for (int i = 0; i < nq; i++) {
-        int *ids = NULL;
-        const int n = parse_ids(texts[i], &ids);
-        if (n < 8) {
-            if (n >= 0) fprintf(stderr, "Error: need at least 8 text tokens (chat template format)\n");
-            free(ids);
+        if (prompt_make(ctx, texts[i], speakers ? speakers[i] : NULL, languages ? languages[i] : NULL,
+                        vcs ? &vcs[i] : NULL, 0, &pr[i]) != 0)
             goto out;
-        }
-        for (int k = 0; k < n; k++)
-            if (ids[k] < 0 || ids[k] >= c->talker_text_vocab) {
-                fprintf(stderr, "Error: text token id %d out of range\n", ids[k]);
-                free(ids);
-                goto out;
-            }
-        int spk, lang;
-        lookup(ctx, speakers ? speakers[i] : NULL, languages ? languages[i] : NULL, &spk, &lang);
-        if (vcs) build_icl_prompt(ctx, ids, n, &vcs[i], lang, 0, &pr[i]);
-        else build_prompt(ctx, ids, n, spk, lang, 0, &pr[i]);
-        free(ids);
         if (pr[i].p_len > max_p) max_p = pr[i].p_len;
         if (pr[i].n_trailing > max_tr) max_tr = pr[i].n_trailing;
     }
@@ -1581,17 +1613,10 @@ static int queue_run(qwen_tts_ctx_t *ctx, const char *who, int nq, const char *c
          * voices without a snapshot are primed and saved once, here) */
         if (qtts_dev_codec_mstream_begin(dev, ns, max_tokens + max_ref, 0) != 0) goto out;
         if (voices && voices_prime(dev, nq, voices, ns, max_ref, &prime_codes) != 0) goto out;
-        qs.stream_of_slot = (int *)malloc(ns * sizeof(int));
-        qs.sdone = (int *)calloc(ns, sizeof(int));
-        qs.sbuf = (float **)calloc(ns, sizeof(float *));
         avail = (int *)calloc(ns, sizeof(int));
         complete = (int *)calloc(ns, sizeof(int));
         ngen = (int *)calloc(ns, sizeof(int));
-        if (!qs.stream_of_slot || !qs.sdone || !qs.sbuf || !avail || !complete || !ngen) goto out;
-        for (int b = 0; b < ns; b++) {
-            qs.stream_of_slot[b] = b;
-            if (!(qs.sbuf[b] = (float *)malloc((size_t)max_tokens * 1920 * sizeof(float)))) goto out;
-        }
+        if (sstate_init(&qs, stream, ns, max_tokens, t_start, 1) != 0 || !avail || !complete || !ngen) goto out;
     }
     /* (a plan row's 4th int is the destination slot: set when the slot is known) */
     /* (the admitted utterance's sampling row goes in with its prompt: before
@@ -1648,7 +1673,7 @@ static int queue_run(qwen_tts_ctx_t *ctx, const char *who, int nq, const char *c
                 avail[b] = cur[b] < 0 ? 0 : complete[b] ? ngen[b] : step - first[b];
                 if (avail[b] > max_tokens) avail[b] = max_tokens;
             }
-            if (queue_stream_flush(ctx, dev, &qs, ns, cur, avail, complete, cadence) != 0) goto out;
+            if (queue_flush(ctx, dev, &qs, cur, avail, complete, cadence) != 0) goto out;
         }
         for (int b = 0; b < ns; b++) {
             if (cur[b] < 0) continue;
@@ -1670,13 +1695,13 @@ static int queue_run(qwen_tts_ctx_t *ctx, const char *who, int nq, const char *c
                 fprintf(stderr, "Queue: utterance %d on slot %d: %s at step %d (frame %d)\n", u, b,
                         hst[b] ? "eos" : "max_tokens", n, step - 1);
             if (stream) {   /* its chunks already are the utterance (flushed above) */
-                if (qs.sdone[b] != n) goto out;
+                if (qs.done[b] != n) goto out;
                 if (n > 0) {
                     if (!(out_audio[u] = (float *)malloc((size_t)n * 1920 * sizeof(float)))) goto out;
-                    memcpy(out_audio[u], qs.sbuf[b], (size_t)n * 1920 * sizeof(float));
+                    memcpy(out_audio[u], qs.buf[b], (size_t)n * 1920 * sizeof(float));
                     out_samples[u] = n * 1920;
                 }
-                qs.sdone[b] = 0;
+                qs.done[b] = 0;
             }
             cur[b] = -1;
             active--;
@@ -1706,10 +1731,10 @@ static int queue_run(qwen_tts_ctx_t *ctx, const char *who, int nq, const char *c
                 cur[j] = -1;
                 if (stream) {   /* the slot's stream, frames delivered and chunk buffer travel with it */
                     const int sw = qs.stream_of_slot[i];
-                    float *bw = qs.sbuf[i];
+                    float *bw = qs.buf[i];
                     qs.stream_of_slot[i] = qs.stream_of_slot[j]; qs.stream_of_slot[j] = sw;
-                    qs.sbuf[i] = qs.sbuf[j]; qs.sbuf[j] = bw;
-                    qs.sdone[i] = qs.sdone[j]; qs.sdone[j] = 0;
+                    qs.buf[i] = qs.buf[j]; qs.buf[j] = bw;
+                    qs.done[i] = qs.done[j]; qs.done[j] = 0;
                 }
             }
             rows = active;
@@ -1727,48 +1752,22 @@ static int queue_run(qwen_tts_ctx_t *ctx, const char *who, int nq, const char *c
             if (ctx->queue_frames[u] == 0) rc = -1;   /* (taken, no frame: no audio) */
         ctx->perf_codec_ms = qs.t_stream;
     } else {
-        /* every finished utterance's codec pass, several side by side */
+        /* every finished utterance's codec pass from its collected codes
+         * (codec_finish; an ICL voice's with its reference codes ahead) */
         int nj = 0;
-        int *uj = (int *)malloc(nq * sizeof(int)), *tj = (int *)malloc(nq * sizeof(int));
-        int *sl = (int *)calloc(nq, sizeof(int)), *sj = (int *)calloc(nq, sizeof(int));
-        const int **hc = (const int **)calloc(nq, sizeof(int *));
-        float **aj = (float **)calloc(nq, sizeof(float *));
-        if (!uj || !tj || !sl || !sj || !hc || !aj) {
-            free(uj); free(tj); free(sl); free(sj); free(hc); free(aj);
-            goto out;
-        }
+        if (!(jobs = (codec_job_t *)calloc(nq, sizeof(codec_job_t)))) goto out;
         rc = 0;
         for (int u = 0; u < nq; u++) {
             if (ctx->queue_frames[u] < 0) continue;   /* not taken by this ctx */
             if (ctx->queue_frames[u] == 0) { rc = -1; continue; }
-            uj[nj] = u; tj[nj] = ctx->queue_frames[u]; hc[nj] = ctx->queue_codes[u];
-            if (vcs && vcs[u].n_ref > 0) {
-                /* an ICL voice decodes reference ++ generated codes and keeps the part after the reference */
-                int *all = (int *)malloc((size_t)(vcs[u].n_ref + tj[nj]) * G * sizeof(int));
-                if (!all) { rc = -1; continue; }
-                memcpy(all, vcs[u].ref_codes, (size_t)vcs[u].n_ref * G * sizeof(int));
-                memcpy(all + (size_t)vcs[u].n_ref * G, ctx->queue_codes[u], (size_t)tj[nj] * G * sizeof(int));
-                hc[nj] = all;
-                tj[nj] += vcs[u].n_ref;
-            }
-            nj++;
+            const int icl = vcs && vcs[u].n_ref > 0;
+            const codec_job_t jb = {u, 0, ctx->queue_frames[u], ctx->queue_codes[u], icl ? vcs[u].ref_codes : NULL,
+                                    icl ? vcs[u].n_ref : 0};
+            jobs[nj++] = jb;
         }
         const double t_codec = now_ms();
-        if (nj > 0 && qtts_dev_codec_multi(dev, nj, hc, sl, tj, aj, sj) != 0) rc = -1;
-        for (int j = 0; j < nj; j++) {
-            const int u = uj[j];
-            if (vcs && vcs[u].n_ref > 0) {
-                cut_reference(aj[j], sj[j], vcs[u].n_ref, tj[j], &out_audio[u], &out_samples[u]);
-                free((void *)hc[j]);
-                if (!out_audio[u]) rc = -1;
-                continue;
-            }
-            out_audio[u] = aj[j];
-            out_samples[u] = aj[j] ? sj[j] : 0;
-            if (!aj[j] || sj[j] <= 0) rc = -1;
-        }
+        if (nj > 0 && codec_finish(ctx, dev, nj, jobs, 0, out_audio, out_samples) != 0) rc = -1;
         ctx->perf_codec_ms = now_ms() - t_codec;
-        free(uj); free(tj); free(sl); free(sj); free(hc); free(aj);
     }
     ctx->perf_total_ms = now_ms() - t_start;
     if (qwen_tts_verbose >= 1)
@@ -1776,15 +1775,12 @@ static int queue_run(qwen_tts_ctx_t *ctx, const char *who, int nq, const char *c
                 done_n, ns, ctx->queue_frames_launched, ctx->queue_rows_launched, ctx->queue_refills,
                 (double)ctx->queue_slot_frames_used / (double)ctx->queue_rows_launched);
 out:
-    if (pr)
-        for (int i = 0; i < nq; i++) { free(pr[i].text); free(pr[i].plan); }
-    free(pr); free(taken); free(cur); free(first); free(retired); free(hst); free(cbuf);
-    if (stream) {
-        if (!finished)   /* a run that failed part-way returns nothing */
-            for (int u = 0; u < nq; u++) { free(out_audio[u]); out_audio[u] = NULL; out_samples[u] = 0; }
-        free_bufs(qs.sbuf, ctx->queue_slots);
-        free(qs.stream_of_slot); free(qs.sdone); free(avail); free(complete); free(ngen);
-    }
+    prompts_free(pr, nq);
+    free(taken); free(cur); free(first); free(retired); free(hst); free(cbuf); free(jobs);
+    if (stream && !finished)   /* a run that failed part-way returns nothing */
+        for (int u = 0; u < nq; u++) { free(out_audio[u]); out_audio[u] = NULL; out_samples[u] = 0; }
+    sstate_free(&qs);
+    free(avail); free(complete); free(ngen);
     sampling_free(sarm);
     free(vcs);
     free(prime_codes);
@@ -1810,6 +1806,39 @@ int qwen_tts_generate_voice_queue(qwen_tts_ctx_t *ctx, int nq, const char *const
                      out_samples, NULL, voices, non_streaming);
 }
 
+/* Reference audio -> what a voice clone takes (create_voice_clone_prompt,
+ * qwen3_tts_model.py:356-458): every audio's 12 Hz codes in ONE padded batch
+ * (codes [nb][*ld][16], frames[nb]) and each x-vector on its own audio (xv
+ * [nb][hidden]); both malloc'd, the caller frees them, also after a failure.
+ * -1 with the message for a model without the encoders and for an ICL
+ * utterance (x_vector_only NULL or 0 for it) without its ref_text. */
+static int ref_audio_encode(qwen_tts_ctx_t *ctx, int nb, const char *const *ref_texts, const float *const *wavs,
+                            const int *n_samples, const int *x_vector_only, int **codes, int *ld, int *frames,
+                            float **xv) {
+    qtts_dev_t *dev = (qtts_dev_t *)ctx->hip;
+    *codes = NULL;
+    *xv = NULL;
+    *ld = 0;
+    if ((qtts_dev_enc_available(dev) & 3) != 3) {
+        fprintf(stderr, "Error: the model directory has no speaker encoder / 12 Hz encoder weights\n");
+        return -1;
+    }
+    for (int b = 0; b < nb; b++)
+        if ((!x_vector_only || !x_vector_only[b]) && (!ref_texts || !ref_texts[b] || !ref_texts[b][0])) {
+            fprintf(stderr, "Error: ref_text is required when x_vector_only_mode=False (ICL mode). Bad index=%d\n", b);
+            return -1;
+        }
+    for (int b = 0; b < nb; b++) {
+        const int T = (n_samples[b] + 1919) / 1920;
+        if (T > *ld) *ld = T;
+    }
+    *codes = (int *)malloc((size_t)nb * (*ld > 0 ? *ld : 1) * 16 * sizeof(int));
+    *xv = (float *)malloc((size_t)nb * ctx->config.talker_hidden * sizeof(float));
+    if (!*codes || !*xv) return -1;
+    if (qtts_dev_encode_audio(dev, nb, wavs, n_samples, *codes, *ld, frames, NULL) != 0) return -1;
+    return qtts_dev_speaker_embed(dev, nb, wavs, n_samples, *xv, NULL);
+}
+
 /* ------------------------------------------------------------- voice handles */
 static qwen_tts_voice_t *voice_new(qwen_tts_ctx_t *ctx, const char *ref_text, const int *ref_codes, int n_ref,
                                    const float *spk) {
@@ -1824,18 +1853,10 @@ static qwen_tts_voice_t *voice_new(qwen_tts_ctx_t *ctx, const char *ref_text, co
     v->ctx = ctx;
     v->hip = ctx->hip;
     if (icl) {
-        v->n_ref_ids = ref_text ? parse_ids(ref_text, &v->ref_ids) : 0;
-        if (v->n_ref_ids < 5) {
-            fprintf(stderr, "Error: ICL voice clone needs the reference text ids (chat template, >= 5 ids)\n");
+        if ((v->n_ref_ids = ref_text_ids(ctx, ref_text, &v->ref_ids)) < 0) {
             qwen_tts_voice_free(v);
             return NULL;
         }
-        for (int i = 0; i < v->n_ref_ids; i++)
-            if (v->ref_ids[i] < 0 || v->ref_ids[i] >= ctx->config.talker_text_vocab) {
-                fprintf(stderr, "Error: text token id %d out of range\n", v->ref_ids[i]);
-                qwen_tts_voice_free(v);
-                return NULL;
-            }
         v->ref_codes = (int *)malloc((size_t)n_ref * 16 * sizeof(int));
         if (v->ref_codes) memcpy(v->ref_codes, ref_codes, (size_t)n_ref * 16 * sizeof(int));
         v->n_ref = n_ref;
@@ -1859,24 +1880,13 @@ qwen_tts_voice_t *qwen_tts_voice_create(qwen_tts_ctx_t *ctx, const char *ref_tex
 qwen_tts_voice_t *qwen_tts_voice_create_audio(qwen_tts_ctx_t *ctx, const char *ref_text, const float *ref_wav,
                                               int n_ref_samples, int x_vector_only) {
     if (!ctx || !ctx->hip || !ref_wav || n_ref_samples <= 0) return NULL;
-    qtts_dev_t *dev = (qtts_dev_t *)ctx->hip;
-    if ((qtts_dev_enc_available(dev) & 3) != 3) {
-        fprintf(stderr, "Error: the model directory has no speaker encoder / 12 Hz encoder weights\n");
-        return NULL;
-    }
-    if (!x_vector_only && (!ref_text || !ref_text[0])) {
-        fprintf(stderr, "Error: ref_text is required when x_vector_only_mode=False (ICL mode). Bad index=0\n");
-        return NULL;
-    }
-    const int T = (n_ref_samples + 1919) / 1920, H = ctx->config.talker_hidden;
-    int *codes = (int *)malloc((size_t)T * 16 * sizeof(int));
-    float *xv = (float *)malloc((size_t)H * sizeof(float));
+    const char *rt[1] = {ref_text};
     const float *w[1] = {ref_wav};
-    const int n[1] = {n_ref_samples};
-    int fr = 0;
+    const int n[1] = {n_ref_samples}, xo[1] = {x_vector_only};
+    int *codes = NULL, ld = 0, fr = 0;
+    float *xv = NULL;
     qwen_tts_voice_t *v = NULL;
-    if (codes && xv && qtts_dev_encode_audio(dev, 1, w, n, codes, T, &fr, NULL) == 0 &&
-        qtts_dev_speaker_embed(dev, 1, w, n, xv, NULL) == 0)
+    if (ref_audio_encode(ctx, 1, rt, w, n, xo, &codes, &ld, &fr, &xv) == 0)
         v = voice_new(ctx, x_vector_only ? NULL : ref_text, x_vector_only ? NULL : codes, x_vector_only ? 0 : fr, xv);
     free(codes);
     free(xv);
@@ -1943,19 +1953,9 @@ static int vclone_run(qwen_tts_ctx_t *ctx, int nb, const char *const *texts, con
             continue;
         }
         int *rid = NULL;
-        vc->n_ref_ids = ref_texts && ref_texts[b] ? parse_ids(ref_texts[b], &rid) : 0;
+        vc->n_ref_ids = ref_text_ids(ctx, ref_texts ? ref_texts[b] : NULL, &rid);
         vc->ref_ids = rid;
-        if (vc->n_ref_ids < 5) {
-            fprintf(stderr, "Error: ICL voice clone needs the reference text ids (chat template, >= 5 ids)\n");
-            rc = -1;
-            continue;
-        }
-        for (int i = 0; i < vc->n_ref_ids; i++)
-            if (rid[i] < 0 || rid[i] >= ctx->config.talker_text_vocab) {
-                fprintf(stderr, "Error: text token id %d out of range\n", rid[i]);
-                rc = -1;
-                break;
-            }
+        if (vc->n_ref_ids < 0) rc = -1;
         vc->ref_codes = codes;
         vc->n_ref = nref;
     }
@@ -1987,13 +1987,7 @@ static int vclone_batch_stream(qwen_tts_ctx_t *ctx, int nb, const char *const *t
     if (ctx) ctx->perf_first_packet_ms = 0;
     const int rc = vclone_run(ctx, nb, texts, ref_texts, ref_codes, n_ref_frames, spk_embeds, languages, non_streaming,
                               out_audio, out_samples, &st, t_start);
-    if (rc == 0 && qwen_tts_verbose >= 1) {
-        double secs = 0;
-        for (int b = 0; b < nb; b++) secs += (double)out_samples[b] / QWEN_TTS_SAMPLE_RATE;
-        fprintf(stderr, "First packet: %.1f ms\n", ctx->perf_first_packet_ms);
-        fprintf(stderr, "Total: %.1f ms (%.2f s audio over %d utterances, %.2fx realtime)\n", ctx->perf_total_ms, secs,
-                nb, secs / (ctx->perf_total_ms / 1000.0));
-    }
+    if (rc == 0) log_totals(ctx, 1, 1, nb, out_samples);
     return rc;
 }
 
@@ -2007,47 +2001,37 @@ int qwen_tts_generate_voice_clone_batch_stream(qwen_tts_ctx_t *ctx, int nb, cons
                                non_streaming, chunk_frames, cb, userdata, out_audio, out_samples, now_ms());
 }
 
-float *qwen_tts_generate_voice_clone_stream(qwen_tts_ctx_t *ctx, const char *text, const char *ref_text,
-                                            const int *ref_codes, int n_ref_frames, const float *spk_embed,
-                                            const char *language, int non_streaming, int chunk_frames,
-                                            qwen_tts_audio_cb cb, void *userdata, int *out_samples) {
+/* one utterance through vclone_run (st NULL: not streamed) */
+static float *vclone_one(qwen_tts_ctx_t *ctx, const char *text, const char *ref_text, const int *ref_codes,
+                         int n_ref_frames, const float *spk_embed, const char *language, int non_streaming,
+                         const stream_t *st, int *out_samples) {
     if (!ctx || !out_samples) return NULL;
     *out_samples = 0;
-    stream_t st = {cb, userdata, chunk_frames > 0 ? chunk_frames : 1};
     float *audio = NULL;
     int n = 0;
     const char *texts[1] = {text}, *rt[1] = {ref_text}, *lang[1] = {language};
     const int *rc1[1] = {ref_codes};
     const int nr1[1] = {n_ref_frames};
     const float *sv1[1] = {spk_embed};
-    ctx->perf_first_packet_ms = 0;
-    if (vclone_run(ctx, 1, texts, rt, rc1, nr1, sv1, lang, non_streaming, &audio, &n, &st, 0) != 0 || !audio ||
-        n <= 0) {
-        free(audio);
-        return NULL;
-    }
-    *out_samples = n;
-    return audio;
+    if (st) ctx->perf_first_packet_ms = 0;
+    const int rc = vclone_run(ctx, 1, texts, rt, rc1, nr1, sv1, lang, non_streaming, &audio, &n, st, 0);
+    return one_result(rc, audio, n, out_samples);
+}
+
+float *qwen_tts_generate_voice_clone_stream(qwen_tts_ctx_t *ctx, const char *text, const char *ref_text,
+                                            const int *ref_codes, int n_ref_frames, const float *spk_embed,
+                                            const char *language, int non_streaming, int chunk_frames,
+                                            qwen_tts_audio_cb cb, void *userdata, int *out_samples) {
+    const stream_t st = {cb, userdata, chunk_frames > 0 ? chunk_frames : 1};
+    return vclone_one(ctx, text, ref_text, ref_codes, n_ref_frames, spk_embed, language, non_streaming, &st,
+                      out_samples);
 }
 
 float *qwen_tts_generate_voice_clone(qwen_tts_ctx_t *ctx, const char *text, const char *ref_text,
                                      const int *ref_codes, int n_ref_frames, const float *spk_embed,
                                      const char *language, int non_streaming, int *out_samples) {
-    if (!ctx || !out_samples) return NULL;
-    *out_samples = 0;
-    float *audio = NULL;
-    int n = 0;
-    const char *texts[1] = {text}, *rt[1] = {ref_text}, *lang[1] = {language};
-    const int *rc1[1] = {ref_codes};
-    const int nr1[1] = {n_ref_frames};
-    const float *sv1[1] = {spk_embed};
-    if (qwen_tts_generate_voice_clone_batch(ctx, 1, texts, rt, rc1, nr1, sv1, lang, non_streaming, &audio, &n) != 0 ||
-        !audio || n <= 0) {
-        free(audio);
-        return NULL;
-    }
-    *out_samples = n;
-    return audio;
+    return vclone_one(ctx, text, ref_text, ref_codes, n_ref_frames, spk_embed, language, non_streaming, NULL,
+                      out_samples);
 }
 
 /* ------------------------------------------- voice clone from reference audio (N3) */
@@ -2084,11 +2068,10 @@ int *qwen_tts_encode_audio(qwen_tts_ctx_t *ctx, const float *wav, int n_samples,
     return codes;
 }
 
-/* create_voice_clone_prompt (qwen3_tts_model.py:356-458) + generate_voice_clone:
- * every reference audio is encoded in ONE padded batch (the tokenizer's batch
- * encode, :427), each x-vector on its own audio (:446), then the codes /
- * x-vector voice clone above.  x_vector_only[b] (NULL: all 0) drops the codes
- * of slot b (ref_code=None, :451). */
+/* generate_voice_clone on reference audio: the audio is encoded
+ * (ref_audio_encode), then the codes / x-vector voice clone above.
+ * x_vector_only[b] (NULL: all 0) drops the codes of slot b (ref_code=None,
+ * qwen3_tts_model.py:451). */
 typedef struct {                 /* the streamed form's extra arguments */
     int chunk_frames;
     qwen_tts_batch_audio_cb cb;
@@ -2106,32 +2089,11 @@ static int vclone_audio_run(qwen_tts_ctx_t *ctx, int nb, const char *const *text
         return -1;
     }
     for (int b = 0; b < nb; b++) { out_audio[b] = NULL; out_samples[b] = 0; }
-    qtts_dev_t *dev = (qtts_dev_t *)ctx->hip;
-    if ((qtts_dev_enc_available(dev) & 3) != 3) {
-        fprintf(stderr, "Error: the model directory has no speaker encoder / 12 Hz encoder weights\n");
-        force_disarm(ctx);
-        return -1;
-    }
-    for (int b = 0; b < nb; b++)
-        if (!x_vector_only || !x_vector_only[b])
-            if (!ref_texts || !ref_texts[b] || !ref_texts[b][0]) {
-                fprintf(stderr, "Error: ref_text is required when x_vector_only_mode=False (ICL mode). Bad index=%d\n", b);
-                force_disarm(ctx);
-                return -1;
-            }
-    double t0 = now_ms();
+    const double t0 = now_ms();
     const int H = ctx->config.talker_hidden;
-    int maxT = 0;
-    for (int b = 0; b < nb; b++) {
-        const int T = (n_ref_samples[b] + 1919) / 1920;
-        if (T > maxT) maxT = T;
-    }
-    int *codes = (int *)malloc((size_t)nb * (maxT > 0 ? maxT : 1) * 16 * sizeof(int));
-    float *xv = (float *)malloc((size_t)nb * H * sizeof(float));
-    int frames[16];
-    int rc = -1;
-    if (codes && xv && qtts_dev_encode_audio(dev, nb, ref_wavs, n_ref_samples, codes, maxT, frames, NULL) == 0 &&
-        qtts_dev_speaker_embed(dev, nb, ref_wavs, n_ref_samples, xv, NULL) == 0) {
+    int *codes = NULL, maxT = 0, frames[16], rc = -1;
+    float *xv = NULL;
+    if (ref_audio_encode(ctx, nb, ref_texts, ref_wavs, n_ref_samples, x_vector_only, &codes, &maxT, frames, &xv) == 0) {
         const int *rc_p[16];
         int nr[16];
         const float *sv[16];
@@ -2153,7 +2115,7 @@ static int vclone_audio_run(qwen_tts_ctx_t *ctx, int nb, const char *const *text
             rc = qwen_tts_generate_voice_clone_batch(ctx, nb, texts, rt, rc_p, nr, sv, languages, non_streaming,
                                                      out_audio, out_samples);
     } else {
-        force_disarm(ctx);
+        force_disarm(ctx);   /* (the call consumes an arming also when it fails before the run) */
     }
     free(codes);
     free(xv);
@@ -2193,27 +2155,13 @@ float *qwen_tts_generate_voice_clone_audio_stream(qwen_tts_ctx_t *ctx, const cha
         if (ctx) force_disarm(ctx);
         return NULL;
     }
-    qtts_dev_t *dev = (qtts_dev_t *)ctx->hip;
-    if ((qtts_dev_enc_available(dev) & 3) != 3) {
-        fprintf(stderr, "Error: the model directory has no speaker encoder / 12 Hz encoder weights\n");
-        force_disarm(ctx);
-        return NULL;
-    }
-    if (!x_vector_only && (!ref_text || !ref_text[0])) {
-        fprintf(stderr, "Error: ref_text is required when x_vector_only_mode=False (ICL mode). Bad index=0\n");
-        force_disarm(ctx);
-        return NULL;
-    }
     const double t0 = now_ms();
-    const int T = (n_ref_samples + 1919) / 1920, H = ctx->config.talker_hidden;
-    int *codes = (int *)malloc((size_t)T * 16 * sizeof(int));
-    float *xv = (float *)malloc((size_t)H * sizeof(float));
+    const char *rt[1] = {ref_text};
     const float *w[1] = {ref_wav};
-    const int n[1] = {n_ref_samples};
-    int fr = 0;
-    float *audio = NULL;
-    if (codes && xv && qtts_dev_encode_audio(dev, 1, w, n, codes, T, &fr, NULL) == 0 &&
-        qtts_dev_speaker_embed(dev, 1, w, n, xv, NULL) == 0) {
+    const int n[1] = {n_ref_samples}, xo[1] = {x_vector_only};
+    int *codes = NULL, ld = 0, fr = 0;
+    float *xv = NULL, *audio = NULL;
+    if (ref_audio_encode(ctx, 1, rt, w, n, xo, &codes, &ld, &fr, &xv) == 0) {
         const double enc_ms = now_ms() - t0;
         audio = qwen_tts_generate_voice_clone_stream(ctx, text, x_vector_only ? NULL : ref_text,
                                                      x_vector_only ? NULL : codes, x_vector_only ? 0 : fr, xv,
@@ -2237,13 +2185,8 @@ float *qwen_tts_generate_voice_clone_audio(qwen_tts_ctx_t *ctx, const char *text
     const char *texts[1] = {text}, *rt[1] = {ref_text}, *lang[1] = {language};
     const float *w[1] = {ref_wav};
     const int nn[1] = {n_ref_samples}, xo[1] = {x_vector_only};
-    if (qwen_tts_generate_voice_clone_audio_batch(ctx, 1, texts, rt, w, nn, lang, xo, non_streaming, &audio, &n) != 0 ||
-        !audio || n <= 0) {
-        free(audio);
-        return NULL;
-    }
-    *out_samples = n;
-    return audio;
+    const int rc = qwen_tts_generate_voice_clone_audio_batch(ctx, 1, texts, rt, w, nn, lang, xo, non_streaming, &audio, &n);
+    return one_result(rc, audio, n, out_samples);
 }
 
 float *qwen_tts_generate_stream(qwen_tts_ctx_t *ctx, const char *text, const char *speaker, const char *language,
@@ -2256,17 +2199,9 @@ float *qwen_tts_generate_stream(qwen_tts_ctx_t *ctx, const char *text, const cha
     int n = 0;
     const char *texts[1] = {text}, *spk[1] = {speaker}, *lang[1] = {language};
     ctx->perf_first_packet_ms = 0;
-    int rc = run_batch(ctx, 1, texts, spk, lang, &audio, &n, t_start, &st, NULL);
-    if (rc != 0 || !audio || n <= 0) {
-        free(audio);
-        return NULL;
-    }
-    if (qwen_tts_verbose >= 1) {
-        fprintf(stderr, "First packet: %.1f ms\n", ctx->perf_first_packet_ms);
-        fprintf(stderr, "Total: %.1f ms (%.2f s audio, %.2fx realtime)\n", ctx->perf_total_ms,
-                (float)n / QWEN_TTS_SAMPLE_RATE, ((float)n / QWEN_TTS_SAMPLE_RATE) / (ctx->perf_total_ms / 1000.0));
-    }
-    *out_samples = n;
+    const int rc = run_batch(ctx, 1, texts, spk, lang, &audio, &n, t_start, &st, NULL);
+    audio = one_result(rc, audio, n, out_samples);
+    if (audio) log_totals(ctx, 1, 0, 1, &n);
     return audio;
 }
 
@@ -2279,13 +2214,7 @@ int qwen_tts_generate_batch_stream(qwen_tts_ctx_t *ctx, int nb, const char *cons
     stream_t st = {NULL, userdata, chunk_frames > 0 ? chunk_frames : 1, 1, cb};
     ctx->perf_first_packet_ms = 0;
     const int rc = run_batch(ctx, nb, texts, speakers, languages, out_audio, out_samples, t_start, &st, NULL);
-    if (rc == 0 && qwen_tts_verbose >= 1) {
-        double secs = 0;
-        for (int b = 0; b < nb; b++) secs += (double)out_samples[b] / QWEN_TTS_SAMPLE_RATE;
-        fprintf(stderr, "First packet: %.1f ms\n", ctx->perf_first_packet_ms);
-        fprintf(stderr, "Total: %.1f ms (%.2f s audio over %d utterances, %.2fx realtime)\n", ctx->perf_total_ms, secs,
-                nb, secs / (ctx->perf_total_ms / 1000.0));
-    }
+    if (rc == 0) log_totals(ctx, 1, 1, nb, out_samples);
     return rc;
 }
 
@@ -2329,13 +2258,7 @@ static int queue_stream_run(qwen_tts_ctx_t *ctx, const char *who, int nq, const 
     if (ctx) ctx->perf_first_packet_ms = 0;
     const int rc = queue_run(ctx, who, nq, texts, speakers, languages, nb, next, userdata, out_audio, out_samples, &st,
                              voices, non_streaming);
-    if (rc == 0 && qwen_tts_verbose >= 1) {
-        double secs = 0;
-        for (int u = 0; u < nq; u++) secs += (double)out_samples[u] / QWEN_TTS_SAMPLE_RATE;
-        fprintf(stderr, "First packet: %.1f ms\n", ctx->perf_first_packet_ms);
-        fprintf(stderr, "Total: %.1f ms (%.2f s audio over %d utterances, %.2fx realtime)\n", ctx->perf_total_ms, secs,
-                nq, secs / (ctx->perf_total_ms / 1000.0));
-    }
+    if (rc == 0) log_totals(ctx, 1, 1, nq, out_samples);
     return rc;
 }
 
