@@ -103,6 +103,10 @@ int qtts_dev_kv_dtype(const qtts_dev_t *dev);
  * to the host as fp32 [n][KV*HD] each (bf16 widened exactly; k_host or v_host
  * may be NULL).  Waits for the context stream.  -1 out of range. */
 int qtts_dev_get_kv(qtts_dev_t *dev, int layer, int b, int pos0, int n, float *k_host, float *v_host);
+/* Diagnostics: slot b's talker input row [hidden] -- after qtts_dev_prefill the
+ * last prompt row's raw hidden state, which frame 0's codec head reads.  Waits
+ * for the context stream. */
+int qtts_dev_get_hidden(qtts_dev_t *dev, int b, float *host);
 /* Diagnostics: what the last talker layer's decode attention of the most
  * recent talker pass read and wrote, for every allocated slot: its q|k|v rows
  * [slots][(NH + 2 KV) HD] and its output [slots][NH HD] (either may be NULL).
@@ -126,10 +130,35 @@ int qtts_dev_begin(qtts_dev_t *dev, int nb, int max_frames, int max_prefill, con
  *   text_ids[n_text]  text tokens to embed+project (text_embedding -> fc1 ->
  *                     SiLU -> fc2, c/qwen_tts.c:823-847)
  *   plan[5*nplan]     per output row {text row, codec id or -1,
- *                     0 = prefill / 1 = trailing, b, slot}
+ *                     0 = prefill / 1 = trailing / 2 = prefill row of the
+ *                     cacheable prefix (below), b, slot}
  *   p_len, n_trailing prefill / trailing lengths; pad_row = text row of tts_pad */
 int qtts_dev_prompt(qtts_dev_t *dev, int b, const int *text_ids, int n_text, const int *plan, int nplan,
                     int p_len, int n_trailing, int pad_row);
+/* The instruct prefix cache.  Plan rows of kind 2 are prefill rows (assembled
+ * like kind 0) that form the slot's cacheable prefix: they must be the plan's
+ * leading rows, prompt rows 0 .. n-1 of slot b in order, text alone (codec id
+ * -1), with n < p_len; any other kind-2 plan returns -1 with nothing
+ * launched.  Their K / V depend on nothing after them, so qtts_dev_prefill and
+ * qtts_dev_refill run a slot with a prefix in two passes, whatever the cache
+ * holds: the prefix rows alone (computed once per distinct prefix and saved,
+ * afterwards copied back: one launch), then the remaining rows at their own
+ * positions.  One cache per device model, keyed by the exact id sequence and
+ * the KV element type, LRU, QTTS_HIP_PREFIX_CACHE entries (read at creation,
+ * default 16, 0: off -- the prefix rows are then ordinary rows of the one
+ * pass).  An entry holds rows [0, n) of all layers, [2][L][n][KV*HD]; entries
+ * survive qtts_dev_begin and state re-allocation, a change of the KV element
+ * type drops them, qtts_dev_destroy drops all.
+ * qtts_dev_prefix_cache: sets the capacity (evicting down to it; 0 clears and
+ *   switches the cache off).  qtts_dev_prefix_cache_bytes: device bytes held.
+ * qtts_hip_prefix_hits / _misses: restores / computed prefixes, and
+ * qtts_hip_prefill_rows: rows sent through the talker prefill passes, since the
+ * library loaded (process-wide, like qtts_hip_gemv_wide_launches). */
+int qtts_dev_prefix_cache(qtts_dev_t *dev, int max_entries);
+size_t qtts_dev_prefix_cache_bytes(const qtts_dev_t *dev);
+long long qtts_hip_prefix_hits(void);
+long long qtts_hip_prefix_misses(void);
+long long qtts_hip_prefill_rows(void);
 /* Voice-clone inputs consumed by the next qtts_dev_prompt (no c/ counterpart;
  * modeling_qwen3_tts.py:1967-2019, 2150-2190): reference codes
  * [n_ref][num_code_groups] that plan codec ids <= -3 address (-3 - frame: the

@@ -190,6 +190,8 @@ typedef struct {
     long long queue_slot_frames_used; /* sum of frames generated */
     long long queue_rows_launched;    /* sum over launched frames of the slot rows they ran (the tail launches
                                          only the running slots): occupancy = frames_used / rows_launched */
+    void *instruct;              /* per-utterance instruct ids armed for the next generation call (one-shot;
+                                    qwen_tts_set_utterance_instruct).  It sits in front of `sampling` */
     void *sampling;              /* per-utterance sampling armed for the next generation call (one-shot;
                                     qwen_tts_set_utterance_sampling).  It sits in front of `force`, which
                                     stays the struct's last field */
@@ -421,6 +423,27 @@ typedef struct {
 } qwen_tts_sampling_t;
 int qwen_tts_sampling_defaults(const qwen_tts_ctx_t *ctx, qwen_tts_sampling_t *s);
 int qwen_tts_set_utterance_sampling(qwen_tts_ctx_t *ctx, int n, const qwen_tts_sampling_t *per);
+/* Instruct (style control) and voice design: the Python reference's
+ * generate_custom_voice(..., instruct=...) and generate_voice_design.  The ids
+ * of "<|im_start|>user\n{instruct}<|im_end|>\n" (qwen_tts_instruct_prompt) go
+ * through the text projection and stand in front of the ordinary prompt rows
+ * (modeling_qwen3_tts.py:2075-2080, 2236-2237); nothing else changes.  Voice
+ * design is the same call with `speaker` NULL or "" on a *-VoiceDesign
+ * checkpoint.
+ * qwen_tts_set_utterance_instruct: instruct_ids[i] is the comma-separated id
+ *   list for utterance i of the NEXT generation call (slot i of a batch,
+ *   utterance i in input order of the queue, entry 0 of the single and stream
+ *   calls); a NULL or empty entry: no instruct for that utterance.  One-shot
+ *   like per-utterance sampling, and free to combine with it and with forced
+ *   codes / taps.  Refused (-1, an earlier arming stays) for n < 1, a NULL
+ *   list, an entry that does not parse or an id outside [0, text vocab).
+ *   Served by qwen_tts_generate, _stream, _batch, _batch_stream, _queue and
+ *   _queue_stream; a call of another utterance count fails with -1 before the
+ *   device is touched, and every voice-clone entry and the voice queue refuse
+ *   an armed instruct (-1); both disarm.
+ * The library applies what it is given: it does not read tts_model_size (the
+ * Python wrapper drops the instruct on the 0.6B CustomVoice checkpoint). */
+int qwen_tts_set_utterance_instruct(qwen_tts_ctx_t *ctx, int n, const char *const *instruct_ids);
 /* Streaming generation (the reference has only a per-step
  * progress callback, c/qwen_tts.h:356): audio is decoded incrementally and
  * exactly (qtts_hip.h codec stream) and handed to `cb` as it is produced --
@@ -621,6 +644,9 @@ int qwen_tts_generate_voice_queue_stream(qwen_tts_ctx_t *ctx, int nq, const char
  * `text` argument of qwen_tts_generate* -- malloc'd, NULL on error. */
 int *qwen_tts_tokenize(const char *model_dir, const char *text, int *n_ids);
 char *qwen_tts_text_prompt(qwen_tts_ctx_t *ctx, const char *text);
+/* the same for an instruct: the ids of "<|im_start|>user\n{instruct}<|im_end|>\n",
+ * an entry of qwen_tts_set_utterance_instruct */
+char *qwen_tts_instruct_prompt(qwen_tts_ctx_t *ctx, const char *instruct);
 
 /* sizeof(qwen_tts_ctx_t) as compiled into the library (FFI layout check) */
 size_t qwen_tts_abi_sizeof_ctx(void);

@@ -376,6 +376,20 @@ int qtts_prompt_assemble(const PromptArgs &a, hipStream_t st);
 int qtts_copy_rows(float *dst, int ldd, const float *src, int lds, const int *src_rows, int nrows, int ncols,
                    hipStream_t st);
 
+// the instruct prefix cache (k_kvprefix.hip): talker K and V rows [0, n) of one
+// slot, all L layers, between the caches [L][B][S][KV*HD] and a packed entry
+// [2][L][n][KV*HD] of the same element type, in one launch; a plain copy
+struct KvPrefixArgs {
+    void *kc = nullptr, *vc = nullptr;   // the slot's row 0 of layer 0 in each cache
+    void *entry = nullptr;
+    size_t layer_stride = 0;             // bytes between two layers of a cache (B * S * row bytes)
+    size_t chunk = 0;                    // bytes of one layer's rows [0, n): n * row bytes
+    int L = 0;
+    int esz = 4;                         // element bytes: 4 fp32, 2 bf16
+    int save = 0;                        // 1: cache -> entry, 0: entry -> cache
+};
+int qtts_kv_prefix_copy(const KvPrefixArgs &a, hipStream_t st);
+
 // work-queue refill of one slot inside a live batch: the
 // slot's talker input row <- its last prompt row, kv_len <- pos, and a fresh
 // utterance's counters (Q.c:1250-1270: n_gen, rows, stop, repetition counts,

@@ -158,6 +158,24 @@ struct qtts_dev {
     float *pspk = nullptr;
     int pref_cap = 0, n_pref = 0, has_spk = 0;
     std::vector<int> p_len_h, n_tr_h;
+    // The instruct prefix cache (DESIGN.md "Instruct and the prefix cache"):
+    // pfx_ids[b] = the text ids of slot b's kind-2 plan rows (its prompt rows
+    // [0, n), qtts_dev_prompt); an entry = those rows' K and V of all layers,
+    // [2][L][n][KV*HD] in the element type it was saved from, keyed by the ids
+    // and that type.  Outside the decode state (sallocs): entries survive
+    // qtts_dev_begin and a re-allocation; a change of the KV element type drops
+    // them (alloc_state), qtts_dev_destroy drops all.
+    struct PrefixEntry {
+        std::vector<int> ids;
+        int dtype = 0;
+        void *buf = nullptr;
+        size_t bytes = 0;
+        unsigned long long used = 0;   // LRU stamp
+    };
+    std::vector<std::vector<int>> pfx_ids;
+    std::vector<PrefixEntry> pfx;
+    int pfx_cap = 16;                  // QTTS_HIP_PREFIX_CACHE entries (0: off), qtts_dev_prefix_cache
+    unsigned long long pfx_clock = 0;
     qtts_gen_params_t par{};
     bool have_par = false;
     hipGraphExec_t g0 = nullptr, gN = nullptr;
@@ -553,6 +571,9 @@ extern "C" qtts_dev_t *qtts_dev_create(const qtts_dims_t *dims, int device) {
         if (!strcmp(kvd, "bf16")) dv->kv_want = 1;
         else if (strcmp(kvd, "fp32")) fprintf(stderr, "qtts: QTTS_HIP_KV=%s ignored (bf16 or fp32)\n", kvd);
     }
+    // QTTS_HIP_PREFIX_CACHE=<entries>: the instruct prefix cache's capacity (default 16, 0 off)
+    const char *pc = getenv("QTTS_HIP_PREFIX_CACHE");
+    if (pc && *pc) dv->pfx_cap = atoi(pc) < 0 ? 0 : atoi(pc);
     const char *tb = getenv("QTTS_HIP_TAB0B");
     dv->tab0b = !(tb && !atoi(tb));
     const char *sp = getenv("QTTS_HIP_ST_PAIR");
@@ -590,10 +611,45 @@ static void snapshots_orphan(qtts_dev *dv) {
     dv->snaps.clear();
 }
 
+// drops the least recently used prefix entries until at most `keep` are left
+// (the stream is drained first: a queued save or restore may still use one)
+static void prefix_evict(qtts_dev *dv, size_t keep) {
+    if (dv->pfx.size() <= keep) return;
+    hipStreamSynchronize(dv->st);
+    while (dv->pfx.size() > keep) {
+        size_t lru = 0;
+        for (size_t i = 1; i < dv->pfx.size(); ++i)
+            if (dv->pfx[i].used < dv->pfx[lru].used) lru = i;
+        hipFree(dv->pfx[lru].buf);
+        dv->pfx.erase(dv->pfx.begin() + lru);
+    }
+}
+
+extern "C" int qtts_dev_prefix_cache(qtts_dev_t *dv, int max_entries) {
+    if (!dv || max_entries < 0) return -1;
+    hipSetDevice(dv->device);
+    dv->pfx_cap = max_entries;
+    prefix_evict(dv, (size_t)max_entries);
+    return 0;
+}
+
+extern "C" size_t qtts_dev_prefix_cache_bytes(const qtts_dev_t *dv) {
+    size_t n = 0;
+    if (dv)
+        for (const auto &e : dv->pfx) n += e.bytes;
+    return n;
+}
+
+static std::atomic<long long> g_prefix_hits{0}, g_prefix_misses{0}, g_prefill_rows{0};
+extern "C" long long qtts_hip_prefix_hits(void) { return g_prefix_hits.load(); }
+extern "C" long long qtts_hip_prefix_misses(void) { return g_prefix_misses.load(); }
+extern "C" long long qtts_hip_prefill_rows(void) { return g_prefill_rows.load(); }
+
 extern "C" void qtts_dev_destroy(qtts_dev_t *dv) {
     if (!dv) return;
     hipSetDevice(dv->device);
     hipStreamSynchronize(dv->st);
+    prefix_evict(dv, 0);
     free_state(dv);
     snapshots_orphan(dv);
     codec_destroy(&dv->codec);
@@ -649,6 +705,14 @@ extern "C" int qtts_dev_get_kv(qtts_dev_t *dv, int layer, int b, int pos0, int n
             CK(hipMemcpy(outs[i], src, cnt * 4, hipMemcpyDeviceToHost));
         }
     }
+    return 0;
+}
+
+extern "C" int qtts_dev_get_hidden(qtts_dev_t *dv, int b, float *host) {
+    if (!dv || !dv->x_tk || !host || b < 0 || b >= dv->nb) return -1;
+    hipSetDevice(dv->device);
+    CK(hipStreamSynchronize(dv->st));
+    CK(hipMemcpy(host, dv->x_tk + (size_t)b * dv->d.H, (size_t)dv->d.H * 4, hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -777,6 +841,7 @@ extern "C" int qtts_dev_encode_audio(qtts_dev_t *dv, int nb, const float *const 
 static int alloc_state(qtts_dev *dv, int nb, int max_frames, int max_prefill) {
     const qtts_dims_t &d = dv->d;
     free_state(dv);
+    if (dv->kv_dtype != dv->kv_want) prefix_evict(dv, 0);   // (entries hold the other element type)
     dv->kv_dtype = dv->kv_want;
     if (dv->kv_dtype == 1 && dv->tengine && !dv->te_kv_said && (dv->te_kv_said = true))
         fprintf(stderr, "qtts: the persistent talker engine (QTTS_HIP_TENGINE) has no bf16 KV form: not used\n");
@@ -889,6 +954,7 @@ static int alloc_state(qtts_dev *dv, int nb, int max_frames, int max_prefill) {
 #undef A
     dv->p_len_h.assign(nb, 0);
     dv->n_tr_h.assign(nb, 0);
+    dv->pfx_ids.assign(nb, std::vector<int>());
     CK(hipMemsetAsync(dv->codes, 0, B * (max_frames + 1) * d.G * sizeof(int), dv->st));
     CK(hipMemsetAsync(dv->kcs, 0, (size_t)d.Ls * B * d.G * d.KVs * d.HDs * 4, dv->st));
     CK(hipMemsetAsync(dv->vcs, 0, (size_t)d.Ls * B * d.G * d.KVs * d.HDs * 4, dv->st));
@@ -1824,6 +1890,24 @@ extern "C" int qtts_dev_prompt_ref(qtts_dev_t *dv, const int *ref_codes, int n_r
 extern "C" int qtts_dev_prompt(qtts_dev_t *dv, int b, const int *text_ids, int n_text, const int *plan, int nplan,
                                int p_len, int n_trailing, int pad_row) {
     if (!dv || b < 0 || b >= dv->nb || p_len > dv->p_cap || n_text < 1) return -1;
+    // kind-2 rows (the cacheable prefix): the plan's leading rows, prompt rows
+    // 0 .. n-1 of this slot in order, text alone (no codec id), and not the
+    // whole prompt; assembled as kind 0
+    std::vector<int> hplan, pids;
+    for (int e = 0; e < nplan; ++e) {
+        const int *r = plan + 5 * e;
+        if (r[2] != 2) continue;
+        if (hplan.empty()) hplan.assign(plan, plan + (size_t)5 * nplan);
+        if (e != (int)pids.size() || r[4] != e || r[1] != -1 || r[3] != b || r[0] < 0 || r[0] >= n_text ||
+            e + 1 >= p_len) {
+            fprintf(stderr, "qtts_dev_prompt: plan row %d: prefix rows (kind 2) must be the leading rows 0..n-1 of "
+                            "the slot's prompt, without a codec id, and fewer than p_len\n", e);
+            return -1;
+        }
+        pids.push_back(text_ids[r[0]]);
+        hplan[5 * e + 2] = 0;
+    }
+    if (!hplan.empty()) plan = hplan.data();
     hipSetDevice(dv->device);
     const qtts_dims_t &d = dv->d;
     CKI(ensure_trailing(dv, n_trailing));
@@ -1865,20 +1949,23 @@ extern "C" int qtts_dev_prompt(qtts_dev_t *dv, int b, const int *text_ids, int n
     CK(hipStreamSynchronize(dv->st));
     dv->p_len_h[b] = p_len;
     dv->n_tr_h[b] = n_trailing;
+    dv->pfx_ids[b] = pids;
     return 0;
 }
 
-// talker prefill (T.c:254-472) of prompt rows [0, nrows[i]) of slots[i];
+// talker prefill (T.c:254-472) of prompt rows [first[i], nrows[i]) of slots[i]
+// at their own positions (first NULL: from row 0); the rows before them are in
+// the cache already: mode-1 attention reads every key back from it.
 // last[i] = the row index (in px) of slot i's last row
 static int prefill_rows(qtts_dev *dv, const std::vector<int> &slots, const std::vector<int> &nrows,
-                        std::vector<int> &last) {
+                        std::vector<int> &last, const std::vector<int> *first = nullptr) {
     const qtts_dims_t &d = dv->d;
     hipStream_t st = dv->st;
     std::vector<int> rb, pp, src;
     last.assign(slots.size(), 0);
     for (size_t i = 0; i < slots.size(); ++i) {
         const int b = slots[i];
-        for (int t = 0; t < nrows[i]; ++t) {
+        for (int t = first ? (*first)[i] : 0; t < nrows[i]; ++t) {
             rb.push_back(b);
             pp.push_back(t);
             src.push_back(b * dv->p_cap + t);
@@ -1887,6 +1974,7 @@ static int prefill_rows(qtts_dev *dv, const std::vector<int> &slots, const std::
     }
     const int R = (int)rb.size();
     if (R < 1 || R > dv->rows_cap) return -1;
+    g_prefill_rows += R;
     CK(hipMemcpyAsync(dv->prow_b, rb.data(), R * 4, hipMemcpyHostToDevice, st));
     CK(hipMemcpyAsync(dv->ppos, pp.data(), R * 4, hipMemcpyHostToDevice, st));
     CK(hipMemcpyAsync(dv->psrc, src.data(), R * 4, hipMemcpyHostToDevice, st));
@@ -1922,15 +2010,76 @@ static int prefill_rows(qtts_dev *dv, const std::vector<int> &slots, const std::
     return 0;
 }
 
+// one launch between slot b's cache rows [0, n) and a prefix entry
+static int prefix_copy(qtts_dev *dv, const qtts_dev::PrefixEntry &e, int b, int save) {
+    const size_t row = (size_t)dv->d.KV * dv->d.HD * dv->kv_esz(), n = e.ids.size();
+    if (b < 0 || b >= dv->nb || (int)n > dv->S || e.dtype != dv->kv_dtype || e.bytes != 2 * dv->d.L * n * row) return -1;
+    KvPrefixArgs a;
+    a.kc = reinterpret_cast<char *>(dv->kc) + (size_t)b * dv->S * row;
+    a.vc = reinterpret_cast<char *>(dv->vc) + (size_t)b * dv->S * row;
+    a.entry = e.buf;
+    a.layer_stride = (size_t)dv->nb * dv->S * row;
+    a.chunk = n * row;
+    a.L = dv->d.L; a.esz = (int)dv->kv_esz(); a.save = save;
+    return qtts_kv_prefix_copy(a, dv->st);
+}
+
+// The prefix stages of a prefill of `slots` (qtts_dev_prefill / _refill).  A
+// slot with a prefix always takes the same two passes, hit or miss, so its
+// state never depends on what the cache holds:
+//   1. once per distinct missing prefix: a prefill pass over its n rows alone,
+//      into the first slot that needs it, and one save launch into a new entry;
+//   2. every other slot with that prefix, and every hit: one restore launch.
+// first[i] = the rows of slots[i] then in the cache (0: no prefix, or the cache
+// is off and the prefix rows are ordinary rows of the one pass).  Save and
+// restore are stream-ordered launches with no host wait; a miss waits once,
+// for its own pass's row lists.
+static int prefix_stages(qtts_dev *dv, const std::vector<int> &slots, std::vector<int> &first) {
+    first.assign(slots.size(), 0);
+    if (dv->pfx_cap < 1) return 0;
+    for (size_t i = 0; i < slots.size(); ++i) {
+        const int b = slots[i];
+        const std::vector<int> &ids = dv->pfx_ids[b];
+        if (ids.empty()) continue;
+        const int n = (int)ids.size();
+        qtts_dev::PrefixEntry *hit = nullptr;
+        for (auto &e : dv->pfx)
+            if (e.dtype == dv->kv_dtype && e.ids == ids) hit = &e;
+        if (hit) {
+            ++g_prefix_hits;
+            hit->used = ++dv->pfx_clock;
+            CKI(prefix_copy(dv, *hit, b, 0));
+        } else {
+            ++g_prefix_misses;
+            std::vector<int> last;
+            CKI(prefill_rows(dv, std::vector<int>{b}, std::vector<int>{n}, last));
+            CK(hipStreamSynchronize(dv->st));   // (the pass's row lists are host vectors; a miss only)
+            prefix_evict(dv, (size_t)dv->pfx_cap - 1);
+            qtts_dev::PrefixEntry e;
+            e.ids = ids; e.dtype = dv->kv_dtype; e.used = ++dv->pfx_clock;
+            e.bytes = (size_t)2 * dv->d.L * n * dv->d.KV * dv->d.HD * dv->kv_esz();
+            if (hipMalloc(&e.buf, e.bytes) != hipSuccess) {
+                fprintf(stderr, "qtts: no memory for a prefix cache entry of %zu bytes\n", e.bytes);
+                return -1;
+            }
+            dv->pfx.push_back(e);
+            CKI(prefix_copy(dv, dv->pfx.back(), b, 1));
+        }
+        first[i] = n;
+    }
+    return 0;
+}
+
 // talker prefill over all slots' prompt rows (T.c:254-472)
 extern "C" int qtts_dev_prefill(qtts_dev_t *dv) {
     if (!dv || dv->nb < 1) return -1;
     hipSetDevice(dv->device);
     const qtts_dims_t &d = dv->d;
     hipStream_t st = dv->st;
-    std::vector<int> slots(dv->nb), last;
+    std::vector<int> slots(dv->nb), last, first;
     for (int b = 0; b < dv->nb; ++b) slots[b] = b;
-    CKI(prefill_rows(dv, slots, dv->p_len_h, last));
+    CKI(prefix_stages(dv, slots, first));
+    CKI(prefill_rows(dv, slots, dv->p_len_h, last, &first));
     // last raw hidden of each slot -> x_tk; kv_len = prefill length
     CK(hipMemcpyAsync(dv->plast, last.data(), dv->nb * 4, hipMemcpyHostToDevice, st));
     CKI(qtts_copy_rows(dv->x_tk, d.H, dv->px, d.H, dv->plast, dv->nb, d.H, st));
@@ -1954,8 +2103,10 @@ extern "C" int qtts_dev_refill(qtts_dev_t *dv, int b) {
     if (force_refuses(dv, "qtts_dev_refill")) return -1;
     hipSetDevice(dv->device);
     const qtts_dims_t &d = dv->d;
-    std::vector<int> last;
-    CKI(prefill_rows(dv, std::vector<int>{b}, std::vector<int>{dv->p_len_h[b] - 1}, last));
+    std::vector<int> last, first;
+    CKI(prefix_stages(dv, std::vector<int>{b}, first));
+    if (first[0] < dv->p_len_h[b] - 1)   // (a prompt of its prefix and one more row: nothing left for the pass)
+        CKI(prefill_rows(dv, std::vector<int>{b}, std::vector<int>{dv->p_len_h[b] - 1}, last, &first));
     SlotResetArgs r;
     r.b = b; r.pos = dv->p_len_h[b] - 1; r.H = d.H; r.V = d.V;
     r.row = dv->prefill + ((size_t)b * dv->p_cap + r.pos) * d.H;
@@ -2031,6 +2182,7 @@ extern "C" int qtts_dev_move_slot(qtts_dev_t *dv, int from, int to) {
     CK(hipStreamSynchronize(st));
     dv->p_len_h[to] = dv->p_len_h[from];
     dv->n_tr_h[to] = dv->n_tr_h[from];
+    dv->pfx_ids[to] = dv->pfx_ids[from];
     if (dv->hstop && from < dv->hstop_cap && to < dv->hstop_cap)
         ((volatile int *)dv->hstop)[to] = ((volatile int *)dv->hstop)[from];
     return 0;
@@ -2773,7 +2925,10 @@ extern "C" int qtts_dev_talker_prefill_host(qtts_dev_t *dv, const float *embeds,
         CKI(qtts_dev_begin(dv, dv->nb, dv->max_frames, dv->p_cap, &p));
     }
     const qtts_dims_t &d = dv->d;
-    for (int b = 0; b < dv->nb; ++b) dv->p_len_h[b] = b == 0 ? n : 0;
+    for (int b = 0; b < dv->nb; ++b) {
+        dv->p_len_h[b] = b == 0 ? n : 0;
+        dv->pfx_ids[b].clear();
+    }
     CK(hipMemcpy(dv->prefill, embeds, (size_t)n * d.H * 4, hipMemcpyHostToDevice));
     CKI(qtts_dev_prefill(dv));
     if (hidden_out) {

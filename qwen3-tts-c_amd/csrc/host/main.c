@@ -41,7 +41,11 @@ static void usage(const char *prog) {
             "  -f <file>   token ids from a file (comma- or newline-separated)\n"
             "  -T <text>   text, tokenized with the model dir's vocab.json / merges.txt (Qwen2 BPE)\n"
             "              inside the chat template; --print-ids prints the ids and exits\n"
-            "  -s <name>   speaker (config.json spk_id)      -l <lang>  language or auto\n"
+            "  -s <name>   speaker (config.json spk_id; optional: none for a VoiceDesign checkpoint)\n"
+            "  -l <lang>   language or auto\n"
+            "  --instruct <text>   style / voice description, tokenized like -T inside its own chat template\n"
+            "                      (qwen_tts_set_utterance_instruct; with --batch N every copy gets it)\n"
+            "  --instruct-ids <ids>  the same as comma-separated ids of \"<|im_start|>user\\n{instruct}<|im_end|>\\n\"\n"
             "  -o <path>   output wav (default output.wav)   -v         verbose (repeatable)\n"
             "  --temperature F (0.9)   --top-k N (50)   --top-p F (1.0)   --repetition-penalty F (1.05)\n"
             "  --max-tokens N (4096)   --fixed-codec-tokens N   --seed N (42)\n"
@@ -188,6 +192,8 @@ int main(int argc, char **argv) {
     int print_ids = 0, xvec_only = 0;
     const char *force_file = NULL, *drawn_file = NULL;
     int seed_step = 0, seed_step_set = 0;
+    const char *instruct = NULL, *instruct_ids = NULL;
+    char *instruct_csv = NULL;
     float temp = -1, st_temp = -1, top_p = -1, st_top_p = -1, rep = -1;
     int top_k = -1, st_top_k = -1, max_tokens = -1, fixed = -1, seed = -1;
     for (int i = 1; i < argc; i++) {
@@ -218,6 +224,8 @@ int main(int argc, char **argv) {
         else if (ARG("--device")) device = (int)strtol(argv[++i], NULL, 10);
         else if (ARG("--batch")) batch = (int)strtol(argv[++i], NULL, 10);
         else if (ARG("--seed-step")) { seed_step = (int)strtol(argv[++i], NULL, 10); seed_step_set = 1; }
+        else if (ARG("--instruct")) instruct = argv[++i];
+        else if (ARG("--instruct-ids")) instruct_ids = argv[++i];
         else if (ARG("--stream")) stream_chunk = (int)strtol(argv[++i], NULL, 10);
         else if (ARG("--kv-cache")) {
             const char *v = argv[++i];
@@ -366,10 +374,23 @@ int main(int argc, char **argv) {
         }
         ids = file_ids;
     }
+    if (instruct && !instruct_ids) {   /* --instruct: the ids of its chat template */
+        if (!(instruct_csv = qwen_tts_instruct_prompt(ctx, instruct))) {
+            fprintf(stderr, "Error: cannot tokenize the instruct\n");
+            qwen_tts_free(ctx); free(ref_codes); free(xvec); free(file_ids);
+            return 1;
+        }
+        instruct_ids = instruct_csv;
+    }
+    if (instruct_ids && (clone || ref_wav)) {
+        fprintf(stderr, "Error: --instruct does not combine with voice clone\n");
+        qwen_tts_free(ctx); free(ref_codes); free(xvec); free(file_ids); free(instruct_csv);
+        return 1;
+    }
     if (xvec && n_xvec != ctx->config.talker_hidden) {
         fprintf(stderr, "Error: --xvector has %d floats, the talker hidden size is %d\n", n_xvec,
                 ctx->config.talker_hidden);
-        qwen_tts_free(ctx); free(ref_codes); free(xvec); free(file_ids);
+        qwen_tts_free(ctx); free(ref_codes); free(xvec); free(file_ids); free(instruct_csv);
         return 1;
     }
     if (temp >= 0) ctx->temperature = temp;
@@ -406,6 +427,16 @@ int main(int argc, char **argv) {
         if ((force_file || drawn_file) && qwen_tts_force_codes(ctx, 0, force_codes, n_force) != 0) {
             rc = 1;
             break;
+        }
+        if (instruct_ids) {   /* (one-shot as well: every copy of the prompt gets the instruct) */
+            const char **in = (const char **)malloc(batch * sizeof(char *));
+            for (int b = 0; in && b < batch; b++) in[b] = instruct_ids;
+            const int r = in ? qwen_tts_set_utterance_instruct(ctx, batch, in) : -1;
+            free(in);
+            if (r != 0) {
+                rc = 1;
+                break;
+            }
         }
         if (clone && batch > 1) {
             /* --batch N --stream K: N copies of the voice clone, every slot streamed (the chunks
@@ -577,6 +608,7 @@ int main(int argc, char **argv) {
     qwen_tts_free(ctx);
     free(force_codes);
     free(file_ids);
+    free(instruct_csv);
     free(ref_wav);
     free(ref_codes);
     free(xvec);

@@ -447,16 +447,16 @@ int *qwen_tts_tokenize(const char *model_dir, const char *text, int *n_ids) {
     return ids;
 }
 
-char *qwen_tts_text_prompt(qwen_tts_ctx_t *ctx, const char *text) {
+/* the ids CSV of pre ++ text ++ post through the ctx's tokenizer (malloc'd) */
+static char *chat_prompt(qwen_tts_ctx_t *ctx, const char *pre, const char *text, const char *post, const char *what) {
     if (!ctx || !text) return NULL;
     if (!ctx->tokenizer && !(ctx->tokenizer = qtok_load(ctx->model_dir))) return NULL;
-    static const char pre[] = "<|im_start|>assistant\n", post[] = "<|im_end|>\n<|im_start|>assistant\n";
-    const size_t lt = strlen(text);
-    char *chat = (char *)malloc(sizeof pre + lt + sizeof post);
+    const size_t lp = strlen(pre), lt = strlen(text), lq = strlen(post);
+    char *chat = (char *)malloc(lp + lt + lq + 1);
     if (!chat) return NULL;
-    memcpy(chat, pre, sizeof pre - 1);
-    memcpy(chat + sizeof pre - 1, text, lt);
-    memcpy(chat + sizeof pre - 1 + lt, post, sizeof post);
+    memcpy(chat, pre, lp);
+    memcpy(chat + lp, text, lt);
+    memcpy(chat + lp + lt, post, lq + 1);
     int *ids = NULL;
     const int n = qtok_encode((qtok_t *)ctx->tokenizer, chat, &ids);
     free(chat);
@@ -467,8 +467,17 @@ char *qwen_tts_text_prompt(qwen_tts_ctx_t *ctx, const char *text) {
     for (int i = 0; i < n; i++) k += (size_t)sprintf(csv + k, i ? ",%d" : "%d", ids[i]);
     csv[k] = 0;
     free(ids);
-    if (qwen_tts_verbose >= 1) fprintf(stderr, "Text: %d tokens (chat template)\n", n);
+    if (qwen_tts_verbose >= 1) fprintf(stderr, "%s: %d tokens (chat template)\n", what, n);
     return csv;
+}
+
+char *qwen_tts_text_prompt(qwen_tts_ctx_t *ctx, const char *text) {
+    return chat_prompt(ctx, "<|im_start|>assistant\n", text, "<|im_end|>\n<|im_start|>assistant\n", "Text");
+}
+
+/* the instruct's chat template (qwen3_tts_model.py:275-276) */
+char *qwen_tts_instruct_prompt(qwen_tts_ctx_t *ctx, const char *instruct) {
+    return chat_prompt(ctx, "<|im_start|>user\n", instruct, "<|im_end|>\n", "Instruct");
 }
 
 void qwen_tts_set_progress_callback(qwen_tts_ctx_t *ctx, qwen_tts_progress_cb cb, void *userdata) {
@@ -513,8 +522,10 @@ typedef struct {
  *   prefill = proj(ids[0:3]),
  *             (tts_pad x (np-2), tts_bos) + codec_emb(prefix[0:np-1]),
  *             proj(ids[3]) + codec_emb(bos)
- *   trailing = proj(ids[4:-5]) ++ tts_eos; tts_pad once exhausted */
-static int build_prompt(const qwen_tts_ctx_t *ctx, const int *ids, int n, int spk, int lang, int b, prompt_t *pr) {
+ *   trailing = proj(ids[4:-5]) ++ tts_eos; tts_pad once exhausted
+ * With an instruct (ins, ni > 0) its ni projected rows come first. */
+static int build_prompt(const qwen_tts_ctx_t *ctx, const int *ids, int n, int spk, int lang, const int *ins, int ni,
+                        int b, prompt_t *pr) {
     const qwen_tts_config_t *c = &ctx->config;
     int prefix[8], np = 0;
     if (lang < 0) {
@@ -528,23 +539,29 @@ static int build_prompt(const qwen_tts_ctx_t *ctx, const int *ids, int n, int sp
     prefix[np++] = c->codec_bos_id;
     int nt = (n - 4 - 5) + 1;
     if (nt < 1) nt = 1;
-    pr->n_text = 7 + (nt - 1);
+    const int n_own = 7 + (nt - 1);   /* the instruct ids go behind the utterance's own text rows */
+    pr->n_text = n_own + ni;
     pr->text = (int *)malloc(pr->n_text * sizeof(int));
-    pr->plan = (int *)malloc((size_t)(3 + np + nt) * 5 * sizeof(int));
+    pr->plan = (int *)malloc((size_t)(ni + 3 + np + nt) * 5 * sizeof(int));
+    if (!pr->text || !pr->plan) return -1;
     int *t = pr->text;
     t[0] = ids[0]; t[1] = ids[1]; t[2] = ids[2];
     t[3] = QWEN_TTS_TOKEN_TTS_PAD; t[4] = QWEN_TTS_TOKEN_TTS_BOS; t[5] = QWEN_TTS_TOKEN_TTS_EOS; t[6] = ids[3];
     for (int i = 0; i < nt - 1; i++) t[7 + i] = ids[4 + i];
+    for (int i = 0; i < ni; i++) t[n_own + i] = ins[i];
     int k = 0;
 #define ROW(src, cid, kind, slot) do { int *r_ = pr->plan + 5 * k++; r_[0] = src; r_[1] = cid; r_[2] = kind; r_[3] = b; r_[4] = slot; } while (0)
-    for (int i = 0; i < 3; i++) ROW(i, -1, 0, i);
-    for (int i = 0; i < np - 1; i++) ROW(i < np - 2 ? 3 : 4, prefix[i], 0, 3 + i);
-    ROW(6, c->codec_bos_id, 0, 3 + np - 1);
+    /* the instruct rows (M.py:2075-2080, 2236-2237): proj(instruct ids) alone, in
+     * front of everything; kind 2 = a prefill row of the cacheable prefix */
+    for (int i = 0; i < ni; i++) ROW(n_own + i, -1, 2, i);
+    for (int i = 0; i < 3; i++) ROW(i, -1, 0, ni + i);
+    for (int i = 0; i < np - 1; i++) ROW(i < np - 2 ? 3 : 4, prefix[i], 0, ni + 3 + i);
+    ROW(6, c->codec_bos_id, 0, ni + 3 + np - 1);
     for (int i = 0; i < nt - 1; i++) ROW(7 + i, -1, 1, i);
     ROW(5, -1, 1, nt - 1);
 #undef ROW
     pr->nplan = k;
-    pr->p_len = 3 + np;
+    pr->p_len = ni + 3 + np;
     pr->n_trailing = nt;
     pr->pad_row = 3;
     return 0;
@@ -662,9 +679,11 @@ static int ref_text_ids(const qwen_tts_ctx_t *ctx, const char *ref_text, int **i
 
 /* Prompt intake of every generate path: one utterance's text ids, checked,
  * its speaker / language looked up, laid out for slot b (vc: the voice-clone
- * layout, the speaker name unused).  -1 with the message on a refusal. */
+ * layout, the speaker name unused; ins / ni: the utterance's instruct ids,
+ * preset-speaker and voice-design layouts only).  -1 with the message on a
+ * refusal. */
 static int prompt_make(const qwen_tts_ctx_t *ctx, const char *text, const char *speaker, const char *language,
-                       const vclone_t *vc, int b, prompt_t *pr) {
+                       const vclone_t *vc, const int *ins, int ni, int b, prompt_t *pr) {
     int *ids = NULL, rc = -1;
     const int n = parse_ids(text, &ids);
     if (n < 8) {
@@ -672,7 +691,7 @@ static int prompt_make(const qwen_tts_ctx_t *ctx, const char *text, const char *
     } else if (ids_in_range(ctx, ids, n)) {
         int spk, lang;
         lookup(ctx, speaker, language, &spk, &lang);
-        rc = vc ? build_icl_prompt(ctx, ids, n, vc, lang, b, pr) : build_prompt(ctx, ids, n, spk, lang, b, pr);
+        rc = vc ? build_icl_prompt(ctx, ids, n, vc, lang, b, pr) : build_prompt(ctx, ids, n, spk, lang, ins, ni, b, pr);
     }
     free(ids);
     return rc;
@@ -823,6 +842,73 @@ static int sampling_apply(qtts_dev_t *dev, const sampling_arm_t *a, int u, int b
     return qtts_dev_slot_params(dev, b, &p);
 }
 
+/* ------------------------------------------------- instruct (one-shot) */
+/* What qwen_tts_set_utterance_instruct armed for the NEXT generation call
+ * (ctx->instruct): utterance i's instruct ids (n_ids[i] 0: none), checked at
+ * arming.  Detached on entry by run_batch / queue_run (instruct_take), dropped
+ * with the other two armings by every entry that fails before them
+ * (force_disarm). */
+typedef struct {
+    int n;
+    int **ids;    /* [n] malloc'd id lists, NULL where none */
+    int *n_ids;   /* [n] */
+} instruct_arm_t;
+
+static void instruct_free(instruct_arm_t *a) {
+    if (!a) return;
+    for (int i = 0; a->ids && i < a->n; i++) free(a->ids[i]);
+    free(a->ids);
+    free(a->n_ids);
+    free(a);
+}
+
+static instruct_arm_t *instruct_take(qwen_tts_ctx_t *ctx) {
+    instruct_arm_t *a = (instruct_arm_t *)ctx->instruct;
+    ctx->instruct = NULL;
+    return a;
+}
+
+int qwen_tts_set_utterance_instruct(qwen_tts_ctx_t *ctx, int n, const char *const *instruct_ids) {
+    if (!ctx || !ctx->hip) return -1;
+    if (n < 1 || !instruct_ids) {
+        fprintf(stderr, "Error: utterance instruct: %d id lists\n", n);
+        return -1;
+    }
+    instruct_arm_t *a = (instruct_arm_t *)calloc(1, sizeof(instruct_arm_t));
+    if (!a) return -1;
+    a->n = n;
+    a->ids = (int **)calloc(n, sizeof(int *));
+    a->n_ids = (int *)calloc(n, sizeof(int));
+    if (!a->ids || !a->n_ids) { instruct_free(a); return -1; }
+    for (int i = 0; i < n; i++) {
+        if (!instruct_ids[i]) continue;   /* (NULL or empty: no instruct for utterance i) */
+        const int k = parse_ids(instruct_ids[i], &a->ids[i]);
+        if (k < 0 || !ids_in_range(ctx, a->ids[i], k)) {
+            fprintf(stderr, "Error: utterance instruct %d refused\n", i);
+            instruct_free(a);
+            return -1;
+        }
+        a->n_ids[i] = k;
+    }
+    instruct_free((instruct_arm_t *)ctx->instruct);   /* armed again: the later call replaces */
+    ctx->instruct = a;
+    return 0;
+}
+
+/* the entry check of a generation call of `n` utterances: 0 to go on */
+static int instruct_refused(const char *who, const instruct_arm_t *ia, int n, int voice_clone) {
+    if (!ia) return 0;
+    if (voice_clone) {
+        fprintf(stderr, "Error: %s: an instruct is armed for a voice-clone call (not supported; disarmed)\n", who);
+        return 1;
+    }
+    if (ia->n != n) {
+        fprintf(stderr, "Error: %s: %d instructs armed for a call of %d utterances (disarmed)\n", who, ia->n, n);
+        return 1;
+    }
+    return 0;
+}
+
 /* the entry checks of a generation call of `n` utterances: 0 to go on */
 static int sampling_refused(const char *who, const sampling_arm_t *sa, const void *force, int n) {
     if (!sa) return 0;
@@ -839,12 +925,21 @@ static int sampling_refused(const char *who, const sampling_arm_t *sa, const voi
     return 0;
 }
 
-/* drops whatever is armed for the next call: forcing / taps and per-utterance
- * sampling (every entry that fails before its run consumes both) */
+/* drops whatever is armed for the next call: forcing / taps, per-utterance
+ * sampling and instruct (every entry that fails before its run consumes all) */
 static void force_disarm(qwen_tts_ctx_t *ctx) {
     force_free((force_arm_t *)ctx->force);
     ctx->force = NULL;
     sampling_free(sampling_take(ctx));
+    instruct_free(instruct_take(ctx));
+}
+
+/* a voice-clone entry with an instruct armed: refused at the door, everything disarmed */
+static int instruct_refuses_clone(qwen_tts_ctx_t *ctx, const char *who) {
+    if (!ctx || !ctx->instruct) return 0;
+    instruct_refused(who, (const instruct_arm_t *)ctx->instruct, 0, 1);
+    force_disarm(ctx);
+    return 1;
 }
 
 static force_arm_t *force_pending(qwen_tts_ctx_t *ctx) {
@@ -1138,6 +1233,7 @@ static int run_batch(qwen_tts_ctx_t *ctx, int nb, const char *const *texts, cons
     force_arm_t *arm = (force_arm_t *)ctx->force;   /* one-shot: this call consumes it, however it ends */
     ctx->force = NULL;
     sampling_arm_t *sarm = sampling_take(ctx);      /* and the per-utterance sampling */
+    instruct_arm_t *iarm = instruct_take(ctx);      /* and the instructs */
     /* what the run owns: freed at `out`, whichever way it is reached */
     prompt_t *pr = NULL;
     int *prime_codes = NULL;   /* the reference frames of a streamed voice-clone batch, kept until the run ends */
@@ -1145,12 +1241,12 @@ static int run_batch(qwen_tts_ctx_t *ctx, int nb, const char *const *texts, cons
     codec_job_t *jobs = NULL;
     sstate_t ss;               /* streaming: exact incremental codec decode of the frames produced so far */
     memset(&ss, 0, sizeof ss);
-    if (sampling_refused("generate", sarm, arm, nb)) goto out;
+    if (sampling_refused("generate", sarm, arm, nb) || instruct_refused("generate", iarm, nb, vcs != NULL)) goto out;
     if (!(pr = (prompt_t *)calloc(nb, sizeof(prompt_t)))) goto out;
     int max_p = 0;
     for (int b = 0; b < nb; b++) {
         if (prompt_make(ctx, texts[b], speakers ? speakers[b] : NULL, languages ? languages[b] : NULL,
-                        vcs ? &vcs[b] : NULL, b, &pr[b]) != 0)
+                        vcs ? &vcs[b] : NULL, iarm ? iarm->ids[b] : NULL, iarm ? iarm->n_ids[b] : 0, b, &pr[b]) != 0)
             goto out;
         if (pr[b].p_len > max_p) max_p = pr[b].p_len;
     }
@@ -1335,6 +1431,7 @@ static int run_batch(qwen_tts_ctx_t *ctx, int nb, const char *const *texts, cons
 out:
     force_free(arm);
     sampling_free(sarm);
+    instruct_free(iarm);
     free(prime_codes);
     free(stopped); free(ngen); free(sstep);
     free(jobs);
@@ -1537,8 +1634,10 @@ static int queue_run(qwen_tts_ctx_t *ctx, const char *who, int nq, const char *c
     }
     if (batch_refused(ctx, who, nb)) return -1;
     sampling_arm_t *sarm = sampling_take(ctx);   /* one-shot: this call consumes it, however it ends */
-    if (sampling_refused(who, sarm, NULL, nq)) {
+    instruct_arm_t *iarm = instruct_take(ctx);   /* (indexed by input order, like the sampling sets) */
+    if (sampling_refused(who, sarm, NULL, nq) || instruct_refused(who, iarm, nq, voices != NULL)) {
         sampling_free(sarm);
+        instruct_free(iarm);
         return -1;
     }
     for (int i = 0; voices && i < nq; i++) {
@@ -1546,6 +1645,7 @@ static int queue_run(qwen_tts_ctx_t *ctx, const char *who, int nq, const char *c
         fprintf(stderr, "Error: %s: utterance %d: %s\n", who, i,
                 voices[i] ? "the voice handle belongs to another context" : "no voice handle (NULL)");
         sampling_free(sarm);
+        instruct_free(iarm);
         return -1;
     }
     qtts_dev_t *dev = (qtts_dev_t *)ctx->hip;
@@ -1588,7 +1688,7 @@ static int queue_run(qwen_tts_ctx_t *ctx, const char *who, int nq, const char *c
     int max_p = 0, max_tr = 0;
     for (int i = 0; i < nq; i++) {
         if (prompt_make(ctx, texts[i], speakers ? speakers[i] : NULL, languages ? languages[i] : NULL,
-                        vcs ? &vcs[i] : NULL, 0, &pr[i]) != 0)
+                        vcs ? &vcs[i] : NULL, iarm ? iarm->ids[i] : NULL, iarm ? iarm->n_ids[i] : 0, 0, &pr[i]) != 0)
             goto out;
         if (pr[i].p_len > max_p) max_p = pr[i].p_len;
         if (pr[i].n_trailing > max_tr) max_tr = pr[i].n_trailing;
@@ -1782,6 +1882,7 @@ out:
     sstate_free(&qs);
     free(avail); free(complete); free(ngen);
     sampling_free(sarm);
+    instruct_free(iarm);
     free(vcs);
     free(prime_codes);
     return rc;
@@ -1933,6 +2034,7 @@ static int vclone_run(qwen_tts_ctx_t *ctx, int nb, const char *const *texts, con
                       const char *const *languages, int non_streaming, float **out_audio, int *out_samples,
                       const stream_t *stream, double t_start) {
     if (!ctx || nb < 1 || !texts || !out_audio || !out_samples || (stream && !stream->multi && nb != 1)) return -1;
+    if (instruct_refuses_clone(ctx, "voice clone")) return -1;
     if (batch_refused(ctx, stream && stream->multi ? "qwen_tts_generate_voice_clone_batch_stream"
                                                    : "qwen_tts_generate_voice_clone_batch", nb))
         return -1;
@@ -2088,6 +2190,7 @@ static int vclone_audio_run(qwen_tts_ctx_t *ctx, int nb, const char *const *text
         if (ctx) force_disarm(ctx);
         return -1;
     }
+    if (instruct_refuses_clone(ctx, "voice clone from audio")) return -1;
     for (int b = 0; b < nb; b++) { out_audio[b] = NULL; out_samples[b] = 0; }
     const double t0 = now_ms();
     const int H = ctx->config.talker_hidden;
@@ -2155,6 +2258,7 @@ float *qwen_tts_generate_voice_clone_audio_stream(qwen_tts_ctx_t *ctx, const cha
         if (ctx) force_disarm(ctx);
         return NULL;
     }
+    if (instruct_refuses_clone(ctx, "voice clone from audio")) return NULL;
     const double t0 = now_ms();
     const char *rt[1] = {ref_text};
     const float *w[1] = {ref_wav};

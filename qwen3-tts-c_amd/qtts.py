@@ -64,7 +64,7 @@ class Ctx(C.Structure):  # qwen_tts_ctx_t (include/qwen_tts.h)
         ("queue_n", C.c_int), ("queue_codes", C.POINTER(_ip)), ("queue_frames", _ip), ("queue_stop_reason", _ip),
         ("queue_slot", _ip), ("queue_slots", C.c_int), ("queue_frames_launched", C.c_int),
         ("queue_refills", C.c_int), ("queue_slot_frames_used", C.c_longlong), ("queue_rows_launched", C.c_longlong),
-        ("sampling", C.c_void_p), ("force", C.c_void_p),
+        ("instruct", C.c_void_p), ("sampling", C.c_void_p), ("force", C.c_void_p),
     ]
 
 
@@ -126,6 +126,9 @@ EXPORTS = [
     "qwen_tts_codec_mstream_save", "qwen_tts_codec_mstream_restore", "qwen_tts_codec_snapshot_free",
     "qwen_tts_codec_snapshot_pos", "qwen_tts_voice_create", "qwen_tts_voice_create_audio", "qwen_tts_voice_info",
     "qwen_tts_voice_free", "qwen_tts_generate_voice_queue", "qwen_tts_generate_voice_queue_stream",
+    "qwen_tts_set_utterance_instruct", "qwen_tts_instruct_prompt", "qtts_dev_prefix_cache",
+    "qtts_dev_prefix_cache_bytes", "qtts_hip_prefix_hits", "qtts_hip_prefix_misses", "qtts_hip_prefill_rows",
+    "qtts_dev_get_hidden",
 ]
 
 MAX_BATCH = 64   # QWEN_TTS_MAX_BATCH / QTTS_HIP_MAX_BATCH: lock-step slots per context
@@ -474,6 +477,20 @@ def lib():
         L.qtts_hip_sample_slot_launches.argtypes = []
         L.qtts_hip_sample_top_k_rows.restype = C.c_int
         L.qtts_hip_sample_top_k_rows.argtypes = [vp, vp, C.c_int, _ip, _fp, _fp, vp, C.c_int, vp]
+    if hasattr(L, "qwen_tts_set_utterance_instruct"):
+        L.qwen_tts_set_utterance_instruct.restype = C.c_int
+        L.qwen_tts_set_utterance_instruct.argtypes = [C.POINTER(Ctx), C.c_int, C.POINTER(C.c_char_p)]
+        L.qwen_tts_instruct_prompt.restype = C.c_void_p
+        L.qwen_tts_instruct_prompt.argtypes = [C.POINTER(Ctx), C.c_char_p]
+        L.qtts_dev_prefix_cache.restype = C.c_int
+        L.qtts_dev_prefix_cache.argtypes = [C.c_void_p, C.c_int]
+        L.qtts_dev_prefix_cache_bytes.restype = C.c_size_t
+        L.qtts_dev_prefix_cache_bytes.argtypes = [C.c_void_p]
+        L.qtts_dev_get_hidden.restype = C.c_int
+        L.qtts_dev_get_hidden.argtypes = [C.c_void_p, C.c_int, _fp]
+        for f in (L.qtts_hip_prefix_hits, L.qtts_hip_prefix_misses, L.qtts_hip_prefill_rows):
+            f.restype = C.c_longlong
+            f.argtypes = []
     if hasattr(L, "qtts_hip_batch_matvec_plan"):
         L.qtts_hip_batch_matvec_plan.restype = C.c_int
         L.qtts_hip_batch_matvec_plan.argtypes = [C.POINTER(BGemvDesc), C.POINTER(BGemvPlan)]
@@ -564,6 +581,42 @@ class QwenTTS:
                 setattr(arr[i], self._SAMPLING_KEYS[k], v)
         if lib().qwen_tts_set_utterance_sampling(self.ctx, len(per), arr) != 0:
             raise ValueError("set_utterance_sampling refused (see stderr)")
+
+    # instruct / voice design (include/qwen_tts.h); one-shot like the sampling sets
+    def instruct_prompt(self, instruct):
+        """ids of "<|im_start|>user\\n{instruct}<|im_end|>\\n" through the model
+        dir's tokenizer (qwen_tts_instruct_prompt); None on error."""
+        p = lib().qwen_tts_instruct_prompt(self.ctx, instruct.encode("utf-8"))
+        if not p:
+            return None
+        csv = C.string_at(p).decode()
+        _libc.free(C.c_void_p(p))
+        return [int(t) for t in csv.split(",")] if csv else []
+
+    def set_utterance_instruct(self, per):
+        """per[i]: the instruct ids (a list, or None / [] for none) of utterance
+        i of the next generate / generate_stream / generate_batch[_stream] /
+        generate_queue[_stream] call; they stand in front of its prompt rows.
+        Voice design: the same with speaker None.  ValueError when refused."""
+        arr = (C.c_char_p * max(len(per), 1))()
+        for i, ids in enumerate(per):
+            arr[i] = ",".join(str(int(t)) for t in ids).encode() if ids is not None and len(ids) else None
+        if lib().qwen_tts_set_utterance_instruct(self.ctx, len(per), arr) != 0:
+            raise ValueError("set_utterance_instruct refused (see stderr)")
+
+    # the device's instruct prefix cache (include/qtts_hip.h)
+    def prefix_cache(self, max_entries):
+        """capacity in entries; evicts down to it, 0 clears and switches it off"""
+        _ok(lib().qtts_dev_prefix_cache(C.c_void_p(self.c.hip), int(max_entries)), "qtts_dev_prefix_cache")
+
+    def prefix_cache_bytes(self):
+        return int(lib().qtts_dev_prefix_cache_bytes(C.c_void_p(self.c.hip)))
+
+    @staticmethod
+    def prefix_counters():
+        """(hits, misses, prefill rows) since the library loaded"""
+        L = lib()
+        return int(L.qtts_hip_prefix_hits()), int(L.qtts_hip_prefix_misses()), int(L.qtts_hip_prefill_rows())
 
     # teacher forcing, the free-draw record and logit taps (include/qwen_tts.h).
     # Arming is one-shot: the next generate* call consumes it.
