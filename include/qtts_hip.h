@@ -277,6 +277,52 @@ typedef struct {
     int seed;
 } qtts_slot_params_t;
 int qtts_dev_slot_params(qtts_dev_t *dev, int b, const qtts_slot_params_t *p);
+/* ---- incremental text input (no c/ counterpart: the reference takes the whole
+ * utterance's ids before the prefill; DESIGN.md "Incremental text input") ----
+ * With content ids c[0..m) trailing row r is proj(c[r + 1]) for r < m - 1 and
+ * row m - 1 is tts_eos; the frame that draws frame r adds row r to the next
+ * talker input.  A fed run's frames therefore start with a gate,
+ *   gate[b] = stopped[b] | (text_open[b] && n_gen[b] >= n_trailing[b]),
+ * and every reader of the stop flag takes it: a slot whose next frame lacks its
+ * row is HELD for that frame exactly as a stopped slot is (no draw, no RNG
+ * advance, no code row, no counter, no KV position, no new input row; its
+ * talker input row is put back at the frame's end), and is looked at again by
+ * the next launch.  No kernel waits on a flag.  The whole frame is held:
+ * deferring only the embedding sum (drawing a frame before its row is there)
+ * is out of scope.  Frame 0 (step 0: the lock-step head on the prefill's
+ * hidden states, no talker step) must not be launched while a slot would be
+ * held: the caller launches it once every slot has row 0 or is closed.
+ * qtts_dev_text_open: after slot b's qtts_dev_prompt -- whose layout is that of
+ *   a template with ONE content id, so its only trailing row is tts_eos -- and
+ *   before frame 0: the row becomes the slot's eos row, the count goes back to
+ *   0, the text is open and the run a fed one, with frame graphs of its own
+ *   (an unfed run captures exactly the graphs it always did; the next
+ *   qtts_dev_begin ends the fed run).  -1 with a message: outside that window,
+ *   forcing / taps armed, QTTS_HIP_TENGINE set, a prompt with other trailing
+ *   rows.  In a fed run qtts_dev_refill, _move_slot and _set_rows return -1.
+ * qtts_dev_text_append: n >= 0 content ids behind the slot's rows, through
+ *   text_embedding -> fc1 + bias + SiLU -> fc2 + bias by ONE kernel path whose
+ *   per-row summation order does not depend on how many ids share a launch
+ *   (k_textfeed.hip: up to 16 ids per launch, passed as kernel arguments);
+ *   close: the tts_eos row behind them, text_open[b] = 0.  The row offset is
+ *   read on the device and the last store publishes the new count.
+ *   Stream-ordered on the context stream, no host wait and no copy -- except
+ *   growth past the allocated rows, which waits and makes the next frame
+ *   capture its graphs again.  -1 with a message: a slot whose text is not
+ *   open (never opened, or closed), an id outside [0, text vocab), n == 0
+ *   without close.
+ * qtts_dev_get_trailing: rows [row0, row0 + n) of slot b, [n][hidden] floats;
+ * qtts_dev_text_state: the device's row count, open flag and held-frame
+ *   counter of slot b (any may be NULL).  Both wait for the context stream.
+ * qtts_hip_text_held_frames: frames a live slot was held, as the
+ *   qtts_dev_poll calls of fed runs saw them, since the library loaded. */
+int qtts_dev_text_open(qtts_dev_t *dev, int b);
+int qtts_dev_text_append(qtts_dev_t *dev, int b, const int *ids, int n, int close);
+int qtts_dev_get_trailing(qtts_dev_t *dev, int b, int row0, int n, float *host);
+/* measurement: qtts_dev_text_append between two events on the context stream; waits, *ms = the device time */
+int qtts_dev_text_append_ms(qtts_dev_t *dev, int b, const int *ids, int n, int close, float *ms);
+int qtts_dev_text_state(qtts_dev_t *dev, int b, int *rows, int *open, int *held);
+long long qtts_hip_text_held_frames(void);
 /* Codec decode of slot b's generated codes (device-resident) into a malloc'd
  * host buffer of T*1920 samples (caller frees). */
 float *qtts_dev_codec_slot(qtts_dev_t *dev, int b, int T, int *out_samples);

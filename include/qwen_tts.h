@@ -482,6 +482,66 @@ typedef void (*qwen_tts_batch_audio_cb)(int utterance, const float *pcm, int n_s
 int qwen_tts_generate_batch_stream(qwen_tts_ctx_t *ctx, int nb, const char *const *texts,
                                    const char *const *speakers, const char *const *languages, int chunk_frames,
                                    qwen_tts_batch_audio_cb cb, void *userdata, float **out_audio, int *out_samples);
+/* Incremental text input: a streaming decode that takes its content ids while
+ * it runs (an LLM producing the text).  The model is a dual-track streamer:
+ * the prefill holds the role ids, the codec prefix and the FIRST content id;
+ * every later content id is one "trailing" row, added to the talker input of
+ * one frame (DESIGN.md "Incremental text input": the frame that draws frame r
+ * adds the row of content id r + 1, or tts_eos behind the last id).  Fed ids
+ * are the content ids alone; the library supplies the chat template's role ids
+ * and the tts_eos row.
+ *
+ * The feed callback is called with wait = 0 before every frame launch (push
+ * what is at hand, possibly nothing; it adds no device wait) and with
+ * wait = 1 when no live utterance can advance (block until you have pushed or
+ * closed something).  Return 0 to go on, < 0 to abort the call.
+ * qwen_tts_feed_ids / _close are valid only inside the callback and return -1
+ * with a message for a bad utterance index, an id outside [0, text vocab) and
+ * a push after the utterance was closed; after the utterance has stopped (EOS
+ * or the frame limit) they return 0 and do nothing.  qwen_tts_feed_state: the
+ * ids taken, the frames launched for the utterance, and whether its next frame
+ * lacks its row (any output may be NULL).
+ *
+ * Start: before the prefill the callback is called with wait = 1 until every
+ * utterance has an id; one closed with none fails the call before the device
+ * is touched.  Frame 0 is the lock-step head on the prefill's hidden states,
+ * so it is launched once every utterance has its second id or is closed (the
+ * first packet needs two ids, or one id and a close); until then the callback
+ * is called with wait = 1.
+ * Holds: a frame runs whole or not at all for a slot.  A slot whose next frame
+ * lacks its row, the text still open, is held for that frame exactly as a
+ * stopped slot is -- no draw, no RNG advance, no code row, no KV position --
+ * and tried again at the next launch.  (Deferring only the embedding sum, so
+ * that a frame's draw runs before its row arrives, is out of scope.)
+ * When every live utterance is starved, everything decoded and not yet
+ * delivered goes out as audio chunks first, then the callback is called with
+ * wait = 1; one that returns 0 without a push or close for a starved live
+ * utterance fails the call ("feed made no progress").  Otherwise the delivery
+ * is qwen_tts_generate_batch_stream's: frame 0, then every chunk_frames, then
+ * the tail; starvation flushes add short chunks, every chunk a multiple of
+ * 1920 samples; out_audio[i] is the concatenation of utterance i's chunks.
+ * Fixed and EOS mode both work; an utterance ends at its EOS or frame limit.
+ * For the same ids every feed schedule gives the same codes bit for bit, in
+ * any slot, whatever the other slots are fed.  Against the unfed call on the
+ * whole template there is no bit guarantee (the unfed text projection changes
+ * kernel with the row count); the layout is the same.
+ * Per-utterance sampling and instructs are consumed as
+ * qwen_tts_generate_batch_stream consumes them; armed forced codes / taps are
+ * refused (-1, disarmed).  Voice clone and the two queues have no fed form.
+ * -1 (NULL) and no audio on any failure, a callback's abort included; the next
+ * call on the context is not affected. */
+typedef struct qwen_tts_feed qwen_tts_feed_t;
+typedef int (*qwen_tts_text_feed_cb)(qwen_tts_feed_t *feed, int wait, void *userdata);
+int qwen_tts_feed_ids(qwen_tts_feed_t *feed, int utterance, const int *ids, int n);
+int qwen_tts_feed_close(qwen_tts_feed_t *feed, int utterance);
+int qwen_tts_feed_state(const qwen_tts_feed_t *feed, int utterance, int *ids_taken, int *frames_done, int *starved);
+float *qwen_tts_generate_fed_stream(qwen_tts_ctx_t *ctx, const char *speaker, const char *language, int chunk_frames,
+                                    qwen_tts_text_feed_cb feed_cb, void *feed_userdata, qwen_tts_audio_cb audio_cb,
+                                    void *audio_userdata, int *out_samples);
+int qwen_tts_generate_fed_batch_stream(qwen_tts_ctx_t *ctx, int nb, const char *const *speakers,
+                                       const char *const *languages, int chunk_frames, qwen_tts_text_feed_cb feed_cb,
+                                       void *feed_userdata, qwen_tts_batch_audio_cb audio_cb, void *audio_userdata,
+                                       float **out_audio, int *out_samples);
 /* qwen_tts_generate_voice_clone_batch with every utterance streamed.  Prompts,
  * decode loop, the nb limit, refusals and the one-shot armings are that
  * call's and the codes are its codes bit for bit; the delivery per utterance

@@ -24,9 +24,17 @@ __global__ __launch_bounds__(1024) void k_sample_w(const float *logits, const in
     qtts_samp::sample_row<true, EM, 1024>(a, blockIdx.x, smraw, logits, stopped, rng, n_gen, counts);
 }
 
+// a fed run's 256-thread forms: the row reads the gate, the EOS goes to a.stopped
+template <bool FAST, int EM>
+__global__ __launch_bounds__(256) void k_sample_g(const int *stop_rd, SampArgs a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smraw[];
+    qtts_samp::sample_row<FAST, EM>(a, blockIdx.x, smraw, a.logits, stop_rd, a.mode == 1 ? a.rng : a.st_rng, a.n_gen,
+                                    a.counts);
+}
+
 }  // namespace
 
-int qtts_sample(const SampArgs &a, hipStream_t st) {
+int qtts_sample(const SampArgs &a, hipStream_t st, const int *stop_rd) {
     if (a.n > qtts_samp::NMAX || a.n < 1) {
         fprintf(stderr, "qtts_sample: vocab %d unsupported (max %d)\n", a.n, qtts_samp::NMAX);
         return -1;
@@ -37,14 +45,27 @@ int qtts_sample(const SampArgs &a, hipStream_t st) {
     if (qtts_samp::fast_path(a) && !(sw && !atoi(sw))) {
         const size_t sm = sizeof(qtts_samp::FastSmemNT<1024>);
         const uint32_t *rng = a.mode == 1 ? a.rng : a.st_rng;
+        const int *rd = stop_rd ? stop_rd : (const int *)a.stopped;
         if (a.n <= 2 * 1024) {
-            hipLaunchKernelGGL((k_sample_w<2>), dim3(a.nb), dim3(1024), sm, st, a.logits, (const int *)a.stopped, rng,
+            hipLaunchKernelGGL((k_sample_w<2>), dim3(a.nb), dim3(1024), sm, st, a.logits, rd, rng,
                                (const int *)a.n_gen, (const int *)a.counts, a);
             qtts_last_kernel = "k_sample_w<2>";
         } else {
-            hipLaunchKernelGGL((k_sample_w<4>), dim3(a.nb), dim3(1024), sm, st, a.logits, (const int *)a.stopped, rng,
+            hipLaunchKernelGGL((k_sample_w<4>), dim3(a.nb), dim3(1024), sm, st, a.logits, rd, rng,
                                (const int *)a.n_gen, (const int *)a.counts, a);
             qtts_last_kernel = "k_sample_w<4>";
+        }
+    } else if (stop_rd) {
+        if (!qtts_samp::fast_path(a)) {
+            hipLaunchKernelGGL((k_sample_g<false, qtts_samp::EMAX>), dim3(a.nb), dim3(256), sizeof(qtts_samp::KSmem), st,
+                               stop_rd, a);
+            qtts_last_kernel = "k_sample_g<false, 16>";
+        } else if (a.n <= 8 * 256) {
+            hipLaunchKernelGGL((k_sample_g<true, 8>), dim3(a.nb), dim3(256), sizeof(qtts_samp::FastSmem), st, stop_rd, a);
+            qtts_last_kernel = "k_sample_g<true, 8>";
+        } else {
+            hipLaunchKernelGGL((k_sample_g<true, 16>), dim3(a.nb), dim3(256), sizeof(qtts_samp::FastSmem), st, stop_rd, a);
+            qtts_last_kernel = "k_sample_g<true, 16>";
         }
     } else if (qtts_samp::fast_path(a)) {
         const size_t sm = sizeof(qtts_samp::FastSmem);

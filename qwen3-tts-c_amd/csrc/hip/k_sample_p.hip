@@ -34,6 +34,14 @@ __global__ __launch_bounds__(1024) void k_sample_pw(const SampSlotRow *tab, cons
     qtts_samp::sample_row_p<true, EM, 1024>(a, tab, blockIdx.x, smraw, logits, stopped, rng, n_gen, counts);
 }
 
+// a fed run's general form: the row reads the gate, the EOS goes to a.stopped
+template <int EM>
+__global__ __launch_bounds__(256) void k_sample_pg(const int *stop_rd, SampArgs a, const SampSlotRow *tab) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smraw[];
+    qtts_samp::sample_row_p<false, EM, 256>(a, tab, blockIdx.x, smraw, a.logits, stop_rd,
+                                            a.mode == 1 ? a.rng : a.st_rng, a.n_gen, a.counts);
+}
+
 std::atomic<long long> g_slot_launches{0};
 
 }  // namespace
@@ -61,7 +69,7 @@ bool qtts_sample_row_fast(const SampSlotRow &r, int mode, int n) {
     return mode == 1 ? qtts_samp::fast_path_row(r.top_p, r.top_k, n) : qtts_samp::fast_path_row(r.st_top_p, r.st_top_k, n);
 }
 
-int qtts_sample_slots(const SampArgs &a, const SampSlotRow *tab, bool all_fast, hipStream_t st) {
+int qtts_sample_slots(const SampArgs &a, const SampSlotRow *tab, bool all_fast, hipStream_t st, const int *stop_rd) {
     if (a.n > qtts_samp::NMAX || a.n < 1) {
         fprintf(stderr, "qtts_sample: vocab %d unsupported (max %d)\n", a.n, qtts_samp::NMAX);
         return -1;
@@ -75,14 +83,24 @@ int qtts_sample_slots(const SampArgs &a, const SampSlotRow *tab, bool all_fast, 
     if (all_fast && !(sw && !atoi(sw))) {
         const size_t sm = sizeof(qtts_samp::FastSmemNT<1024>);
         const uint32_t *rng = a.mode == 1 ? a.rng : a.st_rng;
+        const int *rd = stop_rd ? stop_rd : (const int *)a.stopped;
         if (a.n <= 2 * 1024) {
-            hipLaunchKernelGGL((k_sample_pw<2>), dim3(a.nb), dim3(1024), sm, st, tab, a.logits, (const int *)a.stopped,
+            hipLaunchKernelGGL((k_sample_pw<2>), dim3(a.nb), dim3(1024), sm, st, tab, a.logits, rd,
                                rng, (const int *)a.n_gen, (const int *)a.counts, a);
             qtts_last_kernel = "k_sample_pw<2>";
         } else {
-            hipLaunchKernelGGL((k_sample_pw<4>), dim3(a.nb), dim3(1024), sm, st, tab, a.logits, (const int *)a.stopped,
+            hipLaunchKernelGGL((k_sample_pw<4>), dim3(a.nb), dim3(1024), sm, st, tab, a.logits, rd,
                                rng, (const int *)a.n_gen, (const int *)a.counts, a);
             qtts_last_kernel = "k_sample_pw<4>";
+        }
+    } else if (stop_rd) {
+        const size_t sm = sizeof(qtts_samp::KSmem);
+        if (a.n <= 8 * 256) {
+            hipLaunchKernelGGL((k_sample_pg<8>), dim3(a.nb), dim3(256), sm, st, stop_rd, a, tab);
+            qtts_last_kernel = "k_sample_pg<8>";
+        } else {
+            hipLaunchKernelGGL((k_sample_pg<qtts_samp::EMAX>), dim3(a.nb), dim3(256), sm, st, stop_rd, a, tab);
+            qtts_last_kernel = "k_sample_pg<16>";
         }
     } else {
         const size_t sm = sizeof(qtts_samp::KSmem);

@@ -289,7 +289,10 @@ struct SampArgs {
     int codes_bstride = 0, G = 16, g = 0;
     int *out_tok = nullptr;        // optional plain output [b]
 };
-int qtts_sample(const SampArgs &a, hipStream_t st);
+// stop_rd (a fed run, k_textfeed.hip): the flag row b reads in place of
+// a.stopped -- the gate; an EOS still goes to a.stopped and a.host_stopped.
+// NULL: the launches of before, argument for argument.
+int qtts_sample(const SampArgs &a, hipStream_t st, const int *stop_rd = nullptr);
 
 // Teacher forcing and logit taps: the extra pointers of the sampler's forced
 // form (qtts_sample_dev.h sample_row_forced).  `forced` and `drawn` have the
@@ -330,7 +333,8 @@ bool qtts_sample_row_fast(const SampSlotRow &r, int mode, int n);
 // every row of the run is fast-path eligible in both modes (all_fast; never
 // otherwise) and QTTS_HIP_SAMPLE_W is not 0, else the general 256-thread
 // kernel k_sample_p, which picks fast or full per row.
-int qtts_sample_slots(const SampArgs &a, const SampSlotRow *tab, bool all_fast, hipStream_t st);
+int qtts_sample_slots(const SampArgs &a, const SampSlotRow *tab, bool all_fast, hipStream_t st,
+                      const int *stop_rd = nullptr);
 // its launches enqueued (or captured) since the library loaded (qtts_hip_sample_slot_launches)
 long long qtts_sample_slot_launches();
 // writes row b of the table, stream-ordered; rng / st_rng non-null: the slot's
@@ -374,6 +378,39 @@ struct PromptArgs {
 int qtts_prompt_assemble(const PromptArgs &a, hipStream_t st);
 
 int qtts_copy_rows(float *dst, int ldd, const float *src, int lds, const int *src_rows, int nrows, int ncols,
+                   hipStream_t st);
+
+// incremental text input (k_textfeed.hip).  The append: n <= QTTS_TF_MAX
+// content ids of slot b (kernel arguments) projected into trailing rows
+// n_trailing[b] .. + n - 1, close: the slot's tts_eos row behind them and
+// text_open[b] = 0; the last launch stores the new count.
+constexpr int QTTS_TF_MAX = 16;
+struct TextFeedArgs {
+    int ids[QTTS_TF_MAX] = {};
+    int n = 0, b = 0, close = 0;
+    const bf16_t *text_emb = nullptr, *fc1w = nullptr, *fc2w = nullptr;   // [TV][TH], [TH][TH], [H][TH]
+    const float *fc1b = nullptr, *fc2b = nullptr;
+    int TH = 0, H = 0;
+    float *t1 = nullptr;                 // [QTTS_TF_MAX][TH] fc1's output
+    float *trailing = nullptr;           // [B][tr_cap][H]
+    int tr_cap = 0;
+    int *n_trailing = nullptr, *text_open = nullptr;
+    const float *eos = nullptr;          // [H] slot b's tts_eos row
+};
+int qtts_text_append(const TextFeedArgs &a, hipStream_t st);
+// the first and the last node of a fed run's frame: gate[b] = stopped[b] |
+// (text_open[b] && n_gen[b] >= n_trailing[b]), held[b] counts the frames a live
+// slot was held, and the talker input rows x [nb][H] are saved (x_save; NULL:
+// the frame runs no talker step) and, for gated slots, put back
+struct TextGateArgs {
+    const int *stopped = nullptr, *text_open = nullptr, *n_gen = nullptr, *n_trailing = nullptr;
+    int *gate = nullptr, *held = nullptr;
+    float *x = nullptr, *x_save = nullptr;
+    int H = 0, nb = 1;
+};
+int qtts_text_gate(const TextGateArgs &a, hipStream_t st);
+int qtts_text_restore(const TextGateArgs &a, hipStream_t st);
+int qtts_text_open(float *eos, const float *trailing_row, int H, int *n_trailing, int *text_open, int *held, int b,
                    hipStream_t st);
 
 // the instruct prefix cache (k_kvprefix.hip): talker K and V rows [0, n) of one

@@ -209,6 +209,19 @@ struct qtts_dev {
     SampSlotRow *sp_tab = nullptr;
     std::vector<SampSlotRow> sp_host;
     bool sp_armed = false, sp_general = false;
+    // incremental text input (qtts_dev_text_open / _append, k_textfeed.hip): a
+    // run is fed from its first qtts_dev_text_open until the next
+    // qtts_dev_begin; its frames are graphs of their own (graph_key + 8) whose
+    // first node computes `gate` and whose stop readers take it (stop_rd).  The
+    // buffers live with the state, allocated by the first fed run on it:
+    // tf_open / tf_gate / tf_held [B], tf_eos [B][H] each slot's tts_eos row,
+    // tf_xsave [B][H] the talker input rows of a frame, tf_t1 [16][TH] fc1's
+    // output of an append.  tf_rows / tf_open_h: the host's mirror of
+    // n_trailing / text_open; tf_held_h: held counters as of the last poll
+    bool fed = false;
+    int *tf_open = nullptr, *tf_gate = nullptr, *tf_held = nullptr;
+    float *tf_eos = nullptr, *tf_xsave = nullptr, *tf_t1 = nullptr;
+    std::vector<int> tf_rows, tf_open_h, tf_held_h;
     // EOS-mode lagged poll: the sampler mirrors each slot's stop into pinned
     // host memory; an event after every frame lets the host wait for frame
     // s - 1 while frame s is already queued (qtts_dev_frame_done)
@@ -371,6 +384,9 @@ static void free_state(qtts_dev *dv) {
     dv->ids_cap = 0;  // prompt scratch lived in sallocs
     dv->pids = dv->pplan = nullptr;
     dv->pt1 = dv->pproj = nullptr;
+    dv->fed = false;
+    dv->tf_open = dv->tf_gate = dv->tf_held = nullptr;
+    dv->tf_eos = dv->tf_xsave = dv->tf_t1 = nullptr;
     dv->graph_key = -1;
     codec_free_state(&dv->codec);
 }
@@ -1268,6 +1284,9 @@ static L2Prefetch pf_attn_o(const qtts_dev *dv, const bf16_t *Wo, int R, int NH,
     return p;
 }
 
+// the flag a frame's stop readers take: a fed run's gate (k_textfeed.hip), else `stopped`
+static const int *stop_rd(const qtts_dev *dv) { return dv->fed ? dv->tf_gate : dv->stopped; }
+
 // the talker layers at batch 1 as persistent launches (k_tengine.hip), each
 // bit-identical to the launch-per-op layer below
 static bool tengine_ok(qtts_dev *dv, int kzo, int kzd) {
@@ -1291,7 +1310,7 @@ static int talker_layers_te(qtts_dev *dv) {
         a.in_norm = ly.in; a.post_norm = ly.post; a.qn_w = ly.qn; a.kn_w = ly.kn;
         a.rope_cos = dv->rope_cos; a.rope_sin = dv->rope_sin;
         a.kc = dv->kv_layer(dv->kc, l); a.vc = dv->kv_layer(dv->vc, l);   // (fp32 only: tengine_ok)
-        a.pos = dv->kv_len; a.skip = dv->stopped; a.eps = d.eps;
+        a.pos = dv->kv_len; a.skip = stop_rd(dv); a.eps = d.eps;
         a.part = dv->att_part; a.cnt = dv->att_cnt; a.nsplit = dv->att_nsplit;
         a.g_qkv = dv->te_g; a.g_att = dv->te_g + 4096; a.g_x = a.g_att + 2048; a.g_h = a.g_x + 2048;
         a.epoch = dv->te_ctl; a.err = dv->te_ctl + 1;
@@ -1328,7 +1347,7 @@ static int talker_layers(qtts_dev *dv) {
         t.rope_cos = dv->rope_cos; t.rope_sin = dv->rope_sin;
         t.kc = dv->kv_layer(dv->kc, l); t.vc = dv->kv_layer(dv->vc, l); t.S = dv->S; t.kv_dtype = dv->kv_dtype;
         t.pos = dv->kv_len; t.NH = d.NH; t.KV = d.KV; t.HD = d.HD; t.out = dv->att; t.ld_out = AD; t.nrows = nb;
-        t.skip = dv->stopped;
+        t.skip = stop_rd(dv);
         t.part = dv->att_part; t.cnt = dv->att_cnt; t.nsplit = dv->att_nsplit; t.lpk = dv->attn_lpk;
         // batch 1: the attention's split merge moves into the O projection's
         // prologue (one dependent hand-off fewer per layer)
@@ -1382,8 +1401,10 @@ static int head_sample(qtts_dev *dv, const GemvArgs &a, const SampArgs &s, int k
         return qtts_sample_forced(s, f, dv->st);
     }
     // per-slot parameters: the per-slot sampler (its own frame graphs, graph_key 3 / 4)
-    if (dv->sp_armed) return qtts_sample_slots(s, dv->sp_tab, !dv->sp_general, dv->st);
-    return qtts_sample(s, dv->st);
+    // (a fed run: the rows read the gate; nullptr otherwise -- the launches of before)
+    const int *rd = dv->fed ? dv->tf_gate : nullptr;
+    if (dv->sp_armed) return qtts_sample_slots(s, dv->sp_tab, !dv->sp_general, dv->st, rd);
+    return qtts_sample(s, dv->st, rd);
 }
 
 // final norm + codec head; normed hidden -> tk_hid (T.c:526-530, Q.c:1295)
@@ -1433,7 +1454,7 @@ static AttnArgs st_pair_attn_args(const qtts_dev *dv, int l) {
     t.rope_cos = dv->rope_cos_s; t.rope_sin = dv->rope_sin_s;
     t.kc = dv->kcs + (size_t)l * dv->nb * d.G * KVD; t.vc = dv->vcs + (size_t)l * dv->nb * d.G * KVD; t.S = d.G;
     t.pos = nullptr; t.pos_const = 0; t.NH = d.NHs; t.KV = d.KVs; t.HD = d.HDs; t.ld_out = d.NHs * d.HDs;
-    t.nrows = 2; t.skip = dv->stopped;
+    t.nrows = 2; t.skip = stop_rd(dv);
     if (l == 0) {   // row 1: q|k|v from the load-time table by the talker's draw, its input row to the residual
         const bool proj = dv->st_proj != nullptr;
         t.qkv_tab = dv->qkv0_tab; t.tab_ids = dv->last_tok; t.tab_bstride = 1; t.tab_off = 0;
@@ -1620,7 +1641,7 @@ static int subtalker(qtts_dev *dv) {
             t.rope_cos = dv->rope_cos_s; t.rope_sin = dv->rope_sin_s;
             t.kc = dv->kcs + (size_t)l * NBA * d.G * KVD; t.vc = dv->vcs + (size_t)l * NBA * d.G * KVD; t.S = d.G;
             t.pos = nullptr; t.pos_const = g; t.NH = d.NHs; t.KV = d.KVs; t.HD = d.HDs; t.out = dv->att_s;
-            t.ld_out = AD; t.nrows = nb; t.skip = dv->stopped;
+            t.ld_out = AD; t.nrows = nb; t.skip = stop_rd(dv);
             t.cnt = dv->att_cnt;
             // batch 1, pass g >= 1, layer 0: q|k|v come from the load-time table
             // by the input id (no GEMV); the gate|up GEMV reads the residual
@@ -1714,7 +1735,7 @@ static int embed_sum(qtts_dev *dv, int advance) {
     const qtts_dims_t &d = dv->d;
     EmbedSumArgs e;
     e.codes = dv->codes; e.codes_bstride = (dv->max_frames + 1) * d.G; e.G = d.G;
-    e.cur_row = dv->cur_row; e.stopped = dv->stopped; e.codec_emb = dv->codec_emb; e.st_emb = dv->st_emb;
+    e.cur_row = dv->cur_row; e.stopped = stop_rd(dv); e.codec_emb = dv->codec_emb; e.st_emb = dv->st_emb;
     e.Vs = d.Vs; e.H = d.H; e.nb = dv->nrun; e.trailing = dv->trailing; e.tr_cap = dv->tr_cap;
     e.n_trailing = dv->n_trailing; e.pad = dv->pad_emb; e.out = dv->x_tk; e.kv_len = dv->kv_len; e.advance = advance;
     ProfScope ps(dv, PK_EMBED, 0);
@@ -1724,10 +1745,22 @@ static int embed_sum(qtts_dev *dv, int advance) {
 static int record_frame(qtts_dev *dv, bool with_talker) {
     // step 0 starts from the prefill's hidden in x_tk (no pending partials)
     dv->tk_xfin = dv->x_tk; dv->tk_pend = nullptr; dv->tk_npend = 0;
+    TextGateArgs tg;
+    if (dv->fed) {   // the gate first; a talker step updates x_tk in place, so a held slot's row is saved
+        tg.stopped = dv->stopped; tg.text_open = dv->tf_open; tg.n_gen = dv->n_gen; tg.n_trailing = dv->n_trailing;
+        tg.gate = dv->tf_gate; tg.held = dv->tf_held; tg.x = dv->x_tk; tg.x_save = with_talker ? dv->tf_xsave : nullptr;
+        tg.H = dv->d.H; tg.nb = dv->nrun;
+        ProfScope ps(dv, PK_EMBED, 0);
+        CKI(qtts_text_gate(tg, dv->st));
+    }
     if (with_talker) CKI(talker_layers(dv));
     CKI(talker_head_sample(dv));
     CKI(subtalker(dv));
     CKI(embed_sum(dv, with_talker ? 1 : 0));
+    if (dv->fed && with_talker) {
+        ProfScope ps(dv, PK_EMBED, 0);
+        CKI(qtts_text_restore(tg, dv->st));
+    }
     return 0;
 }
 
@@ -1754,7 +1787,8 @@ static int capture(qtts_dev *dv, bool with_talker, hipGraphExec_t *out) {
 // 31.1 / 30.5 audio-s/s (profiles/r03c_eos_ab.txt).
 static int ensure_graphs(qtts_dev *dv) {
     // (the forced sampler's frame is another graph, and so is each per-slot family's)
-    const int want = dv->f_armed ? 2 : dv->sp_armed ? (dv->sp_general ? 4 : 3) : 1;
+    // (a fed run's frames, with the gate node, are graphs of their own: + 8)
+    const int want = (dv->f_armed ? 2 : dv->sp_armed ? (dv->sp_general ? 4 : 3) : 1) + (dv->fed ? 8 : 0);
     if (dv->g0 && dv->gN && dv->graph_key == want) return 0;
     // (mid-run: a refill admitted the run's first row that needs the full path)
     if (dv->f_phase == 2 && (dv->g0 || dv->gN)) CK(hipStreamSynchronize(dv->st));
@@ -1778,6 +1812,13 @@ static int ensure_graphs(qtts_dev *dv) {
 static bool force_refuses(const qtts_dev *dv, const char *what) {
     if (!dv->f_armed) return false;
     fprintf(stderr, "qtts: %s refused: forced codes / taps are armed (not defined for the work queue)\n", what);
+    return true;
+}
+
+// and so is incremental text input (qtts_dev_text_open)
+static bool fed_refuses(const qtts_dev *dv, const char *what) {
+    if (!dv->fed) return false;
+    fprintf(stderr, "qtts: %s refused: the run takes its text incrementally (not defined for the work queue)\n", what);
     return true;
 }
 
@@ -1824,6 +1865,9 @@ extern "C" int qtts_dev_begin(qtts_dev_t *dv, int nb, int max_frames, int max_pr
     CKI(join_prime(dv));   // a prime left pending by a run that pushed no frames
     free_force(dv);        // forcing and taps last for one run (and their record until the next begins)
     free_slot_params(dv);  // and so do per-slot sampling parameters
+    // and so does incremental text input (the fed frame graphs stay: graph_key tells the families
+    // apart, so the next fed run on this state replays them and an unfed one captures the plain family)
+    dv->fed = false;
     dv->f_run_frames = max_frames;
     if (max_prefill < 16) max_prefill = 16;
     // (another cache element type: new state, and with it new frame graphs)
@@ -2100,7 +2144,7 @@ extern "C" int qtts_dev_prefill(qtts_dev_t *dv) {
 // Everything is ordered on the context stream after the frames already queued.
 extern "C" int qtts_dev_refill(qtts_dev_t *dv, int b) {
     if (!dv || b < 0 || b >= dv->nb || dv->p_len_h[b] < 2) return -1;
-    if (force_refuses(dv, "qtts_dev_refill")) return -1;
+    if (force_refuses(dv, "qtts_dev_refill") || fed_refuses(dv, "qtts_dev_refill")) return -1;
     hipSetDevice(dv->device);
     const qtts_dims_t &d = dv->d;
     std::vector<int> last, first;
@@ -2131,6 +2175,137 @@ extern "C" int qtts_dev_retire(qtts_dev_t *dv, int b) {
     return 0;
 }
 
+// ----------------------------------------------------------------- incremental text input
+// frames a live slot was held for want of a text row, as the polls of fed runs
+// saw them, since the library loaded
+static std::atomic<long long> g_text_held{0};
+extern "C" long long qtts_hip_text_held_frames(void) { return g_text_held.load(); }
+
+// Slot b's text opens (after its qtts_dev_prompt, before frame 0).  The prompt
+// carries the tts_eos row alone (n_trailing 1: a template with one content
+// id); it moves to the slot's eos row, the count goes back to 0 and the run
+// becomes a fed one.  Stream-ordered, no host wait.
+extern "C" int qtts_dev_text_open(qtts_dev_t *dv, int b) {
+    if (!dv || b < 0 || b >= dv->nb) return -1;
+    if (dv->f_phase != 1) {
+        fprintf(stderr, "qtts_dev_text_open: valid after qtts_dev_begin and before the first frame\n");
+        return -1;
+    }
+    if (dv->f_armed) {
+        fprintf(stderr, "qtts_dev_text_open refused: forced codes / taps are armed\n");
+        return -1;
+    }
+    if (dv->tengine) {
+        fprintf(stderr, "qtts_dev_text_open refused: QTTS_HIP_TENGINE has no gate (unset it for fed runs)\n");
+        return -1;
+    }
+    if (dv->n_tr_h[b] != 1) {
+        fprintf(stderr, "qtts_dev_text_open: slot %d's prompt has %d trailing rows (the tts_eos row alone expected)\n",
+                b, dv->n_tr_h[b]);
+        return -1;
+    }
+    hipSetDevice(dv->device);
+    const qtts_dims_t &d = dv->d;
+    const size_t B = dv->nb;
+    if (!dv->tf_gate) {
+        dv->tf_open = (int *)dalloc(dv, B * 4, false);
+        dv->tf_gate = (int *)dalloc(dv, B * 4, false);
+        dv->tf_held = (int *)dalloc(dv, B * 4, false);
+        dv->tf_eos = (float *)dalloc(dv, B * d.H * 4, false);
+        dv->tf_xsave = (float *)dalloc(dv, B * d.H * 4, false);
+        dv->tf_t1 = (float *)dalloc(dv, (size_t)QTTS_TF_MAX * d.TH * 4, false);
+        if (!dv->tf_open || !dv->tf_gate || !dv->tf_held || !dv->tf_eos || !dv->tf_xsave || !dv->tf_t1) {
+            dv->tf_gate = nullptr;
+            return -1;
+        }
+    }
+    if (!dv->fed) {
+        CK(hipMemsetAsync(dv->tf_open, 0, B * 4, dv->st));
+        CK(hipMemsetAsync(dv->tf_gate, 0, B * 4, dv->st));
+        CK(hipMemsetAsync(dv->tf_held, 0, B * 4, dv->st));
+        dv->tf_rows.assign(B, 0);
+        dv->tf_open_h.assign(B, 0);
+        dv->tf_held_h.assign(B, 0);
+        dv->fed = true;
+    }
+    CKI(qtts_text_open(dv->tf_eos + (size_t)b * d.H, dv->trailing + (size_t)b * dv->tr_cap * d.H, d.H, dv->n_trailing,
+                       dv->tf_open, dv->tf_held, b, dv->st));
+    dv->tf_rows[b] = 0;
+    dv->tf_open_h[b] = 1;
+    dv->n_tr_h[b] = 0;
+    return 0;
+}
+
+extern "C" int qtts_dev_text_append(qtts_dev_t *dv, int b, const int *ids, int n, int close) {
+    if (!dv || b < 0 || b >= dv->nb || n < 0 || (n > 0 && !ids) || (n == 0 && !close)) return -1;
+    if (!dv->fed || !dv->tf_open_h[b]) {
+        fprintf(stderr, "qtts_dev_text_append: slot %d's text is not open\n", b);
+        return -1;
+    }
+    const qtts_dims_t &d = dv->d;
+    for (int i = 0; i < n; ++i)
+        if (ids[i] < 0 || ids[i] >= d.TV) {
+            fprintf(stderr, "qtts_dev_text_append: text token id %d out of range\n", ids[i]);
+            return -1;
+        }
+    hipSetDevice(dv->device);
+    // (growth past tr_cap: the one append that waits, and the frame graphs are captured again)
+    CKI(ensure_trailing(dv, dv->tf_rows[b] + n + (close ? 1 : 0)));
+    TextFeedArgs a;
+    a.b = b; a.text_emb = dv->text_emb; a.fc1w = dv->fc1w; a.fc2w = dv->fc2w; a.fc1b = dv->fc1b; a.fc2b = dv->fc2b;
+    a.TH = d.TH; a.H = d.H; a.t1 = dv->tf_t1; a.trailing = dv->trailing; a.tr_cap = dv->tr_cap;
+    a.n_trailing = dv->n_trailing; a.text_open = dv->tf_open; a.eos = dv->tf_eos + (size_t)b * d.H;
+    if (!dv->fc1b) { fprintf(stderr, "qtts: text projection without fc1 bias unsupported\n"); return -1; }
+    int i0 = 0;
+    do {
+        a.n = n - i0 < QTTS_TF_MAX ? n - i0 : QTTS_TF_MAX;
+        for (int j = 0; j < a.n; ++j) a.ids[j] = ids[i0 + j];
+        i0 += a.n;
+        a.close = close && i0 == n;
+        CKI(qtts_text_append(a, dv->st));
+    } while (i0 < n);
+    dv->tf_rows[b] += n + (close ? 1 : 0);
+    if (close) dv->tf_open_h[b] = 0;
+    dv->n_tr_h[b] = dv->tf_rows[b];
+    return 0;
+}
+
+// measurement: the same append between two events on the context stream; waits for it
+extern "C" int qtts_dev_text_append_ms(qtts_dev_t *dv, int b, const int *ids, int n, int close, float *ms) {
+    if (!dv || !ms) return -1;
+    hipSetDevice(dv->device);
+    hipEvent_t e0, e1;
+    CK(hipEventCreate(&e0));
+    CK(hipEventCreate(&e1));
+    CK(hipEventRecord(e0, dv->st));
+    const int rc = qtts_dev_text_append(dv, b, ids, n, close);
+    CK(hipEventRecord(e1, dv->st));
+    CK(hipEventSynchronize(e1));
+    CK(hipEventElapsedTime(ms, e0, e1));
+    hipEventDestroy(e0);
+    hipEventDestroy(e1);
+    return rc;
+}
+
+extern "C" int qtts_dev_get_trailing(qtts_dev_t *dv, int b, int row0, int n, float *host) {
+    if (!dv || !host || b < 0 || b >= dv->nb || row0 < 0 || n < 1 || row0 + n > dv->tr_cap) return -1;
+    hipSetDevice(dv->device);
+    CK(hipStreamSynchronize(dv->st));
+    CK(hipMemcpy(host, dv->trailing + ((size_t)b * dv->tr_cap + row0) * dv->d.H, (size_t)n * dv->d.H * 4,
+                 hipMemcpyDeviceToHost));
+    return 0;
+}
+
+extern "C" int qtts_dev_text_state(qtts_dev_t *dv, int b, int *rows, int *open, int *held) {
+    if (!dv || b < 0 || b >= dv->nb) return -1;
+    hipSetDevice(dv->device);
+    CK(hipStreamSynchronize(dv->st));
+    if (rows) CK(hipMemcpy(rows, dv->n_trailing + b, 4, hipMemcpyDeviceToHost));
+    if (open) { *open = 0; if (dv->tf_open) CK(hipMemcpy(open, dv->tf_open + b, 4, hipMemcpyDeviceToHost)); }
+    if (held) { *held = 0; if (dv->tf_held) CK(hipMemcpy(held, dv->tf_held + b, 4, hipMemcpyDeviceToHost)); }
+    return 0;
+}
+
 // Work queue, lagged as qtts_dev_frame_done: waits until frame `step` has
 // finished and copies every slot's EOS mirror (1: drew EOS by then).
 extern "C" int qtts_dev_frame_stops(qtts_dev_t *dv, int step, int *stopped) {
@@ -2149,7 +2324,7 @@ extern "C" int qtts_dev_frame_stops(qtts_dev_t *dv, int step, int *stopped) {
 // writes either slot).
 extern "C" int qtts_dev_move_slot(qtts_dev_t *dv, int from, int to) {
     if (!dv || from < 0 || to < 0 || from >= dv->nb || to >= dv->nb || from == to) return -1;
-    if (force_refuses(dv, "qtts_dev_move_slot")) return -1;
+    if (force_refuses(dv, "qtts_dev_move_slot") || fed_refuses(dv, "qtts_dev_move_slot")) return -1;
     hipSetDevice(dv->device);
     const qtts_dims_t &d = dv->d;
     hipStream_t st = dv->st;
@@ -2192,7 +2367,7 @@ extern "C" int qtts_dev_move_slot(qtts_dev_t *dv, int from, int to) {
 // <= the slots of qtts_dev_begin; their own graph per row count).
 extern "C" int qtts_dev_set_rows(qtts_dev_t *dv, int rows) {
     if (!dv || rows < 1 || rows > dv->nb || (rows < dv->nb && rows > QTTS_MAX_SLOTS)) return -1;
-    if (force_refuses(dv, "qtts_dev_set_rows")) return -1;
+    if (force_refuses(dv, "qtts_dev_set_rows") || (rows < dv->nb && fed_refuses(dv, "qtts_dev_set_rows"))) return -1;
     dv->nrun = rows;
     return 0;
 }
@@ -2246,7 +2421,16 @@ extern "C" int qtts_dev_poll(qtts_dev_t *dv, int *stopped, int *n_gen, int *stop
     if (stopped) CK(hipMemcpyAsync(stopped, dv->stopped, B * 4, hipMemcpyDeviceToHost, dv->st));
     if (n_gen) CK(hipMemcpyAsync(n_gen, dv->n_gen, B * 4, hipMemcpyDeviceToHost, dv->st));
     if (stop_step) CK(hipMemcpyAsync(stop_step, dv->stop_step, B * 4, hipMemcpyDeviceToHost, dv->st));
+    std::vector<int> held;
+    if (dv->fed) {   // the held counters ride along (qtts_hip_text_held_frames)
+        held.resize(B);
+        CK(hipMemcpyAsync(held.data(), dv->tf_held, B * 4, hipMemcpyDeviceToHost, dv->st));
+    }
     CK(hipStreamSynchronize(dv->st));
+    for (size_t b = 0; b < held.size(); ++b) {
+        if (held[b] > dv->tf_held_h[b]) g_text_held.fetch_add(held[b] - dv->tf_held_h[b]);
+        dv->tf_held_h[b] = held[b];
+    }
     return 0;
 }
 

@@ -19,10 +19,13 @@
  * qwen_tts_last_drawn), --seed-step K (with --batch N: slot b samples with seed
  * + b K, qwen_tts_set_utterance_sampling, and every slot's audio is written).
  */
+#include <errno.h>
+#include <poll.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 #include <time.h>
+#include <unistd.h>
 
 #include "../../../include/qwen_tts.h"
 
@@ -54,6 +57,8 @@ static void usage(const char *prog) {
             "  --device N (HIP device, default 0)   --batch N (lock-step batch of N copies, default 1)\n"
             "  --seed-step K (with --batch N: slot b samples with seed + b*K -- N takes of the prompt -- and\n"
             "                      every slot is written: slot 0 to -o's path, slot b to <stem>_<b>.wav)\n"
+            "  --stdin-ids (the CONTENT ids of one utterance from stdin while it decodes, comma or whitespace\n"
+            "               separated, EOF closes the text; the role ids are supplied; --stream N sets the chunk)\n"
             "  --stream N (streaming decode, audio chunks every N frames after the first; with --batch\n"
             "                      every slot is streamed through the multi-stream codec)\n"
             "  --kv-cache fp32|bf16 (talker KV cache elements, default fp32; bf16 halves the cache,\n"
@@ -184,12 +189,68 @@ static void progress(int step, int total, void *u) {
     }
 }
 
+/* --stdin-ids: the content ids of one utterance from stdin while it decodes
+ * (qwen_tts_generate_fed_stream), comma or whitespace separated; wait = 0 takes
+ * what has arrived without blocking, wait = 1 blocks for more; EOF closes the
+ * text.  A number cut by a read is kept until its end arrives. */
+typedef struct {
+    char part[16];
+    int n_part, closed;
+} stdin_feed_t;
+
+static int stdin_feed(qwen_tts_feed_t *feed, int wait, void *user) {
+    stdin_feed_t *s = (stdin_feed_t *)user;
+    while (!s->closed) {
+        struct pollfd p = {0, POLLIN, 0};
+        if (!wait && poll(&p, 1, 0) <= 0) return 0;
+        char buf[4096];
+        const ssize_t n = read(0, buf, sizeof buf);
+        if (n < 0) {
+            if (errno == EINTR) continue;
+            perror("--stdin-ids");
+            return -1;
+        }
+        int ids[2049], k = 0;
+        for (ssize_t i = 0; i < n; i++) {
+            const char c = buf[i];
+            if (c >= '0' && c <= '9') {
+                if (s->n_part >= (int)sizeof s->part - 1) {
+                    fprintf(stderr, "Error: --stdin-ids: a number too long\n");
+                    return -1;
+                }
+                s->part[s->n_part++] = c;
+            } else if (c == ',' || c == ' ' || c == '\n' || c == '\t' || c == '\r') {
+                if (s->n_part) {
+                    s->part[s->n_part] = 0;
+                    ids[k++] = (int)strtol(s->part, NULL, 10);
+                    s->n_part = 0;
+                }
+            } else {
+                fprintf(stderr, "Error: --stdin-ids: unexpected character '%c'\n", c);
+                return -1;
+            }
+        }
+        if (n == 0 && s->n_part) {   /* EOF ends the last number */
+            s->part[s->n_part] = 0;
+            ids[k++] = (int)strtol(s->part, NULL, 10);
+            s->n_part = 0;
+        }
+        if (k && qwen_tts_feed_ids(feed, 0, ids, k) != 0) return -1;
+        if (n == 0) {
+            s->closed = 1;
+            return qwen_tts_feed_close(feed, 0);
+        }
+        if (k || !wait) return 0;
+    }
+    return 0;
+}
+
 int main(int argc, char **argv) {
     const char *dir = NULL, *ids = NULL, *ids_file = NULL, *spk = NULL, *lang = NULL, *out = "output.wav";
     int verbose = 0, runs = 1, warmup = 0, device = -1, batch = 1, stream_chunk = 0, non_streaming = 0;
     int kv_cache = -1;   /* --kv-cache: -1 = the library's default ($QTTS_HIP_KV or fp32) */
     const char *ref_codes_file = NULL, *ref_text = NULL, *xvec_file = NULL, *text = NULL, *ref_audio = NULL;
-    int print_ids = 0, xvec_only = 0;
+    int print_ids = 0, xvec_only = 0, stdin_ids = 0;
     const char *force_file = NULL, *drawn_file = NULL;
     int seed_step = 0, seed_step_set = 0;
     const char *instruct = NULL, *instruct_ids = NULL;
@@ -205,6 +266,7 @@ int main(int argc, char **argv) {
         else if (ARG("-f")) ids_file = argv[++i];
         else if (ARG("-T")) text = argv[++i];
         else if (!strcmp(a, "--print-ids")) print_ids = 1;
+        else if (!strcmp(a, "--stdin-ids")) stdin_ids = 1;
         else if (ARG("-s")) spk = argv[++i];
         else if (ARG("-l")) lang = argv[++i];
         else if (ARG("-o")) out = argv[++i];
@@ -250,7 +312,15 @@ int main(int argc, char **argv) {
 #undef ARG
     }
     if (!dir) { fprintf(stderr, "Error: model directory required (-d)\n\n"); usage(argv[0]); return 1; }
-    if (!ids && !ids_file && !text) {
+    if (stdin_ids && (ids || ids_file || text)) {
+        fprintf(stderr, "Error: --stdin-ids takes the content ids from stdin (no -t / -f / -T)\n");
+        return 1;
+    }
+    if (stdin_ids && (batch != 1 || runs + warmup != 1 || ref_codes_file || xvec_file || ref_audio)) {
+        fprintf(stderr, "Error: --stdin-ids runs one preset-speaker utterance once (no --batch, benchmark runs or voice clone)\n");
+        return 1;
+    }
+    if (!ids && !ids_file && !text && !stdin_ids) {
         fprintf(stderr, "Error: token IDs required (-t or -f) or text (-T)\n\n");
         usage(argv[0]);
         return 1;
@@ -476,6 +546,12 @@ int main(int argc, char **argv) {
             total_samples = rn;
         } else if (clone) {
             ra = qwen_tts_generate_voice_clone(ctx, ids, ref_text, ref_codes, n_ref, xvec, lang, non_streaming, &rn);
+            total_samples = rn;
+        } else if (stdin_ids) {
+            stdin_feed_t sf;
+            memset(&sf, 0, sizeof sf);
+            ra = qwen_tts_generate_fed_stream(ctx, spk, lang, stream_chunk > 0 ? stream_chunk : 4, stdin_feed, &sf, NULL,
+                                              NULL, &rn);
             total_samples = rn;
         } else if (batch == 1 && stream_chunk > 0) {
             ra = qwen_tts_generate_stream(ctx, ids, spk, lang, stream_chunk, NULL, NULL, &rn);

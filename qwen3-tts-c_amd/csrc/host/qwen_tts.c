@@ -2322,6 +2322,362 @@ int qwen_tts_generate_batch_stream(qwen_tts_ctx_t *ctx, int nb, const char *cons
     return rc;
 }
 
+/* ------------------------------------------------- incremental text input */
+/* The two device entries of a fed run are weak here: a build of this file
+ * against a device layer without them (the host-trace fakes of the other
+ * calls) links, and the fed calls refuse. */
+extern int qtts_dev_text_open(qtts_dev_t *dev, int b) __attribute__((weak));
+extern int qtts_dev_text_append(qtts_dev_t *dev, int b, const int *ids, int n, int close) __attribute__((weak));
+
+/* One fed call's text state.  Before the device run has begun (dev NULL) the
+ * ids are kept here; from then on a push is one qtts_dev_text_append.  With
+ * content ids c[0..m) trailing row r is proj(c[r + 1]), row m - 1 tts_eos, and
+ * the frame that draws frame r needs row r: utterance u is starved when its
+ * text is open and frames[u] >= rows[u], all of it host arithmetic. */
+#define FEED_TOKEN_ASSISTANT 77091   /* "assistant" and "\n" of "<|im_start|>assistant\n" */
+#define FEED_TOKEN_NEWLINE 198
+struct qwen_tts_feed {
+    const qwen_tts_ctx_t *ctx;
+    qtts_dev_t *dev;
+    int nb, in_cb, failed;
+    int **ids;                   /* [nb] ids pushed before the device run began */
+    int *cap;
+    int *taken, *closed, *rows;  /* ids taken; the text is over; trailing rows published (tts_eos included) */
+    int *frames, *stopped;       /* frames launched for it; it drew EOS or reached the limit */
+    int *touched;                /* pushed or closed during the current callback */
+};
+
+static void feed_free(qwen_tts_feed_t *f) {
+    for (int u = 0; f->ids && u < f->nb; u++) free(f->ids[u]);
+    free(f->ids); free(f->cap); free(f->taken); free(f->closed); free(f->rows); free(f->frames); free(f->stopped);
+    free(f->touched);
+    memset(f, 0, sizeof *f);
+}
+
+static int feed_init(qwen_tts_feed_t *f, const qwen_tts_ctx_t *ctx, int nb) {
+    memset(f, 0, sizeof *f);
+    f->ctx = ctx;
+    f->nb = nb;
+    f->ids = (int **)calloc(nb, sizeof(int *));
+    f->cap = (int *)calloc(nb, sizeof(int)); f->taken = (int *)calloc(nb, sizeof(int));
+    f->closed = (int *)calloc(nb, sizeof(int)); f->rows = (int *)calloc(nb, sizeof(int));
+    f->frames = (int *)calloc(nb, sizeof(int)); f->stopped = (int *)calloc(nb, sizeof(int));
+    f->touched = (int *)calloc(nb, sizeof(int));
+    return f->ids && f->cap && f->taken && f->closed && f->rows && f->frames && f->stopped && f->touched ? 0 : -1;
+}
+
+static int feed_starved(const qwen_tts_feed_t *f, int u) {
+    return !f->stopped[u] && !f->closed[u] && (f->taken[u] < 1 || f->frames[u] >= f->rows[u]);
+}
+
+/* the checks every push and close starts with: 1 go on, 0 nothing to do, -1 refused */
+static int feed_enter(qwen_tts_feed_t *f, int u, const char *who) {
+    if (!f || !f->in_cb) {
+        fprintf(stderr, "Error: %s: valid only inside the feed callback\n", who);
+        return -1;
+    }
+    if (u < 0 || u >= f->nb) {
+        fprintf(stderr, "Error: %s: utterance %d of %d\n", who, u, f->nb);
+        return -1;
+    }
+    if (f->stopped[u]) return 0;
+    if (f->closed[u]) {
+        fprintf(stderr, "Error: %s: utterance %d is closed\n", who, u);
+        return -1;
+    }
+    return 1;
+}
+
+static int feed_put(qwen_tts_feed_t *f, int u, const int *ids, int n, int close) {
+    if (f->dev) {
+        /* (the first id is in the prefill; every later one is a trailing row) */
+        if (qtts_dev_text_append(f->dev, u, ids, n, close) != 0) { f->failed = 1; return -1; }
+        f->rows[u] += n + close;
+    } else {
+        if (f->taken[u] + n > f->cap[u]) {
+            const int cap = (f->taken[u] + n) * 2 + 16;
+            int *p = (int *)realloc(f->ids[u], (size_t)cap * sizeof(int));
+            if (!p) { f->failed = 1; return -1; }
+            f->ids[u] = p;
+            f->cap[u] = cap;
+        }
+        if (n) memcpy(f->ids[u] + f->taken[u], ids, (size_t)n * sizeof(int));
+    }
+    f->taken[u] += n;
+    if (close) f->closed[u] = 1;
+    f->touched[u] = 1;
+    return 0;
+}
+
+int qwen_tts_feed_ids(qwen_tts_feed_t *feed, int utterance, const int *ids, int n) {
+    const int go = feed_enter(feed, utterance, "qwen_tts_feed_ids");
+    if (go <= 0) return go;
+    if (!ids || n < 1) {
+        fprintf(stderr, "Error: qwen_tts_feed_ids: %d ids\n", n);
+        return -1;
+    }
+    if (!ids_in_range(feed->ctx, ids, n)) return -1;
+    return feed_put(feed, utterance, ids, n, 0);
+}
+
+int qwen_tts_feed_close(qwen_tts_feed_t *feed, int utterance) {
+    const int go = feed_enter(feed, utterance, "qwen_tts_feed_close");
+    if (go <= 0) return go;
+    return feed_put(feed, utterance, NULL, 0, 1);
+}
+
+int qwen_tts_feed_state(const qwen_tts_feed_t *feed, int utterance, int *ids_taken, int *frames_done, int *starved) {
+    if (!feed || utterance < 0 || utterance >= feed->nb) return -1;
+    if (ids_taken) *ids_taken = feed->taken[utterance];
+    if (frames_done) *frames_done = feed->frames[utterance];
+    if (starved) *starved = feed_starved(feed, utterance);
+    return 0;
+}
+
+/* One callback.  wait: afterwards some utterance that was starved on entry
+ * must have been pushed to or closed, or the loop would spin. */
+static int feed_call(qwen_tts_feed_t *f, qwen_tts_text_feed_cb cb, void *user, int wait) {
+    int was[QWEN_TTS_MAX_BATCH], progress = 0;
+    for (int u = 0; u < f->nb; u++) {
+        was[u] = feed_starved(f, u);
+        f->touched[u] = 0;
+    }
+    f->in_cb = 1;
+    const int rc = cb(f, wait, user);
+    f->in_cb = 0;
+    if (rc < 0) {
+        fprintf(stderr, "Error: the feed callback aborted the call (%d)\n", rc);
+        return -1;
+    }
+    if (f->failed) return -1;
+    for (int u = 0; u < f->nb; u++) progress |= was[u] && f->touched[u];
+    if (wait && !progress) {
+        fprintf(stderr, "Error: feed made no progress (a wait = 1 callback pushed nothing for a starved utterance)\n");
+        return -1;
+    }
+    return 0;
+}
+
+static int run_fed(qwen_tts_ctx_t *ctx, int nb, const char *const *speakers, const char *const *languages,
+                   const stream_t *stream, qwen_tts_text_feed_cb feed_cb, void *feed_user, float **audio,
+                   int *samples, double t_start) {
+    qtts_dev_t *dev = (qtts_dev_t *)ctx->hip;
+    const int G = ctx->config.num_code_groups;
+    int rc = -1;
+    sampling_arm_t *sarm = sampling_take(ctx);
+    instruct_arm_t *iarm = instruct_take(ctx);
+    prompt_t *pr = NULL;
+    int *stopped = NULL, *ngen = NULL, *sstep = NULL, *retired = NULL;
+    sstate_t ss;
+    qwen_tts_feed_t fd;
+    memset(&ss, 0, sizeof ss);
+    memset(&fd, 0, sizeof fd);
+    if (sampling_refused("generate_fed", sarm, NULL, nb) || instruct_refused("generate_fed", iarm, nb, 0)) goto out;
+    if (!qtts_dev_text_open || !qtts_dev_text_append) {
+        fprintf(stderr, "Error: generate_fed: this build's device layer has no incremental text input\n");
+        goto out;
+    }
+    const int fixed = ctx->fixed_codec_tokens > 0 ? ctx->fixed_codec_tokens : 0;
+    const int max_tokens = fixed > 0 ? fixed : ctx->max_new_tokens;
+    if (max_tokens < 1) goto out;
+    if (feed_init(&fd, ctx, nb) != 0) goto out;
+    /* start: every utterance's first content id, before the device is touched */
+    for (;;) {
+        int missing = 0;
+        for (int u = 0; u < nb; u++) {
+            if (fd.taken[u] > 0) continue;
+            if (fd.closed[u]) {
+                fprintf(stderr, "Error: generate_fed: utterance %d was closed without an id\n", u);
+                goto out;
+            }
+            missing = 1;
+        }
+        if (!missing) break;
+        if (feed_call(&fd, feed_cb, feed_user, 1) != 0) goto out;
+    }
+    if (!(pr = (prompt_t *)calloc(nb, sizeof(prompt_t)))) goto out;
+    int max_p = 0;
+    for (int b = 0; b < nb; b++) {
+        /* build_prompt's layout of a template whose one content id is this id:
+         * role ids, id, and the five closing ids it never reads */
+        const int tpl[9] = {QWEN_TTS_TOKEN_IM_START, FEED_TOKEN_ASSISTANT, FEED_TOKEN_NEWLINE, fd.ids[b][0], 0, 0, 0, 0, 0};
+        int spk, lang;
+        lookup(ctx, speakers ? speakers[b] : NULL, languages ? languages[b] : NULL, &spk, &lang);
+        if (build_prompt(ctx, tpl, 9, spk, lang, iarm ? iarm->ids[b] : NULL, iarm ? iarm->n_ids[b] : 0, b, &pr[b]) != 0)
+            goto out;
+        if (pr[b].p_len > max_p) max_p = pr[b].p_len;
+    }
+    qtts_gen_params_t gp;
+    params_of(ctx, &gp);
+    if (qtts_dev_begin(dev, nb, max_tokens, max_p, &gp) != 0) goto out;
+    if (sarm)
+        for (int b = 0; b < nb; b++)
+            if (sampling_apply(dev, sarm, b, b) != 0) goto out;
+    for (int b = 0; b < nb; b++)
+        if (qtts_dev_prompt(dev, b, pr[b].text, pr[b].n_text, pr[b].plan, pr[b].nplan, pr[b].p_len, pr[b].n_trailing,
+                            pr[b].pad_row) != 0 ||
+            qtts_dev_text_open(dev, b) != 0)
+            goto out;
+    /* what came with the first ids goes to the device; later pushes go there directly */
+    for (int b = 0; b < nb; b++) {
+        const int n = fd.taken[b] - 1;
+        if ((n > 0 || fd.closed[b]) && qtts_dev_text_append(dev, b, fd.ids[b] + 1, n, fd.closed[b]) != 0) goto out;
+        fd.rows[b] = n + fd.closed[b];
+    }
+    fd.dev = dev;
+    if (qtts_dev_codec_mstream_begin(dev, nb, max_tokens, 0) != 0) goto out;
+    double t_prefill = now_ms();
+    if (qtts_dev_prefill(dev) != 0) goto out;
+    ctx->perf_prefill_ms = now_ms() - t_prefill;
+    stopped = (int *)calloc(nb, sizeof(int)); ngen = (int *)calloc(nb, sizeof(int));
+    sstep = (int *)calloc(nb, sizeof(int)); retired = (int *)calloc(nb, sizeof(int));
+    if (!stopped || !ngen || !sstep || !retired) goto out;
+    if (sstate_init(&ss, stream, nb, max_tokens, t_start, 0) != 0) goto out;
+    const double t_gen = now_ms();
+    int launched = 0, since_poll = 0;
+    for (;;) {
+        int live = 0, starved = 0, furthest = 0;
+        for (int b = 0; b < nb; b++) {
+            if (!fd.stopped[b] && fd.frames[b] >= max_tokens) {   /* the frame limit: stopped from the next launch on */
+                if (!retired[b] && qtts_dev_retire(dev, b) != 0) goto out;
+                retired[b] = fd.stopped[b] = 1;
+            }
+            live += !fd.stopped[b];
+        }
+        if (!live) break;
+        if (feed_call(&fd, feed_cb, feed_user, 0) != 0) goto out;
+        for (int b = 0; b < nb; b++) starved += feed_starved(&fd, b);
+        /* frame 0 is the lock-step head on the prefill's hidden states: every slot needs its row */
+        const int hold_all = launched == 0 ? starved > 0 : starved == live;
+        int polled = 0;
+        if (hold_all) {
+            /* nothing can advance: what is decoded goes out first, then the feed may block */
+            if (since_poll) polled = 1;
+        } else {
+            if (qtts_dev_frame(dev, launched) != 0) goto out;
+            for (int b = 0; b < nb; b++)
+                if (!fd.stopped[b] && !feed_starved(&fd, b)) fd.frames[b]++;
+            launched++;
+            since_poll++;
+            if (launched == 1) {
+                qtts_dev_poll(dev, NULL, NULL, NULL);
+                ctx->perf_first_frame_ms = now_ms() - t_start;
+            }
+            if (ctx->progress_cb) ctx->progress_cb(launched, max_tokens, ctx->progress_cb_userdata);
+            /* delivery: frame 0, then whenever a slot has chunk_frames new frames, and a slot's tail
+             * as soon as it reaches the limit (EOS mode also looks for stops every 8 launches) */
+            int tail = 0;
+            for (int b = 0; b < nb; b++) {
+                if (fd.frames[b] - ss.done[b] > furthest) furthest = fd.frames[b] - ss.done[b];
+                tail |= !fd.stopped[b] && fd.frames[b] >= max_tokens;
+            }
+            polled = launched == 1 || furthest >= stream->chunk || tail || (!fixed && since_poll >= 8);
+        }
+        if (polled) {
+            if (qtts_dev_poll(dev, stopped, ngen, sstep) != 0) goto out;
+            since_poll = 0;
+            for (int b = 0; b < nb; b++) {
+                /* the host's mirror of the gate against the device's counters
+                 * (an EOS: the frame that drew it stored nothing, and the host
+                 * went on counting until this poll) */
+                const int eos = stopped[b] && !retired[b];
+                if (eos ? ngen[b] > fd.frames[b] : ngen[b] != fd.frames[b]) {
+                    fprintf(stderr, "Error: generate_fed: utterance %d has %d frames on the device, %d by the host's "
+                                    "count of its text rows\n", b, ngen[b], fd.frames[b]);
+                    goto out;
+                }
+                if (eos) {
+                    fd.frames[b] = ngen[b];
+                    fd.stopped[b] = 1;
+                }
+            }
+            if (batch_flush(ctx, dev, &ss, ngen, 1) != 0) goto out;
+        }
+        if (hold_all) {
+            live = 0;
+            for (int b = 0; b < nb; b++) live += !fd.stopped[b];   /* (the poll may have seen the last EOS) */
+            if (live && feed_call(&fd, feed_cb, feed_user, 1) != 0) goto out;
+        }
+    }
+    if (qtts_dev_poll(dev, stopped, ngen, sstep) != 0) goto out;
+    if (batch_flush(ctx, dev, &ss, ngen, 1) != 0) goto out;
+    ctx->perf_talker_ms = now_ms() - t_gen - ss.t_stream;
+    ctx->perf_codec_ms = ss.t_stream;
+    ctx->perf_codec_tokens = ngen[0];
+    ctx->last_stop_reason = stopped[0] && !retired[0] ? 1 : 2;
+    ctx->last_stop_step = stopped[0] && !retired[0] ? sstep[0] : max_tokens;
+    free(ctx->last_codes);
+    ctx->last_codes = (int *)malloc((size_t)(ngen[0] > 0 ? ngen[0] : 1) * G * sizeof(int));
+    ctx->last_frames = ngen[0] > 0 && ctx->last_codes ? qtts_dev_get_codes(dev, 0, ctx->last_codes, ngen[0]) : 0;
+    if (ctx->last_frames < 0) ctx->last_frames = 0;
+    rc = 0;
+    for (int b = 0; b < nb; b++) {
+        audio[b] = ss.buf[b];
+        ss.buf[b] = NULL;
+        samples[b] = ss.done[b] * 1920;
+        if (ss.done[b] <= 0) rc = -1;
+    }
+    if (rc != 0)   /* a failed call returns nothing */
+        for (int b = 0; b < nb; b++) { free(audio[b]); audio[b] = NULL; samples[b] = 0; }
+    ctx->perf_total_ms = now_ms() - t_start;
+out:
+    sampling_free(sarm);
+    instruct_free(iarm);
+    free(stopped); free(ngen); free(sstep); free(retired);
+    sstate_free(&ss);
+    prompts_free(pr, nb);
+    feed_free(&fd);
+    return rc;
+}
+
+int qwen_tts_generate_fed_batch_stream(qwen_tts_ctx_t *ctx, int nb, const char *const *speakers,
+                                       const char *const *languages, int chunk_frames, qwen_tts_text_feed_cb feed_cb,
+                                       void *feed_userdata, qwen_tts_batch_audio_cb audio_cb, void *audio_userdata,
+                                       float **out_audio, int *out_samples) {
+    if (!ctx || !out_audio || !out_samples) return -1;
+    for (int i = 0; i < nb; i++) { out_audio[i] = NULL; out_samples[i] = 0; }   /* a failed call returns nothing */
+    if (nb < 1 || !feed_cb) {
+        fprintf(stderr, "Error: qwen_tts_generate_fed_batch_stream: %s\n", nb < 1 ? "no utterances" : "no feed callback");
+        force_disarm(ctx);
+        return -1;
+    }
+    if (batch_refused(ctx, "qwen_tts_generate_fed_batch_stream", nb)) return -1;
+    if (ctx->force) {
+        fprintf(stderr, "Error: qwen_tts_generate_fed_batch_stream: forced codes / taps are armed (not supported "
+                        "with incremental text; disarmed)\n");
+        force_disarm(ctx);
+        return -1;
+    }
+    const double t_start = now_ms();
+    stream_t st = {NULL, audio_userdata, chunk_frames > 0 ? chunk_frames : 1, 1, audio_cb};
+    ctx->perf_first_packet_ms = 0;
+    const int rc = run_fed(ctx, nb, speakers, languages, &st, feed_cb, feed_userdata, out_audio, out_samples, t_start);
+    if (rc == 0) log_totals(ctx, 1, 1, nb, out_samples);
+    return rc;
+}
+
+/* the single call is the nb = 1 case: the batch callback hands on to the plain one */
+typedef struct { qwen_tts_audio_cb cb; void *user; } fed_one_t;
+static void fed_one_cb(int utterance, const float *pcm, int n_samples, void *userdata) {
+    const fed_one_t *o = (const fed_one_t *)userdata;
+    (void)utterance;
+    if (o->cb) o->cb(pcm, n_samples, o->user);
+}
+
+float *qwen_tts_generate_fed_stream(qwen_tts_ctx_t *ctx, const char *speaker, const char *language, int chunk_frames,
+                                    qwen_tts_text_feed_cb feed_cb, void *feed_userdata, qwen_tts_audio_cb audio_cb,
+                                    void *audio_userdata, int *out_samples) {
+    if (!ctx || !out_samples) return NULL;
+    *out_samples = 0;
+    fed_one_t one = {audio_cb, audio_userdata};
+    float *audio = NULL;
+    int n = 0;
+    const char *spk[1] = {speaker}, *lang[1] = {language};
+    const int rc = qwen_tts_generate_fed_batch_stream(ctx, 1, spk, lang, chunk_frames, feed_cb, feed_userdata,
+                                                      fed_one_cb, &one, &audio, &n);
+    return one_result(rc, audio, n, out_samples);
+}
+
 int qwen_tts_codec_mstream_begin(qwen_tts_ctx_t *ctx, int n_streams, int max_frames) {
     if (!ctx || !ctx->hip) return -1;
     return qtts_dev_codec_mstream_begin((qtts_dev_t *)ctx->hip, n_streams, max_frames, 0);

@@ -27,6 +27,7 @@ PROGRESS_CB = C.CFUNCTYPE(None, C.c_int, C.c_int, C.c_void_p)
 QUEUE_NEXT_CB = C.CFUNCTYPE(C.c_int, C.c_void_p)
 AUDIO_CB = C.CFUNCTYPE(None, C.POINTER(C.c_float), C.c_int, C.c_void_p)
 BATCH_AUDIO_CB = C.CFUNCTYPE(None, C.c_int, C.POINTER(C.c_float), C.c_int, C.c_void_p)
+TEXT_FEED_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_void_p)   # qwen_tts_text_feed_cb(feed, wait, userdata)
 
 
 class Config(C.Structure):  # qwen_tts_config_t (include/qwen_tts.h)
@@ -129,9 +130,35 @@ EXPORTS = [
     "qwen_tts_set_utterance_instruct", "qwen_tts_instruct_prompt", "qtts_dev_prefix_cache",
     "qtts_dev_prefix_cache_bytes", "qtts_hip_prefix_hits", "qtts_hip_prefix_misses", "qtts_hip_prefill_rows",
     "qtts_dev_get_hidden",
+    "qwen_tts_feed_ids", "qwen_tts_feed_close", "qwen_tts_feed_state", "qwen_tts_generate_fed_stream",
+    "qwen_tts_generate_fed_batch_stream", "qtts_dev_text_open", "qtts_dev_text_append", "qtts_dev_get_trailing",
+    "qtts_dev_text_state", "qtts_hip_text_held_frames", "qtts_dev_text_append_ms",
 ]
 
 MAX_BATCH = 64   # QWEN_TTS_MAX_BATCH / QTTS_HIP_MAX_BATCH: lock-step slots per context
+
+
+class FeedHandle:
+    """The feed a text callback pushes into (qwen_tts_feed_t; valid inside the callback only)."""
+
+    def __init__(self, ptr):
+        self._p = C.c_void_p(ptr)
+
+    def push(self, utterance, ids):
+        """content ids of `utterance`, any number >= 1; 0, or -1 where the library refuses"""
+        a = np.ascontiguousarray(ids, np.int32)
+        return int(lib().qwen_tts_feed_ids(self._p, int(utterance), a.ctypes.data_as(_ip), int(a.size)))
+
+    def close(self, utterance):
+        """the utterance's text is over (the tts_eos row); 0 or -1"""
+        return int(lib().qwen_tts_feed_close(self._p, int(utterance)))
+
+    def state(self, utterance):
+        """(ids taken, frames launched, starved) or None for a bad index"""
+        t, f, s = C.c_int(0), C.c_int(0), C.c_int(0)
+        if lib().qwen_tts_feed_state(self._p, int(utterance), C.byref(t), C.byref(f), C.byref(s)) != 0:
+            return None
+        return t.value, f.value, bool(s.value)
 
 
 class BGemvDesc(C.Structure):
@@ -296,6 +323,32 @@ def lib():
     L.qwen_tts_codec_stream_begin.argtypes = [C.POINTER(Ctx), C.c_int]
     L.qwen_tts_codec_stream_push.argtypes = [C.POINTER(Ctx), _ip, C.c_int, _fp]
     # (an older build named by QTTS_LIB for a same-box A/B has no multi-stream entries; build() checks EXPORTS)
+    if hasattr(L, "qwen_tts_generate_fed_batch_stream"):   # (an older build named by QTTS_LIB has no fed entries)
+        L.qwen_tts_feed_ids.restype = C.c_int
+        L.qwen_tts_feed_ids.argtypes = [C.c_void_p, C.c_int, _ip, C.c_int]
+        L.qwen_tts_feed_close.restype = C.c_int
+        L.qwen_tts_feed_close.argtypes = [C.c_void_p, C.c_int]
+        L.qwen_tts_feed_state.restype = C.c_int
+        L.qwen_tts_feed_state.argtypes = [C.c_void_p, C.c_int, _ip, _ip, _ip]
+        L.qwen_tts_generate_fed_stream.restype = C.c_void_p
+        L.qwen_tts_generate_fed_stream.argtypes = [C.POINTER(Ctx), C.c_char_p, C.c_char_p, C.c_int, TEXT_FEED_CB,
+                                                   C.c_void_p, AUDIO_CB, C.c_void_p, _ip]
+        L.qwen_tts_generate_fed_batch_stream.restype = C.c_int
+        L.qwen_tts_generate_fed_batch_stream.argtypes = [C.POINTER(Ctx), C.c_int, C.POINTER(C.c_char_p),
+                                                         C.POINTER(C.c_char_p), C.c_int, TEXT_FEED_CB, C.c_void_p,
+                                                         BATCH_AUDIO_CB, C.c_void_p, C.POINTER(C.c_void_p), _ip]
+        L.qtts_dev_text_open.restype = C.c_int
+        L.qtts_dev_text_open.argtypes = [C.c_void_p, C.c_int]
+        L.qtts_dev_text_append.restype = C.c_int
+        L.qtts_dev_text_append.argtypes = [C.c_void_p, C.c_int, _ip, C.c_int, C.c_int]
+        L.qtts_dev_text_append_ms.restype = C.c_int
+        L.qtts_dev_text_append_ms.argtypes = [C.c_void_p, C.c_int, _ip, C.c_int, C.c_int, _fp]
+        L.qtts_dev_get_trailing.restype = C.c_int
+        L.qtts_dev_get_trailing.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, _fp]
+        L.qtts_dev_text_state.restype = C.c_int
+        L.qtts_dev_text_state.argtypes = [C.c_void_p, C.c_int, _ip, _ip, _ip]
+        L.qtts_hip_text_held_frames.restype = C.c_longlong
+        L.qtts_hip_text_held_frames.argtypes = []
     if hasattr(L, "qwen_tts_generate_batch_stream"):
         L.qwen_tts_generate_batch_stream.argtypes = [C.POINTER(Ctx), C.c_int, C.POINTER(C.c_char_p),
                                                      C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.c_int,
@@ -1043,6 +1096,65 @@ class QwenTTS:
         rc = lib().qwen_tts_generate_batch_stream(self.ctx, nb, tx, sp, lg, int(chunk_frames), cb, None, out, ns)
         self._last_nb = nb
         return rc, [_take_audio(out[i], ns[i]) for i in range(nb)]
+
+    def _feed_cb(self, feed):
+        """the C feed callback around a Python feed(handle, wait); an exception aborts the call"""
+        def _cb(fp, wait, u):
+            try:
+                rc = feed(FeedHandle(fp), int(wait))
+                return 0 if rc is None else int(rc)
+            except Exception as e:   # (ctypes would print and return 0: the loop must not go on)
+                self._feed_error = e
+                return -1
+        self._feed_error = None
+        return TEXT_FEED_CB(_cb)
+
+    def generate_fed_stream(self, feed, speaker=None, language=None, chunk_frames=4, on_chunk=None):
+        """Streaming generation that takes its content ids while it runs
+        (qwen_tts_generate_fed_stream).  feed(handle, wait) is called before every
+        frame launch (wait 0: push what is at hand) and when nothing can advance
+        (wait 1: push or close something); handle.push(0, ids), handle.close(0),
+        handle.state(0) -> (ids_taken, frames_done, starved).  Return None / 0 to
+        go on, < 0 to abort.  Returns the whole utterance, or None."""
+        n = C.c_int(0)
+
+        def _cb(p, k, u):
+            if on_chunk is not None:
+                on_chunk(np.ctypeslib.as_array(p, shape=(k,)).copy())
+        cb, fcb = AUDIO_CB(_cb), self._feed_cb(feed)
+        p = lib().qwen_tts_generate_fed_stream(self.ctx, speaker.encode() if speaker else None,
+                                               language.encode() if language else None, int(chunk_frames), fcb, None,
+                                               cb, None, C.byref(n))
+        self._last_nb = 1
+        if self._feed_error is not None:
+            raise self._feed_error
+        return _take_audio(p, n.value) if p else None
+
+    def generate_fed_batch_stream(self, nb, feed, speakers=None, languages=None, chunk_frames=4, on_chunk=None):
+        """nb fed utterances in lock-step frames (qwen_tts_generate_fed_batch_stream):
+        feed(handle, wait) as generate_fed_stream's with utterance indices 0..nb-1,
+        on_chunk(i, np.ndarray) per utterance.  Returns (rc, [audio])."""
+        n = max(int(nb), 1)
+        sp = (C.c_char_p * n)(*[(s.encode() if s else None) for s in (speakers or [None] * n)])
+        lg = (C.c_char_p * n)(*[(s.encode() if s else None) for s in (languages or [None] * n)])
+        out = (C.c_void_p * n)()
+        ns = (C.c_int * n)()
+
+        def _cb(i, p, k, u):
+            if on_chunk is not None:
+                on_chunk(int(i), np.ctypeslib.as_array(p, shape=(k,)).copy())
+        cb = BATCH_AUDIO_CB(_cb)
+        fcb = self._feed_cb(feed) if feed is not None else C.cast(None, TEXT_FEED_CB)
+        rc = lib().qwen_tts_generate_fed_batch_stream(self.ctx, int(nb), sp, lg, int(chunk_frames), fcb, None, cb, None,
+                                                      out, ns)
+        self._last_nb = n
+        if feed is not None and self._feed_error is not None:
+            raise self._feed_error
+        return rc, [(_take_audio(out[i], ns[i]) if out[i] else None) for i in range(min(n, int(nb)) if nb > 0 else 0)]
+
+    def text_held_frames(self):
+        """frames a live slot of a fed run was held, process-wide (qtts_hip_text_held_frames)"""
+        return int(lib().qtts_hip_text_held_frames())
 
     def codec_mstream_begin(self, n_streams, max_frames=4096):
         """(re)start n_streams independent exact codec streams; 0 or -1"""
