@@ -298,8 +298,8 @@ int qtts_dev_slot_params(qtts_dev_t *dev, int b, const qtts_slot_params_t *p);
  *   0, the text is open and the run a fed one, with frame graphs of its own
  *   (an unfed run captures exactly the graphs it always did; the next
  *   qtts_dev_begin ends the fed run).  -1 with a message: outside that window,
- *   forcing / taps armed, QTTS_HIP_TENGINE set, a prompt with other trailing
- *   rows.  In a fed run qtts_dev_refill, _move_slot and _set_rows return -1.
+ *   forcing / taps armed, a prompt with other trailing rows.  In a fed run
+ *   qtts_dev_refill, _move_slot and _set_rows return -1.
  * qtts_dev_text_append: n >= 0 content ids behind the slot's rows, through
  *   text_embedding -> fc1 + bias + SiLU -> fc2 + bias by ONE kernel path whose
  *   per-row summation order does not depend on how many ids share a launch
@@ -749,9 +749,6 @@ int qtts_hip_xgemm_func(float *out_dev, const float *x_dev, const float *alpha_d
 /* glibc-exact expf replica used by the sampler (for the libm cross-check test) */
 int qtts_hip_expf_glibc(float *out_dev, const float *in_dev, int n, void *stream);
 int qtts_hip_sync(void);
-/* Talker layers enqueued (or captured into a frame graph) on the persistent
- * one-launch layer (QTTS_HIP_TENGINE=1) since the library loaded. */
-long long qtts_hip_tengine_layers(void);
 /* Sub-talker pair passes enqueued (or captured into a frame graph) since the
  * library loaded: positions 0 and 1 run as one two-row pass at batch 1
  * (QTTS_HIP_ST_PAIR=0 at creation: the 16 single-row passes). */

@@ -1,5 +1,7 @@
 // qtts_runtime.hip - device model, weight layout in HBM, generation state,
-// frame HIP graphs and the C-ABI of include/qtts_hip.h.
+// frame HIP graphs and the qtts_dev_* C-ABI of include/qtts_hip.h but its codec
+// entries (qtts_rt_codec.hip); the kernel-level hooks are in qtts_rt_hooks.hip,
+// the context they share in qtts_dev.h.
 //
 // HBM layout (per device, one model, B slots):
 //   talker layer l:  wqkv [(NH+2KV)*HD, H] bf16   fused q|k|v rows
@@ -17,43 +19,9 @@
 // One frame (group-0 sample + 15 sub-talker groups + next embedding) is ONE
 // captured HIP graph; position / row / stop state lives in device memory so
 // the same graph replays every frame with no host round trip.
-#include <math.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include <algorithm>
-#include <map>
-#include <mutex>
-#include <set>
-#include <string>
-#include <atomic>
-#include <vector>
-
-#include "qtts_common.h"
-#include "qtts_kernels.h"
-#include "qtts_codec.h"
-#include "qtts_enc.h"
-#include "../../../include/qtts_hip.h"
-
-#define CK(x)                                                                                              \
-    do {                                                                                                   \
-        hipError_t e_ = (x);                                                                               \
-        if (e_ != hipSuccess) {                                                                            \
-            fprintf(stderr, "HIP error %s at %s:%d: %s\n", hipGetErrorName(e_), __FILE__, __LINE__, #x);   \
-            return -1;                                                                                     \
-        }                                                                                                  \
-    } while (0)
-#define CKI(x)                                                                                             \
-    do {                                                                                                   \
-        if ((x) != 0) return -1;                                                                           \
-    } while (0)
+#include "qtts_dev.h"
 
 namespace {
-
-struct Layer {
-    bf16_t *wqkv = nullptr, *wo = nullptr, *wgu = nullptr, *wdown = nullptr;
-    float *qn = nullptr, *kn = nullptr, *in = nullptr, *post = nullptr;
-};
 
 float host_bf16(uint16_t v) {
     uint32_t u = (uint32_t)v << 16;
@@ -73,229 +41,6 @@ float host_f16(uint16_t h) {
 }
 
 }  // namespace
-
-static constexpr int QTTS_MAX_SLOTS = 64;   // row counts with their own tail graph (qtts_dev_set_rows)
-
-struct qtts_dev {
-    qtts_dims_t d{};
-    int device = 0;
-    hipStream_t st = nullptr;
-    size_t wbytes = 0, sbytes = 0;
-    std::vector<void *> wallocs, sallocs;
-    // QTTS_HIP_ARENA=1: small buffers (<= QTTS_ARENA_SMALL) carved from
-    // 32 MB blocks (dalloc): one 2 MB-fragment mapping for every activation
-    // vector, norm weight and bias instead of one allocation each
-    unsigned char *war = nullptr, *sar = nullptr;
-    size_t war_off = 0, war_cap = 0, sar_off = 0, sar_cap = 0;
-    // talker
-    std::vector<Layer> tl, sl;
-    bf16_t *codec_emb = nullptr, *text_emb = nullptr, *fc1w = nullptr, *fc2w = nullptr, *head = nullptr;
-    float *fc1b = nullptr, *fc2b = nullptr, *tk_norm = nullptr;
-    // sub-talker
-    bf16_t *st_emb = nullptr, *lm = nullptr, *st_proj = nullptr;
-    float *st_projb = nullptr, *st_norm = nullptr;
-    // small_to_mtp_projection applied once at load to every embedding row a
-    // sub-talker pass g >= 1 can consume (fp32): [V][Hs] of the talker codec
-    // embedding (pass 1) and [G-1][Vs][Hs] of the sub-talker ones (passes 2..)
-    float *codec_ptab = nullptr, *st_ptab = nullptr;
-    // the sub-talker's layer-0 q|k|v of every row a pass g >= 1 can consume
-    // (its input is a table row chosen by the previous code alone): fp32
-    // [V + (G-2) Vs][QKVs], pass 1 rows first, then pass g at V + (g-2) Vs;
-    // computed once at load by the per-frame GEMV itself (bit-identical)
-    float *qkv0_tab = nullptr;
-    // codec
-    CodecModel codec;
-    // voice-clone encoders (speaker x-vector, 12 Hz reference codes)
-    EncModel enc;
-    // rope
-    float *rope_cos = nullptr, *rope_sin = nullptr, *rope_cos_s = nullptr, *rope_sin_s = nullptr;
-    int rope_max = 0;
-    std::set<std::string> got;
-    // state
-    int nb = 0, nrun = 0, max_frames = 0, S = 0, p_cap = 0, tr_cap = 0, rows_cap = 0;  // nb: allocated slots (strides), nrun: rows launched
-    float *x_tk = nullptr, *qkv = nullptr, *att = nullptr, *hbuf = nullptr, *logits = nullptr, *tk_hid = nullptr;
-    float *x_st2 = nullptr, *opart = nullptr;   // attn_o: second residual buffer, per-head O partials
-    // batch split-K (nb >= 2): second talker residual, O / down partials; the
-    // talker's final residual = tk_xfin + sum of tk_npend partials at tk_pend
-    float *x_tk2 = nullptr, *bpo = nullptr, *bpd = nullptr;
-    float *ppart = nullptr;      // prefill split-K partials (<= 16 rows, kz <= 4)
-    float *tk_xfin = nullptr;
-    const float *tk_pend = nullptr;
-    int tk_npend = 0;
-    bool bsplit = true;      // QTTS_HIP_BSPLIT=0: batch O / down projections without split-K
-    int bself_min = 9;       // batch split-K producers reduce their own partials from this many rows up
-    int bkz_max = 0;         // QTTS_HIP_BKZ_MAX: cap on the batch split-K columns (0: 2 up to 8 rows, else 4)
-    int bkz_wide = 1;        // QTTS_HIP_BKZ_WIDE=0: above 8 rows, no extra split-K columns for > 2048-wide slices (bsplit_kz); 2: from 2 rows, up to 4 columns
-    float *x_st = nullptr, *qkv_s = nullptr, *att_s = nullptr, *h_s = nullptr, *logits_s = nullptr;
-    float *kc = nullptr, *vc = nullptr, *kcs = nullptr, *vcs = nullptr;
-    // element type of the talker cache kc / vc, [L][B][S][KV*HD]: 0 fp32, 1 bf16
-    // (uint16 rows behind the same pointers; kv_layer() takes the slices).
-    // kv_dtype is what the allocated state holds, kv_want what the next
-    // qtts_dev_begin allocates (qtts_dev_set_kv_dtype, QTTS_HIP_KV at creation);
-    // the sub-talker cache kcs / vcs is always fp32
-    int kv_dtype = 0, kv_want = 0;
-    bool te_kv_said = false;   // the "engine not used with bf16 KV" line went out (once per model)
-    // the last talker pass left its last layer's attention output in `att`
-    // (false: batch 1 with the merge deferred to the O projection, or the engine)
-    bool att_own = false;
-    int *codes = nullptr, *counts = nullptr, *n_gen = nullptr, *stopped = nullptr, *cur_row = nullptr;
-    // [B] the id each slot's last draw produced (every sampler's out_tok): the
-    // next sub-talker pass reads its input row by it -- one dependent load
-    // where codes[b][cur_row[b]][g-1] took two (cur_row, then the code)
-    int *last_tok = nullptr;
-    int *stop_step = nullptr, *kv_len = nullptr, *n_trailing = nullptr;
-    float *att_part = nullptr;   // split-K decode attention partials (talker)
-    int *att_cnt = nullptr, att_nsplit = 0;
-    int *btick = nullptr;        // self-reducing batch split-K tickets [QTTS_GM_TICKS] (zeroed)
-    uint32_t *rng = nullptr, *st_rng = nullptr;
-    float *trailing = nullptr, *prefill = nullptr, *pad_emb = nullptr;
-    // prefill / prompt scratch
-    float *px = nullptr, *pqkv = nullptr, *patt = nullptr, *ph = nullptr, *pt1 = nullptr, *pproj = nullptr;
-    int *prow_b = nullptr, *ppos = nullptr, *psrc = nullptr, *pids = nullptr, *pplan = nullptr, *plast = nullptr;
-    int ids_cap = 0;
-    // voice-clone prompt inputs of the next qtts_dev_prompt (qtts_dev_prompt_ref)
-    int *pref = nullptr;
-    float *pspk = nullptr;
-    int pref_cap = 0, n_pref = 0, has_spk = 0;
-    std::vector<int> p_len_h, n_tr_h;
-    // The instruct prefix cache (DESIGN.md "Instruct and the prefix cache"):
-    // pfx_ids[b] = the text ids of slot b's kind-2 plan rows (its prompt rows
-    // [0, n), qtts_dev_prompt); an entry = those rows' K and V of all layers,
-    // [2][L][n][KV*HD] in the element type it was saved from, keyed by the ids
-    // and that type.  Outside the decode state (sallocs): entries survive
-    // qtts_dev_begin and a re-allocation; a change of the KV element type drops
-    // them (alloc_state), qtts_dev_destroy drops all.
-    struct PrefixEntry {
-        std::vector<int> ids;
-        int dtype = 0;
-        void *buf = nullptr;
-        size_t bytes = 0;
-        unsigned long long used = 0;   // LRU stamp
-    };
-    std::vector<std::vector<int>> pfx_ids;
-    std::vector<PrefixEntry> pfx;
-    int pfx_cap = 16;                  // QTTS_HIP_PREFIX_CACHE entries (0: off), qtts_dev_prefix_cache
-    unsigned long long pfx_clock = 0;
-    qtts_gen_params_t par{};
-    bool have_par = false;
-    hipGraphExec_t g0 = nullptr, gN = nullptr;
-    // work queue, tail of a run: the talker-first frame graph over the first
-    // nrun < nb slots (qtts_dev_set_rows), captured on first use
-    hipGraphExec_t gNr[QTTS_MAX_SLOTS + 1] = {};
-    // what g0 / gN hold: -1 nothing valid, 0 no graphs (QTTS_HIP_NO_GRAPH),
-    // 1 the plain frame, 2 the frame with the forced sampler (f_armed), 3 / 4
-    // the frame with the per-slot sampler, fast-only / general (sp_armed);
-    // every arming and every qtts_dev_begin that drops one resets it to -1, so
-    // a graph of one kind is never replayed for another
-    int graph_key = -1;
-    // teacher forcing, the free-draw record and logit taps (qtts_dev_force /
-    // qtts_dev_tap): allocated by the first arming after a qtts_dev_begin,
-    // freed by the next begin -- a plain run holds none of it.  forced / drawn
-    // are laid out like `codes`; f_phase: 0 no run begun, 1 begun and no frame
-    // launched yet (arming is valid), 2 frames launched
-    int *f_forced = nullptr, *f_drawn = nullptr, *f_taps = nullptr, *f_tap_meta = nullptr;
-    float *f_tap_logits = nullptr;
-    int f_tap_ld = 0, f_ntaps = 0, f_phase = 0;
-    int f_run_frames = 0;   // max_frames of the last qtts_dev_begin (the state may hold more)
-    bool f_armed = false;
-    size_t f_bytes = 0;
-    // per-slot sampling parameters (qtts_dev_slot_params): one SampSlotRow per
-    // slot on the device with its host mirror, allocated by the first call
-    // after a qtts_dev_begin and freed by the next begin -- a plain run holds
-    // none of it.  While armed the frames hold the per-slot samplers (graph_key
-    // 3: the fast-only family; 4: the general kernel, from the first row of the
-    // run that is not fast-path eligible in both modes on -- sp_general never
-    // goes back within a run)
-    SampSlotRow *sp_tab = nullptr;
-    std::vector<SampSlotRow> sp_host;
-    bool sp_armed = false, sp_general = false;
-    // incremental text input (qtts_dev_text_open / _append, k_textfeed.hip): a
-    // run is fed from its first qtts_dev_text_open until the next
-    // qtts_dev_begin; its frames are graphs of their own (graph_key + 8) whose
-    // first node computes `gate` and whose stop readers take it (stop_rd).  The
-    // buffers live with the state, allocated by the first fed run on it:
-    // tf_open / tf_gate / tf_held [B], tf_eos [B][H] each slot's tts_eos row,
-    // tf_xsave [B][H] the talker input rows of a frame, tf_t1 [16][TH] fc1's
-    // output of an append.  tf_rows / tf_open_h: the host's mirror of
-    // n_trailing / text_open; tf_held_h: held counters as of the last poll
-    bool fed = false;
-    int *tf_open = nullptr, *tf_gate = nullptr, *tf_held = nullptr;
-    float *tf_eos = nullptr, *tf_xsave = nullptr, *tf_t1 = nullptr;
-    std::vector<int> tf_rows, tf_open_h, tf_held_h;
-    // EOS-mode lagged poll: the sampler mirrors each slot's stop into pinned
-    // host memory; an event after every frame lets the host wait for frame
-    // s - 1 while frame s is already queued (qtts_dev_frame_done)
-    int *hstop = nullptr;
-    int hstop_cap = 0;
-    hipEvent_t fev[2] = {nullptr, nullptr};
-    // codec overlapped with the decode (qtts_dev_codec_async_*): its own stream,
-    // ordered after the frames it decodes by an event; output stays on device
-    hipStream_t cst = nullptr;
-    hipEvent_t cev = nullptr;
-    float *cwav = nullptr;
-    size_t cwav_cap = 0;
-    // host codes staged for qtts_dev_codec_stream_push_host / _prime (grown on demand)
-    int *push_codes = nullptr;
-    size_t push_cap = 0;
-    bool prime_pending = false;   // a qtts_dev_codec_stream_prime push runs on cst (cev marks its end)
-    float *pwav = nullptr;        // the prime's discarded audio (never the codec_async output cwav)
-    size_t pwav_cap = 0;
-    // the live codec snapshots saved on this context (qtts_dev_codec_mstream_save):
-    // destroy releases their device memory
-    std::vector<qtts_codec_snapshot_t *> snaps;
-    // a batch's codec passes side by side (qtts_dev_codec_multi): lanes 1.. with
-    // their own scratch and stream (lane 0 is `codec`), the waveforms and the
-    // host-given codes staged on the device
-    std::vector<CodecModel *> clanes;
-    std::vector<hipStream_t> clane_st;
-    float *mwav = nullptr;
-    size_t mwav_cap = 0;
-    int *mcodes = nullptr;
-    size_t mcodes_cap = 0;
-    // per-kernel profiling of one eager frame (qtts_dev_profile_frame)
-    struct Prof { int kind; double bytes; hipEvent_t a, b; const char *name; };
-    std::vector<Prof> prof;
-    bool profiling = false;
-    bool attn_o = true;      // QTTS_HIP_ATTN_O=0: sub-talker attention and O projection as two kernels
-    bool tab0b = true;       // QTTS_HIP_TAB0B=0: batch layer-0 q|k|v by GEMV instead of the table
-    bool st_pair = true;     // QTTS_HIP_ST_PAIR=0: batch-1 sub-talker passes 0 and 1 as two single-row chains
-    // QTTS_HIP_L2PF=<mask>: which edges of the batch-1 sub-talker chain carry
-    // the next-launch weight prefetch (0 none): 1 q|k|v -> attention + O,
-    // 2 attention + O -> gate|up, 4 gate|up -> down, 8 down -> next q|k|v or
-    // head, 16 head -> the next pass's first launch (two launches ahead);
-    // (the same for the batch chain on k_gemvb measured 2 % slower at batch 8
-    // and 16, profiles/r04g_ab_l2pf_batch.txt, and was removed)
-    int l2pf = 31;
-    int l2pf_tk = 0;         // QTTS_HIP_L2PF_TK bits (batch-1 talker, non-temporal): 1 q|k|v -> O's W_o, 2 O -> gate|up
-    unsigned *pf_sink = nullptr;
-    bool attn_defer = true;  // QTTS_HIP_ATTN_DEFER=0: batch-1 talker attention merges its own splits
-    int attn_lpk = 0;        // QTTS_HIP_ATTN_LPK=4|8|16 (HD 128 split size), latched here: sizes att_part
-    // QTTS_HIP_GM_DBG=<layer>: phase stamps of that talker layer's batch GEMVs
-    // (q|k|v, O, gate|up, down), printed by qtts_dev_get_codes
-    int gm_dbg_layer = -1;
-    unsigned long long *gm_dbg = nullptr;
-    // QTTS_HIP_TENGINE=1: the batch-1 1.7B talker layer as one persistent
-    // launch (k_tengine.hip); its {tag, value} granules, [epoch, error]
-    int tengine = 0;          // 1 register form, 2 / 3 ring engine (slots in flight 1 / 2)
-    unsigned long long *te_g = nullptr;
-    int *te_ctl = nullptr;
-    float *pinv = nullptr;   // per-row 1/rms scratch of the matrix-core projections
-    int pinv_cap = 0;
-    float *mpart = nullptr;   // split-K partials of the matrix-core projections (k_mgemm_reduce)
-    size_t mpart_elems = 0;
-    // the prefill GEMM's activation planes [3][rows][K] bf16 (k_pgemm.hip)
-    unsigned short *pplanes = nullptr;
-    size_t pplanes_elems = 0;
-    bool pgemm = true;       // QTTS_HIP_PGEMM=0: the prefill on k_mgemm (rounds 1-5)
-
-    int QKV() const { return (d.NH + 2 * d.KV) * d.HD; }
-    int QKVs() const { return (d.NHs + 2 * d.KVs) * d.HDs; }
-    size_t kv_esz() const { return kv_dtype == 1 ? 2 : 4; }
-    // layer l's slice [B][S][KV*HD] of a talker cache (kc or vc)
-    float *kv_layer(float *c, int l) const {
-        return reinterpret_cast<float *>(reinterpret_cast<char *>(c) + (size_t)l * nb * S * d.KV * d.HD * kv_esz());
-    }
-};
 
 // ----------------------------------------------------------------- helpers
 static constexpr size_t QTTS_ARENA_SMALL = (size_t)1 << 20, QTTS_ARENA_BLOCK = (size_t)32 << 20;
@@ -573,14 +318,6 @@ extern "C" qtts_dev_t *qtts_dev_create(const qtts_dims_t *dims, int device) {
     dv->attn_o = !(ao && !atoi(ao));
     const char *pg = getenv("QTTS_HIP_PGEMM");
     dv->pgemm = !(pg && !atoi(pg));
-    const char *te = getenv("QTTS_HIP_TENGINE");
-    if (te && atoi(te)) {
-        // every workgroup of the launch must be resident at once: one per CU, 256 of them
-        int dev = 0, ncu = 0;
-        if (hipGetDevice(&dev) == hipSuccess &&
-            hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && ncu >= 256)
-            dv->tengine = std::min(3, std::max(1, atoi(te)));
-    }
     // QTTS_HIP_KV=bf16|fp32: the talker KV cache's element type (default fp32)
     const char *kvd = getenv("QTTS_HIP_KV");
     if (kvd && *kvd) {
@@ -604,27 +341,6 @@ extern "C" qtts_dev_t *qtts_dev_create(const qtts_dims_t *dims, int device) {
     dv->enc.st = dv->st;
     dv->enc.device = device;
     return dv;
-}
-
-// A codec snapshot as the C-ABI hands it out: the codec's snapshot and the
-// context that saved it.  Every live one is in g_snaps, so a pointer that was
-// freed (or never was a snapshot) is refused by look-up, never dereferenced.
-// A snapshot outlives its context as a dead one (owner NULL, no device
-// memory) until it is freed.
-struct qtts_codec_snapshot {
-    CodecSnapshot s;
-    qtts_dev *owner = nullptr;
-};
-static std::mutex g_snaps_mu;
-static std::set<const qtts_codec_snapshot_t *> g_snaps;
-
-static void snapshots_orphan(qtts_dev *dv) {
-    std::lock_guard<std::mutex> lk(g_snaps_mu);
-    for (qtts_codec_snapshot_t *p : dv->snaps) {
-        codec_snapshot_release(&p->s);
-        p->owner = nullptr;
-    }
-    dv->snaps.clear();
 }
 
 // drops the least recently used prefix entries until at most `keep` are left
@@ -825,8 +541,6 @@ extern "C" int qtts_dev_finalize(qtts_dev_t *dv) {
 }
 
 // ----------------------------------------------------------------- voice-clone encoders
-static int join_prime(qtts_dev *dv);
-
 extern "C" int qtts_dev_enc_config(qtts_dev_t *dv, const qtts_enc_dims_t *dims) {
     if (!dv || !dims) return -1;
     return enc_set_dims(&dv->enc, dims);
@@ -859,8 +573,6 @@ static int alloc_state(qtts_dev *dv, int nb, int max_frames, int max_prefill) {
     free_state(dv);
     if (dv->kv_dtype != dv->kv_want) prefix_evict(dv, 0);   // (entries hold the other element type)
     dv->kv_dtype = dv->kv_want;
-    if (dv->kv_dtype == 1 && dv->tengine && !dv->te_kv_said && (dv->te_kv_said = true))
-        fprintf(stderr, "qtts: the persistent talker engine (QTTS_HIP_TENGINE) has no bf16 KV form: not used\n");
     dv->nb = nb;
     dv->nrun = nb;
     dv->max_frames = max_frames;
@@ -955,12 +667,6 @@ static int alloc_state(qtts_dev *dv, int nb, int max_frames, int max_prefill) {
         CK(hipMemsetAsync(dv->att_cnt, 0, B * kvmax * sizeof(int), dv->st));
         A(pf_sink, unsigned, 1);
         A(btick, int, QTTS_GM_TICKS);
-        if (dv->tengine) {
-            A(te_g, unsigned long long, QTTS_TE_GRANULES);
-            CK(hipMemsetAsync(dv->te_g, 0, QTTS_TE_GRANULES * 8, dv->st));
-            A(te_ctl, int, 2);
-            CK(hipMemsetAsync(dv->te_ctl, 0, 2 * sizeof(int), dv->st));
-        }
         CK(hipMemsetAsync(dv->btick, 0, QTTS_GM_TICKS * sizeof(int), dv->st));
         if (dv->gm_dbg_layer >= 0) {
             A(gm_dbg, unsigned long long, 4 * 2048 * 8);
@@ -1153,7 +859,7 @@ static int qkv_attn(qtts_dev *dv, const GemvArgs &a, const AttnArgs &t, int kind
     ProfScope ps(dv, PK_ATTN, 0);
     return qtts_attention(t, dv->st);
 }
-static GemvArgs gv(const bf16_t *W, int R, int C, const float *x, int ldx, float *y, int ldy, int nb, int epi) {
+GemvArgs gv(const bf16_t *W, int R, int C, const float *x, int ldx, float *y, int ldy, int nb, int epi) {
     GemvArgs a;
     a.W = W; a.R = R; a.C = C; a.x = x; a.ldx = ldx; a.y = y; a.ldy = ldy; a.nb = nb; a.epi = epi;
     return a;
@@ -1287,45 +993,6 @@ static L2Prefetch pf_attn_o(const qtts_dev *dv, const bf16_t *Wo, int R, int NH,
 // the flag a frame's stop readers take: a fed run's gate (k_textfeed.hip), else `stopped`
 static const int *stop_rd(const qtts_dev *dv) { return dv->fed ? dv->tf_gate : dv->stopped; }
 
-// the talker layers at batch 1 as persistent launches (k_tengine.hip), each
-// bit-identical to the launch-per-op layer below
-static bool tengine_ok(qtts_dev *dv, int kzo, int kzd) {
-    const qtts_dims_t &d = dv->d;
-    // (the launch's 32-key splits need nsplit * 32 >= S partial slots; any S)
-    return dv->tengine && dv->te_g && dv->kv_dtype == 0 && dv->nrun == 1 && !kzo && !kzd && dv->attn_defer &&
-           qtts_tlayer_dims_ok(d.H, d.NH, d.KV, d.HD, d.I) && dv->S > 16 && dv->att_nsplit * 32 >= dv->S;
-}
-// layer launches enqueued (or captured) on the engine since the library
-// loaded: a test's proof that the engine, not the launch-per-op layer, ran
-static std::atomic<long long> g_tengine_layers{0};
-extern "C" long long qtts_hip_tengine_layers(void) { return g_tengine_layers.load(); }
-static int talker_layers_te(qtts_dev *dv) {
-    const qtts_dims_t &d = dv->d;
-    const int NBA = dv->nb, KVD = d.KV * d.HD;
-    for (int l = 0; l < d.L; ++l) {
-        Layer &ly = dv->tl[l];
-        TLayerArgs a;
-        a.x_in = dv->x_tk; a.x_out = dv->x_tk;
-        a.wqkv = ly.wqkv; a.wo = ly.wo; a.wgu = ly.wgu; a.wdown = ly.wdown;
-        a.in_norm = ly.in; a.post_norm = ly.post; a.qn_w = ly.qn; a.kn_w = ly.kn;
-        a.rope_cos = dv->rope_cos; a.rope_sin = dv->rope_sin;
-        a.kc = dv->kv_layer(dv->kc, l); a.vc = dv->kv_layer(dv->vc, l);   // (fp32 only: tengine_ok)
-        a.pos = dv->kv_len; a.skip = stop_rd(dv); a.eps = d.eps;
-        a.part = dv->att_part; a.cnt = dv->att_cnt; a.nsplit = dv->att_nsplit;
-        a.g_qkv = dv->te_g; a.g_att = dv->te_g + 4096; a.g_x = a.g_att + 2048; a.g_h = a.g_x + 2048;
-        a.epoch = dv->te_ctl; a.err = dv->te_ctl + 1;
-        a.layer = l; a.last_layer = l == d.L - 1;
-        if (dv->gm_dbg && (l == dv->gm_dbg_layer || l == dv->gm_dbg_layer + 1))
-            a.dbg = dv->gm_dbg + (size_t)(l - dv->gm_dbg_layer) * 256 * 16;
-        ProfScope ps(dv, PK_GEMV_TALKER, 2.0 * ((double)dv->QKV() * d.H + (double)d.H * d.NH * d.HD + 3.0 * d.I * d.H));
-        CKI(qtts_tlayer(a, dv->st, dv->tengine));
-        g_tengine_layers.fetch_add(1);
-    }
-    dv->tk_xfin = dv->x_tk; dv->tk_pend = nullptr; dv->tk_npend = 0;
-    dv->att_own = false;
-    return 0;
-}
-
 static int talker_layers(qtts_dev *dv) {
     const qtts_dims_t &d = dv->d;
     const int nb = dv->nrun, NBA = dv->nb, QKV = dv->QKV(), AD = d.NH * d.HD, KVD = d.KV * d.HD;
@@ -1333,7 +1000,6 @@ static int talker_layers(qtts_dev *dv) {
     // (the talker's O without split-K at batch 8: 142.0 / 142.6 vs 140.7 / 142.1
     // audio-s/s, within noise; its down without: 135.9 / 135.6, gpurun_out/tkz)
     const int kzo = bsplit_kz(dv, d.H, AD), kzd = bsplit_kz(dv, d.H, d.I);
-    if (tengine_ok(dv, kzo, kzd)) return talker_layers_te(dv);
     float *xa = dv->x_tk, *xb = dv->x_tk2;
     const float *pend = nullptr;
     int npend = 0;
@@ -2195,10 +1861,6 @@ extern "C" int qtts_dev_text_open(qtts_dev_t *dv, int b) {
         fprintf(stderr, "qtts_dev_text_open refused: forced codes / taps are armed\n");
         return -1;
     }
-    if (dv->tengine) {
-        fprintf(stderr, "qtts_dev_text_open refused: QTTS_HIP_TENGINE has no gate (unset it for fed runs)\n");
-        return -1;
-    }
     if (dv->n_tr_h[b] != 1) {
         fprintf(stderr, "qtts_dev_text_open: slot %d's prompt has %d trailing rows (the tts_eos row alone expected)\n",
                 b, dv->n_tr_h[b]);
@@ -2440,39 +2102,7 @@ extern "C" int qtts_dev_get_codes(qtts_dev_t *dv, int b, int *host_codes, int ma
     int n = 0;
     CK(hipMemcpyAsync(&n, dv->n_gen + b, 4, hipMemcpyDeviceToHost, dv->st));
     CK(hipStreamSynchronize(dv->st));
-    if (dv->te_ctl) {   // the persistent talker layer gave up waiting on a hand-off: its codes are garbage
-        int ctl[2] = {0, 0};
-        CK(hipMemcpy(ctl, dv->te_ctl, sizeof(ctl), hipMemcpyDeviceToHost));
-        if (ctl[1]) {
-            fprintf(stderr, "qtts: talker layer engine hand-off timed out (code %d, epoch %d)\n", ctl[1], ctl[0]);
-            return -1;
-        }
-    }
-    if (dv->gm_dbg && dv->te_g) {   // QTTS_HIP_GM_DBG + engine: k_tlayer phase stamps of two layers, last frame
-        std::vector<unsigned long long> h(2 * 256 * 16);
-        CK(hipMemcpy(h.data(), dv->gm_dbg, h.size() * 8, hipMemcpyDeviceToHost));
-        static const char *ph[15] = {"start", "x staged", "qkv dot", "qkv put", "head got", "attn done", "att staged",
-                                     "O dot", "x' got", "x' staged", "gu dot", "h staged", "down dot", "ld issued",
-                                     "ld landed"};
-        unsigned long long t00 = ~0ull;
-        for (int i = 0; i < 256; ++i) if (h[i * 16] && h[i * 16] < t00) t00 = h[i * 16];
-        for (int g = 0; g < 2; ++g) {
-            const unsigned long long *b = h.data() + (size_t)g * 256 * 16;
-            unsigned long long t0 = ~0ull;
-            for (int i = 0; i < 256; ++i) if (b[i * 16] && b[i * 16] < t0) t0 = b[i * 16];
-            if (t0 == ~0ull) continue;
-            fprintf(stderr, "[te_dbg] layer +%d starts %7.2f us after layer +0\n", g, (t0 - t00) * 0.01);
-            for (int k = 0; k < 15; ++k) {
-                std::vector<double> v;
-                for (int i = 0; i < 256; ++i) if (b[i * 16 + k]) v.push_back((b[i * 16 + k] - t0) * 0.01);
-                if (v.empty()) continue;
-                std::sort(v.begin(), v.end());
-                fprintf(stderr, "[te_dbg] +%d %-10s n %3zu  min %6.2f  med %6.2f  max %6.2f us\n", g, ph[k], v.size(), v[0],
-                        v[v.size() / 2], v.back());
-            }
-        }
-        hipMemsetAsync(dv->gm_dbg, 0, h.size() * 8, dv->st);
-    } else if (dv->gm_dbg) {   // QTTS_HIP_GM_DBG: phase spans of the chosen talker layer's GEMVs, last frame
+    if (dv->gm_dbg) {   // QTTS_HIP_GM_DBG: phase spans of the chosen talker layer's GEMVs, last frame
         std::vector<unsigned long long> h(4 * 2048 * 8);
         CK(hipMemcpy(h.data(), dv->gm_dbg, h.size() * 8, hipMemcpyDeviceToHost));
         static const char *op[4] = {"q|k|v", "O / -", "gate|up", "down"};
@@ -2622,397 +2252,6 @@ extern "C" int qtts_dev_get_tap(qtts_dev_t *dv, int i, float *logits_host, int m
         CK(hipMemcpy(logits_host, dv->f_tap_logits + (size_t)i * dv->f_tap_ld, (size_t)n * sizeof(float),
                      hipMemcpyDeviceToHost));
     return m[0];
-}
-
-extern "C" float *qtts_dev_codec_slot(qtts_dev_t *dv, int b, int T, int *out_samples) {
-    if (out_samples) *out_samples = 0;
-    if (!dv || b < 0 || b >= dv->nb || T < 1) return nullptr;
-    hipSetDevice(dv->device);
-    if (join_prime(dv)) return nullptr;   // the prime shares the codec scratch and split-K workspace
-    return codec_decode(&dv->codec, dv->codes + (size_t)b * (dv->max_frames + 1) * dv->d.G, T, out_samples);
-}
-
-extern "C" int qtts_dev_codec_timing(qtts_dev_t *dv, int on) {
-    if (!dv) return -1;
-    dv->codec.timing = on != 0;
-    return 0;
-}
-
-extern "C" int qtts_dev_codec_stage_ms(const qtts_dev_t *dv, float *ms) {
-    if (!dv || !ms || !dv->codec.timed) return -1;
-    for (int i = 0; i < 5; ++i) ms[i] = dv->codec.stage_ms[i];
-    return 0;
-}
-
-// ----------------------------------------------------------------- streaming codec (exact, incremental)
-// a pending prime (below) orders every later use of the stream state after it
-static int join_prime(qtts_dev *dv) {
-    if (!dv->prime_pending) return 0;
-    dv->prime_pending = false;
-    CK(hipStreamWaitEvent(dv->st, dv->cev, 0));
-    return 0;
-}
-
-static int ensure_cst(qtts_dev *dv) {
-    if (dv->cst) return 0;
-    int lo = 0, hi = 0;
-    CK(hipDeviceGetStreamPriorityRange(&lo, &hi));
-    CK(hipStreamCreateWithPriority(&dv->cst, hipStreamNonBlocking, lo));   // lowest: the decode goes first
-    CK(hipEventCreateWithFlags(&dv->cev, hipEventDisableTiming));
-    return 0;
-}
-
-static int ensure_push_codes(qtts_dev *dv, size_t n) {
-    if (n <= dv->push_cap) return 0;
-    CK(hipDeviceSynchronize());
-    if (dv->push_codes) CK(hipFree(dv->push_codes));
-    dv->push_codes = nullptr;
-    dv->push_cap = 0;
-    const size_t cap = n < 4096 ? 4096 : n;
-    CK(hipMalloc(&dv->push_codes, cap * 4));
-    dv->push_cap = cap;
-    return 0;
-}
-
-extern "C" int qtts_dev_codec_stream_begin(qtts_dev_t *dv, int max_frames) {
-    return qtts_dev_codec_stream_begin_ex(dv, max_frames, 0);
-}
-
-extern "C" int qtts_dev_codec_stream_begin_ex(qtts_dev_t *dv, int max_frames, int chunk_frames) {
-    if (!dv || max_frames < 1) return -1;
-    hipSetDevice(dv->device);
-    CKI(join_prime(dv));
-    CK(hipStreamSynchronize(dv->st));
-    return codec_stream_begin(&dv->codec, max_frames, chunk_frames);
-}
-
-// Push T host frames through the stream on the second stream (cst) without
-// waiting: their audio is dropped (device scratch), the carried state is what
-// later pushes continue from.  The voice-clone reference frames go this way
-// while the prefill runs on the context stream (SURVEY.md 8f N1 + N2).
-extern "C" int qtts_dev_codec_stream_prime(qtts_dev_t *dv, const int *codes, int T) {
-    if (!dv || !codes || T < 1) return -1;
-    hipSetDevice(dv->device);
-    CKI(join_prime(dv));
-    CKI(ensure_cst(dv));
-    CKI(ensure_push_codes(dv, (size_t)T * dv->d.cq));
-    const size_t need = (size_t)T * 1920;
-    if (need > dv->pwav_cap) {
-        CK(hipStreamSynchronize(dv->cst));
-        if (dv->pwav) CK(hipFree(dv->pwav));
-        dv->pwav = nullptr;
-        dv->pwav_cap = 0;
-        CK(hipMalloc(&dv->pwav, need * 4));
-        dv->pwav_cap = need;
-    }
-    CK(hipEventRecord(dv->cev, dv->st));          // after the begin's resets on st
-    CK(hipStreamWaitEvent(dv->cst, dv->cev, 0));
-    CK(hipMemcpyAsync(dv->push_codes, codes, (size_t)T * dv->d.cq * 4, hipMemcpyHostToDevice, dv->cst));
-    dv->codec.st = dv->cst;
-    const int n = codec_stream_push_to(&dv->codec, dv->push_codes, dv->d.cq, T, dv->pwav, false);
-    dv->codec.st = dv->st;
-    if (n < 0) return -1;
-    CK(hipEventRecord(dv->cev, dv->cst));
-    dv->prime_pending = true;
-    return 0;
-}
-
-extern "C" int qtts_dev_codec_stream_push_slot(qtts_dev_t *dv, int b, int frame0, int T, float *host_out) {
-    if (!dv || b < 0 || b >= dv->nb || T < 1 || frame0 < 0 || frame0 + T > dv->max_frames + 1) return -1;
-    hipSetDevice(dv->device);
-    CKI(join_prime(dv));
-    const int *codes = dv->codes + (size_t)b * (dv->max_frames + 1) * dv->d.G + (size_t)frame0 * dv->d.G;
-    return codec_stream_push(&dv->codec, codes, dv->d.G, T, host_out);
-}
-
-extern "C" int qtts_dev_codec_stream_push_host(qtts_dev_t *dv, const int *codes, int T, float *host_out) {
-    if (!dv || !codes || T < 1) return -1;
-    hipSetDevice(dv->device);
-    CKI(join_prime(dv));
-    const size_t n = (size_t)T * dv->d.cq;
-    CKI(ensure_push_codes(dv, n));   // persistent staging buffer: no allocation per push
-    // ordered on the codec's stream before the push reads it; the synchronous
-    // push waits for the stream before returning, so the host buffer may be reused
-    CK(hipMemcpyAsync(dv->push_codes, codes, n * 4, hipMemcpyHostToDevice, dv->codec.st));
-    return codec_stream_push(&dv->codec, dv->push_codes, dv->d.cq, T, host_out);
-}
-
-// ----------------------------------------------------------------- multi-stream codec (n exact streams, one pass)
-extern "C" int qtts_dev_codec_mstream_begin(qtts_dev_t *dv, int n_streams, int max_frames, int chunk_frames) {
-    if (!dv) return -1;
-    hipSetDevice(dv->device);
-    CKI(join_prime(dv));
-    CK(hipStreamSynchronize(dv->st));
-    return codec_mstream_begin(&dv->codec, n_streams, max_frames, chunk_frames);
-}
-
-// One push of n streams, behind the seven entries below.  The codes come from
-// the slots' generated frames on the device or from host codes staged on the
-// codec's stream; every stream advances by T frames or stream i by counts[i]
-// (ragged: one launch sequence per pass whatever the counts, DESIGN.md 7,
-// "Ragged pushes"); `any`: the streams may stand at independent positions (the
-// work queue's slots: a refilled slot's stream restarts at 0 beside its
-// neighbours; a ragged push always may).  A prime is the ragged host push on
-// the second stream (cst), its audio dropped, not waited for: the carried state
-// is what later pushes continue from.  The reference frames of a voice-clone
-// batch go this way while the prefill runs on the context stream, as
-// qtts_dev_codec_stream_prime's do for one utterance; every later multi-stream
-// call joins it by event.
-enum MsSrc { MS_SLOTS, MS_SLOTS_AT, MS_HOST };
-struct MsPush {
-    MsSrc src;
-    const int *slots;      // MS_SLOTS / MS_SLOTS_AT: slot slots[i]'s frames from
-    int frame0;            //   MS_SLOTS: frame0, the same for every stream
-    const int *frame0s;    //   MS_SLOTS_AT: frame0s[i]
-    const int *codes;      // MS_HOST: [n][ld][16], stream i's first T / counts[i] rows
-    int ld;
-    bool ragged;
-    const int *counts;
-    int T;
-    bool any;
-    bool prime;
-};
-
-static int mstream_push(qtts_dev_t *dv, int n, const int *streams, const MsPush &p, float *const *host_out) {
-    if (!dv) return -1;
-    hipSetDevice(dv->device);
-    const int cap = dv->max_frames + 1;   // frames a slot holds
-    // every refusal before anything is enqueued
-    if (p.ragged ? codec_mstream_check_ragged(&dv->codec, n, streams, p.counts, p.src == MS_HOST ? p.ld : cap)
-                 : codec_mstream_check(&dv->codec, n, streams, p.T, p.any))
-        return -1;
-    if (p.src == MS_HOST) {
-        if (!p.codes || (!p.prime && !host_out)) return -1;
-    } else if (p.src == MS_SLOTS) {
-        if (!p.slots || !host_out || p.frame0 < 0 || p.frame0 + p.T > cap) {
-            fprintf(stderr, "qtts codec mstream: frames [%d, %d) are outside the slots' %d\n", p.frame0,
-                    p.frame0 + p.T, cap);
-            return -1;
-        }
-    } else if (!p.slots || !p.frame0s || !host_out) {
-        return -1;
-    }
-    const size_t per = (size_t)(p.ragged ? p.ld : p.T) * dv->d.cq;   // MS_HOST: the staged codes of one stream
-    long long off[64];   // (the check bounds n by the begin's 1..64 streams)
-    for (int i = 0; i < n; ++i) {
-        if (p.ragged && !p.prime && !host_out[i]) return -1;
-        if (p.src == MS_HOST) {
-            off[i] = (long long)(i * per);
-            continue;
-        }
-        if (p.slots[i] < 0 || p.slots[i] >= dv->nb) {
-            fprintf(stderr, "qtts codec mstream: slot %d out of range (0..%d)\n", p.slots[i], dv->nb - 1);
-            return -1;
-        }
-        const int f0 = p.src == MS_SLOTS ? p.frame0 : p.frame0s[i], c = p.ragged ? p.counts[i] : p.T;
-        if (f0 < 0 || f0 + c > cap) {   // (MS_SLOTS: refused above for all)
-            fprintf(stderr, "qtts codec mstream: frames [%d, %d) are outside slot %d's %d\n", f0, f0 + c, p.slots[i],
-                    cap);
-            return -1;
-        }
-        off[i] = ((long long)p.slots[i] * cap + f0) * dv->d.G;
-    }
-    CKI(join_prime(dv));
-    const int *base = dv->codes;
-    int ldc = dv->d.G;
-    if (p.src == MS_HOST) {
-        if (p.prime) CKI(ensure_cst(dv));
-        CKI(ensure_push_codes(dv, per * n));   // persistent staging buffer: no allocation per push
-        if (p.prime) {
-            CK(hipEventRecord(dv->cev, dv->st));          // after the begin's resets on st
-            CK(hipStreamWaitEvent(dv->cst, dv->cev, 0));
-        }
-        // ordered on the codec's stream before the push reads it
-        CK(hipMemcpyAsync(dv->push_codes, p.codes, per * n * 4, hipMemcpyHostToDevice, p.prime ? dv->cst : dv->codec.st));
-        base = dv->push_codes;
-        ldc = dv->d.cq;
-    }
-    if (p.prime) dv->codec.st = dv->cst;
-    const int r = p.ragged ? codec_mstream_push_ragged(&dv->codec, n, streams, base, off, ldc, p.counts,
-                                                       p.prime ? nullptr : host_out)
-                           : codec_mstream_push(&dv->codec, n, streams, base, off, ldc, p.T, host_out, p.any);
-    if (!p.prime) return r;
-    dv->codec.st = dv->st;
-    if (r < 0) return -1;
-    CK(hipEventRecord(dv->cev, dv->cst));
-    dv->prime_pending = true;
-    return 0;
-}
-
-extern "C" int qtts_dev_codec_mstream_push_slots(qtts_dev_t *dv, int n, const int *streams, const int *slots,
-                                                 int frame0, int T, float *const *host_out) {
-    MsPush p{};
-    p.src = MS_SLOTS; p.slots = slots; p.frame0 = frame0; p.T = T;
-    return mstream_push(dv, n, streams, p, host_out);
-}
-
-extern "C" int qtts_dev_codec_mstream_push_host(qtts_dev_t *dv, int n, const int *streams, const int *codes, int T,
-                                                float *const *host_out) {
-    MsPush p{};
-    p.src = MS_HOST; p.codes = codes; p.T = T;
-    return mstream_push(dv, n, streams, p, host_out);
-}
-
-extern "C" int qtts_dev_codec_mstream_push_slots_at(qtts_dev_t *dv, int n, const int *streams, const int *slots,
-                                                    const int *frame0, int T, float *const *host_out) {
-    MsPush p{};
-    p.src = MS_SLOTS_AT; p.slots = slots; p.frame0s = frame0; p.T = T; p.any = true;
-    return mstream_push(dv, n, streams, p, host_out);
-}
-
-extern "C" int qtts_dev_codec_mstream_push_host_any(qtts_dev_t *dv, int n, const int *streams, const int *codes, int T,
-                                                    float *const *host_out) {
-    MsPush p{};
-    p.src = MS_HOST; p.codes = codes; p.T = T; p.any = true;
-    return mstream_push(dv, n, streams, p, host_out);
-}
-
-// counts[i] * 1920 samples reach host_out[i]; returns the largest count times 1920
-extern "C" int qtts_dev_codec_mstream_push_host_ragged(qtts_dev_t *dv, int n, const int *streams, const int *codes,
-                                                       const int *counts, int ld_frames, float *const *host_out) {
-    MsPush p{};
-    p.src = MS_HOST; p.codes = codes; p.ld = ld_frames; p.ragged = true; p.counts = counts;
-    return mstream_push(dv, n, streams, p, host_out);
-}
-
-extern "C" int qtts_dev_codec_mstream_push_slots_ragged(qtts_dev_t *dv, int n, const int *streams, const int *slots,
-                                                        const int *frame0, const int *count,
-                                                        float *const *host_out) {
-    MsPush p{};
-    p.src = MS_SLOTS_AT; p.slots = slots; p.frame0s = frame0; p.ragged = true; p.counts = count;
-    return mstream_push(dv, n, streams, p, host_out);
-}
-
-extern "C" int qtts_dev_codec_mstream_prime(qtts_dev_t *dv, int n, const int *streams, const int *codes,
-                                            const int *counts, int ld_frames) {
-    MsPush p{};
-    p.src = MS_HOST; p.codes = codes; p.ld = ld_frames; p.ragged = true; p.counts = counts; p.prime = true;
-    return mstream_push(dv, n, streams, p, nullptr);
-}
-
-extern "C" int qtts_dev_codec_mstream_reset(qtts_dev_t *dv, int stream) {
-    if (!dv) return -1;
-    hipSetDevice(dv->device);
-    CKI(join_prime(dv));   // a pending prime owns the histories until joined
-    return codec_mstream_reset(&dv->codec, stream);
-}
-
-extern "C" int qtts_dev_codec_mstream_pos(qtts_dev_t *dv, int stream) {
-    if (!dv) return -1;
-    return codec_mstream_pos(&dv->codec, stream);
-}
-
-// One stream's carried state saved and restored ("Snapshots").
-// Both are one launch on the context stream after a pending prime is joined,
-// and wait for nothing on the host.
-extern "C" qtts_codec_snapshot_t *qtts_dev_codec_mstream_save(qtts_dev_t *dv, int stream) {
-    if (!dv) return nullptr;
-    hipSetDevice(dv->device);
-    if (join_prime(dv)) return nullptr;
-    qtts_codec_snapshot_t *p = new qtts_codec_snapshot_t();
-    if (codec_mstream_save(&dv->codec, stream, &p->s)) {
-        delete p;
-        return nullptr;
-    }
-    p->owner = dv;
-    std::lock_guard<std::mutex> lk(g_snaps_mu);
-    g_snaps.insert(p);
-    dv->snaps.push_back(p);
-    return p;
-}
-
-extern "C" int qtts_dev_codec_mstream_restore(qtts_dev_t *dv, int stream, const qtts_codec_snapshot_t *snap) {
-    if (!dv) return -1;
-    {
-        std::lock_guard<std::mutex> lk(g_snaps_mu);
-        if (!snap || !g_snaps.count(snap)) {
-            fprintf(stderr, "qtts codec mstream: restore takes a live snapshot (got %s)\n",
-                    snap ? "a freed one" : "NULL");
-            return -1;
-        }
-        if (snap->owner != dv) {
-            fprintf(stderr, "qtts codec mstream: restore: the snapshot belongs to %s\n",
-                    snap->owner ? "another context" : "a context that was freed");
-            return -1;
-        }
-    }
-    hipSetDevice(dv->device);
-    CKI(join_prime(dv));
-    return codec_mstream_restore(&dv->codec, stream, &snap->s);
-}
-
-extern "C" void qtts_dev_codec_snapshot_free(qtts_codec_snapshot_t *snap) {
-    std::lock_guard<std::mutex> lk(g_snaps_mu);
-    if (!snap || !g_snaps.count(snap)) return;
-    g_snaps.erase(snap);
-    if (qtts_dev *dv = snap->owner) {
-        hipSetDevice(dv->device);
-        hipStreamSynchronize(dv->st);   // a restore that reads it may still be queued
-        if (dv->cst) hipStreamSynchronize(dv->cst);
-        dv->snaps.erase(std::remove(dv->snaps.begin(), dv->snaps.end(), snap), dv->snaps.end());
-        codec_snapshot_release(&snap->s);
-    }
-    delete snap;
-}
-
-extern "C" int qtts_dev_codec_snapshot_pos(const qtts_codec_snapshot_t *snap) {
-    std::lock_guard<std::mutex> lk(g_snaps_mu);
-    if (!snap || !g_snaps.count(snap) || !snap->owner) return -1;
-    return snap->s.pos0;
-}
-
-extern "C" long long qtts_dev_codec_snapshot_bytes(const qtts_codec_snapshot_t *snap) {
-    std::lock_guard<std::mutex> lk(g_snaps_mu);
-    if (!snap || !g_snaps.count(snap) || !snap->owner) return -1;
-    return (long long)snap->s.elems * 4;
-}
-
-// ----------------------------------------------------------------- codec overlapped with the decode
-// The exact streaming decode (codec_stream_*), run on a second stream while
-// the frame graphs continue on the context stream: each push waits (event)
-// for the frames already enqueued, decodes them into a device waveform, and
-// nothing is waited for on the host until qtts_dev_codec_async_end.
-extern "C" int qtts_dev_codec_async_begin(qtts_dev_t *dv, int max_frames) {
-    if (!dv || max_frames < 1) return -1;
-    hipSetDevice(dv->device);
-    CKI(join_prime(dv));
-    CKI(ensure_cst(dv));
-    const size_t need = (size_t)max_frames * 1920;
-    if (need > dv->cwav_cap) {
-        CK(hipStreamSynchronize(dv->cst));
-        if (dv->cwav) CK(hipFree(dv->cwav));
-        dv->cwav = nullptr;
-        CK(hipMalloc(&dv->cwav, need * 4));
-        dv->cwav_cap = need;
-    }
-    CK(hipStreamSynchronize(dv->st));   // the stream state is shared with the synchronous paths
-    dv->codec.st = dv->cst;
-    const int rc = codec_stream_begin(&dv->codec, max_frames);
-    dv->codec.st = dv->st;
-    return rc;
-}
-
-extern "C" int qtts_dev_codec_async_push(qtts_dev_t *dv, int b, int frame0, int T) {
-    if (!dv || !dv->cst || b < 0 || b >= dv->nb || T < 1 || frame0 < 0 || frame0 + T > dv->max_frames + 1 ||
-        (size_t)(frame0 + T) * 1920 > dv->cwav_cap)
-        return -1;
-    hipSetDevice(dv->device);
-    CK(hipEventRecord(dv->cev, dv->st));
-    CK(hipStreamWaitEvent(dv->cst, dv->cev, 0));
-    const int *codes = dv->codes + (size_t)b * (dv->max_frames + 1) * dv->d.G + (size_t)frame0 * dv->d.G;
-    dv->codec.st = dv->cst;
-    const int n = codec_stream_push_to(&dv->codec, codes, dv->d.G, T, dv->cwav + (size_t)frame0 * 1920, false);
-    dv->codec.st = dv->st;
-    return n;
-}
-
-extern "C" int qtts_dev_codec_async_end(qtts_dev_t *dv, float *host_out, int frames) {
-    if (!dv || !dv->cst || frames < 0 || (size_t)frames * 1920 > dv->cwav_cap) return -1;
-    hipSetDevice(dv->device);
-    if (frames > 0)
-        CK(hipMemcpyAsync(host_out, dv->cwav, (size_t)frames * 1920 * 4, hipMemcpyDeviceToHost, dv->cst));
-    CK(hipStreamSynchronize(dv->cst));
-    return frames * 1920;
 }
 
 // ----------------------------------------------------------------- per-slot sampling parameters
@@ -3167,436 +2406,6 @@ extern "C" int qtts_dev_subtalker_host(qtts_dev_t *dv, const float *hidden, int 
     CKI(rc);
     CK(hipMemcpyAsync(out_codes, dv->codes, (size_t)d.G * 4, hipMemcpyDeviceToHost, dv->st));
     CK(hipStreamSynchronize(dv->st));
-    return 0;
-}
-
-extern "C" float *qtts_dev_codec_decode_host(qtts_dev_t *dv, const int *codes, int T, int *out_samples) {
-    if (out_samples) *out_samples = 0;
-    if (!dv || T < 1) return nullptr;
-    hipSetDevice(dv->device);
-    if (join_prime(dv)) return nullptr;
-    int *dc = nullptr;
-    if (hipMalloc(&dc, (size_t)T * dv->d.cq * 4) != hipSuccess) return nullptr;
-    float *r = nullptr;
-    if (hipMemcpy(dc, codes, (size_t)T * dv->d.cq * 4, hipMemcpyHostToDevice) == hipSuccess)
-        r = codec_decode(&dv->codec, dc, T, out_samples);
-    hipFree(dc);
-    return r;
-}
-
-// Several utterances' codec passes at once (a batch's slots, run_batch): job
-// i decodes host_codes[i] (T[i] frames, [T][cq] time-major) when given, else
-// slot slot[i]'s first T[i] generated frames.  QTTS_HIP_CODEC_LANES (default
-// 8, fewer when the extra lanes' scratch would pass 16 GB) passes run side by
-// side (codec_decode_many); 1 decodes them one after another with
-// codec_decode.  audio[i] is malloc'd host memory.  Measured (1.7B, 128
-// frames, profiles/r05lm_ab_codec_lanes.txt): a batch of 8's codec 73.4 ->
-// 60.7 ms, of 16 146.8 -> 120.0 ms (the passes are mostly conv throughput).
-extern "C" int qtts_dev_codec_multi(qtts_dev_t *dv, int n, const int *const *host_codes, const int *slot, const int *T,
-                                    float **audio, int *samples) {
-    if (!dv || n < 1 || !T || !audio || !samples) return -1;
-    for (int i = 0; i < n; ++i) {
-        audio[i] = nullptr;
-        samples[i] = 0;
-        const bool host = host_codes && host_codes[i];
-        if (T[i] < 1 || (!host && (!slot || slot[i] < 0 || slot[i] >= dv->nb || T[i] > dv->max_frames + 1)))
-            return -1;
-    }
-    hipSetDevice(dv->device);
-    CKI(join_prime(dv));
-    const int cq = dv->d.cq;
-    // host codes staged once for every job
-    size_t nh = 0;
-    for (int i = 0; i < n; ++i)
-        if (host_codes && host_codes[i]) nh += (size_t)T[i] * cq;
-    if (nh > dv->mcodes_cap) {
-        CK(hipDeviceSynchronize());
-        if (dv->mcodes) CK(hipFree(dv->mcodes));
-        dv->mcodes = nullptr;
-        dv->mcodes_cap = 0;
-        CK(hipMalloc(&dv->mcodes, nh * 4));
-        dv->mcodes_cap = nh;
-    }
-    std::vector<const int *> dcodes(n);
-    size_t ho = 0;
-    for (int i = 0; i < n; ++i) {
-        if (host_codes && host_codes[i]) {
-            CK(hipMemcpyAsync(dv->mcodes + ho, host_codes[i], (size_t)T[i] * cq * 4, hipMemcpyHostToDevice, dv->st));
-            dcodes[i] = dv->mcodes + ho;
-            ho += (size_t)T[i] * cq;
-        } else {
-            dcodes[i] = dv->codes + (size_t)slot[i] * (dv->max_frames + 1) * dv->d.G;
-        }
-    }
-    const char *e = getenv("QTTS_HIP_CODEC_LANES");
-    int nl = e ? atoi(e) : 8;
-    if (nl < 1) nl = 1;
-    if (nl > 16) nl = 16;
-    if (nl > n) nl = n;
-    // the extra lanes' scratch within 16 GB (a 128-frame decode state is ~0.4 GB,
-    // a 4096-frame one ~12 GB: long EOS utterances decode on fewer lanes)
-    int tmax = 1;
-    for (int i = 0; i < n; ++i) tmax = T[i] > tmax ? T[i] : tmax;
-    const size_t per_lane = codec_state_bytes(&dv->codec, tmax);
-    while (nl > 1 && (size_t)(nl - 1) * per_lane > ((size_t)16 << 30)) --nl;
-    auto fail = [&]() {
-        for (int i = 0; i < n; ++i) {
-            free(audio[i]);
-            audio[i] = nullptr;
-            samples[i] = 0;
-        }
-        return -1;
-    };
-    if (nl == 1) {
-        for (int i = 0; i < n; ++i) {
-            audio[i] = codec_decode(&dv->codec, dcodes[i], T[i], &samples[i]);
-            if (!audio[i]) return fail();
-        }
-        return 0;
-    }
-    while ((int)dv->clanes.size() < nl - 1) {
-        hipStream_t st = nullptr;
-        CK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-        dv->clane_st.push_back(st);
-        dv->clanes.push_back(codec_lane_new(&dv->codec, st));
-    }
-    std::vector<CodecModel *> lanes(nl, nullptr);
-    for (int k = 1; k < nl; ++k) lanes[k] = dv->clanes[k - 1];
-    // one hop of samples per frame: the decoder's total upsampling (2 x 2 x 8 x
-    // 5 x 4 x 3 = 1920 for the released codec), exactly codec_decode's L / T
-    const size_t hop = (size_t)dv->d.ratios[0] * dv->d.ratios[1] * dv->d.rates[0] * dv->d.rates[1] *
-                       dv->d.rates[2] * dv->d.rates[3];
-    std::vector<size_t> off(n);
-    size_t tot = 0;
-    for (int i = 0; i < n; ++i) {
-        off[i] = tot;
-        tot += (size_t)T[i] * hop;
-    }
-    if (tot > dv->mwav_cap) {
-        CK(hipDeviceSynchronize());
-        if (dv->mwav) CK(hipFree(dv->mwav));
-        dv->mwav = nullptr;
-        dv->mwav_cap = 0;
-        CK(hipMalloc(&dv->mwav, tot * 4));
-        dv->mwav_cap = tot;
-    }
-    std::vector<int> ns(n, 0);
-    if (codec_decode_many(&dv->codec, lanes.data(), nl, n, dcodes.data(), T, dv->mwav, off.data(), ns.data()))
-        return fail();
-    for (int i = 0; i < n; ++i) {
-        if ((size_t)ns[i] != (size_t)T[i] * hop) return fail();
-        audio[i] = (float *)malloc((size_t)ns[i] * sizeof(float));
-        if (!audio[i] ||
-            hipMemcpy(audio[i], dv->mwav + off[i], (size_t)ns[i] * 4, hipMemcpyDeviceToHost) != hipSuccess)
-            return fail();
-        samples[i] = ns[i];
-    }
-    return 0;
-}
-
-// ----------------------------------------------------------------- kernel-level C-ABI
-extern "C" int qtts_hip_device_count(void) {
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess) return 0;
-    return n;
-}
-
-extern "C" int qtts_hip_sync(void) { return hipDeviceSynchronize() == hipSuccess ? 0 : -1; }
-
-// batch >= 2 goes to the matrix-core kernel (as prefill does), else the GEMV
-static int matvec_any(const GemvArgs &a, hipStream_t st) {
-    static float *inv = nullptr;   // per-row 1/rms scratch of this test-level entry
-    if (a.nb >= 2) {
-        if (!inv && hipMalloc(&inv, 64 * sizeof(float)) != hipSuccess) return -1;
-        const int rc = qtts_mgemm(a, inv, st);
-        if (rc != 1) return rc;
-    }
-    return qtts_gemv(a, st);
-}
-
-extern "C" int qtts_hip_matvec_bf16(float *out, const uint16_t *A, const float *x, int rows, int cols, int batch,
-                                    void *stream) {
-    GemvArgs a = gv(A, rows, cols, x, cols, out, rows, batch, EPI_STORE);
-    return matvec_any(a, (hipStream_t)stream);
-}
-
-extern "C" int qtts_hip_rmsnorm_matvec_bf16(float *out, const uint16_t *A, const float *x, const float *w, float eps,
-                                            int rows, int cols, int batch, void *stream) {
-    GemvArgs a = gv(A, rows, cols, x, cols, out, rows, batch, EPI_STORE);
-    a.norm_w = w; a.eps = eps;
-    return matvec_any(a, (hipStream_t)stream);
-}
-
-// the decode dispatcher itself (qtts_gemv): batch 1 -> k_gemvw / k_gemv1;
-// 2..16 -> the batch GEMV's plan (qtts_bgemv: k_gemvb, else k_gemvm, on the
-// matrix cores) where it covers the shape, else k_gemv; 17..64 -> k_gemvx or -1
-extern "C" int qtts_hip_decode_matvec_bf16(float *out, const uint16_t *A, const float *x, const float *w, float eps,
-                                           int rows, int cols, int batch, void *stream) {
-    GemvArgs a = gv(A, rows, cols, x, cols, out, rows, batch, EPI_STORE);
-    a.norm_w = w; a.eps = eps;
-    return qtts_gemv(a, (hipStream_t)stream);
-}
-
-extern "C" int qtts_hip_resident_matvec_bf16(float *out, const uint16_t *A, const float *x, const float *w, float eps,
-                                             int rows, int cols, int epi, void *stream) {
-    if (epi != EPI_STORE && epi != EPI_RESID && epi != EPI_SWIGLU) return -1;
-    GemvArgs a = gv(A, rows, cols, x, cols, out, epi == EPI_SWIGLU ? rows / 2 : rows, 1, epi);
-    a.norm_w = w; a.eps = eps; a.nt = 0;
-    return qtts_gemv(a, (hipStream_t)stream);
-}
-
-extern "C" int qtts_hip_sample_top_k(int *out, const float *logits, int vocab, int top_k, float top_p, float temp,
-                                     uint32_t *rng_bits, int batch, void *stream) {
-    SampArgs s;
-    s.logits = logits; s.ld = vocab; s.n = vocab; s.nb = batch; s.top_k = top_k; s.top_p = top_p; s.temp = temp;
-    s.mode = 0; s.st_rng = rng_bits; s.out_tok = out;
-    return qtts_sample(s, (hipStream_t)stream);
-}
-
-// qtts_hip_sample_top_k with one parameter set per row: the table is built
-// here, the launch family is the one a run with these rows would capture
-extern "C" int qtts_hip_sample_top_k_rows(int *out, const float *logits, int vocab, const int *top_k,
-                                          const float *top_p, const float *temp, uint32_t *rng_bits, int batch,
-                                          void *stream) {
-    if (!out || !logits || !top_k || !top_p || !temp || !rng_bits || batch < 1 || batch > 65535) return -1;
-    std::vector<SampSlotRow> h((size_t)batch);
-    bool all_fast = true;
-    for (int b = 0; b < batch; ++b) {
-        if (!std::isfinite(top_p[b]) || !std::isfinite(temp[b]) || top_p[b] <= 0.0f) {
-            fprintf(stderr, "qtts_hip_sample_top_k_rows: row %d: top_p %g, temperature %g\n", b, top_p[b], temp[b]);
-            return -1;
-        }
-        SampSlotRow &r = h[b];
-        r.temp = r.st_temp = temp[b]; r.top_p = r.st_top_p = top_p[b]; r.top_k = r.st_top_k = top_k[b];
-        r.rep = 1.0f; r.seed_bits = 0;
-        all_fast = all_fast && qtts_sample_row_fast(r, 0, vocab);
-    }
-    hipStream_t st = (hipStream_t)stream;
-    SampSlotRow *t = nullptr;
-    CK(hipMalloc((void **)&t, h.size() * sizeof(SampSlotRow)));
-    int rc = hipMemcpyAsync(t, h.data(), h.size() * sizeof(SampSlotRow), hipMemcpyHostToDevice, st) == hipSuccess ? 0 : -1;
-    if (!rc) {
-        SampArgs s;
-        s.logits = logits; s.ld = vocab; s.n = vocab; s.nb = batch;
-        s.mode = 0; s.st_rng = rng_bits; s.out_tok = out;
-        rc = qtts_sample_slots(s, t, all_fast, st);
-    }
-    if (hipStreamSynchronize(st) != hipSuccess) rc = -1;   // (h and t live until the launch finished)
-    hipFree(t);
-    return rc;
-}
-
-// every rows-long device index vector inside [0, lim) (the kernels index by
-// them unchecked)
-static int attn_ints_ok(const char *who, const char *what, const int *dev, int rows, int lim, hipStream_t st) {
-    std::vector<int> h(rows);
-    CK(hipMemcpyAsync(h.data(), dev, (size_t)rows * 4, hipMemcpyDeviceToHost, st));
-    CK(hipStreamSynchronize(st));
-    for (int v : h)
-        if (v < 0 || v >= lim) { fprintf(stderr, "%s: %s %d outside [0, %d)\n", who, what, v, lim); return -1; }
-    return 0;
-}
-
-static bool attn_dims_ok(int NH, int KV, int HD, int S, int rows, int kv_dtype) {
-    return NH >= 1 && KV >= 1 && HD >= 1 && S >= 1 && rows >= 1 && rows <= 65535 && (kv_dtype == 0 || kv_dtype == 1);
-}
-
-// The talker's decode attention on its own, launched as a talker layer
-// launches it (mode 0, the kernel's own split merge); waits for the result.
-// skip: AttnArgs::skip, per row (may be NULL).
-extern "C" int qtts_hip_attn_decode_ex(float *out, const float *qkv, void *kc, void *vc, const float *qn_w,
-                                       const float *kn_w, const float *rope_cos, const float *rope_sin,
-                                       const int *pos, int NH, int KV, int HD, int S, int rows, float eps,
-                                       int kv_dtype, const int *skip, void *stream) {
-    if (!out || !qkv || !kc || !vc || !qn_w || !kn_w || !rope_cos || !rope_sin || !pos) return -1;
-    if (!attn_dims_ok(NH, KV, HD, S, rows, kv_dtype)) return -1;
-    hipStream_t st = (hipStream_t)stream;
-    CKI(attn_ints_ok("qtts_hip_attn_decode", "position", pos, rows, S, st));
-    AttnArgs t;
-    t.mode = 0; t.qkv = qkv; t.ld_qkv = (NH + 2 * KV) * HD; t.qn_w = qn_w; t.kn_w = kn_w; t.eps = eps;
-    t.rope_cos = rope_cos; t.rope_sin = rope_sin;
-    t.kc = (float *)kc; t.vc = (float *)vc; t.S = S; t.kv_dtype = kv_dtype;
-    t.pos = pos; t.NH = NH; t.KV = KV; t.HD = HD; t.out = out; t.ld_out = NH * HD; t.nrows = rows;
-    t.skip = skip;
-    const int gph = NH % KV ? 1 : NH / KV, ch = qtts_attn_keys_per_split(HD, false, 0);
-    t.nsplit = (S + ch - 1) / ch;
-    const size_t part_n = (size_t)rows * KV * t.nsplit * (gph * HD + 2 * gph), cnt_n = (size_t)rows * KV;
-    void *scratch = nullptr;
-    CK(hipMalloc(&scratch, part_n * 4 + cnt_n * 4));
-    t.part = (float *)scratch;
-    t.cnt = (int *)(t.part + part_n);
-    int rc = hipMemsetAsync(scratch, 0, part_n * 4 + cnt_n * 4, st) == hipSuccess ? 0 : -1;
-    if (!rc) rc = qtts_attention(t, st);
-    if (hipStreamSynchronize(st) != hipSuccess) rc = -1;
-    hipFree(scratch);
-    return rc;
-}
-
-extern "C" int qtts_hip_attn_decode(float *out, const float *qkv, void *kc, void *vc, const float *qn_w,
-                                    const float *kn_w, const float *rope_cos, const float *rope_sin, const int *pos,
-                                    int NH, int KV, int HD, int S, int rows, float eps, int kv_dtype, void *stream) {
-    return qtts_hip_attn_decode_ex(out, qkv, kc, vc, qn_w, kn_w, rope_cos, rope_sin, pos, NH, KV, HD, S, rows, eps,
-                                   kv_dtype, nullptr, stream);
-}
-
-// The cached attention (mode 1) on its own: prep 1 as prefill_rows issues it
-// (qtts_qk_prep, then qtts_attention, on fused q|k|v rows), prep 0 as the
-// codec transformer and the encoder do (q ready, caches filled, a window).
-extern "C" int qtts_hip_attn_cached(float *out, float *q, int ld_q, void *kc, void *vc, const float *qn_w,
-                                    const float *kn_w, const float *rope_cos, const float *rope_sin,
-                                    const int *row_b, const int *pos, int NH, int KV, int HD, int S, int slots,
-                                    int rows, float eps, int win, int kv_dtype, int prep, void *stream) {
-    if (!out || !q || !kc || !vc || !row_b || !pos) return -1;
-    if (prep != 0 && prep != 1) return -1;
-    if (prep && (!qn_w || !kn_w || !rope_cos || !rope_sin)) return -1;
-    if (!attn_dims_ok(NH, KV, HD, S, rows, kv_dtype) || slots < 1 || win < 0) return -1;
-    if (HD < 8 || HD > 128 || (HD & 7) || NH % KV || !qtts_attn_head_ok(HD)) return -1;   // (qtts_attention's own rule, before the cache writes)
-    if (ld_q < (prep ? NH + 2 * KV : NH) * HD) return -1;
-    if (kv_dtype == 1 && win != 0) return -1;   // (as qtts_attention: no bf16 window path)
-    hipStream_t st = (hipStream_t)stream;
-    CKI(attn_ints_ok("qtts_hip_attn_cached", "position", pos, rows, S, st));
-    CKI(attn_ints_ok("qtts_hip_attn_cached", "slot", row_b, rows, slots, st));
-    AttnArgs t;
-    t.mode = 1; t.qkv = q; t.ld_qkv = ld_q; t.qn_w = qn_w; t.kn_w = kn_w; t.eps = eps;
-    t.rope_cos = rope_cos; t.rope_sin = rope_sin;
-    t.kc = (float *)kc; t.vc = (float *)vc; t.S = S; t.kv_dtype = kv_dtype;
-    t.pos = pos; t.row_b = row_b; t.NH = NH; t.KV = KV; t.HD = HD; t.out = out; t.ld_out = NH * HD; t.nrows = rows;
-    t.win = win;
-    int rc = prep ? qtts_qk_prep(t, st) : 0;
-    if (!rc) rc = qtts_attention(t, st);
-    if (hipStreamSynchronize(st) != hipSuccess) rc = -1;
-    return rc;
-}
-
-// The sub-talker's attention + O projection by kv head (k_attn_o) on its own:
-// fp32 caches [rows][S][KV*HD], no id table; part [KV][rows][R].  1 = a shape
-// qtts_attn_o_covers refuses.
-extern "C" int qtts_hip_attn_o(float *part, const float *qkv, float *kc, float *vc, const float *qn_w,
-                               const float *kn_w, const float *rope_cos, const float *rope_sin, const int *pos,
-                               const uint16_t *Wo, int R, int NH, int KV, int HD, int S, int rows, float eps,
-                               void *stream) {
-    if (!part || !qkv || !kc || !vc || !qn_w || !kn_w || !rope_cos || !rope_sin || !pos || !Wo) return -1;
-    if (!attn_dims_ok(NH, KV, HD, S, rows, 0) || R < 1) return -1;
-    AttnArgs t;
-    t.mode = 0; t.qkv = qkv; t.ld_qkv = (NH + 2 * KV) * HD; t.qn_w = qn_w; t.kn_w = kn_w; t.eps = eps;
-    t.rope_cos = rope_cos; t.rope_sin = rope_sin; t.kc = kc; t.vc = vc; t.S = S;
-    t.pos = pos; t.NH = NH; t.KV = KV; t.HD = HD; t.ld_out = NH * HD; t.nrows = rows;
-    if (!qtts_attn_o_covers(t, Wo)) return 1;
-    hipStream_t st = (hipStream_t)stream;
-    CKI(attn_ints_ok("qtts_hip_attn_o", "position", pos, rows, S, st));
-    int rc = qtts_attn_o(t, Wo, R, part, st);
-    if (hipStreamSynchronize(st) != hipSuccess) rc = -1;
-    return rc;
-}
-
-// The pair form of k_attn_o on its own: rows 0 and 1 of one slot at positions
-// 0 and 1, both from qkv [2][(NH + 2 KV) HD] (no id table); caches [S][KV*HD];
-// part [KV][2][R].  1 = a shape qtts_attn_o_pair_covers refuses.
-extern "C" int qtts_hip_attn_o_pair(float *part, const float *qkv, float *kc, float *vc, const float *qn_w,
-                                    const float *kn_w, const float *rope_cos, const float *rope_sin, const int *skip,
-                                    const uint16_t *Wo, int R, int NH, int KV, int HD, int S, float eps,
-                                    void *stream) {
-    if (!part || !qkv || !kc || !vc || !qn_w || !kn_w || !rope_cos || !rope_sin || !Wo) return -1;
-    if (!attn_dims_ok(NH, KV, HD, S, 2, 0) || R < 1) return -1;
-    AttnArgs t;
-    t.mode = 0; t.qkv = qkv; t.ld_qkv = (NH + 2 * KV) * HD; t.qn_w = qn_w; t.kn_w = kn_w; t.eps = eps;
-    t.rope_cos = rope_cos; t.rope_sin = rope_sin; t.kc = kc; t.vc = vc; t.S = S;
-    t.pos = nullptr; t.NH = NH; t.KV = KV; t.HD = HD; t.ld_out = NH * HD; t.nrows = 2; t.skip = skip;
-    if (!qtts_attn_o_pair_covers(t, Wo)) return 1;
-    hipStream_t st = (hipStream_t)stream;
-    int rc = qtts_attn_o_pair(t, Wo, R, part, st);
-    if (hipStreamSynchronize(st) != hipSuccess) rc = -1;
-    return rc;
-}
-
-// k_gemvw (nrows 1) or its pair form (nrows 2) for the default-cache-policy
-// shapes, with the sub-talker chain's prologue: x [nrows][cols] + the partials
-// part [n_part][nrows][cols] summed in order (part NULL: none), the sum stored
-// to x_new [nrows][cols] (NULL: not stored), RMSNorm by w (NULL: none).
-// 1 = a shape the kernel does not cover.
-extern "C" int qtts_hip_resident_matvec_rows_bf16(float *out, const uint16_t *A, const float *x, const float *w,
-                                                  float eps, int rows, int cols, int epi, const float *part,
-                                                  int n_part, float *x_new, int nrows, void *stream) {
-    if (!out || !A || !x || rows < 1 || cols < 1 || (nrows != 1 && nrows != 2)) return -1;
-    if (epi != EPI_STORE && epi != EPI_RESID && epi != EPI_SWIGLU) return -1;
-    if (part && n_part < 1) return -1;
-    if (part && cols > 1024) return 1;   // (the kernels hold the partials in registers up to 1024 columns)
-    GemvArgs a = gv(A, rows, cols, x, cols, out, epi == EPI_SWIGLU ? rows / 2 : rows, nrows, epi);
-    a.norm_w = w; a.eps = eps; a.nt = 0;
-    if (part) { a.xadd = part; a.n_xadd = n_part; a.ld_xadd = nrows * cols; a.ldb_xadd = cols; }
-    if (x_new) { a.xcopy = x_new; a.ldxc = cols; a.xcopy_normed = 0; }
-    return nrows == 2 ? qtts_gemvw_pair(a, (hipStream_t)stream) : qtts_gemvw(a, (hipStream_t)stream);
-}
-
-// qtts_bgemv_desc_t checked and translated to the batch kernels' arguments
-// (the split-K scratch and tickets are the caller's: ypart / tick stay unset).
-// No pointer is dereferenced.  -1 = a bad descriptor.
-static int bgemv_desc_args(const qtts_bgemv_desc_t *d, GemvArgs &a) {
-    if (!d || !d->A || d->rows < 1 || d->cols < 1 || d->batch < 2 || d->batch > QTTS_HIP_MAX_BATCH) return -1;
-    if (d->epi < EPI_STORE || d->epi > EPI_SWIGLU || d->src < 0 || d->src > 2) return -1;
-    if ((d->epi == EPI_BIAS || d->epi == EPI_BIAS_SILU) && !d->bias) return -1;
-    if (d->src == 0 ? !d->x : (!d->table || !d->ids)) return -1;
-    if (d->part_in && (d->src != 0 || d->n_part_in < 1 || d->n_part_in > 4)) return -1;
-    if (d->kz < 0 || d->kz == 1 || d->kz > 4) return -1;
-    if (d->kz >= 2 && (d->self_reduce ? !d->y : !d->part_out)) return -1;
-    if (d->kz < 2 && !d->y) return -1;
-    a = gv(d->A, d->rows, d->cols, d->src == 0 ? d->x : nullptr, d->ldx, d->y, d->ldy, d->batch, d->epi);
-    if (d->src == 1) a.table = (const bf16_t *)d->table;
-    if (d->src == 2) a.table_f32 = (const float *)d->table;
-    a.ids = d->ids; a.ids_bstride = d->ids_bstride; a.ids_rstride = d->ids_rstride; a.ids_off = d->ids_off;
-    a.row_sel = d->row_sel;
-    if (d->part_in) {
-        a.xadd = d->part_in; a.n_xadd = d->n_part_in; a.ld_xadd = d->batch * d->cols; a.ldb_xadd = d->cols;
-    }
-    a.norm_w = d->norm_w; a.eps = d->eps;
-    if (d->xcopy) { a.xcopy = d->xcopy; a.ldxc = d->cols; a.xcopy_normed = d->xcopy_normed; }
-    a.bias = d->bias;
-    if (d->kz >= 2) {
-        a.kz = d->kz; a.ld_ypart = (size_t)d->batch * d->rows;
-        if (!d->self_reduce) { a.ypart = d->part_out; a.y = nullptr; }
-    }
-    return 0;
-}
-
-// One lock-step batch GEMV (qtts_bgemv: 2..16 rows k_gemvb, else k_gemvm;
-// 17..64 k_gemvx) with everything the decode frame can ask of it, on its own.  The
-// split-K scratch is allocated here; the tickets of the self-reducing form
-// live as long as the library (zeroed once: every launch leaves them zero, as
-// the frame graph relies on).  1 = no batch kernel covers the case.
-extern "C" int qtts_hip_batch_matvec_case(const qtts_bgemv_desc_t *d, void *stream) {
-    GemvArgs a;
-    if (bgemv_desc_args(d, a)) return -1;
-    hipStream_t st = (hipStream_t)stream;
-    float *scratch = nullptr;
-    static int *ticks = nullptr;   // (one device: the parity entry of a test process)
-    if (d->kz >= 2 && d->self_reduce) {
-        if (!ticks) {
-            CK(hipMalloc((void **)&ticks, QTTS_GM_TICKS * sizeof(int)));
-            CK(hipMemset(ticks, 0, QTTS_GM_TICKS * sizeof(int)));
-        }
-        CK(hipMalloc((void **)&scratch, (size_t)d->kz * a.ld_ypart * 4));
-        a.ypart = scratch; a.tick = ticks;
-    }
-    int rc = qtts_bgemv(a, st);
-    if (hipStreamSynchronize(st) != hipSuccess) rc = -1;
-    if (scratch) hipFree(scratch);
-    return rc;
-}
-
-// The plan qtts_hip_batch_matvec_case would launch (qtts_bgemv_plan), host
-// only: the self-reducing form's scratch and tickets are stand-in addresses.
-extern "C" int qtts_hip_batch_matvec_plan(const qtts_bgemv_desc_t *d, qtts_bgemv_plan_t *out) {
-    GemvArgs a;
-    if (!out || bgemv_desc_args(d, a)) return -1;
-    if (d->kz >= 2 && d->self_reduce) { a.ypart = (float *)(uintptr_t)256; a.tick = (int *)(uintptr_t)256; }
-    BgPlan p;
-    const int rc = qtts_bgemv_plan(a, p);
-    *out = qtts_bgemv_plan_t();
-    if (rc) return rc;
-    out->kernel = p.kernel; out->n_tmpl = p.nt;
-    for (int i = 0; i < p.nt; ++i) out->tmpl[i] = p.t[i];
-    out->src = p.src; out->grid_x = (int)p.grid.x; out->grid_y = (int)p.grid.y; out->block = (int)p.block.x;
-    out->lds_bytes = p.smem; out->tpw = p.tpw; out->cch = p.cch;
     return 0;
 }
 

@@ -103,7 +103,7 @@ EXPORTS = [
     "qtts_dev_codec_stream_push_host", "qtts_dev_codec_async_begin", "qtts_dev_codec_async_push",
     "qtts_dev_codec_async_end", "qtts_dev_codec_multi", "qtts_dev_enc_config", "qtts_dev_enc_available", "qtts_dev_speaker_embed",
     "qtts_dev_encode_audio", "qwen_tts_generate_queue", "qwen_tts_queue_codes", "qtts_dev_reserve", "qtts_dev_refill",
-    "qtts_dev_retire", "qtts_dev_frame_stops", "qtts_dev_move_slot", "qtts_dev_set_rows", "qtts_hip_tengine_layers",
+    "qtts_dev_retire", "qtts_dev_frame_stops", "qtts_dev_move_slot", "qtts_dev_set_rows",
     "qwen_tts_set_kv_cache_dtype", "qwen_tts_kv_cache_dtype", "qtts_dev_set_kv_dtype", "qtts_dev_kv_dtype",
     "qtts_dev_get_kv", "qtts_dev_get_attn", "qtts_hip_attn_decode",
     "qtts_hip_attn_decode_ex", "qtts_hip_attn_cached", "qtts_hip_attn_o",
@@ -480,7 +480,6 @@ def lib():
     L.qtts_dev_get_tap.restype = C.c_int
     L.qtts_dev_get_tap.argtypes = [C.c_void_p, C.c_int, _fp, C.c_int, _up, _ip]
     L.qtts_hip_device_count.restype = C.c_int
-    L.qtts_hip_tengine_layers.restype = C.c_longlong
     vp = C.c_void_p
     L.qtts_hip_matvec_bf16.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp]
     L.qtts_hip_rmsnorm_matvec_bf16.argtypes = [vp, vp, vp, vp, C.c_float, C.c_int, C.c_int, C.c_int, vp]

@@ -243,7 +243,7 @@ def test_attn_decode_dtype0_is_the_models_fp32_path(gpu, monkeypatch, preset, nb
     must equal the model's.  hd128: 32-key splits, position 108 = 4 splits."""
     import torch
     from qtts_io import bf16_to_f32, read_model_tensors
-    for k in ("QTTS_HIP_KV", "QTTS_HIP_ATTN_LPK", "QTTS_HIP_TENGINE"):
+    for k in ("QTTS_HIP_KV", "QTTS_HIP_ATTN_LPK"):
         monkeypatch.delenv(k, raising=False)
     P_LEN = 10   # prompt rows with a speaker and a language (see test_layer0_cache_rows_slot2_of_three)
     md = model_dir(preset)
