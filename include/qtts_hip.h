@@ -739,6 +739,63 @@ int qtts_hip_xgemm_case(const qtts_xgemm_desc_t *d, size_t part_elems, int force
  * only.  Returns as qtts_hip_xgemm_case (1: force_path does not cover). */
 int qtts_hip_xgemm_seg_case(const qtts_xgemm_desc_t *d, int nseg, int seg_ldb, int seg_ldc, size_t part_elems,
                             int force_path, int *path_out, int *splits_out, void *stream);
+/* One multi-row projection of the prefill and prompt paths, as the runtime's
+ * rows_proj hands it to the multi-row GEMMs (k_mgemm.hip, k_pgemm.hip):
+ *   y[m][r] = epi( sum_c A[r][c] * xin[m][c] ),  m < rows, r < R
+ *   src 0: xin = x rows (stride ldx floats); src 1: xin = row ids[m *
+ *          ids_bstride] of a bf16 table [*][C];
+ *   norm_w NULL: no RMSNorm, else xin[m][c] * inv[m] * norm_w[c] with
+ *          inv[m] = 1 / sqrt(mean_c xin^2 + eps) (src 0 only);
+ *   epi 0 store, 1 +bias, 2 SiLU(+bias), 3 residual (y += ...), 4 SwiGLU over
+ *   interleaved gate|up row quads (R / 2 outputs); y rows at stride ldy.
+ * The device scratch is the caller's: part (part_elems floats; NULL: no
+ * split-K), planes (plane_elems bf16; NULL: no k_pgemm) and inv (>= rows
+ * floats; needed with norm_w).  All pointers are device pointers. */
+typedef struct {
+    int rows, R, C;
+    const uint16_t *A;                /* bf16 [R][C] */
+    int src;
+    const float *x; int ldx;
+    const uint16_t *table;
+    const int *ids; int ids_bstride;
+    const float *norm_w; float eps;
+    int epi;
+    const float *bias;
+    float *y; int ldy;
+    float *part; size_t part_elems;
+    uint16_t *planes; size_t plane_elems;
+    float *inv;
+} qtts_rows_gemm_desc_t;
+/* the seven kernels, as qtts_rows_gemm_plan_t.kernel */
+enum {
+    QTTS_RG_MGEMM_1_1 = 0,   /* k_mgemm<1,1>: 2..16 rows */
+    QTTS_RG_MGEMM_2_1 = 1,   /* k_mgemm<2,1>: 17..32 rows */
+    QTTS_RG_MGEMM_4_1 = 2,   /* k_mgemm<4,1>: 33 rows and more, 64-row chunks on grid.y */
+    QTTS_RG_MGEMM_4_2 = 3,   /* k_mgemm<4,2>: > 64 rows, 2 weight tiles per workgroup */
+    QTTS_RG_MGEMM_4_4 = 4,   /* k_mgemm<4,4>: > 64 rows, 4 weight tiles per workgroup */
+    QTTS_RG_PGEMM_2 = 5,     /* k_pgemm<2>: 128 x 128 tile */
+    QTTS_RG_PGEMM_4 = 6,     /* k_pgemm<4>: 128 x 256 tile */
+};
+/* which kernel, its split-K columns (kz > 1: summed by k_mgemm_reduce), grid and block */
+typedef struct {
+    int kernel, kz;
+    int grid_x, grid_y, grid_z, block;
+} qtts_rows_gemm_plan_t;
+/* The launch plan for the projection with a split workspace of part_elems
+ * floats and plane scratch of plane_elems bf16 (0: none; d->part / d->planes
+ * and their sizes are not looked at).  force -1: as the runtime's prefill
+ * dispatches -- qtts_pgemm above 16 rows where it covers the shape, else
+ * qtts_mgemm; 0: qtts_mgemm; 1 / 2: qtts_pgemm at tile width 128 / 256.
+ * Returns 0 planned, 1 where the (forced) launcher does not cover the shape,
+ * -1 on an argument error.  Host only: no pointer is dereferenced (their
+ * alignment is looked at) and no device is needed. */
+int qtts_hip_rows_gemm_plan(const qtts_rows_gemm_desc_t *d, size_t part_elems, size_t plane_elems, int force,
+                            qtts_rows_gemm_plan_t *plan_out);
+/* Runs the projection through that plan with the descriptor's own scratch,
+ * synchronises and returns; plan_out (may be NULL) receives what ran.  Returns
+ * 1 and launches nothing where the (forced) launcher does not cover the
+ * shape, -1 on an argument or launch error.  A parity entry, not a timing one. */
+int qtts_hip_rows_gemm_case(const qtts_rows_gemm_desc_t *d, int force, qtts_rows_gemm_plan_t *plan_out, void *stream);
 /* snake(x) = x + inv_beta[c] * sin^2(x * alpha[c]) with the codec GEMMs' own
  * sin^2 (sin2 in k_codec.hip; qtts_hip_snake_beta runs sinf), and the fp32
  * expf / tanhf the GELU and SiLU epilogues call: fn 0 snake (needs alpha /

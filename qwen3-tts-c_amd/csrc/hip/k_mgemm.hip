@@ -258,11 +258,16 @@ size_t qtts_mgemm_part_elems(size_t rows, size_t widest) {
     return by_rows < by_grid ? by_rows : by_grid;
 }
 
-int qtts_mgemm(const GemvArgs &a, float *inv_scratch, hipStream_t st, float *part, size_t part_elems) {
-    if (a.nb < 2 || a.C % 32 || a.R % 16 || a.xcopy || a.table_f32 || (a.norm_w && !inv_scratch) ||
+// qtts_mgemm's launch decisions, host only (nothing launched, no pointer
+// dereferenced): the cover test, the template (MT row tiles x NW weight tiles
+// per workgroup), the 64-row chunks, the split-K columns and the grid.
+// has_inv / has_part: the caller has the 1/rms scratch / a split workspace of
+// part_elems floats.  0 = planned, 1 = not covered.
+int qtts_mgemm_plan(const GemvArgs &a, bool has_inv, bool has_part, size_t part_elems, MgPlan &p) {
+    p = MgPlan();
+    if (a.nb < 2 || a.C % 32 || a.R % 16 || a.xcopy || a.table_f32 || (a.norm_w && !has_inv) ||
         (a.table && a.norm_w) || (!a.table && (a.ldx % 4 || ((uintptr_t)a.x & 15))) || (a.C % 8))
         return 1;
-    if (a.norm_w) hipLaunchKernelGGL(k_row_rms, dim3(a.nb), dim3(256), 0, st, a.x, a.ldx, a.C, a.eps, inv_scratch);
     const int nch = (a.nb + 63) / 64;
     // > 64 rows: widest weight tile group that still gives >= 256 workgroups
     const int nw = nch < 2 || a.R % 64 ? 1 : a.R / 64 * nch >= 256 ? 4 : a.R % 32 == 0 && a.R / 32 * nch >= 256 ? 2 : 1;
@@ -272,18 +277,35 @@ int qtts_mgemm(const GemvArgs &a, float *inv_scratch, hipStream_t st, float *par
     const int kzmax = mgemm_kzmax(), wgmax = mgemm_wgmax();
     int kz = 1;
     const int wgs = a.R / (16 * nw) * nch;
-    while (part && 2 * kz <= kzmax && wgs * 2 * kz <= wgmax && a.C % (32 * 2 * kz) == 0 &&
+    while (has_part && 2 * kz <= kzmax && wgs * 2 * kz <= wgmax && a.C % (32 * 2 * kz) == 0 &&
            a.C / 32 / (2 * kz) >= 8 && (size_t)2 * kz * a.nb * a.R <= part_elems)
         kz *= 2;
+    p.nw = nw;
+    p.mt = nw > 1 ? 4 : a.nb <= 16 ? 1 : a.nb <= 32 ? 2 : 4;
+    p.nch = nch;
+    p.kz = kz;
+    p.grid = dim3(a.R / (16 * nw), nch, kz);
+    p.kernel = nw == 4 ? RG_MGEMM_4_4 : nw == 2 ? RG_MGEMM_4_2
+             : p.mt == 1 ? RG_MGEMM_1_1 : p.mt == 2 ? RG_MGEMM_2_1 : RG_MGEMM_4_1;
+    return 0;
+}
+
+int qtts_mgemm(const GemvArgs &a, float *inv_scratch, hipStream_t st, float *part, size_t part_elems) {
+    MgPlan p;
+    if (qtts_mgemm_plan(a, inv_scratch != nullptr, part != nullptr, part_elems, p)) return 1;
+    if (a.norm_w) hipLaunchKernelGGL(k_row_rms, dim3(a.nb), dim3(256), 0, st, a.x, a.ldx, a.C, a.eps, inv_scratch);
+    const int kz = p.kz;
     float *pt = kz > 1 ? part : nullptr;
-    const dim3 grid(a.R / (16 * nw), nch, kz);
-    if (nw == 4) hipLaunchKernelGGL((k_mgemm<4, 4>), grid, dim3(256), 0, st, a, inv_scratch, pt);
-    else if (nw == 2) hipLaunchKernelGGL((k_mgemm<4, 2>), grid, dim3(256), 0, st, a, inv_scratch, pt);
-    else if (a.nb <= 16) hipLaunchKernelGGL((k_mgemm<1, 1>), grid, dim3(256), 0, st, a, inv_scratch, pt);
-    else if (a.nb <= 32) hipLaunchKernelGGL((k_mgemm<2, 1>), grid, dim3(256), 0, st, a, inv_scratch, pt);
-    else hipLaunchKernelGGL((k_mgemm<4, 1>), grid, dim3(256), 0, st, a, inv_scratch, pt);
-    qtts_last_kernel = nw == 4 ? "k_mgemm<4,4>" : nw == 2 ? "k_mgemm<4,2>"
-                     : a.nb <= 16 ? "k_mgemm<1>" : a.nb <= 32 ? "k_mgemm<2>" : "k_mgemm<4>";
+    const dim3 grid = p.grid;
+    switch (p.kernel) {
+        case RG_MGEMM_4_4: hipLaunchKernelGGL((k_mgemm<4, 4>), grid, dim3(256), 0, st, a, inv_scratch, pt); break;
+        case RG_MGEMM_4_2: hipLaunchKernelGGL((k_mgemm<4, 2>), grid, dim3(256), 0, st, a, inv_scratch, pt); break;
+        case RG_MGEMM_1_1: hipLaunchKernelGGL((k_mgemm<1, 1>), grid, dim3(256), 0, st, a, inv_scratch, pt); break;
+        case RG_MGEMM_2_1: hipLaunchKernelGGL((k_mgemm<2, 1>), grid, dim3(256), 0, st, a, inv_scratch, pt); break;
+        default: hipLaunchKernelGGL((k_mgemm<4, 1>), grid, dim3(256), 0, st, a, inv_scratch, pt); break;
+    }
+    qtts_last_kernel = p.kernel == RG_MGEMM_4_4 ? "k_mgemm<4,4>" : p.kernel == RG_MGEMM_4_2 ? "k_mgemm<4,2>"
+                     : p.kernel == RG_MGEMM_1_1 ? "k_mgemm<1>" : p.kernel == RG_MGEMM_2_1 ? "k_mgemm<2>" : "k_mgemm<4>";
     if (kz > 1) {
         const int nout = a.epi == EPI_SWIGLU ? a.R / 2 : a.R;
         hipLaunchKernelGGL(k_mgemm_reduce, dim3((nout + 255) / 256, a.nb), dim3(256), 0, st, a, pt, kz);

@@ -253,40 +253,68 @@ size_t qtts_pgemm_plane_elems(size_t rows, size_t K) {
     return (size_t)3 * ((rows + BM - 1) / BM * BM) * K;
 }
 
-// Returns 1 when the shape is not covered (the caller falls back to
-// qtts_mgemm), 0 ok, -1 error.  inv_scratch >= nb floats (per-row 1/rms, by
-// k_row_rms in qtts_mgemm's file), planes >= qtts_pgemm_plane_elems(nb, C).
-int qtts_pgemm(const GemvArgs &a, float *inv_scratch, unsigned short *planes, size_t plane_elems, hipStream_t st,
-               float *part, size_t part_elems) {
+// qtts_pgemm's launch decisions, host only (nothing launched, no pointer
+// dereferenced): the cover test, the tile width BN, the padded row count Mp,
+// the split-K columns and the grid.  has_planes / has_part: the caller has the
+// plane scratch of plane_elems bf16 / a split workspace of part_elems floats.
+// bn: 128 or 256 forces the tile width, anything else leaves it to the row
+// tiles.  0 = planned, 1 = not covered.
+int qtts_pgemm_plan(const GemvArgs &a, bool has_planes, size_t plane_elems, bool has_part, size_t part_elems, int bn,
+                    PgPlan &p) {
+    p = PgPlan();
     if (a.nb < 17 || a.C % 256 || a.R % 32 || !a.x || a.table || a.table_f32 || a.xadd || a.xcopy || a.bias ||
         a.ldx % 4 || ((uintptr_t)a.x & 15) ||
-        (a.epi != EPI_STORE && a.epi != EPI_RESID && a.epi != EPI_SWIGLU) || !planes)
+        (a.epi != EPI_STORE && a.epi != EPI_RESID && a.epi != EPI_SWIGLU) || !has_planes)
         return 1;
     const int Mp = (a.nb + BM - 1) / BM * BM;
     if ((a.C / BK) % 2) return 1;   // (an even stage count per column: k_pgemm's loop)
     if ((size_t)3 * Mp * a.C > plane_elems) return 1;
-    hipLaunchKernelGGL(k_split3, dim3(Mp), dim3(256), 0, st, a.x, a.ldx, a.nb, a.C, a.norm_w, a.eps, planes, Mp);
-    // split-K while the tiles would not fill the chip (one workgroup per CU
-    // cannot hide its own stage loads), each column >= 8 stages
     // The weight-row width of a workgroup's tile: 256 once there are several
     // 128-row tiles (the plane re-reads dominate: voice-clone batch-8 prefill
     // 10.1 -> 9.15 ms), 128 for one row tile (half the weight tiles would need
     // twice the split-K partials: voice-clone batch-1 prefill 6.87 vs 7.16 ms;
-    // profiles/r06q_ab_pgemm_bn.txt).  QTTS_HIP_PGEMM_BN=128|256 forces one
-    // (read per call: a test switches it between contexts of one process).
-    const char *bne = getenv("QTTS_HIP_PGEMM_BN");
-    const int BN = bne && atoi(bne) == 128 ? 128 : bne && atoi(bne) == 256 ? 256 : Mp >= 2 * BM ? 256 : 128;
+    // profiles/r06q_ab_pgemm_bn.txt).
+    const int BN = bn == 128 ? 128 : bn == 256 ? 256 : Mp >= 2 * BM ? 256 : 128;
+    // split-K while the tiles would not fill the chip (one workgroup per CU
+    // cannot hide its own stage loads), each column >= 8 stages
     const int tiles = (a.R + BN - 1) / BN * (Mp / BM);
     int kz = 1;
-    while (part && tiles * kz < 256 && kz < 8 && (a.C / BK) % (4 * kz) == 0 && a.C / BK / (2 * kz) >= 8 &&
+    while (has_part && tiles * kz < 256 && kz < 8 && (a.C / BK) % (4 * kz) == 0 && a.C / BK / (2 * kz) >= 8 &&
            (size_t)2 * kz * a.nb * a.R <= part_elems)
         kz *= 2;
-    const dim3 grid((a.R + BN - 1) / BN, Mp / BM, kz);
-    if (BN == 256) {
-        hipLaunchKernelGGL(k_pgemm<4>, grid, dim3(512), 0, st, a, planes, Mp, kz > 1 ? part : nullptr);
+    p.BN = BN;
+    p.Mp = Mp;
+    p.kz = kz;
+    p.grid = dim3((a.R + BN - 1) / BN, Mp / BM, kz);
+    p.kernel = BN == 256 ? RG_PGEMM_4 : RG_PGEMM_2;
+    return 0;
+}
+
+// QTTS_HIP_PGEMM_BN=128|256 forces the tile width of every qtts_pgemm call
+// that does not name one (read per call: a test switches it between contexts
+// of one process); 0 otherwise.
+int qtts_pgemm_bn_env() {
+    const char *bne = getenv("QTTS_HIP_PGEMM_BN");
+    const int v = bne ? atoi(bne) : 0;
+    return v == 128 || v == 256 ? v : 0;
+}
+
+// Returns 1 when the shape is not covered (the caller falls back to
+// qtts_mgemm), 0 ok, -1 error.  inv_scratch >= nb floats (per-row 1/rms, by
+// k_row_rms in qtts_mgemm's file), planes >= qtts_pgemm_plane_elems(nb, C).
+// bn: the tile width as qtts_pgemm_plan takes it; 0 = QTTS_HIP_PGEMM_BN.
+int qtts_pgemm(const GemvArgs &a, float *inv_scratch, unsigned short *planes, size_t plane_elems, hipStream_t st,
+               float *part, size_t part_elems, int bn) {
+    PgPlan p;
+    if (!bn) bn = qtts_pgemm_bn_env();
+    if (qtts_pgemm_plan(a, planes != nullptr, plane_elems, part != nullptr, part_elems, bn, p)) return 1;
+    const int Mp = p.Mp, kz = p.kz;
+    hipLaunchKernelGGL(k_split3, dim3(Mp), dim3(256), 0, st, a.x, a.ldx, a.nb, a.C, a.norm_w, a.eps, planes, Mp);
+    if (p.BN == 256) {
+        hipLaunchKernelGGL(k_pgemm<4>, p.grid, dim3(512), 0, st, a, planes, Mp, kz > 1 ? part : nullptr);
         qtts_last_kernel = "k_pgemm<4>";
     } else {
-        hipLaunchKernelGGL(k_pgemm<2>, grid, dim3(256), 0, st, a, planes, Mp, kz > 1 ? part : nullptr);
+        hipLaunchKernelGGL(k_pgemm<2>, p.grid, dim3(256), 0, st, a, planes, Mp, kz > 1 ? part : nullptr);
         qtts_last_kernel = "k_pgemm<2>";
     }
     if (kz > 1 && qtts_mgemm_reduce(a, part, kz, st) != 0) return -1;

@@ -133,6 +133,19 @@ int qtts_gemvb_launch(const GemvArgs &a, const BgPlan &p, hipStream_t st);
 int qtts_gemvx_launch(const GemvArgs &a, const BgPlan &p, hipStream_t st);
 // the weight shapes k_gemvx takes (qtts_dev_begin refuses a model with another above 16 slots)
 bool qtts_gemvx_shape_ok(int R, int C);
+// The seven kernels of the multi-row GEMMs (k_mgemm<MT,NW>, k_pgemm<WN>), as
+// the plans below name them (QTTS_RG_* of qtts_hip.h).
+enum { RG_MGEMM_1_1 = 0, RG_MGEMM_2_1 = 1, RG_MGEMM_4_1 = 2, RG_MGEMM_4_2 = 3, RG_MGEMM_4_4 = 4, RG_PGEMM_2 = 5,
+       RG_PGEMM_4 = 6 };
+// qtts_mgemm's plan: the kernel (RG_*), its template (mt row tiles x nw weight
+// tiles per workgroup), the 64-row chunks, the split-K columns and the grid
+struct MgPlan {
+    int kernel = -1, mt = 0, nw = 0, nch = 0, kz = 1;
+    dim3 grid;
+};
+// host only: 0 = planned, 1 = not covered (what qtts_mgemm launches for the
+// same arguments; has_inv / has_part: its inv_scratch / part are non-null)
+int qtts_mgemm_plan(const GemvArgs &a, bool has_inv, bool has_part, size_t part_elems, MgPlan &p);
 // multi-row (2..64) projection on the bf16 matrix cores (k_mgemm.hip); 1 = not covered
 int qtts_mgemm(const GemvArgs &a, float *inv_scratch, hipStream_t st, float *part = nullptr, size_t part_elems = 0);
 // split-K partial floats qtts_mgemm may use for `rows` activation rows and outputs <= widest
@@ -142,9 +155,21 @@ int qtts_row_rms(const float *x, int ldx, int rows, int C, float eps, float *inv
 int qtts_mgemm_reduce(const GemvArgs &a, const float *part, int kz, hipStream_t st);
 // the talker prefill's projections over > 16 rows (k_pgemm.hip): activations
 // split once into 3 bf16 planes (scratch: qtts_pgemm_plane_elems), then an
-// LDS-tiled 128 x 128 MFMA GEMM; 1 = shape not covered
+// LDS-tiled 128 x 128 MFMA GEMM; 1 = shape not covered.  bn: the tile width
+// (128 | 256), 0 = QTTS_HIP_PGEMM_BN, else by the row tiles
 int qtts_pgemm(const GemvArgs &a, float *inv_scratch, unsigned short *planes, size_t plane_elems, hipStream_t st,
-               float *part, size_t part_elems);
+               float *part, size_t part_elems, int bn = 0);
+// qtts_pgemm's plan: the kernel (RG_*), the tile width, the padded rows, the
+// split-K columns and the grid
+struct PgPlan {
+    int kernel = -1, BN = 0, Mp = 0, kz = 1;
+    dim3 grid;
+};
+// host only: 0 = planned, 1 = not covered (what qtts_pgemm launches for the
+// same arguments; bn 128 | 256 forces the tile width, else by the row tiles)
+int qtts_pgemm_plan(const GemvArgs &a, bool has_planes, size_t plane_elems, bool has_part, size_t part_elems, int bn,
+                    PgPlan &p);
+int qtts_pgemm_bn_env();   // QTTS_HIP_PGEMM_BN as a tile width (128 | 256), else 0
 size_t qtts_pgemm_plane_elems(size_t rows, size_t K);
 
 struct AttnArgs {

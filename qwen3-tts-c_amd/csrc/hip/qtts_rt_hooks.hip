@@ -308,3 +308,84 @@ extern "C" int qtts_hip_batch_matvec_plan(const qtts_bgemv_desc_t *d, qtts_bgemv
     out->lds_bytes = p.smem; out->tpw = p.tpw; out->cch = p.cch;
     return 0;
 }
+
+// qtts_rows_gemm_desc_t checked and translated to the multi-row GEMMs'
+// arguments.  No pointer is dereferenced.  -1 = a bad descriptor.
+static int rows_gemm_args(const qtts_rows_gemm_desc_t *d, int force, GemvArgs &a) {
+    if (!d || !d->A || !d->y || d->rows < 1 || d->R < 1 || d->C < 1 || force < -1 || force > 2) return -1;
+    if (d->epi < EPI_STORE || d->epi > EPI_SWIGLU || d->src < 0 || d->src > 1) return -1;
+    if ((d->epi == EPI_BIAS || d->epi == EPI_BIAS_SILU) && !d->bias) return -1;
+    if (d->src == 0 ? !d->x : (!d->table || !d->ids)) return -1;
+    if (d->ldy < (d->epi == EPI_SWIGLU ? d->R / 2 : d->R) || (d->src == 0 && d->ldx < d->C)) return -1;
+    a = gv(d->A, d->R, d->C, d->src == 0 ? d->x : nullptr, d->ldx, d->y, d->ldy, d->rows, d->epi);
+    if (d->src == 1) { a.table = d->table; a.ids = d->ids; a.ids_bstride = d->ids_bstride; }
+    a.norm_w = d->norm_w; a.eps = d->eps; a.bias = d->bias; a.nt = 0;
+    return 0;
+}
+
+// The plan of one multi-row projection under `force` (qtts_hip.h): pgemm's
+// where it is asked for (or dispatched to) and covers, else mgemm's.
+// 0 planned, 1 not covered.
+static int rows_gemm_plan(const GemvArgs &a, bool has_inv, bool has_part, size_t part_elems, bool has_planes,
+                          size_t plane_elems, int force, bool &use_pgemm, PgPlan &pp, MgPlan &mp) {
+    use_pgemm = false;
+    if (force >= 1 || (force < 0 && a.nb > 16)) {
+        const int bn = force == 1 ? 128 : force == 2 ? 256 : qtts_pgemm_bn_env();
+        const int rc = qtts_pgemm_plan(a, has_planes, plane_elems, has_part, part_elems, bn, pp);
+        if (rc == 0) { use_pgemm = true; return 0; }
+        if (force >= 1) return rc;
+    }
+    return qtts_mgemm_plan(a, has_inv, has_part, part_elems, mp);
+}
+
+static void rows_gemm_report(bool use_pgemm, const PgPlan &pp, const MgPlan &mp, qtts_rows_gemm_plan_t *out) {
+    if (!out) return;
+    const dim3 g = use_pgemm ? pp.grid : mp.grid;
+    out->kernel = use_pgemm ? pp.kernel : mp.kernel;
+    out->kz = use_pgemm ? pp.kz : mp.kz;
+    out->grid_x = (int)g.x; out->grid_y = (int)g.y; out->grid_z = (int)g.z;
+    out->block = use_pgemm && pp.kernel == RG_PGEMM_4 ? 512 : 256;
+}
+
+extern "C" int qtts_hip_rows_gemm_plan(const qtts_rows_gemm_desc_t *d, size_t part_elems, size_t plane_elems,
+                                       int force, qtts_rows_gemm_plan_t *plan_out) {
+    GemvArgs a;
+    if (!plan_out || rows_gemm_args(d, force, a)) return -1;
+    *plan_out = qtts_rows_gemm_plan_t();
+    bool use_pgemm;
+    PgPlan pp;
+    MgPlan mp;
+    const int rc = rows_gemm_plan(a, true, part_elems > 0, part_elems, plane_elems > 0, plane_elems, force, use_pgemm,
+                                  pp, mp);
+    if (rc) return rc;
+    rows_gemm_report(use_pgemm, pp, mp, plan_out);
+    return 0;
+}
+
+// One multi-row projection on its own, through the launchers themselves
+// (which plan again from the same arguments: the report is their plan).
+extern "C" int qtts_hip_rows_gemm_case(const qtts_rows_gemm_desc_t *d, int force, qtts_rows_gemm_plan_t *plan_out,
+                                       void *stream) {
+    GemvArgs a;
+    if (rows_gemm_args(d, force, a)) return -1;
+    if (plan_out) *plan_out = qtts_rows_gemm_plan_t();
+    if (d->norm_w && !d->inv) return -1;
+    if ((d->part_elems > 0 && !d->part) || (d->plane_elems > 0 && !d->planes)) return -1;
+    float *part = d->part_elems > 0 ? d->part : nullptr;
+    unsigned short *planes = d->plane_elems > 0 ? d->planes : nullptr;
+    bool use_pgemm;
+    PgPlan pp;
+    MgPlan mp;
+    int rc = rows_gemm_plan(a, d->inv != nullptr, part != nullptr, d->part_elems, planes != nullptr, d->plane_elems,
+                            force, use_pgemm, pp, mp);
+    if (rc) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    if (use_pgemm)
+        rc = qtts_pgemm(a, d->inv, planes, d->plane_elems, st, part, d->part_elems, pp.BN);
+    else
+        rc = qtts_mgemm(a, d->inv, st, part, d->part_elems);
+    if (rc == 1) return -1;   // (the launcher's own plan disagreed with the one reported)
+    if (hipStreamSynchronize(st) != hipSuccess) rc = -1;
+    if (!rc) rows_gemm_report(use_pgemm, pp, mp, plan_out);
+    return rc;
+}

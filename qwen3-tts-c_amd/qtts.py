@@ -133,6 +133,7 @@ EXPORTS = [
     "qwen_tts_feed_ids", "qwen_tts_feed_close", "qwen_tts_feed_state", "qwen_tts_generate_fed_stream",
     "qwen_tts_generate_fed_batch_stream", "qtts_dev_text_open", "qtts_dev_text_append", "qtts_dev_get_trailing",
     "qtts_dev_text_state", "qtts_hip_text_held_frames", "qtts_dev_text_append_ms",
+    "qtts_hip_rows_gemm_plan", "qtts_hip_rows_gemm_case",
 ]
 
 MAX_BATCH = 64   # QWEN_TTS_MAX_BATCH / QTTS_HIP_MAX_BATCH: lock-step slots per context
@@ -196,6 +197,38 @@ class BGemvPlan(C.Structure):
 
 
 BGEMV_KERNELS = {1: "k_gemvm", 2: "k_gemvb", 4: "k_gemvx"}   # qtts_bgemv_plan_t.kernel
+
+
+class RowsGemmDesc(C.Structure):
+    """qtts_rows_gemm_desc_t (include/qtts_hip.h): one multi-row projection of
+    the prefill and prompt paths; the pointers are device addresses."""
+    _fields_ = [
+        ("rows", C.c_int), ("R", C.c_int), ("C", C.c_int),
+        ("A", C.c_void_p),
+        ("src", C.c_int),
+        ("x", C.c_void_p), ("ldx", C.c_int),
+        ("table", C.c_void_p),
+        ("ids", C.c_void_p), ("ids_bstride", C.c_int),
+        ("norm_w", C.c_void_p), ("eps", C.c_float),
+        ("epi", C.c_int),
+        ("bias", C.c_void_p),
+        ("y", C.c_void_p), ("ldy", C.c_int),
+        ("part", C.c_void_p), ("part_elems", C.c_size_t),
+        ("planes", C.c_void_p), ("plane_elems", C.c_size_t),
+        ("inv", C.c_void_p),
+    ]
+
+
+class RowsGemmPlan(C.Structure):
+    """qtts_rows_gemm_plan_t (include/qtts_hip.h): what the multi-row GEMMs launch."""
+    _fields_ = [
+        ("kernel", C.c_int), ("kz", C.c_int),
+        ("grid_x", C.c_int), ("grid_y", C.c_int), ("grid_z", C.c_int), ("block", C.c_int),
+    ]
+
+
+# qtts_rows_gemm_plan_t.kernel (QTTS_RG_* of qtts_hip.h)
+RG_NAMES = ["k_mgemm<1,1>", "k_mgemm<2,1>", "k_mgemm<4,1>", "k_mgemm<4,2>", "k_mgemm<4,4>", "k_pgemm<2>", "k_pgemm<4>"]
 
 
 class XGemmDesc(C.Structure):
@@ -543,6 +576,12 @@ def lib():
         for f in (L.qtts_hip_prefix_hits, L.qtts_hip_prefix_misses, L.qtts_hip_prefill_rows):
             f.restype = C.c_longlong
             f.argtypes = []
+    if hasattr(L, "qtts_hip_rows_gemm_case"):
+        L.qtts_hip_rows_gemm_plan.restype = C.c_int
+        L.qtts_hip_rows_gemm_plan.argtypes = [C.POINTER(RowsGemmDesc), C.c_size_t, C.c_size_t, C.c_int,
+                                              C.POINTER(RowsGemmPlan)]
+        L.qtts_hip_rows_gemm_case.restype = C.c_int
+        L.qtts_hip_rows_gemm_case.argtypes = [C.POINTER(RowsGemmDesc), C.c_int, C.POINTER(RowsGemmPlan), vp]
     if hasattr(L, "qtts_hip_batch_matvec_plan"):
         L.qtts_hip_batch_matvec_plan.restype = C.c_int
         L.qtts_hip_batch_matvec_plan.argtypes = [C.POINTER(BGemvDesc), C.POINTER(BGemvPlan)]
@@ -1552,6 +1591,34 @@ class Kernels:
         _ok(rc, "batch_matvec_plan")
         return dict(kernel=BGEMV_KERNELS[p.kernel], tmpl=list(p.tmpl[:p.n_tmpl]), grid=[p.grid_x, p.grid_y],
                     block=p.block, lds=int(p.lds_bytes), tpw=p.tpw, cch=p.cch)
+
+    @staticmethod
+    def _rows_gemm_result(rc, p, who):
+        if rc == 1:
+            return None
+        _ok(rc, who)
+        return dict(kernel=RG_NAMES[p.kernel], kz=p.kz, grid=[p.grid_x, p.grid_y, p.grid_z], block=p.block)
+
+    @staticmethod
+    def rows_gemm_plan(desc, part_elems=0, plane_elems=0, force=-1):
+        """The multi-row GEMMs' launch plan for a RowsGemmDesc with a split
+        workspace of part_elems floats and plane_elems bf16 of plane scratch
+        (qtts_hip_rows_gemm_plan; host only, no device needed).  force -1: the
+        prefill's dispatch, 0: qtts_mgemm, 1 / 2: qtts_pgemm at tile width 128 /
+        256.  A dict with the kernel's name, kz, grid and block, or None where
+        the (forced) launcher does not cover the shape."""
+        p = RowsGemmPlan()
+        rc = lib().qtts_hip_rows_gemm_plan(C.byref(desc), part_elems, plane_elems, force, C.byref(p))
+        return Kernels._rows_gemm_result(rc, p, "rows_gemm_plan")
+
+    @staticmethod
+    def rows_gemm_case(desc, force=-1):
+        """Runs one multi-row projection (qtts_hip_rows_gemm_case) with the
+        descriptor's own scratch: the plan that ran, or None where the (forced)
+        launcher does not cover the shape (nothing ran)."""
+        p = RowsGemmPlan()
+        rc = lib().qtts_hip_rows_gemm_case(C.byref(desc), force, C.byref(p), _stream())
+        return Kernels._rows_gemm_result(rc, p, "rows_gemm_case")
 
     @staticmethod
     def sample_top_k_rows(out_i32, logits, vocab, top_k, top_p, temperature, rng_u32, batch=1):

@@ -55,15 +55,16 @@ def _epilogue(acc, bound, epi, y0, bias):
 
 
 def run_case(dev, R, Cc, B, *, norm=False, epi=STORE, src="x", n_part=0, xcopy=None, kz=0, self_reduce=True,
-             row_sel=False, seed=0, x_override=None, kernel=None):
+             row_sel=False, seed=0, x_override=None, kernel=None, A_override=None):
     """One qtts_hip_batch_matvec_case against float64.  Returns (got, ref,
     bound) of y (or of the summed consumer-add partials), after asserting the
     xcopy output.  Inputs and partials are of order 1, so a dropped partial or
     row is far outside the bound.  kernel: the kernel the planner must have
-    chosen for the case (qtts_hip_batch_matvec_plan on the same arguments)."""
+    chosen for the case (qtts_hip_batch_matvec_plan on the same arguments).
+    A_override: the weights' bf16 bits in place of the random ones."""
     import torch
     rng = np.random.default_rng(seed + R + 3 * Cc + 7 * B)
-    A = _weights(R, Cc)
+    A = _weights(R, Cc) if A_override is None else A_override
     w = (1 + 0.1 * rng.standard_normal(Cc)).astype(np.float32) if norm else None
     kw = {}
     if src == "x":
@@ -243,6 +244,41 @@ def test_narrow_small_split_k_and_partials(gpu, narrow_kernel, B):
     for kz in (2, 4):
         check(*run_case(gpu, 256, 128, B, epi=RESID, kz=kz, self_reduce=True, kernel=k))
         check(*run_case(gpu, 256, 128, B, epi=RESID, kz=kz, self_reduce=False, kernel=k))
+
+
+# ---------------------------------------------------------------- 1c. exact planes
+# The 2e-6 bound above cannot see a lost third bf16 plane of x (at most 0.21 of
+# the bound on these inputs' kind; rows_gemm_ref.py).  The three batch kernels
+# split x into three planes as the multi-row GEMMs do, so they run the same
+# instrument: inputs whose planes are known and whose every partial sum is
+# exact in fp32 (rows_gemm_ref.exact_inputs), so the result equals the float64
+# one bit for bit whatever the order, K slot or split column.
+EXACT_SHAPE = (256, 128)   # the smallest shape of SMALL all three planners take with and without kz
+EXACT_RUNS = [("k_gemvb", None, 2), ("k_gemvb", None, 16), ("k_gemvm", "0", 2), ("k_gemvm", "0", 16),
+              ("k_gemvx", None, 17), ("k_gemvx", None, 64)]
+
+
+@pytest.mark.parametrize("kernel,env,B", EXACT_RUNS, ids=[f"{k}-{B}" for k, _, B in EXACT_RUNS])
+def test_exact_planes_bit_equal_float64(gpu, monkeypatch, kernel, env, B):
+    """store without kz, and kz 2 both consumer-add (the raw partials summed in
+    float64 here) and self-reducing (y0 + (p0 + p1): one fp32 rounding of the
+    exact float64 sum)"""
+    from rows_gemm_ref import exact_inputs
+    if env is None:
+        monkeypatch.delenv("QTTS_HIP_GEMVB", raising=False)
+    else:
+        monkeypatch.setenv("QTTS_HIP_GEMVB", env)
+    monkeypatch.delenv("QTTS_HIP_GB_W", raising=False)
+    R, Cc = EXACT_SHAPE
+    A, x, _ = exact_inputs(B, R, Cc, np.random.default_rng(1000 + B))
+    kw = dict(x_override=x, A_override=A, kernel=kernel)
+    got, ref, _ = run_case(gpu, R, Cc, B, **kw)
+    assert np.array_equal(got.astype(np.float64), ref), int(np.count_nonzero(got.astype(np.float64) != ref))
+    got, ref, _ = run_case(gpu, R, Cc, B, epi=RESID, kz=2, self_reduce=False, **kw)
+    assert np.array_equal(got, ref), int(np.count_nonzero(got != ref))
+    got, ref, _ = run_case(gpu, R, Cc, B, epi=RESID, kz=2, self_reduce=True, **kw)
+    assert got.dtype == np.float32
+    assert np.array_equal(got, ref.astype(np.float32)), int(np.count_nonzero(got != ref.astype(np.float32)))
 
 
 # ---------------------------------------------------------------- 2. row independence, bitwise

@@ -9,6 +9,20 @@ dispatcher sends a small shape there) within 2e-5 abs + 1e-4 rel of the
 golden / float64 output and within xgemm_ref.py's float64 bound
 (2e-6 * sum|w x| + 1e-6 and the epilogue's 2e-7), which test_gpu_xgemm.py holds
 every kernel of that family to path by path.
+
+What the 2e-6 bound sees and what it does not: the matrix-core kernels
+(k_mgemm, k_pgemm, k_gemvb, k_gemvm, k_gemvx) write each fp32 activation as
+three bf16 planes and claim an fp32 product up to summation order.  Measured
+on the CPU with the kernels' own rounding (standard-normal x, bf16 weights of
+scale 1/sqrt(K), 64 x 2048 x 64): a dropped second plane is 100 times the
+bound, but a dropped THIRD plane reaches at most 0.21 of it (a sequential fp32
+sum 0.095), so a kernel that loses, misroutes or double-counts the third plane
+passes every test under this bound.  The exact-plane cases close that hole
+(rows_gemm_ref.exact_inputs; test_gpu_rows_gemm.py::test_exact_planes for the
+multi-row GEMMs, test_gpu_batch_wide.py::test_exact_planes_bit_equal_float64
+for the batch GEMVs): inputs whose three planes are known and whose every
+partial sum is exact in fp32, so the output must equal the float64 result bit
+for bit.
 """
 import ctypes as C
 
