@@ -1115,7 +1115,6 @@ void codec_init(CodecModel *m, const qtts_dims_t *d, hipStream_t st) {
 void codec_free_state(CodecModel *m) {
     for (void *p : m->scratch) hipFree(p);
     m->scratch.clear();
-    m->scratch_bytes = 0;
     m->buf_elems = 0;
     m->t_cap = 0;
     m->rope_cap = 0;
@@ -1269,33 +1268,53 @@ int codec_finalize(CodecModel *m) {
     return 0;
 }
 
-static void *scratch_alloc(CodecModel *m, size_t bytes) {
+// hipMalloc remembered in `owner` (the state that frees it); zero: cleared
+// too.  who: what follows "qtts codec" in the failure message
+static void *dev_alloc(std::vector<void *> &owner, const char *who, size_t bytes, bool zero) {
     void *p = nullptr;
     const hipError_t prior = hipPeekAtLastError();
     const hipError_t e = hipMalloc(&p, bytes ? bytes : 16);
     if (e != hipSuccess) {
-        fprintf(stderr, "qtts codec: hipMalloc(%zu) failed: %s (last error before it: %s)\n", bytes,
+        fprintf(stderr, "qtts codec%s: hipMalloc(%zu) failed: %s (last error before it: %s)\n", who, bytes,
                 hipGetErrorName(e), hipGetErrorName(prior));
         return nullptr;
     }
-    m->scratch.push_back(p);
-    m->scratch_bytes += bytes;
+    if (zero) hipMemset(p, 0, bytes ? bytes : 16);
+    owner.push_back(p);
     return p;
 }
 
-// largest channel-major intermediate over the decoder at `cap` frames (elements)
-static size_t codec_buf_elems(const qtts_dims_t &d, int cap) {
-    size_t L = (size_t)cap * d.ratios[0] * d.ratios[1];
-    size_t mx = (size_t)d.clat * L * 4;  // ConvNeXt pw1 [L][4C]
-    if ((size_t)d.cdec * L > mx) mx = (size_t)d.cdec * L;
+static void *scratch_alloc(CodecModel *m, size_t bytes) { return dev_alloc(m->scratch, "", bytes, false); }
+
+// largest channel-major intermediate (elements) over the decoder at `frames`
+// frames, every row with a left margin of hm columns (0: the one-shot decode)
+static size_t codec_plane_elems(const qtts_dims_t &d, int frames, int hm) {
+    size_t L = (size_t)frames * d.ratios[0] * d.ratios[1];
+    size_t mx = (size_t)d.clat * L * 4 + (size_t)4 * d.clat * hm;  // ConvNeXt pw1 [L][4C]
+    if ((size_t)d.cdec * (L + hm) > mx) mx = (size_t)d.cdec * (L + hm);
     int C = d.cdec;
     for (int b = 0; b < 4; ++b) {
         L *= d.rates[b];
         C /= 2;
-        if ((size_t)C * L > mx) mx = (size_t)C * L;
+        if ((size_t)C * (L + hm) > mx) mx = (size_t)C * (L + hm);
     }
-    const size_t lat_t = (size_t)d.clat * cap;
+    const size_t lat_t = (size_t)d.clat * (frames + hm);
     return lat_t > mx ? lat_t : mx;
+}
+
+// RoPE table of positions [0, rows), [rows][hd] cos and sin (theta fixed at 1e4
+// in the reference, Cd.c:309; head_dim = hidden/heads, Cd.c:275)
+static void rope_table(int hd, int rows, std::vector<float> &c, std::vector<float> &s) {
+    const int half = hd / 2;
+    c.resize((size_t)rows * hd);
+    s.resize((size_t)rows * hd);
+    for (int p = 0; p < rows; ++p)
+        for (int i = 0; i < half; ++i) {
+            float freq = 1.0f / powf(10000.0f, (float)(2 * i) / (float)hd);
+            float ang = (float)p * freq;
+            c[(size_t)p * hd + i] = c[(size_t)p * hd + i + half] = cosf(ang);
+            s[(size_t)p * hd + i] = s[(size_t)p * hd + i + half] = sinf(ang);
+        }
 }
 
 // device bytes of one decode state for T frames (ensure_codec_state's allocations)
@@ -1303,7 +1322,7 @@ size_t codec_state_bytes(const CodecModel *m, int T) {
     const qtts_dims_t &d = m->d;
     const size_t cap = T < 64 ? 64 : T;
     const size_t hid = d.chid, kvd = (size_t)d.ckv * (d.chid / d.cheads);
-    return 4 * codec_buf_elems(d, (int)cap) * 4 + cap * (4 * hid + 2 * kvd + 2 * (size_t)d.cinter + 2) * 4 +
+    return 4 * codec_plane_elems(d, (int)cap, 0) * 4 + cap * (4 * hid + 2 * kvd + 2 * (size_t)d.cinter + 2) * 4 +
            ((size_t)8 << 20) * 4 + 2 * cap * (hid / d.cheads) * 4;
 }
 
@@ -1312,7 +1331,7 @@ static int ensure_codec_state(CodecModel *m, int T) {
     if (T <= m->t_cap) return 0;
     codec_free_state(m);
     const int cap = T < 64 ? 64 : T;
-    const size_t mx = codec_buf_elems(d, cap);
+    const size_t mx = codec_plane_elems(d, cap, 0);
     m->buf_elems = mx;
     m->bufA = (float *)scratch_alloc(m, mx * 4);
     m->bufB = (float *)scratch_alloc(m, mx * 4);
@@ -1334,16 +1353,8 @@ static int ensure_codec_state(CodecModel *m, int T) {
         return -1;
     hipLaunchKernelGGL(k_iota, dim3((cap + 255) / 256), dim3(256), 0, m->st, m->codes_tmp, cap, 0);
     hipLaunchKernelGGL(k_iota, dim3((cap + 255) / 256), dim3(256), 0, m->st, m->codes_tmp + cap, cap, 1);
-    // RoPE table (theta fixed at 1e4 in the reference, Cd.c:309; head_dim = hidden/heads, Cd.c:275)
-    const int hd = d.chid / d.cheads, half = hd / 2;
-    std::vector<float> c((size_t)cap * hd), s((size_t)cap * hd);
-    for (int p = 0; p < cap; ++p)
-        for (int i = 0; i < half; ++i) {
-            float freq = 1.0f / powf(10000.0f, (float)(2 * i) / (float)hd);
-            float ang = (float)p * freq;
-            c[(size_t)p * hd + i] = c[(size_t)p * hd + i + half] = cosf(ang);
-            s[(size_t)p * hd + i] = s[(size_t)p * hd + i + half] = sinf(ang);
-        }
+    std::vector<float> c, s;
+    rope_table(d.chid / d.cheads, cap, c, s);
     m->rope_cos = (float *)scratch_alloc(m, c.size() * 4);
     m->rope_sin = (float *)scratch_alloc(m, s.size() * 4);
     if (!m->rope_cos || !m->rope_sin) return -1;
@@ -1368,21 +1379,6 @@ static XGemm lin(const float *A, int M, int K, const float *W, int N, float *C, 
     g.M = M; g.N = N; g.K = K; g.amode = XA_ROWS; g.A = A; g.lda = K; g.bmode = XB_WT; g.B = W; g.ldb = K;
     g.C = C; g.ldc = N; g.emode = emode;
     return g;
-}
-
-// causal conv as implicit GEMM: out[co][L] = W[co][ci*K] . im2col(snake?(x))
-static int conv(CodecModel *m, const float *x, int ci, int L, const std::string &wn, const std::string &bn, int co,
-                int K, int dil, float *out, int emode, const float *sa, const float *sb, const float *res,
-                const float *ea = nullptr, const float *eb = nullptr) {
-    XGemm g;
-    g.M = co; g.N = L; g.K = ci * K;
-    g.amode = XA_ROWS; g.A = cw(m, wn); g.lda = ci * K; g.wt = cwt(m, wn, co, ci, K);
-    g.bmode = XB_CONV; g.B = x; g.ldb = L; g.Kw = K; g.dil = dil; g.pad = (K - 1) * dil; g.L = L;
-    g.sa = sa; g.sb = sb;
-    g.C = out; g.ldc = L; g.emode = emode; g.bias = bn.empty() ? nullptr : cw(m, bn); g.res = res; g.ldres = L;
-    g.ea = ea; g.eb = eb;
-    if (!g.A) return -1;
-    return xgm(m, g, m->st);
 }
 
 // transposed conv (stride s, kernel Kw = s * ntap) as s phase GEMMs
@@ -1443,163 +1439,334 @@ static int tconv_run(CodecModel *m, const XGemm &gin, hipStream_t st, int force 
     return 0;
 }
 
-static int tconv(CodecModel *m, const float *x, int ci, int L, const float *w, const float *bias, int co, int Kw,
-                 int s, float *out, const float *sa, const float *sb, hipStream_t st) {
+// causal conv as implicit GEMM: out[co][L] = W[co][ci*K] . im2col(snake?(x));
+// rows of x / out (and res) at stride ldx / ldo, input columns t >= tmin read
+static XGemm conv_desc(CodecModel *m, const float *x, int ldx, int ci, int L, const std::string &wn,
+                       const std::string &bn, int co, int K, int dil, float *out, int ldo, int emode, int tmin) {
+    XGemm g;
+    g.M = co; g.N = L; g.K = ci * K;
+    g.amode = XA_ROWS; g.A = cw(m, wn); g.lda = ci * K; g.wt = cwt(m, wn, co, ci, K);
+    g.bmode = XB_CONV; g.B = x; g.ldb = ldx; g.Kw = K; g.dil = dil; g.pad = (K - 1) * dil; g.L = L; g.tmin = tmin;
+    g.C = out; g.ldc = ldo; g.emode = emode; g.bias = bn.empty() ? nullptr : cw(m, bn); g.ldres = ldo;
+    return g;
+}
+
+// transposed conv (stride s, kernel Kw = s * ntap), bias in the epilogue
+static XGemm tconv_desc(const float *x, int ldx, int ci, int L, const float *w, const float *bias, int co, int Kw,
+                        int s, float *out, int ldo, const float *sa, const float *sb, int tmin) {
     XGemm g;
     g.M = co; g.N = L; g.K = ci * (Kw / s);
     g.amode = XA_TCONV_W; g.A = w; g.co = co; g.Kw = Kw; g.stride = s;
-    g.bmode = XB_TCONV; g.B = x; g.ldb = L; g.L = L; g.sa = sa; g.sb = sb;
-    g.C = out; g.ldc = L * s; g.emode = XE_BIAS_M; g.bias = bias;
-    return tconv_run(m, g, st);
+    g.bmode = XB_TCONV; g.B = x; g.ldb = ldx; g.L = L; g.tmin = tmin; g.sa = sa; g.sb = sb;
+    g.C = out; g.ldc = ldo; g.emode = XE_BIAS_M; g.bias = bias;
+    return g;
 }
 
-static int codec_transformer(CodecModel *m, const float *pc /*[lat][T]*/, int T, float *out /*[lat][T]*/) {
+// ===================================================================== the decoder network
+// The codec decoder is written down once: net_decode walks its stages (RVQ,
+// pre-conv, transformer, two upsample + ConvNeXt stages, the vocoder, clamp)
+// and net_transformer its layer stack.  They hold the weight names, shapes,
+// epilogues, the buffer rotation and the history-slot counter.  What differs
+// between the one-shot decode, the single stream and the multi-stream is
+// *placement*, and a Place carries it: how many planes a launch covers, the
+// left margin of their rows, which buffers, how a history slot travels around
+// its conv, where K/V rows land and how they are kept, and which twin of the
+// small per-stage kernels runs.  The defaults below are the single-plane ones
+// that the one-shot decode and the single stream share.
+struct LayerKV {
+    float *q, *k, *v;    // where a layer's rows are projected to
+    float *kc, *vc;      // the K / V rows attention reads
+};
+
+struct Place {
+    CodecModel *m = nullptr;
+    int n = 1;                       // planes (streams) a launch covers
+    int hm = 0;                      // left margin (columns) of every row; 0: nothing is carried, nothing left of column 0
+    float *A = nullptr, *B = nullptr, *Cb = nullptr, *D = nullptr;   // activations; A and B start past the margin
+    float *tx = nullptr, *txn = nullptr, *tq = nullptr, *tatt = nullptr, *tg = nullptr, *tu = nullptr;  // [n * T] rows
+    float *rvq_s = nullptr, *rvq_a = nullptr;
+    const float *rope_cos = nullptr, *rope_sin = nullptr;   // the table row of the first new position
+
+    int ld(int L) const { return hm + L; }
+    int tmin(int H) const { return hm ? -H : 0; }
+    int kvd() const { return m->d.ckv * (m->d.chid / m->d.cheads); }
+    // a state's buffers (CodecModel, CodecStream and CodecMStream name them alike)
+    template <class State>
+    void take(CodecModel *cm, State &S, int margin) {
+        m = cm;
+        hm = margin;
+        A = S.bufA + hm; B = S.bufB + hm; Cb = S.bufC; D = S.bufD;
+        tx = S.tx; txn = S.txn; tq = S.tq; tatt = S.tatt; tg = S.tg; tu = S.tu;
+        rope_cos = S.rope_cos; rope_sin = S.rope_sin;
+    }
+    virtual ~Place() {}
+    // history slot (C, H) into the margin of x (out false) / the last H columns of [margin | x[0, L)) back (out true)
+    virtual int hist(int, int, int, float *, int, int, bool) { return 0; }
+    // the plane axis of a conv form / of a linear form's plane-laid operands (seg_m columns a plane, C channels)
+    virtual void planes(XGemm &, int, int) {}
+    virtual void rows(XGemm &, int, int) {}
+    virtual void mark(int) {}
+    virtual void rvq(const int *codes, const float *ps, const float *pa, int T, int ldo, float *out) {
+        const qtts_dims_t &d = m->d;
+        const int vq = d.ccbdim / 2, half = d.clat / 2;
+        hipLaunchKernelGGL(k_rvq_sum, dim3(T), dim3(vq < 64 ? 64 : (vq + 63) / 64 * 64), 0, m->st, codes, T, d.cq, d.ccb,
+                           vq, m->cb, rvq_s, rvq_a);
+        hipLaunchKernelGGL(k_rvq_proj, dim3((half * T + 3) / 4), dim3(256), 0, m->st, ps, pa, rvq_s, rvq_a, vq, half, T,
+                           ldo, out);
+    }
+    virtual void dwconv(const float *x, int ldx, const float *w, const float *b, int C, int L, int K, float *y) {
+        hipLaunchKernelGGL(k_dwconv, dim3((unsigned)(((size_t)C * L + 255) / 256)), dim3(256), 0, m->st, x, ldx,
+                           tmin(K - 1), w, b, C, L, K, y, L);
+    }
+    virtual void ln_t(const float *x, int L, int C, const float *w, const float *b, float *y) {
+        hipLaunchKernelGGL(k_ln_t, dim3(L), dim3(256), 0, m->st, x, L, C, w, b, 1e-6f, y);
+    }
+    virtual void clamp(float *wav, int, int L, int) {
+        hipLaunchKernelGGL(k_clamp, dim3((L + 255) / 256), dim3(256), 0, m->st, wav, L);
+    }
+    // transformer: before / after the layers, a layer's rows, their rotation, what attention sees, after a layer
+    virtual void layers_begin(int) {}
+    virtual void layers_end(int) {}
+    virtual LayerKV layer(int l, int T) = 0;
+    virtual void rope(const LayerKV &r, int T) {
+        const qtts_dims_t &d = m->d;
+        const int hid = d.chid, hd = hid / d.cheads;
+        hipLaunchKernelGGL(k_rope_rows, dim3(T), dim3(256), 0, m->st, r.q, hid, d.cheads, hd, rope_cos, rope_sin);
+        hipLaunchKernelGGL(k_rope_rows, dim3(T), dim3(256), 0, m->st, r.k, d.ckv * hd, d.ckv, hd, rope_cos, rope_sin);
+    }
+    virtual void attn_rows(AttnArgs &a, int T) = 0;   // S, pos, row_b
+    virtual void layer_end(const LayerKV &, int) {}
+};
+
+#define NCK(x) do { if ((x) != 0) { fprintf(stderr, "qtts codec: stage failed at %s:%d\n", __FILE__, __LINE__); return -1; } } while (0)
+
+// a causal conv of the network; K > 1 takes the next history slot (in before
+// the conv and before its weights' first-use relayout, out after it), the
+// K = 1 residual conv takes none
+static int net_conv(Place &p, int &slot, float *x, int ldx, int ci, int L, const std::string &wn, const std::string &bn,
+                    int co, int K, int dil, float *out, int ldo, int emode, const float *sa, const float *sb,
+                    const float *res, const float *ea = nullptr, const float *eb = nullptr) {
+    const int H = (K - 1) * dil;
+    if (H > 0) KCK(p.hist(slot, ci, H, x, ldx, L, false));
+    XGemm g = conv_desc(p.m, x, ldx, ci, L, wn, bn, co, K, dil, out, ldo, emode, p.tmin(H));
+    g.sa = sa; g.sb = sb; g.res = res; g.ea = ea; g.eb = eb;
+    p.planes(g, ci, co);
+    if (!g.A) return -1;
+    KCK(xgm(p.m, g, p.m->st));
+    if (H > 0) KCK(p.hist(slot++, ci, H, x, ldx, L, true));
+    return 0;
+}
+
+// a transposed conv of the network; K = 2s takes the next history slot (the last input frame), K = s none
+static int net_tconv(Place &p, int &slot, float *x, int ldx, int ci, int L, const float *w, const float *bias, int co,
+                     int Kw, int s, float *out, int ldo, const float *sa, const float *sb) {
+    const int H = Kw / s - 1;
+    if (H > 0) KCK(p.hist(slot, ci, H, x, ldx, L, false));
+    XGemm g = tconv_desc(x, ldx, ci, L, w, bias, co, Kw, s, out, ldo, sa, sb, p.tmin(H));
+    p.planes(g, ci, co);
+    KCK(tconv_run(p.m, g, p.m->st));
+    if (H > 0) KCK(p.hist(slot++, ci, H, x, ldx, L, true));
+    return 0;
+}
+
+static const int kResDil[3] = {1, 3, 9};   // the ResUnits' dilations
+
+// (C, H) of the history slots in the order net_decode consumes them: the
+// last (K-1)*dil input columns of a conv, the last input frame of a K = 2s
+// transposed conv.  A stream's begin allocates by it; a Place's hist refuses a
+// stage that asks for something else, so the two cannot drift apart unseen
+static std::vector<std::pair<int, int>> codec_hist_slots(const qtts_dims_t &d) {
+    std::vector<std::pair<int, int>> v;
+    v.push_back({d.ccbdim, 2});                  // 0 pre-conv k3
+    v.push_back({d.clat, 6});                    // 1 upsample 0 dwconv k7
+    v.push_back({d.clat, 6});                    // 2 upsample 1 dwconv k7
+    v.push_back({d.clat, 6});                    // 3 vocoder conv0 k7
+    int C = d.cdec;
+    for (int b = 0; b < 4; ++b) {
+        v.push_back({C, 1});                     // block tconv (K = 2r): last input frame
+        for (int u = 0; u < 3; ++u) v.push_back({C / 2, 6 * kResDil[u]});   // ResUnit conv1 k7 dil
+        C /= 2;
+    }
+    v.push_back({C, 6});                         // final conv k7
+    return v;
+}
+
+// the transformer over the n * T stacked rows of the planes pc [lat][ldp] -> out [lat][ldo]
+static int net_transformer(Place &p, const float *pc, int ldp, int T, float *out, int ldo) {
+    CodecModel *m = p.m;
     const qtts_dims_t &d = m->d;
     const int lat = d.clat, hid = d.chid, nh = d.cheads, nkv = d.ckv, hd = hid / nh, kvd = nkv * hd, I = d.cinter;
+    const int M = p.n * T;
     hipStream_t st = m->st;
     const std::string P = "decoder.pre_transformer.";
     XGemm g;
-    g.M = T; g.N = hid; g.K = lat; g.amode = XA_TRANS; g.A = pc; g.lda = T; g.bmode = XB_WT;
-    g.B = cw(m, P + "input_proj.weight"); g.ldb = lat; g.C = m->tx; g.ldc = hid;
+    g.M = M; g.N = hid; g.K = lat; g.amode = XA_TRANS; g.A = pc; g.lda = ldp; g.bmode = XB_WT;
+    g.B = cw(m, P + "input_proj.weight"); g.ldb = lat; g.C = p.tx; g.ldc = hid;
     g.bias = cw(m, P + "input_proj.bias");
     g.emode = g.bias ? XE_BIAS_N : XE_STORE;
+    p.rows(g, T, lat);
     KCK(xgm(m, g, st));
-    float *q = m->tq, *k = m->tq + (size_t)T * hid, *v = k + (size_t)T * kvd;
+    p.layers_begin(T);
     for (int l = 0; l < d.clayers; ++l) {
-        const std::string p = P + "layers." + std::to_string(l) + ".";
-        hipLaunchKernelGGL(k_rms_rows, dim3(T), dim3(256), 0, st, m->tx, hid, cw(m, p + "input_layernorm.weight"),
-                           d.ceps, m->txn);
-        KCK(xgm(m, lin(m->txn, T, hid, cw(m, p + "self_attn.q_proj.weight"), hid, q, XE_STORE), st));
-        KCK(xgm(m, lin(m->txn, T, hid, cw(m, p + "self_attn.k_proj.weight"), kvd, k, XE_STORE), st));
-        KCK(xgm(m, lin(m->txn, T, hid, cw(m, p + "self_attn.v_proj.weight"), kvd, v, XE_STORE), st));
-        hipLaunchKernelGGL(k_rope_rows, dim3(T), dim3(256), 0, st, q, hid, nh, hd, m->rope_cos, m->rope_sin);
-        hipLaunchKernelGGL(k_rope_rows, dim3(T), dim3(256), 0, st, k, kvd, nkv, hd, m->rope_cos, m->rope_sin);
+        const std::string q = P + "layers." + std::to_string(l) + ".";
+        const LayerKV r = p.layer(l, T);
+        hipLaunchKernelGGL(k_rms_rows, dim3(M), dim3(256), 0, st, p.tx, hid, cw(m, q + "input_layernorm.weight"),
+                           d.ceps, p.txn);
+        KCK(xgm(m, lin(p.txn, M, hid, cw(m, q + "self_attn.q_proj.weight"), hid, r.q, XE_STORE), st));
+        KCK(xgm(m, lin(p.txn, M, hid, cw(m, q + "self_attn.k_proj.weight"), kvd, r.k, XE_STORE), st));
+        KCK(xgm(m, lin(p.txn, M, hid, cw(m, q + "self_attn.v_proj.weight"), kvd, r.v, XE_STORE), st));
+        p.rope(r, T);
         AttnArgs a;
-        a.mode = 1; a.qkv = q; a.ld_qkv = hid; a.kc = k; a.vc = v; a.S = T; a.pos = m->codes_tmp;
-        a.row_b = m->codes_tmp + m->t_cap; a.NH = nh; a.KV = nkv; a.HD = hd; a.out = m->tatt; a.ld_out = hid;
-        a.nrows = T; a.win = d.cwin;
+        a.mode = 1; a.qkv = r.q; a.ld_qkv = hid; a.kc = r.kc; a.vc = r.vc; a.NH = nh; a.KV = nkv; a.HD = hd;
+        a.out = p.tatt; a.ld_out = hid; a.nrows = M; a.win = d.cwin;
+        p.attn_rows(a, T);
         KCK(qtts_attention(a, st));
-        const float *ls1 = cw(m, p + "self_attn_layer_scale.scale");
-        XGemm o = lin(m->tatt, T, hid, cw(m, p + "self_attn.o_proj.weight"), hid, m->tx, XE_SCALE_RESID_N);
-        o.vec = ls1;
+        const float *ls1 = cw(m, q + "self_attn_layer_scale.scale");
         if (!ls1) return -1;
+        XGemm o = lin(p.tatt, M, hid, cw(m, q + "self_attn.o_proj.weight"), hid, p.tx, XE_SCALE_RESID_N);
+        o.vec = ls1;
         KCK(xgm(m, o, st));
-        hipLaunchKernelGGL(k_rms_rows, dim3(T), dim3(256), 0, st, m->tx, hid,
-                           cw(m, p + "post_attention_layernorm.weight"), d.ceps, m->txn);
-        KCK(xgm(m, lin(m->txn, T, hid, cw(m, p + "mlp.gate_proj.weight"), I, m->tg, XE_STORE), st));
-        XGemm u = lin(m->txn, T, hid, cw(m, p + "mlp.up_proj.weight"), I, m->tu, XE_SILU_MUL);
-        u.aux = m->tg; u.ldaux = I;
+        hipLaunchKernelGGL(k_rms_rows, dim3(M), dim3(256), 0, st, p.tx, hid,
+                           cw(m, q + "post_attention_layernorm.weight"), d.ceps, p.txn);
+        KCK(xgm(m, lin(p.txn, M, hid, cw(m, q + "mlp.gate_proj.weight"), I, p.tg, XE_STORE), st));
+        XGemm u = lin(p.txn, M, hid, cw(m, q + "mlp.up_proj.weight"), I, p.tu, XE_SILU_MUL);
+        u.aux = p.tg; u.ldaux = I;
         KCK(xgm(m, u, st));
-        const float *ls2 = cw(m, p + "mlp_layer_scale.scale");
-        XGemm dn = lin(m->tu, T, I, cw(m, p + "mlp.down_proj.weight"), hid, m->tx, XE_SCALE_RESID_N);
-        dn.vec = ls2;
+        const float *ls2 = cw(m, q + "mlp_layer_scale.scale");
         if (!ls2) return -1;
+        XGemm dn = lin(p.tu, M, I, cw(m, q + "mlp.down_proj.weight"), hid, p.tx, XE_SCALE_RESID_N);
+        dn.vec = ls2;
         KCK(xgm(m, dn, st));
+        p.layer_end(r, T);
     }
+    p.layers_end(T);
     const float *fn = cw(m, P + "norm.weight");
-    const float *xin = m->tx;
+    const float *xin = p.tx;
     if (fn) {
-        hipLaunchKernelGGL(k_rms_rows, dim3(T), dim3(256), 0, st, m->tx, hid, fn, d.ceps, m->txn);
-        xin = m->txn;
+        hipLaunchKernelGGL(k_rms_rows, dim3(M), dim3(256), 0, st, p.tx, hid, fn, d.ceps, p.txn);
+        xin = p.txn;
     }
-    XGemm og = lin(xin, T, hid, cw(m, P + "output_proj.weight"), lat, out, XE_BIAS_T);
+    XGemm og = lin(xin, M, hid, cw(m, P + "output_proj.weight"), lat, out, XE_BIAS_T);
     og.bias = cw(m, P + "output_proj.bias");
-    og.ldc = T;
+    og.ldc = ldo;
+    p.rows(og, T, lat);
     if (!og.bias) return -1;
     return xgm(m, og, st);
 }
 
-// the whole decode enqueued on m->st; the clamped waveform stays in m's
-// scratch (*wav, *L samples) until the next use of m
-static int codec_decode_enqueue(CodecModel *m, const int *codes, int T, float **wav_out, int *L_out) {
+// T frames of every plane of `p`, all of it enqueued on m->st; *wav: the
+// waveform rows [1][ld(L)] of the planes after the clamp, *L_out samples each
+static int net_decode(Place &p, const int *codes, int T, float **wav_out, int *L_out) {
+    CodecModel *m = p.m;
     const qtts_dims_t &d = m->d;
-    if (ensure_codec_state(m, T)) return -1;
     hipStream_t st = m->st;
-    const int lat = d.clat, vq = d.ccbdim / 2, half = lat / 2;
-    float *A = m->bufA, *B = m->bufB, *Cb = m->bufC, *D = m->bufD;
-#define DCK(x) do { if ((x) != 0) { fprintf(stderr, "qtts codec: stage failed at %s:%d\n", __FILE__, __LINE__); return -1; } } while (0)
-    m->timed = false;
-    if (m->timing && !m->tev[0])
-        for (hipEvent_t &e : m->tev)
-            if (hipEventCreate(&e) != hipSuccess) { e = nullptr; m->timing = false; }
-    auto mark = [&](int i) { if (m->timing) hipEventRecord(m->tev[i], st); };
-    mark(0);
+    const int lat = d.clat, n = p.n;
+    float *A = p.A, *B = p.B, *Cb = p.Cb, *D = p.D;
+    int L = T, ld = p.ld(L), slot = 0;
+    p.mark(0);
     // 1. RVQ dequantise -> A [half][T]
-    hipLaunchKernelGGL(k_rvq_sum, dim3(T), dim3(vq < 64 ? 64 : (vq + 63) / 64 * 64), 0, st, codes, T, d.cq, d.ccb, vq,
-                       m->cb, B, Cb);
-    hipLaunchKernelGGL(k_rvq_proj, dim3((half * T + 3) / 4), dim3(256), 0, st,
-                       cw(m, "decoder.quantizer.rvq_first.output_proj.weight"),
-                       cw(m, "decoder.quantizer.rvq_rest.output_proj.weight"), B, Cb, vq, half, T, T, A);
-    mark(1);
+    p.rvq(codes, cw(m, "decoder.quantizer.rvq_first.output_proj.weight"),
+          cw(m, "decoder.quantizer.rvq_rest.output_proj.weight"), T, ld, A);
+    p.mark(1);
     // 2. pre-conv k=3 -> B [lat][T]
-    DCK(conv(m, A, d.ccbdim, T, "decoder.pre_conv.conv.weight", "decoder.pre_conv.conv.bias", lat, 3, 1, B, XE_BIAS_M,
-             nullptr, nullptr, nullptr));
-    mark(2);
+    NCK(net_conv(p, slot, A, ld, d.ccbdim, L, "decoder.pre_conv.conv.weight", "decoder.pre_conv.conv.bias", lat, 3, 1,
+                 B, ld, XE_BIAS_M, nullptr, nullptr, nullptr));
+    p.mark(2);
     // 3. transformer -> A [lat][T]
-    DCK(codec_transformer(m, B, T, A));
-    mark(3);
-    // 4. upsample: transposed conv + ConvNeXt, x2
-    int L = T;
+    NCK(net_transformer(p, B, ld, T, A, ld));
+    p.mark(3);
+    // 4. upsample: transposed conv (K = s, no history) + ConvNeXt, x2
     float *cur = A;
     for (int s = 0; s < 2; ++s) {
         const int f = d.ratios[s];
-        const std::string p = "decoder.upsample." + std::to_string(s) + ".";
+        const std::string q = "decoder.upsample." + std::to_string(s) + ".";
         float *up = cur == A ? B : A;
-        DCK(tconv(m, cur, lat, L, cw(m, p + "0.conv.weight"), cw(m, p + "0.conv.bias"), lat, f, f, up, nullptr, nullptr,
-                  st));
+        const int ldu = p.ld(L * f);
+        NCK(net_tconv(p, slot, cur, ld, lat, L, cw(m, q + "0.conv.weight"), cw(m, q + "0.conv.bias"), lat, f, f, up, ldu,
+                      nullptr, nullptr));
         L *= f;
+        ld = ldu;
         cur = up;
         // ConvNeXt: dwconv -> LN (time-major) -> pw1+GELU -> pw2*gamma (+res, channel-major)
-        hipLaunchKernelGGL(k_dwconv, dim3((unsigned)(((size_t)lat * L + 255) / 256)), dim3(256), 0, st, cur, L, 0,
-                           cw(m, p + "1.dwconv.conv.weight"), cw(m, p + "1.dwconv.conv.bias"), lat, L, 7, Cb, L);
-        hipLaunchKernelGGL(k_ln_t, dim3(L), dim3(256), 0, st, Cb, L, lat, cw(m, p + "1.norm.weight"),
-                           cw(m, p + "1.norm.bias"), 1e-6f, D);
-        XGemm g1 = lin(D, L, lat, cw(m, p + "1.pwconv1.weight"), 4 * lat, Cb, XE_BIAS_N_GELU);
-        g1.bias = cw(m, p + "1.pwconv1.bias");
-        DCK(xgm(m, g1, st));
-        XGemm g2 = lin(Cb, L, 4 * lat, cw(m, p + "1.pwconv2.weight"), lat, cur, XE_BIAS_GAMMA_RES_T);
-        g2.bias = cw(m, p + "1.pwconv2.bias");
-        g2.vec = cw(m, p + "1.gamma");
-        g2.res = cur; g2.ldres = L; g2.ldc = L;
-        DCK(xgm(m, g2, st));
+        NCK(p.hist(slot, lat, 6, cur, ld, L, false));
+        p.dwconv(cur, ld, cw(m, q + "1.dwconv.conv.weight"), cw(m, q + "1.dwconv.conv.bias"), lat, L, 7, Cb);
+        NCK(p.hist(slot++, lat, 6, cur, ld, L, true));
+        p.ln_t(Cb, L, lat, cw(m, q + "1.norm.weight"), cw(m, q + "1.norm.bias"), D);
+        XGemm g1 = lin(D, n * L, lat, cw(m, q + "1.pwconv1.weight"), 4 * lat, Cb, XE_BIAS_N_GELU);
+        g1.bias = cw(m, q + "1.pwconv1.bias");
+        NCK(xgm(m, g1, st));
+        XGemm g2 = lin(Cb, n * L, 4 * lat, cw(m, q + "1.pwconv2.weight"), lat, cur, XE_BIAS_GAMMA_RES_T);
+        g2.bias = cw(m, q + "1.pwconv2.bias");
+        g2.vec = cw(m, q + "1.gamma");
+        g2.res = cur; g2.ldres = ld; g2.ldc = ld;
+        p.rows(g2, L, lat);
+        NCK(xgm(m, g2, st));
     }
-    mark(4);
+    p.mark(4);
     // 5. vocoder
     float *voc = cur == A ? B : A;
-    DCK(conv(m, cur, lat, L, "decoder.decoder.0.conv.weight", "decoder.decoder.0.conv.bias", d.cdec, 7, 1, voc,
-             XE_BIAS_M, nullptr, nullptr, nullptr));
+    NCK(net_conv(p, slot, cur, ld, lat, L, "decoder.decoder.0.conv.weight", "decoder.decoder.0.conv.bias", d.cdec, 7, 1,
+                 voc, ld, XE_BIAS_M, nullptr, nullptr, nullptr));
     int C = d.cdec;
-    static const int dil[3] = {1, 3, 9};
     for (int b = 0; b < 4; ++b) {
         const int r = d.rates[b], co = C / 2;
-        const std::string p = "decoder.decoder." + std::to_string(b + 1) + ".block.";
+        const std::string q = "decoder.decoder." + std::to_string(b + 1) + ".block.";
         float *nx = voc == A ? B : A;
-        DCK(tconv(m, voc, C, L, cw(m, p + "1.conv.weight"), cw(m, p + "1.conv.bias"), co, 2 * r, r, nx,
-                  cw(m, p + "0.alpha"), cw(m, p + "0.beta"), st));
+        const int ldn = p.ld(L * r);
+        NCK(net_tconv(p, slot, voc, ld, C, L, cw(m, q + "1.conv.weight"), cw(m, q + "1.conv.bias"), co, 2 * r, r, nx,
+                      ldn, cw(m, q + "0.alpha"), cw(m, q + "0.beta")));
         L *= r;
+        ld = ldn;
         C = co;
         voc = nx;
         for (int u = 0; u < 3; ++u) {
-            const std::string q = p + std::to_string(u + 2) + ".";
-            // conv1(snake1(x)) -> snake2 fused in the epilogue -> Cb
-            DCK(conv(m, voc, C, L, q + "conv1.conv.weight", q + "conv1.conv.bias", C, 7, dil[u], Cb, XE_BIAS_M_SNAKE,
-                     cw(m, q + "act1.alpha"), cw(m, q + "act1.beta"), nullptr, cw(m, q + "act2.alpha"),
-                     cw(m, q + "act2.beta")));
+            const std::string ru = q + std::to_string(u + 2) + ".";
+            // conv1(snake1(x)) -> snake2 fused in the epilogue -> Cb (compact rows)
+            NCK(net_conv(p, slot, voc, ld, C, L, ru + "conv1.conv.weight", ru + "conv1.conv.bias", C, 7, kResDil[u], Cb,
+                         L, XE_BIAS_M_SNAKE, cw(m, ru + "act1.alpha"), cw(m, ru + "act1.beta"), nullptr,
+                         cw(m, ru + "act2.alpha"), cw(m, ru + "act2.beta")));
             // conv2 (k=1) + residual, in place on x
-            DCK(conv(m, Cb, C, L, q + "conv2.conv.weight", q + "conv2.conv.bias", C, 1, 1, voc, XE_BIAS_M_RES, nullptr,
-                     nullptr, voc));
+            NCK(net_conv(p, slot, Cb, L, C, L, ru + "conv2.conv.weight", ru + "conv2.conv.bias", C, 1, 1, voc, ld,
+                         XE_BIAS_M_RES, nullptr, nullptr, voc));
         }
     }
     // final SnakeBeta + conv -> 1 channel, clamp
     float *wav = voc == A ? B : A;
-    DCK(conv(m, voc, C, L, "decoder.decoder.6.conv.weight", "decoder.decoder.6.conv.bias", 1, 7, 1, wav, XE_BIAS_M,
-             cw(m, "decoder.decoder.5.alpha"), cw(m, "decoder.decoder.5.beta"), nullptr));
-    hipLaunchKernelGGL(k_clamp, dim3((L + 255) / 256), dim3(256), 0, st, wav, L);
-    mark(5);
+    NCK(net_conv(p, slot, voc, ld, C, L, "decoder.decoder.6.conv.weight", "decoder.decoder.6.conv.bias", 1, 7, 1, wav,
+                 ld, XE_BIAS_M, cw(m, "decoder.decoder.5.alpha"), cw(m, "decoder.decoder.5.beta"), nullptr));
+    p.clamp(wav, ld, L, T);
+    p.mark(5);
     *wav_out = wav;
     *L_out = L;
+    return 0;
+}
+
+// ---------------------------------------------------------------- the one-shot decode's placement
+// one plane, no margin, nothing carried; k and v packed behind q in m->tq
+struct FullPlace : Place {
+    explicit FullPlace(CodecModel *cm) {
+        take(cm, *cm, 0);
+        rvq_s = B; rvq_a = Cb;
+    }
+    void mark(int i) override { if (m->timing) hipEventRecord(m->tev[i], m->st); }
+    LayerKV layer(int, int T) override {
+        float *k = tq + (size_t)T * m->d.chid, *v = k + (size_t)T * kvd();
+        return {tq, k, v, k, v};
+    }
+    void attn_rows(AttnArgs &a, int T) override { a.S = T; a.pos = m->codes_tmp; a.row_b = m->codes_tmp + m->t_cap; }
+};
+
+// the whole decode enqueued on m->st; the clamped waveform stays in m's
+// scratch (*wav, *L samples) until the next use of m
+static int codec_decode_enqueue(CodecModel *m, const int *codes, int T, float **wav_out, int *L_out) {
+    if (ensure_codec_state(m, T)) return -1;
+    m->timed = false;
+    if (m->timing && !m->tev[0])
+        for (hipEvent_t &e : m->tev)
+            if (hipEventCreate(&e) != hipSuccess) { e = nullptr; m->timing = false; }
+    FullPlace p(m);
+    if (net_decode(p, codes, T, wav_out, L_out)) return -1;
     return hipGetLastError() == hipSuccess ? 0 : -1;
-#undef DCK
 }
 
 float *codec_decode(CodecModel *m, const int *codes, int T, int *out_samples) {
@@ -1731,7 +1898,8 @@ extern "C" int qtts_hip_transposed_conv1d(float *out, const float *in, const flo
                                           int k, int stride, int L, void *stream) {
     if (k % stride) return -1;
     CodecModel dummy;
-    int rc = tconv(&dummy, in, ci, L, w, b, co, k, stride, out, nullptr, nullptr, (hipStream_t)stream);
+    int rc = tconv_run(&dummy, tconv_desc(in, L, ci, L, w, b, co, k, stride, out, L * stride, nullptr, nullptr, 0),
+                       (hipStream_t)stream);
     if (!dummy.wt.empty()) {
         if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) rc = -1;
         for (auto &kv : dummy.wt) hipFree(kv.second);
@@ -1907,147 +2075,68 @@ namespace {
 constexpr int kStreamChunk = 16;      // frames per internal chunk
 constexpr int kStreamChunkMax = 128;  // largest chunk a begin may ask for
 
-void *salloc(CodecStream &S, size_t bytes) {
-    void *p = nullptr;
-    const hipError_t prior = hipPeekAtLastError();
-    const hipError_t e = hipMalloc(&p, bytes ? bytes : 16);
-    if (e != hipSuccess) {
-        fprintf(stderr, "qtts codec stream: hipMalloc(%zu) failed: %s (last error before it: %s)\n", bytes,
-                hipGetErrorName(e), hipGetErrorName(prior));
-        return nullptr;
-    }
-    hipMemset(p, 0, bytes ? bytes : 16);
-    S.allocs.push_back(p);
-    return p;
-}
-
 void copy2d(hipStream_t st, float *dst, int ldd, const float *src, int lds, int rows, int cols) {
     const size_t n = (size_t)rows * cols;
     if (n) hipLaunchKernelGGL(k_copy2d, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, dst, ldd, src, lds, rows, cols);
 }
 
-// history in: slot -> margin of x;  history out: last H columns of [margin | x[0, L)) -> slot
-void hist_in(CodecModel *m, int slot, float *x, int ldx) {
-    CodecStream &S = m->cs;
-    const int H = S.hist_h[slot];
-    copy2d(m->st, x - H, ldx, S.hist[slot], H, S.hist_c[slot], H);
+// the history slots of a stream state (codec_hist_slots), `planes` [C][H]
+// blocks each, zeroed; their bytes, or 0 where an allocation failed
+template <class State>
+size_t add_hist_slots(State &S, const qtts_dims_t &d, int planes, const char *who) {
+    size_t total = 0;
+    for (const std::pair<int, int> &ch : codec_hist_slots(d)) {
+        const size_t bytes = (size_t)planes * ch.first * (ch.second > 0 ? ch.second : 1) * 4;
+        S.hist_c.push_back(ch.first);
+        S.hist_h.push_back(ch.second);
+        S.hist.push_back((float *)dev_alloc(S.allocs, who, bytes, true));
+        if (!S.hist.back()) return 0;
+        total += bytes;
+    }
+    return total;
 }
-void hist_out(CodecModel *m, int slot, const float *x, int ldx, int L) {
-    CodecStream &S = m->cs;
-    const int H = S.hist_h[slot];
-    copy2d(m->st, S.hist[slot], H, x + L - H, ldx, S.hist_c[slot], H);
-}
-
-int sconv(CodecModel *m, int slot, float *x, int ldx, int ci, int L, const std::string &wn, const std::string &bn,
-          int co, int K, int dil, float *out, int ldo, int emode, const float *sa, const float *sb, const float *res,
-          const float *ea = nullptr, const float *eb = nullptr) {
-    const int H = (K - 1) * dil;
-    if (H > 0) hist_in(m, slot, x, ldx);
-    XGemm g;
-    g.M = co; g.N = L; g.K = ci * K;
-    g.amode = XA_ROWS; g.A = cw(m, wn); g.lda = ci * K; g.wt = cwt(m, wn, co, ci, K);
-    g.bmode = XB_CONV; g.B = x; g.ldb = ldx; g.Kw = K; g.dil = dil; g.pad = H; g.L = L; g.tmin = -H;
-    g.sa = sa; g.sb = sb;
-    g.C = out; g.ldc = ldo; g.emode = emode; g.bias = bn.empty() ? nullptr : cw(m, bn); g.res = res; g.ldres = ldo;
-    g.ea = ea; g.eb = eb;
-    if (!g.A) return -1;
-    KCK(xgm(m, g, m->st));
-    if (H > 0) hist_out(m, slot, x, ldx, L);
-    return 0;
+template <class State>
+bool hist_slot_is(const State &S, int slot, int C, int H) {
+    return slot >= 0 && slot < (int)S.hist.size() && S.hist_c[slot] == C && S.hist_h[slot] == H;
 }
 
-int stconv(CodecModel *m, int slot, float *x, int ldx, int ci, int L, const float *w, const float *bias, int co, int Kw,
-           int s, float *out, int ldo, const float *sa, const float *sb) {
-    const int H = Kw / s - 1;
-    if (H > 0) hist_in(m, slot, x, ldx);
-    XGemm g;
-    g.M = co; g.N = L; g.K = ci * (Kw / s);
-    g.amode = XA_TCONV_W; g.A = w; g.co = co; g.Kw = Kw; g.stride = s;
-    g.bmode = XB_TCONV; g.B = x; g.ldb = ldx; g.L = L; g.tmin = -H; g.sa = sa; g.sb = sb;
-    g.C = out; g.ldc = ldo; g.emode = XE_BIAS_M; g.bias = bias;
-    KCK(tconv_run(m, g, m->st));
-    if (H > 0) hist_out(m, slot, x, ldx, L);
-    return 0;
-}
-
-int stransformer(CodecModel *m, const float *pc, int ldp, int T, float *out, int ldo) {
-    CodecStream &S = m->cs;
-    const qtts_dims_t &d = m->d;
-    const int lat = d.clat, hid = d.chid, nh = d.cheads, nkv = d.ckv, hd = hid / nh, kvd = nkv * hd, I = d.cinter;
-    const int keepmax = d.cwin - 1;
-    hipStream_t st = m->st;
-    const std::string P = "decoder.pre_transformer.";
-    XGemm g;
-    g.M = T; g.N = hid; g.K = lat; g.amode = XA_TRANS; g.A = pc; g.lda = ldp; g.bmode = XB_WT;
-    g.B = cw(m, P + "input_proj.weight"); g.ldb = lat; g.C = S.tx; g.ldc = hid;
-    g.bias = cw(m, P + "input_proj.bias");
-    g.emode = g.bias ? XE_BIAS_N : XE_STORE;
-    KCK(xgm(m, g, st));
-    const float *cs = S.rope_cos + (size_t)S.pos0 * hd, *sn = S.rope_sin + (size_t)S.pos0 * hd;
-    const int hl = S.hl;
-    for (int l = 0; l < d.clayers; ++l) {
-        const std::string p = P + "layers." + std::to_string(l) + ".";
-        float *kcl = S.kc[l], *vcl = S.vc[l];
-        hipLaunchKernelGGL(k_rms_rows, dim3(T), dim3(256), 0, st, S.tx, hid, cw(m, p + "input_layernorm.weight"),
-                           d.ceps, S.txn);
-        KCK(xgm(m, lin(S.txn, T, hid, cw(m, p + "self_attn.q_proj.weight"), hid, S.tq, XE_STORE), st));
-        KCK(xgm(m, lin(S.txn, T, hid, cw(m, p + "self_attn.k_proj.weight"), kvd, kcl + (size_t)hl * kvd, XE_STORE), st));
-        KCK(xgm(m, lin(S.txn, T, hid, cw(m, p + "self_attn.v_proj.weight"), kvd, vcl + (size_t)hl * kvd, XE_STORE), st));
-        hipLaunchKernelGGL(k_rope_rows, dim3(T), dim3(256), 0, st, S.tq, hid, nh, hd, cs, sn);
-        hipLaunchKernelGGL(k_rope_rows, dim3(T), dim3(256), 0, st, kcl + (size_t)hl * kvd, kvd, nkv, hd, cs, sn);
-        AttnArgs a;
-        a.mode = 1; a.qkv = S.tq; a.ld_qkv = hid; a.kc = kcl; a.vc = vcl; a.S = hl + T; a.pos = S.iota + hl;
-        a.row_b = S.zeros; a.NH = nh; a.KV = nkv; a.HD = hd; a.out = S.tatt; a.ld_out = hid;
-        a.nrows = T; a.win = d.cwin;
-        KCK(qtts_attention(a, st));
-        const float *ls1 = cw(m, p + "self_attn_layer_scale.scale");
-        if (!ls1) return -1;
-        XGemm o = lin(S.tatt, T, hid, cw(m, p + "self_attn.o_proj.weight"), hid, S.tx, XE_SCALE_RESID_N);
-        o.vec = ls1;
-        KCK(xgm(m, o, st));
-        hipLaunchKernelGGL(k_rms_rows, dim3(T), dim3(256), 0, st, S.tx, hid,
-                           cw(m, p + "post_attention_layernorm.weight"), d.ceps, S.txn);
-        KCK(xgm(m, lin(S.txn, T, hid, cw(m, p + "mlp.gate_proj.weight"), I, S.tg, XE_STORE), st));
-        XGemm u = lin(S.txn, T, hid, cw(m, p + "mlp.up_proj.weight"), I, S.tu, XE_SILU_MUL);
-        u.aux = S.tg; u.ldaux = I;
-        KCK(xgm(m, u, st));
-        const float *ls2 = cw(m, p + "mlp_layer_scale.scale");
-        if (!ls2) return -1;
-        XGemm dn = lin(S.tu, T, I, cw(m, p + "mlp.down_proj.weight"), hid, S.tx, XE_SCALE_RESID_N);
-        dn.vec = ls2;
-        KCK(xgm(m, dn, st));
-        // keep the last window-1 rows for the next chunk
-        const int tot = hl + T, keep = tot < keepmax ? tot : keepmax;
+// the single stream's placement: one plane with the margin, history by
+// copy2d pairs, k and v projected straight into the layer's cache at row hl,
+// the keep-shift after every layer
+struct StreamPlace : Place {
+    CodecStream &S;
+    explicit StreamPlace(CodecModel *cm) : S(cm->cs) {
+        take(cm, S, S.hm);
+        rvq_s = S.rvq_s; rvq_a = S.rvq_a;
+        const size_t row0 = (size_t)S.pos0 * (m->d.chid / m->d.cheads);   // the table continues at pos0
+        rope_cos += row0; rope_sin += row0;
+    }
+    int hist(int slot, int C, int H, float *x, int ldx, int L, bool out) override {
+        if (!hist_slot_is(S, slot, C, H)) return -1;
+        if (out) copy2d(m->st, S.hist[slot], H, x + L - H, ldx, C, H);
+        else copy2d(m->st, x - H, ldx, S.hist[slot], H, C, H);
+        return 0;
+    }
+    LayerKV layer(int l, int) override {
+        float *k = S.kc[l] + (size_t)S.hl * kvd(), *v = S.vc[l] + (size_t)S.hl * kvd();
+        return {tq, k, v, S.kc[l], S.vc[l]};
+    }
+    void attn_rows(AttnArgs &a, int T) override { a.S = S.hl + T; a.pos = S.iota + S.hl; a.row_b = S.zeros; }
+    // keep the last window-1 rows for the next chunk
+    void layer_end(const LayerKV &r, int T) override {
+        const int keepmax = m->d.cwin - 1, tot = S.hl + T, keep = tot < keepmax ? tot : keepmax, kd = kvd();
         if (keep > 0 && tot > keep) {
-            copy2d(st, S.kvtmp, kvd, kcl + (size_t)(tot - keep) * kvd, kvd, keep, kvd);
-            copy2d(st, kcl, kvd, S.kvtmp, kvd, keep, kvd);
-            copy2d(st, S.kvtmp, kvd, vcl + (size_t)(tot - keep) * kvd, kvd, keep, kvd);
-            copy2d(st, vcl, kvd, S.kvtmp, kvd, keep, kvd);
+            copy2d(m->st, S.kvtmp, kd, r.kc + (size_t)(tot - keep) * kd, kd, keep, kd);
+            copy2d(m->st, r.kc, kd, S.kvtmp, kd, keep, kd);
+            copy2d(m->st, S.kvtmp, kd, r.vc + (size_t)(tot - keep) * kd, kd, keep, kd);
+            copy2d(m->st, r.vc, kd, S.kvtmp, kd, keep, kd);
         }
     }
-    {
-        const int tot = hl + T;
+    void layers_end(int T) override {
+        const int keepmax = m->d.cwin - 1, tot = S.hl + T;
         S.hl = tot < keepmax ? tot : keepmax;
     }
-    const float *fn = cw(m, P + "norm.weight");
-    const float *xin = S.tx;
-    if (fn) {
-        hipLaunchKernelGGL(k_rms_rows, dim3(T), dim3(256), 0, st, S.tx, hid, fn, d.ceps, S.txn);
-        xin = S.txn;
-    }
-    XGemm og = lin(xin, T, hid, cw(m, P + "output_proj.weight"), lat, out, XE_BIAS_T);
-    og.bias = cw(m, P + "output_proj.bias");
-    og.ldc = ldo;
-    if (!og.bias) return -1;
-    return xgm(m, og, st);
-}
-
-int add_slot(CodecStream &S, int c, int h) {
-    S.hist_c.push_back(c);
-    S.hist_h.push_back(h);
-    S.hist.push_back((float *)salloc(S, (size_t)c * (h > 0 ? h : 1) * 4));
-    return S.hist.back() ? (int)S.hist.size() - 1 : -1;
-}
+};
 }  // namespace
 
 void codec_stream_free(CodecModel *m) {
@@ -2083,75 +2172,43 @@ int codec_stream_begin(CodecModel *m, int max_frames, int chunk) {
     CodecStream &S = m->cs;
     S.tc = tc_want;
     const int hm = S.hm, tc = S.tc;
+    auto salloc = [&](size_t bytes) { return dev_alloc(S.allocs, " stream", bytes, true); };
     // activation buffers: largest C x (hm + L) over the stages at tc frames
-    size_t L = (size_t)tc * d.ratios[0] * d.ratios[1];
-    size_t mx = (size_t)d.clat * L * 4 + (size_t)4 * d.clat * hm;
-    if ((size_t)d.cdec * (L + hm) > mx) mx = (size_t)d.cdec * (L + hm);
-    int C = d.cdec;
-    for (int b = 0; b < 4; ++b) {
-        L *= d.rates[b];
-        C /= 2;
-        if ((size_t)C * (L + hm) > mx) mx = (size_t)C * (L + hm);
-    }
-    if ((size_t)d.clat * (tc + hm) > mx) mx = (size_t)d.clat * (tc + hm);
-    S.buf_elems = mx + hm;
-    S.bufA = (float *)salloc(S, S.buf_elems * 4);
-    S.bufB = (float *)salloc(S, S.buf_elems * 4);
-    S.bufC = (float *)salloc(S, S.buf_elems * 4);
-    S.bufD = (float *)salloc(S, S.buf_elems * 4);
+    S.buf_elems = codec_plane_elems(d, tc, hm) + hm;
+    S.bufA = (float *)salloc(S.buf_elems * 4);
+    S.bufB = (float *)salloc(S.buf_elems * 4);
+    S.bufC = (float *)salloc(S.buf_elems * 4);
+    S.bufD = (float *)salloc(S.buf_elems * 4);
     const int hid = d.chid, hd = hid / d.cheads, kvd = d.ckv * hd, keep = d.cwin - 1;
-    S.tx = (float *)salloc(S, (size_t)tc * hid * 4);
-    S.txn = (float *)salloc(S, (size_t)tc * hid * 4);
-    S.tq = (float *)salloc(S, (size_t)tc * hid * 4);
-    S.tatt = (float *)salloc(S, (size_t)tc * hid * 4);
-    S.tg = (float *)salloc(S, (size_t)tc * d.cinter * 4);
-    S.tu = (float *)salloc(S, (size_t)tc * d.cinter * 4);
+    S.tx = (float *)salloc((size_t)tc * hid * 4);
+    S.txn = (float *)salloc((size_t)tc * hid * 4);
+    S.tq = (float *)salloc((size_t)tc * hid * 4);
+    S.tatt = (float *)salloc((size_t)tc * hid * 4);
+    S.tg = (float *)salloc((size_t)tc * d.cinter * 4);
+    S.tu = (float *)salloc((size_t)tc * d.cinter * 4);
     const int vq = d.ccbdim / 2;
-    S.rvq_s = (float *)salloc(S, (size_t)vq * tc * 4);
-    S.rvq_a = (float *)salloc(S, (size_t)vq * tc * 4);
+    S.rvq_s = (float *)salloc((size_t)vq * tc * 4);
+    S.rvq_a = (float *)salloc((size_t)vq * tc * 4);
     for (int l = 0; l < d.clayers; ++l) {
-        S.kc.push_back((float *)salloc(S, (size_t)(keep + tc) * kvd * 4));
-        S.vc.push_back((float *)salloc(S, (size_t)(keep + tc) * kvd * 4));
+        S.kc.push_back((float *)salloc((size_t)(keep + tc) * kvd * 4));
+        S.vc.push_back((float *)salloc((size_t)(keep + tc) * kvd * 4));
     }
-    S.kvtmp = (float *)salloc(S, (size_t)(keep > 0 ? keep : 1) * kvd * 4);
+    S.kvtmp = (float *)salloc((size_t)(keep > 0 ? keep : 1) * kvd * 4);
     // RoPE table for absolute positions [0, max_frames + tc) (theta 1e4, Cd.c:309)
     S.rope_cap = max_frames + tc;
-    const int half = hd / 2;
-    std::vector<float> c((size_t)S.rope_cap * hd), s((size_t)S.rope_cap * hd);
-    for (int p = 0; p < S.rope_cap; ++p)
-        for (int i = 0; i < half; ++i) {
-            float freq = 1.0f / powf(10000.0f, (float)(2 * i) / (float)hd);
-            float ang = (float)p * freq;
-            c[(size_t)p * hd + i] = c[(size_t)p * hd + i + half] = cosf(ang);
-            s[(size_t)p * hd + i] = s[(size_t)p * hd + i + half] = sinf(ang);
-        }
-    S.rope_cos = (float *)salloc(S, c.size() * 4);
-    S.rope_sin = (float *)salloc(S, s.size() * 4);
+    std::vector<float> c, s;
+    rope_table(hd, S.rope_cap, c, s);
+    S.rope_cos = (float *)salloc(c.size() * 4);
+    S.rope_sin = (float *)salloc(s.size() * 4);
     std::vector<int> io(keep + tc + 1);
     for (size_t i = 0; i < io.size(); ++i) io[i] = (int)i;
-    S.iota = (int *)salloc(S, io.size() * 4);
-    S.zeros = (int *)salloc(S, (size_t)tc * 4);
-    for (void *p : S.allocs)
-        if (!p) return -1;
+    S.iota = (int *)salloc(io.size() * 4);
+    S.zeros = (int *)salloc((size_t)tc * 4);
     if (!S.bufA || !S.bufB || !S.bufC || !S.bufD || !S.rope_cos || !S.rope_sin || !S.iota || !S.zeros) return -1;
     if (hipMemcpy(S.rope_cos, c.data(), c.size() * 4, hipMemcpyHostToDevice) != hipSuccess) return -1;
     if (hipMemcpy(S.rope_sin, s.data(), s.size() * 4, hipMemcpyHostToDevice) != hipSuccess) return -1;
     if (hipMemcpy(S.iota, io.data(), io.size() * 4, hipMemcpyHostToDevice) != hipSuccess) return -1;
-    // history slots, in the order codec_stream_push consumes them
-    add_slot(S, d.ccbdim, 2);                  // 0 pre-conv k3
-    add_slot(S, d.clat, 6);                    // 1 upsample 0 dwconv k7
-    add_slot(S, d.clat, 6);                    // 2 upsample 1 dwconv k7
-    add_slot(S, d.clat, 6);                    // 3 vocoder conv0 k7
-    C = d.cdec;
-    static const int dil[3] = {1, 3, 9};
-    for (int b = 0; b < 4; ++b) {
-        add_slot(S, C, 1);                     // block tconv (K = 2r): last input frame
-        for (int u = 0; u < 3; ++u) add_slot(S, C / 2, 6 * dil[u]);   // ResUnit conv1 k7 dil
-        C /= 2;
-    }
-    add_slot(S, C, 6);                         // final conv k7
-    for (float *h : S.hist)
-        if (!h) return -1;
+    if (!add_hist_slots(S, d, 1, " stream")) return -1;
     if (hipDeviceSynchronize() != hipSuccess) return -1;
     S.active = true;
     return 0;
@@ -2174,80 +2231,13 @@ int codec_stream_push_to(CodecModel *m, const int *codes, int ldc_codes, int Tto
         return -1;
     }
     hipStream_t st = m->st;
-    const int lat = d.clat, vq = d.ccbdim / 2, half = lat / 2, hm = S.hm;
     int written = 0;
     for (int t0 = 0; t0 < Ttot; t0 += S.tc) {
         const int T = Ttot - t0 < S.tc ? Ttot - t0 : S.tc;
-        float *A = S.bufA + hm, *B = S.bufB + hm, *Cb = S.bufC, *D = S.bufD;
-        int L = T, ld = hm + L;
-        // 1. RVQ dequantise -> A [half][T]
-        hipLaunchKernelGGL(k_rvq_sum, dim3(T), dim3(vq < 64 ? 64 : (vq + 63) / 64 * 64), 0, st,
-                           codes + (size_t)t0 * d.cq, T, d.cq, d.ccb, vq, m->cb, S.rvq_s, S.rvq_a);
-        hipLaunchKernelGGL(k_rvq_proj, dim3((half * T + 3) / 4), dim3(256), 0, st,
-                           cw(m, "decoder.quantizer.rvq_first.output_proj.weight"),
-                           cw(m, "decoder.quantizer.rvq_rest.output_proj.weight"), S.rvq_s, S.rvq_a, vq, half, T, ld, A);
-        // 2. pre-conv k3 -> B
-        KCK(sconv(m, 0, A, ld, d.ccbdim, L, "decoder.pre_conv.conv.weight", "decoder.pre_conv.conv.bias", lat, 3, 1, B,
-                  ld, XE_BIAS_M, nullptr, nullptr, nullptr));
-        // 3. transformer -> A
-        KCK(stransformer(m, B, ld, T, A, ld));
-        // 4. upsample x2: tconv (K = s, no history) + ConvNeXt
-        float *cur = A;
-        for (int s = 0; s < 2; ++s) {
-            const int f = d.ratios[s];
-            const std::string p = "decoder.upsample." + std::to_string(s) + ".";
-            float *up = cur == A ? B : A;
-            const int ldu = hm + L * f;
-            KCK(stconv(m, -1, cur, ld, lat, L, cw(m, p + "0.conv.weight"), cw(m, p + "0.conv.bias"), lat, f, f, up, ldu,
-                       nullptr, nullptr));
-            L *= f;
-            ld = ldu;
-            cur = up;
-            hist_in(m, 1 + s, cur, ld);
-            hipLaunchKernelGGL(k_dwconv, dim3((unsigned)(((size_t)lat * L + 255) / 256)), dim3(256), 0, st, cur, ld, -6,
-                               cw(m, p + "1.dwconv.conv.weight"), cw(m, p + "1.dwconv.conv.bias"), lat, L, 7, Cb, L);
-            hist_out(m, 1 + s, cur, ld, L);
-            hipLaunchKernelGGL(k_ln_t, dim3(L), dim3(256), 0, st, Cb, L, lat, cw(m, p + "1.norm.weight"),
-                               cw(m, p + "1.norm.bias"), 1e-6f, D);
-            XGemm g1 = lin(D, L, lat, cw(m, p + "1.pwconv1.weight"), 4 * lat, Cb, XE_BIAS_N_GELU);
-            g1.bias = cw(m, p + "1.pwconv1.bias");
-            KCK(xgm(m, g1, st));
-            XGemm g2 = lin(Cb, L, 4 * lat, cw(m, p + "1.pwconv2.weight"), lat, cur, XE_BIAS_GAMMA_RES_T);
-            g2.bias = cw(m, p + "1.pwconv2.bias");
-            g2.vec = cw(m, p + "1.gamma");
-            g2.res = cur; g2.ldres = ld; g2.ldc = ld;
-            KCK(xgm(m, g2, st));
-        }
-        // 5. vocoder
-        float *voc = cur == A ? B : A;
-        KCK(sconv(m, 3, cur, ld, lat, L, "decoder.decoder.0.conv.weight", "decoder.decoder.0.conv.bias", d.cdec, 7, 1,
-                  voc, ld, XE_BIAS_M, nullptr, nullptr, nullptr));
-        int C = d.cdec, slot = 4;
-        static const int dil[3] = {1, 3, 9};
-        for (int b = 0; b < 4; ++b) {
-            const int r = d.rates[b], co = C / 2;
-            const std::string p = "decoder.decoder." + std::to_string(b + 1) + ".block.";
-            float *nx = voc == A ? B : A;
-            const int ldn = hm + L * r;
-            KCK(stconv(m, slot++, voc, ld, C, L, cw(m, p + "1.conv.weight"), cw(m, p + "1.conv.bias"), co, 2 * r, r, nx,
-                       ldn, cw(m, p + "0.alpha"), cw(m, p + "0.beta")));
-            L *= r;
-            ld = ldn;
-            C = co;
-            voc = nx;
-            for (int u = 0; u < 3; ++u) {
-                const std::string q = p + std::to_string(u + 2) + ".";
-                KCK(sconv(m, slot++, voc, ld, C, L, q + "conv1.conv.weight", q + "conv1.conv.bias", C, 7, dil[u], Cb, L,
-                          XE_BIAS_M_SNAKE, cw(m, q + "act1.alpha"), cw(m, q + "act1.beta"), nullptr,
-                          cw(m, q + "act2.alpha"), cw(m, q + "act2.beta")));
-                KCK(sconv(m, -1, Cb, L, C, L, q + "conv2.conv.weight", q + "conv2.conv.bias", C, 1, 1, voc, ld,
-                          XE_BIAS_M_RES, nullptr, nullptr, voc));
-            }
-        }
-        float *wav = voc == A ? B : A;
-        KCK(sconv(m, slot, voc, ld, C, L, "decoder.decoder.6.conv.weight", "decoder.decoder.6.conv.bias", 1, 7, 1, wav,
-                  ld, XE_BIAS_M, cw(m, "decoder.decoder.5.alpha"), cw(m, "decoder.decoder.5.beta"), nullptr));
-        hipLaunchKernelGGL(k_clamp, dim3((L + 255) / 256), dim3(256), 0, st, wav, L);
+        StreamPlace p(m);   // at this chunk's pos0 and hl
+        float *wav = nullptr;
+        int L = 0;
+        KCK(net_decode(p, codes + (size_t)t0 * d.cq, T, &wav, &L));
         if (hipMemcpyAsync(out + written, wav, (size_t)L * 4, host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice,
                            st) != hipSuccess)
             return -1;
@@ -2269,18 +2259,6 @@ int codec_stream_push_to(CodecModel *m, const int *codes, int ldc_codes, int Tto
 // read once, and XGemm::seg_m sends the transposed operands to the planes.
 namespace {
 constexpr size_t kMsScratchBudget = (size_t)2 << 30;   // bytes of the four activation buffers
-
-void *msalloc(CodecMStream &S, size_t bytes) {
-    void *p = nullptr;
-    const hipError_t e = hipMalloc(&p, bytes ? bytes : 16);
-    if (e != hipSuccess) {
-        fprintf(stderr, "qtts codec mstream: hipMalloc(%zu) failed: %s\n", bytes, hipGetErrorName(e));
-        return nullptr;
-    }
-    hipMemset(p, 0, bytes ? bytes : 16);
-    S.allocs.push_back(p);
-    return p;
-}
 
 // k_rvq_sum over the stacked rows r = s * T + t of a push: stream s's codes
 // start at codes + coff[s], frame t0 + t.  Stream s has tv[s] >= 1 frames in
@@ -2481,150 +2459,89 @@ __global__ void k_clamp_ms(const float *x, size_t seg, int L, float *y, const in
     y[(size_t)s * L + i] = v;
 }
 
-void ms_hist(CodecModel *m, int n, int slot, float *x, size_t seg, int ldx, int L, int out) {
-    CodecMStream &S = m->ms;
-    const int C = S.hist_c[slot], H = S.hist_h[slot];
-    hipLaunchKernelGGL(k_hist_ms, dim3((C * H + 255) / 256, n), dim3(256), 0, m->st, S.hist[slot], S.sid, x, seg, ldx,
-                       C, H, S.pass_tv, L / S.pass_T, out);   // (L: a whole number of columns per frame)
-}
-
-// sconv / stconv over n planes: input plane stride ci * ldx, output co * ldo
-int ms_sconv(CodecModel *m, int n, int slot, float *x, int ldx, int ci, int L, const std::string &wn,
-             const std::string &bn, int co, int K, int dil, float *out, int ldo, int emode, const float *sa,
-             const float *sb, const float *res, const float *ea = nullptr, const float *eb = nullptr) {
-    const int H = (K - 1) * dil;
-    const size_t segx = (size_t)ci * ldx;
-    if (H > 0) ms_hist(m, n, slot, x, segx, ldx, L, 0);
-    XGemm g;
-    g.M = co; g.N = L; g.K = ci * K;
-    g.amode = XA_ROWS; g.A = cw(m, wn); g.lda = ci * K; g.wt = cwt(m, wn, co, ci, K);
-    g.bmode = XB_CONV; g.B = x; g.ldb = ldx; g.Kw = K; g.dil = dil; g.pad = H; g.L = L; g.tmin = -H;
-    g.sa = sa; g.sb = sb;
-    g.C = out; g.ldc = ldo; g.emode = emode; g.bias = bn.empty() ? nullptr : cw(m, bn); g.res = res; g.ldres = ldo;
-    g.ea = ea; g.eb = eb;
-    g.nseg = n; g.seg_ldb = ci * ldx; g.seg_ldc = co * ldo; g.seg_ldres = co * ldo;
-    if (!g.A) return -1;
-    KCK(xgm(m, g, m->st));
-    if (H > 0) ms_hist(m, n, slot, x, segx, ldx, L, 1);
-    return 0;
-}
-
-int ms_stconv(CodecModel *m, int n, int slot, float *x, int ldx, int ci, int L, const float *w, const float *bias,
-              int co, int Kw, int s, float *out, int ldo, const float *sa, const float *sb) {
-    const int H = Kw / s - 1;
-    const size_t segx = (size_t)ci * ldx;
-    if (H > 0) ms_hist(m, n, slot, x, segx, ldx, L, 0);
-    XGemm g;
-    g.M = co; g.N = L; g.K = ci * (Kw / s);
-    g.amode = XA_TCONV_W; g.A = w; g.co = co; g.Kw = Kw; g.stride = s;
-    g.bmode = XB_TCONV; g.B = x; g.ldb = ldx; g.L = L; g.tmin = -H; g.sa = sa; g.sb = sb;
-    g.C = out; g.ldc = ldo; g.emode = XE_BIAS_M; g.bias = bias;
-    g.nseg = n; g.seg_ldb = ci * ldx; g.seg_ldc = co * ldo;
-    KCK(tconv_run(m, g, m->st));
-    if (H > 0) ms_hist(m, n, slot, x, segx, ldx, L, 1);
-    return 0;
-}
-
-// the transformer over the stacked rows M = n * T of a pass; pc / out: planes
-// [lat][ldp] / [lat][ldo]; stream i of the pass is at dpos0[i] with dhl[i] history
-// rows and has dtv[i] valid frames (device arrays); shifts: some stream's window
+// the multi-stream's placement for one pass: n planes a launch, history of
+// every plane by k_hist_ms, k and v projected to S.tk / S.tv and sent to
+// their stream's cache rows by k_rope_kv_ms, one keep-shift after the layers.
+// Stream i of the pass is at dpos0[i] with dhl[i] history rows and has dtv[i]
+// of the pass's T frames valid (device arrays); shifts: some stream's window
 // runs over in this pass
-int ms_transformer(CodecModel *m, int n, const float *pc, int ldp, int T, float *out, int ldo, const int *dpos0,
-                   const int *dhl, const int *dtv, bool shifts) {
-    CodecMStream &S = m->ms;
-    const qtts_dims_t &d = m->d;
-    const int lat = d.clat, hid = d.chid, nh = d.cheads, nkv = d.ckv, hd = hid / nh, kvd = nkv * hd, I = d.cinter;
-    const int keepmax = d.cwin - 1, M = n * T;
-    hipStream_t st = m->st;
-    const std::string P = "decoder.pre_transformer.";
-    XGemm g;
-    g.M = M; g.N = hid; g.K = lat; g.amode = XA_TRANS; g.A = pc; g.lda = ldp; g.bmode = XB_WT;
-    g.B = cw(m, P + "input_proj.weight"); g.ldb = lat; g.C = S.tx; g.ldc = hid;
-    g.bias = cw(m, P + "input_proj.bias");
-    g.emode = g.bias ? XE_BIAS_N : XE_STORE;
-    g.seg_m = T; g.seg_lda = lat * ldp;
-    KCK(xgm(m, g, st));
-    hipLaunchKernelGGL(k_ms_index, dim3((M + 255) / 256), dim3(256), 0, st, S.sid, dhl, n, T, S.row_b, S.pos);
-    const size_t lsz = (size_t)S.ns * S.S * kvd;   // one layer's K (or V) of every stream
-    for (int l = 0; l < d.clayers; ++l) {
-        const std::string p = P + "layers." + std::to_string(l) + ".";
-        float *kcl = S.kv + (size_t)(2 * l) * lsz, *vcl = kcl + lsz;
-        hipLaunchKernelGGL(k_rms_rows, dim3(M), dim3(256), 0, st, S.tx, hid, cw(m, p + "input_layernorm.weight"),
-                           d.ceps, S.txn);
-        KCK(xgm(m, lin(S.txn, M, hid, cw(m, p + "self_attn.q_proj.weight"), hid, S.tq, XE_STORE), st));
-        KCK(xgm(m, lin(S.txn, M, hid, cw(m, p + "self_attn.k_proj.weight"), kvd, S.tk, XE_STORE), st));
-        KCK(xgm(m, lin(S.txn, M, hid, cw(m, p + "self_attn.v_proj.weight"), kvd, S.tv, XE_STORE), st));
-        hipLaunchKernelGGL(k_rope_kv_ms, dim3(M), dim3(256), 0, st, S.tq, hid, nh, S.tk, S.tv, kvd, nkv, hd, S.rope_cos,
-                           S.rope_sin, T, S.sid, dpos0, dhl, dtv, kcl, vcl, S.S);
-        AttnArgs a;
-        a.mode = 1; a.qkv = S.tq; a.ld_qkv = hid; a.kc = kcl; a.vc = vcl; a.S = S.S; a.pos = S.pos;
-        a.row_b = S.row_b; a.NH = nh; a.KV = nkv; a.HD = hd; a.out = S.tatt; a.ld_out = hid;
-        a.nrows = M; a.win = d.cwin;
-        KCK(qtts_attention(a, st));
-        const float *ls1 = cw(m, p + "self_attn_layer_scale.scale");
-        if (!ls1) return -1;
-        XGemm o = lin(S.tatt, M, hid, cw(m, p + "self_attn.o_proj.weight"), hid, S.tx, XE_SCALE_RESID_N);
-        o.vec = ls1;
-        KCK(xgm(m, o, st));
-        hipLaunchKernelGGL(k_rms_rows, dim3(M), dim3(256), 0, st, S.tx, hid,
-                           cw(m, p + "post_attention_layernorm.weight"), d.ceps, S.txn);
-        KCK(xgm(m, lin(S.txn, M, hid, cw(m, p + "mlp.gate_proj.weight"), I, S.tg, XE_STORE), st));
-        XGemm u = lin(S.txn, M, hid, cw(m, p + "mlp.up_proj.weight"), I, S.tu, XE_SILU_MUL);
-        u.aux = S.tg; u.ldaux = I;
-        KCK(xgm(m, u, st));
-        const float *ls2 = cw(m, p + "mlp_layer_scale.scale");
-        if (!ls2) return -1;
-        XGemm dn = lin(S.tu, M, I, cw(m, p + "mlp.down_proj.weight"), hid, S.tx, XE_SCALE_RESID_N);
-        dn.vec = ls2;
-        KCK(xgm(m, dn, st));
+struct MsPlace : Place {
+    CodecMStream &S;
+    const int ldc_codes, t0, T;
+    const int *dpos0, *dhl, *dtv;
+    const bool shifts;
+    MsPlace(CodecModel *cm, int n_, int ldc_codes_, int t0_, int T_, const int *dpos0_, const int *dhl_,
+            const int *dtv_, bool shifts_)
+        : S(cm->ms), ldc_codes(ldc_codes_), t0(t0_), T(T_), dpos0(dpos0_), dhl(dhl_), dtv(dtv_), shifts(shifts_) {
+        take(cm, S, S.hm);   // (the whole RoPE table: every row rotates by its own stream's position)
+        n = n_;
+        rvq_s = S.rvq_s; rvq_a = S.rvq_a;
     }
+    int hist(int slot, int C, int H, float *x, int ldx, int L, bool out) override {
+        if (!hist_slot_is(S, slot, C, H)) return -1;
+        hipLaunchKernelGGL(k_hist_ms, dim3((C * H + 255) / 256, n), dim3(256), 0, m->st, S.hist[slot], S.sid, x,
+                           (size_t)C * ldx, ldx, C, H, dtv, L / T, out ? 1 : 0);   // (L: a whole number of columns per frame)
+        return 0;
+    }
+    // input plane stride ci * ldb, output (and residual) co * ldc
+    void planes(XGemm &g, int ci, int co) override {
+        g.nseg = n; g.seg_ldb = ci * g.ldb; g.seg_ldc = co * g.ldc;
+        if (g.bmode == XB_CONV) g.seg_ldres = co * g.ldres;
+    }
+    void rows(XGemm &g, int seg_m, int C) override {
+        g.seg_m = seg_m;
+        if (g.amode == XA_TRANS) g.seg_lda = C * g.lda;
+        else g.seg_ldc = C * g.ldc;
+        if (g.res) g.seg_ldres = C * g.ldres;
+    }
+    void rvq(const int *codes, const float *ps, const float *pa, int, int ldo, float *out) override {
+        const qtts_dims_t &d = m->d;
+        const int vq = d.ccbdim / 2, half = d.clat / 2;
+        hipLaunchKernelGGL(k_rvq_sum_ms, dim3(n * T), dim3(vq < 64 ? 64 : (vq + 63) / 64 * 64), 0, m->st, codes, S.coff,
+                           ldc_codes, t0, T, n, d.cq, d.ccb, vq, m->cb, rvq_s, rvq_a, dtv);
+        hipLaunchKernelGGL(k_rvq_proj_ms, dim3((half * n * T + 3) / 4), dim3(256), 0, m->st, ps, pa, rvq_s, rvq_a, vq,
+                           half, T, n, ldo, (size_t)d.ccbdim * ldo, out);
+    }
+    void dwconv(const float *x, int ldx, const float *w, const float *b, int C, int L, int K, float *y) override {
+        hipLaunchKernelGGL(k_dwconv_ms, dim3((unsigned)(((size_t)C * L + 255) / 256), n), dim3(256), 0, m->st, x,
+                           (size_t)C * ldx, ldx, tmin(K - 1), w, b, C, L, K, y, (size_t)C * L, L);
+    }
+    void ln_t(const float *x, int L, int C, const float *w, const float *b, float *y) override {
+        hipLaunchKernelGGL(k_ln_t_ms, dim3(n * L), dim3(256), 0, m->st, x, (size_t)C * L, L, L, C, w, b, 1e-6f, y);
+    }
+    // into the compact S.wav [n][L], the valid samples only
+    void clamp(float *wav, int ld, int L, int) override {
+        hipLaunchKernelGGL(k_clamp_ms, dim3((L + 255) / 256, n), dim3(256), 0, m->st, wav, (size_t)ld, L, S.wav, dtv,
+                           L / T);
+    }
+    void layers_begin(int) override {
+        hipLaunchKernelGGL(k_ms_index, dim3((n * T + 255) / 256), dim3(256), 0, m->st, S.sid, dhl, n, T, S.row_b, S.pos);
+    }
+    LayerKV layer(int l, int) override {
+        const size_t lsz = (size_t)S.ns * S.S * kvd();   // one layer's K (or V) of every stream
+        float *kc = S.kv + (size_t)(2 * l) * lsz;
+        return {tq, S.tk, S.tv, kc, kc + lsz};
+    }
+    void rope(const LayerKV &r, int) override {
+        const qtts_dims_t &d = m->d;
+        const int hid = d.chid, hd = hid / d.cheads;
+        hipLaunchKernelGGL(k_rope_kv_ms, dim3(n * T), dim3(256), 0, m->st, r.q, hid, d.cheads, r.k, r.v, kvd(), d.ckv, hd,
+                           rope_cos, rope_sin, T, S.sid, dpos0, dhl, dtv, r.kc, r.vc, S.S);
+    }
+    void attn_rows(AttnArgs &a, int) override { a.S = S.S; a.pos = S.pos; a.row_b = S.row_b; }
     // keep the last window-1 rows of every layer for the next pass (each stream by its own count)
-    if (keepmax > 0 && shifts)
-        hipLaunchKernelGGL(k_kv_shift_ms, dim3((kvd + 255) / 256, n, 2 * d.clayers), dim3(256), 0, st, S.kv, S.sid, dhl,
-                           dtv, S.ns, S.S, kvd, keepmax);
-    const float *fn = cw(m, P + "norm.weight");
-    const float *xin = S.tx;
-    if (fn) {
-        hipLaunchKernelGGL(k_rms_rows, dim3(M), dim3(256), 0, st, S.tx, hid, fn, d.ceps, S.txn);
-        xin = S.txn;
+    void layers_end(int) override {
+        const int keepmax = m->d.cwin - 1;
+        if (keepmax > 0 && shifts)
+            hipLaunchKernelGGL(k_kv_shift_ms, dim3((kvd() + 255) / 256, n, 2 * m->d.clayers), dim3(256), 0, m->st, S.kv,
+                               S.sid, dhl, dtv, S.ns, S.S, kvd(), keepmax);
     }
-    XGemm og = lin(xin, M, hid, cw(m, P + "output_proj.weight"), lat, out, XE_BIAS_T);
-    og.bias = cw(m, P + "output_proj.bias");
-    og.ldc = ldo;
-    og.seg_m = T; og.seg_ldc = lat * ldo;
-    if (!og.bias) return -1;
-    return xgm(m, og, st);
-}
-
-int ms_add_slot(CodecMStream &S, int c, int h) {
-    S.hist_c.push_back(c);
-    S.hist_h.push_back(h);
-    const size_t bytes = (size_t)S.ns * c * (h > 0 ? h : 1) * 4;
-    S.hist.push_back((float *)msalloc(S, bytes));
-    S.state_bytes += bytes;
-    return S.hist.back() ? 0 : -1;
-}
-
-// largest per-stream plane (elements) over the stages at tc frames: codec_stream_begin's sizing
-size_t ms_plane_elems(const qtts_dims_t &d, int tc, int hm) {
-    size_t L = (size_t)tc * d.ratios[0] * d.ratios[1];
-    size_t mx = (size_t)d.clat * L * 4 + (size_t)4 * d.clat * hm;
-    if ((size_t)d.cdec * (L + hm) > mx) mx = (size_t)d.cdec * (L + hm);
-    int C = d.cdec;
-    for (int b = 0; b < 4; ++b) {
-        L *= d.rates[b];
-        C /= 2;
-        if ((size_t)C * (L + hm) > mx) mx = (size_t)C * (L + hm);
-    }
-    if ((size_t)d.clat * (tc + hm) > mx) mx = (size_t)d.clat * (tc + hm);
-    return mx;
-}
-
+};
 // frames per internal pass for n streams: the chunk asked for, lowered until
 // the four activation buffers of n planes fit the budget
 int ms_chunk(const qtts_dims_t &d, int n, int chunk, int hm) {
     int tc = chunk > kStreamChunk ? (chunk < kStreamChunkMax ? chunk : kStreamChunkMax) : kStreamChunk;
-    while (tc > 1 && 4 * (size_t)n * ms_plane_elems(d, tc, hm) * 4 > kMsScratchBudget) --tc;
+    while (tc > 1 && 4 * (size_t)n * codec_plane_elems(d, tc, hm) * 4 > kMsScratchBudget) --tc;
     return tc;
 }
 
@@ -2638,88 +2555,9 @@ int ms_samples_per_frame(const qtts_dims_t &d) {
 // push), dtv[i] <= T of them valid, audio to S.wav [n][T * spf]
 int ms_pass(CodecModel *m, int n, const int *codes, int ldc_codes, int t0, int T, const int *dpos0, const int *dhl,
             const int *dtv, bool shifts, int *L_out) {
-    CodecMStream &S = m->ms;
-    S.pass_tv = dtv;
-    S.pass_T = T;
-    const qtts_dims_t &d = m->d;
-    hipStream_t st = m->st;
-    const int lat = d.clat, vq = d.ccbdim / 2, half = lat / 2, hm = S.hm;
-    float *A = S.bufA + hm, *B = S.bufB + hm, *Cb = S.bufC, *D = S.bufD;
-    int L = T, ld = hm + L;
-    // 1. RVQ dequantise -> A planes [half][T]
-    hipLaunchKernelGGL(k_rvq_sum_ms, dim3(n * T), dim3(vq < 64 ? 64 : (vq + 63) / 64 * 64), 0, st, codes, S.coff,
-                       ldc_codes, t0, T, n, d.cq, d.ccb, vq, m->cb, S.rvq_s, S.rvq_a, dtv);
-    hipLaunchKernelGGL(k_rvq_proj_ms, dim3((half * n * T + 3) / 4), dim3(256), 0, st,
-                       cw(m, "decoder.quantizer.rvq_first.output_proj.weight"),
-                       cw(m, "decoder.quantizer.rvq_rest.output_proj.weight"), S.rvq_s, S.rvq_a, vq, half, T, n, ld,
-                       (size_t)d.ccbdim * ld, A);
-    // 2. pre-conv k3 -> B
-    KCK(ms_sconv(m, n, 0, A, ld, d.ccbdim, L, "decoder.pre_conv.conv.weight", "decoder.pre_conv.conv.bias", lat, 3, 1,
-                 B, ld, XE_BIAS_M, nullptr, nullptr, nullptr));
-    // 3. transformer -> A
-    KCK(ms_transformer(m, n, B, ld, T, A, ld, dpos0, dhl, dtv, shifts));
-    // 4. upsample x2: tconv (K = s, no history) + ConvNeXt
-    float *cur = A;
-    for (int s = 0; s < 2; ++s) {
-        const int f = d.ratios[s];
-        const std::string p = "decoder.upsample." + std::to_string(s) + ".";
-        float *up = cur == A ? B : A;
-        const int ldu = hm + L * f;
-        KCK(ms_stconv(m, n, -1, cur, ld, lat, L, cw(m, p + "0.conv.weight"), cw(m, p + "0.conv.bias"), lat, f, f, up,
-                      ldu, nullptr, nullptr));
-        L *= f;
-        ld = ldu;
-        cur = up;
-        const size_t seg = (size_t)lat * ld;
-        ms_hist(m, n, 1 + s, cur, seg, ld, L, 0);
-        hipLaunchKernelGGL(k_dwconv_ms, dim3((unsigned)(((size_t)lat * L + 255) / 256), n), dim3(256), 0, st, cur, seg,
-                           ld, -6, cw(m, p + "1.dwconv.conv.weight"), cw(m, p + "1.dwconv.conv.bias"), lat, L, 7, Cb,
-                           (size_t)lat * L, L);
-        ms_hist(m, n, 1 + s, cur, seg, ld, L, 1);
-        hipLaunchKernelGGL(k_ln_t_ms, dim3(n * L), dim3(256), 0, st, Cb, (size_t)lat * L, L, L, lat,
-                           cw(m, p + "1.norm.weight"), cw(m, p + "1.norm.bias"), 1e-6f, D);
-        XGemm g1 = lin(D, n * L, lat, cw(m, p + "1.pwconv1.weight"), 4 * lat, Cb, XE_BIAS_N_GELU);
-        g1.bias = cw(m, p + "1.pwconv1.bias");
-        KCK(xgm(m, g1, st));
-        XGemm g2 = lin(Cb, n * L, 4 * lat, cw(m, p + "1.pwconv2.weight"), lat, cur, XE_BIAS_GAMMA_RES_T);
-        g2.bias = cw(m, p + "1.pwconv2.bias");
-        g2.vec = cw(m, p + "1.gamma");
-        g2.res = cur; g2.ldres = ld; g2.ldc = ld;
-        g2.seg_m = L; g2.seg_ldc = lat * ld; g2.seg_ldres = lat * ld;
-        KCK(xgm(m, g2, st));
-    }
-    // 5. vocoder
-    float *voc = cur == A ? B : A;
-    KCK(ms_sconv(m, n, 3, cur, ld, lat, L, "decoder.decoder.0.conv.weight", "decoder.decoder.0.conv.bias", d.cdec, 7, 1,
-                 voc, ld, XE_BIAS_M, nullptr, nullptr, nullptr));
-    int C = d.cdec, slot = 4;
-    static const int dil[3] = {1, 3, 9};
-    for (int b = 0; b < 4; ++b) {
-        const int r = d.rates[b], co = C / 2;
-        const std::string p = "decoder.decoder." + std::to_string(b + 1) + ".block.";
-        float *nx = voc == A ? B : A;
-        const int ldn = hm + L * r;
-        KCK(ms_stconv(m, n, slot++, voc, ld, C, L, cw(m, p + "1.conv.weight"), cw(m, p + "1.conv.bias"), co, 2 * r, r,
-                      nx, ldn, cw(m, p + "0.alpha"), cw(m, p + "0.beta")));
-        L *= r;
-        ld = ldn;
-        C = co;
-        voc = nx;
-        for (int u = 0; u < 3; ++u) {
-            const std::string q = p + std::to_string(u + 2) + ".";
-            KCK(ms_sconv(m, n, slot++, voc, ld, C, L, q + "conv1.conv.weight", q + "conv1.conv.bias", C, 7, dil[u], Cb,
-                         L, XE_BIAS_M_SNAKE, cw(m, q + "act1.alpha"), cw(m, q + "act1.beta"), nullptr,
-                         cw(m, q + "act2.alpha"), cw(m, q + "act2.beta")));
-            KCK(ms_sconv(m, n, -1, Cb, L, C, L, q + "conv2.conv.weight", q + "conv2.conv.bias", C, 1, 1, voc, ld,
-                         XE_BIAS_M_RES, nullptr, nullptr, voc));
-        }
-    }
-    float *wav = voc == A ? B : A;
-    KCK(ms_sconv(m, n, slot, voc, ld, C, L, "decoder.decoder.6.conv.weight", "decoder.decoder.6.conv.bias", 1, 7, 1, wav,
-                 ld, XE_BIAS_M, cw(m, "decoder.decoder.5.alpha"), cw(m, "decoder.decoder.5.beta"), nullptr));
-    hipLaunchKernelGGL(k_clamp_ms, dim3((L + 255) / 256, n), dim3(256), 0, st, wav, (size_t)ld, L, S.wav,
-                       dtv, L / T);
-    *L_out = L;
+    MsPlace p(m, n, ldc_codes, t0, T, dpos0, dhl, dtv, shifts);
+    float *wav = nullptr;
+    KCK(net_decode(p, codes, T, &wav, L_out));
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 }  // namespace
@@ -2770,72 +2608,53 @@ int codec_mstream_begin(CodecModel *m, int n_streams, int max_frames, int chunk)
     S.hl.assign(n_streams, 0);
     const int hm = S.hm, ns = n_streams;
     const size_t rows = (size_t)ns * tc;
-    S.buf_elems = ms_plane_elems(d, tc, hm);
+    auto msalloc = [&](size_t bytes) { return dev_alloc(S.allocs, " mstream", bytes, true); };
+    S.buf_elems = codec_plane_elems(d, tc, hm);
     const size_t bbytes = ((size_t)ns * S.buf_elems + hm) * 4;
-    S.bufA = (float *)msalloc(S, bbytes);
-    S.bufB = (float *)msalloc(S, bbytes);
-    S.bufC = (float *)msalloc(S, bbytes);
-    S.bufD = (float *)msalloc(S, bbytes);
+    S.bufA = (float *)msalloc(bbytes);
+    S.bufB = (float *)msalloc(bbytes);
+    S.bufC = (float *)msalloc(bbytes);
+    S.bufD = (float *)msalloc(bbytes);
     const int hid = d.chid, hd = hid / d.cheads, kvd = d.ckv * hd, keep = d.cwin - 1, vq = d.ccbdim / 2;
-    S.tx = (float *)msalloc(S, rows * hid * 4);
-    S.txn = (float *)msalloc(S, rows * hid * 4);
-    S.tq = (float *)msalloc(S, rows * hid * 4);
-    S.tk = (float *)msalloc(S, rows * kvd * 4);
-    S.tv = (float *)msalloc(S, rows * kvd * 4);
-    S.tatt = (float *)msalloc(S, rows * hid * 4);
-    S.tg = (float *)msalloc(S, rows * d.cinter * 4);
-    S.tu = (float *)msalloc(S, rows * d.cinter * 4);
-    S.rvq_s = (float *)msalloc(S, rows * vq * 4);
-    S.rvq_a = (float *)msalloc(S, rows * vq * 4);
+    S.tx = (float *)msalloc(rows * hid * 4);
+    S.txn = (float *)msalloc(rows * hid * 4);
+    S.tq = (float *)msalloc(rows * hid * 4);
+    S.tk = (float *)msalloc(rows * kvd * 4);
+    S.tv = (float *)msalloc(rows * kvd * 4);
+    S.tatt = (float *)msalloc(rows * hid * 4);
+    S.tg = (float *)msalloc(rows * d.cinter * 4);
+    S.tu = (float *)msalloc(rows * d.cinter * 4);
+    S.rvq_s = (float *)msalloc(rows * vq * 4);
+    S.rvq_a = (float *)msalloc(rows * vq * 4);
     const int spf = ms_samples_per_frame(d);
-    S.wav = (float *)msalloc(S, rows * spf * 4);
+    S.wav = (float *)msalloc(rows * spf * 4);
     S.scratch_bytes = 4 * bbytes + rows * ((size_t)4 * hid + 2 * kvd + 2 * d.cinter + 2 * vq + spf) * 4;
     S.S = keep + tc;
     const size_t kvbytes = (size_t)2 * d.clayers * ns * S.S * kvd * 4;
-    S.kv = (float *)msalloc(S, kvbytes);
+    S.kv = (float *)msalloc(kvbytes);
     S.state_bytes = kvbytes;
     // RoPE table for absolute positions [0, max_frames + tc) (theta 1e4, Cd.c:309)
     S.rope_cap = max_frames + tc;
-    const int half = hd / 2;
-    std::vector<float> c((size_t)S.rope_cap * hd), s((size_t)S.rope_cap * hd);
-    for (int p = 0; p < S.rope_cap; ++p)
-        for (int i = 0; i < half; ++i) {
-            float freq = 1.0f / powf(10000.0f, (float)(2 * i) / (float)hd);
-            float ang = (float)p * freq;
-            c[(size_t)p * hd + i] = c[(size_t)p * hd + i + half] = cosf(ang);
-            s[(size_t)p * hd + i] = s[(size_t)p * hd + i + half] = sinf(ang);
-        }
-    S.rope_cos = (float *)msalloc(S, c.size() * 4);
-    S.rope_sin = (float *)msalloc(S, s.size() * 4);
-    S.sid = (int *)msalloc(S, (size_t)ns * 4);
-    S.row_b = (int *)msalloc(S, rows * 4);
-    S.pos = (int *)msalloc(S, rows * 4);
-    S.coff = (long long *)msalloc(S, (size_t)ns * 8);
+    std::vector<float> c, s;
+    rope_table(hd, S.rope_cap, c, s);
+    S.rope_cos = (float *)msalloc(c.size() * 4);
+    S.rope_sin = (float *)msalloc(s.size() * 4);
+    S.sid = (int *)msalloc((size_t)ns * 4);
+    S.row_b = (int *)msalloc(rows * 4);
+    S.pos = (int *)msalloc(rows * 4);
+    S.coff = (long long *)msalloc((size_t)ns * 8);
     S.pp_passes = (max_frames + tc - 1) / tc;   // a push holds at most max_frames frames
-    S.pp = (int *)msalloc(S, (size_t)S.pp_passes * 3 * ns * 4);
-    for (void *p : S.allocs)
-        if (!p) return -1;
+    S.pp = (int *)msalloc((size_t)S.pp_passes * 3 * ns * 4);
     if (!S.bufA || !S.bufB || !S.bufC || !S.bufD || !S.kv || !S.wav || !S.rope_cos || !S.rope_sin || !S.sid ||
         !S.row_b || !S.pos || !S.coff || !S.tx || !S.txn || !S.tq || !S.tk || !S.tv || !S.tatt || !S.tg || !S.tu ||
         !S.rvq_s || !S.rvq_a)
         return -1;
     if (hipMemcpy(S.rope_cos, c.data(), c.size() * 4, hipMemcpyHostToDevice) != hipSuccess) return -1;
     if (hipMemcpy(S.rope_sin, s.data(), s.size() * 4, hipMemcpyHostToDevice) != hipSuccess) return -1;
-    // history slots, in codec_stream_begin's order, each [ns][C][H]
-    int rc = 0;
-    rc |= ms_add_slot(S, d.ccbdim, 2);                  // 0 pre-conv k3
-    rc |= ms_add_slot(S, d.clat, 6);                    // 1 upsample 0 dwconv k7
-    rc |= ms_add_slot(S, d.clat, 6);                    // 2 upsample 1 dwconv k7
-    rc |= ms_add_slot(S, d.clat, 6);                    // 3 vocoder conv0 k7
-    int C = d.cdec;
-    static const int dil[3] = {1, 3, 9};
-    for (int b = 0; b < 4; ++b) {
-        rc |= ms_add_slot(S, C, 1);                     // block tconv (K = 2r): last input frame
-        for (int u = 0; u < 3; ++u) rc |= ms_add_slot(S, C / 2, 6 * dil[u]);   // ResUnit conv1 k7 dil
-        C /= 2;
-    }
-    rc |= ms_add_slot(S, C, 6);                         // final conv k7
-    if (rc) return -1;
+    // history slots, each [ns][C][H]
+    const size_t hbytes = add_hist_slots(S, d, ns, " mstream");
+    if (!hbytes) return -1;
+    S.state_bytes += hbytes;
     // the carried parts' table: the slots for the per-stream reset, then the
     // K/V planes for the save / restore of one stream
     const size_t nsl = S.hist.size(), npart = nsl + (size_t)2 * d.clayers;
@@ -2852,9 +2671,9 @@ int codec_mstream_begin(CodecModel *m, int n_streams, int max_frames, int chunk)
         pb.push_back(S.kv + (i - nsl) * (size_t)ns * S.S * kvd);
         he[i] = S.S * kvd;
     }
-    S.hist_base = (float **)msalloc(S, npart * sizeof(float *));
-    S.hist_elems = (int *)msalloc(S, npart * 4);
-    S.snap_off = (int *)msalloc(S, (nsl + 1) * 4);
+    S.hist_base = (float **)msalloc(npart * sizeof(float *));
+    S.hist_elems = (int *)msalloc(npart * 4);
+    S.snap_off = (int *)msalloc((nsl + 1) * 4);
     if (!S.hist_base || !S.hist_elems || !S.snap_off) return -1;
     if (hipMemcpy(S.hist_base, pb.data(), npart * sizeof(float *), hipMemcpyHostToDevice) != hipSuccess) return -1;
     if (hipMemcpy(S.hist_elems, he.data(), npart * 4, hipMemcpyHostToDevice) != hipSuccess) return -1;

@@ -70,8 +70,6 @@ struct CodecMStream {
     std::vector<int> hpp;          // its host copy
     std::vector<int> hsid, hord, hend;   // a push's stream ids in pass order, their places in the caller's order, end state
     std::vector<long long> hcoff;
-    const int *pass_tv = nullptr;  // the running pass's tv (device) and frames, for its history saves
-    int pass_T = 1;
     // device table of the carried parts of one stream: the history slots'
     // base pointers and per-stream sizes (C * H), for the reset of one stream,
     // then the 2 * layers K/V planes (base of stream 0's rows, per-stream
@@ -111,7 +109,6 @@ struct CodecModel {
     size_t wbytes = 0;
     // scratch (grown on demand)
     std::vector<void *> scratch;
-    size_t scratch_bytes = 0;
     float *bufA = nullptr, *bufB = nullptr, *bufC = nullptr, *bufD = nullptr;
     size_t buf_elems = 0;
     float *tq = nullptr, *tx = nullptr, *txn = nullptr, *tatt = nullptr, *tg = nullptr, *tu = nullptr;
