@@ -777,6 +777,9 @@ bool qtts_attn_o_covers(const AttnArgs &a, const bf16_t *Wo) {
 }
 
 int qtts_attn_o(const AttnArgs &a, const bf16_t *Wo, int R, float *part, hipStream_t st) {
+#ifdef QTTS_ARGDUMP
+    qtts_argdump::attn("qtts_attn_o", a, R, Wo, part);
+#endif
     if (!qtts_attn_o_covers(a, Wo)) return 1;
     const int W2 = 2 * a.HD, LPS = W2 / 8 < 8 ? W2 / 8 : 8, RPW = 256 / LPS;
     const dim3 grid((R + RPW - 1) / RPW, a.KV, a.nrows);
@@ -818,6 +821,9 @@ bool qtts_attn_defer_ok(const AttnArgs &a) {
 }
 
 int qtts_attention(const AttnArgs &a, hipStream_t st) {
+#ifdef QTTS_ARGDUMP
+    qtts_argdump::attn("qtts_attention", a);
+#endif
     if (a.HD > 128 || a.HD < 8 || (a.HD & 7) || a.NH % a.KV) {
         fprintf(stderr, "qtts_attention: unsupported head config NH=%d KV=%d HD=%d\n", a.NH, a.KV, a.HD);
         return -1;
@@ -900,6 +906,9 @@ int qtts_attention(const AttnArgs &a, hipStream_t st) {
 }
 
 int qtts_qk_prep(const AttnArgs &a, hipStream_t st) {
+#ifdef QTTS_ARGDUMP
+    qtts_argdump::attn("qtts_qk_prep", a);
+#endif
     if ((a.NH + a.KV) * a.HD > 4096) {
         fprintf(stderr, "qtts_qk_prep: (NH+KV)*HD=%d exceeds 4096\n", (a.NH + a.KV) * a.HD);
         return -1;

@@ -435,6 +435,9 @@ static void wide_config(int R, int C, int epi, int &ks_out, int &nthr_out) {
 }
 
 int qtts_gemv(const GemvArgs &in, hipStream_t st) {
+#ifdef QTTS_ARGDUMP
+    qtts_argdump::gemv("qtts_gemv", in);
+#endif
     GemvArgs a = in;
     if (a.nb > 16 && a.nb <= 64) {   // wide lock-step batch: one launch for all rows (k_gemvx.hip), or none
         const int rc = qtts_bgemv(a, st);

@@ -331,6 +331,9 @@ __global__ __launch_bounds__(256) void k_gemvw(const void *src, const bf16_t *W,
 bool qtts_gemvw_amerge_ok(int R, int C) { return C == 2048 && (R == 1024 || R == 2048); }
 
 int qtts_gemvw(const GemvArgs &a, hipStream_t st) {
+#ifdef QTTS_ARGDUMP
+    qtts_argdump::gemv("qtts_gemvw", a);
+#endif
     if (a.amerge) {   // the talker O projection with the attention merge in its prologue
         if (a.nb != 1 || !qtts_gemvw_amerge_ok(a.R, a.C) || a.xadd || a.table || a.table_f32 || a.norm_w ||
             a.am_gph * a.am_hd * (a.C / (a.am_gph * a.am_hd)) != a.C || a.am_hd % 4 || a.am_nsplit < 1 || a.reps != 1) {

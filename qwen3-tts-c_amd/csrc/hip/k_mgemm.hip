@@ -291,6 +291,9 @@ int qtts_mgemm_plan(const GemvArgs &a, bool has_inv, bool has_part, size_t part_
 }
 
 int qtts_mgemm(const GemvArgs &a, float *inv_scratch, hipStream_t st, float *part, size_t part_elems) {
+#ifdef QTTS_ARGDUMP
+    qtts_argdump::gemv("qtts_mgemm", a, (long long)part_elems, inv_scratch, part);
+#endif
     MgPlan p;
     if (qtts_mgemm_plan(a, inv_scratch != nullptr, part != nullptr, part_elems, p)) return 1;
     if (a.norm_w) hipLaunchKernelGGL(k_row_rms, dim3(a.nb), dim3(256), 0, st, a.x, a.ldx, a.C, a.eps, inv_scratch);

@@ -108,6 +108,9 @@ int qtts_slot_reset(const SlotResetArgs &a, hipStream_t st) {
 }
 
 int qtts_embed_sum(const EmbedSumArgs &a, hipStream_t st) {
+#ifdef QTTS_ARGDUMP
+    qtts_argdump::embed("qtts_embed_sum", a);
+#endif
     if (a.G < 2 || a.G > 16) {
         fprintf(stderr, "qtts_embed_sum: %d code groups (2..16 supported)\n", a.G);
         return -1;

@@ -305,6 +305,9 @@ int qtts_pgemm_bn_env() {
 // bn: the tile width as qtts_pgemm_plan takes it; 0 = QTTS_HIP_PGEMM_BN.
 int qtts_pgemm(const GemvArgs &a, float *inv_scratch, unsigned short *planes, size_t plane_elems, hipStream_t st,
                float *part, size_t part_elems, int bn) {
+#ifdef QTTS_ARGDUMP
+    qtts_argdump::gemv("qtts_pgemm", a, (long long)part_elems * 1024 + bn, inv_scratch, part, planes);
+#endif
     PgPlan p;
     if (!bn) bn = qtts_pgemm_bn_env();
     if (qtts_pgemm_plan(a, planes != nullptr, plane_elems, part != nullptr, part_elems, bn, p)) return 1;

@@ -35,6 +35,9 @@ __global__ __launch_bounds__(256) void k_sample_g(const int *stop_rd, SampArgs a
 }  // namespace
 
 int qtts_sample(const SampArgs &a, hipStream_t st, const int *stop_rd) {
+#ifdef QTTS_ARGDUMP
+    qtts_argdump::samp("qtts_sample", a, 0, stop_rd);
+#endif
     if (a.n > qtts_samp::NMAX || a.n < 1) {
         fprintf(stderr, "qtts_sample: vocab %d unsupported (max %d)\n", a.n, qtts_samp::NMAX);
         return -1;

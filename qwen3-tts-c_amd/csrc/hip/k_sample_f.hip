@@ -28,6 +28,9 @@ __global__ __launch_bounds__(1024) void k_sample_wf(const float *logits, const i
 
 // the same choice of launch family as qtts_sample, on the forced kernels
 int qtts_sample_forced(const SampArgs &a, const SampForce &f, hipStream_t st) {
+#ifdef QTTS_ARGDUMP
+    qtts_argdump::samp("qtts_sample_forced", a, 0, nullptr, nullptr, &f);
+#endif
     if (a.n > qtts_samp::NMAX || a.n < 1) {
         fprintf(stderr, "qtts_sample: vocab %d unsupported (max %d)\n", a.n, qtts_samp::NMAX);
         return -1;

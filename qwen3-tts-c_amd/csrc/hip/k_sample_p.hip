@@ -70,6 +70,9 @@ bool qtts_sample_row_fast(const SampSlotRow &r, int mode, int n) {
 }
 
 int qtts_sample_slots(const SampArgs &a, const SampSlotRow *tab, bool all_fast, hipStream_t st, const int *stop_rd) {
+#ifdef QTTS_ARGDUMP
+    qtts_argdump::samp("qtts_sample_slots", a, all_fast, stop_rd, tab);
+#endif
     if (a.n > qtts_samp::NMAX || a.n < 1) {
         fprintf(stderr, "qtts_sample: vocab %d unsupported (max %d)\n", a.n, qtts_samp::NMAX);
         return -1;

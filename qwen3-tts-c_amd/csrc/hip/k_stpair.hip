@@ -451,6 +451,9 @@ bool qtts_gemvw_pair_covers(int R, int C, int epi) {
 
 // Two x rows (a.x, stride a.ldx) against one weight stream: 1 = not covered.
 int qtts_gemvw_pair(const GemvArgs &a, hipStream_t st) {
+#ifdef QTTS_ARGDUMP
+    qtts_argdump::gemv("qtts_gemvw_pair", a);
+#endif
     if (a.nb != 2 || !qtts_gemvw_pair_covers(a.R, a.C, a.epi)) return 1;
     if (a.table || a.table_f32 || a.amerge || a.ypart || a.reps != 1 || a.nt || a.xcopy_normed || !a.x || !a.y) return 1;
     if (a.ldx % 4 || a.ldx < a.C || ((uintptr_t)a.x & 15)) return 1;
@@ -487,6 +490,9 @@ bool qtts_attn_o_pair_covers(const AttnArgs &a, const bf16_t *Wo) {
 }
 
 int qtts_attn_o_pair(const AttnArgs &a, const bf16_t *Wo, int R, float *part, hipStream_t st) {
+#ifdef QTTS_ARGDUMP
+    qtts_argdump::attn("qtts_attn_o_pair", a, R, Wo, part);
+#endif
     if (!qtts_attn_o_pair_covers(a, Wo)) return 1;
     const int W2 = 2 * a.HD, LPS = W2 / 8 < 8 ? W2 / 8 : 8, RPW = 256 / LPS;
     const dim3 grid((R + RPW - 1) / RPW, a.KV);

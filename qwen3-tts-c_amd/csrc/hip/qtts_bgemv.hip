@@ -188,6 +188,9 @@ int qtts_bgemv_plan(const GemvArgs &a, BgPlan &p, unsigned allowed) {
 }
 
 int qtts_bgemv(const GemvArgs &a, hipStream_t st, unsigned allowed) {
+#ifdef QTTS_ARGDUMP
+    qtts_argdump::gemv("qtts_bgemv", a, allowed);
+#endif
     BgPlan p;
     const int rc = qtts_bgemv_plan(a, p, allowed);
     if (rc) return rc;

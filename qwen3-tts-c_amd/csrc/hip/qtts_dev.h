@@ -1,6 +1,7 @@
 // qtts_dev.h - the device context behind the C-ABI of include/qtts_hip.h, as
-// the three runtime translation units share it (internal, not installed):
-//   qtts_runtime.hip   the model, its state, the frame loop
+// the four runtime translation units share it (internal, not installed):
+//   qtts_runtime.hip   the model, its state, prompts, slots, the stage entries
+//   qtts_rt_frame.hip  the launches of a decode frame and of a prefill layer
 //   qtts_rt_codec.hip  the codec entries (they forward to k_codec.hip)
 //   qtts_rt_hooks.hip  the kernel-level test hooks qtts_hip_* (no qtts_dev)
 #pragma once
@@ -38,6 +39,51 @@
 struct Layer {
     bf16_t *wqkv = nullptr, *wo = nullptr, *wgu = nullptr, *wdown = nullptr;
     float *qn = nullptr, *kn = nullptr, *in = nullptr, *post = nullptr;
+};
+
+// The residual stream of a chain of layers: `rows` rows of R floats in xa, plus
+// npend partials at pend that are still to be added to them (row b of partial
+// p at pend + (p rows + b) R): the split-K columns of an O / down projection
+// that does not reduce them itself, or the per-head partials of the fused
+// attention + O.  The next GEMV that reads the residual adds them in its
+// prologue and writes the sum to the other buffer, xb, which is the residual
+// from then on.
+struct ResidStream {
+    float *xa = nullptr, *xb = nullptr;
+    const float *pend = nullptr;
+    int npend = 0, R = 0, rows = 0;
+    void reset(float *a, float *b, int R_, int rows_) { xa = a; xb = b; pend = nullptr; npend = 0; R = R_; rows = rows_; }
+    // this launch left n partials of the residual at `part`
+    void hold(const float *part, int n) { pend = part; npend = n; }
+    // g reads the residual: it takes what is pending and, with `copy`, writes
+    // the summed rows to xb (the buffers flip); a head, which reads the
+    // residual last, passes copy = false
+    void read(GemvArgs &g, bool copy = true) {
+        if (!pend) return;
+        add_in(g, copy ? xb : nullptr);
+        if (copy) { std::swap(xa, xb); pend = nullptr; npend = 0; }
+    }
+    // g writes the residual (EPI_RESID) split over kz columns of K (0: no
+    // split): from self_min rows up its last column adds the partials itself
+    // (GemvArgs::tick) and nothing is pending; below, the next reader adds them
+    // (measured: profiles/r02r_bsplit_self_ab.txt; batch 16 174.3 vs 169.5
+    // audio-s/s self-reducing, batch 8 109.9 vs 113.9; again after the loads of
+    // both sides were unserialised, same box: self-reducing at every batch
+    // size gave batch 2 38.7 vs 42.6, 4 70.5 vs 76.0, 8 123.6 vs 126.3, 16
+    // 193.3 vs 189.0)
+    void write_split(GemvArgs &g, float *part, int kz, int *tick, int self_min) {
+        if (!kz) return;
+        g.ypart = part; g.kz = kz; g.ld_ypart = (size_t)rows * g.R;
+        if (rows >= self_min) { g.tick = tick; return; }
+        g.y = nullptr;
+        hold(part, kz);
+    }
+
+private:
+    void add_in(GemvArgs &g, float *xnew) const {
+        g.xadd = pend; g.n_xadd = npend; g.ld_xadd = rows * R; g.ldb_xadd = R;
+        if (xnew) { g.xcopy = xnew; g.ldxc = R; g.xcopy_normed = 0; }
+    }
 };
 
 static constexpr int QTTS_MAX_SLOTS = 64;   // row counts with their own tail graph (qtts_dev_set_rows)
@@ -82,12 +128,10 @@ struct qtts_dev {
     float *x_tk = nullptr, *qkv = nullptr, *att = nullptr, *hbuf = nullptr, *logits = nullptr, *tk_hid = nullptr;
     float *x_st2 = nullptr, *opart = nullptr;   // attn_o: second residual buffer, per-head O partials
     // batch split-K (nb >= 2): second talker residual, O / down partials; the
-    // talker's final residual = tk_xfin + sum of tk_npend partials at tk_pend
+    // talker's residual after its last layer (what the codec head reads): tk_res
     float *x_tk2 = nullptr, *bpo = nullptr, *bpd = nullptr;
     float *ppart = nullptr;      // prefill split-K partials (<= 16 rows, kz <= 4)
-    float *tk_xfin = nullptr;
-    const float *tk_pend = nullptr;
-    int tk_npend = 0;
+    ResidStream tk_res;
     bool bsplit = true;      // QTTS_HIP_BSPLIT=0: batch O / down projections without split-K
     int bself_min = 9;       // batch split-K producers reduce their own partials from this many rows up
     int bkz_max = 0;         // QTTS_HIP_BKZ_MAX: cap on the batch split-K columns (0: 2 up to 8 rows, else 4)
@@ -268,8 +312,29 @@ struct qtts_codec_snapshot {
 };
 
 // ----------------------------------------------------------------- helpers called across the files
+inline uint32_t seed_bits(int seed) {   // a seed as the float-bit RNG state the samplers start from
+    float f = (float)seed;
+    uint32_t u;
+    memcpy(&u, &f, 4);
+    return u;
+}
 // qtts_runtime.hip
+void *dalloc(qtts_dev *dv, size_t n, bool weight);
+void drop_row_graphs(qtts_dev *dv);
+// qtts_rt_frame.hip
 GemvArgs gv(const bf16_t *W, int R, int C, const float *x, int ldx, float *y, int ldy, int nb, int epi);
+int rows_proj(qtts_dev *dv, GemvArgs a, int rows, bool prefill = false);
+int build_proj_tables(qtts_dev *dv);
+int build_qkv0_table(qtts_dev *dv);
+int talker_layers(qtts_dev *dv);
+GemvArgs talker_head_args(qtts_dev *dv);
+int talker_tail(qtts_dev *dv);
+int subtalker(qtts_dev *dv);
+int record_frame(qtts_dev *dv, bool with_talker);
+int capture(qtts_dev *dv, bool with_talker, hipGraphExec_t *out);
+int ensure_graphs(qtts_dev *dv);
+int prefill_rows(qtts_dev *dv, const std::vector<int> &slots, const std::vector<int> &nrows, std::vector<int> &last,
+                 const std::vector<int> *first = nullptr);
 // qtts_rt_codec.hip
 int join_prime(qtts_dev *dv);
 void snapshots_orphan(qtts_dev *dv);

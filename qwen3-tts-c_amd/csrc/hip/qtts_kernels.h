@@ -439,3 +439,7 @@ struct SlotResetArgs {
     uint32_t seed_bits = 0;
 };
 int qtts_slot_reset(const SlotResetArgs &a, hipStream_t st);
+
+#ifdef QTTS_ARGDUMP
+#include "qtts_argdump.h"   // the launcher entries' argument dump (tools/frame_args_ab.py)
+#endif

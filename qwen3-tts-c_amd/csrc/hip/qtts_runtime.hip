@@ -1,7 +1,8 @@
-// qtts_runtime.hip - device model, weight layout in HBM, generation state,
-// frame HIP graphs and the qtts_dev_* C-ABI of include/qtts_hip.h but its codec
-// entries (qtts_rt_codec.hip); the kernel-level hooks are in qtts_rt_hooks.hip,
-// the context they share in qtts_dev.h.
+// qtts_runtime.hip - device model, weight layout in HBM, generation state and
+// the qtts_dev_* C-ABI of include/qtts_hip.h but its codec entries
+// (qtts_rt_codec.hip); the launches of a frame and its graphs are in
+// qtts_rt_frame.hip, the kernel-level hooks in qtts_rt_hooks.hip, the context
+// they share in qtts_dev.h.
 //
 // HBM layout (per device, one model, B slots):
 //   talker layer l:  wqkv [(NH+2KV)*HD, H] bf16   fused q|k|v rows
@@ -44,7 +45,7 @@ float host_f16(uint16_t h) {
 
 // ----------------------------------------------------------------- helpers
 static constexpr size_t QTTS_ARENA_SMALL = (size_t)1 << 20, QTTS_ARENA_BLOCK = (size_t)32 << 20;
-static void *dalloc(qtts_dev *dv, size_t n, bool weight) {
+void *dalloc(qtts_dev *dv, size_t n, bool weight) {
     void *p = nullptr;
     if (n == 0) n = 16;
     // (off by default: +1.2 % in one same-box A/B, -1.3 % in the next,
@@ -76,7 +77,7 @@ static void *dalloc(qtts_dev *dv, size_t n, bool weight) {
     return p;
 }
 
-static void drop_row_graphs(qtts_dev *dv) {
+void drop_row_graphs(qtts_dev *dv) {
     for (auto &g : dv->gNr)
         if (g) { hipGraphExecDestroy(g); g = nullptr; }
 }
@@ -372,10 +373,9 @@ extern "C" size_t qtts_dev_prefix_cache_bytes(const qtts_dev_t *dv) {
     return n;
 }
 
-static std::atomic<long long> g_prefix_hits{0}, g_prefix_misses{0}, g_prefill_rows{0};
+static std::atomic<long long> g_prefix_hits{0}, g_prefix_misses{0};
 extern "C" long long qtts_hip_prefix_hits(void) { return g_prefix_hits.load(); }
 extern "C" long long qtts_hip_prefix_misses(void) { return g_prefix_misses.load(); }
-extern "C" long long qtts_hip_prefill_rows(void) { return g_prefill_rows.load(); }
 
 extern "C" void qtts_dev_destroy(qtts_dev_t *dv) {
     if (!dv) return;
@@ -480,9 +480,6 @@ static int build_rope(qtts_dev *dv, int npos, int hd, float theta, float **cs, f
     CK(hipMemcpy(*sn, s.data(), s.size() * 4, hipMemcpyHostToDevice));
     return 0;
 }
-
-static int build_proj_tables(qtts_dev *dv);
-static int build_qkv0_table(qtts_dev *dv);
 
 extern "C" int qtts_dev_finalize(qtts_dev_t *dv) {
     const qtts_dims_t &d = dv->d;
@@ -691,13 +688,6 @@ static int alloc_state(qtts_dev *dv, int nb, int max_frames, int max_prefill) {
     return 0;
 }
 
-static uint32_t seed_bits(int seed) {
-    float f = (float)seed;
-    uint32_t u;
-    memcpy(&u, &f, 4);
-    return u;
-}
-
 static int reset_counters(qtts_dev *dv) {
     const size_t B = dv->nb;
     hipStream_t st = dv->st;
@@ -723,753 +713,6 @@ static int reset_counters(qtts_dev *dv) {
     CK(hipMemcpyAsync(dv->rng, r.data(), B * 4, hipMemcpyHostToDevice, st));
     CK(hipMemcpyAsync(dv->st_rng, r.data(), B * 4, hipMemcpyHostToDevice, st));
     CK(hipStreamSynchronize(st));
-    return 0;
-}
-
-// ----------------------------------------------------------------- kernels of one frame
-enum { PK_GEMV_TALKER = 0, PK_GEMV_SUB = 1, PK_ATTN = 2, PK_SAMPLE = 3, PK_EMBED = 4 };
-struct ProfScope {  // brackets one launch with events when profiling is on
-    qtts_dev *dv;
-    size_t idx;
-    ProfScope(qtts_dev *d, int kind, double bytes) : dv(d), idx((size_t)-1) {
-        if (!dv->profiling) return;
-        qtts_dev::Prof p{kind, bytes, nullptr, nullptr, ""};
-        // no system-scope fence per event: a default event's cache write-back /
-        // invalidate would be timed as part of every short kernel
-        hipEventCreateWithFlags(&p.a, hipEventDisableSystemFence);
-        hipEventCreateWithFlags(&p.b, hipEventDisableSystemFence);
-        hipEventRecord(p.a, dv->st);
-        dv->prof.push_back(p);
-        idx = dv->prof.size() - 1;
-    }
-    void cancel() {
-        if (idx == (size_t)-1) return;
-        hipEventDestroy(dv->prof[idx].a);
-        hipEventDestroy(dv->prof[idx].b);
-        dv->prof.pop_back();
-        idx = (size_t)-1;
-    }
-    ~ProfScope() {
-        if (idx == (size_t)-1) return;
-        hipEventRecord(dv->prof[idx].b, dv->st);
-        dv->prof[idx].name = qtts_last_kernel;
-    }
-};
-static double gemv_bytes(const GemvArgs &a) {
-    return (double)a.R * a.C * 2 + (double)a.nb * a.C * 4 + (double)a.nb * a.R * 4 + (a.norm_w ? a.C * 4.0 : 0.0);
-}
-static int pgemv(qtts_dev *dv, const GemvArgs &a, int kind) {
-    ProfScope ps(dv, kind, gemv_bytes(a));
-    return qtts_gemv(a, dv->st);
-}
-// Multi-row projection over `rows` activation rows (prefill, text
-// projection): > 64 rows in one matrix-core launch (64-row chunks on its
-// grid.y), else the matrix-core kernel / batch GEMV / GEMV in chunks of 64 /
-// 16.  Row r of x / y / ids is at r*ldx / r*ldy / r*ids_bstride.
-static int rows_proj(qtts_dev *dv, GemvArgs a, int rows, bool prefill = false) {
-    const int xs = a.ldx, ys = a.ldy;
-    // the talker prefill over > 16 rows (voice-clone prompts, long prefills):
-    // activations split once, LDS-tiled MFMA GEMM (k_pgemm.hip;
-    // QTTS_HIP_PGEMM=0: k_mgemm as before)
-    if (prefill && dv->pgemm && rows > 16 && (!a.norm_w || rows <= dv->pinv_cap)) {
-        GemvArgs c = a;
-        c.nb = rows;
-        const int rc = qtts_pgemm(c, dv->pinv, dv->pplanes, dv->pplanes_elems, dv->st, dv->mpart, dv->mpart_elems);
-        if (rc <= 0) return rc;
-    }
-    if (rows > 64 && (!a.norm_w || rows <= dv->pinv_cap)) {
-        GemvArgs c = a;
-        c.nb = rows;
-        const int rc = qtts_mgemm(c, dv->pinv, dv->st, dv->mpart, dv->mpart_elems);
-        if (rc <= 0) return rc;
-    }
-    for (int r0 = 0; r0 < rows;) {
-        GemvArgs c = a;
-        int nr = rows - r0 < 64 ? rows - r0 : 64;
-        if (c.x) c.x = a.x + (size_t)r0 * xs;
-        if (c.ids) c.ids = a.ids + (size_t)r0 * a.ids_bstride;
-        c.y = a.y + (size_t)r0 * ys;
-        c.nb = nr;
-        int rc = 1;
-        // <= 16 rows (a custom-voice prompt): the batch decode kernels (k_gemvb,
-        // x sliced per wave, else k_gemvm, x split once per workgroup; ~1
-        // round over the CUs) stream the weights faster than the 64-row
-        // prefill GEMM.  (QTTS_HIP_PREFILL_GEMVB=0: k_gemvm only, the round-4
-        // path: 72 us of prefill per talker layer at the P128 prompt's rows,
-        // profiles/r05af_first_packet.txt)
-        static const bool pgb = [] { const char *e = getenv("QTTS_HIP_PREFILL_GEMVB"); return !(e && !atoi(e)); }();
-        // the residual projections (O, down: R / 16 row tiles, too few for
-        // the chip) split over K in two columns that reduce their own
-        // partials, as the talker's decode does (QTTS_HIP_PREFILL_SPLIT=kz,
-        // 2 or 4; 0: none)
-        static const int psk = [] { const char *e = getenv("QTTS_HIP_PREFILL_SPLIT");
-                                    int v = e ? atoi(e) : 2; return v == 4 ? 4 : v ? 2 : 0; }();
-        if (nr >= 2 && nr <= 16 && pgb && psk && c.epi == EPI_RESID && !c.norm_w && c.R / 16 < 256 &&
-            c.C % (32 * psk) == 0 && c.R <= (dv->d.H > dv->d.Hs ? dv->d.H : dv->d.Hs)) {
-            GemvArgs k = c;
-            k.ypart = dv->ppart; k.kz = psk; k.ld_ypart = (size_t)nr * k.R; k.tick = dv->btick;
-            rc = qtts_bgemv(k, dv->st, BG_GEMVB);
-        }
-        // (never k_gemvx: above 16 rows the prefill GEMM below; the planner answers 1 outside 2..16 rows)
-        if (rc == 1) rc = qtts_bgemv(c, dv->st, pgb ? BG_GEMVB | BG_GEMVM : BG_GEMVM);
-        if (rc == 1 && nr >= 2) rc = qtts_mgemm(c, dv->pinv, dv->st, dv->mpart, dv->mpart_elems);
-        if (rc < 0) return -1;
-        if (rc == 1) {
-            nr = nr < 16 ? nr : 16;
-            c.nb = nr;
-            CKI(qtts_gemv(c, dv->st));
-        }
-        r0 += nr;
-    }
-    return 0;
-}
-
-// ST_PROJECT_INPUT (T.c:693-702) of every embedding row a pass g >= 1 can
-// read, once at load: the per-frame input projection GEMV of those passes
-// becomes a row gather (the row a pass needs is fixed by the code id alone).
-static int build_proj_tables(qtts_dev *dv) {
-    const qtts_dims_t &d = dv->d;
-    const int nid = d.V > d.Vs ? d.V : d.Vs;
-    std::vector<int> io(nid);
-    for (int i = 0; i < nid; ++i) io[i] = i;
-    int *ids = (int *)dalloc(dv, (size_t)nid * 4, false);
-    dv->codec_ptab = (float *)dalloc(dv, (size_t)d.V * d.Hs * 4, true);
-    dv->st_ptab = (float *)dalloc(dv, (size_t)(d.G - 1) * d.Vs * d.Hs * 4, true);
-    if (!ids || !dv->codec_ptab || !dv->st_ptab) return -1;
-    CK(hipMemcpy(ids, io.data(), (size_t)nid * 4, hipMemcpyHostToDevice));
-    GemvArgs a;
-    a.W = dv->st_proj; a.R = d.Hs; a.C = d.H; a.y = dv->codec_ptab; a.ldy = d.Hs;
-    a.epi = dv->st_projb ? EPI_BIAS : EPI_STORE;
-    a.bias = dv->st_projb;
-    a.nt = 0;
-    a.table = dv->codec_emb; a.ids = ids; a.ids_bstride = 1;
-    CKI(rows_proj(dv, a, d.V));
-    for (int g = 0; g < d.G - 1; ++g) {
-        a.table = dv->st_emb + (size_t)g * d.Vs * d.H;
-        a.y = dv->st_ptab + (size_t)g * d.Vs * d.Hs;
-        CKI(rows_proj(dv, a, d.Vs));
-    }
-    CK(hipStreamSynchronize(dv->st));
-    return 0;
-}
-
-// QKV projection, then the decode attention
-static int qkv_attn(qtts_dev *dv, const GemvArgs &a, const AttnArgs &t, int kind) {
-    CKI(pgemv(dv, a, kind));
-    ProfScope ps(dv, PK_ATTN, 0);
-    return qtts_attention(t, dv->st);
-}
-GemvArgs gv(const bf16_t *W, int R, int C, const float *x, int ldx, float *y, int ldy, int nb, int epi) {
-    GemvArgs a;
-    a.W = W; a.R = R; a.C = C; a.x = x; a.ldx = ldx; a.y = y; a.ldy = ldy; a.nb = nb; a.epi = epi;
-    return a;
-}
-
-// The layer-0 q|k|v table (qtts_dev::qkv0_tab): row r of group g's block is
-// exactly what the per-frame GEMV computes for input id r (same lean kernel,
-// same arguments but the output row), so reading it is bit-identical.  One
-// launch per group, the ids on grid.y (GemvArgs::reps); a per-row launch for
-// each of ~32k ids took ~0.2 s and crashed rocprofv3's counter collection.
-static int build_qkv0_table(qtts_dev *dv) {
-    const qtts_dims_t &d = dv->d;
-    if (d.G < 2 || d.Ls < 1) return 0;
-    if (d.NHs != 2 * d.KVs) return 0;   // read only by the fused attention + O kernel (qtts_attn_o_covers)
-    const int QKV = dv->QKVs();
-    const size_t rows = (size_t)d.V + (size_t)(d.G - 2) * d.Vs;
-    const int nid = d.V > d.Vs ? d.V : d.Vs;
-    std::vector<int> io(nid);
-    for (int i = 0; i < nid; ++i) io[i] = i;
-    int *ids = (int *)dalloc(dv, (size_t)nid * 4, true);
-    dv->qkv0_tab = (float *)dalloc(dv, rows * QKV * 4, true);
-    if (!ids || !dv->qkv0_tab) return -1;
-    CK(hipMemcpy(ids, io.data(), (size_t)nid * 4, hipMemcpyHostToDevice));
-    const bool proj = dv->st_proj != nullptr;
-    for (int g = 1; g < d.G; ++g) {
-        GemvArgs a = gv(dv->sl[0].wqkv, QKV, d.Hs, nullptr, d.Hs, nullptr, QKV, 1, EPI_STORE);
-        a.norm_w = dv->sl[0].in; a.eps = d.eps; a.nt = 0;
-        if (proj) a.table_f32 = g == 1 ? dv->codec_ptab : dv->st_ptab + (size_t)(g - 2) * d.Vs * d.Hs;
-        else a.table = g == 1 ? dv->codec_emb : dv->st_emb + (size_t)(g - 2) * d.Vs * d.H;
-        a.ids = ids; a.ids_bstride = 1;
-        a.reps = g == 1 ? d.V : d.Vs;
-        a.ldy_rep = QKV;
-        a.y = dv->qkv0_tab + (g == 1 ? 0 : (size_t)d.V + (size_t)(g - 2) * d.Vs) * QKV;
-        const int rc = qtts_gemvw(a, dv->st);
-        if (rc < 0) return -1;
-        if (rc == 0) continue;
-        // shapes the lean kernel does not cover (small test models): the
-        // per-frame path runs k_gemv1, so the table does too, one row a launch
-        const int n = a.reps;
-        float *base = a.y;
-        a.reps = 1;
-        for (int r = 0; r < n; ++r) {
-            a.ids_off = r;
-            a.y = base + (size_t)r * QKV;
-            CKI(qtts_gemv(a, dv->st));
-        }
-    }
-    CK(hipStreamSynchronize(dv->st));
-    return 0;
-}
-
-
-// Batch split-K (nb >= 2, k_gemvm): the O and down projections of R rows take
-// kz workgroup columns when R / 16 tiles would not fill the chip; they store
-// partials, and the next GEMV that reads the residual adds them (xadd) and
-// writes the new residual to the other buffer (xcopy).  0 = no split.
-static int bsplit_kz(const qtts_dev *dv, int R, int C) {
-    if (!dv->bsplit || dv->nrun < 2) return 0;
-    int kz = R / 16 >= 256 ? 1 : 256 / (R / 16);
-    // (up to 8 rows the consumers add the partials: 2 columns measured +0.8 %
-    // at batch 8 over 4, gpurun_out/kz1, profiles/r03b_batch_kz_ab.txt)
-    const int cap = dv->bkz_max > 0 ? dv->bkz_max : dv->nrun <= 8 ? 2 : 4;
-    if (kz > cap) kz = cap;
-    // above 8 rows, a column slice wider than 2048 (the 1.7B talker's down
-    // projection: 6144 / 2) gives k_gemvb's waves 8 steps of 16 staged rows,
-    // over the 160 KB of LDS, and the launch fell back to k_gemvm (17.5 us at
-    // batch 16 against 10.1 us for batch 8's k_gemvb); more columns keep the
-    // slices at <= 4 steps a wave
-    if ((dv->nrun > 8 && dv->bkz_wide) || dv->bkz_wide == 2) {
-        const int wcap = dv->bkz_wide == 2 ? 4 : cap;
-        while (2 * kz <= wcap && C / kz > 2048 && C % (64 * kz) == 0) kz *= 2;
-    }
-    while (kz > 1 && C % (32 * kz)) kz /= 2;
-    return kz > 1 ? kz : 0;
-}
-// Above 8 rows the producer reduces its own partials (GemvArgs::tick: its
-// last column adds them to the residual) and nothing is pending; up to 8 the
-// consumer adds them (returns true).  Measured (profiles/r02r_bsplit_self_ab.txt):
-// batch 16 174.3 vs 169.5 audio-s/s self-reducing, batch 8 109.9 vs 113.9;
-// again after the loads of both sides were unserialised (gpurun_out ab5, same
-// box): self-reducing at every batch size gave batch 2 38.7 vs 42.6, 4 70.5
-// vs 76.0, 8 123.6 vs 126.3, 16 193.3 vs 189.0.
-static bool split_out(qtts_dev *dv, GemvArgs &g, float *part, int kz, int self_min = 0) {
-    g.ypart = part; g.kz = kz; g.ld_ypart = (size_t)dv->nrun * g.R;
-    if (dv->nrun >= (self_min > 0 ? self_min : dv->bself_min)) { g.tick = dv->btick; return false; }
-    g.y = nullptr;
-    return true;
-}
-static void add_in(GemvArgs &g, const float *part, int n, int R, int nrun, float *xnew) {
-    g.xadd = part; g.n_xadd = n; g.ld_xadd = nrun * R; g.ldb_xadd = R;
-    if (xnew) { g.xcopy = xnew; g.ldxc = R; g.xcopy_normed = 0; }
-}
-
-// Next-launch weight slices (L2Prefetch): what workgroup b of the NEXT launch
-// reads, for the two launch shapes of the batch-1 sub-talker chain
-//   k_gemvw (grid 256): rows [b R / 256, (b + 1) R / 256), contiguous
-//   (a next launch of `grid` workgroups, 256 or 512: this launch's workgroup b
-//   < 256 takes the first cap bytes of the next one's workgroup b -- b and
-//   b + 256 share an XCD, so a 512 grid is half covered)
-static L2Prefetch pf_gemvw(const qtts_dev *dv, const bf16_t *W, int R, int C, int grid = 256, bool on = true) {
-    L2Prefetch p;
-    if (!on || R % grid) return p;
-    long long bytes = (long long)(R / grid) * C * 2;
-    if (bytes > 64LL * 256 * QTTS_PF_LOADS) bytes = 64LL * 256 * QTTS_PF_LOADS;
-    if (bytes % 64) return p;
-    p.base = reinterpret_cast<const unsigned char *>(W);
-    p.pa = (long long)(R / grid) * C * 2; p.pb = 0; p.chunks = (int)(bytes / 64); p.lg = 30; p.ld = 0;
-    p.nwg = grid;
-    p.sink = dv->pf_sink;
-    return p;
-}
-#ifdef QTTS_STAMPS
-#define DBG_XFIRST(a) do { const char *e_ = getenv("QTTS_HIP_DBG_XFIRST"); (a).dbg_xfirst = e_ ? atoi(e_) : 0; } while (0)
-#else
-#define DBG_XFIRST(a) do { } while (0)
-#endif
-//   k_attn_o (grid (R / RPW, KV), linear b = rb + (R / RPW) kvh): rows
-//   [RPW rb, +RPW) x columns [2 HD kvh, +2 HD) of W_o [R][NH HD]
-static L2Prefetch pf_attn_o(const qtts_dev *dv, const bf16_t *Wo, int R, int NH, int HD) {
-    L2Prefetch p;
-    const int W2 = 2 * HD, LPS = W2 / 8 < 8 ? W2 / 8 : 8, RPW = 256 / LPS;
-    const int cpr = W2 * 2 / 64;   // 64-B chunks per row slice
-    if (R % RPW || (cpr & (cpr - 1)) || cpr < 1 || RPW * cpr > 256 * QTTS_PF_LOADS) return p;
-    p.base = reinterpret_cast<const unsigned char *>(Wo);
-    p.pm = R / RPW; p.pa = (long long)RPW * NH * HD * 2; p.pb = W2 * 2;
-    p.chunks = RPW * cpr; p.lg = __builtin_ctz(cpr); p.ld = NH * HD * 2; p.sink = dv->pf_sink;
-    p.nwg = (R / RPW) * (NH / 2);   // (R / RPW) row blocks x the kv heads of a GQA-2 W_o
-    return p;
-}
-
-// the flag a frame's stop readers take: a fed run's gate (k_textfeed.hip), else `stopped`
-static const int *stop_rd(const qtts_dev *dv) { return dv->fed ? dv->tf_gate : dv->stopped; }
-
-static int talker_layers(qtts_dev *dv) {
-    const qtts_dims_t &d = dv->d;
-    const int nb = dv->nrun, NBA = dv->nb, QKV = dv->QKV(), AD = d.NH * d.HD, KVD = d.KV * d.HD;
-    hipStream_t st = dv->st;
-    // (the talker's O without split-K at batch 8: 142.0 / 142.6 vs 140.7 / 142.1
-    // audio-s/s, within noise; its down without: 135.9 / 135.6, gpurun_out/tkz)
-    const int kzo = bsplit_kz(dv, d.H, AD), kzd = bsplit_kz(dv, d.H, d.I);
-    float *xa = dv->x_tk, *xb = dv->x_tk2;
-    const float *pend = nullptr;
-    int npend = 0;
-    for (int l = 0; l < d.L; ++l) {
-        Layer &ly = dv->tl[l];
-        GemvArgs a = gv(ly.wqkv, QKV, d.H, xa, d.H, dv->qkv, QKV, nb, EPI_STORE);
-        a.norm_w = ly.in; a.eps = d.eps;
-        if (pend) add_in(a, pend, npend, d.H, nb, xb);
-        AttnArgs t;
-        t.mode = 0; t.qkv = dv->qkv; t.ld_qkv = QKV; t.qn_w = ly.qn; t.kn_w = ly.kn; t.eps = d.eps;
-        t.rope_cos = dv->rope_cos; t.rope_sin = dv->rope_sin;
-        t.kc = dv->kv_layer(dv->kc, l); t.vc = dv->kv_layer(dv->vc, l); t.S = dv->S; t.kv_dtype = dv->kv_dtype;
-        t.pos = dv->kv_len; t.NH = d.NH; t.KV = d.KV; t.HD = d.HD; t.out = dv->att; t.ld_out = AD; t.nrows = nb;
-        t.skip = stop_rd(dv);
-        t.part = dv->att_part; t.cnt = dv->att_cnt; t.nsplit = dv->att_nsplit; t.lpk = dv->attn_lpk;
-        // batch 1: the attention's split merge moves into the O projection's
-        // prologue (one dependent hand-off fewer per layer)
-        const bool defer = dv->attn_defer && nb == 1 && qtts_attn_defer_ok(t) && qtts_gemvw_amerge_ok(d.H, AD);
-        t.defer = defer;
-        dv->att_own = !defer;
-        const bool dbg = dv->gm_dbg && l == dv->gm_dbg_layer;
-        if (dbg) a.dbg = dv->gm_dbg;
-        // (batch 1: the O projection's slices two launches ahead, the attention in between)
-        if (nb == 1 && (dv->l2pf_tk & 1)) a.pf = pf_gemvw(dv, ly.wo, d.H, AD);
-        CKI(qkv_attn(dv, a, t, PK_GEMV_TALKER));
-        if (pend) { std::swap(xa, xb); pend = nullptr; }
-        GemvArgs o = gv(ly.wo, d.H, AD, dv->att, AD, xa, d.H, nb, EPI_RESID);
-        if (dbg) o.dbg = dv->gm_dbg + 2048 * 8;
-        if (defer) {
-            o.amerge = dv->att_part; o.am_pos = dv->kv_len; o.am_nsplit = dv->att_nsplit;
-            o.am_ch = qtts_attn_keys_per_split(d.HD, true, dv->attn_lpk); o.am_hd = d.HD; o.am_gph = d.NH / d.KV;
-        }
-        // the talker's O / down reduce their own partials at every batch size:
-        // its q|k|v and gate|up prologues (2048-wide x rows) then read x alone
-        // (batch 8: 141.1 / 143.1 vs 138.9 / 141.2 audio-s/s adding the partials
-        // there, same box, gpurun_out/bstk; the sub-talker keeps the consumer
-        // add up to 8 rows, where self-reduction measured slower)
-        const int tk_self = 2;
-        const bool opend = kzo && split_out(dv, o, dv->bpo, kzo, tk_self);
-        if (nb == 1 && (dv->l2pf_tk & 2)) o.pf = pf_gemvw(dv, ly.wgu, 2 * d.I, d.H, 512);
-        CKI(pgemv(dv, o, PK_GEMV_TALKER));
-        a = gv(ly.wgu, 2 * d.I, d.H, xa, d.H, dv->hbuf, d.I, nb, EPI_SWIGLU);
-        a.norm_w = ly.post; a.eps = d.eps;
-        if (dbg) a.dbg = dv->gm_dbg + 2 * 2048 * 8;
-        if (opend) add_in(a, dv->bpo, kzo, d.H, nb, xb);
-        CKI(pgemv(dv, a, PK_GEMV_TALKER));
-        if (opend) std::swap(xa, xb);
-        GemvArgs dn = gv(ly.wdown, d.H, d.I, dv->hbuf, d.I, xa, d.H, nb, EPI_RESID);
-        if (dbg) dn.dbg = dv->gm_dbg + 3 * 2048 * 8;
-        if (kzd && split_out(dv, dn, dv->bpd, kzd, tk_self)) { pend = dv->bpd; npend = kzd; }
-        CKI(pgemv(dv, dn, PK_GEMV_TALKER));
-    }
-    dv->tk_xfin = xa; dv->tk_pend = pend; dv->tk_npend = npend;
-    return 0;
-}
-
-// logit head, then the sampler
-static int head_sample(qtts_dev *dv, const GemvArgs &a, const SampArgs &s, int kind) {
-    CKI(pgemv(dv, a, kind));
-    ProfScope ps(dv, PK_SAMPLE, 0);
-    if (dv->f_armed) {   // forcing or taps armed: the forced sampler (its own frame graphs, graph_key 2)
-        SampForce f;
-        f.forced = dv->f_forced; f.drawn = dv->f_drawn; f.taps = dv->f_taps;
-        f.tap_logits = dv->f_tap_logits; f.tap_meta = dv->f_tap_meta; f.tap_ld = dv->f_tap_ld;
-        return qtts_sample_forced(s, f, dv->st);
-    }
-    // per-slot parameters: the per-slot sampler (its own frame graphs, graph_key 3 / 4)
-    // (a fed run: the rows read the gate; nullptr otherwise -- the launches of before)
-    const int *rd = dv->fed ? dv->tf_gate : nullptr;
-    if (dv->sp_armed) return qtts_sample_slots(s, dv->sp_tab, !dv->sp_general, dv->st, rd);
-    return qtts_sample(s, dv->st, rd);
-}
-
-// final norm + codec head; normed hidden -> tk_hid (T.c:526-530, Q.c:1295)
-static GemvArgs talker_head_args(qtts_dev *dv) {
-    const qtts_dims_t &d = dv->d;
-    GemvArgs a = gv(dv->head, d.V, d.H, dv->tk_xfin ? dv->tk_xfin : dv->x_tk, d.H, dv->logits, d.V, dv->nrun,
-                    EPI_STORE);
-    a.norm_w = dv->tk_norm; a.eps = d.eps; a.xcopy = dv->tk_hid; a.ldxc = d.H; a.xcopy_normed = 1;
-    if (dv->tk_pend) add_in(a, dv->tk_pend, dv->tk_npend, d.H, dv->nrun, nullptr);
-    return a;
-}
-static int talker_tail(qtts_dev *dv) { return pgemv(dv, talker_head_args(dv), PK_GEMV_TALKER); }
-
-// codec head, then the group-0 draw with suppression / repetition penalty / EOS rules
-static int talker_head_sample(qtts_dev *dv) {
-    const qtts_dims_t &d = dv->d;
-    const GemvArgs a = talker_head_args(dv);
-    SampArgs s;
-    s.logits = dv->logits; s.ld = d.V; s.n = d.V; s.nb = dv->nrun;
-    s.top_k = dv->par.top_k; s.top_p = dv->par.top_p; s.temp = dv->par.temperature;
-    s.rng = dv->rng; s.mode = 1; s.suppress_lo = d.V - 1024; s.eos = d.eos_id;
-    s.rep = dv->par.repetition_penalty; s.counts = dv->counts; s.fixed = dv->par.fixed_codec_tokens;
-    s.n_gen = dv->n_gen; s.stopped = dv->stopped; s.cur_row = dv->cur_row; s.stop_step = dv->stop_step;
-    s.host_stopped = dv->hstop;
-    s.st_rng = dv->st_rng; s.seed_bits = seed_bits(dv->par.seed);
-    s.codes = dv->codes; s.codes_bstride = (dv->max_frames + 1) * d.G; s.G = d.G; s.out_tok = dv->last_tok;
-    return head_sample(dv, a, s, PK_GEMV_TALKER);
-}
-
-// Batch 1: passes 0 and 1 as one two-row pass (k_stpair.hip).  Pass 0's input
-// is the talker hidden and pass 1's the table row of the talker's draw
-// (last_tok, written by the talker's sampler before the sub-talker's first
-// launch), so both rows are known up front: positions 0 and 1 are a causal
-// two-token prefill, every matrix is read once for both, and per row the
-// arithmetic is the single-row kernels' (bit-identical codes).
-// pair passes enqueued (or captured) since the library loaded: a test's proof
-// that the pair path, not the 16-pass chain, ran
-static std::atomic<long long> g_st_pair_passes{0};
-extern "C" long long qtts_hip_st_pair_passes(void) { return g_st_pair_passes.load(); }
-
-static AttnArgs st_pair_attn_args(const qtts_dev *dv, int l) {
-    const qtts_dims_t &d = dv->d;
-    const int KVD = d.KVs * d.HDs;
-    const Layer &ly = dv->sl[l];
-    AttnArgs t;
-    t.mode = 0; t.qkv = dv->qkv_s; t.ld_qkv = dv->QKVs(); t.qn_w = ly.qn; t.kn_w = ly.kn; t.eps = d.eps;
-    t.rope_cos = dv->rope_cos_s; t.rope_sin = dv->rope_sin_s;
-    t.kc = dv->kcs + (size_t)l * dv->nb * d.G * KVD; t.vc = dv->vcs + (size_t)l * dv->nb * d.G * KVD; t.S = d.G;
-    t.pos = nullptr; t.pos_const = 0; t.NH = d.NHs; t.KV = d.KVs; t.HD = d.HDs; t.ld_out = d.NHs * d.HDs;
-    t.nrows = 2; t.skip = stop_rd(dv);
-    if (l == 0) {   // row 1: q|k|v from the load-time table by the talker's draw, its input row to the residual
-        const bool proj = dv->st_proj != nullptr;
-        t.qkv_tab = dv->qkv0_tab; t.tab_ids = dv->last_tok; t.tab_bstride = 1; t.tab_off = 0;
-        t.xc_tab = proj ? dv->codec_ptab : nullptr; t.xc_tab16 = proj ? nullptr : dv->codec_emb;
-        t.xc_dst = dv->x_st + d.Hs; t.xc_n = d.Hs;
-    }
-    return t;
-}
-// where today's fast path runs (fused attention + O, the layer-0 q|k|v table)
-// and the pair kernels cover every shape; everything else keeps the 16 passes
-static bool st_pair_ok(const qtts_dev *dv) {
-    const qtts_dims_t &d = dv->d;
-    if (!dv->st_pair || dv->nrun != 1 || !dv->attn_o || !dv->qkv0_tab || d.G < 2 || d.Ls < 1) return false;
-    if (dv->st_proj && !(dv->st_ptab && dv->codec_ptab)) return false;
-    if (!dv->st_proj && d.H != d.Hs) return false;
-    if (!qtts_gemvw_pair_covers(dv->QKVs(), d.Hs, EPI_STORE) || !qtts_gemvw_pair_covers(2 * d.Is, d.Hs, EPI_SWIGLU) ||
-        !qtts_gemvw_pair_covers(d.Hs, d.Is, EPI_RESID))
-        return false;
-    for (int l = 0; l < d.Ls; ++l)
-        if (!qtts_attn_o_pair_covers(st_pair_attn_args(dv, l), dv->sl[l].wo)) return false;
-    return true;
-}
-static int pgemv_pair(qtts_dev *dv, const GemvArgs &a) {
-    ProfScope ps(dv, PK_GEMV_SUB, gemv_bytes(a));
-    if (qtts_gemvw_pair(a, dv->st) != 0) {
-        fprintf(stderr, "qtts: pair GEMV launch failed (R=%d C=%d)\n", a.R, a.C);
-        return -1;
-    }
-    return 0;
-}
-// the layers of passes 0 and 1; *xfin: the residual rows [2][Hs] after the last layer
-static int subtalker_pair_layers(qtts_dev *dv, int pfm, float **xfin) {
-    const qtts_dims_t &d = dv->d;
-    const int QKV = dv->QKVs(), AD = d.NHs * d.HDs;
-    const bool proj = dv->st_proj != nullptr;
-    float *xa = dv->x_st, *xb = dv->x_st2;
-    if (proj) {   // ST_PROJECT_INPUT of row 0 (T.c:693-702); row 1's projected row is a table row
-        GemvArgs a = gv(dv->st_proj, d.Hs, d.H, dv->tk_hid, d.H, dv->x_st, d.Hs, 1, dv->st_projb ? EPI_BIAS : EPI_STORE);
-        a.bias = dv->st_projb;
-        a.nt = 0;
-        CKI(pgemv(dv, a, PK_GEMV_SUB));
-    }
-    {   // layer-0 q|k|v of row 0 (the single-row kernel; row 1's is the table's)
-        Layer &ly = dv->sl[0];
-        GemvArgs a = gv(ly.wqkv, QKV, d.Hs, xa, d.Hs, dv->qkv_s, QKV, 1, EPI_STORE);
-        a.norm_w = ly.in; a.eps = d.eps; a.nt = 0;
-        if (!proj) { a.x = dv->tk_hid; a.ldx = d.H; a.xcopy = dv->x_st; a.ldxc = d.Hs; a.xcopy_normed = 0; }
-        if (pfm & 1) a.pf = pf_attn_o(dv, ly.wo, d.Hs, d.NHs, d.HDs);
-        CKI(pgemv(dv, a, PK_GEMV_SUB));
-    }
-    for (int l = 0; l < d.Ls; ++l) {
-        Layer &ly = dv->sl[l];
-        // QTTS_HIP_GM_DBG=98: stamps of the pair pass, layer 2's q|k|v / attention + O / gate|up / down
-        const bool sdbg = dv->gm_dbg && dv->gm_dbg_layer == 98 && l == 2;
-        if (l > 0) {
-            GemvArgs a = gv(ly.wqkv, QKV, d.Hs, xa, d.Hs, dv->qkv_s, QKV, 2, EPI_STORE);
-            a.norm_w = ly.in; a.eps = d.eps; a.nt = 0;
-            if (sdbg) a.dbg = dv->gm_dbg;
-            if (pfm & 1) a.pf = pf_attn_o(dv, ly.wo, d.Hs, d.NHs, d.HDs);
-            CKI(pgemv_pair(dv, a));
-        }
-        AttnArgs t = st_pair_attn_args(dv, l);
-        if (pfm & 2) t.pf = pf_gemvw(dv, ly.wgu, 2 * d.Is, d.Hs);
-#ifdef QTTS_STAMPS
-        if (sdbg) t.dbg = dv->gm_dbg + 2048 * 8;
-#endif
-        {
-            ProfScope ps(dv, PK_ATTN, (double)d.Hs * AD * 2);
-            if (qtts_attn_o_pair(t, ly.wo, d.Hs, dv->opart, dv->st) != 0) {
-                fprintf(stderr, "qtts: pair attention + O launch failed (layer %d)\n", l);
-                return -1;
-            }
-        }
-        // gate|up: residual + the per-head O partials of both rows, the new residual to the other buffer
-        GemvArgs a = gv(ly.wgu, 2 * d.Is, d.Hs, xa, d.Hs, dv->h_s, d.Is, 2, EPI_SWIGLU);
-        a.norm_w = ly.post; a.eps = d.eps; a.nt = 0;
-        if (pfm & 4) a.pf = pf_gemvw(dv, ly.wdown, d.Hs, d.Is);
-        add_in(a, dv->opart, d.KVs, d.Hs, 2, xb);
-        if (sdbg) a.dbg = dv->gm_dbg + 2 * 2048 * 8;
-        CKI(pgemv_pair(dv, a));
-        std::swap(xa, xb);
-        // (row 0 in the last layer needs only its k / v store; its MLP rides along)
-        a = gv(ly.wdown, d.Hs, d.Is, dv->h_s, d.Is, xa, d.Hs, 2, EPI_RESID);
-        a.nt = 0;
-        if (pfm & 8) {
-            if (l + 1 < d.Ls) a.pf = pf_gemvw(dv, dv->sl[l + 1].wqkv, QKV, d.Hs);
-            else a.pf = pf_gemvw(dv, dv->lm, d.Vs, d.Hs);
-        }
-        if (sdbg) a.dbg = dv->gm_dbg + 3 * 2048 * 8;
-        CKI(pgemv_pair(dv, a));
-    }
-    *xfin = xa;
-    g_st_pair_passes.fetch_add(1);
-    return 0;
-}
-
-// 16 sub-talker passes (T.c:539-736)
-static int subtalker(qtts_dev *dv) {
-    const qtts_dims_t &d = dv->d;
-    const int nb = dv->nrun, NBA = dv->nb, QKV = dv->QKVs(), AD = d.NHs * d.HDs, KVD = d.KVs * d.HDs;
-    const int cstride = (dv->max_frames + 1) * d.G;
-    hipStream_t st = dv->st;
-    const bool proj = dv->st_proj != nullptr;
-    // batch 1, fused attention + O: each launch also pulls the next launch's
-    // weight slice into its XCD's L2 (GemvArgs::pf / AttnArgs::pf)
-    const bool pfon = nb == 1 && dv->attn_o && dv->l2pf;
-    const int pfm = pfon ? dv->l2pf : 0;
-    const bool tab0_ok = nb == 1 && dv->attn_o && dv->qkv0_tab && (!proj || dv->st_ptab);
-    auto first_op_pf = [&](int gn) {   // pass gn's first launch (layer 0: the table attention or q|k|v)
-        if (gn >= d.G) return L2Prefetch();
-        if (gn >= 1 && tab0_ok) return pf_attn_o(dv, dv->sl[0].wo, d.Hs, d.NHs, d.HDs);
-        return pf_gemvw(dv, dv->sl[0].wqkv, QKV, d.Hs);
-    };
-    // pass g's lm head on residual row(s) x, then its sampler
-    auto pass_head = [&](int g, const float *x, const float *pend, int npend) -> int {
-        GemvArgs a = gv(dv->lm + (size_t)(g - 1) * d.Vs * d.Hs, d.Vs, d.Hs, x, d.Hs, dv->logits_s, d.Vs, nb,
-                        EPI_STORE);
-        a.norm_w = dv->st_norm; a.eps = d.eps; a.nt = 0;
-        if (pend) add_in(a, pend, npend, d.Hs, nb, nullptr);
-        if (pfm & 16) a.pf = first_op_pf(g + 1);   // (two launches ahead: the sampler runs in between)
-        SampArgs s;
-        s.logits = dv->logits_s; s.ld = d.Vs; s.n = d.Vs; s.nb = nb;
-        s.top_k = dv->par.st_top_k; s.top_p = dv->par.st_top_p; s.temp = dv->par.st_temperature;
-        s.mode = 0; s.st_rng = dv->st_rng; s.stopped = dv->stopped; s.cur_row = dv->cur_row;
-        s.codes = dv->codes; s.codes_bstride = cstride; s.G = d.G; s.g = g; s.out_tok = dv->last_tok;
-        return head_sample(dv, a, s, PK_GEMV_SUB);
-    };
-    int g0 = 0;
-    if (st_pair_ok(dv)) {   // passes 0 and 1 as one two-row pass; pass 1's head reads row 1
-        float *xfin = nullptr;
-        CKI(subtalker_pair_layers(dv, pfm, &xfin));
-        CKI(pass_head(1, xfin + d.Hs, nullptr, 0));
-        g0 = 2;
-    }
-    for (int g = g0; g < d.G; ++g) {
-        // input source for this pass
-        GemvArgs src;  // x / table description only
-        src.nb = nb;
-        // passes >= 1 of a projecting model gather their already-projected row
-        const bool ptab = proj && g >= 1 && dv->st_ptab;
-        if (g == 0) { src.x = dv->tk_hid; src.ldx = d.H; }
-        else {
-            if (ptab) src.table_f32 = g == 1 ? dv->codec_ptab : dv->st_ptab + (size_t)(g - 2) * d.Vs * d.Hs;
-            else src.table = g == 1 ? dv->codec_emb : dv->st_emb + (size_t)(g - 2) * d.Vs * d.H;
-            // the previous draw's id (group g - 1: the talker's for g = 1)
-            src.ids = dv->last_tok; src.ids_bstride = 1; src.row_sel = nullptr; src.ids_rstride = 0;
-            src.ids_off = 0;
-        }
-        auto set_src = [&](GemvArgs &a) {
-            a.x = src.x; a.ldx = src.ldx; a.table = src.table; a.table_f32 = src.table_f32; a.ids = src.ids;
-            a.ids_bstride = src.ids_bstride; a.row_sel = src.row_sel; a.ids_rstride = src.ids_rstride;
-            a.ids_off = src.ids_off;
-        };
-        if (proj && !ptab) {  // ST_PROJECT_INPUT (T.c:693-702)
-            GemvArgs a = gv(dv->st_proj, d.Hs, d.H, nullptr, 0, dv->x_st, d.Hs, nb, dv->st_projb ? EPI_BIAS : EPI_STORE);
-            set_src(a);
-            a.bias = dv->st_projb;
-            a.nt = 0;
-            CKI(pgemv(dv, a, PK_GEMV_SUB));
-        }
-        // attn_o (batch 1): attention + O projection by kv head into per-head
-        // partials, summed with the residual in the gate|up GEMV's prologue,
-        // which writes the new residual to the other buffer (xa -> xb)
-        // batch (nb >= 2): O / down split-K partials added by the next
-        // residual reader (bsplit_kz)
-        float *xa = dv->x_st, *xb = dv->x_st2;
-        const int kzo = bsplit_kz(dv, d.Hs, AD), kzd = bsplit_kz(dv, d.Hs, d.Is);
-        const float *pend = nullptr;
-        int npend = 0;
-        for (int l = 0; l < d.Ls; ++l) {
-            Layer &ly = dv->sl[l];
-            // pass 0 produces no logits: its last layer only has to store its k / v
-            // (ST_FORWARD of pass 1 restarts from its own input, T.c:704-714)
-            const bool kv_only = g == 0 && l == d.Ls - 1;
-            GemvArgs a = gv(ly.wqkv, QKV, d.Hs, xa, d.Hs, dv->qkv_s, QKV, nb, EPI_STORE);
-            a.norm_w = ly.in; a.eps = d.eps; a.nt = 0;
-            // QTTS_HIP_GM_DBG=99: stamps of pass 5, layer 2's q|k|v / (batch: O) / gate|up / down
-            const bool sdbg = dv->gm_dbg && dv->gm_dbg_layer == 99 && g == 5 && l == 2;
-            if (sdbg) { a.dbg = dv->gm_dbg; DBG_XFIRST(a); }
-            if (l == 0 && (!proj || ptab)) { set_src(a); a.xcopy = dv->x_st; a.ldxc = d.Hs; a.xcopy_normed = 0; }
-            else if (pend) add_in(a, pend, npend, d.Hs, nb, xb);
-            AttnArgs t;
-            t.mode = 0; t.qkv = dv->qkv_s; t.ld_qkv = QKV; t.qn_w = ly.qn; t.kn_w = ly.kn; t.eps = d.eps;
-            t.rope_cos = dv->rope_cos_s; t.rope_sin = dv->rope_sin_s;
-            t.kc = dv->kcs + (size_t)l * NBA * d.G * KVD; t.vc = dv->vcs + (size_t)l * NBA * d.G * KVD; t.S = d.G;
-            t.pos = nullptr; t.pos_const = g; t.NH = d.NHs; t.KV = d.KVs; t.HD = d.HDs; t.out = dv->att_s;
-            t.ld_out = AD; t.nrows = nb; t.skip = stop_rd(dv);
-            t.cnt = dv->att_cnt;
-            // batch 1, pass g >= 1, layer 0: q|k|v come from the load-time table
-            // by the input id (no GEMV); the gate|up GEMV reads the residual
-            // from the input table row itself.  Only where the fused attention +
-            // O kernel runs: it alone reads the table, and the skipped GEMV is
-            // also what copies the residual (the generic paths would read a
-            // stale qkv_s and an unwritten x_st)
-            const bool tab0 = l == 0 && g >= 1 && nb == 1 && dv->attn_o && dv->qkv0_tab && (!proj || ptab) &&
-                              qtts_attn_o_covers(t, ly.wo);
-            GemvArgs o = gv(ly.wo, d.Hs, AD, dv->att_s, AD, xa, d.Hs, nb, EPI_RESID);
-            o.nt = 0;
-            bool fused_o = false, opend = false;
-            // (batch 1 only: at batch 8 / 16 the per-row recompute measured slower than
-            // the separate attention + split-K O projection, 98 vs 107 / 132 vs 155
-            // audio-s/s, profiles/r01av_bench_batch_attn_o.txt)
-            // batch, pass g >= 1, layer 0: the same table, read by the short
-            // attention kernel, which also copies the input row to the
-            // residual (AttnArgs::xc_dst; the skipped GEMV's xcopy)
-            const bool hd_ok = d.HDs == 128 || d.HDs == 64 || d.HDs == 32 || d.HDs == 16;
-            const bool tab0b = l == 0 && g >= 1 && nb >= 2 && dv->tab0b && dv->qkv0_tab && (!proj || ptab) &&
-                               d.NHs == 2 * d.KVs && d.G <= 16 && hd_ok;
-            if (tab0 || tab0b) {
-                t.qkv_tab = dv->qkv0_tab + (g == 1 ? 0 : (size_t)d.V + (size_t)(g - 2) * d.Vs) * QKV;
-                t.tab_ids = src.ids; t.tab_bstride = src.ids_bstride; t.tab_row_sel = src.row_sel;
-                t.tab_rstride = src.ids_rstride; t.tab_off = src.ids_off;
-            }
-            if (tab0b) { t.xc_tab = src.table_f32; t.xc_tab16 = src.table; t.xc_dst = xa; t.xc_n = d.Hs; }
-            if (pfm & 1) a.pf = pf_attn_o(dv, ly.wo, d.Hs, d.NHs, d.HDs);
-            if (pfm & 2) t.pf = kv_only ? first_op_pf(g + 1) : pf_gemvw(dv, ly.wgu, 2 * d.Is, d.Hs);
-#ifdef QTTS_STAMPS
-            if (sdbg) t.dbg = dv->gm_dbg + 2048 * 8;   // (batch 1: the attention + O launch in the "O / -" slot)
-#endif
-            if (dv->attn_o && nb == 1) {
-                if (!tab0) CKI(pgemv(dv, a, PK_GEMV_SUB));
-                if (pend) { std::swap(xa, xb); pend = nullptr; }   // the QKV GEMV wrote xa + partials to xb
-                ProfScope ps(dv, PK_ATTN, (double)d.Hs * AD * 2);
-                const int rc = qtts_attn_o(t, ly.wo, d.Hs, dv->opart, st);
-                if (rc < 0) return -1;
-                if (rc == 1) {   // not covered: the attention kernel, then the O GEMV below
-                    ps.cancel();
-                    { ProfScope pa(dv, PK_ATTN, 0); CKI(qtts_attention(t, st)); }
-                    o.y = xa;
-                    if (kzo) opend = split_out(dv, o, dv->bpo, kzo);
-                    if (!kv_only) CKI(pgemv(dv, o, PK_GEMV_SUB));
-                } else {
-                    fused_o = true;
-                }
-            } else {
-                if (tab0b) {
-                    ProfScope pa(dv, PK_ATTN, 0);
-                    CKI(qtts_attention(t, st));
-                } else {
-                    CKI(qkv_attn(dv, a, t, PK_GEMV_SUB));
-                }
-                if (pend) { std::swap(xa, xb); pend = nullptr; }   // the QKV GEMV wrote xa + partials to xb
-                o.y = xa;
-                if (kzo) opend = split_out(dv, o, dv->bpo, kzo);
-                if (sdbg) o.dbg = dv->gm_dbg + 2048 * 8;
-                if (!kv_only) CKI(pgemv(dv, o, PK_GEMV_SUB));
-            }
-            if (kv_only) break;
-            a = gv(ly.wgu, 2 * d.Is, d.Hs, xa, d.Hs, dv->h_s, d.Is, nb, EPI_SWIGLU);
-            a.norm_w = ly.post; a.eps = d.eps; a.nt = 0;
-            if (pfm & 4) a.pf = pf_gemvw(dv, ly.wdown, d.Hs, d.Is);
-            if (sdbg) { a.dbg = dv->gm_dbg + 2 * 2048 * 8; DBG_XFIRST(a); }
-            if (tab0) set_src(a);   // the residual is the input table row (x_st was not written)
-            if (fused_o) {
-                add_in(a, dv->opart, d.KVs, d.Hs, nb, xb);
-            } else if (opend) {
-                add_in(a, dv->bpo, kzo, d.Hs, nb, xb);
-            }
-            CKI(pgemv(dv, a, PK_GEMV_SUB));
-            if (fused_o || opend) std::swap(xa, xb);
-            a = gv(ly.wdown, d.Hs, d.Is, dv->h_s, d.Is, xa, d.Hs, nb, EPI_RESID);
-            a.nt = 0;
-            if (pfm & 8) {
-                if (l + 1 < d.Ls) a.pf = pf_gemvw(dv, dv->sl[l + 1].wqkv, QKV, d.Hs);
-                else if (g >= 1) a.pf = pf_gemvw(dv, dv->lm + (size_t)(g - 1) * d.Vs * d.Hs, d.Vs, d.Hs);
-            }
-            if (sdbg) { a.dbg = dv->gm_dbg + 3 * 2048 * 8; DBG_XFIRST(a); }
-            if (kzd && split_out(dv, a, dv->bpd, kzd)) { pend = dv->bpd; npend = kzd; }
-            CKI(pgemv(dv, a, PK_GEMV_SUB));
-        }
-        if (g == 0) continue;  // pass 0 produces no logits
-        CKI(pass_head(g, xa, pend, npend));
-    }
-    return 0;
-}
-
-static int embed_sum(qtts_dev *dv, int advance) {
-    const qtts_dims_t &d = dv->d;
-    EmbedSumArgs e;
-    e.codes = dv->codes; e.codes_bstride = (dv->max_frames + 1) * d.G; e.G = d.G;
-    e.cur_row = dv->cur_row; e.stopped = stop_rd(dv); e.codec_emb = dv->codec_emb; e.st_emb = dv->st_emb;
-    e.Vs = d.Vs; e.H = d.H; e.nb = dv->nrun; e.trailing = dv->trailing; e.tr_cap = dv->tr_cap;
-    e.n_trailing = dv->n_trailing; e.pad = dv->pad_emb; e.out = dv->x_tk; e.kv_len = dv->kv_len; e.advance = advance;
-    ProfScope ps(dv, PK_EMBED, 0);
-    return qtts_embed_sum(e, dv->st);
-}
-
-static int record_frame(qtts_dev *dv, bool with_talker) {
-    // step 0 starts from the prefill's hidden in x_tk (no pending partials)
-    dv->tk_xfin = dv->x_tk; dv->tk_pend = nullptr; dv->tk_npend = 0;
-    TextGateArgs tg;
-    if (dv->fed) {   // the gate first; a talker step updates x_tk in place, so a held slot's row is saved
-        tg.stopped = dv->stopped; tg.text_open = dv->tf_open; tg.n_gen = dv->n_gen; tg.n_trailing = dv->n_trailing;
-        tg.gate = dv->tf_gate; tg.held = dv->tf_held; tg.x = dv->x_tk; tg.x_save = with_talker ? dv->tf_xsave : nullptr;
-        tg.H = dv->d.H; tg.nb = dv->nrun;
-        ProfScope ps(dv, PK_EMBED, 0);
-        CKI(qtts_text_gate(tg, dv->st));
-    }
-    if (with_talker) CKI(talker_layers(dv));
-    CKI(talker_head_sample(dv));
-    CKI(subtalker(dv));
-    CKI(embed_sum(dv, with_talker ? 1 : 0));
-    if (dv->fed && with_talker) {
-        ProfScope ps(dv, PK_EMBED, 0);
-        CKI(qtts_text_restore(tg, dv->st));
-    }
-    return 0;
-}
-
-static int capture(qtts_dev *dv, bool with_talker, hipGraphExec_t *out) {
-    hipGraph_t g = nullptr;
-    CK(hipStreamBeginCapture(dv->st, hipStreamCaptureModeThreadLocal));
-    int rc = record_frame(dv, with_talker);
-    hipError_t e = hipStreamEndCapture(dv->st, &g);
-    if (rc || e != hipSuccess) {
-        fprintf(stderr, "qtts: frame graph capture failed\n");
-        if (g) hipGraphDestroy(g);
-        return -1;
-    }
-    e = hipGraphInstantiate(out, g, nullptr, nullptr, 0);
-    hipGraphDestroy(g);
-    CK(e);
-    return 0;
-}
-
-// One graph for step 0 (no talker) and one for every later frame, its talker
-// attention grid sized from the KV capacity (splits past the live length exit
-// at once).  Graphs per power-of-two bucket of the live key count measured no
-// faster, also in EOS mode (4096-frame capacity, 65 splits): 31.0 / 31.3 vs
-// 31.1 / 30.5 audio-s/s (profiles/r03c_eos_ab.txt).
-static int ensure_graphs(qtts_dev *dv) {
-    // (the forced sampler's frame is another graph, and so is each per-slot family's)
-    // (a fed run's frames, with the gate node, are graphs of their own: + 8)
-    const int want = (dv->f_armed ? 2 : dv->sp_armed ? (dv->sp_general ? 4 : 3) : 1) + (dv->fed ? 8 : 0);
-    if (dv->g0 && dv->gN && dv->graph_key == want) return 0;
-    // (mid-run: a refill admitted the run's first row that needs the full path)
-    if (dv->f_phase == 2 && (dv->g0 || dv->gN)) CK(hipStreamSynchronize(dv->st));
-    if (dv->g0) { hipGraphExecDestroy(dv->g0); dv->g0 = nullptr; }
-    if (dv->gN) { hipGraphExecDestroy(dv->gN); dv->gN = nullptr; }
-    drop_row_graphs(dv);
-    if (getenv("QTTS_HIP_NO_GRAPH")) { dv->graph_key = 0; return 0; }
-    // (the two main graphs always cover every slot)
-    const int nrun = dv->nrun;
-    dv->nrun = dv->nb;
-    int rc = capture(dv, false, &dv->g0);
-    if (!rc) rc = capture(dv, true, &dv->gN);
-    dv->nrun = nrun;
-    CKI(rc);
-    dv->graph_key = want;
     return 0;
 }
 
@@ -1660,63 +903,6 @@ extern "C" int qtts_dev_prompt(qtts_dev_t *dv, int b, const int *text_ids, int n
     dv->p_len_h[b] = p_len;
     dv->n_tr_h[b] = n_trailing;
     dv->pfx_ids[b] = pids;
-    return 0;
-}
-
-// talker prefill (T.c:254-472) of prompt rows [first[i], nrows[i]) of slots[i]
-// at their own positions (first NULL: from row 0); the rows before them are in
-// the cache already: mode-1 attention reads every key back from it.
-// last[i] = the row index (in px) of slot i's last row
-static int prefill_rows(qtts_dev *dv, const std::vector<int> &slots, const std::vector<int> &nrows,
-                        std::vector<int> &last, const std::vector<int> *first = nullptr) {
-    const qtts_dims_t &d = dv->d;
-    hipStream_t st = dv->st;
-    std::vector<int> rb, pp, src;
-    last.assign(slots.size(), 0);
-    for (size_t i = 0; i < slots.size(); ++i) {
-        const int b = slots[i];
-        for (int t = first ? (*first)[i] : 0; t < nrows[i]; ++t) {
-            rb.push_back(b);
-            pp.push_back(t);
-            src.push_back(b * dv->p_cap + t);
-        }
-        last[i] = (int)rb.size() - 1;
-    }
-    const int R = (int)rb.size();
-    if (R < 1 || R > dv->rows_cap) return -1;
-    g_prefill_rows += R;
-    CK(hipMemcpyAsync(dv->prow_b, rb.data(), R * 4, hipMemcpyHostToDevice, st));
-    CK(hipMemcpyAsync(dv->ppos, pp.data(), R * 4, hipMemcpyHostToDevice, st));
-    CK(hipMemcpyAsync(dv->psrc, src.data(), R * 4, hipMemcpyHostToDevice, st));
-    CKI(qtts_copy_rows(dv->px, d.H, dv->prefill, d.H, dv->psrc, R, d.H, st));
-    const int QKV = dv->QKV(), AD = d.NH * d.HD, KVD = d.KV * d.HD;
-    for (int l = 0; l < d.L; ++l) {
-        Layer &ly = dv->tl[l];
-        {
-            GemvArgs a = gv(ly.wqkv, QKV, d.H, dv->px, d.H, dv->pqkv, QKV, 1, EPI_STORE);
-            a.norm_w = ly.in; a.eps = d.eps; a.nt = 0;
-            CKI(rows_proj(dv, a, R, true));
-        }
-        AttnArgs t;
-        t.mode = 1; t.qkv = dv->pqkv; t.ld_qkv = QKV; t.qn_w = ly.qn; t.kn_w = ly.kn; t.eps = d.eps;
-        t.rope_cos = dv->rope_cos; t.rope_sin = dv->rope_sin;
-        t.kc = dv->kv_layer(dv->kc, l); t.vc = dv->kv_layer(dv->vc, l); t.kv_dtype = dv->kv_dtype;
-        t.S = dv->S; t.pos = dv->ppos; t.row_b = dv->prow_b; t.NH = d.NH; t.KV = d.KV; t.HD = d.HD;
-        t.out = dv->patt; t.ld_out = AD; t.nrows = R;
-        CKI(qtts_qk_prep(t, st));
-        CKI(qtts_attention(t, st));
-        {
-            GemvArgs a = gv(ly.wo, d.H, AD, dv->patt, AD, dv->px, d.H, 1, EPI_RESID);
-            a.nt = 0;
-            CKI(rows_proj(dv, a, R, true));
-            a = gv(ly.wgu, 2 * d.I, d.H, dv->px, d.H, dv->ph, d.I, 1, EPI_SWIGLU);
-            a.norm_w = ly.post; a.eps = d.eps; a.nt = 0;
-            CKI(rows_proj(dv, a, R, true));
-            a = gv(ly.wdown, d.H, d.I, dv->ph, d.I, dv->px, d.H, 1, EPI_RESID);
-            a.nt = 0;
-            CKI(rows_proj(dv, a, R, true));
-        }
-    }
     return 0;
 }
 
@@ -2355,8 +1541,10 @@ extern "C" int qtts_dev_talker_prefill_host(qtts_dev_t *dv, const float *embeds,
     CK(hipMemcpy(dv->prefill, embeds, (size_t)n * d.H * 4, hipMemcpyHostToDevice));
     CKI(qtts_dev_prefill(dv));
     if (hidden_out) {
-        GemvArgs a = gv(dv->head, d.V, d.H, dv->x_tk, d.H, dv->logits, d.V, 1, EPI_STORE);
-        a.norm_w = dv->tk_norm; a.eps = d.eps; a.xcopy = dv->tk_hid; a.ldxc = d.H; a.xcopy_normed = 1;
+        dv->nrun = 1;   // slot 0's row of the prefill's hidden in x_tk, nothing pending
+        dv->tk_res.reset(dv->x_tk, dv->x_tk2, d.H, 1);
+        const GemvArgs a = talker_head_args(dv);
+        dv->nrun = dv->nb;
         CKI(qtts_gemv(a, dv->st));
         CK(hipMemcpyAsync(hidden_out, dv->tk_hid, (size_t)d.H * 4, hipMemcpyDeviceToHost, dv->st));
         CK(hipStreamSynchronize(dv->st));
@@ -2407,32 +1595,4 @@ extern "C" int qtts_dev_subtalker_host(qtts_dev_t *dv, const float *hidden, int 
     CK(hipMemcpyAsync(out_codes, dv->codes, (size_t)d.G * 4, hipMemcpyDeviceToHost, dv->st));
     CK(hipStreamSynchronize(dv->st));
     return 0;
-}
-
-// One frame run eagerly with an event pair around every kernel launch on the
-// context stream; returns the number of kernels, fills kind/bytes/ms.
-extern "C" int qtts_dev_profile_frame(qtts_dev_t *dv, int step, int max, int *kind, double *bytes, float *ms,
-                                      char *names) {
-    if (!dv || dv->nb < 1) return -1;
-    hipSetDevice(dv->device);
-    CK(hipStreamSynchronize(dv->st));
-    dv->prof.clear();
-    dv->profiling = true;
-    int rc = record_frame(dv, step > 0);
-    dv->profiling = false;
-    CK(hipStreamSynchronize(dv->st));
-    int n = 0;
-    for (auto &p : dv->prof) {
-        float t = 0.f;
-        hipEventElapsedTime(&t, p.a, p.b);
-        if (n < max) {
-            kind[n] = p.kind; bytes[n] = p.bytes; ms[n] = t;
-            if (names) snprintf(names + (size_t)n * 64, 64, "%s", p.name ? p.name : "");
-        }
-        ++n;
-        hipEventDestroy(p.a);
-        hipEventDestroy(p.b);
-    }
-    dv->prof.clear();
-    return rc ? -1 : n;
 }

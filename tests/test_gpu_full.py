@@ -81,6 +81,16 @@ def test_full_bench_workload_properties(full_tts):
     assert a1.shape == (128 * 1920,) and np.isfinite(a1).all() and np.abs(a1).max() <= 1.0
 
 
+def test_full_frame_launches_equal_the_recorded_list(full_tts):
+    """the launch list of a batch-1 frame at full size (the pair pass, the fused
+    attention + O and the layer-0 table run here): tests/frame_launches.py"""
+    from frame_launches import FULL_CASE, first_difference, fixture, frame_launches
+    got = frame_launches(full_tts, 1)
+    print(f"{FULL_CASE}: {len(got['step0'])} launches in step 0, {len(got['step1'])} in step 1")
+    diff = first_difference(got, fixture()[FULL_CASE])
+    assert diff is None, diff
+
+
 def test_full_batch_identical_slots(full_tts):
     ids = prompt_ids("p128", 1300)
     full_tts.set_params(max_tokens=32, fixed=32, seed=5, **DEFAULT)
