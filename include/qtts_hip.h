@@ -532,6 +532,29 @@ int qtts_hip_sample_top_k(int *out_dev, const float *logits_dev, int vocab, int 
 int qtts_hip_sample_top_k_rows(int *out_dev, const float *logits_dev, int vocab, const int *top_k,
                                const float *top_p, const float *temperature, uint32_t *rng_bits_dev, int batch,
                                void *stream);
+/* The sampler with the nucleus short list (k_sample_n.hip): a row with
+ * top_p < 1 and top_k <= 64 or top-k off draws from at most 64 ids and one
+ * sequential sum over the vocabulary, and runs the full path in the same
+ * launch when the short list cannot decide; every other row draws as above.
+ * Same ids and RNG states as qtts_hip_sample_top_k / _rows.  path_dev (may be
+ * NULL) takes, per row, the path it ran: 1 fast top-k, 2 nucleus short list,
+ * 3 full, 0 stopped.  QTTS_HIP_SAMPLE_NUCLEUS=0: no row tries the short list
+ * (path 3 where it would have).  -1 without touching a device for a NULL
+ * out / logits / rng (or host array), batch < 1, vocab outside 1..4096,
+ * top_p <= 0 or a non-finite top_p / temperature.
+ * qtts_hip_sample_nucleus: the parameters as launch arguments (the kernel a
+ * run with a ctx-wide top_p < 1 launches).
+ * qtts_hip_sample_nucleus_rows: one parameter set per row (HOST arrays), the
+ * per-slot kernel; eos >= 0 && redraw: talker mode with a fixed length not
+ * yet reached, so a row that draws `eos` is redrawn with that logit at -1e9
+ * (c/qwen_tts.c:1315-1321), no suppression, no penalty; the entry owns the
+ * scratch words of that mode.  Waits for the launch; not counted by
+ * qtts_hip_sample_slot_launches. */
+int qtts_hip_sample_nucleus(int *out_dev, const float *logits_dev, int vocab, int top_k, float top_p,
+                            float temperature, uint32_t *rng_bits_dev, int batch, void *stream, int *path_dev);
+int qtts_hip_sample_nucleus_rows(int *out_dev, int *path_dev, const float *logits_dev, int vocab, const int *top_k,
+                                 const float *top_p, const float *temperature, uint32_t *rng_bits_dev, int batch,
+                                 int eos, int redraw, void *stream);
 /* kernel_causal_conv1d (c/qwen_tts_kernels.c:659): [ci, L] -> [co, L] */
 int qtts_hip_causal_conv1d(float *out_dev, const float *in_dev, const float *w_dev, const float *b_dev, int ci,
                            int co, int k, int L, int dilation, int groups, void *stream);

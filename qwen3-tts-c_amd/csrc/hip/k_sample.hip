@@ -42,6 +42,10 @@ int qtts_sample(const SampArgs &a, hipStream_t st, const int *stop_rd) {
         fprintf(stderr, "qtts_sample: vocab %d unsupported (max %d)\n", a.n, qtts_samp::NMAX);
         return -1;
     }
+    // top_p < 1 with top_k <= 64 or top-k off: the nucleus short list (k_sample_n.hip;
+    // QTTS_HIP_SAMPLE_NUCLEUS=0, read per call: the full-path kernels below)
+    if (!qtts_samp::fast_path(a) && qtts_sample_nucleus_row(a.top_p, a.top_k, a.n) && qtts_sample_nucleus_on())
+        return qtts_sample_n(a, st, stop_rd, nullptr, true);
     // QTTS_HIP_SAMPLE_W=0: the 256-thread fast path (A/B; read per call so a
     // test's setting applies to its own launches)
     const char *sw = getenv("QTTS_HIP_SAMPLE_W");

@@ -96,6 +96,9 @@ int qtts_sample_slots(const SampArgs &a, const SampSlotRow *tab, bool all_fast, 
                                rng, (const int *)a.n_gen, (const int *)a.counts, a);
             qtts_last_kernel = "k_sample_pw<4>";
         }
+    } else if (qtts_sample_nucleus_on()) {
+        // fast, nucleus short list or full per row (k_sample_n.hip; QTTS_HIP_SAMPLE_NUCLEUS=0: the kernels below)
+        if (qtts_sample_slots_n(a, tab, st, stop_rd, nullptr, true) != 0) return -1;
     } else if (stop_rd) {
         const size_t sm = sizeof(qtts_samp::KSmem);
         if (a.n <= 8 * 256) {

@@ -335,6 +335,20 @@ int qtts_sample_slots(const SampArgs &a, const SampSlotRow *tab, bool all_fast, 
                       const int *stop_rd = nullptr);
 // its launches enqueued (or captured) since the library loaded (qtts_hip_sample_slot_launches)
 long long qtts_sample_slot_launches();
+// The nucleus short list (k_sample_n.hip; qtts_sample_dev.h sample_nucleus):
+// a draw with top_p < 1 and top_k <= 64 or top-k off (qtts_sample_nucleus_row)
+// from at most 64 ids, the full path behind it in the same launch.  qtts_sample
+// sends such SampArgs to qtts_sample_n and qtts_sample_slots' general branch
+// launches qtts_sample_slots_n unless QTTS_HIP_SAMPLE_NUCLEUS=0 (read per
+// call: qtts_sample_nucleus_on), which restores the kernels of before.
+// path (may be NULL): per row 1 fast top-k, 2 nucleus short list, 3 full, 0
+// stopped.  nucleus false: no row tries the short list.  Neither counts as a
+// per-slot launch by itself (qtts_sample_slots counts its own).
+bool qtts_sample_nucleus_on();
+bool qtts_sample_nucleus_row(float top_p, int top_k, int n);
+int qtts_sample_n(const SampArgs &a, hipStream_t st, const int *stop_rd, int *path, bool nucleus);
+int qtts_sample_slots_n(const SampArgs &a, const SampSlotRow *tab, hipStream_t st, const int *stop_rd, int *path,
+                        bool nucleus);
 // writes row b of the table, stream-ordered; rng / st_rng non-null: the slot's
 // RNG states start from the row's seed as well
 int qtts_slot_row_set(SampSlotRow *tab, int b, const SampSlotRow &r, uint32_t *rng, uint32_t *st_rng, hipStream_t st);

@@ -95,6 +95,67 @@ extern "C" int qtts_hip_sample_top_k_rows(int *out, const float *logits, int voc
     return rc;
 }
 
+// the nucleus short-list kernels (k_sample_n.hip) with the path each row took
+static bool nucleus_params_ok(const char *who, int b, float top_p, float temp) {
+    if (std::isfinite(top_p) && std::isfinite(temp) && top_p > 0.0f) return true;
+    fprintf(stderr, "%s: row %d: top_p %g, temperature %g\n", who, b, top_p, temp);
+    return false;
+}
+
+extern "C" int qtts_hip_sample_nucleus(int *out, const float *logits, int vocab, int top_k, float top_p, float temp,
+                                       uint32_t *rng_bits, int batch, void *stream, int *path) {
+    if (!out || !logits || !rng_bits || batch < 1 || batch > 65535 || vocab < 1 || vocab > 4096) return -1;
+    if (!nucleus_params_ok("qtts_hip_sample_nucleus", 0, top_p, temp)) return -1;
+    SampArgs s;
+    s.logits = logits; s.ld = vocab; s.n = vocab; s.nb = batch; s.top_k = top_k; s.top_p = top_p; s.temp = temp;
+    s.mode = 0; s.st_rng = rng_bits; s.out_tok = out;
+    hipStream_t st = (hipStream_t)stream;
+    int rc = qtts_sample_n(s, st, nullptr, path, qtts_sample_nucleus_on());
+    if (hipStreamSynchronize(st) != hipSuccess) rc = -1;
+    return rc;
+}
+
+extern "C" int qtts_hip_sample_nucleus_rows(int *out, int *path, const float *logits, int vocab, const int *top_k,
+                                            const float *top_p, const float *temp, uint32_t *rng_bits, int batch,
+                                            int eos, int redraw, void *stream) {
+    if (!out || !logits || !top_k || !top_p || !temp || !rng_bits || batch < 1 || batch > 65535 || vocab < 1 ||
+        vocab > 4096)
+        return -1;
+    std::vector<SampSlotRow> h((size_t)batch);
+    for (int b = 0; b < batch; ++b) {
+        if (!nucleus_params_ok("qtts_hip_sample_nucleus_rows", b, top_p[b], temp[b])) return -1;
+        SampSlotRow &r = h[b];
+        r.temp = r.st_temp = temp[b]; r.top_p = r.st_top_p = top_p[b]; r.top_k = r.st_top_k = top_k[b];
+        r.rep = 1.0f; r.seed_bits = 0;
+    }
+    const bool talker = eos >= 0 && redraw;
+    if (talker && eos >= vocab) return -1;
+    hipStream_t st = (hipStream_t)stream;
+    // the table, then (talker mode) n_gen | stopped | cur_row | codes | st_rng, `batch` words each
+    const size_t tab_b = h.size() * sizeof(SampSlotRow), scr_b = talker ? (size_t)batch * 5 * 4 : 0;
+    char *mem = nullptr;
+    CK(hipMalloc((void **)&mem, tab_b + scr_b));
+    SampSlotRow *t = (SampSlotRow *)mem;
+    int rc = hipMemcpyAsync(t, h.data(), tab_b, hipMemcpyHostToDevice, st) == hipSuccess ? 0 : -1;
+    if (!rc && talker) rc = hipMemsetAsync(mem + tab_b, 0, scr_b, st) == hipSuccess ? 0 : -1;
+    if (!rc) {
+        SampArgs s;
+        s.logits = logits; s.ld = vocab; s.n = vocab; s.nb = batch; s.out_tok = out;
+        if (talker) {
+            int *w = (int *)(mem + tab_b);
+            s.mode = 1; s.rng = rng_bits; s.suppress_lo = vocab; s.eos = eos; s.rep = 1.0f; s.fixed = 1;
+            s.n_gen = w; s.stopped = w + batch; s.cur_row = w + 2 * batch; s.codes = w + 3 * batch;
+            s.codes_bstride = 1; s.G = 1; s.st_rng = (uint32_t *)(w + 4 * batch);
+        } else {
+            s.mode = 0; s.st_rng = rng_bits;
+        }
+        rc = qtts_sample_slots_n(s, t, st, nullptr, path, qtts_sample_nucleus_on());
+    }
+    if (hipStreamSynchronize(st) != hipSuccess) rc = -1;   // (h and the scratch live until the launch finished)
+    hipFree(mem);
+    return rc;
+}
+
 // every rows-long device index vector inside [0, lim) (the kernels index by
 // them unchecked)
 static int attn_ints_ok(const char *who, const char *what, const int *dev, int rows, int lim, hipStream_t st) {

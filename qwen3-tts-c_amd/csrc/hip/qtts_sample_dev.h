@@ -1321,4 +1321,381 @@ __device__ __forceinline__ void sample_row_p(const SampArgs &a, const SampSlotRo
     }
 }
 
+// ---------------------------------------------------------------------------
+// Nucleus draw on a short list: the full path's result (K.c:486-557, id and
+// RNG state) for top_p < 1 with (A) 0 < top_k <= KC or (B) top-k off, from at
+// most KC ids and ONE sequential sum over the vocabulary.
+//   v_i = lg_i / T, mx = max v (a maximum is exact in any order), e_i =
+//   expf(v_i - mx); S = e_0 + ... + e_{n-1} in index order -- the one chain
+//   that stays n terms long: every wave walks the e_i from LDS broadcasts
+//   (64 values in registers, the next 64 in flight) and adds them on its own
+//   SIMD, so no wave waits for another's sum -- inv = 1 / S, p_i = e_i * inv.
+//   Survivors: (A) every id with p_i >= the k-th largest p (with multiplicity:
+//   ties at the threshold all survive), (B) the KC largest p in (value desc,
+//   index asc) order, a prefix of the reference's sorted list; both come from
+//   the radix select's threshold over the keys of the non-zero p.
+//   One wave ranks the survivors by (value desc, index asc) -- the order the
+//   reference's stable sort leaves, zeros behind them -- walks the running sum
+//   to the first j with c_j >= top_p (cut = j + 1; (A) not reached: nothing is
+//   cut, the reference walks on over zeros), then sums the kept p in INDEX
+//   order (the reference's renormalising sum adds zeros between them, which
+//   change nothing), scales, draws r and takes the first kept id in index
+//   order whose running sum reaches r; r == 0 hits at id 0 whatever is kept
+//   (the reference's 0 >= 0), a sum that never reaches r returns 0.
+// Returns -1 in EVERY thread, the RNG untouched, when the short list cannot
+// decide -- more than KC survivors, a threshold of 0 (fewer than k non-zero
+// p), S not finite and positive (NaN / inf logits), a (B) cut past KC -- and
+// the caller runs sample_full on the same logits.  Otherwise the id in every
+// thread.  256 threads; thread t holds ids [t E, t E + E) in x[] (-inf past n).
+struct NucSmem {
+    alignas(16) float e[NMAX];   // e_i in index order, zeros up to the next multiple of 64
+    FastSmem fs;                 // the select's histograms; cand / rk / pv / pi / sel_v / sel_i of the ranking wave
+    float red[4];
+    int ncand, res;
+};
+static_assert(offsetof(NucSmem, fs) % 16 == 0 && offsetof(FastSmem, pv) % 16 == 0 && offsetof(FastSmem, sel_v) % 16 == 0,
+              "float4 LDS reads");
+
+__host__ __device__ inline bool nucleus_row(float top_p, int top_k, int n) {
+    return top_p < 1.0f && n <= NMAX && (top_k <= 0 || top_k >= n || top_k <= KC);
+}
+
+template <int EM>
+__device__ __forceinline__ int sample_nucleus(NucSmem &ns, const float (&x)[EM], int E, int n, int k, float top_p,
+                                              float temp, uint32_t &rng, uint64_t etab) {
+#pragma clang fp contract(off)
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int i0 = tid * E;
+    FastSmem &fs = ns.fs;
+    float e[EM];
+    float m = -INFINITY;
+#pragma unroll
+    for (int j = 0; j < EM; ++j) {
+        e[j] = div_rn(x[j], temp);
+        if (j < E && i0 + j < n) m = fmaxf(m, e[j]);
+    }
+    m = wave_max(m);
+    if (lane == 0) ns.red[w] = m;
+    if (tid == 0) ns.ncand = 0;
+    __syncthreads();
+    const float M = fmaxf(fmaxf(ns.red[0], ns.red[1]), fmaxf(ns.red[2], ns.red[3]));
+    const int n64 = (n + 63) & ~63;
+#pragma unroll
+    for (int j = 0; j < EM; ++j) {
+        e[j] = expf_glibc_wave_all(e[j] - M, etab);   // (every lane, every j: the table's cross-lane reads)
+        if (j < E && i0 + j < n) ns.e[i0 + j] = e[j];
+    }
+    for (int i = n + tid; i < n64; i += 256) ns.e[i] = 0.0f;   // (adding +0 leaves a sum >= 0 as it is)
+    __syncthreads();
+    float S = 0.0f;
+    {
+        const float4 *e4 = reinterpret_cast<const float4 *>(ns.e);
+        const int nb = n64 >> 6;
+        float4 q[16];
+#pragma unroll
+        for (int u = 0; u < 16; ++u) q[u] = e4[u];
+        for (int b = 0; b < nb; ++b) {
+            const int bn = b + 1 < nb ? b + 1 : b;
+            float4 nx[16];
+#pragma unroll
+            for (int u = 0; u < 16; ++u) nx[u] = e4[16 * bn + u];
+#pragma unroll
+            for (int u = 0; u < 16; ++u) { S += q[u].x; S += q[u].y; S += q[u].z; S += q[u].w; }
+#pragma unroll
+            for (int u = 0; u < 16; ++u) q[u] = nx[u];
+        }
+    }
+    if (!(S > 0.0f && S < INFINITY)) { __syncthreads(); return -1; }
+    const float inv = div_rn(1.0f, S);
+    uint32_t kk[EM];
+#pragma unroll
+    for (int j = 0; j < EM; ++j) {
+        const float p = e[j] * inv;
+        kk[j] = (j < E && i0 + j < n && p > 0.0f) ? okey(p) : 0u;
+    }
+    const bool topk = k > 0 && k < n;
+    uint32_t T, Tm;
+    int take_eq, ne;
+    radix_select_regs<EM>(fs, kk, E, topk ? k : KC, T, Tm, take_eq, ne);
+    if (topk && ne < k) { __syncthreads(); return -1; }   // the k-th largest p is 0
+    // survivors to slots: one returning LDS atomic per wave (the ranking below orders them)
+    // (A) every key >= the threshold; (B) of the keys equal to it only the
+    // first take_eq in index order, so that a tie across the KC-th rank is cut
+    // where the reference's stable order cuts it
+    int eqc = 0, eq_take = 0x7FFFFFFF;
+    if (!topk) {
+        int neq = 0, unused;
+#pragma unroll
+        for (int j = 0; j < EM; ++j) neq += (kk[j] != 0u && (kk[j] & Tm) == T) ? 1 : 0;
+        block_scan2(fs, 0, neq, unused, eqc);
+        eq_take = take_eq;
+    }
+    uint32_t sv = 0;
+#pragma unroll
+    for (int j = 0; j < EM; ++j) {
+        if (kk[j] != 0u) {
+            const uint32_t km = kk[j] & Tm;
+            bool s = km > T;
+            if (km == T) { s = eqc < eq_take; ++eqc; }
+            sv |= s ? 1u << j : 0u;
+        }
+    }
+    const int mine = __builtin_popcount(sv);
+    const int wi = wave_incl_scan(mine);
+    const int wtot = __builtin_amdgcn_readlane(wi, 63);
+    int base = 0;
+    if (wtot > 0) {
+        if (lane == 0) base = atomicAdd(&ns.ncand, wtot);
+        base = __builtin_amdgcn_readlane(base, 0);
+    }
+    int pos = base + wi - mine;
+#pragma unroll
+    for (int j = 0; j < EM; ++j)
+        if (sv & (1u << j)) {
+            if (pos < KC) fs.cand[0][pos] = ((unsigned long long)kk[j] << 32) | (0xFFFFFFFFu - (uint32_t)(i0 + j));
+            ++pos;
+        }
+    __syncthreads();
+    const int nc = ns.ncand;
+    if (nc > KC) { __syncthreads(); return -1; }
+    if (w == 0) {
+        const unsigned long long key = lane < nc ? fs.cand[0][lane] : 0ull;   // 0: below every real key
+        fs.rk[lane] = key;
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // one wave: LDS is in order once the writes landed
+        // rank by (value desc, index asc), and the position in index order
+        // (the low word is ~index: a smaller index is a larger low word)
+        int rank = 0, irank = 0;
+        for (int t0 = 0; t0 < nc; t0 += 8) {
+            unsigned long long kt[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) kt[u] = fs.rk[t0 + u];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                rank += kt[u] > key;
+                irank += (uint32_t)kt[u] > (uint32_t)key;
+            }
+        }
+        const float p = key_val((uint32_t)(key >> 32));
+        fs.pv[lane < nc ? rank : lane] = lane < nc ? p : 0.0f;
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        // c_j in rank order; p_j >= 0, so the first j with c_j >= top_p is the number of j with c_j < top_p
+        float c = 0.0f;
+        int jf = 0;
+#pragma unroll
+        for (int i = 0; i < KC / 4; ++i) {
+            const float4 q = reinterpret_cast<const float4 *>(fs.pv)[i];
+            c += q.x; jf += (4 * i < nc && c < top_p) ? 1 : 0;
+            c += q.y; jf += (4 * i + 1 < nc && c < top_p) ? 1 : 0;
+            c += q.z; jf += (4 * i + 2 < nc && c < top_p) ? 1 : 0;
+            c += q.w; jf += (4 * i + 3 < nc && c < top_p) ? 1 : 0;
+        }
+        int out;
+        if (jf >= nc && !topk) {
+            out = -1;   // (B) the cut lies past the list
+        } else {
+            const int cut = jf < nc ? jf + 1 : nc;
+            const bool kept = lane < nc && rank < cut;
+            fs.sel_v[lane < nc ? irank : lane] = kept ? p : 0.0f;
+            if (lane < nc) fs.sel_i[irank] = (int)(0xFFFFFFFFu - (uint32_t)key);
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            float4 q[KC / 4];
+#pragma unroll
+            for (int i = 0; i < KC / 4; ++i) q[i] = reinterpret_cast<const float4 *>(fs.sel_v)[i];
+            float s2 = 0.0f;
+#pragma unroll
+            for (int i = 0; i < KC / 4; ++i) { s2 += q[i].x; s2 += q[i].y; s2 += q[i].z; s2 += q[i].w; }
+            if (s2 > 0.0f) {
+                const float iv = div_rn(1.0f, s2);
+#pragma unroll
+                for (int i = 0; i < KC / 4; ++i) { q[i].x *= iv; q[i].y *= iv; q[i].z *= iv; q[i].w *= iv; }
+            }
+            float r = 0.f;
+            if (lane == 0) r = rand_uniform(rng);
+            r = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(r), 0));
+            float c2 = 0.0f;
+            int jr = 0;
+#pragma unroll
+            for (int i = 0; i < KC / 4; ++i) {
+                c2 += q[i].x; jr += (4 * i < nc && c2 < r) ? 1 : 0;
+                c2 += q[i].y; jr += (4 * i + 1 < nc && c2 < r) ? 1 : 0;
+                c2 += q[i].z; jr += (4 * i + 2 < nc && c2 < r) ? 1 : 0;
+                c2 += q[i].w; jr += (4 * i + 3 < nc && c2 < r) ? 1 : 0;
+            }
+            // r == 0: the reference's c >= r holds at id 0; never reached: 0 as well
+            out = (r > 0.0f && jr < nc) ? fs.sel_i[jr] : 0;
+        }
+        if (lane == 0) ns.res = out;
+    }
+    __syncthreads();
+    const int out = ns.res;
+    __syncthreads();   // ns is reused: a second draw (the fixed-mode EOS redraw) or the full path behind a -1
+    return out;
+}
+
+union NKSmem {
+    SampSmem full;
+    FastSmem fast;
+    NucSmem nuc;
+};
+static_assert(sizeof(NKSmem) == sizeof(KSmem), "the nucleus list fits the general kernel's LDS");
+
+// One row's draw with the nucleus short list (k_sample_n.hip), 256 threads on
+// NKSmem: sample_row (SLOT false: the parameters of `a`; a non-fast row that
+// the short list does not take, or gives back, runs sample_any as
+// k_sample<false, EM> does) or sample_row_p (SLOT true: row b of `tab`; such a
+// row runs sample_list / sample_any as k_sample_p does), statement for
+// statement around the draw.  nucleus false: no row tries the short list
+// (QTTS_HIP_SAMPLE_NUCLEUS=0 at the kernel-level entries).  path (may be
+// NULL): path[b] = 1 fast top-k, 2 nucleus short list, 3 full, 0 stopped; a
+// redrawn row reports the larger of its two draws.
+template <bool SLOT, int EM>
+__device__ __forceinline__ void sample_row_n(const SampArgs &a, const SampSlotRow *tab, int b, unsigned char *smraw,
+                                             const int *stopped_p, int *path, bool nucleus) {
+#pragma clang fp contract(off)
+    NKSmem &U = *reinterpret_cast<NKSmem *>(smraw);
+    const int tid = threadIdx.x, n = a.n;
+    const float *logits = a.logits;
+    const uint32_t *rng_p = a.mode == 1 ? a.rng : a.st_rng;
+    const int *ngen_p = a.n_gen, *counts_p = a.counts;
+    int zr;
+    asm volatile("v_mov_b32 %0, 0" : "=v"(zr));
+    uint4 r0 = make_uint4(0, 0, 0, 0), r1 = r0;
+    if constexpr (SLOT) {
+        const uint4 *tp = reinterpret_cast<const uint4 *>(tab + b);
+        r0 = tp[zr];
+        r1 = tp[zr + 1];
+    }
+    constexpr int NT = 256;
+    const int E = (n + NT - 1) / NT;
+    const float *lg = logits + (size_t)b * a.ld;
+    const int i0 = tid * E;
+    float x[EM];
+    int cnt[EM];
+    const bool pen = a.mode == 1 && counts_p && (SLOT || a.rep != 1.0f);
+    const int *cbase = pen ? counts_p + (size_t)b * n : reinterpret_cast<const int *>(lg);
+#pragma unroll
+    for (int j = 0; j < EM; ++j) {
+        const int i = i0 + j < n ? i0 + j : n - 1;
+        x[j] = lg[i];
+        cnt[j] = cbase[i];
+    }
+    int z0;
+    asm volatile("v_mov_b32 %0, 0" : "=v"(z0));
+    const int *sp = stopped_p ? stopped_p + b : reinterpret_cast<const int *>(lg);
+    const int *np = a.mode == 1 ? ngen_p + b : reinterpret_cast<const int *>(lg);
+    const uint32_t *rp = rng_p + b;
+    int stopped = sp[z0];
+    int ng = np[z0];
+    uint32_t rng = rp[z0];
+    const uint64_t etab = kExp2fTab[tid & 31];
+    asm volatile("" :: "v"(stopped), "v"(ng), "v"(rng));
+    float temp_in = a.temp, top_p = a.top_p, rep = a.rep;
+    int top_k = a.top_k;
+    uint32_t seed_bits = a.seed_bits;
+    if constexpr (SLOT) {
+        asm volatile("" :: "v"(r0.x), "v"(r0.y), "v"(r0.z), "v"(r0.w), "v"(r1.x), "v"(r1.y), "v"(r1.z), "v"(r1.w));
+        const bool tk = a.mode == 1;
+        temp_in = __uint_as_float(__builtin_amdgcn_readfirstlane(tk ? r0.x : r1.x));
+        top_p = __uint_as_float(__builtin_amdgcn_readfirstlane(tk ? r0.y : r1.y));
+        top_k = (int)__builtin_amdgcn_readfirstlane(tk ? r0.w : r1.z);
+        rep = __uint_as_float(__builtin_amdgcn_readfirstlane(r0.z));
+        seed_bits = __builtin_amdgcn_readfirstlane(r1.w);
+    }
+    const bool pen_on = pen && rep != 1.0f;
+    if (!stopped_p) stopped = 0;
+    if (a.mode != 1) ng = 0;
+#pragma unroll
+    for (int j = 0; j < EM; ++j) {
+        const bool ok = j < E && i0 + j < n;
+        if (!ok) x[j] = -INFINITY;
+        if (!(ok && pen_on)) cnt[j] = 0;
+    }
+    if (stopped) {
+        if (path && tid == 0) path[b] = 0;
+        return;
+    }
+    if (a.mode == 1) {
+#pragma unroll
+        for (int j = 0; j < EM; ++j) {
+            const int i = i0 + j;
+            float v = x[j];
+            if (i >= a.suppress_lo && i != a.eos) v = -1e9f;
+            for (int c = 0; c < cnt[j]; ++c) v = v > 0 ? div_rn(v, rep) : v * rep;
+            x[j] = (j < E && i < n) ? v : -INFINITY;
+        }
+    }
+    float temp = temp_in;
+    if (temp <= 0.0f) temp = 1e-5f;
+    const bool fast = fast_path_row(top_p, top_k, n);
+    const bool redraw = a.mode == 1 && a.fixed > 0 && ng < a.fixed;   // Q.c:1315-1321: an EOS draw is redrawn
+    int tok = 0, pcode = 0;
+    if (fast) {
+        pcode = 1;
+        float v[EM];
+#pragma unroll
+        for (int j = 0; j < EM; ++j) v[j] = div_rn(x[j], temp);
+        tok = sample_fast_regs<EM, true>(U.fast, v, E, n, top_k, rng, etab);
+        if (redraw) {
+            if (tid == 0) U.fast.misc[3] = tok;
+            __syncthreads();
+            tok = U.fast.misc[3];
+            if (tok == a.eos) {
+#pragma unroll
+                for (int j = 0; j < EM; ++j)
+                    if (i0 + j == a.eos) v[j] = div_rn(-1e9f, temp);
+                tok = sample_fast_regs<EM, true>(U.fast, v, E, n, top_k, rng, etab);
+            }
+        }
+    } else {
+        const bool nuc = nucleus && nucleus_row(top_p, top_k, n);
+        const bool list = SLOT && top_p >= 1.0f && top_k > 0 && top_k < n;   // (k > KFAST: the reference's list path)
+        auto draw = [&]() {
+            int t = -1;
+            if (nuc) t = sample_nucleus<EM>(U.nuc, x, E, n, top_k, top_p, temp, rng, etab);
+            if (t >= 0) {
+                pcode = pcode > 2 ? pcode : 2;
+                return t;
+            }
+            pcode = 3;
+            SampSmem &sm = U.full;   // the logits are still in registers: to LDS on this branch only
+#pragma unroll
+            for (int j = 0; j < EM; ++j)
+                if (j < E && i0 + j < n) sm.lg[i0 + j] = x[j];
+            __syncthreads();
+            t = list ? sample_list(sm, n, top_k, temp, rng) : sample_any(sm, n, top_k, top_p, temp_in, rng);
+            __syncthreads();   // sm.misc is read: the next draw's list may overwrite it
+            return t;
+        };
+        tok = draw();
+        if (redraw && tok == a.eos) {
+#pragma unroll
+            for (int j = 0; j < EM; ++j)
+                if (i0 + j == a.eos) x[j] = -1e9f;
+            tok = draw();
+        }
+    }
+    if (tid == 0) {
+        if (path) path[b] = pcode;
+        if (a.mode == 1) {
+            a.rng[b] = rng;
+            if (a.fixed == 0 && tok == a.eos) {
+                a.stopped[b] = 1;
+                if (a.host_stopped) a.host_stopped[b] = 1;
+                if (a.stop_step) a.stop_step[b] = ng;
+            } else {
+                a.cur_row[b] = ng;
+                a.codes[(size_t)b * a.codes_bstride + (size_t)ng * a.G + 0] = tok;
+                if (a.counts) a.counts[(size_t)b * n + tok] += 1;
+                a.n_gen[b] = ng + 1;
+                a.st_rng[b] = seed_bits;
+            }
+            if (a.out_tok) a.out_tok[b] = (a.fixed == 0 && tok == a.eos) ? 0 : tok;   // (see sample_row)
+        } else {
+            a.st_rng[b] = rng;
+            if (a.codes) a.codes[(size_t)b * a.codes_bstride + (size_t)a.cur_row[b] * a.G + a.g] = tok;
+            if (a.out_tok) a.out_tok[b] = tok;
+        }
+    }
+}
+
 }  // namespace qtts_samp

@@ -114,6 +114,7 @@ EXPORTS = [
     "qtts_hip_batch_matvec_case", "qtts_hip_gemv_wide_launches", "qtts_hip_batch_matvec_plan",
     "qwen_tts_sampling_defaults", "qwen_tts_set_utterance_sampling", "qtts_dev_slot_params",
     "qtts_hip_sample_slot_launches", "qtts_hip_sample_top_k_rows",
+    "qtts_hip_sample_nucleus", "qtts_hip_sample_nucleus_rows",
     "qwen_tts_generate_batch_stream", "qwen_tts_codec_mstream_begin", "qwen_tts_codec_mstream_push",
     "qtts_dev_codec_mstream_begin", "qtts_dev_codec_mstream_push_slots", "qtts_dev_codec_mstream_push_host",
     "qtts_dev_codec_mstream_pos", "qtts_hip_xgemm_seg_case",
@@ -562,6 +563,12 @@ def lib():
         L.qtts_hip_sample_slot_launches.argtypes = []
         L.qtts_hip_sample_top_k_rows.restype = C.c_int
         L.qtts_hip_sample_top_k_rows.argtypes = [vp, vp, C.c_int, _ip, _fp, _fp, vp, C.c_int, vp]
+    if hasattr(L, "qtts_hip_sample_nucleus_rows"):
+        L.qtts_hip_sample_nucleus.restype = C.c_int
+        L.qtts_hip_sample_nucleus.argtypes = [vp, vp, C.c_int, C.c_int, C.c_float, C.c_float, vp, C.c_int, vp, vp]
+        L.qtts_hip_sample_nucleus_rows.restype = C.c_int
+        L.qtts_hip_sample_nucleus_rows.argtypes = [vp, vp, vp, C.c_int, _ip, _fp, _fp, vp, C.c_int, C.c_int, C.c_int,
+                                                   vp]
     if hasattr(L, "qwen_tts_set_utterance_instruct"):
         L.qwen_tts_set_utterance_instruct.restype = C.c_int
         L.qwen_tts_set_utterance_instruct.argtypes = [C.POINTER(Ctx), C.c_int, C.POINTER(C.c_char_p)]
@@ -1632,6 +1639,31 @@ class Kernels:
         _ok(lib().qtts_hip_sample_top_k_rows(_ptr(out_i32), _ptr(logits), vocab, k.ctypes.data_as(_ip),
                                              p.ctypes.data_as(_fp), t.ctypes.data_as(_fp), _ptr(rng_u32), batch,
                                              _stream()), "sample_top_k_rows")
+
+    @staticmethod
+    def sample_nucleus(out_i32, logits, vocab, top_k, top_p, temperature, rng_u32, batch=1, path_i32=None):
+        """sample_top_k on the kernel with the nucleus short list
+        (qtts_hip_sample_nucleus); path_i32 takes, per row, 1 fast top-k, 2
+        nucleus short list, 3 full."""
+        _ok(lib().qtts_hip_sample_nucleus(_ptr(out_i32), _ptr(logits), vocab, top_k, top_p, temperature,
+                                          _ptr(rng_u32), batch, _stream(),
+                                          _ptr(path_i32) if path_i32 is not None else None), "sample_nucleus")
+
+    @staticmethod
+    def sample_nucleus_rows(out_i32, path_i32, logits, vocab, top_k, top_p, temperature, rng_u32, batch=1, eos=-1,
+                            redraw=False):
+        """sample_top_k_rows on the per-slot kernel with the nucleus short
+        list (qtts_hip_sample_nucleus_rows); path_i32 (may be None) as in
+        sample_nucleus; eos >= 0 and redraw: talker mode before a fixed length
+        is reached, so a row that draws eos is redrawn without it."""
+        k = np.ascontiguousarray(top_k, np.int32)
+        p = np.ascontiguousarray(top_p, np.float32)
+        t = np.ascontiguousarray(temperature, np.float32)
+        assert k.shape == p.shape == t.shape == (batch,)
+        _ok(lib().qtts_hip_sample_nucleus_rows(_ptr(out_i32), _ptr(path_i32) if path_i32 is not None else None,
+                                               _ptr(logits), vocab, k.ctypes.data_as(_ip), p.ctypes.data_as(_fp),
+                                               t.ctypes.data_as(_fp), _ptr(rng_u32), batch, eos, 1 if redraw else 0,
+                                               _stream()), "sample_nucleus_rows")
 
     @staticmethod
     def sample_slot_launches():
