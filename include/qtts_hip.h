@@ -826,6 +826,78 @@ int qtts_hip_rows_gemm_case(const qtts_rows_gemm_desc_t *d, int force, qtts_rows
  * For measuring those functions against float64. */
 int qtts_hip_xgemm_func(float *out_dev, const float *x_dev, const float *alpha_dev, const float *inv_beta_dev,
                         int channels, int length, int fn, void *stream);
+/* One launch of the voice-clone encoders' contraction kernel (k_enc.hip:
+ * k_econv through launch_econv), as the encoders describe it:
+ *   y[b*yb + m*yc + n*yt] = epi( sum_k w[m][k] * x'(b, k, n) ),  k = c * kw + tap, m < M, n < lout[b]
+ *   x'(b, k, n) = act_in( x[b*xb + c*xc + t*xt] (+ x2, same strides) ),  t = n*stride + tap*dil - padl,
+ *                 t outside [0, lin[b]) remapped by pmode: 0 zero, 1 reflect, 2 replicate;
+ *   act_in 0 none, 1 ELU;  epi: +bias[m], +bias2[b*bias2_b + m], act_out (0 none, 1 ReLU,
+ *   2 tanh(ReLU), 3 exact GELU, 4 sigmoid), *vec[m], +res[b*rb + m*rc + n*rt]; NULL: absent.
+ * w is fp32 [M][ci*kw]; part (optional) is the caller's split-K workspace of
+ * part_elems floats, NULL: the entry allocates what the plan needs.  All
+ * pointers are device pointers. */
+typedef struct {
+    int M, ci, kw, stride, dil, padl, pmode, act_in;
+    const float *w;
+    const float *x, *x2; size_t xb; int xc, xt;
+    int lin[16], lout[16], nb, nmax;
+    float *y; size_t yb; int yc, yt;
+    const float *bias, *bias2; int bias2_b, act_out;
+    const float *vec;
+    const float *res; size_t rb; int rc, rt;
+    float *part; size_t part_elems;
+} qtts_econv_desc_t;
+/* rows 1: the time-major fast path k_econv<true>, 0: the generic kernel; kz:
+ * split-K factor (kz > 1: k_econv_reduce sums part_elems floats of partials) */
+typedef struct {
+    int rows, kz;
+    int grid_x, grid_y, grid_z;
+    size_t part_elems;
+} qtts_econv_plan_t;
+/* The launcher's plan for the descriptor.  Returns 0 planned, -1 for what the
+ * launcher refuses: nb outside 1..16, M / ci / kw / nmax < 1, lout[b] outside
+ * 0..nmax, reflect padding with padl >= lin[b] or lin[b] < 2.  Host only: no
+ * pointer is dereferenced (x's alignment is looked at) and no device is needed. */
+int qtts_hip_econv_plan(const qtts_econv_desc_t *d, qtts_econv_plan_t *plan_out);
+/* Runs the launch: splits w into the three bf16 planes as the model load does
+ * (k_ewsplit), launches through launch_econv, synchronises and frees what it
+ * allocated.  plan_out (may be NULL) receives what ran.  -1 on a refusal (as
+ * above, before any device call; also a part smaller than the plan needs or a
+ * NULL w / x / y) or a device error.  A parity entry, not a timing one. */
+int qtts_hip_econv_case(const qtts_econv_desc_t *d, qtts_econv_plan_t *plan_out, void *stream);
+/* One launch of one of the encoders' small kernels through the launch helper
+ * the encoders use.  in / out / n / s per op (device pointers; nb utterances,
+ * len = int[nb] valid columns, ldt = row length of a [b][C][ldt] buffer):
+ *   0 k_mel       in spec [b][2nf][ldt], len, fb [nm][nf], flo [nm], fhi [nm]; out mel [b][nm][ldt]; n nf, ldt, nb, nm (nf <= 1040)
+ *   1 k_row_mean  in x, len; out [b][C]; n ldt, C, nb; s xb
+ *   2 k_egemv     in W [R][Cc], x [b][ldx], bias or NULL; out y [b][ldy]; n R, Cc, ldx, act, ldy, nb
+ *   3 k_se_apply  in h, s [b][C], res, len; out; n C, ldt, nb; s hb, rb, ob
+ *   4 k_asp_stats in x, len; out [b][2C]; n ldt, C, nb; s xb
+ *   5 k_asp_pool  in x, logits, len; out [b][2C]; n ldt, C, nb; s xb, lb
+ *   6 k_ln_rows   in x [R][D], w, b; out y; n R, D; eps
+ *   7 k_rope_bt   in cos [T][hd], sin; out x [R][ld] in place; n R, ld, nh, hd, T
+ *   8 k_rows_bt   out row_b [R], pos [R] (int); n R, T
+ *   9 k_rvq_enc   in lat [b][hid][T12], psemT [hid][vq], pacT, cbkT [q][vq][CB]; out codes [b][ldc_t][16] (int);
+ *                 n T12, hid, rows, CB, vq, nvalid, nsem, ldc_t (hid, vq multiples of 16; nvalid <= 16) */
+enum {
+    QTTS_EO_MEL = 0, QTTS_EO_ROW_MEAN, QTTS_EO_EGEMV, QTTS_EO_SE_APPLY, QTTS_EO_ASP_STATS, QTTS_EO_ASP_POOL,
+    QTTS_EO_LN_ROWS, QTTS_EO_ROPE_BT, QTTS_EO_ROWS_BT, QTTS_EO_RVQ_ENC, QTTS_EO_COUNT
+};
+typedef struct {
+    int op;
+    const void *in[6];
+    void *out[2];
+    int n[8];
+    size_t s[3];
+    float eps;
+} qtts_enc_op_t;
+/* Returns 0 launched (not synchronised), -1 refused before any device call
+ * (unknown op, a NULL operand the op needs, a size below 1 or outside the
+ * limits above) or on a launch error. */
+int qtts_hip_enc_op(const qtts_enc_op_t *d, void *stream);
+/* The fp32 erff (fn 0) / expm1f (fn 1) k_econv's GELU epilogue and ELU
+ * prologue call, elementwise over n values, for measuring them against float64. */
+int qtts_hip_enc_func(float *out_dev, const float *x_dev, size_t n, int fn, void *stream);
 /* glibc-exact expf replica used by the sampler (for the libm cross-check test) */
 int qtts_hip_expf_glibc(float *out_dev, const float *in_dev, int n, void *stream);
 int qtts_hip_sync(void);

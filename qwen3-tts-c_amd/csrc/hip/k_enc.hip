@@ -517,11 +517,20 @@ __global__ __launch_bounds__(RVQ_NT) void k_rvq_enc(const float *lat, int T12, i
 }
 
 // ----------------------------------------------------------------- host helpers
-int launch_econv(EncModel *em, const EConv &gin, int nb, int nmax, hipStream_t st) {
-    EConv g = gin;
-    if (g.M <= 0 || nmax <= 0) return 0;
-    if (nb > ENC_MAXB || !g.w || g.Kp % 32 || g.K > g.Kp) {
-        fprintf(stderr, "qtts enc: bad conv launch (nb %d, K %d, Kp %d)\n", nb, g.K, g.Kp);
+// What launch_econv launches for a conv over nb utterances of at most nmax
+// output columns: the ROWS fast path or the generic kernel, the split-K
+// factor, the grid and the partial workspace (floats).  Host only: no pointer
+// is dereferenced (the input's alignment is looked at).  -1: refused.
+struct EConvPlan {
+    bool rows = false;
+    int kz = 1;
+    dim3 grid, rgrid;     // k_econv; k_econv_reduce (kz > 1)
+    size_t part = 0;
+};
+
+int plan_econv(const EConv &g, int nb, int nmax, EConvPlan *p) {
+    if (nb < 1 || nb > ENC_MAXB || g.M <= 0 || nmax <= 0 || g.Kp <= 0 || g.Kp % 32 || g.K > g.Kp || g.K <= 0) {
+        fprintf(stderr, "qtts enc: bad conv launch (nb %d, M %d, K %d, Kp %d)\n", nb, g.M, g.K, g.Kp);
         return -1;
     }
     for (int b = 0; b < nb; ++b) {
@@ -532,8 +541,8 @@ int launch_econv(EncModel *em, const EConv &gin, int nb, int nmax, hipStream_t s
             return -1;
         }
     }
-    const bool rows = g.kw == 1 && g.xc == 1 && g.stride == 1 && g.padl == 0 && !g.x2 && g.act_in == ACT_NONE &&
-                      g.K % 8 == 0 && g.xt % 4 == 0 && ((uintptr_t)g.x & 15) == 0;
+    p->rows = g.kw == 1 && g.xc == 1 && g.stride == 1 && g.padl == 0 && !g.x2 && g.act_in == ACT_NONE &&
+              g.K % 8 == 0 && g.xt % 4 == 0 && ((uintptr_t)g.x & 15) == 0;
     // split-K when one utterance's output tiles cannot fill the chip: each
     // K-step waits on its loads (a few steps of MFMA work cannot hide them),
     // so more, shorter workgroups are the latency cover.  The split depends
@@ -541,11 +550,24 @@ int launch_econv(EncModel *em, const EConv &gin, int nb, int nmax, hipStream_t s
     // an utterance gets the same sums alone or in a batch of equal padding.
     const int tiles1 = (nmax + 63) / 64 * ((g.M + 63) / 64), nk = g.Kp / 32;
     int kz = 1;
-    if (rows) kz = nk >= 8 ? std::min(4, nk / 4) : 1;
+    if (p->rows) kz = nk >= 8 ? std::min(4, nk / 4) : 1;
     else if (tiles1 < 256 && nk >= 8) kz = std::max(1, std::min(std::min(nk / 4, 16), (512 + tiles1 - 1) / tiles1));
+    p->kz = kz;
+    p->part = kz > 1 ? (size_t)kz * nb * g.M * nmax : 0;
+    p->grid = dim3((nmax + 63) / 64, (g.M + 63) / 64, nb * kz);
+    p->rgrid = dim3((nmax + 255) / 256, g.M, nb);
+    return 0;
+}
+
+int launch_econv(EncModel *em, const EConv &gin, int nb, int nmax, hipStream_t st) {
+    EConv g = gin;
+    if (g.M <= 0 || nmax <= 0) return 0;
+    EConvPlan pl;
+    if (!g.w || plan_econv(g, nb, nmax, &pl)) return -1;
+    const int kz = pl.kz;
     g.kz = kz; g.nb = nb; g.pn = nmax;
     if (kz > 1) {
-        const size_t need = (size_t)kz * nb * g.M * nmax;
+        const size_t need = pl.part;
         if (need > em->part_cap) {
             hipStreamSynchronize(st);
             if (em->part) hipFree(em->part);
@@ -559,11 +581,59 @@ int launch_econv(EncModel *em, const EConv &gin, int nb, int nmax, hipStream_t s
         }
         g.part = em->part;
     }
-    const dim3 grid((nmax + 63) / 64, (g.M + 63) / 64, nb * kz);
-    if (rows) hipLaunchKernelGGL((k_econv<true>), grid, dim3(256), 0, st, g);
-    else hipLaunchKernelGGL((k_econv<false>), grid, dim3(256), 0, st, g);
-    if (kz > 1) hipLaunchKernelGGL(k_econv_reduce, dim3((nmax + 255) / 256, g.M, nb), dim3(256), 0, st, g);
+    if (pl.rows) hipLaunchKernelGGL((k_econv<true>), pl.grid, dim3(256), 0, st, g);
+    else hipLaunchKernelGGL((k_econv<false>), pl.grid, dim3(256), 0, st, g);
+    if (kz > 1) hipLaunchKernelGGL(k_econv_reduce, pl.rgrid, dim3(256), 0, st, g);
     return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+// ---- the small kernels' launch rules, written once: the encoders below and
+// qtts_hip_enc_op both go through these
+void launch_mel(hipStream_t st, const float *spec, int nf, int ldt, int nb, const int *T, const float *fb,
+                const int *flo, const int *fhi, int nm, float *mel) {
+    hipLaunchKernelGGL(k_mel, dim3(ldt, nb), dim3(256), 0, st, spec, nf, ldt, T, fb, flo, fhi, nm, mel);
+}
+void launch_row_mean(hipStream_t st, const float *x, size_t xb, int ldt, const int *len, int C, int nb, float *out) {
+    hipLaunchKernelGGL(k_row_mean, dim3((C + 3) / 4, nb), dim3(256), 0, st, x, xb, ldt, len, C, out);
+}
+void launch_egemv(hipStream_t st, const float *Wm, int R, int Cc, const float *x, int ldx, const float *bias, int act,
+                  float *y, int ldy, int nb) {
+    hipLaunchKernelGGL(k_egemv, dim3((R + 3) / 4, nb), dim3(256), 0, st, Wm, R, Cc, x, ldx, bias, act, y, ldy);
+}
+void launch_se_apply(hipStream_t st, const float *h, size_t hb, const float *s, int C, const float *res, size_t rb,
+                     float *out, size_t ob, int ldt, const int *len, int nb) {
+    hipLaunchKernelGGL(k_se_apply, dim3((ldt + 255) / 256, C, nb), dim3(256), 0, st, h, hb, s, C, res, rb, out, ob, ldt,
+                       len);
+}
+void launch_asp_stats(hipStream_t st, const float *x, size_t xb, int ldt, const int *len, int C, int nb, float *stats) {
+    hipLaunchKernelGGL(k_asp_stats, dim3((C + 3) / 4, nb), dim3(256), 0, st, x, xb, ldt, len, C, stats);
+}
+void launch_asp_pool(hipStream_t st, const float *x, size_t xb, const float *lg, size_t lb, int ldt, const int *len,
+                     int C, int nb, float *pooled) {
+    hipLaunchKernelGGL(k_asp_pool, dim3((C + 3) / 4, nb), dim3(256), 0, st, x, xb, lg, lb, ldt, len, C, pooled);
+}
+void launch_ln_rows(hipStream_t st, const float *x, int R, int D, const float *w, const float *bb, float eps, float *y) {
+    hipLaunchKernelGGL(k_ln_rows, dim3(R), dim3(256), 0, st, x, D, w, bb, eps, y);
+}
+void launch_rope_bt(hipStream_t st, float *x, int R, int ld, int nh, int hd, int T, const float *cs, const float *sn) {
+    hipLaunchKernelGGL(k_rope_bt, dim3(R), dim3(256), 0, st, x, ld, nh, hd, T, cs, sn);
+}
+void launch_rows_bt(hipStream_t st, int *row_b, int *pos, int R, int T) {
+    hipLaunchKernelGGL(k_rows_bt, dim3((R + 255) / 256), dim3(256), 0, st, row_b, pos, R, T);
+}
+size_t rvq_enc_smem(int hid, int vq) {
+    return ((size_t)RVQ_ROWS * (hid + vq) + 2 * (RVQ_NT / 64) * RVQ_ROWS + RVQ_ROWS) * 4 + 64;
+}
+void launch_rvq_enc(hipStream_t st, const float *lat, int T12, int hid, int rows, const float *psemT, const float *pacT,
+                    const float *cbkT, int CB, int vq, int nvalid, int nsem, int *codes, int ldc_t) {
+    hipLaunchKernelGGL(k_rvq_enc, dim3((rows + RVQ_ROWS - 1) / RVQ_ROWS), dim3(RVQ_NT), rvq_enc_smem(hid, vq), st, lat,
+                       T12, hid, rows, psemT, pacT, cbkT, CB, vq, nvalid, nsem, codes, ldc_t);
+}
+
+// erff / expm1f as k_econv's GELU epilogue and ELU prologue call them
+__global__ void k_enc_func(const float *x, size_t n, int fn, float *y) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) y[i] = fn == 0 ? erff(x[i]) : expm1f(x[i]);
 }
 
 }  // namespace
@@ -589,22 +659,27 @@ static float *up_f32(EncModel *m, const std::vector<float> &v) {
     return p;
 }
 
-// host [M][K] fp32 -> device planes [3][M][Kp]
-static int make_planes(EncModel *m, const float *host, int M, int K, int kw, EncW *out) {
+// device [M][K] fp32 -> device planes [3][M][Kp]
+static int split_planes(EncModel *m, const float *dev, int M, int K, int kw, EncW *out) {
     const int Kp = (K + 31) / 32 * 32;
-    float *tmp = nullptr;
-    if (hipMalloc(&tmp, (size_t)M * K * 4) != hipSuccess) return -1;
     unsigned short *pl = (unsigned short *)ewalloc(m, (size_t)3 * M * Kp * 2);
-    int rc = -1;
-    if (pl && hipMemcpy(tmp, host, (size_t)M * K * 4, hipMemcpyHostToDevice) == hipSuccess) {
-        const size_t n = (size_t)M * Kp;
-        hipLaunchKernelGGL(k_ewsplit, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, tmp, M, K, Kp, pl);
-        rc = hipDeviceSynchronize() == hipSuccess ? 0 : -1;
-    }
-    hipFree(tmp);
-    if (rc) return -1;
+    if (!pl) return -1;
+    const size_t n = (size_t)M * Kp;
+    hipLaunchKernelGGL(k_ewsplit, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, dev, M, K, Kp, pl);
+    if (hipDeviceSynchronize() != hipSuccess) return -1;
     out->p = pl; out->M = M; out->K = K; out->Kp = Kp; out->kw = kw;
     return 0;
+}
+
+// host [M][K] fp32 -> device planes [3][M][Kp]
+static int make_planes(EncModel *m, const float *host, int M, int K, int kw, EncW *out) {
+    float *tmp = nullptr;
+    if (hipMalloc(&tmp, (size_t)M * K * 4) != hipSuccess) return -1;
+    int rc = -1;
+    if (hipMemcpy(tmp, host, (size_t)M * K * 4, hipMemcpyHostToDevice) == hipSuccess)
+        rc = split_planes(m, tmp, M, K, kw, out);
+    hipFree(tmp);
+    return rc;
 }
 
 int enc_set_dims(EncModel *m, const qtts_enc_dims_t *d) {
@@ -1017,9 +1092,8 @@ int enc_speaker(EncModel *m, int nb, const float *const *wav, const int *n, floa
         for (int b = 0; b < nb; ++b) { g.lin[b] = n[b]; g.lout[b] = T[b]; }
         ECK(launch_econv(m, g, nb, Tm, st));
     }
-    hipLaunchKernelGGL(k_mel, dim3(Tm, nb), dim3(256), 0, st, spec, nf, Tm, lens, m->melfb,
-                       reinterpret_cast<const int *>(F(m, "#melfb_lo")),
-                       reinterpret_cast<const int *>(F(m, "#melfb_lo")) + nm, nm, mel);
+    launch_mel(st, spec, nf, Tm, nb, lens, m->melfb, reinterpret_cast<const int *>(F(m, "#melfb_lo")),
+               reinterpret_cast<const int *>(F(m, "#melfb_lo")) + nm, nm, mel);
     const std::string P = "speaker_encoder.";
     auto tdnn = [&](const std::string &name, const float *x, int Cx, const float *x2, float *y, int Cy, int dil,
                     int act) {
@@ -1052,20 +1126,19 @@ int enc_speaker(EncModel *m, int nb, const float *const *wav, const int *n, floa
             ECK(tdnn(rp, h1 + (size_t)j * cs * Tm, C, x2, h2 + (size_t)j * cs * Tm, C, d.dil[i], ACT_RELU));
         }
         ECK(tdnn(bp + "tdnn2.conv", h2, C, nullptr, h3, C, 1, ACT_RELU));
-        hipLaunchKernelGGL(k_row_mean, dim3((C + 3) / 4, nb), dim3(256), 0, st, h3, (size_t)C * Tm, Tm, lens, C, mean);
-        hipLaunchKernelGGL(k_egemv, dim3((d.se_ch + 3) / 4, nb), dim3(256), 0, st, F(m, bp + "se_block.conv1.weight"),
-                           d.se_ch, C, mean, C, F(m, bp + "se_block.conv1.bias"), (int)ACT_RELU, s1, d.se_ch);
-        hipLaunchKernelGGL(k_egemv, dim3((C + 3) / 4, nb), dim3(256), 0, st, F(m, bp + "se_block.conv2.weight"), C,
-                           d.se_ch, s1, d.se_ch, F(m, bp + "se_block.conv2.bias"), (int)ACT_SIGMOID, s2, C);
-        hipLaunchKernelGGL(k_se_apply, dim3((Tm + 255) / 256, C, nb), dim3(256), 0, st, h3, (size_t)C * Tm, s2, C, in,
-                           (size_t)inC * Tm, cat + (size_t)(i - 1) * C * Tm, (size_t)CM * Tm, Tm, lens);
+        launch_row_mean(st, h3, (size_t)C * Tm, Tm, lens, C, nb, mean);
+        launch_egemv(st, F(m, bp + "se_block.conv1.weight"), d.se_ch, C, mean, C, F(m, bp + "se_block.conv1.bias"),
+                     (int)ACT_RELU, s1, d.se_ch, nb);
+        launch_egemv(st, F(m, bp + "se_block.conv2.weight"), C, d.se_ch, s1, d.se_ch, F(m, bp + "se_block.conv2.bias"),
+                     (int)ACT_SIGMOID, s2, C, nb);
+        launch_se_apply(st, h3, (size_t)C * Tm, s2, C, in, (size_t)inC * Tm, cat + (size_t)(i - 1) * C * Tm,
+                        (size_t)CM * Tm, Tm, lens, nb);
     }
     // 4. multi-layer feature aggregation
     ECK(tdnn(P + "mfa.conv", cat, CM, nullptr, mfa, CM, d.dil[d.n_ch - 1], ACT_RELU));
     // 5. attentive statistics pooling
-    hipLaunchKernelGGL(k_asp_stats, dim3((CM + 3) / 4, nb), dim3(256), 0, st, mfa, (size_t)CM * Tm, Tm, lens, CM, stats);
-    hipLaunchKernelGGL(k_egemv, dim3((A + 3) / 4, nb), dim3(256), 0, st, F(m, "#asp_ms"), A, 2 * CM, stats, 2 * CM,
-                       F(m, P + "asp.tdnn.conv.bias"), (int)ACT_NONE, b2, A);
+    launch_asp_stats(st, mfa, (size_t)CM * Tm, Tm, lens, CM, nb, stats);
+    launch_egemv(st, F(m, "#asp_ms"), A, 2 * CM, stats, 2 * CM, F(m, P + "asp.tdnn.conv.bias"), (int)ACT_NONE, b2, A, nb);
     {
         const EncW *w = W(m, "#asp_x");
         if (!w) return -1;
@@ -1076,11 +1149,10 @@ int enc_speaker(EncModel *m, int nb, const float *const *wav, const int *n, floa
         ECK(launch_econv(m, g, nb, Tm, st));
     }
     ECK(tdnn(P + "asp.conv", a1, A, nullptr, lg, CM, 1, ACT_NONE));
-    hipLaunchKernelGGL(k_asp_pool, dim3((CM + 3) / 4, nb), dim3(256), 0, st, mfa, (size_t)CM * Tm, lg, (size_t)CM * Tm,
-                       Tm, lens, CM, pooled);
+    launch_asp_pool(st, mfa, (size_t)CM * Tm, lg, (size_t)CM * Tm, Tm, lens, CM, nb, pooled);
     // 6. final 1x1 conv on the pooled statistics
-    hipLaunchKernelGGL(k_egemv, dim3((d.enc_dim + 3) / 4, nb), dim3(256), 0, st, F(m, P + "fc.weight"), d.enc_dim,
-                       2 * CM, pooled, 2 * CM, F(m, P + "fc.bias"), (int)ACT_NONE, xv, d.enc_dim);
+    launch_egemv(st, F(m, P + "fc.weight"), d.enc_dim, 2 * CM, pooled, 2 * CM, F(m, P + "fc.bias"), (int)ACT_NONE, xv,
+                 d.enc_dim, nb);
     ECK(hipGetLastError() != hipSuccess);
     ECK(hipMemcpyAsync(out, xv, (size_t)nb * d.enc_dim * 4, hipMemcpyDeviceToHost, st) != hipSuccess);
     if (mel_out) {
@@ -1203,7 +1275,7 @@ int enc_codes(EncModel *m, int nb, const float *const *wav, const int *n, int *c
         ECK(launch_econv(m, g, nb, T25, st));
     }
     // transformer over R = nb * T25 rows (MimiTransformerModel, no final norm)
-    hipLaunchKernelGGL(k_rows_bt, dim3((R + 255) / 256), dim3(256), 0, st, row_b, pos, R, T25);
+    launch_rows_bt(st, row_b, pos, R, T25);
     auto lin = [&](const std::string &name, const float *xin, int K, float *y, int N, int act, const float *vec,
                    bool resid) {
         const EncW *w = W(m, name);
@@ -1218,22 +1290,20 @@ int enc_codes(EncModel *m, int nb, const float *const *wav, const int *n, int *c
     };
     for (int l = 0; l < d.layers; ++l) {
         const std::string p = "encoder.encoder_transformer.layers." + std::to_string(l) + ".";
-        hipLaunchKernelGGL(k_ln_rows, dim3(R), dim3(256), 0, st, x, H, F(m, p + "input_layernorm.weight"),
-                           F(m, p + "input_layernorm.bias"), d.norm_eps, h);
+        launch_ln_rows(st, x, R, H, F(m, p + "input_layernorm.weight"), F(m, p + "input_layernorm.bias"), d.norm_eps, h);
         ECK(lin(p + "self_attn.q_proj.weight", h, H, q, qd, ACT_NONE, nullptr, false));
         ECK(lin(p + "self_attn.k_proj.weight", h, H, k, kd, ACT_NONE, nullptr, false));
         ECK(lin(p + "self_attn.v_proj.weight", h, H, v, kd, ACT_NONE, nullptr, false));
-        hipLaunchKernelGGL(k_rope_bt, dim3(R), dim3(256), 0, st, q, qd, d.heads, d.head_dim, T25, m->rope_cos, m->rope_sin);
-        hipLaunchKernelGGL(k_rope_bt, dim3(R), dim3(256), 0, st, k, kd, d.kv_heads, d.head_dim, T25, m->rope_cos,
-                           m->rope_sin);
+        launch_rope_bt(st, q, R, qd, d.heads, d.head_dim, T25, m->rope_cos, m->rope_sin);
+        launch_rope_bt(st, k, R, kd, d.kv_heads, d.head_dim, T25, m->rope_cos, m->rope_sin);
         AttnArgs a;
         a.mode = 1; a.qkv = q; a.ld_qkv = qd; a.kc = k; a.vc = v; a.S = T25; a.pos = pos; a.row_b = row_b;
         a.NH = d.heads; a.KV = d.kv_heads; a.HD = d.head_dim; a.out = att; a.ld_out = qd; a.nrows = R;
         a.win = d.window;
         ECK(qtts_attention(a, st));
         ECK(lin(p + "self_attn.o_proj.weight", att, qd, x, H, ACT_NONE, F(m, p + "self_attn_layer_scale.scale"), true));
-        hipLaunchKernelGGL(k_ln_rows, dim3(R), dim3(256), 0, st, x, H, F(m, p + "post_attention_layernorm.weight"),
-                           F(m, p + "post_attention_layernorm.bias"), d.norm_eps, h);
+        launch_ln_rows(st, x, R, H, F(m, p + "post_attention_layernorm.weight"),
+                       F(m, p + "post_attention_layernorm.bias"), d.norm_eps, h);
         ECK(lin(p + "mlp.fc1.weight", h, H, mlp, d.inter, ACT_GELU, nullptr, false));
         ECK(lin(p + "mlp.fc2.weight", mlp, d.inter, x, H, ACT_NONE, F(m, p + "mlp_layer_scale.scale"), true));
     }
@@ -1250,12 +1320,10 @@ int enc_codes(EncModel *m, int nb, const float *const *wav, const int *n, int *c
     }
     // split RVQ encode of the first n_valid codebooks
     {
-        const int rows = nb * T12;
-        const size_t smem = ((size_t)RVQ_ROWS * (H + d.vq_dim) + 2 * (RVQ_NT / 64) * RVQ_ROWS + RVQ_ROWS) * 4 + 64;
-        hipLaunchKernelGGL(k_rvq_enc, dim3((rows + RVQ_ROWS - 1) / RVQ_ROWS), dim3(RVQ_NT), smem, st, lat, T12, H, rows,
-                           F(m, "encoder.quantizer.semantic_residual_vector_quantizer.input_proj.weight"),
-                           F(m, "encoder.quantizer.acoustic_residual_vector_quantizer.input_proj.weight"), m->cbk,
-                           d.cb_size, d.vq_dim, d.n_valid, d.n_sem, dcodes, T12);
+        launch_rvq_enc(st, lat, T12, H, nb * T12,
+                       F(m, "encoder.quantizer.semantic_residual_vector_quantizer.input_proj.weight"),
+                       F(m, "encoder.quantizer.acoustic_residual_vector_quantizer.input_proj.weight"), m->cbk, d.cb_size,
+                       d.vq_dim, d.n_valid, d.n_sem, dcodes, T12);
     }
     ECK(hipGetLastError() != hipSuccess);
     std::vector<int> hc((size_t)nb * T12 * 16);
@@ -1277,4 +1345,125 @@ int enc_codes(EncModel *m, int nb, const float *const *wav, const int *n, int *c
                         t < frames[b] ? hl[((size_t)b * H + c) * T12 + t] : 0.f;
     }
     return 0;
+}
+
+// ===================================================================== kernel-level parity entries
+namespace {
+// the descriptor as launch_econv takes it (weights and workspace aside)
+int econv_of_desc(const qtts_econv_desc_t *d, EConv *g) {
+    if (!d || d->M < 1 || d->ci < 1 || d->kw < 1 || d->nmax < 1 || d->nb < 1 || d->nb > ENC_MAXB ||
+        (long long)d->ci * d->kw > (1 << 24))
+        return -1;
+    g->M = d->M; g->K = d->ci * d->kw; g->Kp = (g->K + 31) / 32 * 32; g->kw = d->kw;
+    g->wplane = (size_t)g->M * g->Kp;
+    g->stride = d->stride; g->dil = d->dil; g->padl = d->padl; g->pmode = d->pmode; g->act_in = d->act_in;
+    g->x = d->x; g->x2 = d->x2; g->xb = d->xb; g->xc = d->xc; g->xt = d->xt;
+    for (int b = 0; b < ENC_MAXB; ++b) { g->lin[b] = b < d->nb ? d->lin[b] : 0; g->lout[b] = b < d->nb ? d->lout[b] : 0; }
+    g->y = d->y; g->yb = d->yb; g->yc = d->yc; g->yt = d->yt;
+    g->bias = d->bias; g->bias2 = d->bias2; g->bias2_b = d->bias2_b; g->act_out = d->act_out; g->vec = d->vec;
+    g->res = d->res; g->rb = d->rb; g->rc = d->rc; g->rt = d->rt;
+    return 0;
+}
+
+void plan_out_of(const EConvPlan &p, qtts_econv_plan_t *o) {
+    if (!o) return;
+    o->rows = p.rows ? 1 : 0; o->kz = p.kz;
+    o->grid_x = (int)p.grid.x; o->grid_y = (int)p.grid.y; o->grid_z = (int)p.grid.z;
+    o->part_elems = p.part;
+}
+}  // namespace
+
+extern "C" int qtts_hip_econv_plan(const qtts_econv_desc_t *d, qtts_econv_plan_t *plan_out) {
+    EConv g;
+    EConvPlan p;
+    if (econv_of_desc(d, &g) || plan_econv(g, d->nb, d->nmax, &p)) return -1;
+    plan_out_of(p, plan_out);
+    return 0;
+}
+
+extern "C" int qtts_hip_econv_case(const qtts_econv_desc_t *d, qtts_econv_plan_t *plan_out, void *stream) {
+    EConv g;
+    EConvPlan p;
+    if (econv_of_desc(d, &g) || plan_econv(g, d->nb, d->nmax, &p)) return -1;
+    if (!d->w || !d->x || !d->y || d->stride < 1 || d->dil < 1 || d->padl < 0 || d->pmode < PAD_ZERO ||
+        d->pmode > PAD_REPLICATE || (d->part && d->part_elems < p.part))
+        return -1;
+    hipStream_t st = (hipStream_t)stream;
+    EncModel em;
+    EncW w;
+    int rc = -1;
+    if (hipStreamSynchronize(st) == hipSuccess && split_planes(&em, d->w, g.M, g.K, g.kw, &w) == 0) {
+        g.w = w.p;
+        em.part = d->part;                    // the caller's workspace is large enough: never regrown
+        em.part_cap = d->part ? d->part_elems : 0;
+        rc = launch_econv(&em, g, d->nb, d->nmax, st);
+        if (hipStreamSynchronize(st) != hipSuccess) rc = -1;
+    }
+    if (d->part) em.part = nullptr;           // not ours to free
+    enc_destroy(&em);
+    if (rc == 0) plan_out_of(p, plan_out);
+    return rc;
+}
+
+extern "C" int qtts_hip_enc_op(const qtts_enc_op_t *d, void *stream) {
+    if (!d || d->op < 0 || d->op >= QTTS_EO_COUNT) return -1;
+    static const int n_in[QTTS_EO_COUNT] = {5, 2, 2, 4, 2, 3, 3, 2, 0, 4};
+    static const int n_out[QTTS_EO_COUNT] = {1, 1, 1, 1, 1, 1, 1, 1, 2, 1};
+    static const int n_n[QTTS_EO_COUNT] = {4, 3, 6, 3, 3, 3, 2, 5, 2, 8};
+    for (int i = 0; i < n_in[d->op]; ++i) if (!d->in[i]) return -1;
+    for (int i = 0; i < n_out[d->op]; ++i) if (!d->out[i]) return -1;
+    for (int i = 0; i < n_n[d->op]; ++i)
+        if (d->n[i] < 1 && !(d->op == QTTS_EO_EGEMV && i == 3)) return -1;
+    const int *n = d->n;
+    hipStream_t st = (hipStream_t)stream;
+    auto F32 = [&](int i) { return static_cast<const float *>(d->in[i]); };
+    auto I32 = [&](int i) { return static_cast<const int *>(d->in[i]); };
+    float *o = static_cast<float *>(d->out[0]);
+    switch (d->op) {
+        case QTTS_EO_MEL:
+            if (n[0] > 1040) return -1;       // k_mel keeps mag[1040]
+            launch_mel(st, F32(0), n[0], n[1], n[2], I32(1), F32(2), I32(3), I32(4), n[3], o);
+            break;
+        case QTTS_EO_ROW_MEAN:
+            launch_row_mean(st, F32(0), d->s[0], n[0], I32(1), n[1], n[2], o);
+            break;
+        case QTTS_EO_EGEMV:
+            if (n[3] < ACT_NONE || n[3] > ACT_SIGMOID) return -1;
+            launch_egemv(st, F32(0), n[0], n[1], F32(1), n[2], F32(2), n[3], o, n[4], n[5]);
+            break;
+        case QTTS_EO_SE_APPLY:
+            launch_se_apply(st, F32(0), d->s[0], F32(1), n[0], F32(2), d->s[1], o, d->s[2], n[1], I32(3), n[2]);
+            break;
+        case QTTS_EO_ASP_STATS:
+            launch_asp_stats(st, F32(0), d->s[0], n[0], I32(1), n[1], n[2], o);
+            break;
+        case QTTS_EO_ASP_POOL:
+            launch_asp_pool(st, F32(0), d->s[0], F32(1), d->s[1], n[0], I32(2), n[1], n[2], o);
+            break;
+        case QTTS_EO_LN_ROWS:
+            launch_ln_rows(st, F32(0), n[0], n[1], F32(1), F32(2), d->eps, o);
+            break;
+        case QTTS_EO_ROPE_BT:
+            if (n[3] % 2 || n[1] < n[2] * n[3]) return -1;
+            launch_rope_bt(st, o, n[0], n[1], n[2], n[3], n[4], F32(0), F32(1));
+            break;
+        case QTTS_EO_ROWS_BT:
+            launch_rows_bt(st, static_cast<int *>(d->out[0]), static_cast<int *>(d->out[1]), n[0], n[1]);
+            break;
+        case QTTS_EO_RVQ_ENC:
+            if (n[1] % 16 || n[4] % 16 || n[5] > 16 || n[6] > n[5] || n[7] < n[0] || n[2] % n[0] ||
+                rvq_enc_smem(n[1], n[4]) > 64 * 1024)
+                return -1;
+            launch_rvq_enc(st, F32(0), n[0], n[1], n[2], F32(1), F32(2), F32(3), n[3], n[4], n[5], n[6],
+                           static_cast<int *>(d->out[0]), n[7]);
+            break;
+        default: return -1;
+    }
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+extern "C" int qtts_hip_enc_func(float *out, const float *x, size_t n, int fn, void *stream) {
+    if (!out || !x || n == 0 || fn < 0 || fn > 1) return -1;
+    hipLaunchKernelGGL(k_enc_func, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, n, fn, out);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
 }

@@ -135,6 +135,7 @@ EXPORTS = [
     "qwen_tts_generate_fed_batch_stream", "qtts_dev_text_open", "qtts_dev_text_append", "qtts_dev_get_trailing",
     "qtts_dev_text_state", "qtts_hip_text_held_frames", "qtts_dev_text_append_ms",
     "qtts_hip_rows_gemm_plan", "qtts_hip_rows_gemm_case",
+    "qtts_hip_econv_plan", "qtts_hip_econv_case", "qtts_hip_enc_op", "qtts_hip_enc_func",
 ]
 
 MAX_BATCH = 64   # QWEN_TTS_MAX_BATCH / QTTS_HIP_MAX_BATCH: lock-step slots per context
@@ -230,6 +231,42 @@ class RowsGemmPlan(C.Structure):
 
 # qtts_rows_gemm_plan_t.kernel (QTTS_RG_* of qtts_hip.h)
 RG_NAMES = ["k_mgemm<1,1>", "k_mgemm<2,1>", "k_mgemm<4,1>", "k_mgemm<4,2>", "k_mgemm<4,4>", "k_pgemm<2>", "k_pgemm<4>"]
+
+
+class EConvDesc(C.Structure):
+    """qtts_econv_desc_t (include/qtts_hip.h): one launch of the voice-clone
+    encoders' contraction kernel k_econv, as the encoders describe it.  Device
+    pointers as integers; w is fp32 [M][ci * kw]."""
+    _fields_ = [("M", C.c_int), ("ci", C.c_int), ("kw", C.c_int), ("stride", C.c_int), ("dil", C.c_int),
+                ("padl", C.c_int), ("pmode", C.c_int), ("act_in", C.c_int),
+                ("w", C.c_void_p),
+                ("x", C.c_void_p), ("x2", C.c_void_p), ("xb", C.c_size_t), ("xc", C.c_int), ("xt", C.c_int),
+                ("lin", C.c_int * 16), ("lout", C.c_int * 16), ("nb", C.c_int), ("nmax", C.c_int),
+                ("y", C.c_void_p), ("yb", C.c_size_t), ("yc", C.c_int), ("yt", C.c_int),
+                ("bias", C.c_void_p), ("bias2", C.c_void_p), ("bias2_b", C.c_int), ("act_out", C.c_int),
+                ("vec", C.c_void_p),
+                ("res", C.c_void_p), ("rb", C.c_size_t), ("rc", C.c_int), ("rt", C.c_int),
+                ("part", C.c_void_p), ("part_elems", C.c_size_t)]
+
+
+class EConvPlan(C.Structure):
+    """qtts_econv_plan_t (include/qtts_hip.h): what launch_econv launches."""
+    _fields_ = [("rows", C.c_int), ("kz", C.c_int), ("grid_x", C.c_int), ("grid_y", C.c_int), ("grid_z", C.c_int),
+                ("part_elems", C.c_size_t)]
+
+
+class EncOp(C.Structure):
+    """qtts_enc_op_t (include/qtts_hip.h): one launch of one small encoder kernel."""
+    _fields_ = [("op", C.c_int), ("inp", C.c_void_p * 6), ("out", C.c_void_p * 2), ("n", C.c_int * 8),
+                ("s", C.c_size_t * 3), ("eps", C.c_float)]
+
+
+# qtts_enc_op_t.op (QTTS_EO_* of qtts_hip.h)
+(EO_MEL, EO_ROW_MEAN, EO_EGEMV, EO_SE_APPLY, EO_ASP_STATS, EO_ASP_POOL, EO_LN_ROWS, EO_ROPE_BT, EO_ROWS_BT,
+ EO_RVQ_ENC) = range(10)
+# k_econv padding modes and activations (k_enc.hip)
+EPAD_ZERO, EPAD_REFLECT, EPAD_REPLICATE = range(3)
+EACT_NONE, EACT_RELU, EACT_RELU_TANH, EACT_GELU, EACT_SIGMOID = range(5)
 
 
 class XGemmDesc(C.Structure):
@@ -583,6 +620,15 @@ def lib():
         for f in (L.qtts_hip_prefix_hits, L.qtts_hip_prefix_misses, L.qtts_hip_prefill_rows):
             f.restype = C.c_longlong
             f.argtypes = []
+    if hasattr(L, "qtts_hip_econv_case"):
+        L.qtts_hip_econv_plan.restype = C.c_int
+        L.qtts_hip_econv_plan.argtypes = [C.POINTER(EConvDesc), C.POINTER(EConvPlan)]
+        L.qtts_hip_econv_case.restype = C.c_int
+        L.qtts_hip_econv_case.argtypes = [C.POINTER(EConvDesc), C.POINTER(EConvPlan), vp]
+        L.qtts_hip_enc_op.restype = C.c_int
+        L.qtts_hip_enc_op.argtypes = [C.POINTER(EncOp), vp]
+        L.qtts_hip_enc_func.restype = C.c_int
+        L.qtts_hip_enc_func.argtypes = [vp, vp, C.c_size_t, C.c_int, vp]
     if hasattr(L, "qtts_hip_rows_gemm_case"):
         L.qtts_hip_rows_gemm_plan.restype = C.c_int
         L.qtts_hip_rows_gemm_plan.argtypes = [C.POINTER(RowsGemmDesc), C.c_size_t, C.c_size_t, C.c_int,
@@ -1626,6 +1672,52 @@ class Kernels:
         p = RowsGemmPlan()
         rc = lib().qtts_hip_rows_gemm_case(C.byref(desc), force, C.byref(p), _stream())
         return Kernels._rows_gemm_result(rc, p, "rows_gemm_case")
+
+    @staticmethod
+    def _econv_result(rc, p, who):
+        if rc == -1:
+            return None
+        _ok(rc, who)
+        return dict(rows=p.rows, kz=p.kz, grid=[p.grid_x, p.grid_y, p.grid_z], part_elems=int(p.part_elems))
+
+    @staticmethod
+    def econv_plan(desc):
+        """launch_econv's plan for an EConvDesc (qtts_hip_econv_plan; host only,
+        no device needed): a dict with rows (1: the time-major fast path), kz,
+        the grid and the split-K workspace floats, or None where the launcher
+        refuses the descriptor."""
+        p = EConvPlan()
+        return Kernels._econv_result(lib().qtts_hip_econv_plan(C.byref(desc), C.byref(p)), p, "econv_plan")
+
+    @staticmethod
+    def econv_case(desc):
+        """Runs one k_econv launch through launch_econv (qtts_hip_econv_case):
+        the plan that ran, or None on a refusal or a device error."""
+        p = EConvPlan()
+        return Kernels._econv_result(lib().qtts_hip_econv_case(C.byref(desc), C.byref(p), _stream()), p, "econv_case")
+
+    @staticmethod
+    def enc_op(op, inp=(), out=(), n=(), s=(), eps=0.0):
+        """One launch of a small encoder kernel (qtts_hip_enc_op): op EO_*, inp /
+        out torch tensors (None: NULL), n / s the integers of qtts_hip.h's table.
+        True when launched, False when refused."""
+        d = EncOp()
+        d.op = op
+        for i, t in enumerate(inp):
+            d.inp[i] = t.data_ptr() if t is not None else None
+        for i, t in enumerate(out):
+            d.out[i] = t.data_ptr() if t is not None else None
+        for i, v in enumerate(n):
+            d.n[i] = int(v)
+        for i, v in enumerate(s):
+            d.s[i] = int(v)
+        d.eps = eps
+        return lib().qtts_hip_enc_op(C.byref(d), _stream()) == 0
+
+    @staticmethod
+    def enc_func(out, x, fn):
+        """k_econv's own device functions elementwise (qtts_hip_enc_func): fn 0 erff, 1 expm1f."""
+        _ok(lib().qtts_hip_enc_func(_ptr(out), _ptr(x), x.numel(), fn, _stream()), "enc_func")
 
     @staticmethod
     def sample_top_k_rows(out_i32, logits, vocab, top_k, top_p, temperature, rng_u32, batch=1):
