@@ -609,6 +609,27 @@ int qtts_hip_attn_cached(float *out_dev, float *q_dev, int ld_q, void *kc_dev, v
                          const float *rope_cos_dev, const float *rope_sin_dev,
                          const int *row_b_dev, const int *pos_dev, int NH, int KV, int HD, int S, int slots,
                          int rows, float eps, int win, int kv_dtype, int prep, void *stream);
+/* The tiled causal attention of long prefills (k_attn_tile) over segments:
+ * seg_table_dev [nseg][4] ints = {slot, first row, first position, count}, a
+ * run of `count` consecutive rows of q_dev / out_dev of one slot at
+ * consecutive positions; a row at position p attends keys [0, p] of its slot
+ * of the caches [slots][S][KV*HD].  One workgroup loads each key block once
+ * for a tile of 32 positions and every query head of a kv head, and multiplies
+ * on the fp32 matrix cores.
+ * prep 1: fused q|k|v rows, qtts_qk_prep first (every row of the call in
+ *   exactly one segment), as qtts_hip_attn_cached; prep 0: q ready, caches filled.
+ * Covers HD 64 | 128, NH / KV 1 | 2, kv_dtype 0 | 1, win 0, 16-byte aligned
+ * rows; returns 1 for any other shape, with nothing launched and nothing
+ * written.  -1: a segment outside the rows, the slots or the cache.
+ * qtts_hip_attn_tile_launches: tiled launches since the library loaded (the
+ * talker prefill takes one per layer when a segment of the call has at least
+ * QTTS_HIP_ATTN_TILE rows: default 256, 0 never, latched by qtts_dev_create). */
+int qtts_hip_attn_tiled(float *out_dev, float *q_dev, int ld_q, void *kc_dev, void *vc_dev,
+                        const float *qn_w_dev, const float *kn_w_dev,
+                        const float *rope_cos_dev, const float *rope_sin_dev,
+                        const int *seg_table_dev, int nseg, int NH, int KV, int HD, int S, int slots,
+                        int rows, float eps, int win, int kv_dtype, int prep, void *stream);
+long long qtts_hip_attn_tile_launches(void);
 /* The sub-talker's attention + O projection by kv head (k_attn_o), fp32 caches
  * [rows][S][KV*HD], no id table: part_dev[(g * rows + r) * R + i] =
  * Wo[i, 2 HD g .. 2 HD (g + 1)) . attention of kv head g's two query heads;

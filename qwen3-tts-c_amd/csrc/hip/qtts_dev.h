@@ -279,6 +279,10 @@ struct qtts_dev {
     unsigned *pf_sink = nullptr;
     bool attn_defer = true;  // QTTS_HIP_ATTN_DEFER=0: batch-1 talker attention merges its own splits
     int attn_lpk = 0;        // QTTS_HIP_ATTN_LPK=4|8|16 (HD 128 split size), latched here: sizes att_part
+    // QTTS_HIP_ATTN_TILE=<rows>: a prefill call with a segment of at least this
+    // many rows takes the tiled attention (k_attn_tile.hip); 0: never; latched here
+    int attn_tile_min = 256;
+    AttnSeg *pseg = nullptr; // [nb] the prefill call's segments (with prow_b / ppos)
     // QTTS_HIP_GM_DBG=<layer>: phase stamps of that talker layer's batch GEMVs
     // (q|k|v, O, gate|up, down), printed by qtts_dev_get_codes
     int gm_dbg_layer = -1;

@@ -226,7 +226,23 @@ struct AttnArgs {
     // paths refuse it.  K and V rows are rounded to nearest even as they are
     // stored, and the token's own k, v enter its attention as the rounded values
     int kv_dtype = 0;
+    // k_attn_tile: rows of the longest segment (sizes the grid; 0: nrows)
+    int seg_max = 0;
 };
+// A run of `count` consecutive rows of slot `slot` at consecutive positions
+// pos0, pos0 + 1, ...: rows row0 .. row0 + count - 1 of AttnArgs::qkv / out
+// (four ints, the layout of qtts_hip_attn_tiled's seg_table)
+struct AttnSeg {
+    int slot, row0, pos0, count;
+};
+// Tiled causal attention over segments on the fp32 matrix cores
+// (k_attn_tile.hip): the cached attention (mode 1, q ready, every key in the
+// cache) of long prefills; AttnArgs::pos / row_b are not read.  segs: device
+// memory, nseg entries.  HD 64 | 128, NH / KV 1 | 2, fp32 or bf16 cache, no
+// window; 1 = not covered (nothing launched)
+bool qtts_attn_tile_covers(const AttnArgs &a);
+int qtts_attn_tile(const AttnArgs &a, const AttnSeg *segs, int nseg, hipStream_t st);
+long long qtts_attn_tile_launches();   // launches since the library loaded
 // keys per split of the talker decode attention (deferred merge or not; lpk
 // as AttnArgs::lpk)
 int qtts_attn_keys_per_split(int HD, bool defer, int lpk);

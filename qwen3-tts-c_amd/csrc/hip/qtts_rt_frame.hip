@@ -780,10 +780,18 @@ int prefill_rows(qtts_dev *dv, const std::vector<int> &slots, const std::vector<
     const qtts_dims_t &d = dv->d;
     hipStream_t st = dv->st;
     std::vector<int> rb, pp, src;
+    // a slot's rows are one segment: consecutive rows at consecutive positions
+    std::vector<AttnSeg> segs;
+    int seg_max = 0;
     last.assign(slots.size(), 0);
     for (size_t i = 0; i < slots.size(); ++i) {
         const int b = slots[i];
-        for (int t = first ? (*first)[i] : 0; t < nrows[i]; ++t) {
+        const int t0 = first ? (*first)[i] : 0;
+        if (nrows[i] > t0) {
+            segs.push_back(AttnSeg{b, (int)rb.size(), t0, nrows[i] - t0});
+            seg_max = std::max(seg_max, nrows[i] - t0);
+        }
+        for (int t = t0; t < nrows[i]; ++t) {
             rb.push_back(b);
             pp.push_back(t);
             src.push_back(b * dv->p_cap + t);
@@ -797,12 +805,21 @@ int prefill_rows(qtts_dev *dv, const std::vector<int> &slots, const std::vector<
     CK(hipMemcpyAsync(dv->ppos, pp.data(), R * 4, hipMemcpyHostToDevice, st));
     CK(hipMemcpyAsync(dv->psrc, src.data(), R * 4, hipMemcpyHostToDevice, st));
     CKI(qtts_copy_rows(dv->px, d.H, dv->prefill, d.H, dv->psrc, R, d.H, st));
+    // the tiled attention for the whole call (every layer, every segment) when
+    // one segment is long enough and the shape is covered, else row by row
+    bool tiled = dv->attn_tile_min > 0 && seg_max >= dv->attn_tile_min && (int)segs.size() <= dv->nb &&
+                 qtts_attn_tile_covers(talker_attn(dv, 0, R, true));
+    if (tiled) CK(hipMemcpyAsync(dv->pseg, segs.data(), segs.size() * sizeof(AttnSeg), hipMemcpyHostToDevice, st));
     for (int l = 0; l < d.L; ++l) {
         const LayerView lv = talker_view(dv, l, 0);
         CKI(rows_proj(dv, lv.qkv(dv->px, dv->pqkv, 1), R, true));
-        const AttnArgs t = talker_attn(dv, l, R, true);
+        AttnArgs t = talker_attn(dv, l, R, true);
         CKI(qtts_qk_prep(t, st));
-        CKI(qtts_attention(t, st));
+        if (tiled) {
+            t.seg_max = seg_max;
+            CKI(qtts_attn_tile(t, dv->pseg, (int)segs.size(), st));
+        } else
+            CKI(qtts_attention(t, st));
         CKI(rows_proj(dv, lv.o(dv->patt, dv->px, 1), R, true));
         CKI(rows_proj(dv, lv.gate_up(dv->px, dv->ph, 1), R, true));
         CKI(rows_proj(dv, lv.down(dv->ph, dv->px, 1), R, true));

@@ -238,6 +238,66 @@ extern "C" int qtts_hip_attn_cached(float *out, float *q, int ld_q, void *kc, vo
     return rc;
 }
 
+// The tiled attention (k_attn_tile) on its own over seg_table [nseg][4] =
+// {slot, first row, first position, count} (device memory): prep 1 as
+// prefill_rows issues it (qtts_qk_prep over the segments' rows, then the
+// tiled launch, on fused q|k|v rows), prep 0 with q ready and the caches
+// filled.  1 = a shape qtts_attn_tile_covers refuses: nothing is written.
+extern "C" long long qtts_hip_attn_tile_launches(void) { return qtts_attn_tile_launches(); }
+
+extern "C" int qtts_hip_attn_tiled(float *out, float *q, int ld_q, void *kc, void *vc, const float *qn_w,
+                                   const float *kn_w, const float *rope_cos, const float *rope_sin,
+                                   const int *seg_table, int nseg, int NH, int KV, int HD, int S, int slots, int rows,
+                                   float eps, int win, int kv_dtype, int prep, void *stream) {
+    if (!out || !q || !kc || !vc || !seg_table || nseg < 1 || nseg > 65535) return -1;
+    if (prep != 0 && prep != 1) return -1;
+    if (prep && (!qn_w || !kn_w || !rope_cos || !rope_sin)) return -1;
+    if (!attn_dims_ok(NH, KV, HD, S, rows, kv_dtype) || slots < 1 || win < 0) return -1;
+    if (ld_q < (prep ? NH + 2 * KV : NH) * HD) return -1;
+    hipStream_t st = (hipStream_t)stream;
+    AttnArgs t;
+    t.mode = 1; t.qkv = q; t.ld_qkv = ld_q; t.qn_w = qn_w; t.kn_w = kn_w; t.eps = eps;
+    t.rope_cos = rope_cos; t.rope_sin = rope_sin;
+    t.kc = (float *)kc; t.vc = (float *)vc; t.S = S; t.kv_dtype = kv_dtype;
+    t.NH = NH; t.KV = KV; t.HD = HD; t.out = out; t.ld_out = NH * HD; t.nrows = rows; t.win = win;
+    if (!qtts_attn_tile_covers(t)) return 1;   // (before the cache writes)
+    // the table on the host: every segment inside the rows, the slots and the
+    // cache (the kernels index by it unchecked), no row in two segments
+    std::vector<AttnSeg> sg(nseg);
+    CK(hipMemcpyAsync(sg.data(), seg_table, (size_t)nseg * sizeof(AttnSeg), hipMemcpyDeviceToHost, st));
+    CK(hipStreamSynchronize(st));
+    std::vector<int> rb(rows, -1), pp(rows, 0);
+    for (const AttnSeg &s : sg) {
+        if (s.slot < 0 || s.slot >= slots || s.count < 1 || s.row0 < 0 || s.pos0 < 0 || s.count > rows ||
+            s.row0 > rows - s.count || s.pos0 > S - s.count) {
+            fprintf(stderr, "qtts_hip_attn_tiled: segment {%d, %d, %d, %d} outside %d rows, %d slots, %d positions\n",
+                    s.slot, s.row0, s.pos0, s.count, rows, slots, S);
+            return -1;
+        }
+        for (int i = 0; i < s.count; ++i) {
+            if (rb[s.row0 + i] >= 0) { fprintf(stderr, "qtts_hip_attn_tiled: row %d in two segments\n", s.row0 + i); return -1; }
+            rb[s.row0 + i] = s.slot;
+            pp[s.row0 + i] = s.pos0 + i;
+        }
+        t.seg_max = std::max(t.seg_max, s.count);
+    }
+    int rc = 0;
+    int *tab = nullptr;
+    if (prep) {   // qtts_qk_prep's row tables (every row of the call must then be in a segment)
+        for (int r = 0; r < rows; ++r)
+            if (rb[r] < 0) { fprintf(stderr, "qtts_hip_attn_tiled: prep with row %d in no segment\n", r); return -1; }
+        CK(hipMalloc((void **)&tab, (size_t)rows * 8));
+        rc = hipMemcpyAsync(tab, rb.data(), (size_t)rows * 4, hipMemcpyHostToDevice, st) == hipSuccess &&
+             hipMemcpyAsync(tab + rows, pp.data(), (size_t)rows * 4, hipMemcpyHostToDevice, st) == hipSuccess ? 0 : -1;
+        t.row_b = tab; t.pos = tab + rows;
+        if (!rc) rc = qtts_qk_prep(t, st);
+    }
+    if (!rc) rc = qtts_attn_tile(t, reinterpret_cast<const AttnSeg *>(seg_table), nseg, st);
+    if (hipStreamSynchronize(st) != hipSuccess) rc = -1;
+    if (tab) hipFree(tab);
+    return rc;
+}
+
 // The sub-talker's attention + O projection by kv head (k_attn_o) on its own:
 // fp32 caches [rows][S][KV*HD], no id table; part [KV][rows][R].  1 = a shape
 // qtts_attn_o_covers refuses.

@@ -315,6 +315,8 @@ extern "C" qtts_dev_t *qtts_dev_create(const qtts_dims_t *dims, int device) {
     dv->attn_defer = !(ad && !atoi(ad));
     const char *lk = getenv("QTTS_HIP_ATTN_LPK");
     dv->attn_lpk = lk ? atoi(lk) : 0;
+    const char *at = getenv("QTTS_HIP_ATTN_TILE");
+    if (at && *at) dv->attn_tile_min = atoi(at) < 0 ? 0 : atoi(at);
     const char *ao = getenv("QTTS_HIP_ATTN_O");
     dv->attn_o = !(ao && !atoi(ao));
     const char *pg = getenv("QTTS_HIP_PGEMM");
@@ -634,6 +636,7 @@ static int alloc_state(qtts_dev *dv, int nb, int max_frames, int max_prefill) {
     A(ppos, int, R);
     A(psrc, int, R);
     A(plast, int, B);
+    A(pseg, AttnSeg, B);
     dv->pinv_cap = dv->rows_cap > 64 ? dv->rows_cap : 64;
     A(pinv, float, dv->pinv_cap);
     {

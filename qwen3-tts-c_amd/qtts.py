@@ -136,6 +136,7 @@ EXPORTS = [
     "qtts_dev_text_state", "qtts_hip_text_held_frames", "qtts_dev_text_append_ms",
     "qtts_hip_rows_gemm_plan", "qtts_hip_rows_gemm_case",
     "qtts_hip_econv_plan", "qtts_hip_econv_case", "qtts_hip_enc_op", "qtts_hip_enc_func",
+    "qtts_hip_attn_tiled", "qtts_hip_attn_tile_launches",
 ]
 
 MAX_BATCH = 64   # QWEN_TTS_MAX_BATCH / QTTS_HIP_MAX_BATCH: lock-step slots per context
@@ -1548,6 +1549,33 @@ class Kernels:
         _ok(lib().qtts_hip_attn_cached(_ptr(out), _ptr(q), ld_q, _ptr(kc), _ptr(vc), _ptr(qn_w), _ptr(kn_w),
                                        _ptr(rope_cos), _ptr(rope_sin), _ptr(row_b_i32), _ptr(pos_i32), NH, KV, HD, S,
                                        slots, rows, eps, win, kv_dtype, prep, _stream()), "attn_cached")
+
+    @staticmethod
+    def attn_tiled(out, q, ld_q, kc, vc, qn_w, kn_w, rope_cos, rope_sin, seg_table_i32, nseg, NH, KV, HD, S, slots,
+                   rows, eps, win=0, kv_dtype=0, prep=0):
+        """The tiled causal attention (qtts_hip_attn_tiled) over seg_table
+        [nseg, 4] = {slot, first row, first position, count}; prep as
+        attn_cached.  False where the kernel does not cover the shape
+        (nothing ran)."""
+        L = lib()
+        L.qtts_hip_attn_tiled.restype = C.c_int
+        L.qtts_hip_attn_tiled.argtypes = ([C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 7 + [C.c_int] * 7 +
+                                          [C.c_float] + [C.c_int] * 3 + [C.c_void_p])
+        rc = L.qtts_hip_attn_tiled(_ptr(out), _ptr(q), ld_q, _ptr(kc), _ptr(vc), _ptr(qn_w), _ptr(kn_w),
+                                   _ptr(rope_cos), _ptr(rope_sin), _ptr(seg_table_i32), nseg, NH, KV, HD, S, slots,
+                                   rows, eps, win, kv_dtype, prep, _stream())
+        if rc == 1:
+            return False
+        _ok(rc, "attn_tiled")
+        return True
+
+    @staticmethod
+    def attn_tile_launches():
+        """tiled attention launches since the library loaded (qtts_hip_attn_tile_launches)"""
+        L = lib()
+        L.qtts_hip_attn_tile_launches.restype = C.c_longlong
+        L.qtts_hip_attn_tile_launches.argtypes = []
+        return int(L.qtts_hip_attn_tile_launches())
 
     @staticmethod
     def attn_o(part, qkv, kc, vc, qn_w, kn_w, rope_cos, rope_sin, pos_i32, Wo_u16, R, NH, KV, HD, S, rows, eps):
