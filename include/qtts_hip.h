@@ -99,6 +99,13 @@ size_t qtts_dev_bytes(const qtts_dev_t *dev, int which /*0 weights, 1 state*/);
  * the getter returns the value the next begin will use. */
 int qtts_dev_set_kv_dtype(qtts_dev_t *dev, int dtype);
 int qtts_dev_kv_dtype(const qtts_dev_t *dev);
+/* Precision of the codec's conv / transposed-conv products: 0 exact (default,
+ * or $QTTS_HIP_CODEC at creation), 1 one bf16 plane per operand (k_convh on
+ * every shape k_convb covers; linears, sums, epilogues and state fp32).
+ * Read by the next stateless decode; a codec stream or multi-stream latches it
+ * at begin.  -1 on a bad value. */
+int qtts_dev_set_codec_precision(qtts_dev_t *dev, int precision);
+int qtts_dev_codec_precision(const qtts_dev_t *dev);
 /* Diagnostics: talker cache rows [pos0, pos0 + n) of layer `layer`, slot b,
  * to the host as fp32 [n][KV*HD] each (bf16 widened exactly; k_host or v_host
  * may be NULL).  Waits for the context stream.  -1 out of range. */
@@ -753,6 +760,8 @@ enum {
     QTTS_XP_XLIN = 3,     /* k_xlin: bf16 3-plane linear */
     QTTS_XP_XGEMV = 4,    /* k_xgemv: linear at <= 4 rows */
     QTTS_XP_XGEMM = 5,    /* k_xgemm: generic */
+    QTTS_XP_CONVH2 = 6,   /* k_convh<Kw,2>: bf16 one-plane conv, 64 x 128 tile (opt-in codec precision) */
+    QTTS_XP_CONVH4 = 7,   /* k_convh<Kw,4>: 64 x 256 tile */
 };
 /* The dispatcher's plan for the contraction with a split workspace of
  * part_elems floats (0: none): which kernel (path_out) and how many splits

@@ -238,6 +238,22 @@ qwen_tts_ctx_t *qwen_tts_load_on(const char *model_dir, int device);
 #define QWEN_TTS_KV_BF16 1
 int qwen_tts_set_kv_cache_dtype(qwen_tts_ctx_t *ctx, int dtype);
 int qwen_tts_kv_cache_dtype(qwen_tts_ctx_t *ctx);
+/* Arithmetic of the codec's vocoder convolutions.  QWEN_TTS_CODEC_EXACT (the
+ * default) keeps fp32-equivalent products.  QWEN_TTS_CODEC_BF16 rounds the
+ * conv and transposed-conv weights and their (SnakeBeta'd) inputs to bf16
+ * (nearest even) and multiplies them with one matrix instruction where the
+ * exact path needs six; sums, epilogues, every linear (transformer, ConvNeXt,
+ * RVQ) and all carried state stay fp32, and the codes are untouched (the Python
+ * reference runs the whole codec in bf16).  -1 on a bad value.  The stateless
+ * decode reads the value per call.  A stream (single or multi-stream) latches
+ * it at its begin and keeps it for every push until its next begin, so a
+ * change between pushes of a live stream takes effect with the next begin;
+ * snapshots hold fp32 state and restore into either mode.
+ * $QTTS_HIP_CODEC=bf16|exact sets the default of every ctx loaded after it. */
+#define QWEN_TTS_CODEC_EXACT 0
+#define QWEN_TTS_CODEC_BF16  1
+int qwen_tts_set_codec_precision(qwen_tts_ctx_t *ctx, int precision);
+int qwen_tts_codec_precision(qwen_tts_ctx_t *ctx);
 /* Most lock-step slots of one ctx (qwen_tts_generate_batch, the slots of
  * qwen_tts_generate_queue, qwen_tts_generate_voice_clone_batch): up to 16 run
  * on the 16-row matrix-core batch kernels, 17..64 on the wide batch kernel. */

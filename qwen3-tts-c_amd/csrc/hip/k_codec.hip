@@ -21,60 +21,11 @@
 #include "qtts_codec.h"
 #include "qtts_common.h"
 #include "qtts_kernels.h"
-
-typedef float floatx16 __attribute__((ext_vector_type(16)));
+#include "qtts_xgemm_dev.h"
 
 namespace {
 
 constexpr int BM = 64, BN = 64, BK = 32;
-
-// sin^2(r): the sign of sin drops out, so one Cody-Waite step by pi
-// (pi = PI_HI + PI_LO; both products exact inside the fmas, k exact below
-// 2^24) and the odd Taylor series through y^13 on [-pi/2, pi/2] (truncation
-// < 1e-9) give sinf(r)^2 to 2.2e-7 absolute (checked over |r| <= 8192) in
-// ~15 instructions instead of the general sinf's ~90 plus its inlined
-// large-argument path.
-__device__ __forceinline__ float sin2(float r) {
-    const float k = rintf(r * 0.318309886183790672f);
-    float y = fmaf(-k, 3.14159274101257324f, r);
-    y = fmaf(-k, -8.74227765734758577e-08f, y);
-    const float y2 = y * y;
-    float p = 1.6059043836821613e-10f;                 // 1/13!
-    p = fmaf(p, y2, -2.5052108385441720e-08f);         // -1/11!
-    p = fmaf(p, y2, 2.7557319223985893e-06f);          // 1/9!
-    p = fmaf(p, y2, -1.9841269841269841e-04f);         // -1/7!
-    p = fmaf(p, y2, 8.3333333333333333e-03f);          // 1/5!
-    p = fmaf(p, y2, -1.6666666666666667e-01f);         // -1/3!
-    const float sn = fmaf(y * y2, p, y);
-    return sn * sn;
-}
-
-__device__ __forceinline__ float snake1(float x, float a, float ib) { return x + ib * sin2(x * a); }
-
-// stream axis (XGemm::nseg / seg_m).  Conv forms: workgroup column bx of the
-// grid is tile bx % tiles of segment bx / tiles; xg_seg moves the operands to
-// that segment (nz: the main kernel's grid z, whose partials a segment owns).
-__device__ __forceinline__ void xg_seg(XGemm &g, int sg, int nz) {
-    g.B += (size_t)sg * g.seg_ldb;
-    g.C += (size_t)sg * g.seg_ldc;
-    if (g.res) g.res += (size_t)sg * g.seg_ldres;
-    if (g.part) g.part += (size_t)sg * nz * g.M * g.N;
-}
-__device__ __forceinline__ int xg_seg_tile(XGemm &g) {
-    int bx = blockIdx.x;
-    if (g.nseg > 1) {
-        const int tps = gridDim.x / g.nseg, sg = bx / tps;
-        bx -= sg * tps;
-        xg_seg(g, sg, gridDim.z);
-    }
-    return bx;
-}
-// stacked rows: where row m of a per-segment operand lies (ld: its segment stride)
-__device__ __forceinline__ size_t xg_srow(const XGemm &g, int m, int ld) {
-    if (!g.seg_m) return (size_t)m;
-    const int sg = m / g.seg_m;
-    return (size_t)sg * ld + (m - sg * g.seg_m);
-}
 
 __device__ __forceinline__ float loadB(const XGemm &g, int k, int n) {
     if (k >= g.K || n >= g.N) return 0.f;
@@ -101,37 +52,6 @@ __device__ __forceinline__ float loadA(const XGemm &g, int m, int k) {
     const int ntap = g.Kw / g.stride;  // tconv weight [ci][co][Kw], k = ic*ntap + j
     const int ic = k / ntap, j = k - ic * ntap;
     return g.A[((size_t)ic * g.co + m) * g.Kw + g.phase + j * g.stride];
-}
-
-__device__ __forceinline__ float gelu_tanh(float v) {
-    return 0.5f * v * (1.0f + tanhf(0.7978845608028654f * (v + 0.044715f * v * v * v)));
-}
-
-__device__ __forceinline__ void xg_epi(const XGemm &g, int m, int n, float v) {
-    switch (g.emode) {
-        case XE_STORE: g.C[(size_t)m * g.ldc + n] = v; break;
-        case XE_BIAS_N: g.C[(size_t)m * g.ldc + n] = v + g.bias[n]; break;
-        case XE_BIAS_N_GELU: g.C[(size_t)m * g.ldc + n] = gelu_tanh(v + g.bias[n]); break;
-        case XE_SILU_MUL: {
-            const float gt = g.aux[(size_t)m * g.ldaux + n];
-            g.C[(size_t)m * g.ldc + n] = (gt / (1.0f + expf(-gt))) * v;
-            break;
-        }
-        case XE_SCALE_RESID_N: g.C[(size_t)m * g.ldc + n] += v * g.vec[n]; break;
-        case XE_BIAS_T: g.C[(size_t)n * g.ldc + xg_srow(g, m, g.seg_ldc)] = v + g.bias[n]; break;
-        case XE_BIAS_GAMMA_RES_T:
-            g.C[(size_t)n * g.ldc + xg_srow(g, m, g.seg_ldc)] =
-                (v + g.bias[n]) * g.vec[n] + g.res[(size_t)n * g.ldres + xg_srow(g, m, g.seg_ldres)];
-            break;
-        case XE_BIAS_M: {
-            float y = v + (g.bias ? g.bias[m] : 0.f);
-            if (g.stride > 1 || g.phase > 0) g.C[(size_t)m * g.ldc + (size_t)n * g.stride + g.phase] = y;
-            else g.C[(size_t)m * g.ldc + n] = y;
-            break;
-        }
-        case XE_BIAS_M_RES: g.C[(size_t)m * g.ldc + n] = v + g.bias[m] + g.res[(size_t)m * g.ldres + n]; break;
-        case XE_BIAS_M_SNAKE: g.C[(size_t)m * g.ldc + n] = snake1(v + g.bias[m], g.ea[m], g.eb[m]); break;
-    }
 }
 
 // 64x64 output tile per workgroup (2x2 waves of 32x32 on v_mfma_f32_32x32x2f32),
@@ -221,7 +141,7 @@ __global__ __launch_bounds__(256) void k_xgemm(XGemm g) {
 // per element -- and every tap reads it shifted by tap*dil; the stage's
 // Kw x 64 x 16 weights come from the re-laid [Kw][co][ci] copy as float4.
 // The next stage's loads are in registers while the MFMAs consume this one.
-constexpr int CV_BM = 64, CV_BN = 128, CV_BC = 16, CV_HALO = 64;   // halo >= (Kw-1)*dil (host-checked)
+// (tile constants CV_*: qtts_xgemm_dev.h)
 
 // blockIdx.z = phase * kz + split: the transposed-conv output phase
 // (tconv_run: weights g.wt + phase*KW*M*ci, outputs at column
@@ -333,16 +253,9 @@ __global__ __launch_bounds__(256) void k_conv(XGemm g) {
 // LDS rows are 16 channels (32 B) with the two 16-B halves swapped on odd
 // 8-row groups: conflict-free ds_read_b128 fragments.  The weight planes
 // follow the fp32 relayout in the same allocation (wt_planes).
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-constexpr int CB_SNAKE_MAX = 1536;   // input channels per split k_convb takes with SnakeBeta (larger: k_conv)
 
 __device__ __forceinline__ int cb_swz(int row, int half) { return row * 16 + 8 * (half ^ ((row >> 3) & 1)); }
 
-__device__ __forceinline__ uint32_t cb_pk(float lo, float hi) {
-    typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
-    const bf2 v = {(__bf16)lo, (__bf16)hi};
-    return __builtin_bit_cast(uint32_t, v);
-}
 __device__ __forceinline__ float cb_lo(uint32_t p) { return __uint_as_float(p << 16); }
 __device__ __forceinline__ float cb_hi(uint32_t p) { return __uint_as_float(p & 0xFFFF0000u); }
 
@@ -873,7 +786,10 @@ static bool conv_ok(const XGemm &g) {
     if (!conv_shape_ok(g)) return false;
     const int tiles =
         ((g.N + CV_BN - 1) / CV_BN) * ((g.M + CV_BM - 1) / CV_BM) * (g.stride > 1 ? g.stride : 1) * xg_nseg(g);
-    return tiles >= min_tiles || (g.part && conv_splits(g) > 1);
+    // (the bf16 precision takes every shape the conv kernels cover: which convs
+    // round their operands must not depend on how many columns a call holds, or a
+    // short stream push and a long decode of the same codes differ by a rounding)
+    return tiles >= min_tiles || g.prec || (g.part && conv_splits(g) > 1);
 }
 
 // input-channel splits for a grid that would not fill the chip: up to 1024
@@ -975,6 +891,8 @@ static XPlan xg_plan(const XGemm &g) {
     } else if (conv_ok(g)) {
         p.splits = conv_splits(g);
         p.path = conv_path(g, p.splits);
+        // the opt-in bf16 precision: k_convb's shapes on one plane (k_convh), same tile width
+        if (g.prec && p.path != QTTS_XP_CONV) p.path = p.path == QTTS_XP_CONVB4 ? QTTS_XP_CONVH4 : QTTS_XP_CONVH2;
     } else {
         p.path = QTTS_XP_XGEMM;
         p.splits = xgemm_splits(g);
@@ -989,10 +907,12 @@ static bool xg_plan_forced(const XGemm &g, int path, XPlan *p) {
     switch (path) {
         case QTTS_XP_CONVB2:
         case QTTS_XP_CONVB4:
+        case QTTS_XP_CONVH2:
+        case QTTS_XP_CONVH4:
         case QTTS_XP_CONV:
             if (!conv_shape_ok(g)) return false;
             p->splits = conv_splits(g);
-            // k_convb takes a SnakeBeta prologue up to CB_SNAKE_MAX channels per split
+            // k_convb / k_convh take a SnakeBeta prologue up to CB_SNAKE_MAX channels per split
             return path == QTTS_XP_CONV || conv_path(g, p->splits) != QTTS_XP_CONV;
         case QTTS_XP_XLIN: p->splits = xlin_splits(g); return xlin_ok(g);
         case QTTS_XP_XGEMV: p->splits = xgemv_ks(g); return xgemv_ok(g);
@@ -1010,8 +930,10 @@ static int conv_launch(const XGemm &gin, const XPlan &p, hipStream_t st) {
     g.kz = p.splits;
     const int ns = xg_nseg(g);   // grid x: the segments' column tiles one after another
     const dim3 cg((g.N + CV_BN - 1) / CV_BN * ns, (g.M + CV_BM - 1) / CV_BM, nph * g.kz);
-    if (p.path == QTTS_XP_CONVB4) {
-        const dim3 c4((g.N + 255) / 256 * ns, cg.y, cg.z);
+    const dim3 c4((g.N + 255) / 256 * ns, cg.y, cg.z);
+    if (p.path == QTTS_XP_CONVH4 || p.path == QTTS_XP_CONVH2) {
+        qtts_convh_launch(g, p.path == QTTS_XP_CONVH4 ? 4 : 2, p.path == QTTS_XP_CONVH4 ? c4 : cg, st);
+    } else if (p.path == QTTS_XP_CONVB4) {
         switch (g.Kw) {
             case 7: hipLaunchKernelGGL((k_convb<7, 4>), c4, dim3(512), 0, st, g); break;
             case 3: hipLaunchKernelGGL((k_convb<3, 4>), c4, dim3(512), 0, st, g); break;
@@ -1481,6 +1403,7 @@ struct LayerKV {
 struct Place {
     CodecModel *m = nullptr;
     int n = 1;                       // planes (streams) a launch covers
+    int prec = 0;                    // the convs' XGemm::prec: the model's (one-shot decode) or the stream's latched one
     int hm = 0;                      // left margin (columns) of every row; 0: nothing is carried, nothing left of column 0
     float *A = nullptr, *B = nullptr, *Cb = nullptr, *D = nullptr;   // activations; A and B start past the margin
     float *tx = nullptr, *txn = nullptr, *tq = nullptr, *tatt = nullptr, *tg = nullptr, *tu = nullptr;  // [n * T] rows
@@ -1549,7 +1472,7 @@ static int net_conv(Place &p, int &slot, float *x, int ldx, int ci, int L, const
     const int H = (K - 1) * dil;
     if (H > 0) KCK(p.hist(slot, ci, H, x, ldx, L, false));
     XGemm g = conv_desc(p.m, x, ldx, ci, L, wn, bn, co, K, dil, out, ldo, emode, p.tmin(H));
-    g.sa = sa; g.sb = sb; g.res = res; g.ea = ea; g.eb = eb;
+    g.sa = sa; g.sb = sb; g.res = res; g.ea = ea; g.eb = eb; g.prec = p.prec;
     p.planes(g, ci, co);
     if (!g.A) return -1;
     KCK(xgm(p.m, g, p.m->st));
@@ -1563,6 +1486,7 @@ static int net_tconv(Place &p, int &slot, float *x, int ldx, int ci, int L, cons
     const int H = Kw / s - 1;
     if (H > 0) KCK(p.hist(slot, ci, H, x, ldx, L, false));
     XGemm g = tconv_desc(x, ldx, ci, L, w, bias, co, Kw, s, out, ldo, sa, sb, p.tmin(H));
+    g.prec = p.prec;
     p.planes(g, ci, co);
     KCK(tconv_run(p.m, g, p.m->st));
     if (H > 0) KCK(p.hist(slot++, ci, H, x, ldx, L, true));
@@ -1746,6 +1670,7 @@ static int net_decode(Place &p, const int *codes, int T, float **wav_out, int *L
 struct FullPlace : Place {
     explicit FullPlace(CodecModel *cm) {
         take(cm, *cm, 0);
+        prec = cm->prec;
         rvq_s = B; rvq_a = Cb;
     }
     void mark(int i) override { if (m->timing) hipEventRecord(m->tev[i], m->st); }
@@ -1806,6 +1731,7 @@ static void lane_sync_weights(CodecModel *m, CodecModel *ln) {
     ln->cb = m->cb;
     ln->w = m->w;
     ln->wt = m->wt;
+    ln->prec = m->prec;
     ln->timing = false;
 }
 
@@ -2107,6 +2033,7 @@ struct StreamPlace : Place {
     CodecStream &S;
     explicit StreamPlace(CodecModel *cm) : S(cm->cs) {
         take(cm, S, S.hm);
+        prec = S.prec;
         rvq_s = S.rvq_s; rvq_a = S.rvq_a;
         const size_t row0 = (size_t)S.pos0 * (m->d.chid / m->d.cheads);   // the table continues at pos0
         rope_cos += row0; rope_sin += row0;
@@ -2165,12 +2092,14 @@ int codec_stream_begin(CodecModel *m, int max_frames, int chunk) {
                 return -1;
         S0.pos0 = 0;
         S0.hl = 0;
+        S0.prec = m->prec;
         return 0;
     }
     codec_stream_free(m);
     // (ensure_codec_state ran above: the split-K workspace exists)
     CodecStream &S = m->cs;
     S.tc = tc_want;
+    S.prec = m->prec;
     const int hm = S.hm, tc = S.tc;
     auto salloc = [&](size_t bytes) { return dev_alloc(S.allocs, " stream", bytes, true); };
     // activation buffers: largest C x (hm + L) over the stages at tc frames
@@ -2475,6 +2404,7 @@ struct MsPlace : Place {
         : S(cm->ms), ldc_codes(ldc_codes_), t0(t0_), T(T_), dpos0(dpos0_), dhl(dhl_), dtv(dtv_), shifts(shifts_) {
         take(cm, S, S.hm);   // (the whole RoPE table: every row rotates by its own stream's position)
         n = n_;
+        prec = S.prec;
         rvq_s = S.rvq_s; rvq_a = S.rvq_a;
     }
     int hist(int slot, int C, int H, float *x, int ldx, int L, bool out) override {
@@ -2596,6 +2526,7 @@ int codec_mstream_begin(CodecModel *m, int n_streams, int max_frames, int chunk)
         std::fill(S0.pos0.begin(), S0.pos0.end(), 0);
         std::fill(S0.hl.begin(), S0.hl.end(), 0);
         S0.max_frames = max_frames;
+        S0.prec = m->prec;
         return 0;
     }
     if (hipStreamSynchronize(m->st) != hipSuccess) return -1;
@@ -2604,6 +2535,7 @@ int codec_mstream_begin(CodecModel *m, int n_streams, int max_frames, int chunk)
     S.ns = n_streams;
     S.tc = tc;
     S.max_frames = max_frames;
+    S.prec = m->prec;
     S.pos0.assign(n_streams, 0);
     S.hl.assign(n_streams, 0);
     const int hm = S.hm, ns = n_streams;

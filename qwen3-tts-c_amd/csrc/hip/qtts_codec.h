@@ -19,6 +19,7 @@ struct CodecStream {
     int pos0 = 0;              // frames decoded so far (absolute transformer position)
     int tc = 0;                // max frames per internal chunk
     int hm = 64;               // left margin (columns) of every channel-major buffer
+    int prec = 0;              // the model's codec precision at begin: a stream keeps it until its next begin
     std::vector<float *> hist; // history slots [C][H]
     std::vector<int> hist_c, hist_h;
     std::vector<float *> kc, vc;  // transformer layer caches [(win-1) + tc][kvd]
@@ -45,6 +46,7 @@ struct CodecMStream {
     int ns = 0;                    // streams
     int tc = 0;                    // frames per internal pass (<= 16, fewer where ns planes would pass the scratch budget)
     int hm = 64;                   // left margin (columns) of every plane's rows
+    int prec = 0;                  // the model's codec precision at begin, kept by every push until the next begin
     int max_frames = 0;
     std::vector<int> pos0, hl;     // per stream: frames decoded, valid K/V history rows
     std::vector<float *> hist;     // slot -> [ns][C][H]
@@ -106,6 +108,9 @@ struct CodecModel {
     std::map<std::string, std::vector<int64_t>> shape;
     std::map<std::string, std::vector<float>> host_keep;  // usage / esum pending codebook build
     float *cb = nullptr;                              // [Q][CB][vq] codebooks
+    // codec precision (QWEN_TTS_CODEC_EXACT 0 / _BF16 1): the convs' XGemm::prec.
+    // The stateless decode reads it per call; a stream latches it at begin.
+    int prec = 0;
     size_t wbytes = 0;
     // scratch (grown on demand)
     std::vector<void *> scratch;
@@ -243,5 +248,11 @@ struct XGemm {
     // row m at segment m / seg_m, column m % seg_m (seg_lda / seg_ldc / seg_ldres).
     int nseg = 1, seg_m = 0;
     int seg_lda = 0, seg_ldb = 0, seg_ldc = 0, seg_ldres = 0;
+    // products: 0 exact (fp32-equivalent, the default), 1 one bf16 plane per
+    // operand on every shape k_convb covers (then k_convh, whatever the tile
+    // count); every other kernel ignores it
+    int prec = 0;
 };
 int qtts_xgemm(const XGemm &g, hipStream_t st);
+// k_convh.hip: k_convh<g.Kw, wn> on `grid` (k_convb's grid for the same wn; g.kz set)
+void qtts_convh_launch(const XGemm &g, int wn, dim3 grid, hipStream_t st);

@@ -341,6 +341,12 @@ extern "C" qtts_dev_t *qtts_dev_create(const qtts_dims_t *dims, int device) {
     const char *gd = getenv("QTTS_HIP_GM_DBG");
     if (gd) dv->gm_dbg_layer = atoi(gd);
     codec_init(&dv->codec, dims, dv->st);
+    // QTTS_HIP_CODEC=bf16|exact: the codec convs' precision (default exact)
+    const char *cpr = getenv("QTTS_HIP_CODEC");
+    if (cpr && *cpr) {
+        if (!strcmp(cpr, "bf16")) dv->codec.prec = 1;
+        else if (strcmp(cpr, "exact")) fprintf(stderr, "qtts: QTTS_HIP_CODEC=%s ignored (bf16 or exact)\n", cpr);
+    }
     dv->enc.st = dv->st;
     dv->enc.device = device;
     return dv;
@@ -418,6 +424,14 @@ extern "C" int qtts_dev_set_kv_dtype(qtts_dev_t *dv, int dtype) {
 }
 
 extern "C" int qtts_dev_kv_dtype(const qtts_dev_t *dv) { return dv ? dv->kv_want : -1; }
+
+extern "C" int qtts_dev_set_codec_precision(qtts_dev_t *dv, int precision) {
+    if (!dv || (precision != 0 && precision != 1)) return -1;
+    dv->codec.prec = precision;   // (read by the next stateless decode and the next stream begin)
+    return 0;
+}
+
+extern "C" int qtts_dev_codec_precision(const qtts_dev_t *dv) { return dv ? dv->codec.prec : -1; }
 
 extern "C" int qtts_dev_get_kv(qtts_dev_t *dv, int layer, int b, int pos0, int n, float *k_host, float *v_host) {
     if (!dv || !dv->kc || !dv->vc || dv->nb < 1 || layer < 0 || layer >= dv->d.L || b < 0 || b >= dv->nb ||

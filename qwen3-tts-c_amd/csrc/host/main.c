@@ -63,6 +63,8 @@ static void usage(const char *prog) {
             "                      every slot is streamed through the multi-stream codec)\n"
             "  --kv-cache fp32|bf16 (talker KV cache elements, default fp32; bf16 halves the cache,\n"
             "                      codes then no longer bit-exact against the reference)\n"
+            "  --codec exact|bf16 (vocoder conv arithmetic, default exact; bf16 rounds conv weights and inputs to\n"
+            "                      bf16, one matrix instruction per product instead of six; codes unchanged)\n"
             "  --force-codes <file>  continue on these codes, 16 ints per frame as --ref-codes reads them\n"
             "                      (-1: leave that draw free; later frames are free), qwen_tts_force_codes\n"
             "  --dump-drawn <file> write the id the sampler itself drew at every draw in that format\n"
@@ -248,6 +250,7 @@ static int stdin_feed(qwen_tts_feed_t *feed, int wait, void *user) {
 int main(int argc, char **argv) {
     const char *dir = NULL, *ids = NULL, *ids_file = NULL, *spk = NULL, *lang = NULL, *out = "output.wav";
     int verbose = 0, runs = 1, warmup = 0, device = -1, batch = 1, stream_chunk = 0, non_streaming = 0;
+    int codec_prec = -1; /* --codec: -1 = the library's default ($QTTS_HIP_CODEC or exact) */
     int kv_cache = -1;   /* --kv-cache: -1 = the library's default ($QTTS_HIP_KV or fp32) */
     const char *ref_codes_file = NULL, *ref_text = NULL, *xvec_file = NULL, *text = NULL, *ref_audio = NULL;
     int print_ids = 0, xvec_only = 0, stdin_ids = 0;
@@ -294,6 +297,12 @@ int main(int argc, char **argv) {
             if (!strcmp(v, "bf16")) kv_cache = QWEN_TTS_KV_BF16;
             else if (!strcmp(v, "fp32")) kv_cache = QWEN_TTS_KV_F32;
             else { fprintf(stderr, "Error: --kv-cache takes fp32 or bf16\n\n"); usage(argv[0]); return 1; }
+        }
+        else if (ARG("--codec")) {
+            const char *v = argv[++i];
+            if (!strcmp(v, "bf16")) codec_prec = QWEN_TTS_CODEC_BF16;
+            else if (!strcmp(v, "exact")) codec_prec = QWEN_TTS_CODEC_EXACT;
+            else { fprintf(stderr, "Error: --codec takes exact or bf16\n\n"); usage(argv[0]); return 1; }
         }
         else if (ARG("--ref-codes")) ref_codes_file = argv[++i];
         else if (ARG("--force-codes")) force_file = argv[++i];
@@ -433,6 +442,11 @@ int main(int argc, char **argv) {
     }
     if (kv_cache >= 0 && qwen_tts_set_kv_cache_dtype(ctx, kv_cache) != 0) {
         fprintf(stderr, "Error: cannot select the KV cache type\n");
+        qwen_tts_free(ctx); free(ref_codes); free(xvec); free(file_ids);
+        return 1;
+    }
+    if (codec_prec >= 0 && qwen_tts_set_codec_precision(ctx, codec_prec) != 0) {
+        fprintf(stderr, "Error: cannot select the codec precision\n");
         qwen_tts_free(ctx); free(ref_codes); free(xvec); free(file_ids);
         return 1;
     }
