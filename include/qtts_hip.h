@@ -106,6 +106,16 @@ int qtts_dev_kv_dtype(const qtts_dev_t *dev);
  * at begin.  -1 on a bad value. */
 int qtts_dev_set_codec_precision(qtts_dev_t *dev, int precision);
 int qtts_dev_codec_precision(const qtts_dev_t *dev);
+/* Precision of the codec's linears (transformer q/k/v/o and MLP, ConvNeXt
+ * pointwise layers), a switch of its own beside the conv one: 0 exact
+ * (default, or $QTTS_HIP_CODEC_LIN at creation), 1 one bf16 plane per operand
+ * (k_xlinh on every linear it covers, whatever the row count; sums, epilogues,
+ * RVQ, attention, norms and state fp32).  The first 1 makes the weights' bf16
+ * twins (2 bytes per element, counted by qtts_dev_bytes(dev, 0) from then on).
+ * Read by the next stateless decode; a codec stream or multi-stream latches it
+ * at begin.  -1 on a bad value. */
+int qtts_dev_set_codec_linear_precision(qtts_dev_t *dev, int precision);
+int qtts_dev_codec_linear_precision(const qtts_dev_t *dev);
 /* Diagnostics: talker cache rows [pos0, pos0 + n) of layer `layer`, slot b,
  * to the host as fp32 [n][KV*HD] each (bf16 widened exactly; k_host or v_host
  * may be NULL).  Waits for the context stream.  -1 out of range. */
@@ -762,6 +772,7 @@ enum {
     QTTS_XP_XGEMM = 5,    /* k_xgemm: generic */
     QTTS_XP_CONVH2 = 6,   /* k_convh<Kw,2>: bf16 one-plane conv, 64 x 128 tile (opt-in codec precision) */
     QTTS_XP_CONVH4 = 7,   /* k_convh<Kw,4>: 64 x 256 tile */
+    QTTS_XP_XLINH = 8,    /* k_xlinh: bf16 one-plane linear, any row count (opt-in codec linear precision) */
 };
 /* The dispatcher's plan for the contraction with a split workspace of
  * part_elems floats (0: none): which kernel (path_out) and how many splits

@@ -254,6 +254,19 @@ int qwen_tts_kv_cache_dtype(qwen_tts_ctx_t *ctx);
 #define QWEN_TTS_CODEC_BF16  1
 int qwen_tts_set_codec_precision(qwen_tts_ctx_t *ctx, int precision);
 int qwen_tts_codec_precision(qwen_tts_ctx_t *ctx);
+/* Arithmetic of the codec's linears: the transformer's q/k/v/o and MLP and the
+ * ConvNeXt pointwise layers.  A switch of its own, orthogonal to the conv one,
+ * with the same two values and the same semantics: QWEN_TTS_CODEC_BF16 rounds
+ * weights (a bf16 copy made the first time the mode is switched on, 2 bytes
+ * per element) and inputs to bf16, one matrix instruction per product block;
+ * sums, epilogues, RVQ, attention, norms and all carried state stay fp32, the
+ * codes are untouched.  A row's result does not depend on how many rows the
+ * call holds, so a streamed push and a stateless decode round alike.  -1 on a
+ * bad value; read per stateless decode, latched by a stream at its begin;
+ * snapshots restore into either mode.
+ * $QTTS_HIP_CODEC_LIN=bf16|exact sets the default of every ctx loaded after it. */
+int qwen_tts_set_codec_linear_precision(qwen_tts_ctx_t *ctx, int precision);
+int qwen_tts_codec_linear_precision(qwen_tts_ctx_t *ctx);
 /* Most lock-step slots of one ctx (qwen_tts_generate_batch, the slots of
  * qwen_tts_generate_queue, qwen_tts_generate_voice_clone_batch): up to 16 run
  * on the 16-row matrix-core batch kernels, 17..64 on the wide batch kernel. */

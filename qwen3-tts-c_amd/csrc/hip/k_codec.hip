@@ -833,6 +833,13 @@ static bool xlin_ok(const XGemm &g) {
            g.lda % 4 == 0 && g.ldb % 4 == 0 && ((uintptr_t)g.A & 15) == 0 && ((uintptr_t)g.B & 15) == 0;
 }
 
+// k_xlinh (k_xlinh.hip) covers a linear whose weight has a bf16 twin: N in
+// whole 16s, K in whole 32s, 16-B loads.  Nothing here looks at M.
+static bool xlinh_ok(const XGemm &g) {
+    return g.Bh && g.bmode == XB_WT && (g.amode == XA_ROWS || g.amode == XA_TRANS) && g.N % 16 == 0 && g.K % 32 == 0 &&
+           ((uintptr_t)g.Bh & 15) == 0 && (g.amode == XA_TRANS || (g.lda % 4 == 0 && ((uintptr_t)g.A & 15) == 0));
+}
+
 // k_xlin's split-K where the tiles would not fill the chip: >= 1 stage each,
 // partials within the workspace
 static int xlin_splits(const XGemm &g) {
@@ -882,7 +889,10 @@ struct XPlan {
 static XPlan xg_plan(const XGemm &g) {
     static const bool xl_on = [] { const char *e = getenv("QTTS_HIP_XLIN"); return !(e && !atoi(e)); }();
     XPlan p;
-    if (xl_on && xlin_ok(g)) {
+    if (g.precl && xlinh_ok(g)) {
+        // the opt-in bf16 linear precision: every covered linear, whatever M; splits stays 1
+        p.path = QTTS_XP_XLINH;
+    } else if (xl_on && xlin_ok(g)) {
         p.path = QTTS_XP_XLIN;
         p.splits = xlin_splits(g);
     } else if (xgemv_ok(g)) {
@@ -916,6 +926,7 @@ static bool xg_plan_forced(const XGemm &g, int path, XPlan *p) {
             return path == QTTS_XP_CONV || conv_path(g, p->splits) != QTTS_XP_CONV;
         case QTTS_XP_XLIN: p->splits = xlin_splits(g); return xlin_ok(g);
         case QTTS_XP_XGEMV: p->splits = xgemv_ks(g); return xgemv_ok(g);
+        case QTTS_XP_XLINH: p->splits = 1; return xlinh_ok(g);
         case QTTS_XP_XGEMM:
             p->splits = xgemm_splits(g);
             // (a transposed conv's all-phase conv form has no A operand: conv kernels only)
@@ -963,9 +974,16 @@ static int conv_launch(const XGemm &gin, const XPlan &p, hipStream_t st) {
 }
 
 static int xg_launch(const XGemm &g, const XPlan &p, hipStream_t st) {
-    const int nz = p.splits, ns = xg_nseg(g);
+    int nz = p.splits;
+    const int ns = xg_nseg(g);
     if (g.nseg > 1 && g.bmode == XB_WT) return -1;   // (linears stack their rows: seg_m)
     switch (p.path) {
+        case QTTS_XP_XLINH: {
+            // (not a split of the plan: the eight K phases are the kernel's arithmetic at every M; the
+            // launcher says whether it left their partials to k_xg_reduce or summed them in registers)
+            nz = qtts_xlinh_launch(g, st);
+            break;
+        }
         case QTTS_XP_XLIN: {
             hipLaunchKernelGGL(k_xlin, dim3(g.N / 64, (g.M + 63) / 64, nz), dim3(256), 0, st, g);
             break;
@@ -1063,6 +1081,8 @@ void codec_destroy(CodecModel *m) {
     m->w.clear();
     for (auto &kv : m->wt) hipFree(kv.second);
     m->wt.clear();
+    for (auto &kv : m->wh) hipFree(kv.second);
+    m->wh.clear();
     if (m->cb) hipFree(m->cb);
     m->cb = nullptr;
 }
@@ -1187,6 +1207,53 @@ int codec_finalize(CodecModel *m) {
         fprintf(stderr, "Error: codec requires codebook_dim == latent_dim/2 (got %d, %d)\n", d.ccbdim, d.clat);
         return -1;
     }
+    return 0;
+}
+
+// The bf16 twins of exactly the weights net_transformer and net_decode hand to
+// the linear planner, made once, the first time the bf16 linear precision is
+// on (the setter, or the first decode / begin under $QTTS_HIP_CODEC_LIN); a
+// weight k_xlinh would not cover (xlinh_ok's N and K) gets none and keeps its
+// exact kernel.  2 bytes per element beside the weight's 4.
+int codec_lin_twins(CodecModel *m) {
+    if (!m->wh.empty()) return 0;
+    const std::string P = "decoder.pre_transformer.";
+    std::vector<std::string> names = {P + "input_proj.weight", P + "output_proj.weight"};
+    for (int l = 0; l < m->d.clayers; ++l)
+        for (const char *s : {"self_attn.q_proj.weight", "self_attn.k_proj.weight", "self_attn.v_proj.weight",
+                              "self_attn.o_proj.weight", "mlp.gate_proj.weight", "mlp.up_proj.weight",
+                              "mlp.down_proj.weight"})
+            names.push_back(P + "layers." + std::to_string(l) + "." + s);
+    for (int s = 0; s < 2; ++s)
+        for (const char *t : {"1.pwconv1.weight", "1.pwconv2.weight"})
+            names.push_back("decoder.upsample." + std::to_string(s) + "." + t);
+    // all or none: the twins are collected here and handed to the model only when every one
+    // exists, so a failure part-way frees what was made and the next call starts over
+    std::map<const float *, unsigned short *> made;
+    size_t bytes = 0;
+    bool ok = true;
+    for (auto &nm : names) {
+        const float *w = cw(m, nm);
+        auto sh = m->shape.find(nm);
+        if (!w || sh == m->shape.end() || sh->second.empty()) { ok = false; break; }
+        size_t cnt = 1;
+        for (int64_t v : sh->second) cnt *= (size_t)v;
+        const int N = (int)sh->second[0], K = (int)(cnt / (size_t)N);
+        if (N % 16 || K % 32 || made.count(w)) continue;
+        unsigned short *h = nullptr;
+        if (hipMalloc(&h, cnt * 2) != hipSuccess) { ok = false; break; }
+        qtts_xlinh_twin(w, K, N, K, h, m->st);
+        made[w] = h;
+        bytes += cnt * 2;
+    }
+    if (ok && hipGetLastError() != hipSuccess) ok = false;
+    if (!ok) {
+        hipStreamSynchronize(m->st);
+        for (auto &kv : made) hipFree(kv.second);
+        return -1;
+    }
+    m->wh = made;
+    m->wbytes += bytes;
     return 0;
 }
 
@@ -1404,6 +1471,7 @@ struct Place {
     CodecModel *m = nullptr;
     int n = 1;                       // planes (streams) a launch covers
     int prec = 0;                    // the convs' XGemm::prec: the model's (one-shot decode) or the stream's latched one
+    int precl = 0;                   // the linears' XGemm::precl, from the same two places
     int hm = 0;                      // left margin (columns) of every row; 0: nothing is carried, nothing left of column 0
     float *A = nullptr, *B = nullptr, *Cb = nullptr, *D = nullptr;   // activations; A and B start past the margin
     float *tx = nullptr, *txn = nullptr, *tq = nullptr, *tatt = nullptr, *tg = nullptr, *tu = nullptr;  // [n * T] rows
@@ -1428,6 +1496,16 @@ struct Place {
     // the plane axis of a conv form / of a linear form's plane-laid operands (seg_m columns a plane, C channels)
     virtual void planes(XGemm &, int, int) {}
     virtual void rows(XGemm &, int, int) {}
+    // a linear of the network: its precision and, in bf16, its weight's twin (a covered shape without one is an error)
+    int lin(XGemm g) {
+        if (precl) {
+            auto it = m->wh.find(g.B);
+            g.precl = precl;
+            g.Bh = it == m->wh.end() ? nullptr : it->second;
+            if (!g.Bh && g.N % 16 == 0 && g.K % 32 == 0) return -1;
+        }
+        return xgm(m, g, m->st);
+    }
     virtual void mark(int) {}
     virtual void rvq(const int *codes, const float *ps, const float *pa, int T, int ldo, float *out) {
         const qtts_dims_t &d = m->d;
@@ -1529,16 +1607,16 @@ static int net_transformer(Place &p, const float *pc, int ldp, int T, float *out
     g.bias = cw(m, P + "input_proj.bias");
     g.emode = g.bias ? XE_BIAS_N : XE_STORE;
     p.rows(g, T, lat);
-    KCK(xgm(m, g, st));
+    KCK(p.lin(g));
     p.layers_begin(T);
     for (int l = 0; l < d.clayers; ++l) {
         const std::string q = P + "layers." + std::to_string(l) + ".";
         const LayerKV r = p.layer(l, T);
         hipLaunchKernelGGL(k_rms_rows, dim3(M), dim3(256), 0, st, p.tx, hid, cw(m, q + "input_layernorm.weight"),
                            d.ceps, p.txn);
-        KCK(xgm(m, lin(p.txn, M, hid, cw(m, q + "self_attn.q_proj.weight"), hid, r.q, XE_STORE), st));
-        KCK(xgm(m, lin(p.txn, M, hid, cw(m, q + "self_attn.k_proj.weight"), kvd, r.k, XE_STORE), st));
-        KCK(xgm(m, lin(p.txn, M, hid, cw(m, q + "self_attn.v_proj.weight"), kvd, r.v, XE_STORE), st));
+        KCK(p.lin(lin(p.txn, M, hid, cw(m, q + "self_attn.q_proj.weight"), hid, r.q, XE_STORE)));
+        KCK(p.lin(lin(p.txn, M, hid, cw(m, q + "self_attn.k_proj.weight"), kvd, r.k, XE_STORE)));
+        KCK(p.lin(lin(p.txn, M, hid, cw(m, q + "self_attn.v_proj.weight"), kvd, r.v, XE_STORE)));
         p.rope(r, T);
         AttnArgs a;
         a.mode = 1; a.qkv = r.q; a.ld_qkv = hid; a.kc = r.kc; a.vc = r.vc; a.NH = nh; a.KV = nkv; a.HD = hd;
@@ -1549,18 +1627,18 @@ static int net_transformer(Place &p, const float *pc, int ldp, int T, float *out
         if (!ls1) return -1;
         XGemm o = lin(p.tatt, M, hid, cw(m, q + "self_attn.o_proj.weight"), hid, p.tx, XE_SCALE_RESID_N);
         o.vec = ls1;
-        KCK(xgm(m, o, st));
+        KCK(p.lin(o));
         hipLaunchKernelGGL(k_rms_rows, dim3(M), dim3(256), 0, st, p.tx, hid,
                            cw(m, q + "post_attention_layernorm.weight"), d.ceps, p.txn);
-        KCK(xgm(m, lin(p.txn, M, hid, cw(m, q + "mlp.gate_proj.weight"), I, p.tg, XE_STORE), st));
+        KCK(p.lin(lin(p.txn, M, hid, cw(m, q + "mlp.gate_proj.weight"), I, p.tg, XE_STORE)));
         XGemm u = lin(p.txn, M, hid, cw(m, q + "mlp.up_proj.weight"), I, p.tu, XE_SILU_MUL);
         u.aux = p.tg; u.ldaux = I;
-        KCK(xgm(m, u, st));
+        KCK(p.lin(u));
         const float *ls2 = cw(m, q + "mlp_layer_scale.scale");
         if (!ls2) return -1;
         XGemm dn = lin(p.tu, M, I, cw(m, q + "mlp.down_proj.weight"), hid, p.tx, XE_SCALE_RESID_N);
         dn.vec = ls2;
-        KCK(xgm(m, dn, st));
+        KCK(p.lin(dn));
         p.layer_end(r, T);
     }
     p.layers_end(T);
@@ -1575,7 +1653,7 @@ static int net_transformer(Place &p, const float *pc, int ldp, int T, float *out
     og.ldc = ldo;
     p.rows(og, T, lat);
     if (!og.bias) return -1;
-    return xgm(m, og, st);
+    return p.lin(og);
 }
 
 // T frames of every plane of `p`, all of it enqueued on m->st; *wav: the
@@ -1618,13 +1696,13 @@ static int net_decode(Place &p, const int *codes, int T, float **wav_out, int *L
         p.ln_t(Cb, L, lat, cw(m, q + "1.norm.weight"), cw(m, q + "1.norm.bias"), D);
         XGemm g1 = lin(D, n * L, lat, cw(m, q + "1.pwconv1.weight"), 4 * lat, Cb, XE_BIAS_N_GELU);
         g1.bias = cw(m, q + "1.pwconv1.bias");
-        NCK(xgm(m, g1, st));
+        NCK(p.lin(g1));
         XGemm g2 = lin(Cb, n * L, 4 * lat, cw(m, q + "1.pwconv2.weight"), lat, cur, XE_BIAS_GAMMA_RES_T);
         g2.bias = cw(m, q + "1.pwconv2.bias");
         g2.vec = cw(m, q + "1.gamma");
         g2.res = cur; g2.ldres = ld; g2.ldc = ld;
         p.rows(g2, L, lat);
-        NCK(xgm(m, g2, st));
+        NCK(p.lin(g2));
     }
     p.mark(4);
     // 5. vocoder
@@ -1671,6 +1749,7 @@ struct FullPlace : Place {
     explicit FullPlace(CodecModel *cm) {
         take(cm, *cm, 0);
         prec = cm->prec;
+        precl = cm->precl;
         rvq_s = B; rvq_a = Cb;
     }
     void mark(int i) override { if (m->timing) hipEventRecord(m->tev[i], m->st); }
@@ -1684,7 +1763,7 @@ struct FullPlace : Place {
 // the whole decode enqueued on m->st; the clamped waveform stays in m's
 // scratch (*wav, *L samples) until the next use of m
 static int codec_decode_enqueue(CodecModel *m, const int *codes, int T, float **wav_out, int *L_out) {
-    if (ensure_codec_state(m, T)) return -1;
+    if (ensure_codec_state(m, T) || (m->precl && codec_lin_twins(m))) return -1;
     m->timed = false;
     if (m->timing && !m->tev[0])
         for (hipEvent_t &e : m->tev)
@@ -1732,6 +1811,8 @@ static void lane_sync_weights(CodecModel *m, CodecModel *ln) {
     ln->w = m->w;
     ln->wt = m->wt;
     ln->prec = m->prec;
+    ln->precl = m->precl;
+    ln->wh = m->wh;
     ln->timing = false;
 }
 
@@ -1747,6 +1828,7 @@ CodecModel *codec_lane_new(CodecModel *m, hipStream_t st) {
 void codec_lane_delete(CodecModel *ln) {
     if (!ln) return;
     ln->wt.clear();
+    ln->wh.clear();
     ln->w.clear();
     codec_free_state(ln);
     delete ln;
@@ -1756,6 +1838,7 @@ int codec_decode_many(CodecModel *m, CodecModel *const *lanes, int nl, int n, co
                       const int *T, float *dwav, const size_t *dwav_off, int *out_samples) {
     if (nl < 1 || n < 0) return -1;
     if (nl > n) nl = n;
+    if (m->precl && codec_lin_twins(m)) return -1;   // (before the lanes take m's twins over)
     for (int k = 1; k < nl; ++k) lane_sync_weights(m, lanes[k]);
     hipEvent_t ready = nullptr;
     if (hipEventCreateWithFlags(&ready, hipEventDisableTiming) != hipSuccess) return -1;
@@ -1901,6 +1984,7 @@ extern "C" int qtts_hip_xgemm_plan(const qtts_xgemm_desc_t *d, size_t part_elems
         if (tconv_plan(g, force_path, &as_conv, &p)) return 1;
     } else {
         if (g.bmode == XB_CONV) g.wt = (const float *)16;   // the relayout the run makes
+        if (force_path == QTTS_XP_XLINH) g.Bh = (const unsigned short *)16;   // and the twin
         if (force_path < 0) p = xg_plan(g);
         else if (!xg_plan_forced(g, force_path, &p)) return 1;
     }
@@ -1944,6 +2028,14 @@ static int xcase_run(const qtts_xgemm_desc_t *d, int nseg, int seg_ldb, int seg_
                 wt_planes(t, cnt, st);
                 dummy.wt["xcase"] = t;
                 g.wt = t;
+            }
+        } else if (force_path == QTTS_XP_XLINH) {
+            unsigned short *h = nullptr;
+            if (hipMalloc(&h, (size_t)g.N * g.K * 2) != hipSuccess) rc = -1;
+            if (!rc) {
+                qtts_xlinh_twin(g.B, g.ldb, g.N, g.K, h, st);
+                dummy.wt["xcase"] = reinterpret_cast<float *>(h);
+                g.Bh = h;
             }
         }
         if (!rc) rc = xgm(&dummy, g, st, force_path, &ran);
@@ -2034,6 +2126,7 @@ struct StreamPlace : Place {
     explicit StreamPlace(CodecModel *cm) : S(cm->cs) {
         take(cm, S, S.hm);
         prec = S.prec;
+        precl = S.precl;
         rvq_s = S.rvq_s; rvq_a = S.rvq_a;
         const size_t row0 = (size_t)S.pos0 * (m->d.chid / m->d.cheads);   // the table continues at pos0
         rope_cos += row0; rope_sin += row0;
@@ -2082,7 +2175,7 @@ int codec_stream_begin(CodecModel *m, int max_frames, int chunk) {
     // the codec GEMMs' split-K workspace belongs to the (non-streaming) codec
     // state, which the decode state's re-allocation frees (free_state ->
     // codec_free_state): re-create it before a stream reuses its own buffers
-    if (ensure_codec_state(m, 1)) return -1;
+    if (ensure_codec_state(m, 1) || (m->precl && codec_lin_twins(m))) return -1;
     if (S0.active && max_frames + S0.tc <= S0.rope_cap && S0.tc >= tc_want) {
         // reuse the buffers: only the carried state restarts (zero histories =
         // the causal left padding, no K/V rows, position 0), on the codec stream
@@ -2093,6 +2186,7 @@ int codec_stream_begin(CodecModel *m, int max_frames, int chunk) {
         S0.pos0 = 0;
         S0.hl = 0;
         S0.prec = m->prec;
+        S0.precl = m->precl;
         return 0;
     }
     codec_stream_free(m);
@@ -2100,6 +2194,7 @@ int codec_stream_begin(CodecModel *m, int max_frames, int chunk) {
     CodecStream &S = m->cs;
     S.tc = tc_want;
     S.prec = m->prec;
+    S.precl = m->precl;
     const int hm = S.hm, tc = S.tc;
     auto salloc = [&](size_t bytes) { return dev_alloc(S.allocs, " stream", bytes, true); };
     // activation buffers: largest C x (hm + L) over the stages at tc frames
@@ -2405,6 +2500,7 @@ struct MsPlace : Place {
         take(cm, S, S.hm);   // (the whole RoPE table: every row rotates by its own stream's position)
         n = n_;
         prec = S.prec;
+        precl = S.precl;
         rvq_s = S.rvq_s; rvq_a = S.rvq_a;
     }
     int hist(int slot, int C, int H, float *x, int ldx, int L, bool out) override {
@@ -2514,7 +2610,7 @@ int codec_mstream_begin(CodecModel *m, int n_streams, int max_frames, int chunk)
     // the split-K workspace belongs to the codec state (codec_stream_begin has
     // the story): re-create it first; a re-allocation of that state frees this
     // one too, so look at it only afterwards
-    if (ensure_codec_state(m, 1)) return -1;
+    if (ensure_codec_state(m, 1) || (m->precl && codec_lin_twins(m))) return -1;
     const int tc = ms_chunk(d, n_streams, chunk, m->ms.hm);
     CodecMStream &S0 = m->ms;
     if (S0.active && S0.ns == n_streams && S0.tc == tc && max_frames + tc <= S0.rope_cap) {
@@ -2527,6 +2623,7 @@ int codec_mstream_begin(CodecModel *m, int n_streams, int max_frames, int chunk)
         std::fill(S0.hl.begin(), S0.hl.end(), 0);
         S0.max_frames = max_frames;
         S0.prec = m->prec;
+        S0.precl = m->precl;
         return 0;
     }
     if (hipStreamSynchronize(m->st) != hipSuccess) return -1;
@@ -2536,6 +2633,7 @@ int codec_mstream_begin(CodecModel *m, int n_streams, int max_frames, int chunk)
     S.tc = tc;
     S.max_frames = max_frames;
     S.prec = m->prec;
+    S.precl = m->precl;
     S.pos0.assign(n_streams, 0);
     S.hl.assign(n_streams, 0);
     const int hm = S.hm, ns = n_streams;

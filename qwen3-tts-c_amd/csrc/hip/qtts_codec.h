@@ -20,6 +20,7 @@ struct CodecStream {
     int tc = 0;                // max frames per internal chunk
     int hm = 64;               // left margin (columns) of every channel-major buffer
     int prec = 0;              // the model's codec precision at begin: a stream keeps it until its next begin
+    int precl = 0;             // the model's codec linear precision at begin, kept alike
     std::vector<float *> hist; // history slots [C][H]
     std::vector<int> hist_c, hist_h;
     std::vector<float *> kc, vc;  // transformer layer caches [(win-1) + tc][kvd]
@@ -47,6 +48,7 @@ struct CodecMStream {
     int tc = 0;                    // frames per internal pass (<= 16, fewer where ns planes would pass the scratch budget)
     int hm = 64;                   // left margin (columns) of every plane's rows
     int prec = 0;                  // the model's codec precision at begin, kept by every push until the next begin
+    int precl = 0;                 // the model's codec linear precision at begin, kept alike
     int max_frames = 0;
     std::vector<int> pos0, hl;     // per stream: frames decoded, valid K/V history rows
     std::vector<float *> hist;     // slot -> [ns][C][H]
@@ -111,6 +113,11 @@ struct CodecModel {
     // codec precision (QWEN_TTS_CODEC_EXACT 0 / _BF16 1): the convs' XGemm::prec.
     // The stateless decode reads it per call; a stream latches it at begin.
     int prec = 0;
+    // codec linear precision (the same values): the linears' XGemm::precl, read and latched as prec is.
+    // wh: the bf16 twins of the weights that reach the linear planner, by fp32 pointer, made the
+    // first time the mode is on (codec_lin_twins); empty and unallocated in the default mode
+    int precl = 0;
+    std::map<const float *, unsigned short *> wh;
     size_t wbytes = 0;
     // scratch (grown on demand)
     std::vector<void *> scratch;
@@ -141,6 +148,8 @@ size_t codec_weight_bytes(const CodecModel *m);
 int codec_put_tensor(CodecModel *m, const std::string &name, const void *host, int dtype, const int64_t *shape,
                      int ndim, size_t n);
 int codec_finalize(CodecModel *m);
+// the bf16 twins of the linear weights (net_decode / net_transformer), once; 0 or -1
+int codec_lin_twins(CodecModel *m);
 // codes: device int32 [T][cq] (time-major).  Returns malloc'd host audio.
 float *codec_decode(CodecModel *m, const int *codes_dev, int T, int *out_samples);
 // independent decodes side by side: job i (device codes[i], T[i] frames) on
@@ -252,7 +261,15 @@ struct XGemm {
     // operand on every shape k_convb covers (then k_convh, whatever the tile
     // count); every other kernel ignores it
     int prec = 0;
+    // linears (XB_WT): 1 sends every form k_xlinh covers to it, whatever M, reading W from its
+    // bf16 twin Bh (compact [N][K], the weight rounded to nearest even); 0 (the default): today's plan
+    int precl = 0;
+    const unsigned short *Bh = nullptr;
 };
 int qtts_xgemm(const XGemm &g, hipStream_t st);
 // k_convh.hip: k_convh<g.Kw, wn> on `grid` (k_convb's grid for the same wn; g.kz set)
 void qtts_convh_launch(const XGemm &g, int wn, dim3 grid, hipStream_t st);
+// k_xlinh.hip: the one-plane bf16 linear on g (XB_WT, g.Bh set; g.part: the workspace its phase
+// kernel may use), returning how many partials k_xg_reduce has to sum (1: none); and the kernel that makes a twin
+int qtts_xlinh_launch(const XGemm &g, hipStream_t st);
+void qtts_xlinh_twin(const float *w, int ldb, int N, int K, unsigned short *out, hipStream_t st);

@@ -347,6 +347,12 @@ extern "C" qtts_dev_t *qtts_dev_create(const qtts_dims_t *dims, int device) {
         if (!strcmp(cpr, "bf16")) dv->codec.prec = 1;
         else if (strcmp(cpr, "exact")) fprintf(stderr, "qtts: QTTS_HIP_CODEC=%s ignored (bf16 or exact)\n", cpr);
     }
+    // QTTS_HIP_CODEC_LIN=bf16|exact: the codec linears' precision (default exact; the twins come with the first use)
+    const char *clp = getenv("QTTS_HIP_CODEC_LIN");
+    if (clp && *clp) {
+        if (!strcmp(clp, "bf16")) dv->codec.precl = 1;
+        else if (strcmp(clp, "exact")) fprintf(stderr, "qtts: QTTS_HIP_CODEC_LIN=%s ignored (bf16 or exact)\n", clp);
+    }
     dv->enc.st = dv->st;
     dv->enc.device = device;
     return dv;
@@ -432,6 +438,16 @@ extern "C" int qtts_dev_set_codec_precision(qtts_dev_t *dv, int precision) {
 }
 
 extern "C" int qtts_dev_codec_precision(const qtts_dev_t *dv) { return dv ? dv->codec.prec : -1; }
+
+extern "C" int qtts_dev_set_codec_linear_precision(qtts_dev_t *dv, int precision) {
+    if (!dv || (precision != 0 && precision != 1)) return -1;
+    // the first switch to bf16 on a loaded model makes the weights' twins (before loading: the first decode does)
+    if (precision && !dv->codec.w.empty() && codec_lin_twins(&dv->codec)) return -1;
+    dv->codec.precl = precision;
+    return 0;
+}
+
+extern "C" int qtts_dev_codec_linear_precision(const qtts_dev_t *dv) { return dv ? dv->codec.precl : -1; }
 
 extern "C" int qtts_dev_get_kv(qtts_dev_t *dv, int layer, int b, int pos0, int n, float *k_host, float *v_host) {
     if (!dv || !dv->kc || !dv->vc || dv->nb < 1 || layer < 0 || layer >= dv->d.L || b < 0 || b >= dv->nb ||

@@ -106,7 +106,8 @@ EXPORTS = [
     "qtts_dev_retire", "qtts_dev_frame_stops", "qtts_dev_move_slot", "qtts_dev_set_rows",
     "qwen_tts_set_kv_cache_dtype", "qwen_tts_kv_cache_dtype", "qtts_dev_set_kv_dtype", "qtts_dev_kv_dtype",
     "qwen_tts_set_codec_precision", "qwen_tts_codec_precision", "qtts_dev_set_codec_precision",
-    "qtts_dev_codec_precision",
+    "qtts_dev_codec_precision", "qwen_tts_set_codec_linear_precision", "qwen_tts_codec_linear_precision",
+    "qtts_dev_set_codec_linear_precision", "qtts_dev_codec_linear_precision",
     "qtts_dev_get_kv", "qtts_dev_get_attn", "qtts_hip_attn_decode",
     "qtts_hip_attn_decode_ex", "qtts_hip_attn_cached", "qtts_hip_attn_o",
     "qtts_hip_attn_o_pair", "qtts_hip_resident_matvec_rows_bf16", "qtts_hip_st_pair_passes",
@@ -295,9 +296,9 @@ XA_ROWS, XA_TRANS, XA_TCONV_W = 0, 1, 2
 XB_WT, XB_CONV, XB_TCONV = 0, 1, 2
 (XE_STORE, XE_BIAS_N, XE_BIAS_N_GELU, XE_SILU_MUL, XE_SCALE_RESID_N, XE_BIAS_T, XE_BIAS_GAMMA_RES_T, XE_BIAS_M,
  XE_BIAS_M_RES, XE_BIAS_M_SNAKE) = range(10)
-XP_CONVB2, XP_CONVB4, XP_CONV, XP_XLIN, XP_XGEMV, XP_XGEMM, XP_CONVH2, XP_CONVH4 = range(8)
+XP_CONVB2, XP_CONVB4, XP_CONV, XP_XLIN, XP_XGEMV, XP_XGEMM, XP_CONVH2, XP_CONVH4, XP_XLINH = range(9)
 XP_NAMES = ["k_convb<Kw,2>", "k_convb<Kw,4>", "k_conv<Kw>", "k_xlin", "k_xgemv", "k_xgemm", "k_convh<Kw,2>",
-            "k_convh<Kw,4>"]
+            "k_convh<Kw,4>", "k_xlinh"]
 
 MAX_TAPS = 8   # taps per run (qwen_tts_tap_draw)
 
@@ -537,6 +538,15 @@ def lib():
         L.qtts_dev_set_codec_precision.argtypes = [C.c_void_p, C.c_int]
         L.qtts_dev_codec_precision.restype = C.c_int
         L.qtts_dev_codec_precision.argtypes = [C.c_void_p]
+    if hasattr(L, "qwen_tts_set_codec_linear_precision"):   # (nor a codec linear precision)
+        L.qwen_tts_set_codec_linear_precision.restype = C.c_int
+        L.qwen_tts_set_codec_linear_precision.argtypes = [C.POINTER(Ctx), C.c_int]
+        L.qwen_tts_codec_linear_precision.restype = C.c_int
+        L.qwen_tts_codec_linear_precision.argtypes = [C.POINTER(Ctx)]
+        L.qtts_dev_set_codec_linear_precision.restype = C.c_int
+        L.qtts_dev_set_codec_linear_precision.argtypes = [C.c_void_p, C.c_int]
+        L.qtts_dev_codec_linear_precision.restype = C.c_int
+        L.qtts_dev_codec_linear_precision.argtypes = [C.c_void_p]
     L.qtts_dev_set_kv_dtype.restype = C.c_int
     L.qtts_dev_set_kv_dtype.argtypes = [C.c_void_p, C.c_int]
     L.qtts_dev_kv_dtype.restype = C.c_int
@@ -723,6 +733,19 @@ class QwenTTS:
 
     def codec_precision(self):
         return lib().qwen_tts_codec_precision(self.ctx)
+
+    def set_codec_linear_precision(self, precision):
+        """Arithmetic of the codec's linears (transformer, ConvNeXt pointwise)
+        from the next codec call (a live stream: its next begin) on: "exact" /
+        CODEC_EXACT (default) or "bf16" / CODEC_BF16 (one bf16 plane per operand
+        on k_xlinh; qwen_tts_set_codec_linear_precision).  Independent of
+        set_codec_precision."""
+        v = {"exact": CODEC_EXACT, "bf16": CODEC_BF16}.get(precision, precision)
+        if not isinstance(v, int) or lib().qwen_tts_set_codec_linear_precision(self.ctx, v) != 0:
+            raise ValueError(f"codec linear precision {precision!r} (exact or bf16)")
+
+    def codec_linear_precision(self):
+        return lib().qwen_tts_codec_linear_precision(self.ctx)
 
     def state_bytes(self):
         """device bytes of the generation state (qtts_dev_bytes(dev, 1))"""
