@@ -936,6 +936,54 @@ typedef struct {
  * (unknown op, a NULL operand the op needs, a size below 1 or outside the
  * limits above) or on a launch error. */
 int qtts_hip_enc_op(const qtts_enc_op_t *d, void *stream);
+/* One launch of one of the codec decoder's small kernels (k_codec.hip: the
+ * kernels between the contractions and the multi-stream placement kernels)
+ * through the launch helper the network uses.  in / out / n / s per op (device
+ * pointers; n streams of the push, sid / hl / pos0 / tv = int[n]; (0): the size
+ * may be 0):
+ *    0 k_rvq_sum        in codes [T][Q] (int), cb [Q][CB][vq]; out ss [vq][T], as; n T, Q, CB, vq (vq <= 1024)
+ *    1 k_rvq_proj       in ps [half][vq], pa, ss [vq][T], as; out [half][ldo]; n vq, half, T, ldo
+ *    2 k_rvq_sum_ms     in codes (int), coff (long long [n]), cb, tv; out ss [vq][n T], as; n ldc, t0 (0), T, n, Q, CB, vq
+ *    3 k_rvq_proj_ms    in ps, pa, ss, as; out [n] planes of [half][ldo]; n vq, half, T, n, ldo; s plane stride
+ *    4 k_dwconv         in x (column 0 of row 0), w [C][K], b or NULL; out y [C][ldy]; n ldx, H (0), C, L, K, ldy
+ *                       (H history columns are read left of column 0: tmin = -H)
+ *    5 k_dwconv_ms      as 4; n ldx, H (0), C, L, K, ldy, n; s x plane stride, y plane stride
+ *    6 k_ln_t           in x [C][ldx], w, b; out y [L][C]; n ldx, L, C; eps
+ *    7 k_ln_t_ms        in x, w, b; out y [n L][C]; n ldx, L, C, n; s x plane stride; eps
+ *    8 k_rms_rows       in x [M][D], w; out y; n M, D; eps
+ *    9 k_rope_rows      in cos [T][hd], sin; out x [T][ld] in place; n T, ld, nh, hd (hd even)
+ *   10 k_rope_kv_ms     in k [n T][kvd], v, cos, sin, sid, pos0, hl, tv; out q [n T][hid] in place, kc [streams][S][kvd], vc;
+ *                       n hid, nh, kvd, nkv, hd, T, n, S
+ *   11 k_ms_index       in sid, hl; out row_b [n T], pos (int); n n, T
+ *   12 k_clamp          out x in place; n count
+ *   13 k_copy2d         in src; out dst; n ldd, lds, rows, cols
+ *   14 k_clamp_ms       in x, tv; out y [n][L]; n L, spf, n; s x plane stride
+ *   15 k_hist_ms        in sid, tv; out hist [streams][C][H], x (column 0 of row 0 of plane 0); n ldx, C, H, mul, n,
+ *                       out (0: 0 slot -> margin, 1 the last H valid columns -> slot); s plane stride
+ *   16 k_kv_shift_ms    in sid, hl, tv; out kv [nl2][ns][S][kvd]; n ns, S, kvd, keepmax (<= S), n, nl2
+ *   17 k_hist_reset_ms  in base (float *[nslots]), elems (int[nslots]); n nslots, most (0), stream (0)
+ *   18 k_ms_state_save  in base (float *[nh + nkv]), elems, soff (int[nh + 1]); out snap;
+ *                       n nh (0), nkv (0), most (0), stream (0), kvn (0), kvpad (0; >= kvn, a multiple of 4)
+ *   19 k_ms_state_load  in base, elems, soff, snap; n as 18 */
+enum {
+    QTTS_CO_RVQ_SUM = 0, QTTS_CO_RVQ_PROJ, QTTS_CO_RVQ_SUM_MS, QTTS_CO_RVQ_PROJ_MS, QTTS_CO_DWCONV, QTTS_CO_DWCONV_MS,
+    QTTS_CO_LN_T, QTTS_CO_LN_T_MS, QTTS_CO_RMS_ROWS, QTTS_CO_ROPE_ROWS, QTTS_CO_ROPE_KV_MS, QTTS_CO_MS_INDEX,
+    QTTS_CO_CLAMP, QTTS_CO_COPY2D, QTTS_CO_CLAMP_MS, QTTS_CO_HIST_MS, QTTS_CO_KV_SHIFT_MS, QTTS_CO_HIST_RESET_MS,
+    QTTS_CO_MS_STATE_SAVE, QTTS_CO_MS_STATE_LOAD, QTTS_CO_COUNT
+};
+typedef struct {
+    int op;
+    const void *in[8];
+    void *out[3];
+    int n[8];
+    size_t s[2];
+    float eps;
+} qtts_codec_op_t;
+/* Returns 0 launched (not synchronised), -1 refused before any device call
+ * (unknown op, a NULL operand the op needs, a size below 1 or outside the
+ * limits above or the launch helper's: odd hd, rows shorter than their heads,
+ * a row stride below the row) or on a launch error. */
+int qtts_hip_codec_op(const qtts_codec_op_t *d, void *stream);
 /* The fp32 erff (fn 0) / expm1f (fn 1) k_econv's GELU epilogue and ELU
  * prologue call, elementwise over n values, for measuring them against float64. */
 int qtts_hip_enc_func(float *out_dev, const float *x_dev, size_t n, int fn, void *stream);

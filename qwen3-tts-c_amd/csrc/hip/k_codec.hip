@@ -766,6 +766,60 @@ __global__ void k_iota(int *p, int n, int zero) {
     if (i < n) p[i] = zero ? 0 : i;
 }
 
+// Launch helpers of the small codec kernels: the one place that holds the grid
+// and block of each, called by the network (Place, net_transformer, copy2d)
+// and by qtts_hip_codec_op, so a kernel-level test runs the launch the model
+// runs.  -1 and no launch for what the kernel cannot serve
+constexpr size_t kGridMax = 0x7fffffff;
+int launch_rvq_sum(hipStream_t st, const int *codes, int T, int Q, int CB, int vq, const float *cb, float *ss,
+                   float *as) {
+    if (T < 1 || Q < 1 || CB < 1 || vq < 1 || vq > 1024) return -1;   // (the block is vq rounded up to 64)
+    hipLaunchKernelGGL(k_rvq_sum, dim3(T), dim3(vq < 64 ? 64 : (vq + 63) / 64 * 64), 0, st, codes, T, Q, CB, vq, cb, ss,
+                       as);
+    return 0;
+}
+int launch_rvq_proj(hipStream_t st, const float *ps, const float *pa, const float *ss, const float *as, int vq, int half,
+                    int T, int ldo, float *out) {
+    if (vq < 1 || half < 1 || T < 1 || ldo < T || (size_t)half * T > kGridMax - 3) return -1;
+    hipLaunchKernelGGL(k_rvq_proj, dim3((half * T + 3) / 4), dim3(256), 0, st, ps, pa, ss, as, vq, half, T, ldo, out);
+    return 0;
+}
+// tmin <= 0: -tmin history columns are read left of every row
+int launch_dwconv(hipStream_t st, const float *x, int ldx, int tmin, const float *w, const float *b, int C, int L, int K,
+                  float *y, int ldy) {
+    if (C < 1 || L < 1 || K < 1 || tmin > 0 || ldx < L || ldy < L || ((size_t)C * L + 255) / 256 > kGridMax) return -1;
+    hipLaunchKernelGGL(k_dwconv, dim3((unsigned)(((size_t)C * L + 255) / 256)), dim3(256), 0, st, x, ldx, tmin, w, b, C,
+                       L, K, y, ldy);
+    return 0;
+}
+int launch_copy2d(hipStream_t st, float *dst, int ldd, const float *src, int lds, int rows, int cols) {
+    const size_t n = (size_t)rows * cols;
+    if (rows < 1 || cols < 1 || ldd < cols || lds < cols || (n + 255) / 256 > kGridMax) return -1;
+    hipLaunchKernelGGL(k_copy2d, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, dst, ldd, src, lds, rows, cols);
+    return 0;
+}
+int launch_ln_t(hipStream_t st, const float *x, int ldx, int L, int C, const float *w, const float *b, float eps,
+                float *y) {
+    if (L < 1 || C < 1 || ldx < L) return -1;
+    hipLaunchKernelGGL(k_ln_t, dim3(L), dim3(256), 0, st, x, ldx, C, w, b, eps, y);
+    return 0;
+}
+int launch_rms_rows(hipStream_t st, const float *x, int M, int D, const float *w, float eps, float *y) {
+    if (M < 1 || D < 1) return -1;
+    hipLaunchKernelGGL(k_rms_rows, dim3(M), dim3(256), 0, st, x, D, w, eps, y);
+    return 0;
+}
+int launch_rope_rows(hipStream_t st, float *x, int T, int ld, int nh, int hd, const float *cs, const float *sn) {
+    if (T < 1 || nh < 1 || hd < 2 || hd % 2 || ld < nh * hd) return -1;
+    hipLaunchKernelGGL(k_rope_rows, dim3(T), dim3(256), 0, st, x, ld, nh, hd, cs, sn);
+    return 0;
+}
+int launch_clamp(hipStream_t st, float *x, int n) {
+    if (n < 1 || n > 0x7fffffff - 255) return -1;
+    hipLaunchKernelGGL(k_clamp, dim3((n + 255) / 256), dim3(256), 0, st, x, n);
+    return 0;
+}
+
 }  // namespace
 
 // k_conv covers the conv when its re-laid weights are given, the channels
@@ -1507,33 +1561,28 @@ struct Place {
         return xgm(m, g, m->st);
     }
     virtual void mark(int) {}
-    virtual void rvq(const int *codes, const float *ps, const float *pa, int T, int ldo, float *out) {
+    virtual int rvq(const int *codes, const float *ps, const float *pa, int T, int ldo, float *out) {
         const qtts_dims_t &d = m->d;
         const int vq = d.ccbdim / 2, half = d.clat / 2;
-        hipLaunchKernelGGL(k_rvq_sum, dim3(T), dim3(vq < 64 ? 64 : (vq + 63) / 64 * 64), 0, m->st, codes, T, d.cq, d.ccb,
-                           vq, m->cb, rvq_s, rvq_a);
-        hipLaunchKernelGGL(k_rvq_proj, dim3((half * T + 3) / 4), dim3(256), 0, m->st, ps, pa, rvq_s, rvq_a, vq, half, T,
-                           ldo, out);
+        if (launch_rvq_sum(m->st, codes, T, d.cq, d.ccb, vq, m->cb, rvq_s, rvq_a)) return -1;
+        return launch_rvq_proj(m->st, ps, pa, rvq_s, rvq_a, vq, half, T, ldo, out);
     }
-    virtual void dwconv(const float *x, int ldx, const float *w, const float *b, int C, int L, int K, float *y) {
-        hipLaunchKernelGGL(k_dwconv, dim3((unsigned)(((size_t)C * L + 255) / 256)), dim3(256), 0, m->st, x, ldx,
-                           tmin(K - 1), w, b, C, L, K, y, L);
+    virtual int dwconv(const float *x, int ldx, const float *w, const float *b, int C, int L, int K, float *y) {
+        return launch_dwconv(m->st, x, ldx, tmin(K - 1), w, b, C, L, K, y, L);
     }
-    virtual void ln_t(const float *x, int L, int C, const float *w, const float *b, float *y) {
-        hipLaunchKernelGGL(k_ln_t, dim3(L), dim3(256), 0, m->st, x, L, C, w, b, 1e-6f, y);
+    virtual int ln_t(const float *x, int L, int C, const float *w, const float *b, float *y) {
+        return launch_ln_t(m->st, x, L, L, C, w, b, 1e-6f, y);
     }
-    virtual void clamp(float *wav, int, int L, int) {
-        hipLaunchKernelGGL(k_clamp, dim3((L + 255) / 256), dim3(256), 0, m->st, wav, L);
-    }
+    virtual int clamp(float *wav, int, int L, int) { return launch_clamp(m->st, wav, L); }
     // transformer: before / after the layers, a layer's rows, their rotation, what attention sees, after a layer
-    virtual void layers_begin(int) {}
-    virtual void layers_end(int) {}
+    virtual int layers_begin(int) { return 0; }
+    virtual int layers_end(int) { return 0; }
     virtual LayerKV layer(int l, int T) = 0;
-    virtual void rope(const LayerKV &r, int T) {
+    virtual int rope(const LayerKV &r, int T) {
         const qtts_dims_t &d = m->d;
         const int hid = d.chid, hd = hid / d.cheads;
-        hipLaunchKernelGGL(k_rope_rows, dim3(T), dim3(256), 0, m->st, r.q, hid, d.cheads, hd, rope_cos, rope_sin);
-        hipLaunchKernelGGL(k_rope_rows, dim3(T), dim3(256), 0, m->st, r.k, d.ckv * hd, d.ckv, hd, rope_cos, rope_sin);
+        if (launch_rope_rows(m->st, r.q, T, hid, d.cheads, hd, rope_cos, rope_sin)) return -1;
+        return launch_rope_rows(m->st, r.k, T, d.ckv * hd, d.ckv, hd, rope_cos, rope_sin);
     }
     virtual void attn_rows(AttnArgs &a, int T) = 0;   // S, pos, row_b
     virtual void layer_end(const LayerKV &, int) {}
@@ -1608,16 +1657,15 @@ static int net_transformer(Place &p, const float *pc, int ldp, int T, float *out
     g.emode = g.bias ? XE_BIAS_N : XE_STORE;
     p.rows(g, T, lat);
     KCK(p.lin(g));
-    p.layers_begin(T);
+    KCK(p.layers_begin(T));
     for (int l = 0; l < d.clayers; ++l) {
         const std::string q = P + "layers." + std::to_string(l) + ".";
         const LayerKV r = p.layer(l, T);
-        hipLaunchKernelGGL(k_rms_rows, dim3(M), dim3(256), 0, st, p.tx, hid, cw(m, q + "input_layernorm.weight"),
-                           d.ceps, p.txn);
+        KCK(launch_rms_rows(st, p.tx, M, hid, cw(m, q + "input_layernorm.weight"), d.ceps, p.txn));
         KCK(p.lin(lin(p.txn, M, hid, cw(m, q + "self_attn.q_proj.weight"), hid, r.q, XE_STORE)));
         KCK(p.lin(lin(p.txn, M, hid, cw(m, q + "self_attn.k_proj.weight"), kvd, r.k, XE_STORE)));
         KCK(p.lin(lin(p.txn, M, hid, cw(m, q + "self_attn.v_proj.weight"), kvd, r.v, XE_STORE)));
-        p.rope(r, T);
+        KCK(p.rope(r, T));
         AttnArgs a;
         a.mode = 1; a.qkv = r.q; a.ld_qkv = hid; a.kc = r.kc; a.vc = r.vc; a.NH = nh; a.KV = nkv; a.HD = hd;
         a.out = p.tatt; a.ld_out = hid; a.nrows = M; a.win = d.cwin;
@@ -1628,8 +1676,7 @@ static int net_transformer(Place &p, const float *pc, int ldp, int T, float *out
         XGemm o = lin(p.tatt, M, hid, cw(m, q + "self_attn.o_proj.weight"), hid, p.tx, XE_SCALE_RESID_N);
         o.vec = ls1;
         KCK(p.lin(o));
-        hipLaunchKernelGGL(k_rms_rows, dim3(M), dim3(256), 0, st, p.tx, hid,
-                           cw(m, q + "post_attention_layernorm.weight"), d.ceps, p.txn);
+        KCK(launch_rms_rows(st, p.tx, M, hid, cw(m, q + "post_attention_layernorm.weight"), d.ceps, p.txn));
         KCK(p.lin(lin(p.txn, M, hid, cw(m, q + "mlp.gate_proj.weight"), I, p.tg, XE_STORE)));
         XGemm u = lin(p.txn, M, hid, cw(m, q + "mlp.up_proj.weight"), I, p.tu, XE_SILU_MUL);
         u.aux = p.tg; u.ldaux = I;
@@ -1641,11 +1688,11 @@ static int net_transformer(Place &p, const float *pc, int ldp, int T, float *out
         KCK(p.lin(dn));
         p.layer_end(r, T);
     }
-    p.layers_end(T);
+    KCK(p.layers_end(T));
     const float *fn = cw(m, P + "norm.weight");
     const float *xin = p.tx;
     if (fn) {
-        hipLaunchKernelGGL(k_rms_rows, dim3(M), dim3(256), 0, st, p.tx, hid, fn, d.ceps, p.txn);
+        KCK(launch_rms_rows(st, p.tx, M, hid, fn, d.ceps, p.txn));
         xin = p.txn;
     }
     XGemm og = lin(xin, M, hid, cw(m, P + "output_proj.weight"), lat, out, XE_BIAS_T);
@@ -1667,8 +1714,8 @@ static int net_decode(Place &p, const int *codes, int T, float **wav_out, int *L
     int L = T, ld = p.ld(L), slot = 0;
     p.mark(0);
     // 1. RVQ dequantise -> A [half][T]
-    p.rvq(codes, cw(m, "decoder.quantizer.rvq_first.output_proj.weight"),
-          cw(m, "decoder.quantizer.rvq_rest.output_proj.weight"), T, ld, A);
+    NCK(p.rvq(codes, cw(m, "decoder.quantizer.rvq_first.output_proj.weight"),
+              cw(m, "decoder.quantizer.rvq_rest.output_proj.weight"), T, ld, A));
     p.mark(1);
     // 2. pre-conv k=3 -> B [lat][T]
     NCK(net_conv(p, slot, A, ld, d.ccbdim, L, "decoder.pre_conv.conv.weight", "decoder.pre_conv.conv.bias", lat, 3, 1,
@@ -1691,9 +1738,9 @@ static int net_decode(Place &p, const int *codes, int T, float **wav_out, int *L
         cur = up;
         // ConvNeXt: dwconv -> LN (time-major) -> pw1+GELU -> pw2*gamma (+res, channel-major)
         NCK(p.hist(slot, lat, 6, cur, ld, L, false));
-        p.dwconv(cur, ld, cw(m, q + "1.dwconv.conv.weight"), cw(m, q + "1.dwconv.conv.bias"), lat, L, 7, Cb);
+        NCK(p.dwconv(cur, ld, cw(m, q + "1.dwconv.conv.weight"), cw(m, q + "1.dwconv.conv.bias"), lat, L, 7, Cb));
         NCK(p.hist(slot++, lat, 6, cur, ld, L, true));
-        p.ln_t(Cb, L, lat, cw(m, q + "1.norm.weight"), cw(m, q + "1.norm.bias"), D);
+        NCK(p.ln_t(Cb, L, lat, cw(m, q + "1.norm.weight"), cw(m, q + "1.norm.bias"), D));
         XGemm g1 = lin(D, n * L, lat, cw(m, q + "1.pwconv1.weight"), 4 * lat, Cb, XE_BIAS_N_GELU);
         g1.bias = cw(m, q + "1.pwconv1.bias");
         NCK(p.lin(g1));
@@ -1736,7 +1783,7 @@ static int net_decode(Place &p, const int *codes, int T, float **wav_out, int *L
     float *wav = voc == A ? B : A;
     NCK(net_conv(p, slot, voc, ld, C, L, "decoder.decoder.6.conv.weight", "decoder.decoder.6.conv.bias", 1, 7, 1, wav,
                  ld, XE_BIAS_M, cw(m, "decoder.decoder.5.alpha"), cw(m, "decoder.decoder.5.beta"), nullptr));
-    p.clamp(wav, ld, L, T);
+    NCK(p.clamp(wav, ld, L, T));
     p.mark(5);
     *wav_out = wav;
     *L_out = L;
@@ -1881,8 +1928,7 @@ extern "C" int qtts_hip_causal_conv1d(float *out, const float *in, const float *
     hipStream_t st = (hipStream_t)stream;
     if (groups == ci && ci == co) {
         if (dilation != 1) return -1;
-        hipLaunchKernelGGL(k_dwconv, dim3((unsigned)(((size_t)co * L + 255) / 256)), dim3(256), 0, st, in, L, 0, w, b, co,
-                           L, k, out, L);
+        if (launch_dwconv(st, in, L, 0, w, b, co, L, k, out, L)) return -1;
         return hipGetLastError() == hipSuccess ? 0 : -1;
     }
     if (groups != 1) return -1;
@@ -2094,8 +2140,7 @@ constexpr int kStreamChunk = 16;      // frames per internal chunk
 constexpr int kStreamChunkMax = 128;  // largest chunk a begin may ask for
 
 void copy2d(hipStream_t st, float *dst, int ldd, const float *src, int lds, int rows, int cols) {
-    const size_t n = (size_t)rows * cols;
-    if (n) hipLaunchKernelGGL(k_copy2d, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, dst, ldd, src, lds, rows, cols);
+    if ((size_t)rows * cols) launch_copy2d(st, dst, ldd, src, lds, rows, cols);
 }
 
 // the history slots of a stream state (codec_hist_slots), `planes` [C][H]
@@ -2152,9 +2197,10 @@ struct StreamPlace : Place {
             copy2d(m->st, r.vc, kd, S.kvtmp, kd, keep, kd);
         }
     }
-    void layers_end(int T) override {
+    int layers_end(int T) override {
         const int keepmax = m->d.cwin - 1, tot = S.hl + T;
         S.hl = tot < keepmax ? tot : keepmax;
+        return 0;
     }
 };
 }  // namespace
@@ -2483,6 +2529,95 @@ __global__ void k_clamp_ms(const float *x, size_t seg, int L, float *y, const in
     y[(size_t)s * L + i] = v;
 }
 
+// Launch helpers of the multi-stream twins and the placement kernels (as the
+// single-plane ones above: MsPlace, the reset and the snapshots, and
+// qtts_hip_codec_op launch through them).  n: streams of the push
+int launch_rvq_sum_ms(hipStream_t st, const int *codes, const long long *coff, int ldc, int t0, int T, int n, int Q,
+                      int CB, int vq, const float *cb, float *ss, float *as, const int *tv) {
+    if (T < 1 || n < 1 || Q < 1 || CB < 1 || vq < 1 || vq > 1024 || t0 < 0 || ldc < Q || (size_t)n * T > kGridMax)
+        return -1;
+    hipLaunchKernelGGL(k_rvq_sum_ms, dim3(n * T), dim3(vq < 64 ? 64 : (vq + 63) / 64 * 64), 0, st, codes, coff, ldc, t0,
+                       T, n, Q, CB, vq, cb, ss, as, tv);
+    return 0;
+}
+int launch_rvq_proj_ms(hipStream_t st, const float *ps, const float *pa, const float *ss, const float *as, int vq,
+                       int half, int T, int n, int ldo, size_t seg, float *out) {
+    if (vq < 1 || half < 1 || T < 1 || n < 1 || ldo < T || (size_t)half * n * T > kGridMax - 3) return -1;
+    hipLaunchKernelGGL(k_rvq_proj_ms, dim3((half * n * T + 3) / 4), dim3(256), 0, st, ps, pa, ss, as, vq, half, T, n, ldo,
+                       seg, out);
+    return 0;
+}
+int launch_hist_ms(hipStream_t st, float *hist, const int *sid, float *x, size_t seg, int ldx, int C, int H,
+                   const int *tv, int mul, int n, int out) {
+    if (C < 1 || H < 1 || mul < 1 || n < 1 || ldx < H || (size_t)C * H > kGridMax - 255) return -1;
+    hipLaunchKernelGGL(k_hist_ms, dim3((C * H + 255) / 256, n), dim3(256), 0, st, hist, sid, x, seg, ldx, C, H, tv, mul,
+                       out ? 1 : 0);
+    return 0;
+}
+int launch_dwconv_ms(hipStream_t st, const float *x, size_t segx, int ldx, int tmin, const float *w, const float *b,
+                     int C, int L, int K, int n, float *y, size_t segy, int ldy) {
+    if (C < 1 || L < 1 || K < 1 || n < 1 || tmin > 0 || ldx < L || ldy < L || ((size_t)C * L + 255) / 256 > kGridMax)
+        return -1;
+    hipLaunchKernelGGL(k_dwconv_ms, dim3((unsigned)(((size_t)C * L + 255) / 256), n), dim3(256), 0, st, x, segx, ldx,
+                       tmin, w, b, C, L, K, y, segy, ldy);
+    return 0;
+}
+int launch_ln_t_ms(hipStream_t st, const float *x, size_t segx, int ldx, int L, int C, int n, const float *w,
+                   const float *b, float eps, float *y) {
+    if (L < 1 || C < 1 || n < 1 || ldx < L || (size_t)n * L > kGridMax) return -1;
+    hipLaunchKernelGGL(k_ln_t_ms, dim3(n * L), dim3(256), 0, st, x, segx, ldx, L, C, w, b, eps, y);
+    return 0;
+}
+int launch_clamp_ms(hipStream_t st, const float *x, size_t seg, int L, int n, float *y, const int *tv, int spf) {
+    if (L < 1 || n < 1 || spf < 1 || L > 0x7fffffff - 255) return -1;
+    hipLaunchKernelGGL(k_clamp_ms, dim3((L + 255) / 256, n), dim3(256), 0, st, x, seg, L, y, tv, spf);
+    return 0;
+}
+int launch_ms_index(hipStream_t st, const int *sid, const int *hl, int n, int T, int *row_b, int *pos) {
+    if (n < 1 || T < 1 || (size_t)n * T > kGridMax - 255) return -1;
+    hipLaunchKernelGGL(k_ms_index, dim3((n * T + 255) / 256), dim3(256), 0, st, sid, hl, n, T, row_b, pos);
+    return 0;
+}
+int launch_rope_kv_ms(hipStream_t st, float *q, int hid, int nh, const float *k, const float *v, int kvd, int nkv, int hd,
+                      const float *cs, const float *sn, int T, int n, const int *sid, const int *pos0, const int *hl,
+                      const int *tv, float *kc, float *vc, int S) {
+    if (T < 1 || n < 1 || nh < 1 || nkv < 1 || S < 1 || hd < 2 || hd % 2 || hid < nh * hd || kvd < nkv * hd ||
+        (size_t)n * T > kGridMax)
+        return -1;
+    hipLaunchKernelGGL(k_rope_kv_ms, dim3(n * T), dim3(256), 0, st, q, hid, nh, k, v, kvd, nkv, hd, cs, sn, T, sid, pos0,
+                       hl, tv, kc, vc, S);
+    return 0;
+}
+int launch_kv_shift_ms(hipStream_t st, float *kv, const int *sid, const int *hl, const int *tv, int ns, int S, int kvd,
+                       int keepmax, int n, int nl2) {
+    if (ns < 1 || S < 1 || kvd < 1 || keepmax < 1 || keepmax > S || n < 1 || n > 65535 || nl2 < 1 || nl2 > 65535)
+        return -1;
+    hipLaunchKernelGGL(k_kv_shift_ms, dim3((kvd + 255) / 256, n, nl2), dim3(256), 0, st, kv, sid, hl, tv, ns, S, kvd,
+                       keepmax);
+    return 0;
+}
+// base / elems: the device table of nslots history slots; most: the largest slot's floats per stream
+int launch_hist_reset_ms(hipStream_t st, float *const *base, const int *elems, int nslots, int most, int stream) {
+    if (nslots < 1 || nslots > 65535 || most < 0 || stream < 0) return -1;
+    const int gx = (most + 255) / 256 < 64 ? (most + 255) / 256 : 64;
+    hipLaunchKernelGGL(k_hist_reset_ms, dim3(gx > 0 ? gx : 1, (unsigned)nslots), dim3(256), 0, st, base, elems, stream);
+    return 0;
+}
+// save (load 0) / load of one stream's nh history parts and nkv K/V planes; grid
+// x over the largest part (most: the largest history part) in 16-byte units,
+// at most 64 groups, y over the parts
+int launch_ms_state(hipStream_t st, int load, float *const *base, const int *elems, const int *soff, int nh, int nkv,
+                    int most, int stream, int kvn, int kvpad, float *snap) {
+    if (nh < 0 || nkv < 0 || nh + nkv < 1 || nh + nkv > 65535 || most < 0 || stream < 0 || kvn < 0 || kvpad < kvn ||
+        kvpad % 4)
+        return -1;
+    const int big = most > kvn ? most : kvn, gx = (big / 4 + 255) / 256;
+    const dim3 grid(gx < 1 ? 1 : gx > 64 ? 64 : gx, (unsigned)(nh + nkv));
+    if (load) hipLaunchKernelGGL(k_ms_state_load, grid, dim3(256), 0, st, base, elems, soff, nh, stream, kvn, kvpad, snap);
+    else hipLaunchKernelGGL(k_ms_state_save, grid, dim3(256), 0, st, base, elems, soff, nh, stream, kvn, kvpad, snap);
+    return 0;
+}
+
 // the multi-stream's placement for one pass: n planes a launch, history of
 // every plane by k_hist_ms, k and v projected to S.tk / S.tv and sent to
 // their stream's cache rows by k_rope_kv_ms, one keep-shift after the layers.
@@ -2505,9 +2640,8 @@ struct MsPlace : Place {
     }
     int hist(int slot, int C, int H, float *x, int ldx, int L, bool out) override {
         if (!hist_slot_is(S, slot, C, H)) return -1;
-        hipLaunchKernelGGL(k_hist_ms, dim3((C * H + 255) / 256, n), dim3(256), 0, m->st, S.hist[slot], S.sid, x,
-                           (size_t)C * ldx, ldx, C, H, dtv, L / T, out ? 1 : 0);   // (L: a whole number of columns per frame)
-        return 0;
+        // (L: a whole number of columns per frame)
+        return launch_hist_ms(m->st, S.hist[slot], S.sid, x, (size_t)C * ldx, ldx, C, H, dtv, L / T, n, out ? 1 : 0);
     }
     // input plane stride ci * ldb, output (and residual) co * ldc
     void planes(XGemm &g, int ci, int co) override {
@@ -2520,47 +2654,42 @@ struct MsPlace : Place {
         else g.seg_ldc = C * g.ldc;
         if (g.res) g.seg_ldres = C * g.ldres;
     }
-    void rvq(const int *codes, const float *ps, const float *pa, int, int ldo, float *out) override {
+    int rvq(const int *codes, const float *ps, const float *pa, int, int ldo, float *out) override {
         const qtts_dims_t &d = m->d;
         const int vq = d.ccbdim / 2, half = d.clat / 2;
-        hipLaunchKernelGGL(k_rvq_sum_ms, dim3(n * T), dim3(vq < 64 ? 64 : (vq + 63) / 64 * 64), 0, m->st, codes, S.coff,
-                           ldc_codes, t0, T, n, d.cq, d.ccb, vq, m->cb, rvq_s, rvq_a, dtv);
-        hipLaunchKernelGGL(k_rvq_proj_ms, dim3((half * n * T + 3) / 4), dim3(256), 0, m->st, ps, pa, rvq_s, rvq_a, vq,
-                           half, T, n, ldo, (size_t)d.ccbdim * ldo, out);
+        if (launch_rvq_sum_ms(m->st, codes, S.coff, ldc_codes, t0, T, n, d.cq, d.ccb, vq, m->cb, rvq_s, rvq_a, dtv))
+            return -1;
+        return launch_rvq_proj_ms(m->st, ps, pa, rvq_s, rvq_a, vq, half, T, n, ldo, (size_t)d.ccbdim * ldo, out);
     }
-    void dwconv(const float *x, int ldx, const float *w, const float *b, int C, int L, int K, float *y) override {
-        hipLaunchKernelGGL(k_dwconv_ms, dim3((unsigned)(((size_t)C * L + 255) / 256), n), dim3(256), 0, m->st, x,
-                           (size_t)C * ldx, ldx, tmin(K - 1), w, b, C, L, K, y, (size_t)C * L, L);
+    int dwconv(const float *x, int ldx, const float *w, const float *b, int C, int L, int K, float *y) override {
+        return launch_dwconv_ms(m->st, x, (size_t)C * ldx, ldx, tmin(K - 1), w, b, C, L, K, n, y, (size_t)C * L, L);
     }
-    void ln_t(const float *x, int L, int C, const float *w, const float *b, float *y) override {
-        hipLaunchKernelGGL(k_ln_t_ms, dim3(n * L), dim3(256), 0, m->st, x, (size_t)C * L, L, L, C, w, b, 1e-6f, y);
+    int ln_t(const float *x, int L, int C, const float *w, const float *b, float *y) override {
+        return launch_ln_t_ms(m->st, x, (size_t)C * L, L, L, C, n, w, b, 1e-6f, y);
     }
     // into the compact S.wav [n][L], the valid samples only
-    void clamp(float *wav, int ld, int L, int) override {
-        hipLaunchKernelGGL(k_clamp_ms, dim3((L + 255) / 256, n), dim3(256), 0, m->st, wav, (size_t)ld, L, S.wav, dtv,
-                           L / T);
+    int clamp(float *wav, int ld, int L, int) override {
+        return launch_clamp_ms(m->st, wav, (size_t)ld, L, n, S.wav, dtv, L / T);
     }
-    void layers_begin(int) override {
-        hipLaunchKernelGGL(k_ms_index, dim3((n * T + 255) / 256), dim3(256), 0, m->st, S.sid, dhl, n, T, S.row_b, S.pos);
-    }
+    int layers_begin(int) override { return launch_ms_index(m->st, S.sid, dhl, n, T, S.row_b, S.pos); }
     LayerKV layer(int l, int) override {
         const size_t lsz = (size_t)S.ns * S.S * kvd();   // one layer's K (or V) of every stream
         float *kc = S.kv + (size_t)(2 * l) * lsz;
         return {tq, S.tk, S.tv, kc, kc + lsz};
     }
-    void rope(const LayerKV &r, int) override {
+    int rope(const LayerKV &r, int) override {
         const qtts_dims_t &d = m->d;
         const int hid = d.chid, hd = hid / d.cheads;
-        hipLaunchKernelGGL(k_rope_kv_ms, dim3(n * T), dim3(256), 0, m->st, r.q, hid, d.cheads, r.k, r.v, kvd(), d.ckv, hd,
-                           rope_cos, rope_sin, T, S.sid, dpos0, dhl, dtv, r.kc, r.vc, S.S);
+        return launch_rope_kv_ms(m->st, r.q, hid, d.cheads, r.k, r.v, kvd(), d.ckv, hd, rope_cos, rope_sin, T, n, S.sid,
+                                 dpos0, dhl, dtv, r.kc, r.vc, S.S);
     }
     void attn_rows(AttnArgs &a, int) override { a.S = S.S; a.pos = S.pos; a.row_b = S.row_b; }
     // keep the last window-1 rows of every layer for the next pass (each stream by its own count)
-    void layers_end(int) override {
+    int layers_end(int) override {
         const int keepmax = m->d.cwin - 1;
         if (keepmax > 0 && shifts)
-            hipLaunchKernelGGL(k_kv_shift_ms, dim3((kvd() + 255) / 256, n, 2 * m->d.clayers), dim3(256), 0, m->st, S.kv,
-                               S.sid, dhl, dtv, S.ns, S.S, kvd(), keepmax);
+            return launch_kv_shift_ms(m->st, S.kv, S.sid, dhl, dtv, S.ns, S.S, kvd(), keepmax, n, 2 * m->d.clayers);
+        return 0;
     }
 };
 // frames per internal pass for n streams: the chunk asked for, lowered until
@@ -2925,9 +3054,7 @@ int codec_mstream_reset(CodecModel *m, int stream) {
         const int e = S.hist_c[i] * (S.hist_h[i] > 0 ? S.hist_h[i] : 1);
         if (e > most) most = e;
     }
-    const int gx = (most + 255) / 256 < 64 ? (most + 255) / 256 : 64;
-    hipLaunchKernelGGL(k_hist_reset_ms, dim3(gx > 0 ? gx : 1, (unsigned)S.hist.size()), dim3(256), 0, m->st, S.hist_base,
-                       S.hist_elems, stream);
+    if (launch_hist_reset_ms(m->st, S.hist_base, S.hist_elems, (int)S.hist.size(), most, stream)) return -1;
     if (hipGetLastError() != hipSuccess) return -1;
     S.pos0[stream] = 0;
     S.hl[stream] = 0;
@@ -2952,15 +3079,14 @@ int ms_state_check(const CodecModel *m, int stream, const char *what) {
 
 int ms_kvd(const qtts_dims_t &d) { return d.ckv * (d.chid / d.cheads); }
 
-// grid of the state copy: x over the largest part in 16-byte units (at most 64 groups), y over the parts
-dim3 ms_state_grid(const CodecMStream &S, const qtts_dims_t &d, int kvn) {
-    int most = kvn;
+// the largest history part of a stream's state, floats (launch_ms_state sizes its grid by it)
+int ms_state_most(const CodecMStream &S) {
+    int most = 0;
     for (size_t i = 0; i < S.hist.size(); ++i) {
         const int e = S.hist_c[i] * (S.hist_h[i] > 0 ? S.hist_h[i] : 1);
         if (e > most) most = e;
     }
-    const int gx = (most / 4 + 255) / 256;
-    return dim3(gx < 1 ? 1 : gx > 64 ? 64 : gx, (unsigned)(S.hist.size() + 2 * d.clayers));
+    return most;
 }
 }  // namespace
 
@@ -2980,9 +3106,9 @@ int codec_mstream_save(CodecModel *m, int stream, CodecSnapshot *snap) {
         fprintf(stderr, "qtts codec mstream: save: no device memory for %zu bytes\n", elems * 4);
         return -1;
     }
-    hipLaunchKernelGGL(k_ms_state_save, ms_state_grid(S, d, kvn), dim3(256), 0, m->st, S.hist_base, S.hist_elems,
-                       S.snap_off, (int)S.hist.size(), stream, kvn, kvpad, buf);
-    if (hipGetLastError() != hipSuccess) {
+    if (launch_ms_state(m->st, 0, S.hist_base, S.hist_elems, S.snap_off, (int)S.hist.size(), 2 * d.clayers,
+                        ms_state_most(S), stream, kvn, kvpad, buf) ||
+        hipGetLastError() != hipSuccess) {
         hipFree(buf);
         return -1;
     }
@@ -3024,9 +3150,10 @@ int codec_mstream_restore(CodecModel *m, int stream, const CodecSnapshot *snap) 
                 stream, snap->pos0, S.max_frames);
         return -1;
     }
-    hipLaunchKernelGGL(k_ms_state_load, ms_state_grid(S, d, kvn), dim3(256), 0, m->st, S.hist_base, S.hist_elems,
-                       S.snap_off, (int)S.hist.size(), stream, kvn, kvpad, snap->dev);
-    if (hipGetLastError() != hipSuccess) return -1;
+    if (launch_ms_state(m->st, 1, S.hist_base, S.hist_elems, S.snap_off, (int)S.hist.size(), 2 * d.clayers,
+                        ms_state_most(S), stream, kvn, kvpad, snap->dev) ||
+        hipGetLastError() != hipSuccess)
+        return -1;
     S.pos0[stream] = snap->pos0;
     S.hl[stream] = snap->hl;
     return 0;
@@ -3036,4 +3163,94 @@ void codec_snapshot_release(CodecSnapshot *snap) {
     if (!snap) return;
     if (snap->dev) hipFree(snap->dev);
     *snap = CodecSnapshot();
+}
+
+// ===================================================================== kernel-level entry of the small kernels
+// one launch of one small codec kernel through its launch helper (qtts_hip.h
+// lists the operands); for the kernel-level tests, not a timing entry
+extern "C" int qtts_hip_codec_op(const qtts_codec_op_t *d, void *stream) {
+    if (!d || d->op < 0 || d->op >= QTTS_CO_COUNT) return -1;
+    // operands an op needs, sizes it takes, and which of those may be 0 (bit i: n[i])
+    static const struct { int n_in, n_out, n_n, zero_ok; int opt_in; } T[QTTS_CO_COUNT] = {
+        {2, 2, 4, 0, -1},        // RVQ_SUM
+        {4, 1, 4, 0, -1},        // RVQ_PROJ
+        {4, 2, 7, 1 << 1, -1},   // RVQ_SUM_MS (t0)
+        {4, 1, 5, 0, -1},        // RVQ_PROJ_MS
+        {3, 1, 6, 1 << 1, 2},    // DWCONV (margin; b optional)
+        {3, 1, 7, 1 << 1, 2},    // DWCONV_MS
+        {3, 1, 3, 0, -1},        // LN_T
+        {3, 1, 4, 0, -1},        // LN_T_MS
+        {2, 1, 2, 0, -1},        // RMS_ROWS
+        {2, 1, 4, 0, -1},        // ROPE_ROWS
+        {8, 3, 8, 0, -1},        // ROPE_KV_MS
+        {2, 2, 2, 0, -1},        // MS_INDEX
+        {0, 1, 1, 0, -1},        // CLAMP
+        {1, 1, 4, 0, -1},        // COPY2D
+        {2, 1, 3, 0, -1},        // CLAMP_MS
+        {2, 2, 6, 1 << 5, -1},   // HIST_MS (out flag)
+        {3, 1, 6, 0, -1},        // KV_SHIFT_MS
+        {2, 0, 3, 1 << 2, -1},   // HIST_RESET_MS (stream)
+        {3, 1, 6, 0x3f, -1},     // MS_STATE_SAVE (helper checks)
+        {4, 0, 6, 0x3f, -1},     // MS_STATE_LOAD
+    };
+    const auto &t = T[d->op];
+    for (int i = 0; i < t.n_in; ++i) if (!d->in[i] && i != t.opt_in) return -1;
+    for (int i = 0; i < t.n_out; ++i) if (!d->out[i]) return -1;
+    for (int i = 0; i < t.n_n; ++i)
+        if (d->n[i] < ((t.zero_ok >> i) & 1 ? 0 : 1)) return -1;
+    const int *n = d->n;
+    hipStream_t st = (hipStream_t)stream;
+    auto F = [&](int i) { return static_cast<const float *>(d->in[i]); };
+    auto I = [&](int i) { return static_cast<const int *>(d->in[i]); };
+    auto O = [&](int i) { return static_cast<float *>(d->out[i]); };
+    auto Tab = [&](int i) { return static_cast<float *const *>(d->in[i]); };
+    int rc = -1;
+    switch (d->op) {
+        case QTTS_CO_RVQ_SUM: rc = launch_rvq_sum(st, I(0), n[0], n[1], n[2], n[3], F(1), O(0), O(1)); break;
+        case QTTS_CO_RVQ_PROJ: rc = launch_rvq_proj(st, F(0), F(1), F(2), F(3), n[0], n[1], n[2], n[3], O(0)); break;
+        case QTTS_CO_RVQ_SUM_MS:
+            rc = launch_rvq_sum_ms(st, I(0), static_cast<const long long *>(d->in[1]), n[0], n[1], n[2], n[3], n[4], n[5],
+                                   n[6], F(2), O(0), O(1), I(3));
+            break;
+        case QTTS_CO_RVQ_PROJ_MS:
+            rc = launch_rvq_proj_ms(st, F(0), F(1), F(2), F(3), n[0], n[1], n[2], n[3], n[4], d->s[0], O(0));
+            break;
+        case QTTS_CO_DWCONV: rc = launch_dwconv(st, F(0), n[0], -n[1], F(1), F(2), n[2], n[3], n[4], O(0), n[5]); break;
+        case QTTS_CO_DWCONV_MS:
+            rc = launch_dwconv_ms(st, F(0), d->s[0], n[0], -n[1], F(1), F(2), n[2], n[3], n[4], n[6], O(0), d->s[1], n[5]);
+            break;
+        case QTTS_CO_LN_T: rc = launch_ln_t(st, F(0), n[0], n[1], n[2], F(1), F(2), d->eps, O(0)); break;
+        case QTTS_CO_LN_T_MS:
+            rc = launch_ln_t_ms(st, F(0), d->s[0], n[0], n[1], n[2], n[3], F(1), F(2), d->eps, O(0));
+            break;
+        case QTTS_CO_RMS_ROWS: rc = launch_rms_rows(st, F(0), n[0], n[1], F(1), d->eps, O(0)); break;
+        case QTTS_CO_ROPE_ROWS: rc = launch_rope_rows(st, O(0), n[0], n[1], n[2], n[3], F(0), F(1)); break;
+        case QTTS_CO_ROPE_KV_MS:
+            rc = launch_rope_kv_ms(st, O(0), n[0], n[1], F(0), F(1), n[2], n[3], n[4], F(2), F(3), n[5], n[6], I(4), I(5),
+                                   I(6), I(7), O(1), O(2), n[7]);
+            break;
+        case QTTS_CO_MS_INDEX:
+            rc = launch_ms_index(st, I(0), I(1), n[0], n[1], static_cast<int *>(d->out[0]), static_cast<int *>(d->out[1]));
+            break;
+        case QTTS_CO_CLAMP: rc = launch_clamp(st, O(0), n[0]); break;
+        case QTTS_CO_COPY2D: rc = launch_copy2d(st, O(0), n[0], F(0), n[1], n[2], n[3]); break;
+        case QTTS_CO_CLAMP_MS: rc = launch_clamp_ms(st, F(0), d->s[0], n[0], n[2], O(0), I(1), n[1]); break;
+        case QTTS_CO_HIST_MS:
+            rc = launch_hist_ms(st, O(0), I(0), O(1), d->s[0], n[0], n[1], n[2], I(1), n[3], n[4], n[5]);
+            break;
+        case QTTS_CO_KV_SHIFT_MS:
+            rc = launch_kv_shift_ms(st, O(0), I(0), I(1), I(2), n[0], n[1], n[2], n[3], n[4], n[5]);
+            break;
+        case QTTS_CO_HIST_RESET_MS: rc = launch_hist_reset_ms(st, Tab(0), I(1), n[0], n[1], n[2]); break;
+        case QTTS_CO_MS_STATE_SAVE:
+            rc = launch_ms_state(st, 0, Tab(0), I(1), I(2), n[0], n[1], n[2], n[3], n[4], n[5], O(0));
+            break;
+        case QTTS_CO_MS_STATE_LOAD:
+            rc = launch_ms_state(st, 1, Tab(0), I(1), I(2), n[0], n[1], n[2], n[3], n[4], n[5],
+                                 const_cast<float *>(F(3)));
+            break;
+        default: return -1;
+    }
+    if (rc) return -1;
+    return hipGetLastError() == hipSuccess ? 0 : -1;
 }

@@ -138,7 +138,7 @@ EXPORTS = [
     "qwen_tts_generate_fed_batch_stream", "qtts_dev_text_open", "qtts_dev_text_append", "qtts_dev_get_trailing",
     "qtts_dev_text_state", "qtts_hip_text_held_frames", "qtts_dev_text_append_ms",
     "qtts_hip_rows_gemm_plan", "qtts_hip_rows_gemm_case",
-    "qtts_hip_econv_plan", "qtts_hip_econv_case", "qtts_hip_enc_op", "qtts_hip_enc_func",
+    "qtts_hip_econv_plan", "qtts_hip_econv_case", "qtts_hip_enc_op", "qtts_hip_enc_func", "qtts_hip_codec_op",
     "qtts_hip_attn_tiled", "qtts_hip_attn_tile_launches",
 ]
 
@@ -268,6 +268,18 @@ class EncOp(C.Structure):
 # qtts_enc_op_t.op (QTTS_EO_* of qtts_hip.h)
 (EO_MEL, EO_ROW_MEAN, EO_EGEMV, EO_SE_APPLY, EO_ASP_STATS, EO_ASP_POOL, EO_LN_ROWS, EO_ROPE_BT, EO_ROWS_BT,
  EO_RVQ_ENC) = range(10)
+
+
+class CodecOp(C.Structure):
+    """qtts_codec_op_t (include/qtts_hip.h): one launch of one small codec-decoder kernel."""
+    _fields_ = [("op", C.c_int), ("inp", C.c_void_p * 8), ("out", C.c_void_p * 3), ("n", C.c_int * 8),
+                ("s", C.c_size_t * 2), ("eps", C.c_float)]
+
+
+# qtts_codec_op_t.op (QTTS_CO_* of qtts_hip.h)
+(CO_RVQ_SUM, CO_RVQ_PROJ, CO_RVQ_SUM_MS, CO_RVQ_PROJ_MS, CO_DWCONV, CO_DWCONV_MS, CO_LN_T, CO_LN_T_MS, CO_RMS_ROWS,
+ CO_ROPE_ROWS, CO_ROPE_KV_MS, CO_MS_INDEX, CO_CLAMP, CO_COPY2D, CO_CLAMP_MS, CO_HIST_MS, CO_KV_SHIFT_MS,
+ CO_HIST_RESET_MS, CO_MS_STATE_SAVE, CO_MS_STATE_LOAD) = range(20)
 # k_econv padding modes and activations (k_enc.hip)
 EPAD_ZERO, EPAD_REFLECT, EPAD_REPLICATE = range(3)
 EACT_NONE, EACT_RELU, EACT_RELU_TANH, EACT_GELU, EACT_SIGMOID = range(5)
@@ -651,6 +663,8 @@ def lib():
         L.qtts_hip_econv_case.argtypes = [C.POINTER(EConvDesc), C.POINTER(EConvPlan), vp]
         L.qtts_hip_enc_op.restype = C.c_int
         L.qtts_hip_enc_op.argtypes = [C.POINTER(EncOp), vp]
+        L.qtts_hip_codec_op.restype = C.c_int
+        L.qtts_hip_codec_op.argtypes = [C.POINTER(CodecOp), vp]
         L.qtts_hip_enc_func.restype = C.c_int
         L.qtts_hip_enc_func.argtypes = [vp, vp, C.c_size_t, C.c_int, vp]
     if hasattr(L, "qtts_hip_rows_gemm_case"):
@@ -1788,6 +1802,24 @@ class Kernels:
             d.s[i] = int(v)
         d.eps = eps
         return lib().qtts_hip_enc_op(C.byref(d), _stream()) == 0
+
+    @staticmethod
+    def codec_op(op, inp=(), out=(), n=(), s=(), eps=0.0):
+        """One launch of a small codec-decoder kernel (qtts_hip_codec_op): op
+        CO_*, inp / out torch tensors (None: NULL; an int: a device address), n /
+        s the integers of qtts_hip.h's table.  True when launched, False when
+        refused."""
+        d = CodecOp()
+        d.op = op
+        for dst, src in ((d.inp, inp), (d.out, out)):
+            for i, t in enumerate(src):
+                dst[i] = None if t is None else t if isinstance(t, int) else t.data_ptr()
+        for i, v in enumerate(n):
+            d.n[i] = int(v)
+        for i, v in enumerate(s):
+            d.s[i] = int(v)
+        d.eps = eps
+        return lib().qtts_hip_codec_op(C.byref(d), _stream()) == 0
 
     @staticmethod
     def enc_func(out, x, fn):
