@@ -116,6 +116,16 @@ int qtts_dev_codec_precision(const qtts_dev_t *dev);
  * at begin.  -1 on a bad value. */
 int qtts_dev_set_codec_linear_precision(qtts_dev_t *dev, int precision);
 int qtts_dev_codec_linear_precision(const qtts_dev_t *dev);
+/* Precision of the talker prefill's projections over more than 16 rows: 0
+ * exact (default, or $QTTS_HIP_PREFILL at creation: three bf16 planes per
+ * activation, k_pgemm), 1 one bf16 plane (k_round1 + k_pgemmh on every shape
+ * k_pgemm covers, the others on the exact kernels; sums, epilogues, attention,
+ * norms, cache and residual fp32).  Read per projection; prefix cache entries
+ * are keyed by it.  -1 on a bad value.
+ * qtts_hip_pgemmh_launches: k_pgemmh launches since the library loaded. */
+int qtts_dev_set_prefill_precision(qtts_dev_t *dev, int precision);
+int qtts_dev_prefill_precision(const qtts_dev_t *dev);
+long long qtts_hip_pgemmh_launches(void);
 /* Diagnostics: talker cache rows [pos0, pos0 + n) of layer `layer`, slot b,
  * to the host as fp32 [n][KV*HD] each (bf16 widened exactly; k_host or v_host
  * may be NULL).  Waits for the context stream.  -1 out of range. */
@@ -160,8 +170,8 @@ int qtts_dev_prompt(qtts_dev_t *dev, int b, const int *text_ids, int n_text, con
  * qtts_dev_refill run a slot with a prefix in two passes, whatever the cache
  * holds: the prefix rows alone (computed once per distinct prefix and saved,
  * afterwards copied back: one launch), then the remaining rows at their own
- * positions.  One cache per device model, keyed by the exact id sequence and
- * the KV element type, LRU, QTTS_HIP_PREFIX_CACHE entries (read at creation,
+ * positions.  One cache per device model, keyed by the exact id sequence,
+ * the KV element type and the prefill precision, LRU, QTTS_HIP_PREFIX_CACHE entries (read at creation,
  * default 16, 0: off -- the prefix rows are then ordinary rows of the one
  * pass).  An entry holds rows [0, n) of all layers, [2][L][n][KV*HD]; entries
  * survive qtts_dev_begin and state re-allocation, a change of the KV element
@@ -840,6 +850,11 @@ enum {
     QTTS_RG_PGEMM_2 = 5,     /* k_pgemm<2>: 128 x 128 tile */
     QTTS_RG_PGEMM_4 = 6,     /* k_pgemm<4>: 128 x 256 tile */
 };
+/* behind them, the pair of the bf16 prefill precision (qtts_hip_rows_gemm_bf16_case below): 7 and 8 */
+enum {
+    QTTS_RG_PGEMMH_2 = QTTS_RG_PGEMM_4 + 1,   /* k_pgemmh<2>: one bf16 plane, 128 x 128 tile */
+    QTTS_RG_PGEMMH_4,                         /* k_pgemmh<4>: one bf16 plane, 128 x 256 tile */
+};
 /* which kernel, its split-K columns (kz > 1: summed by k_mgemm_reduce), grid and block */
 typedef struct {
     int kernel, kz;
@@ -860,6 +875,16 @@ int qtts_hip_rows_gemm_plan(const qtts_rows_gemm_desc_t *d, size_t part_elems, s
  * 1 and launches nothing where the (forced) launcher does not cover the
  * shape, -1 on an argument or launch error.  A parity entry, not a timing one. */
 int qtts_hip_rows_gemm_case(const qtts_rows_gemm_desc_t *d, int force, qtts_rows_gemm_plan_t *plan_out, void *stream);
+/* The same pair for the bf16 prefill precision's launcher: force 3 / 4 (the
+ * values that continue the ones above; any other is an argument error, as 3
+ * and 4 are to the exact pair) run qtts_pgemmh -- one bf16 plane, k_round1 +
+ * k_pgemmh -- at tile width 128 / 256 and report QTTS_RG_PGEMMH_2 / _4.  The
+ * plane scratch it needs is a third of qtts_pgemm's: ceil(rows / 128) * 128 * C
+ * bf16; d->inv is not used.  Returns as the exact pair does. */
+int qtts_hip_rows_gemm_bf16_plan(const qtts_rows_gemm_desc_t *d, size_t part_elems, size_t plane_elems, int force,
+                                 qtts_rows_gemm_plan_t *plan_out);
+int qtts_hip_rows_gemm_bf16_case(const qtts_rows_gemm_desc_t *d, int force, qtts_rows_gemm_plan_t *plan_out,
+                                 void *stream);
 /* snake(x) = x + inv_beta[c] * sin^2(x * alpha[c]) with the codec GEMMs' own
  * sin^2 (sin2 in k_codec.hip; qtts_hip_snake_beta runs sinf), and the fp32
  * expf / tanhf the GELU and SiLU epilogues call: fn 0 snake (needs alpha /

@@ -267,6 +267,25 @@ int qwen_tts_codec_precision(qwen_tts_ctx_t *ctx);
  * $QTTS_HIP_CODEC_LIN=bf16|exact sets the default of every ctx loaded after it. */
 int qwen_tts_set_codec_linear_precision(qwen_tts_ctx_t *ctx, int precision);
 int qwen_tts_codec_linear_precision(qwen_tts_ctx_t *ctx);
+/* Arithmetic of the talker prefill's projections (q|k|v, O, gate|up, down)
+ * when a prefill call holds more than 16 rows.  QWEN_TTS_PREFILL_EXACT (the
+ * default) keeps fp32-equivalent products (three bf16 planes per activation).
+ * QWEN_TTS_PREFILL_BF16 rounds the (RMS-normalised) activations to bf16,
+ * nearest even, and multiplies them with the bf16 weights by one matrix
+ * instruction where the exact path needs three; sums, epilogues, attention,
+ * norms, the K / V written to the cache and the residual stream stay fp32, as
+ * do calls of 16 rows and fewer, the text projection and every decode step.
+ * No new weight memory.  The ids are then no longer bit-exact against the
+ * reference, and because the path follows the call's total row count (16 and
+ * fewer: exact) and the split of the sums follows the tile count, an
+ * utterance's codes may depend on what it is prefilled together with.  Read
+ * per prefill call; an instruct prefix cache entry is served only in the mode
+ * it was made in.  -1 on any other value.
+ * $QTTS_HIP_PREFILL=bf16|exact sets the default of every ctx loaded after it. */
+#define QWEN_TTS_PREFILL_EXACT 0
+#define QWEN_TTS_PREFILL_BF16  1
+int qwen_tts_set_prefill_precision(qwen_tts_ctx_t *ctx, int precision);
+int qwen_tts_prefill_precision(qwen_tts_ctx_t *ctx);
 /* Most lock-step slots of one ctx (qwen_tts_generate_batch, the slots of
  * qwen_tts_generate_queue, qwen_tts_generate_voice_clone_batch): up to 16 run
  * on the 16-row matrix-core batch kernels, 17..64 on the wide batch kernel. */

@@ -170,13 +170,14 @@ struct qtts_dev {
     // The instruct prefix cache (DESIGN.md "Instruct and the prefix cache"):
     // pfx_ids[b] = the text ids of slot b's kind-2 plan rows (its prompt rows
     // [0, n), qtts_dev_prompt); an entry = those rows' K and V of all layers,
-    // [2][L][n][KV*HD] in the element type it was saved from, keyed by the ids
-    // and that type.  Outside the decode state (sallocs): entries survive
+    // [2][L][n][KV*HD] in the element type it was saved from, keyed by the ids,
+    // that type and the prefill precision it was computed in.  Outside the decode state (sallocs): entries survive
     // qtts_dev_begin and a re-allocation; a change of the KV element type drops
     // them (alloc_state), qtts_dev_destroy drops all.
     struct PrefixEntry {
         std::vector<int> ids;
         int dtype = 0;
+        int pprec = 0;                 // prefill_prec of the pass that made it
         void *buf = nullptr;
         size_t bytes = 0;
         unsigned long long used = 0;   // LRU stamp
@@ -295,6 +296,10 @@ struct qtts_dev {
     unsigned short *pplanes = nullptr;
     size_t pplanes_elems = 0;
     bool pgemm = true;       // QTTS_HIP_PGEMM=0: the prefill on k_mgemm (rounds 1-5)
+    // precision of the talker prefill's projections over > 16 rows: 0 exact (three
+    // planes, k_pgemm), 1 one bf16 plane (k_pgemmh).  Read per rows_proj call
+    // (qtts_dev_set_prefill_precision, QTTS_HIP_PREFILL at creation).
+    int prefill_prec = 0;
 
     int QKV() const { return (d.NH + 2 * d.KV) * d.HD; }
     int QKVs() const { return (d.NHs + 2 * d.KVs) * d.HDs; }

@@ -136,7 +136,7 @@ bool qtts_gemvx_shape_ok(int R, int C);
 // The seven kernels of the multi-row GEMMs (k_mgemm<MT,NW>, k_pgemm<WN>), as
 // the plans below name them (QTTS_RG_* of qtts_hip.h).
 enum { RG_MGEMM_1_1 = 0, RG_MGEMM_2_1 = 1, RG_MGEMM_4_1 = 2, RG_MGEMM_4_2 = 3, RG_MGEMM_4_4 = 4, RG_PGEMM_2 = 5,
-       RG_PGEMM_4 = 6 };
+       RG_PGEMM_4 = 6, RG_PGEMMH_2 = 7, RG_PGEMMH_4 = 8 };   // (7, 8: the one-plane k_pgemmh<WN>, k_pgemmh.hip)
 // qtts_mgemm's plan: the kernel (RG_*), its template (mt row tiles x nw weight
 // tiles per workgroup), the 64-row chunks, the split-K columns and the grid
 struct MgPlan {
@@ -171,6 +171,16 @@ int qtts_pgemm_plan(const GemvArgs &a, bool has_planes, size_t plane_elems, bool
                     PgPlan &p);
 int qtts_pgemm_bn_env();   // QTTS_HIP_PGEMM_BN as a tile width (128 | 256), else 0
 size_t qtts_pgemm_plane_elems(size_t rows, size_t K);
+// the same projections on ONE bf16 plane per operand (k_pgemmh.hip, the opt-in
+// bf16 prefill precision): k_round1 writes x (+ RMSNorm) rounded to nearest even
+// as one plane [Mp][C] into `plane` (>= Mp C bf16: the first third of the scratch
+// above), k_pgemmh<WN> multiplies it on 64-deep LDS stages.  Covers what
+// qtts_pgemm covers; 1 = not covered, nothing launched.  The plan reports
+// RG_PGEMMH_2 / _4.
+int qtts_pgemmh(const GemvArgs &a, unsigned short *plane, size_t plane_elems, hipStream_t st, float *part,
+                size_t part_elems, int bn = 0);
+int qtts_pgemmh_plan(const GemvArgs &a, bool has_planes, size_t plane_elems, bool has_part, size_t part_elems, int bn,
+                     PgPlan &p);
 
 struct AttnArgs {
     int mode = 0;                  // 0 decode (fused q/k norm + rope + cache write), 1 cached

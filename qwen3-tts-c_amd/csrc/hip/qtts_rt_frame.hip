@@ -54,6 +54,12 @@ int rows_proj(qtts_dev *dv, GemvArgs a, int rows, bool prefill) {
     if (prefill && dv->pgemm && rows > 16 && (!a.norm_w || rows <= dv->pinv_cap)) {
         GemvArgs c = a;
         c.nb = rows;
+        // the bf16 prefill precision (qtts_dev_set_prefill_precision): one plane on
+        // k_pgemmh.hip; what it does not cover goes on to the exact kernels
+        if (dv->prefill_prec) {
+            const int rh = qtts_pgemmh(c, dv->pplanes, dv->pplanes_elems, dv->st, dv->mpart, dv->mpart_elems);
+            if (rh <= 0) return rh;
+        }
         const int rc = qtts_pgemm(c, dv->pinv, dv->pplanes, dv->pplanes_elems, dv->st, dv->mpart, dv->mpart_elems);
         if (rc <= 0) return rc;
     }

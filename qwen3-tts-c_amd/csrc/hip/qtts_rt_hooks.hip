@@ -431,9 +431,10 @@ extern "C" int qtts_hip_batch_matvec_plan(const qtts_bgemv_desc_t *d, qtts_bgemv
 }
 
 // qtts_rows_gemm_desc_t checked and translated to the multi-row GEMMs'
-// arguments.  No pointer is dereferenced.  -1 = a bad descriptor.
-static int rows_gemm_args(const qtts_rows_gemm_desc_t *d, int force, GemvArgs &a) {
-    if (!d || !d->A || !d->y || d->rows < 1 || d->R < 1 || d->C < 1 || force < -1 || force > 2) return -1;
+// arguments.  No pointer is dereferenced.  -1 = a bad descriptor, or a force
+// outside [fmin, fmax] (-1 .. 2: the exact entries; 3 .. 4: the bf16 ones).
+static int rows_gemm_args(const qtts_rows_gemm_desc_t *d, int force, int fmin, int fmax, GemvArgs &a) {
+    if (!d || !d->A || !d->y || d->rows < 1 || d->R < 1 || d->C < 1 || force < fmin || force > fmax) return -1;
     if (d->epi < EPI_STORE || d->epi > EPI_SWIGLU || d->src < 0 || d->src > 1) return -1;
     if ((d->epi == EPI_BIAS || d->epi == EPI_BIAS_SILU) && !d->bias) return -1;
     if (d->src == 0 ? !d->x : (!d->table || !d->ids)) return -1;
@@ -445,11 +446,16 @@ static int rows_gemm_args(const qtts_rows_gemm_desc_t *d, int force, GemvArgs &a
 }
 
 // The plan of one multi-row projection under `force` (qtts_hip.h): pgemm's
-// where it is asked for (or dispatched to) and covers, else mgemm's.
-// 0 planned, 1 not covered.
+// (3 / 4: the one-plane pgemmh's) where it is asked for (or dispatched to) and
+// covers, else mgemm's.  0 planned, 1 not covered.
 static int rows_gemm_plan(const GemvArgs &a, bool has_inv, bool has_part, size_t part_elems, bool has_planes,
                           size_t plane_elems, int force, bool &use_pgemm, PgPlan &pp, MgPlan &mp) {
     use_pgemm = false;
+    if (force >= 3) {
+        const int rc = qtts_pgemmh_plan(a, has_planes, plane_elems, has_part, part_elems, force == 3 ? 128 : 256, pp);
+        use_pgemm = rc == 0;
+        return rc;
+    }
     if (force >= 1 || (force < 0 && a.nb > 16)) {
         const int bn = force == 1 ? 128 : force == 2 ? 256 : qtts_pgemm_bn_env();
         const int rc = qtts_pgemm_plan(a, has_planes, plane_elems, has_part, part_elems, bn, pp);
@@ -465,13 +471,13 @@ static void rows_gemm_report(bool use_pgemm, const PgPlan &pp, const MgPlan &mp,
     out->kernel = use_pgemm ? pp.kernel : mp.kernel;
     out->kz = use_pgemm ? pp.kz : mp.kz;
     out->grid_x = (int)g.x; out->grid_y = (int)g.y; out->grid_z = (int)g.z;
-    out->block = use_pgemm && pp.kernel == RG_PGEMM_4 ? 512 : 256;
+    out->block = use_pgemm && (pp.kernel == RG_PGEMM_4 || pp.kernel == RG_PGEMMH_4) ? 512 : 256;
 }
 
-extern "C" int qtts_hip_rows_gemm_plan(const qtts_rows_gemm_desc_t *d, size_t part_elems, size_t plane_elems,
-                                       int force, qtts_rows_gemm_plan_t *plan_out) {
+static int rows_gemm_plan_entry(const qtts_rows_gemm_desc_t *d, size_t part_elems, size_t plane_elems, int force,
+                                int fmin, int fmax, qtts_rows_gemm_plan_t *plan_out) {
     GemvArgs a;
-    if (!plan_out || rows_gemm_args(d, force, a)) return -1;
+    if (!plan_out || rows_gemm_args(d, force, fmin, fmax, a)) return -1;
     *plan_out = qtts_rows_gemm_plan_t();
     bool use_pgemm;
     PgPlan pp;
@@ -483,12 +489,21 @@ extern "C" int qtts_hip_rows_gemm_plan(const qtts_rows_gemm_desc_t *d, size_t pa
     return 0;
 }
 
+extern "C" int qtts_hip_rows_gemm_plan(const qtts_rows_gemm_desc_t *d, size_t part_elems, size_t plane_elems,
+                                       int force, qtts_rows_gemm_plan_t *plan_out) {
+    return rows_gemm_plan_entry(d, part_elems, plane_elems, force, -1, 2, plan_out);
+}
+extern "C" int qtts_hip_rows_gemm_bf16_plan(const qtts_rows_gemm_desc_t *d, size_t part_elems, size_t plane_elems,
+                                            int force, qtts_rows_gemm_plan_t *plan_out) {
+    return rows_gemm_plan_entry(d, part_elems, plane_elems, force, 3, 4, plan_out);
+}
+
 // One multi-row projection on its own, through the launchers themselves
 // (which plan again from the same arguments: the report is their plan).
-extern "C" int qtts_hip_rows_gemm_case(const qtts_rows_gemm_desc_t *d, int force, qtts_rows_gemm_plan_t *plan_out,
-                                       void *stream) {
+static int rows_gemm_case_entry(const qtts_rows_gemm_desc_t *d, int force, int fmin, int fmax,
+                                qtts_rows_gemm_plan_t *plan_out, void *stream) {
     GemvArgs a;
-    if (rows_gemm_args(d, force, a)) return -1;
+    if (rows_gemm_args(d, force, fmin, fmax, a)) return -1;
     if (plan_out) *plan_out = qtts_rows_gemm_plan_t();
     if (d->norm_w && !d->inv) return -1;
     if ((d->part_elems > 0 && !d->part) || (d->plane_elems > 0 && !d->planes)) return -1;
@@ -501,7 +516,9 @@ extern "C" int qtts_hip_rows_gemm_case(const qtts_rows_gemm_desc_t *d, int force
                             force, use_pgemm, pp, mp);
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
-    if (use_pgemm)
+    if (use_pgemm && force >= 3)
+        rc = qtts_pgemmh(a, planes, d->plane_elems, st, part, d->part_elems, pp.BN);
+    else if (use_pgemm)
         rc = qtts_pgemm(a, d->inv, planes, d->plane_elems, st, part, d->part_elems, pp.BN);
     else
         rc = qtts_mgemm(a, d->inv, st, part, d->part_elems);
@@ -509,4 +526,12 @@ extern "C" int qtts_hip_rows_gemm_case(const qtts_rows_gemm_desc_t *d, int force
     if (hipStreamSynchronize(st) != hipSuccess) rc = -1;
     if (!rc) rows_gemm_report(use_pgemm, pp, mp, plan_out);
     return rc;
+}
+extern "C" int qtts_hip_rows_gemm_case(const qtts_rows_gemm_desc_t *d, int force, qtts_rows_gemm_plan_t *plan_out,
+                                       void *stream) {
+    return rows_gemm_case_entry(d, force, -1, 2, plan_out, stream);
+}
+extern "C" int qtts_hip_rows_gemm_bf16_case(const qtts_rows_gemm_desc_t *d, int force, qtts_rows_gemm_plan_t *plan_out,
+                                            void *stream) {
+    return rows_gemm_case_entry(d, force, 3, 4, plan_out, stream);
 }

@@ -67,6 +67,9 @@ static void usage(const char *prog) {
             "                      bf16, one matrix instruction per product instead of six; codes unchanged)\n"
             "  --codec-linears exact|bf16 (codec transformer / ConvNeXt linear arithmetic, default exact; bf16 rounds\n"
             "                      weights and inputs to bf16 on one matrix instruction per product; codes unchanged)\n"
+            "  --prefill exact|bf16 (talker prefill projections over more than 16 rows, default exact; bf16 rounds the\n"
+            "                      normalised activations to bf16, one matrix instruction per product instead of three;\n"
+            "                      codes then no longer bit-exact against the reference)\n"
             "  --force-codes <file>  continue on these codes, 16 ints per frame as --ref-codes reads them\n"
             "                      (-1: leave that draw free; later frames are free), qwen_tts_force_codes\n"
             "  --dump-drawn <file> write the id the sampler itself drew at every draw in that format\n"
@@ -254,6 +257,7 @@ int main(int argc, char **argv) {
     int verbose = 0, runs = 1, warmup = 0, device = -1, batch = 1, stream_chunk = 0, non_streaming = 0;
     int codec_prec = -1; /* --codec: -1 = the library's default ($QTTS_HIP_CODEC or exact) */
     int codec_lin = -1;  /* --codec-linears: -1 = the library's default ($QTTS_HIP_CODEC_LIN or exact) */
+    int prefill_prec = -1; /* --prefill: -1 = the library's default ($QTTS_HIP_PREFILL or exact) */
     int kv_cache = -1;   /* --kv-cache: -1 = the library's default ($QTTS_HIP_KV or fp32) */
     const char *ref_codes_file = NULL, *ref_text = NULL, *xvec_file = NULL, *text = NULL, *ref_audio = NULL;
     int print_ids = 0, xvec_only = 0, stdin_ids = 0;
@@ -312,6 +316,12 @@ int main(int argc, char **argv) {
             if (!strcmp(v, "bf16")) codec_lin = QWEN_TTS_CODEC_BF16;
             else if (!strcmp(v, "exact")) codec_lin = QWEN_TTS_CODEC_EXACT;
             else { fprintf(stderr, "Error: --codec-linears takes exact or bf16\n\n"); usage(argv[0]); return 1; }
+        }
+        else if (ARG("--prefill")) {
+            const char *v = argv[++i];
+            if (!strcmp(v, "bf16")) prefill_prec = QWEN_TTS_PREFILL_BF16;
+            else if (!strcmp(v, "exact")) prefill_prec = QWEN_TTS_PREFILL_EXACT;
+            else { fprintf(stderr, "Error: --prefill takes exact or bf16\n\n"); usage(argv[0]); return 1; }
         }
         else if (ARG("--ref-codes")) ref_codes_file = argv[++i];
         else if (ARG("--force-codes")) force_file = argv[++i];
@@ -461,6 +471,11 @@ int main(int argc, char **argv) {
     }
     if (codec_lin >= 0 && qwen_tts_set_codec_linear_precision(ctx, codec_lin) != 0) {
         fprintf(stderr, "Error: cannot select the codec linear precision\n");
+        qwen_tts_free(ctx); free(ref_codes); free(xvec); free(file_ids);
+        return 1;
+    }
+    if (prefill_prec >= 0 && qwen_tts_set_prefill_precision(ctx, prefill_prec) != 0) {
+        fprintf(stderr, "Error: cannot select the prefill precision\n");
         qwen_tts_free(ctx); free(ref_codes); free(xvec); free(file_ids);
         return 1;
     }

@@ -140,6 +140,9 @@ EXPORTS = [
     "qtts_hip_rows_gemm_plan", "qtts_hip_rows_gemm_case",
     "qtts_hip_econv_plan", "qtts_hip_econv_case", "qtts_hip_enc_op", "qtts_hip_enc_func", "qtts_hip_codec_op",
     "qtts_hip_attn_tiled", "qtts_hip_attn_tile_launches",
+    "qwen_tts_set_prefill_precision", "qwen_tts_prefill_precision", "qtts_dev_set_prefill_precision",
+    "qtts_dev_prefill_precision", "qtts_hip_pgemmh_launches",
+    "qtts_hip_rows_gemm_bf16_plan", "qtts_hip_rows_gemm_bf16_case",
 ]
 
 MAX_BATCH = 64   # QWEN_TTS_MAX_BATCH / QTTS_HIP_MAX_BATCH: lock-step slots per context
@@ -235,6 +238,7 @@ class RowsGemmPlan(C.Structure):
 
 # qtts_rows_gemm_plan_t.kernel (QTTS_RG_* of qtts_hip.h)
 RG_NAMES = ["k_mgemm<1,1>", "k_mgemm<2,1>", "k_mgemm<4,1>", "k_mgemm<4,2>", "k_mgemm<4,4>", "k_pgemm<2>", "k_pgemm<4>"]
+RG_NAMES_BF16 = ["k_pgemmh<2>", "k_pgemmh<4>"]   # QTTS_RG_PGEMMH_2 / _4 (7, 8): the one-plane prefill GEMM
 
 
 class EConvDesc(C.Structure):
@@ -316,6 +320,7 @@ MAX_TAPS = 8   # taps per run (qwen_tts_tap_draw)
 
 KV_F32, KV_BF16 = 0, 1   # QWEN_TTS_KV_F32 / QWEN_TTS_KV_BF16
 CODEC_EXACT, CODEC_BF16 = 0, 1   # QWEN_TTS_CODEC_EXACT / QWEN_TTS_CODEC_BF16
+PREFILL_EXACT, PREFILL_BF16 = 0, 1   # QWEN_TTS_PREFILL_EXACT / QWEN_TTS_PREFILL_BF16
 
 _LIB = None
 
@@ -559,6 +564,22 @@ def lib():
         L.qtts_dev_set_codec_linear_precision.argtypes = [C.c_void_p, C.c_int]
         L.qtts_dev_codec_linear_precision.restype = C.c_int
         L.qtts_dev_codec_linear_precision.argtypes = [C.c_void_p]
+    if hasattr(L, "qwen_tts_set_prefill_precision"):   # (nor a prefill precision)
+        L.qwen_tts_set_prefill_precision.restype = C.c_int
+        L.qwen_tts_set_prefill_precision.argtypes = [C.POINTER(Ctx), C.c_int]
+        L.qwen_tts_prefill_precision.restype = C.c_int
+        L.qwen_tts_prefill_precision.argtypes = [C.POINTER(Ctx)]
+        L.qtts_dev_set_prefill_precision.restype = C.c_int
+        L.qtts_dev_set_prefill_precision.argtypes = [C.c_void_p, C.c_int]
+        L.qtts_dev_prefill_precision.restype = C.c_int
+        L.qtts_dev_prefill_precision.argtypes = [C.c_void_p]
+        L.qtts_hip_pgemmh_launches.restype = C.c_longlong
+        L.qtts_hip_pgemmh_launches.argtypes = []
+        L.qtts_hip_rows_gemm_bf16_plan.restype = C.c_int
+        L.qtts_hip_rows_gemm_bf16_plan.argtypes = [C.POINTER(RowsGemmDesc), C.c_size_t, C.c_size_t, C.c_int,
+                                                   C.POINTER(RowsGemmPlan)]
+        L.qtts_hip_rows_gemm_bf16_case.restype = C.c_int
+        L.qtts_hip_rows_gemm_bf16_case.argtypes = [C.POINTER(RowsGemmDesc), C.c_int, C.POINTER(RowsGemmPlan), C.c_void_p]
     L.qtts_dev_set_kv_dtype.restype = C.c_int
     L.qtts_dev_set_kv_dtype.argtypes = [C.c_void_p, C.c_int]
     L.qtts_dev_kv_dtype.restype = C.c_int
@@ -760,6 +781,19 @@ class QwenTTS:
 
     def codec_linear_precision(self):
         return lib().qwen_tts_codec_linear_precision(self.ctx)
+
+    def set_prefill_precision(self, precision):
+        """Arithmetic of the talker prefill's projections over more than 16
+        rows, from the next prefill call on: "exact" / PREFILL_EXACT (default,
+        ids bit-exact against the reference) or "bf16" / PREFILL_BF16 (the
+        activations rounded to one bf16 plane on k_pgemmh;
+        qwen_tts_set_prefill_precision)."""
+        v = {"exact": PREFILL_EXACT, "bf16": PREFILL_BF16}.get(precision, precision)
+        if not isinstance(v, int) or lib().qwen_tts_set_prefill_precision(self.ctx, v) != 0:
+            raise ValueError(f"prefill precision {precision!r} (exact or bf16)")
+
+    def prefill_precision(self):
+        return lib().qwen_tts_prefill_precision(self.ctx)
 
     def state_bytes(self):
         """device bytes of the generation state (qtts_dev_bytes(dev, 1))"""
@@ -1639,6 +1673,11 @@ class Kernels:
         return int(L.qtts_hip_attn_tile_launches())
 
     @staticmethod
+    def pgemmh_launches():
+        """k_pgemmh launches since the library loaded (qtts_hip_pgemmh_launches)"""
+        return int(lib().qtts_hip_pgemmh_launches())
+
+    @staticmethod
     def attn_o(part, qkv, kc, vc, qn_w, kn_w, rope_cos, rope_sin, pos_i32, Wo_u16, R, NH, KV, HD, S, rows, eps):
         """The sub-talker's attention + O projection by kv head
         (qtts_hip_attn_o): part [KV, rows, R].  False where the kernel does
@@ -1739,7 +1778,7 @@ class Kernels:
         if rc == 1:
             return None
         _ok(rc, who)
-        return dict(kernel=RG_NAMES[p.kernel], kz=p.kz, grid=[p.grid_x, p.grid_y, p.grid_z], block=p.block)
+        return dict(kernel=(RG_NAMES + RG_NAMES_BF16)[p.kernel], kz=p.kz, grid=[p.grid_x, p.grid_y, p.grid_z], block=p.block)
 
     @staticmethod
     def rows_gemm_plan(desc, part_elems=0, plane_elems=0, force=-1):
@@ -1747,10 +1786,12 @@ class Kernels:
         workspace of part_elems floats and plane_elems bf16 of plane scratch
         (qtts_hip_rows_gemm_plan; host only, no device needed).  force -1: the
         prefill's dispatch, 0: qtts_mgemm, 1 / 2: qtts_pgemm at tile width 128 /
-        256.  A dict with the kernel's name, kz, grid and block, or None where
+        256, 3 / 4: the one-plane qtts_pgemmh at 128 / 256 (through
+        qtts_hip_rows_gemm_bf16_plan: to the exact entry 3 is an argument error).  A dict with the kernel's name, kz, grid and block, or None where
         the (forced) launcher does not cover the shape."""
         p = RowsGemmPlan()
-        rc = lib().qtts_hip_rows_gemm_plan(C.byref(desc), part_elems, plane_elems, force, C.byref(p))
+        fn = lib().qtts_hip_rows_gemm_bf16_plan if force >= 3 else lib().qtts_hip_rows_gemm_plan
+        rc = fn(C.byref(desc), part_elems, plane_elems, force, C.byref(p))
         return Kernels._rows_gemm_result(rc, p, "rows_gemm_plan")
 
     @staticmethod
@@ -1759,7 +1800,8 @@ class Kernels:
         descriptor's own scratch: the plan that ran, or None where the (forced)
         launcher does not cover the shape (nothing ran)."""
         p = RowsGemmPlan()
-        rc = lib().qtts_hip_rows_gemm_case(C.byref(desc), force, C.byref(p), _stream())
+        fn = lib().qtts_hip_rows_gemm_bf16_case if force >= 3 else lib().qtts_hip_rows_gemm_case
+        rc = fn(C.byref(desc), force, C.byref(p), _stream())
         return Kernels._rows_gemm_result(rc, p, "rows_gemm_case")
 
     @staticmethod
