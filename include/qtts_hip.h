@@ -126,6 +126,17 @@ int qtts_dev_codec_linear_precision(const qtts_dev_t *dev);
 int qtts_dev_set_prefill_precision(qtts_dev_t *dev, int precision);
 int qtts_dev_prefill_precision(const qtts_dev_t *dev);
 long long qtts_hip_pgemmh_launches(void);
+/* Precision of the talker prefill's tiled attention (a call with a slot of at
+ * least QTTS_HIP_ATTN_TILE rows, default 256): 0 exact (default, or
+ * $QTTS_HIP_PREFILL_ATTN at creation: k_attn_tile on the fp32 matrix cores), 1
+ * bf16 (k_attn_tileh: q, K, V and the probabilities rounded to bf16, one
+ * v_mfma_f32_16x16x32_bf16 where the exact kernel issues eight fp32 ones;
+ * softmax state and sums fp32).  The K / V written to the cache, the row-by-row
+ * path below the threshold and decode are untouched.  Independent of the
+ * prefill precision above.  Read per prefill call; prefix cache entries are
+ * keyed by it.  -1 on a bad value. */
+int qtts_dev_set_prefill_attention_precision(qtts_dev_t *dev, int precision);
+int qtts_dev_prefill_attention_precision(const qtts_dev_t *dev);
 /* Diagnostics: talker cache rows [pos0, pos0 + n) of layer `layer`, slot b,
  * to the host as fp32 [n][KV*HD] each (bf16 widened exactly; k_host or v_host
  * may be NULL).  Waits for the context stream.  -1 out of range. */
@@ -171,7 +182,7 @@ int qtts_dev_prompt(qtts_dev_t *dev, int b, const int *text_ids, int n_text, con
  * holds: the prefix rows alone (computed once per distinct prefix and saved,
  * afterwards copied back: one launch), then the remaining rows at their own
  * positions.  One cache per device model, keyed by the exact id sequence,
- * the KV element type and the prefill precision, LRU, QTTS_HIP_PREFIX_CACHE entries (read at creation,
+ * the KV element type and the two prefill precisions (projections, attention), LRU, QTTS_HIP_PREFIX_CACHE entries (read at creation,
  * default 16, 0: off -- the prefix rows are then ordinary rows of the one
  * pass).  An entry holds rows [0, n) of all layers, [2][L][n][KV*HD]; entries
  * survive qtts_dev_begin and state re-allocation, a change of the KV element
@@ -657,6 +668,21 @@ int qtts_hip_attn_tiled(float *out_dev, float *q_dev, int ld_q, void *kc_dev, vo
                         const int *seg_table_dev, int nseg, int NH, int KV, int HD, int S, int slots,
                         int rows, float eps, int win, int kv_dtype, int prep, void *stream);
 long long qtts_hip_attn_tile_launches(void);
+/* The same call on the bf16 matrix cores (k_attn_tileh, the kernel of the
+ * bf16 prefill attention precision): the argument list, the prep step, the
+ * coverage and the return codes of qtts_hip_attn_tiled.  q is rounded to bf16
+ * (nearest even) as it is loaded, K and V as they enter LDS (a bf16 cache's
+ * bits go in as they are), the probabilities before the P V product; scores,
+ * scale, mask, max, exp, row sums (of the rounded probabilities), accumulators
+ * and the division fp32.  Tiles of 64 positions, blocks of 64 keys.  q_dev and
+ * the caches are left exactly as qtts_hip_attn_tiled leaves them.
+ * qtts_hip_attn_tileh_launches: its launches since the library loaded. */
+int qtts_hip_attn_tiled_bf16(float *out_dev, float *q_dev, int ld_q, void *kc_dev, void *vc_dev,
+                             const float *qn_w_dev, const float *kn_w_dev,
+                             const float *rope_cos_dev, const float *rope_sin_dev,
+                             const int *seg_table_dev, int nseg, int NH, int KV, int HD, int S, int slots,
+                             int rows, float eps, int win, int kv_dtype, int prep, void *stream);
+long long qtts_hip_attn_tileh_launches(void);
 /* The sub-talker's attention + O projection by kv head (k_attn_o), fp32 caches
  * [rows][S][KV*HD], no id table: part_dev[(g * rows + r) * R + i] =
  * Wo[i, 2 HD g .. 2 HD (g + 1)) . attention of kv head g's two query heads;

@@ -286,6 +286,23 @@ int qwen_tts_codec_linear_precision(qwen_tts_ctx_t *ctx);
 #define QWEN_TTS_PREFILL_BF16  1
 int qwen_tts_set_prefill_precision(qwen_tts_ctx_t *ctx, int precision);
 int qwen_tts_prefill_precision(qwen_tts_ctx_t *ctx);
+/* Arithmetic of the talker prefill's attention when a prefill call holds a
+ * slot of 256 rows or more (the tiled attention; QTTS_HIP_ATTN_TILE moves the
+ * threshold).  QWEN_TTS_PREFILL_ATTN_EXACT (the default) multiplies on the fp32
+ * matrix cores.  QWEN_TTS_PREFILL_ATTN_BF16 rounds the query, the keys and
+ * values (as they are read from the cache: the cache itself is unchanged) and
+ * the softmax probabilities to bf16, nearest even, and multiplies on the bf16
+ * matrix cores; scores, softmax state, sums and the division stay fp32.  A
+ * switch of its own beside qwen_tts_set_prefill_precision: either may be on
+ * alone.  The ids are then no longer bit-exact against the reference -- only
+ * for prompts that reach the tiled path; shorter prefills and every decode
+ * step are untouched.  Read per prefill call; an instruct prefix cache entry
+ * is served only in the mode it was made in.  -1 on any other value.
+ * $QTTS_HIP_PREFILL_ATTN=bf16|exact sets the default of every ctx loaded after it. */
+#define QWEN_TTS_PREFILL_ATTN_EXACT 0
+#define QWEN_TTS_PREFILL_ATTN_BF16  1
+int qwen_tts_set_prefill_attention_precision(qwen_tts_ctx_t *ctx, int precision);
+int qwen_tts_prefill_attention_precision(qwen_tts_ctx_t *ctx);
 /* Most lock-step slots of one ctx (qwen_tts_generate_batch, the slots of
  * qwen_tts_generate_queue, qwen_tts_generate_voice_clone_batch): up to 16 run
  * on the 16-row matrix-core batch kernels, 17..64 on the wide batch kernel. */

@@ -171,13 +171,14 @@ struct qtts_dev {
     // pfx_ids[b] = the text ids of slot b's kind-2 plan rows (its prompt rows
     // [0, n), qtts_dev_prompt); an entry = those rows' K and V of all layers,
     // [2][L][n][KV*HD] in the element type it was saved from, keyed by the ids,
-    // that type and the prefill precision it was computed in.  Outside the decode state (sallocs): entries survive
+    // that type and the prefill precisions (projections, attention) it was computed in.  Outside the decode state (sallocs): entries survive
     // qtts_dev_begin and a re-allocation; a change of the KV element type drops
     // them (alloc_state), qtts_dev_destroy drops all.
     struct PrefixEntry {
         std::vector<int> ids;
         int dtype = 0;
         int pprec = 0;                 // prefill_prec of the pass that made it
+        int paprec = 0;                // its prefill_attn_prec
         void *buf = nullptr;
         size_t bytes = 0;
         unsigned long long used = 0;   // LRU stamp
@@ -300,6 +301,10 @@ struct qtts_dev {
     // planes, k_pgemm), 1 one bf16 plane (k_pgemmh).  Read per rows_proj call
     // (qtts_dev_set_prefill_precision, QTTS_HIP_PREFILL at creation).
     int prefill_prec = 0;
+    // precision of the prefill's tiled attention: 0 exact (k_attn_tile, fp32 matrix
+    // cores), 1 bf16 (k_attn_tileh).  Read per prefill_rows call
+    // (qtts_dev_set_prefill_attention_precision, QTTS_HIP_PREFILL_ATTN at creation).
+    int prefill_attn_prec = 0;
 
     int QKV() const { return (d.NH + 2 * d.KV) * d.HD; }
     int QKVs() const { return (d.NHs + 2 * d.KVs) * d.HDs; }

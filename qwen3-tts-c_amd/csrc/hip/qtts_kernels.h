@@ -253,6 +253,13 @@ struct AttnSeg {
 bool qtts_attn_tile_covers(const AttnArgs &a);
 int qtts_attn_tile(const AttnArgs &a, const AttnSeg *segs, int nseg, hipStream_t st);
 long long qtts_attn_tile_launches();   // launches since the library loaded
+// The same contract on the bf16 matrix cores (k_attn_tileh.hip, the opt-in
+// bf16 prefill attention precision): q, K, V and P rounded to bf16, scores,
+// softmax state, accumulators and the division fp32; tiles of 64 positions,
+// blocks of 64 keys
+bool qtts_attn_tileh_covers(const AttnArgs &a);
+int qtts_attn_tileh(const AttnArgs &a, const AttnSeg *segs, int nseg, hipStream_t st);
+long long qtts_attn_tileh_launches();
 // keys per split of the talker decode attention (deferred merge or not; lpk
 // as AttnArgs::lpk)
 int qtts_attn_keys_per_split(int HD, bool defer, int lpk);

@@ -816,6 +816,9 @@ int prefill_rows(qtts_dev *dv, const std::vector<int> &slots, const std::vector<
     bool tiled = dv->attn_tile_min > 0 && seg_max >= dv->attn_tile_min && (int)segs.size() <= dv->nb &&
                  qtts_attn_tile_covers(talker_attn(dv, 0, R, true));
     if (tiled) CK(hipMemcpyAsync(dv->pseg, segs.data(), segs.size() * sizeof(AttnSeg), hipMemcpyHostToDevice, st));
+    // the bf16 prefill attention precision (qtts_dev_set_prefill_attention_precision):
+    // the tiled launch on the bf16 matrix cores (k_attn_tileh.hip)
+    const bool tiledh = tiled && dv->prefill_attn_prec && qtts_attn_tileh_covers(talker_attn(dv, 0, R, true));
     for (int l = 0; l < d.L; ++l) {
         const LayerView lv = talker_view(dv, l, 0);
         CKI(rows_proj(dv, lv.qkv(dv->px, dv->pqkv, 1), R, true));
@@ -823,7 +826,10 @@ int prefill_rows(qtts_dev *dv, const std::vector<int> &slots, const std::vector<
         CKI(qtts_qk_prep(t, st));
         if (tiled) {
             t.seg_max = seg_max;
-            CKI(qtts_attn_tile(t, dv->pseg, (int)segs.size(), st));
+            if (tiledh)
+                CKI(qtts_attn_tileh(t, dv->pseg, (int)segs.size(), st));
+            else
+                CKI(qtts_attn_tile(t, dv->pseg, (int)segs.size(), st));
         } else
             CKI(qtts_attention(t, st));
         CKI(rows_proj(dv, lv.o(dv->patt, dv->px, 1), R, true));

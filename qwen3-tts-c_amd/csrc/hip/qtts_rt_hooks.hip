@@ -245,10 +245,13 @@ extern "C" int qtts_hip_attn_cached(float *out, float *q, int ld_q, void *kc, vo
 // filled.  1 = a shape qtts_attn_tile_covers refuses: nothing is written.
 extern "C" long long qtts_hip_attn_tile_launches(void) { return qtts_attn_tile_launches(); }
 
-extern "C" int qtts_hip_attn_tiled(float *out, float *q, int ld_q, void *kc, void *vc, const float *qn_w,
-                                   const float *kn_w, const float *rope_cos, const float *rope_sin,
-                                   const int *seg_table, int nseg, int NH, int KV, int HD, int S, int slots, int rows,
-                                   float eps, int win, int kv_dtype, int prep, void *stream) {
+extern "C" long long qtts_hip_attn_tileh_launches(void) { return qtts_attn_tileh_launches(); }
+
+// (bf16: k_attn_tileh behind qtts_hip_attn_tiled_bf16, else k_attn_tile)
+static int attn_tiled_entry(bool bf16, float *out, float *q, int ld_q, void *kc, void *vc, const float *qn_w,
+                            const float *kn_w, const float *rope_cos, const float *rope_sin, const int *seg_table,
+                            int nseg, int NH, int KV, int HD, int S, int slots, int rows, float eps, int win,
+                            int kv_dtype, int prep, void *stream) {
     if (!out || !q || !kc || !vc || !seg_table || nseg < 1 || nseg > 65535) return -1;
     if (prep != 0 && prep != 1) return -1;
     if (prep && (!qn_w || !kn_w || !rope_cos || !rope_sin)) return -1;
@@ -260,7 +263,7 @@ extern "C" int qtts_hip_attn_tiled(float *out, float *q, int ld_q, void *kc, voi
     t.rope_cos = rope_cos; t.rope_sin = rope_sin;
     t.kc = (float *)kc; t.vc = (float *)vc; t.S = S; t.kv_dtype = kv_dtype;
     t.NH = NH; t.KV = KV; t.HD = HD; t.out = out; t.ld_out = NH * HD; t.nrows = rows; t.win = win;
-    if (!qtts_attn_tile_covers(t)) return 1;   // (before the cache writes)
+    if (!(bf16 ? qtts_attn_tileh_covers(t) : qtts_attn_tile_covers(t))) return 1;   // (before the cache writes)
     // the table on the host: every segment inside the rows, the slots and the
     // cache (the kernels index by it unchecked), no row in two segments
     std::vector<AttnSeg> sg(nseg);
@@ -292,10 +295,25 @@ extern "C" int qtts_hip_attn_tiled(float *out, float *q, int ld_q, void *kc, voi
         t.row_b = tab; t.pos = tab + rows;
         if (!rc) rc = qtts_qk_prep(t, st);
     }
-    if (!rc) rc = qtts_attn_tile(t, reinterpret_cast<const AttnSeg *>(seg_table), nseg, st);
+    if (!rc) rc = (bf16 ? qtts_attn_tileh : qtts_attn_tile)(t, reinterpret_cast<const AttnSeg *>(seg_table), nseg, st);
     if (hipStreamSynchronize(st) != hipSuccess) rc = -1;
     if (tab) hipFree(tab);
     return rc;
+}
+
+extern "C" int qtts_hip_attn_tiled(float *out, float *q, int ld_q, void *kc, void *vc, const float *qn_w,
+                                   const float *kn_w, const float *rope_cos, const float *rope_sin,
+                                   const int *seg_table, int nseg, int NH, int KV, int HD, int S, int slots, int rows,
+                                   float eps, int win, int kv_dtype, int prep, void *stream) {
+    return attn_tiled_entry(false, out, q, ld_q, kc, vc, qn_w, kn_w, rope_cos, rope_sin, seg_table, nseg, NH, KV, HD, S,
+                            slots, rows, eps, win, kv_dtype, prep, stream);
+}
+extern "C" int qtts_hip_attn_tiled_bf16(float *out, float *q, int ld_q, void *kc, void *vc, const float *qn_w,
+                                        const float *kn_w, const float *rope_cos, const float *rope_sin,
+                                        const int *seg_table, int nseg, int NH, int KV, int HD, int S, int slots,
+                                        int rows, float eps, int win, int kv_dtype, int prep, void *stream) {
+    return attn_tiled_entry(true, out, q, ld_q, kc, vc, qn_w, kn_w, rope_cos, rope_sin, seg_table, nseg, NH, KV, HD, S,
+                            slots, rows, eps, win, kv_dtype, prep, stream);
 }
 
 // The sub-talker's attention + O projection by kv head (k_attn_o) on its own:

@@ -333,6 +333,12 @@ extern "C" qtts_dev_t *qtts_dev_create(const qtts_dims_t *dims, int device) {
         if (!strcmp(ppr, "bf16")) dv->prefill_prec = 1;
         else if (strcmp(ppr, "exact")) fprintf(stderr, "qtts: QTTS_HIP_PREFILL=%s ignored (bf16 or exact)\n", ppr);
     }
+    // QTTS_HIP_PREFILL_ATTN=bf16|exact: the prefill's tiled attention precision (default exact)
+    const char *pap = getenv("QTTS_HIP_PREFILL_ATTN");
+    if (pap && *pap) {
+        if (!strcmp(pap, "bf16")) dv->prefill_attn_prec = 1;
+        else if (strcmp(pap, "exact")) fprintf(stderr, "qtts: QTTS_HIP_PREFILL_ATTN=%s ignored (bf16 or exact)\n", pap);
+    }
     // QTTS_HIP_PREFIX_CACHE=<entries>: the instruct prefix cache's capacity (default 16, 0 off)
     const char *pc = getenv("QTTS_HIP_PREFIX_CACHE");
     if (pc && *pc) dv->pfx_cap = atoi(pc) < 0 ? 0 : atoi(pc);
@@ -444,6 +450,14 @@ extern "C" int qtts_dev_set_prefill_precision(qtts_dev_t *dv, int precision) {
 }
 
 extern "C" int qtts_dev_prefill_precision(const qtts_dev_t *dv) { return dv ? dv->prefill_prec : -1; }
+
+extern "C" int qtts_dev_set_prefill_attention_precision(qtts_dev_t *dv, int precision) {
+    if (!dv || (precision != 0 && precision != 1)) return -1;
+    dv->prefill_attn_prec = precision;   // (read by the next prefill call; prefix entries carry their own)
+    return 0;
+}
+
+extern "C" int qtts_dev_prefill_attention_precision(const qtts_dev_t *dv) { return dv ? dv->prefill_attn_prec : -1; }
 
 extern "C" int qtts_dev_set_codec_precision(qtts_dev_t *dv, int precision) {
     if (!dv || (precision != 0 && precision != 1)) return -1;
@@ -987,7 +1001,8 @@ static int prefix_stages(qtts_dev *dv, const std::vector<int> &slots, std::vecto
         const int n = (int)ids.size();
         qtts_dev::PrefixEntry *hit = nullptr;
         for (auto &e : dv->pfx)
-            if (e.dtype == dv->kv_dtype && e.pprec == dv->prefill_prec && e.ids == ids) hit = &e;
+            if (e.dtype == dv->kv_dtype && e.pprec == dv->prefill_prec && e.paprec == dv->prefill_attn_prec && e.ids == ids)
+                hit = &e;
         if (hit) {
             ++g_prefix_hits;
             hit->used = ++dv->pfx_clock;
@@ -999,7 +1014,8 @@ static int prefix_stages(qtts_dev *dv, const std::vector<int> &slots, std::vecto
             CK(hipStreamSynchronize(dv->st));   // (the pass's row lists are host vectors; a miss only)
             prefix_evict(dv, (size_t)dv->pfx_cap - 1);
             qtts_dev::PrefixEntry e;
-            e.ids = ids; e.dtype = dv->kv_dtype; e.pprec = dv->prefill_prec; e.used = ++dv->pfx_clock;
+            e.ids = ids; e.dtype = dv->kv_dtype; e.pprec = dv->prefill_prec; e.paprec = dv->prefill_attn_prec;
+            e.used = ++dv->pfx_clock;
             e.bytes = (size_t)2 * dv->d.L * n * dv->d.KV * dv->d.HD * dv->kv_esz();
             if (hipMalloc(&e.buf, e.bytes) != hipSuccess) {
                 fprintf(stderr, "qtts: no memory for a prefix cache entry of %zu bytes\n", e.bytes);

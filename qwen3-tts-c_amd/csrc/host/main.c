@@ -70,6 +70,9 @@ static void usage(const char *prog) {
             "  --prefill exact|bf16 (talker prefill projections over more than 16 rows, default exact; bf16 rounds the\n"
             "                      normalised activations to bf16, one matrix instruction per product instead of three;\n"
             "                      codes then no longer bit-exact against the reference)\n"
+            "  --prefill-attn exact|bf16 (tiled attention of talker prefills of 256 rows and more per slot, default exact;\n"
+            "                      bf16 rounds q, K, V and the probabilities to bf16 on the bf16 matrix instruction;\n"
+            "                      codes then no longer bit-exact against the reference)\n"
             "  --force-codes <file>  continue on these codes, 16 ints per frame as --ref-codes reads them\n"
             "                      (-1: leave that draw free; later frames are free), qwen_tts_force_codes\n"
             "  --dump-drawn <file> write the id the sampler itself drew at every draw in that format\n"
@@ -258,6 +261,7 @@ int main(int argc, char **argv) {
     int codec_prec = -1; /* --codec: -1 = the library's default ($QTTS_HIP_CODEC or exact) */
     int codec_lin = -1;  /* --codec-linears: -1 = the library's default ($QTTS_HIP_CODEC_LIN or exact) */
     int prefill_prec = -1; /* --prefill: -1 = the library's default ($QTTS_HIP_PREFILL or exact) */
+    int prefill_attn = -1; /* --prefill-attn: -1 = the library's default ($QTTS_HIP_PREFILL_ATTN or exact) */
     int kv_cache = -1;   /* --kv-cache: -1 = the library's default ($QTTS_HIP_KV or fp32) */
     const char *ref_codes_file = NULL, *ref_text = NULL, *xvec_file = NULL, *text = NULL, *ref_audio = NULL;
     int print_ids = 0, xvec_only = 0, stdin_ids = 0;
@@ -322,6 +326,12 @@ int main(int argc, char **argv) {
             if (!strcmp(v, "bf16")) prefill_prec = QWEN_TTS_PREFILL_BF16;
             else if (!strcmp(v, "exact")) prefill_prec = QWEN_TTS_PREFILL_EXACT;
             else { fprintf(stderr, "Error: --prefill takes exact or bf16\n\n"); usage(argv[0]); return 1; }
+        }
+        else if (ARG("--prefill-attn")) {
+            const char *v = argv[++i];
+            if (!strcmp(v, "bf16")) prefill_attn = QWEN_TTS_PREFILL_ATTN_BF16;
+            else if (!strcmp(v, "exact")) prefill_attn = QWEN_TTS_PREFILL_ATTN_EXACT;
+            else { fprintf(stderr, "Error: --prefill-attn takes exact or bf16\n\n"); usage(argv[0]); return 1; }
         }
         else if (ARG("--ref-codes")) ref_codes_file = argv[++i];
         else if (ARG("--force-codes")) force_file = argv[++i];
@@ -476,6 +486,11 @@ int main(int argc, char **argv) {
     }
     if (prefill_prec >= 0 && qwen_tts_set_prefill_precision(ctx, prefill_prec) != 0) {
         fprintf(stderr, "Error: cannot select the prefill precision\n");
+        qwen_tts_free(ctx); free(ref_codes); free(xvec); free(file_ids);
+        return 1;
+    }
+    if (prefill_attn >= 0 && qwen_tts_set_prefill_attention_precision(ctx, prefill_attn) != 0) {
+        fprintf(stderr, "Error: cannot select the prefill attention precision\n");
         qwen_tts_free(ctx); free(ref_codes); free(xvec); free(file_ids);
         return 1;
     }

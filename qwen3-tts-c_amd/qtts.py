@@ -143,6 +143,9 @@ EXPORTS = [
     "qwen_tts_set_prefill_precision", "qwen_tts_prefill_precision", "qtts_dev_set_prefill_precision",
     "qtts_dev_prefill_precision", "qtts_hip_pgemmh_launches",
     "qtts_hip_rows_gemm_bf16_plan", "qtts_hip_rows_gemm_bf16_case",
+    "qwen_tts_set_prefill_attention_precision", "qwen_tts_prefill_attention_precision",
+    "qtts_dev_set_prefill_attention_precision", "qtts_dev_prefill_attention_precision",
+    "qtts_hip_attn_tiled_bf16", "qtts_hip_attn_tileh_launches",
 ]
 
 MAX_BATCH = 64   # QWEN_TTS_MAX_BATCH / QTTS_HIP_MAX_BATCH: lock-step slots per context
@@ -321,6 +324,7 @@ MAX_TAPS = 8   # taps per run (qwen_tts_tap_draw)
 KV_F32, KV_BF16 = 0, 1   # QWEN_TTS_KV_F32 / QWEN_TTS_KV_BF16
 CODEC_EXACT, CODEC_BF16 = 0, 1   # QWEN_TTS_CODEC_EXACT / QWEN_TTS_CODEC_BF16
 PREFILL_EXACT, PREFILL_BF16 = 0, 1   # QWEN_TTS_PREFILL_EXACT / QWEN_TTS_PREFILL_BF16
+PREFILL_ATTN_EXACT, PREFILL_ATTN_BF16 = 0, 1   # QWEN_TTS_PREFILL_ATTN_EXACT / QWEN_TTS_PREFILL_ATTN_BF16
 
 _LIB = None
 
@@ -580,6 +584,17 @@ def lib():
                                                    C.POINTER(RowsGemmPlan)]
         L.qtts_hip_rows_gemm_bf16_case.restype = C.c_int
         L.qtts_hip_rows_gemm_bf16_case.argtypes = [C.POINTER(RowsGemmDesc), C.c_int, C.POINTER(RowsGemmPlan), C.c_void_p]
+    if hasattr(L, "qwen_tts_set_prefill_attention_precision"):   # (nor a prefill attention precision)
+        L.qwen_tts_set_prefill_attention_precision.restype = C.c_int
+        L.qwen_tts_set_prefill_attention_precision.argtypes = [C.POINTER(Ctx), C.c_int]
+        L.qwen_tts_prefill_attention_precision.restype = C.c_int
+        L.qwen_tts_prefill_attention_precision.argtypes = [C.POINTER(Ctx)]
+        L.qtts_dev_set_prefill_attention_precision.restype = C.c_int
+        L.qtts_dev_set_prefill_attention_precision.argtypes = [C.c_void_p, C.c_int]
+        L.qtts_dev_prefill_attention_precision.restype = C.c_int
+        L.qtts_dev_prefill_attention_precision.argtypes = [C.c_void_p]
+        L.qtts_hip_attn_tileh_launches.restype = C.c_longlong
+        L.qtts_hip_attn_tileh_launches.argtypes = []
     L.qtts_dev_set_kv_dtype.restype = C.c_int
     L.qtts_dev_set_kv_dtype.argtypes = [C.c_void_p, C.c_int]
     L.qtts_dev_kv_dtype.restype = C.c_int
@@ -794,6 +809,19 @@ class QwenTTS:
 
     def prefill_precision(self):
         return lib().qwen_tts_prefill_precision(self.ctx)
+
+    def set_prefill_attention_precision(self, precision):
+        """Arithmetic of the talker prefill's tiled attention (calls with a slot
+        of 256 rows or more), from the next prefill call on: "exact" /
+        PREFILL_ATTN_EXACT (default, ids bit-exact against the reference) or
+        "bf16" / PREFILL_ATTN_BF16 (q, K, V and the probabilities rounded to
+        bf16 on k_attn_tileh; qwen_tts_set_prefill_attention_precision)."""
+        v = {"exact": PREFILL_ATTN_EXACT, "bf16": PREFILL_ATTN_BF16}.get(precision, precision)
+        if not isinstance(v, int) or lib().qwen_tts_set_prefill_attention_precision(self.ctx, v) != 0:
+            raise ValueError(f"prefill attention precision {precision!r} (exact or bf16)")
+
+    def prefill_attention_precision(self):
+        return lib().qwen_tts_prefill_attention_precision(self.ctx)
 
     def state_bytes(self):
         """device bytes of the generation state (qtts_dev_bytes(dev, 1))"""
@@ -1646,23 +1674,39 @@ class Kernels:
                                        slots, rows, eps, win, kv_dtype, prep, _stream()), "attn_cached")
 
     @staticmethod
-    def attn_tiled(out, q, ld_q, kc, vc, qn_w, kn_w, rope_cos, rope_sin, seg_table_i32, nseg, NH, KV, HD, S, slots,
-                   rows, eps, win=0, kv_dtype=0, prep=0):
-        """The tiled causal attention (qtts_hip_attn_tiled) over seg_table
-        [nseg, 4] = {slot, first row, first position, count}; prep as
-        attn_cached.  False where the kernel does not cover the shape
-        (nothing ran)."""
-        L = lib()
-        L.qtts_hip_attn_tiled.restype = C.c_int
-        L.qtts_hip_attn_tiled.argtypes = ([C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 7 + [C.c_int] * 7 +
-                                          [C.c_float] + [C.c_int] * 3 + [C.c_void_p])
-        rc = L.qtts_hip_attn_tiled(_ptr(out), _ptr(q), ld_q, _ptr(kc), _ptr(vc), _ptr(qn_w), _ptr(kn_w),
-                                   _ptr(rope_cos), _ptr(rope_sin), _ptr(seg_table_i32), nseg, NH, KV, HD, S, slots,
-                                   rows, eps, win, kv_dtype, prep, _stream())
+    def _attn_tiled(entry, out, q, ld_q, kc, vc, qn_w, kn_w, rope_cos, rope_sin, seg_table_i32, nseg, NH, KV, HD, S,
+                    slots, rows, eps, win=0, kv_dtype=0, prep=0):
+        fn = getattr(lib(), entry)
+        fn.restype = C.c_int
+        fn.argtypes = ([C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 7 + [C.c_int] * 7 +
+                       [C.c_float] + [C.c_int] * 3 + [C.c_void_p])
+        rc = fn(_ptr(out), _ptr(q), ld_q, _ptr(kc), _ptr(vc), _ptr(qn_w), _ptr(kn_w),
+                _ptr(rope_cos), _ptr(rope_sin), _ptr(seg_table_i32), nseg, NH, KV, HD, S, slots,
+                rows, eps, win, kv_dtype, prep, _stream())
         if rc == 1:
             return False
-        _ok(rc, "attn_tiled")
+        _ok(rc, entry[9:])
         return True
+
+    @staticmethod
+    def attn_tiled(*args, **kw):
+        """The tiled causal attention (qtts_hip_attn_tiled): (out, q, ld_q, kc,
+        vc, qn_w, kn_w, rope_cos, rope_sin, seg_table_i32, nseg, NH, KV, HD, S,
+        slots, rows, eps, win=0, kv_dtype=0, prep=0) over seg_table [nseg, 4] =
+        {slot, first row, first position, count}; prep as attn_cached.  False
+        where the kernel does not cover the shape (nothing ran)."""
+        return Kernels._attn_tiled("qtts_hip_attn_tiled", *args, **kw)
+
+    @staticmethod
+    def attn_tiled_bf16(*args, **kw):
+        """attn_tiled on the bf16 matrix cores (qtts_hip_attn_tiled_bf16,
+        k_attn_tileh): the same arguments and results"""
+        return Kernels._attn_tiled("qtts_hip_attn_tiled_bf16", *args, **kw)
+
+    @staticmethod
+    def attn_tileh_launches():
+        """k_attn_tileh launches since the library loaded (qtts_hip_attn_tileh_launches)"""
+        return int(lib().qtts_hip_attn_tileh_launches())
 
     @staticmethod
     def attn_tile_launches():
