@@ -137,6 +137,17 @@ long long qtts_hip_pgemmh_launches(void);
  * keyed by it.  -1 on a bad value. */
 int qtts_dev_set_prefill_attention_precision(qtts_dev_t *dev, int precision);
 int qtts_dev_prefill_attention_precision(const qtts_dev_t *dev);
+/* Precision of the voice-clone encoders' contractions: 0 exact (default, or
+ * $QTTS_HIP_ENC at creation: k_econv, three bf16 planes per operand, six matrix
+ * instructions per product block), 1 bf16 (k_econvh: plane 0 of the weights and
+ * the inputs rounded to bf16 as they are staged, one instruction per block;
+ * sums and epilogues fp32).  The STFT launch, k_mel, k_rvq_enc, the small
+ * kernels, attention, norms and RoPE are exact in either.  Read per launch.
+ * -1 on a bad value.  qtts_hip_econvh_launches: k_econvh launches since the
+ * library loaded. */
+int qtts_dev_set_encoder_precision(qtts_dev_t *dev, int precision);
+int qtts_dev_encoder_precision(const qtts_dev_t *dev);
+long long qtts_hip_econvh_launches(void);
 /* Diagnostics: talker cache rows [pos0, pos0 + n) of layer `layer`, slot b,
  * to the host as fp32 [n][KV*HD] each (bf16 widened exactly; k_host or v_host
  * may be NULL).  Waits for the context stream.  -1 out of range. */
@@ -957,6 +968,11 @@ int qtts_hip_econv_plan(const qtts_econv_desc_t *d, qtts_econv_plan_t *plan_out)
  * above, before any device call; also a part smaller than the plan needs or a
  * NULL w / x / y) or a device error.  A parity entry, not a timing one. */
 int qtts_hip_econv_case(const qtts_econv_desc_t *d, qtts_econv_plan_t *plan_out, void *stream);
+/* The same launch in the bf16 encoder precision (k_econvh.hip: plane 0 of the
+ * split, round to nearest even, against x' rounded to bf16 nearest even, one
+ * matrix instruction per product block): the descriptor, the plan, the
+ * workspace and the refusals of qtts_hip_econv_case. */
+int qtts_hip_econvh_case(const qtts_econv_desc_t *d, qtts_econv_plan_t *plan_out, void *stream);
 /* One launch of one of the encoders' small kernels through the launch helper
  * the encoders use.  in / out / n / s per op (device pointers; nb utterances,
  * len = int[nb] valid columns, ldt = row length of a [b][C][ldt] buffer):

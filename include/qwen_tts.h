@@ -303,6 +303,22 @@ int qwen_tts_prefill_precision(qwen_tts_ctx_t *ctx);
 #define QWEN_TTS_PREFILL_ATTN_BF16  1
 int qwen_tts_set_prefill_attention_precision(qwen_tts_ctx_t *ctx, int precision);
 int qwen_tts_prefill_attention_precision(qwen_tts_ctx_t *ctx);
+/* Arithmetic of the voice-clone audio encoders' contractions (every call that
+ * encodes reference audio: qwen_tts_speaker_embedding, qwen_tts_encode_audio,
+ * the clone-from-audio generate calls, qwen_tts_voice_create_audio).
+ * QWEN_TTS_ENC_EXACT (the default) keeps fp32-equivalent products.
+ * QWEN_TTS_ENC_BF16 rounds the weights and the inputs of every TDNN / SE-Res2Net
+ * / ASP conv of the speaker encoder, every SEANet conv, the downsample and the
+ * encoder transformer's linears to bf16, nearest even, one matrix instruction
+ * per product where the exact kernel issues six; sums, epilogues, the STFT, the
+ * mel, attention, norms, RoPE and the quantizer stay as they are.  The reference
+ * codes and the x-vector are then no longer those of exact mode, and hence
+ * neither are the generated codes.  Read per encode.  -1 on any other value.
+ * $QTTS_HIP_ENC=bf16|exact sets the default of every ctx loaded after it. */
+#define QWEN_TTS_ENC_EXACT 0
+#define QWEN_TTS_ENC_BF16  1
+int qwen_tts_set_encoder_precision(qwen_tts_ctx_t *ctx, int precision);
+int qwen_tts_encoder_precision(qwen_tts_ctx_t *ctx);
 /* Most lock-step slots of one ctx (qwen_tts_generate_batch, the slots of
  * qwen_tts_generate_queue, qwen_tts_generate_voice_clone_batch): up to 16 run
  * on the 16-row matrix-core batch kernels, 17..64 on the wide batch kernel. */

@@ -20,6 +20,8 @@
 // residual.  Tile 64 (out channels) x 64 (time) per 256-thread workgroup,
 // 2 x 2 waves of 32 x 32, K-steps of 32 double-buffered through registers,
 // LDS rows of 64 B with an XOR swizzle (conflict-free 16-B fragment reads).
+// Under the opt-in bf16 encoder precision (EncModel::prec) every launch but the
+// STFT takes the same plan to k_econvh.hip: plane 0 alone, one MFMA per block.
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
@@ -27,11 +29,9 @@
 #include <algorithm>
 
 #include "qtts_common.h"
+#include "qtts_econv_dev.h"
 #include "qtts_enc.h"
 #include "qtts_kernels.h"
-
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
 
 #define ECK(x)                                                                        \
     do {                                                                              \
@@ -43,57 +43,8 @@ typedef short bf16x8 __attribute__((ext_vector_type(8)));
 
 namespace {
 
-enum { PAD_ZERO = 0, PAD_REFLECT = 1, PAD_REPLICATE = 2 };
-enum { ACT_NONE = 0, ACT_RELU = 1, ACT_RELU_TANH = 2, ACT_GELU = 3, ACT_SIGMOID = 4 };
-
-struct EConv {
-    const unsigned short *w = nullptr;  // [3][M][Kp] bf16 planes
-    size_t wplane = 0;                  // M * Kp
-    int M = 0, K = 0, Kp = 0, kw = 1, stride = 1, dil = 1, padl = 0, pmode = PAD_ZERO, act_in = ACT_NONE;
-    const float *x = nullptr, *x2 = nullptr;   // x'(ci, t) = x[b*xb + ci*xc + t*xt] (+ x2, same strides)
-    size_t xb = 0;
-    int xc = 0, xt = 1;
-    int lin[ENC_MAXB], lout[ENC_MAXB];
-    float *y = nullptr;                 // y[b*yb + m*yc + n*yt]
-    size_t yb = 0;
-    int yc = 0, yt = 1;
-    const float *bias = nullptr;        // [M]
-    const float *bias2 = nullptr;       // [b][bias2_b] per-utterance bias
-    int bias2_b = 0;
-    int act_out = ACT_NONE;
-    const float *vec = nullptr;         // LayerScale [M] (after the activation)
-    const float *res = nullptr;         // residual, res[b*rb + m*rc + n*rt]
-    size_t rb = 0;
-    int rc = 0, rt = 1;
-    // split-K (set by launch_econv): blockIdx.z = b * kz + split; raw partial
-    // tiles to part[split][b][M][pn], k_econv_reduce sums them in split order
-    float *part = nullptr;
-    int kz = 1, pn = 0, nb = 1;
-};
-
-__device__ __forceinline__ void econv_store(const EConv &g, int b, int m, int n, float v) {
-    const float *bias2 = g.bias2 ? g.bias2 + (size_t)b * g.bias2_b : nullptr;
-    if (g.bias) v += g.bias[m];
-    if (bias2) v += bias2[m];
-    switch (g.act_out) {
-        case 1: v = fmaxf(v, 0.f); break;
-        case 2: v = tanhf(fmaxf(v, 0.f)); break;
-        case 3: v = 0.5f * v * (1.0f + erff(v * 0.70710678118654752f)); break;
-        case 4: v = 1.0f / (1.0f + expf(-v)); break;
-        default: break;
-    }
-    if (g.vec) v *= g.vec[m];
-    if (g.res) v += g.res[(size_t)b * g.rb + (size_t)m * g.rc + (size_t)n * g.rt];
-    g.y[(size_t)b * g.yb + (size_t)m * g.yc + (size_t)n * g.yt] = v;
-}
-
 __device__ __forceinline__ int eswz(int r, int c) { return r * 32 + ((c ^ ((r >> 2) & 3)) << 3); }
 
-__device__ __forceinline__ uint32_t e_pk(float lo, float hi) {
-    typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
-    const bf2 v = {(__bf16)lo, (__bf16)hi};
-    return __builtin_bit_cast(uint32_t, v);
-}
 __device__ __forceinline__ float e_lo(uint32_t p) { return __uint_as_float(p << 16); }
 __device__ __forceinline__ float e_hi(uint32_t p) { return __uint_as_float(p & 0xFFFF0000u); }
 
@@ -559,7 +510,9 @@ int plan_econv(const EConv &g, int nb, int nmax, EConvPlan *p) {
     return 0;
 }
 
-int launch_econv(EncModel *em, const EConv &gin, int nb, int nmax, hipStream_t st) {
+// em->prec 1 (the bf16 encoder precision): the same plan on k_econvh, one bf16
+// plane per operand, unless the call site keeps its launch exact
+int launch_econv(EncModel *em, const EConv &gin, int nb, int nmax, hipStream_t st, bool keep_exact = false) {
     EConv g = gin;
     if (g.M <= 0 || nmax <= 0) return 0;
     EConvPlan pl;
@@ -581,7 +534,8 @@ int launch_econv(EncModel *em, const EConv &gin, int nb, int nmax, hipStream_t s
         }
         g.part = em->part;
     }
-    if (pl.rows) hipLaunchKernelGGL((k_econv<true>), pl.grid, dim3(256), 0, st, g);
+    if (em->prec && !keep_exact) qtts_econvh_launch(g, pl.rows, pl.grid, st);
+    else if (pl.rows) hipLaunchKernelGGL((k_econv<true>), pl.grid, dim3(256), 0, st, g);
     else hipLaunchKernelGGL((k_econv<false>), pl.grid, dim3(256), 0, st, g);
     if (kz > 1) hipLaunchKernelGGL(k_econv_reduce, pl.rgrid, dim3(256), 0, st, g);
     return hipGetLastError() == hipSuccess ? 0 : -1;
@@ -1083,14 +1037,16 @@ int enc_speaker(EncModel *m, int nb, const float *const *wav, const int *n, floa
         g.x = x; g.xb = (size_t)Cx * Tm; g.xc = Tm; g.xt = 1;
         g.y = y; g.yb = (size_t)Cy * Tm; g.yc = Tm; g.yt = 1;
     };
-    // 1. STFT: one input channel, kw = n_fft, stride = hop, reflect pad (n_fft - hop) / 2
+    // 1. STFT: one input channel, kw = n_fft, stride = hop, reflect pad (n_fft - hop) / 2.  Exact in
+    // either precision: the basis runs over raw audio and feeds a log (k_mel), which turns a
+    // bf16 product's relative error in a quiet bin into an absolute one of the whole feature
     {
         EConv g = conv_of(m->stft);
         g.stride = hop; g.padl = padr; g.pmode = PAD_REFLECT;
         g.x = dw; g.xb = nmax; g.xc = 0; g.xt = 1;
         g.y = spec; g.yb = (size_t)2 * nf * Tm; g.yc = Tm; g.yt = 1;
         for (int b = 0; b < nb; ++b) { g.lin[b] = n[b]; g.lout[b] = T[b]; }
-        ECK(launch_econv(m, g, nb, Tm, st));
+        ECK(launch_econv(m, g, nb, Tm, st, true));
     }
     launch_mel(st, spec, nf, Tm, nb, lens, m->melfb, reinterpret_cast<const int *>(F(m, "#melfb_lo")),
                reinterpret_cast<const int *>(F(m, "#melfb_lo")) + nm, nm, mel);
@@ -1381,7 +1337,8 @@ extern "C" int qtts_hip_econv_plan(const qtts_econv_desc_t *d, qtts_econv_plan_t
     return 0;
 }
 
-extern "C" int qtts_hip_econv_case(const qtts_econv_desc_t *d, qtts_econv_plan_t *plan_out, void *stream) {
+// one launch through launch_econv in the given encoder precision
+static int econv_case(const qtts_econv_desc_t *d, qtts_econv_plan_t *plan_out, void *stream, int prec) {
     EConv g;
     EConvPlan p;
     if (econv_of_desc(d, &g) || plan_econv(g, d->nb, d->nmax, &p)) return -1;
@@ -1390,6 +1347,7 @@ extern "C" int qtts_hip_econv_case(const qtts_econv_desc_t *d, qtts_econv_plan_t
         return -1;
     hipStream_t st = (hipStream_t)stream;
     EncModel em;
+    em.prec = prec;
     EncW w;
     int rc = -1;
     if (hipStreamSynchronize(st) == hipSuccess && split_planes(&em, d->w, g.M, g.K, g.kw, &w) == 0) {
@@ -1404,6 +1362,16 @@ extern "C" int qtts_hip_econv_case(const qtts_econv_desc_t *d, qtts_econv_plan_t
     if (rc == 0) plan_out_of(p, plan_out);
     return rc;
 }
+
+extern "C" int qtts_hip_econv_case(const qtts_econv_desc_t *d, qtts_econv_plan_t *plan_out, void *stream) {
+    return econv_case(d, plan_out, stream, 0);
+}
+
+extern "C" int qtts_hip_econvh_case(const qtts_econv_desc_t *d, qtts_econv_plan_t *plan_out, void *stream) {
+    return econv_case(d, plan_out, stream, 1);
+}
+
+extern "C" long long qtts_hip_econvh_launches(void) { return qtts_econvh_launches(); }
 
 extern "C" int qtts_hip_enc_op(const qtts_enc_op_t *d, void *stream) {
     if (!d || d->op < 0 || d->op >= QTTS_EO_COUNT) return -1;

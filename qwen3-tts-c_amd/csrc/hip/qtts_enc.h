@@ -34,6 +34,10 @@ struct EncModel {
     bool have_dims = false;
     hipStream_t st = nullptr;
     int device = 0;
+    // precision of the encoders' contractions: 0 exact (k_econv, three planes), 1 bf16 (k_econvh,
+    // plane 0 alone; the STFT stays on k_econv).  Read per launch (qtts_dev_set_encoder_precision,
+    // QTTS_HIP_ENC at creation).
+    int prec = 0;
     // host copies until enc_finalize builds the device layout
     std::map<std::string, std::vector<float>> host;
     std::map<std::string, std::vector<int64_t>> shape;

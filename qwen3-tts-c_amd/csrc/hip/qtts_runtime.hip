@@ -367,6 +367,12 @@ extern "C" qtts_dev_t *qtts_dev_create(const qtts_dims_t *dims, int device) {
     }
     dv->enc.st = dv->st;
     dv->enc.device = device;
+    // QTTS_HIP_ENC=bf16|exact: the voice-clone encoders' precision (default exact)
+    const char *epr = getenv("QTTS_HIP_ENC");
+    if (epr && *epr) {
+        if (!strcmp(epr, "bf16")) dv->enc.prec = 1;
+        else if (strcmp(epr, "exact")) fprintf(stderr, "qtts: QTTS_HIP_ENC=%s ignored (bf16 or exact)\n", epr);
+    }
     return dv;
 }
 
@@ -458,6 +464,14 @@ extern "C" int qtts_dev_set_prefill_attention_precision(qtts_dev_t *dv, int prec
 }
 
 extern "C" int qtts_dev_prefill_attention_precision(const qtts_dev_t *dv) { return dv ? dv->prefill_attn_prec : -1; }
+
+extern "C" int qtts_dev_set_encoder_precision(qtts_dev_t *dv, int precision) {
+    if (!dv || (precision != 0 && precision != 1)) return -1;
+    dv->enc.prec = precision;   // (read by every contraction launch of the next encode)
+    return 0;
+}
+
+extern "C" int qtts_dev_encoder_precision(const qtts_dev_t *dv) { return dv ? dv->enc.prec : -1; }
 
 extern "C" int qtts_dev_set_codec_precision(qtts_dev_t *dv, int precision) {
     if (!dv || (precision != 0 && precision != 1)) return -1;

@@ -1,4 +1,4 @@
-/* codec_precision.c - the precision switches (codec convs, codec linears, talker prefill, prefill attention) of the public API
+/* codec_precision.c - the precision switches (codec convs, codec linears, talker prefill, prefill attention, voice-clone encoders) of the public API
  * (include/qwen_tts.h).  The value lives in the device model behind ctx->hip;
  * the ctx itself holds nothing of it.  Its own file: qwen_tts.c stays the
  * orchestration that runs against any device layer with the generate ABI. */
@@ -43,4 +43,14 @@ int qwen_tts_set_prefill_attention_precision(qwen_tts_ctx_t *ctx, int precision)
 int qwen_tts_prefill_attention_precision(qwen_tts_ctx_t *ctx) {
     if (!ctx || !ctx->hip) return -1;
     return qtts_dev_prefill_attention_precision((const qtts_dev_t *)ctx->hip);
+}
+
+int qwen_tts_set_encoder_precision(qwen_tts_ctx_t *ctx, int precision) {
+    if (!ctx || !ctx->hip) return -1;
+    return qtts_dev_set_encoder_precision((qtts_dev_t *)ctx->hip, precision);
+}
+
+int qwen_tts_encoder_precision(qwen_tts_ctx_t *ctx) {
+    if (!ctx || !ctx->hip) return -1;
+    return qtts_dev_encoder_precision((const qtts_dev_t *)ctx->hip);
 }

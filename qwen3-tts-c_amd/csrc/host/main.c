@@ -73,6 +73,10 @@ static void usage(const char *prog) {
             "  --prefill-attn exact|bf16 (tiled attention of talker prefills of 256 rows and more per slot, default exact;\n"
             "                      bf16 rounds q, K, V and the probabilities to bf16 on the bf16 matrix instruction;\n"
             "                      codes then no longer bit-exact against the reference)\n"
+            "  --encoder exact|bf16 (voice-clone audio encoders: the ECAPA and SEANet convs, the downsample and the\n"
+            "                      transformer's linears, default exact; bf16 rounds weights and inputs to bf16, one matrix\n"
+            "                      instruction per product instead of six; the STFT stays exact; reference codes and\n"
+            "                      x-vector, hence the codes, are then no longer those of exact mode)\n"
             "  --force-codes <file>  continue on these codes, 16 ints per frame as --ref-codes reads them\n"
             "                      (-1: leave that draw free; later frames are free), qwen_tts_force_codes\n"
             "  --dump-drawn <file> write the id the sampler itself drew at every draw in that format\n"
@@ -262,6 +266,7 @@ int main(int argc, char **argv) {
     int codec_lin = -1;  /* --codec-linears: -1 = the library's default ($QTTS_HIP_CODEC_LIN or exact) */
     int prefill_prec = -1; /* --prefill: -1 = the library's default ($QTTS_HIP_PREFILL or exact) */
     int prefill_attn = -1; /* --prefill-attn: -1 = the library's default ($QTTS_HIP_PREFILL_ATTN or exact) */
+    int enc_prec = -1;   /* --encoder: -1 = the library's default ($QTTS_HIP_ENC or exact) */
     int kv_cache = -1;   /* --kv-cache: -1 = the library's default ($QTTS_HIP_KV or fp32) */
     const char *ref_codes_file = NULL, *ref_text = NULL, *xvec_file = NULL, *text = NULL, *ref_audio = NULL;
     int print_ids = 0, xvec_only = 0, stdin_ids = 0;
@@ -332,6 +337,12 @@ int main(int argc, char **argv) {
             if (!strcmp(v, "bf16")) prefill_attn = QWEN_TTS_PREFILL_ATTN_BF16;
             else if (!strcmp(v, "exact")) prefill_attn = QWEN_TTS_PREFILL_ATTN_EXACT;
             else { fprintf(stderr, "Error: --prefill-attn takes exact or bf16\n\n"); usage(argv[0]); return 1; }
+        }
+        else if (ARG("--encoder")) {
+            const char *v = argv[++i];
+            if (!strcmp(v, "bf16")) enc_prec = QWEN_TTS_ENC_BF16;
+            else if (!strcmp(v, "exact")) enc_prec = QWEN_TTS_ENC_EXACT;
+            else { fprintf(stderr, "Error: --encoder takes exact or bf16\n\n"); usage(argv[0]); return 1; }
         }
         else if (ARG("--ref-codes")) ref_codes_file = argv[++i];
         else if (ARG("--force-codes")) force_file = argv[++i];
@@ -491,6 +502,11 @@ int main(int argc, char **argv) {
     }
     if (prefill_attn >= 0 && qwen_tts_set_prefill_attention_precision(ctx, prefill_attn) != 0) {
         fprintf(stderr, "Error: cannot select the prefill attention precision\n");
+        qwen_tts_free(ctx); free(ref_codes); free(xvec); free(file_ids);
+        return 1;
+    }
+    if (enc_prec >= 0 && qwen_tts_set_encoder_precision(ctx, enc_prec) != 0) {
+        fprintf(stderr, "Error: cannot select the encoder precision\n");
         qwen_tts_free(ctx); free(ref_codes); free(xvec); free(file_ids);
         return 1;
     }

@@ -146,6 +146,8 @@ EXPORTS = [
     "qwen_tts_set_prefill_attention_precision", "qwen_tts_prefill_attention_precision",
     "qtts_dev_set_prefill_attention_precision", "qtts_dev_prefill_attention_precision",
     "qtts_hip_attn_tiled_bf16", "qtts_hip_attn_tileh_launches",
+    "qwen_tts_set_encoder_precision", "qwen_tts_encoder_precision", "qtts_dev_set_encoder_precision",
+    "qtts_dev_encoder_precision", "qtts_hip_econvh_launches", "qtts_hip_econvh_case",
 ]
 
 MAX_BATCH = 64   # QWEN_TTS_MAX_BATCH / QTTS_HIP_MAX_BATCH: lock-step slots per context
@@ -325,6 +327,7 @@ KV_F32, KV_BF16 = 0, 1   # QWEN_TTS_KV_F32 / QWEN_TTS_KV_BF16
 CODEC_EXACT, CODEC_BF16 = 0, 1   # QWEN_TTS_CODEC_EXACT / QWEN_TTS_CODEC_BF16
 PREFILL_EXACT, PREFILL_BF16 = 0, 1   # QWEN_TTS_PREFILL_EXACT / QWEN_TTS_PREFILL_BF16
 PREFILL_ATTN_EXACT, PREFILL_ATTN_BF16 = 0, 1   # QWEN_TTS_PREFILL_ATTN_EXACT / QWEN_TTS_PREFILL_ATTN_BF16
+ENC_EXACT, ENC_BF16 = 0, 1   # QWEN_TTS_ENC_EXACT / QWEN_TTS_ENC_BF16
 
 _LIB = None
 
@@ -595,6 +598,19 @@ def lib():
         L.qtts_dev_prefill_attention_precision.argtypes = [C.c_void_p]
         L.qtts_hip_attn_tileh_launches.restype = C.c_longlong
         L.qtts_hip_attn_tileh_launches.argtypes = []
+    if hasattr(L, "qwen_tts_set_encoder_precision"):   # (nor an encoder precision)
+        L.qwen_tts_set_encoder_precision.restype = C.c_int
+        L.qwen_tts_set_encoder_precision.argtypes = [C.POINTER(Ctx), C.c_int]
+        L.qwen_tts_encoder_precision.restype = C.c_int
+        L.qwen_tts_encoder_precision.argtypes = [C.POINTER(Ctx)]
+        L.qtts_dev_set_encoder_precision.restype = C.c_int
+        L.qtts_dev_set_encoder_precision.argtypes = [C.c_void_p, C.c_int]
+        L.qtts_dev_encoder_precision.restype = C.c_int
+        L.qtts_dev_encoder_precision.argtypes = [C.c_void_p]
+        L.qtts_hip_econvh_launches.restype = C.c_longlong
+        L.qtts_hip_econvh_launches.argtypes = []
+        L.qtts_hip_econvh_case.restype = C.c_int
+        L.qtts_hip_econvh_case.argtypes = [C.POINTER(EConvDesc), C.POINTER(EConvPlan), C.c_void_p]
     L.qtts_dev_set_kv_dtype.restype = C.c_int
     L.qtts_dev_set_kv_dtype.argtypes = [C.c_void_p, C.c_int]
     L.qtts_dev_kv_dtype.restype = C.c_int
@@ -822,6 +838,19 @@ class QwenTTS:
 
     def prefill_attention_precision(self):
         return lib().qwen_tts_prefill_attention_precision(self.ctx)
+
+    def set_encoder_precision(self, precision):
+        """Arithmetic of the voice-clone audio encoders' contractions, from the
+        next encode on: "exact" / ENC_EXACT (default) or "bf16" / ENC_BF16
+        (weights and inputs rounded to bf16 on k_econvh; the STFT stays exact;
+        reference codes and x-vector are then no longer those of exact mode;
+        qwen_tts_set_encoder_precision)."""
+        v = {"exact": ENC_EXACT, "bf16": ENC_BF16}.get(precision, precision)
+        if not isinstance(v, int) or lib().qwen_tts_set_encoder_precision(self.ctx, v) != 0:
+            raise ValueError(f"encoder precision {precision!r} (exact or bf16)")
+
+    def encoder_precision(self):
+        return lib().qwen_tts_encoder_precision(self.ctx)
 
     def state_bytes(self):
         """device bytes of the generation state (qtts_dev_bytes(dev, 1))"""
@@ -1870,6 +1899,19 @@ class Kernels:
         the plan that ran, or None on a refusal or a device error."""
         p = EConvPlan()
         return Kernels._econv_result(lib().qtts_hip_econv_case(C.byref(desc), C.byref(p), _stream()), p, "econv_case")
+
+    @staticmethod
+    def econvh_case(desc):
+        """econv_case in the bf16 encoder precision (qtts_hip_econvh_case,
+        k_econvh): the same descriptor, plan and refusals."""
+        p = EConvPlan()
+        rc = lib().qtts_hip_econvh_case(C.byref(desc), C.byref(p), _stream())
+        return Kernels._econv_result(rc, p, "econvh_case")
+
+    @staticmethod
+    def econvh_launches():
+        """k_econvh launches since the library loaded (qtts_hip_econvh_launches)"""
+        return int(lib().qtts_hip_econvh_launches())
 
     @staticmethod
     def enc_op(op, inp=(), out=(), n=(), s=(), eps=0.0):
